@@ -23,7 +23,17 @@ value = seconds of TRACK produced per wall second: the N*batch segments of a ste
 overlapping segments of one stretch of a track (stride 257985 samples = 5.85 s of new audio per 7.8 s
 segment, src/model_apply.cpp:162), which the root overlap-adds into n_track = N*batch*257985 - 22050
 samples; value = n_track/44100 * K / T, T = max over ranks of the barrier-bracketed wall time of the K timed
-steps.
+steps; ms_per_step = T / K.
+
+A plain run sets up, warms up, times the K steps, writes the outputs if asked (--dump-outputs) and prints the line.
+Everything else below (the other GEMM modes, the single-segment latency, the host-buffer and strong-scaled track legs,
+the roofline, the CPU baseline, and the self-check of --backend gloo) runs only with --full; the --no-* switches
+leave out single legs of a --full run.
+
+--dump-outputs DIR writes, after the timed steps, what the root's last timed step produced: the overlap-added stems
+(sources, 2, n_track), as a fixed sample of at most 2**21 values (indices drawn with numpy seed 0, sorted) -
+DIR/stems_sample.npy (float32, the values) and DIR/stems_sample_index.npy (float64, their flat C-order indices), 24 MB
+at most. The inputs are seeded, so two builds run with the same arguments can be compared value for value.
 
 --model selects the workload (each has its own metric name; the driver's default is 4s = the BASELINE metric):
   4s  htdemucs 4-source (configs[1] / configs[2])
@@ -35,11 +45,11 @@ steps.
   v3  Demucs v3 hdemucs_mmi
 --gemm f32|bf16x3|fp16x3 selects the GEMM arithmetic of the measured context (include/demucs_hip.h DMX_GEMM_*; default: the
 library default = bf16x3, the exact operand-split path, unless the environment says otherwise through DMX_GEMM); at N = 1
-the OTHER modes are measured on the same workload in the same process and reported as config.f32_mfma_xRT /
+and with --full the OTHER modes are measured on the same workload in the same process and reported as config.f32_mfma_xRT /
 _ms_per_segment (config.bf16x3_xRT / ... when the run itself is the fp32 MFMA path) and config.fp16x3_xRT / ... - the
 opt-in mode whose linear layers use fp16 terms under a per-row scale (bounded, not exact: never `value` unless asked for).
 
-config also reports, as SCALAR keys, measured in this same run:
+config also reports, as SCALAR keys, measured in this same run with --full (null otherwise):
   track_4min_host_xRT / track_4min_host_wall_s   (N = 1) the same track end to end with HOST buffers in and out
                       (dmx_track_infer; for the bag dmx_engine_track_infer = the call the drop-in demucs_ft CLI makes):
                       PCIe inclusive, 240 s / best wall of 3; never `value` (the boundary rule of the contract);
@@ -49,7 +59,7 @@ config also reports, as SCALAR keys, measured in this same run:
   single_segment_latency_ms  BASELINE configs[1] read literally (one segment per call, device resident);
   single_segment_launches    kernel launches of that call (one plan run at batch 1).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a --full run:
   roofline     : dominant kernel (by device time) measured live with HIP events on the stream
                  it runs on (dmx_debug_profile), algorithmic FLOPs / duration vs the MFMA peak of the arithmetic that
                  kernel runs (fp32 MFMA 157.3 TFLOP/s; exact bf16 split kernels: bf16 dense peak 2516.6 / 5 partial
@@ -146,6 +156,11 @@ def main():
     ap.add_argument("--model", default="4s", choices=["4s", "6s", "ft", "v3"],
                     help="4s: htdemucs (the BASELINE metric); 6s: the 6-source model of configs[3]; ft: the fine-tuned bag of configs[4]; v3: hdemucs_mmi")
     ap.add_argument("--gemm", default=None, choices=["f32", "bf16x3", "fp16x3"], help="GEMM arithmetic of the measured context (default: library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks (other GEMM modes, single-segment latency, track legs, "
+                         "roofline, CPU baseline, the gloo self-check); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the last step's stems to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-single", action="store_true")
@@ -340,7 +355,15 @@ def main():
 
     elapsed = timed_run()
     out = outs[(args.steps - 1) & 1] if args.steps > 0 else outs[0]
-    if test_mode and world > 1:
+    if args.dump_outputs and rank == 0:
+        # the stems of the last timed step, before any --full leg reuses track_out
+        total = track_out.numel()
+        idx = np.sort(np.random.default_rng(0).choice(total, min(total, 1 << 21), replace=False))
+        vals = track_out.reshape(-1)[torch.from_numpy(idx).cuda()].cpu().numpy().astype(np.float32)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "stems_sample.npy"), vals)
+        np.save(os.path.join(args.dump_outputs, "stems_sample_index.npy"), idx.astype(np.float64))
+    if test_mode and world > 1 and args.full:
         # the root checks that the track it overlap-added from the gathered slabs equals the overlap-add of the slabs
         # recomputed locally (ranks use different seeds)
         torch.cuda.synchronize()
@@ -383,7 +406,7 @@ def main():
 
     # ---- the other GEMM mode on the same workload, same process, same buffers (N = 1)
     other_runs = {}
-    if world == 1 and not (args.no_other_gemm or args.no_split_probe) and not test_mode:
+    if args.full and world == 1 and not (args.no_other_gemm or args.no_split_probe) and not test_mode:
         for other in others:
             ctx2 = dmx.Context(models[0], SEG, B, gemm=gemm_names[other])
             ctx2.set_stream(stream.cuda_stream)
@@ -400,7 +423,7 @@ def main():
     # BASELINE.json configs[1] read literally: ONE segment per call (latency), device resident
     single_ms = None
     single_launches = None
-    if rank == 0 and world == 1 and not args.no_single:
+    if args.full and rank == 0 and world == 1 and not args.no_single:
         torch.cuda.synchronize()
         ctx.set_stream(None)  # the context's own stream: repeated identical calls replay a captured HIP graph
         o1 = out[0]
@@ -420,7 +443,7 @@ def main():
     # (segments dealt in contiguous ranges, RCCL gather, root overlap-add)
     track_4min = None
     track_strong = None
-    if not args.no_track:
+    if args.full and not args.no_track:
         n4 = 240 * 44100
         g4 = torch.Generator(device="cpu").manual_seed(1)
         audio_il = (0.1 * torch.randn((n4, 2), generator=g4))  # the same track on every rank
@@ -505,7 +528,7 @@ def main():
         ctx.set_stream(stream.cuda_stream)
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         prof = ctx.profile(B, 3)
         by_kernel = {}
         for nm, k, ms, fl, by in prof:
@@ -544,7 +567,7 @@ def main():
         }
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle_lib as orc  # test infrastructure, timed here only as the reported CPU baseline
 
         om = orc.OracleModel(mpaths[0])
@@ -630,7 +653,8 @@ def main():
                        "single_segment_latency_ms": None if single_ms is None else round(single_ms, 3),
                        "single_segment_launches": single_launches,
                        "single_segment_xRT": None if single_ms is None else round(SEG_SECONDS / (single_ms * 1e-3), 1),
-                       "parallelism": f"segment-sharded x{world}"},
+                       "parallelism": f"segment-sharded x{world}",
+                       "full": args.full},
         }
         seg_flops = MODEL_FLOPS.get("4s" if ft else args.model)
         if single_ms is not None and seg_flops:

@@ -19,6 +19,13 @@ def test_bench_refuses_without_gpu():
     assert "needs a GPU" in (r.stdout + r.stderr)
 
 
+def test_bench_offers_full_and_dump_outputs():
+    """The secondary measurements are behind --full; --dump-outputs DIR writes the last timed step's outputs."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def _check_line(d, kernel_stats_csv, rnd=3, items=42, track_s=240.0):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):

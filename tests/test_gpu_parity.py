@@ -323,7 +323,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu(model, port):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--batch", "2", "--model", model, "--backend", "gloo", "--no-cpu-baseline", "--no-roofline", "--no-single"]
+                        "--batch", "2", "--model", model, "--backend", "gloo", "--full", "--no-cpu-baseline", "--no-roofline", "--no-single"]
                        + ([] if model == "ft" else ["--no-track"]),
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -481,6 +481,36 @@ def test_bench_self_launches_its_ranks_from_a_bare_shell():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["config"]["outputs_finite"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain `bench.py` run times the headline steps alone (the secondary legs belong to --full), and --dump-outputs writes
+    a fixed seeded sample of the last timed step's stems: two runs with the same arguments write the same values."""
+    import json
+    import subprocess
+    import sys
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        cfg = line["config"]
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and cfg["outputs_finite"]
+        assert abs(line["value"] - cfg["track_samples_per_step"] / 44100.0 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-2
+        assert cfg["full"] is False and "roofline" not in line and "cpu_baseline" not in line
+        assert all(v is None for key, v in cfg.items() if key.endswith("_xRT") or key.startswith("single_segment_"))
+        vals, idx = np.load(d / "stems_sample.npy"), np.load(d / "stems_sample_index.npy")
+        assert sorted(os.listdir(d)) == ["stems_sample.npy", "stems_sample_index.npy"]
+        assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape
+        n = 4 * 2 * cfg["track_samples_per_step"]  # (sources, channels, samples) of the 4-source model's stems
+        assert len(vals) == min(n, 1 << 21) < n and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+        assert vals.nbytes + idx.nbytes <= 64 << 20 and np.isfinite(vals).all() and np.abs(vals).max() > 0
+        dumps.append((vals, idx))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
 
 
 def test_stream_schedule_does_not_change_a_bit(dmx, tmp_models, monkeypatch):

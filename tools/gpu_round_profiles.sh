@@ -14,14 +14,14 @@ if has tests; then
   ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep smoke ) >> $O/gpu_tests.txt
 fi
 if has bench || has headline; then
-  ( timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | grep '^{' ) > $O/bench_4s_b42.json
+  ( timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | grep '^{' ) > $O/bench_4s_b42.json
 fi
 if has bench; then
-  ( timeout 600 python bench.py --model 6s 2>&1 | grep '^{' ) > $O/bench_6s_b42.json
-  ( timeout 600 python bench.py --model ft --steps 3 --warmup 1 2>&1 | grep '^{' ) > $O/bench_ft_b42.json
-  ( timeout 600 python bench.py --model v3 2>&1 | grep '^{' ) > $O/bench_v3_b42.json
+  ( timeout 600 python bench.py --full --model 6s 2>&1 | grep '^{' ) > $O/bench_6s_b42.json
+  ( timeout 600 python bench.py --full --model ft --steps 3 --warmup 1 2>&1 | grep '^{' ) > $O/bench_ft_b42.json
+  ( timeout 600 python bench.py --full --model v3 2>&1 | grep '^{' ) > $O/bench_v3_b42.json
   rm -f $O/bench_4s_b1_b4_b12_b24.jsonl
-  for b in 1 4 12 24; do ( timeout 600 python bench.py --batch $b --steps 10 --warmup 3 --no-cpu-baseline --no-track 2>&1 | grep '^{' ) >> $O/bench_4s_b1_b4_b12_b24.jsonl; done
+  for b in 1 4 12 24; do ( timeout 600 python bench.py --full --batch $b --steps 10 --warmup 3 --no-cpu-baseline --no-track 2>&1 | grep '^{' ) >> $O/bench_4s_b1_b4_b12_b24.jsonl; done
 fi
 if has ops; then
   MODEL=4s PBS="1 42" bash tools/gpu_prof.sh > $O/ops_4s.log 2>&1; cp gpurun_out/profile_ops_4s_b42.tsv $O/ops_4s_b42.tsv; cp gpurun_out/profile_ops_4s_b1.tsv $O/ops_4s_b1.tsv
@@ -51,7 +51,7 @@ if has pmc; then
   cp gpurun_out/pmc/traffic.json $O/traffic_bf16x3.json
 fi
 if has fp16; then
-  ( timeout 900 python bench.py --gemm fp16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-track 2>&1 | grep '^{' ) > $O/bench_4s_b42_fp16x3.json
+  ( timeout 900 python bench.py --full --gemm fp16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-track 2>&1 | grep '^{' ) > $O/bench_4s_b42_fp16x3.json
   DMX_GEMM=fp16x3 MODEL=4s PBS="42" bash tools/gpu_prof.sh > $O/ops_4s_fp16x3.log 2>&1; cp gpurun_out/profile_ops_4s_b42.tsv $O/ops_4s_b42_fp16x3.tsv
   ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/profh -o traceh -- python $R/bench.py --gemm fp16x3 --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-single --no-track --no-other-gemm 2>&1 | tail -2 ) >> $O/ops_4s_fp16x3.log
   python tools/pmc_summary.py $(find /tmp/profh -name "*.db" | head -1) --class > $O/kernel_stats_b42_fp16x3_by_class.csv
