@@ -33,6 +33,7 @@ EXPORTS = [
     "dmx_resample_length", "dmx_resample_filter", "dmx_resample_device", "dmx_resample",
     "dmx_ctx_create_gemm", "dmx_ctx_gemm", "dmx_default_gemm", "dmx_set_default_gemm", "dmx_debug_split_weights", "dmx_debug_split_activations", "dmx_debug_split_activations_fp16",
     "dmx_model_arch", "dmx_engine_arch", "dmx_engine_transport", "dmx_engine_set_finish", "dmx_engine_finish", "dmx_engine_root_ctx", "dmx_engine_track_infer", "dmx_engine_partition",
+    "dmx_tracks_infer",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -90,6 +91,7 @@ def lib():
         L.dmx_segment_infer.argtypes = [vp, fp, fp, ci]
         L.dmx_segment_infer_device.argtypes = [vp, fp, fp, ci]
         L.dmx_track_infer.argtypes = [vp, fp, i64, ci, fp, ci, vp, vp]
+        L.dmx_tracks_infer.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
         L.dmx_track_gather_device.argtypes = [vp, fp, i64, fp, ci, vp, ci, fp]
@@ -243,6 +245,36 @@ class Context:
         cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
         cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
         _chk(lib().dmx_track_infer(self.h, audio.ctypes.data, n, shift_offset, out.ctypes.data, LAYOUT_PLANAR, cbp, None))
+        return out
+
+    def tracks(self, audios, shift_offsets=None, progress=None, out=None, layout: int = LAYOUT_PLANAR) -> List[np.ndarray]:
+        """Several (2, n_t) planar tracks -> list of (S, 2, n_t) in ONE call (dmx_tracks_infer: their segments share batches);
+        each result is bit-identical to track() of that track. shift_offsets: None or one per track (-1: rand() % 22050,
+        drawn in track order). `out`: a list of result buffers to reuse. layout=LAYOUT_EIGEN passes the tracks and receives
+        the results through the C ABI as Eigen column-major images; the arrays seen by the caller are the same."""
+        T = len(audios)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        if out is None:
+            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
+        assert len(out) == T
+        for o, n in zip(out, ns):
+            assert o.shape == (self.S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
+        if layout == LAYOUT_EIGEN:
+            src = [np.ascontiguousarray(a.T) for a in audios]  # [n][2] == column-major 2 x n
+            dst = [np.zeros((n, 2, self.S), np.float32) for n in ns]  # flat index s + S*(c + 2*i)
+        else:
+            src, dst = audios, out
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        so = (ctypes.c_int * max(T, 1))(*shift_offsets) if shift_offsets is not None else None
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        _chk(lib().dmx_tracks_infer(self.h, T, ap, na, so, op, layout, cbp, None))
+        if layout == LAYOUT_EIGEN:
+            for o, img in zip(out, dst):
+                o[...] = img.transpose(2, 1, 0)
         return out
 
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:

@@ -641,7 +641,7 @@ static int ctx_init(dmx_ctx *c, const dmx_model *m, int64_t segment_samples, int
         const char *f = getenv("DMX_FUSE_ISTFT");
         c->fuseIstft = f ? atoi(f) : 1;
     }
-    HIPCHK(hipMalloc((void **)&c->dPartials, sizeof(double) * 2 * dmx_ctx::kStatBlocks));
+    HIPCHK(hipMalloc((void **)&c->dPartials, sizeof(double) * 2 * dmx_ctx::kStatBlocks * TrackStatsTable::kMax));
     HIPCHK(hipMalloc((void **)&c->dStats, sizeof(float) * 4));
     if (gemm == DMX_GEMM_FP16X3)
     {
@@ -701,7 +701,7 @@ dmx_ctx::~dmx_ctx()
         for (auto &kv : graphs)
             (void)hipGraphExecDestroy(kv.second);
     }
-    for (hipStream_t s : {ownStream, stream2, copyStream})
+    for (hipStream_t s : {ownStream, stream2, copyStream, uploadStream})
         if (s)
         {
             (void)hipStreamSynchronize(s);
@@ -717,6 +717,16 @@ dmx_ctx::~dmx_ctx()
         (void)hipEventDestroy(evFork);
     if (evJoin)
         (void)hipEventDestroy(evJoin);
+    if (evUpload)
+        (void)hipEventDestroy(evUpload);
+    for (TrackSlot &sl : slots)
+    {
+        if (sl.copied)
+            (void)hipEventDestroy(sl.copied);
+        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats})
+            if (b->p)
+                (void)hipFree(b->p);
+    }
     for (void *p : {(void *)dA, (void *)dPartials, (void *)dStats, (void *)dStatus, (void *)dRowScale[0], (void *)dRowScale[1], (void *)bAudio.p, (void *)bTmp.p, (void *)bMix.p,
                     (void *)bSegOut.p, (void *)bOut.p})
         if (p)
@@ -1296,14 +1306,244 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
                                         2 * c->m->pm.n_sources);
 }
 
-// demucs_inference on one device. All device buffers belong to the context (grown on first use, then
-// reused: no allocation on the per-track path); every batch is enqueued without waiting for the one
-// before; progress is reported from per-batch events, i.e. the stream is never synchronised before the
-// end; and the track is FINISHED IN PIECES: as soon as the batch ending with segment g is enqueued, the
-// output samples below g*stride + (first sample of segment g+1) can no longer change, so their
-// overlap-add is launched right behind that batch and their device-to-host copy runs on a second stream
-// underneath the kernels of the following batch (the 339 MB result of a 4-minute track otherwise costs
-// as much wall time after the last kernel as a dozen segments).
+// demucs_inference on one device, for one track or several. All device buffers belong to the context (grown on first use,
+// then reused: no allocation on the per-batch path); every batch is enqueued without waiting for the one before; progress
+// is reported from per-batch events, i.e. the stream is never synchronised before the end; and each track is FINISHED IN
+// PIECES: as soon as the batch ending with segment g of a track is enqueued, the track's output samples below
+// g*stride + (first sample of segment g+1) can no longer change, so their overlap-add is launched right behind that batch
+// and their device-to-host copy runs on a second stream underneath the kernels of the following batch (the 339 MB result
+// of a 4-minute track otherwise costs as much wall time after the last kernel as a dozen segments).
+//
+// Several tracks: their segments are laid end to end in track order (global segment index) and dealt in batches of
+// max_batch, so a batch may hold the tail of one track and the head of the next. Every kernel serves each of its tracks
+// exactly as it serves a track of its own (misc.hip), so every result is the bits of a call per track.
+//   * Segment outputs live in a ring of R = min(2 max_batch, total segments) blocks: global segment G is block G mod R.
+//     Batch k writes blocks [k B mod R, + nb) (contiguous: B divides R, or nothing wraps), and the overlap-add behind batch
+//     k reads segments >= k B - 1 only - the previous batch's last one at most - which batch k+1 does not overwrite; all
+//     of it is ordered on the context's stream.
+//   * A track holds a slot (upload, statistics, result) from the batch of its first segment until its last copy-out has
+//     completed. Batch k needs the slots of the tracks with first batch <= k and last batch >= k-1 (the copy-out of batch
+//     k-1 is issued after batch k has been enqueued); the call sizes that many slots for its longest track up front.
+//     A slot whose track finished in batch k-2 or earlier is taken over after a host wait on that track's copy-out event
+//     (its batch is long done).
+//   * A track is uploaded (and its statistics computed) when the first batch that needs it is enqueued.
+namespace
+{
+struct TrackJob
+{
+    const float *audio;
+    float *out;
+    i64 n, len, g0, done;
+    int shift, nseg, kFirst, kLast, slot;
+};
+struct TrackPiece
+{
+    int t;
+    i64 lo, hi;
+};
+} // namespace
+
+static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, const int *shifts,
+                      float *const *out, int layout, dmx_progress_fn progress, void *user)
+{
+    HIPCHK(hipSetDevice(c->m->device));
+    const int S = c->m->pm.n_sources, B = c->maxBatch;
+    const i64 seg = c->seg, blk = (i64)S * 2 * seg;
+    std::vector<TrackJob> jobs((size_t)T);
+    i64 stride = 0, N = 0, nmax = 0;
+    for (int t = 0; t < T; ++t)
+    {
+        TrackJob &j = jobs[(size_t)t];
+        j.audio = audio[t], j.out = out[t], j.n = n[t], j.shift = shifts[t], j.done = 0, j.slot = -1;
+        DMXCHK(dmx_track_geometry(c, j.n, j.shift, &j.len, &j.nseg, &stride));
+        j.g0 = N;
+        N += j.nseg;
+        j.kFirst = (int)(j.g0 / B), j.kLast = (int)((N - 1) / B);
+        nmax = std::max(nmax, j.n);
+    }
+    const int nBatches = (int)((N + B - 1) / B);
+    const i64 R = std::min<i64>(2 * (i64)B, N);
+    // slots: track t is held during batches [kFirst, kLast + 1]
+    int nSlots = 0;
+    {
+        std::vector<int> diff((size_t)nBatches + 2, 0);
+        for (const TrackJob &j : jobs)
+            ++diff[(size_t)j.kFirst], --diff[(size_t)j.kLast + 2];
+        int live = 0;
+        for (int k = 0; k <= nBatches; ++k)
+            nSlots = std::max(nSlots, live += diff[(size_t)k]);
+    }
+    DMXCHK(dmx_ensure_buf(c->bMix, 2 * seg * B));
+    DMXCHK(dmx_ensure_buf(c->bSegOut, R * blk));
+    if ((int)c->slots.size() < nSlots)
+        c->slots.resize((size_t)nSlots);
+    for (int i = 0; i < nSlots; ++i)
+    {
+        dmx_ctx::TrackSlot &sl = c->slots[(size_t)i];
+        DMXCHK(dmx_ensure_buf(sl.audio, 2 * nmax));
+        if (layout == DMX_LAYOUT_PLANAR)
+            DMXCHK(dmx_ensure_buf(sl.tmp, 2 * nmax));
+        DMXCHK(dmx_ensure_buf(sl.out, (i64)S * 2 * nmax));
+        DMXCHK(dmx_ensure_buf(sl.stats, 4));
+        if (!sl.copied)
+            HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
+        sl.holder = -1;
+    }
+    if (!c->uploadStream)
+        HIPCHK(hipStreamCreateWithFlags(&c->uploadStream, hipStreamNonBlocking));
+    if (!c->evUpload)
+        HIPCHK(hipEventCreateWithFlags(&c->evUpload, hipEventDisableTiming));
+    float *dMix = c->bMix.p, *ring = c->bSegOut.p;
+    const int eigen = layout == DMX_LAYOUT_EIGEN ? 1 : 0;
+
+    if (progress)
+        progress(0.0f, "1., apply model w/ shift", user);
+    // pieces[k & 1]: the output samples [lo, hi) of the tracks of batch k that are final once batch k is done. Their copy
+    // is issued AFTER batch k+1 has been enqueued: a device-to-host copy into pageable memory blocks the calling thread
+    // until the data has left the GPU, and the GPU must have its next batch queued by then.
+    std::vector<TrackPiece> pieces[2];
+    auto copy_piece = [&](int k) -> int {
+        HIPCHK(hipStreamWaitEvent(c->copyStream, c->batchEvents[(size_t)k], 0));
+        for (const TrackPiece &pc : pieces[k & 1])
+        {
+            const TrackJob &j = jobs[(size_t)pc.t];
+            const float *dOut = c->slots[(size_t)j.slot].out.p;
+            const i64 i0 = pc.lo, i1 = pc.hi;
+            if (i1 > i0)
+            {
+                if (eigen)
+                    HIPCHK(hipMemcpyAsync(j.out + (size_t)i0 * 2 * S, dOut + (size_t)i0 * 2 * S, sizeof(float) * (size_t)(i1 - i0) * 2 * S,
+                                          hipMemcpyDeviceToHost, c->copyStream));
+                else
+                    for (int pl = 0; pl < 2 * S; ++pl)
+                        HIPCHK(hipMemcpyAsync(j.out + (size_t)pl * j.n + i0, dOut + (size_t)pl * j.n + i0, sizeof(float) * (size_t)(i1 - i0),
+                                              hipMemcpyDeviceToHost, c->copyStream));
+            }
+            if (j.kLast == k)
+                HIPCHK(hipEventRecord(c->slots[(size_t)j.slot].copied, c->copyStream));
+        }
+        if (progress)
+        {
+            const i64 g0 = (i64)k * B, nb = std::min<i64>(B, N - g0);
+            HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
+            char msg[128];
+            snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %lld..%lld of %lld", (long long)g0, (long long)(g0 + nb - 1),
+                     (long long)N);
+            progress((float)(g0 + nb) / (float)N, msg, user);
+        }
+        return DMX_OK;
+    };
+
+    std::vector<TrackSegItem> items((size_t)B);
+    std::vector<TrackOlaEntry> ola;
+    int tLo = 0; // first track of the current batch
+    for (int k = 0; k < nBatches; ++k)
+    {
+        const i64 g0 = (i64)k * B, nb = std::min<i64>(B, N - g0);
+        while (jobs[(size_t)tLo].kLast < k)
+            ++tLo;
+        int tHi = tLo; // one past the last track of the batch
+        while (tHi < T && jobs[(size_t)tHi].kFirst <= k)
+            ++tHi;
+        // upload the tracks that start in this batch
+        TrackStatsTable st{};
+        int nSt = 0;
+        for (int t = tLo; t < tHi; ++t)
+        {
+            TrackJob &j = jobs[(size_t)t];
+            if (j.kFirst != k || j.slot >= 0)
+                continue;
+            // a free slot, else the one whose track finished first (in batch k-2 or earlier: its copy-out has been issued)
+            int pick = -1;
+            for (int i = 0; i < nSlots; ++i)
+            {
+                const int h = c->slots[(size_t)i].holder;
+                if (h < 0)
+                {
+                    pick = i;
+                    break;
+                }
+                if (jobs[(size_t)h].kLast <= k - 2 && (pick < 0 || jobs[(size_t)h].kLast < jobs[(size_t)c->slots[(size_t)pick].holder].kLast))
+                    pick = i;
+            }
+            if (pick < 0)
+                return fail(DMX_ERR_ARG, "%s: internal error (no free track slot in batch %d)", fn, k);
+            dmx_ctx::TrackSlot &sl = c->slots[(size_t)pick];
+            if (sl.holder >= 0) // the previous holder's copy-out (and every kernel that read the slot) is done
+                HIPCHK(hipEventSynchronize(sl.copied));
+            sl.holder = t, j.slot = pick;
+            if (eigen)
+                HIPCHK(hipMemcpyAsync(sl.audio.p, j.audio, sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
+            else
+            {
+                HIPCHK(hipMemcpyAsync(sl.tmp.p, j.audio, sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
+                launch_planar_to_interleaved(sl.tmp.p, sl.audio.p, j.n, c->uploadStream);
+            }
+            st.audio[nSt] = sl.audio.p, st.n[nSt] = j.n, st.stats[nSt] = sl.stats.p;
+            if (++nSt == TrackStatsTable::kMax || t == tHi - 1)
+            {
+                HIPCHK(hipEventRecord(c->evUpload, c->uploadStream));
+                HIPCHK(hipStreamWaitEvent(c->stream, c->evUpload, 0));
+                launch_track_stats(st, nSt, c->dPartials, dmx_ctx::kStatBlocks, c->stream);
+                launch_track_stats_final(st, nSt, c->dPartials, dmx_ctx::kStatBlocks, c->stream);
+                nSt = 0;
+            }
+        }
+        // gather the batch: global segments [g0, g0 + nb)
+        {
+            int t = tLo;
+            for (i64 g = g0; g < g0 + nb; ++g)
+            {
+                while (jobs[(size_t)t].g0 + jobs[(size_t)t].nseg <= g)
+                    ++t;
+                const TrackJob &j = jobs[(size_t)t];
+                items[(size_t)(g - g0)] = TrackSegItem{c->slots[(size_t)j.slot].audio.p, c->slots[(size_t)j.slot].stats.p, j.n, j.shift,
+                                                       (int)(g - j.g0)};
+            }
+        }
+        launch_track_gather(items.data(), (int)nb, seg, stride, dMix, c->stream);
+        HIPCHK(hipGetLastError());
+        DMXCHK(dmx_segment_infer_device(c, dMix, ring + (g0 % R) * blk, (int)nb));
+        // finish what this batch makes final
+        std::vector<TrackPiece> &pcs = pieces[k & 1];
+        pcs.clear();
+        ola.clear();
+        for (int t = tLo; t < tHi; ++t)
+        {
+            TrackJob &j = jobs[(size_t)t];
+            const i64 off = DMX_MAX_SHIFT - j.shift;
+            // shifted-track positions below (segments done)*stride are covered only by segments done
+            i64 fin = j.kLast == k ? j.n : (g0 + nb - j.g0) * stride - off;
+            fin = std::max<i64>(j.done, std::min<i64>(fin, j.n));
+            pcs.push_back(TrackPiece{t, j.done, fin});
+            if (fin > j.done)
+            {
+                const i64 j0 = j.done + off; // first shifted position of the piece and the first segment covering it
+                const i64 gLo = j0 - seg + 1 <= 0 ? 0 : (j0 - seg + stride) / stride;
+                ola.push_back(TrackOlaEntry{ring, c->slots[(size_t)j.slot].stats.p, c->slots[(size_t)j.slot].out.p, j.n, j.len, j.done, fin,
+                                            gLo, (j.g0 + gLo) % R, j.nseg, j.shift});
+            }
+            j.done = fin;
+        }
+        launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, R, eigen, 0, 2 * S, c->stream);
+        HIPCHK(hipGetLastError());
+        hipEvent_t ev = dmx_batch_event(c, (size_t)k);
+        if (!ev)
+            return fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+        HIPCHK(hipEventRecord(ev, c->stream));
+        if (k > 0)
+            DMXCHK(copy_piece(k - 1));
+    }
+    DMXCHK(copy_piece(nBatches - 1));
+    const int rcSync = dmx_ctx_sync_checked(c);
+    HIPCHK(hipStreamSynchronize(c->copyStream));
+    for (int i = 0; i < nSlots; ++i)
+        c->slots[(size_t)i].holder = -1;
+    if (rcSync != DMX_OK)
+        return rcSync;
+    return DMX_OK;
+}
+
 extern "C" int dmx_track_infer(dmx_ctx *c, const float *audio, int64_t n, int shift_offset, float *out, int layout,
                                dmx_progress_fn progress, void *user)
 {
@@ -1315,89 +1555,35 @@ extern "C" int dmx_track_infer(dmx_ctx *c, const float *audio, int64_t n, int sh
         shift_offset = rand() % DMX_MAX_SHIFT; // model_apply.cpp:114
     if (shift_offset >= DMX_MAX_SHIFT)
         return fail(DMX_ERR_ARG, "dmx_track_infer: shift_offset must be < %d", DMX_MAX_SHIFT);
-    HIPCHK(hipSetDevice(c->m->device));
-    const int S = c->m->pm.n_sources;
-    const i64 seg = c->seg;
-    i64 len, stride;
-    int nseg;
-    DMXCHK(dmx_track_geometry(c, n, shift_offset, &len, &nseg, &stride));
-    DMXCHK(dmx_ensure_buf(c->bAudio, 2 * n));
-    DMXCHK(dmx_ensure_buf(c->bMix, 2 * seg * c->maxBatch));
-    DMXCHK(dmx_ensure_buf(c->bSegOut, (i64)nseg * S * 2 * seg));
-    DMXCHK(dmx_ensure_buf(c->bOut, (i64)S * 2 * n));
-    float *dAudio = c->bAudio.p, *dMix = c->bMix.p, *dSegOut = c->bSegOut.p, *dOut = c->bOut.p;
-    if (layout == DMX_LAYOUT_EIGEN)
-        HIPCHK(hipMemcpyAsync(dAudio, audio, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    else
+    return tracks_run(c, "dmx_track_infer", 1, &audio, &n, &shift_offset, &out, layout, progress, user);
+}
+
+extern "C" int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, const int *shift_offsets,
+                                float *const *out, int layout, dmx_progress_fn progress, void *user)
+{
+    if (!c)
+        return fail(DMX_ERR_ARG, "dmx_tracks_infer: null context");
+    if (n_tracks < 1)
+        return fail(DMX_ERR_ARG, "dmx_tracks_infer: n_tracks must be >= 1, got %d", n_tracks);
+    if (!audio || !n || !out)
+        return fail(DMX_ERR_ARG, "dmx_tracks_infer: null %s array", !audio ? "audio" : !n ? "n" : "out");
+    if (layout != DMX_LAYOUT_EIGEN && layout != DMX_LAYOUT_PLANAR)
+        return fail(DMX_ERR_ARG, "dmx_tracks_infer: unknown layout %d", layout);
+    for (int t = 0; t < n_tracks; ++t)
     {
-        DMXCHK(dmx_ensure_buf(c->bTmp, 2 * n));
-        HIPCHK(hipMemcpyAsync(c->bTmp.p, audio, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        launch_planar_to_interleaved(c->bTmp.p, dAudio, n, c->stream);
+        if (!audio[t])
+            return fail(DMX_ERR_ARG, "dmx_tracks_infer: track %d: null audio pointer", t);
+        if (!out[t])
+            return fail(DMX_ERR_ARG, "dmx_tracks_infer: track %d: null out pointer", t);
+        if (n[t] < 2)
+            return fail(DMX_ERR_ARG, "dmx_tracks_infer: track %d: n = %lld, must be >= 2", t, (long long)n[t]);
+        if (shift_offsets && (shift_offsets[t] < -1 || shift_offsets[t] >= DMX_MAX_SHIFT))
+            return fail(DMX_ERR_ARG, "dmx_tracks_infer: track %d: shift_offset %d not in [-1, %d)", t, shift_offsets[t], DMX_MAX_SHIFT);
     }
-    if (progress)
-        progress(0.0f, "1., apply model w/ shift", user);
-    DMXCHK(dmx_track_stats_device(c, dAudio, n, c->dStats));
-    const int nBatches = (nseg + c->maxBatch - 1) / c->maxBatch;
-    std::vector<int> idx;
-    // the piecewise finish needs the planar layout (a piece is a contiguous run per plane); the Eigen image
-    // interleaves stems and channels per sample, so a piece is contiguous there too: [i0*2S, i1*2S)
-    // Piece k = output samples [lo[k], hi[k]) that are final once batch k is done. Its copy is issued
-    // AFTER batch k+1 has been enqueued: a device-to-host copy into pageable memory blocks the calling
-    // thread until the data has left the GPU, and the GPU must have its next batch queued by then.
-    std::vector<i64> lo((size_t)nBatches), hi((size_t)nBatches);
-    auto copy_piece = [&](int k) -> int {
-        const i64 i0 = lo[(size_t)k], i1 = hi[(size_t)k];
-        if (i1 > i0)
-        {
-            HIPCHK(hipStreamWaitEvent(c->copyStream, c->batchEvents[(size_t)k], 0));
-            if (layout == DMX_LAYOUT_EIGEN)
-                HIPCHK(hipMemcpyAsync(out + (size_t)i0 * 2 * S, dOut + (size_t)i0 * 2 * S, sizeof(float) * (size_t)(i1 - i0) * 2 * S,
-                                      hipMemcpyDeviceToHost, c->copyStream));
-            else
-                for (int pl = 0; pl < 2 * S; ++pl)
-                    HIPCHK(hipMemcpyAsync(out + (size_t)pl * n + i0, dOut + (size_t)pl * n + i0, sizeof(float) * (size_t)(i1 - i0),
-                                          hipMemcpyDeviceToHost, c->copyStream));
-        }
-        if (progress)
-        {
-            const int g0 = k * c->maxBatch, nb = std::min(c->maxBatch, nseg - g0);
-            HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
-            char msg[128];
-            snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %d..%d of %d", g0, g0 + nb - 1, nseg);
-            progress((float)(g0 + nb) / (float)nseg, msg, user);
-        }
-        return DMX_OK;
-    };
-    i64 done = 0; // output samples [0, done) are final
-    for (int k = 0; k < nBatches; ++k)
-    {
-        const int g0 = k * c->maxBatch, nb = std::min(c->maxBatch, nseg - g0);
-        idx.resize((size_t)nb);
-        for (int i = 0; i < nb; ++i)
-            idx[(size_t)i] = g0 + i;
-        DMXCHK(dmx_track_gather_device(c, dAudio, n, c->dStats, shift_offset, idx.data(), nb, dMix));
-        DMXCHK(dmx_segment_infer_device(c, dMix, dSegOut + (size_t)g0 * S * 2 * seg, nb));
-        // shifted-track positions below (g0+nb)*stride are covered only by segments < g0+nb
-        i64 fin = k == nBatches - 1 ? n : (i64)(g0 + nb) * stride - (DMX_MAX_SHIFT - shift_offset);
-        fin = std::max<i64>(done, std::min<i64>(fin, n));
-        lo[(size_t)k] = done, hi[(size_t)k] = fin;
-        launch_track_ola(dSegOut, nseg, S, seg, stride, len, n, shift_offset, c->dStats, dOut, layout == DMX_LAYOUT_EIGEN ? 1 : 0, 0,
-                         2 * S, done, fin, c->stream);
-        HIPCHK(hipGetLastError());
-        done = fin;
-        hipEvent_t ev = dmx_batch_event(c, (size_t)k);
-        if (!ev)
-            return fail(DMX_ERR_HIP, "dmx_track_infer: hipEventCreate failed");
-        HIPCHK(hipEventRecord(ev, c->stream));
-        if (k > 0)
-            DMXCHK(copy_piece(k - 1));
-    }
-    DMXCHK(copy_piece(nBatches - 1));
-    const int rcSync = dmx_ctx_sync_checked(c);
-    HIPCHK(hipStreamSynchronize(c->copyStream));
-    if (rcSync != DMX_OK)
-        return rcSync;
-    return DMX_OK;
+    std::vector<int> shifts((size_t)n_tracks);
+    for (int t = 0; t < n_tracks; ++t) // drawn in track order, like successive dmx_track_infer calls (model_apply.cpp:114)
+        shifts[(size_t)t] = !shift_offsets || shift_offsets[t] < 0 ? rand() % DMX_MAX_SHIFT : shift_offsets[t];
+    return tracks_run(c, "dmx_tracks_infer", n_tracks, audio, n, shifts.data(), out, layout, progress, user);
 }
 
 // --------------------------------------------------------------------------- debug

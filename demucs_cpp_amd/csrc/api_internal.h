@@ -85,7 +85,18 @@ struct dmx_ctx
     // track-level scratch
     double *dPartials = nullptr;
     static const int kStatBlocks = 256;
-    DevBuf bAudio, bTmp, bMix, bSegOut, bOut;
+    DevBuf bAudio, bTmp, bMix, bSegOut, bOut; // bSegOut: the ring of segment outputs of dmx_track(s)_infer
+    // dmx_track(s)_infer: one slot per track in flight (its upload, statistics and result), reused once the track's last
+    // copy-out has completed; uploads run on their own stream so that a pageable source never waits for queued kernels
+    struct TrackSlot
+    {
+        DevBuf audio, tmp, out, stats;
+        hipEvent_t copied = nullptr; // on copyStream behind the last copy-out of the track that holds the slot
+        int holder = -1;             // track index within the running call, -1: free
+    };
+    std::vector<TrackSlot> slots;
+    hipStream_t uploadStream = nullptr;
+    hipEvent_t evUpload = nullptr;
     float *dStats = nullptr;            // 4 floats
     float *dRowScale[2] = {nullptr, nullptr}; // GEMM_FP16X3: per-row scales of the linear layer in flight, one buffer per stream of the plan
     unsigned *dStatus = nullptr;        // device status word: raised by a kernel whose bounded spin timed out (v3.hip LSTM)

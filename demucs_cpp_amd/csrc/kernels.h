@@ -240,25 +240,65 @@ struct LocalAttnArgs
 int launch_local_attn(const LocalAttnArgs &a, hipStream_t s); // -1: unsupported shape
 
 // ---- track level (model_apply.cpp:60-288) ----
-// partial (sum, sumsq) of the mono reference (mean over channels); audio interleaved [n][2]
+// Every track-level kernel serves several tracks per launch (dmx_tracks_infer); one track is the T = 1 case. The per-track
+// tables travel by value in the kernel arguments (no device table, no host synchronisation between launches); each stays
+// well inside HIP's 4 KB kernel-argument limit.
+struct TrackStatsTable
+{
+    static const int kMax = 32;
+    const float *audio[kMax]; // interleaved [n][2]
+    i64 n[kMax];
+    float *stats[kMax];       // 2 floats: mean, std
+};
+// partial (sum, sumsq) of the mono reference (mean over channels) of tracks 0..T-1: grid (nblk, T), track t's block b covers
+// samples [b*per, (b+1)*per), per = ceil(n_t / nblk); partials [T][nblk][2]
+void launch_track_stats(const TrackStatsTable &t, int T, double *partials, int nblk, hipStream_t s);
+// stats_t[0]=mean, stats_t[1]=std (unbiased) from partials, blocks summed in order
+void launch_track_stats_final(const TrackStatsTable &t, int T, const double *partials, int nblk, hipStream_t s);
+// one track (dmx_track_stats_device)
 void launch_track_stats(const float *audio, i64 n, double *partials, int nblk, hipStream_t s);
-// stats[0]=mean, stats[1]=std (unbiased) from partials
 void launch_track_stats_final(const double *partials, int nblk, i64 n, float *stats, hipStream_t s);
-// chunk extraction: mixes[i] = segment `segIdx[i]` of the normalised, shifted, zero-padded track,
-// centred in a zero segment (segment_inference, model_apply.cpp:250-288). segIdx is a HOST array
-// (passed to the kernel by value, kMax per launch).
+// chunk extraction: mixes[i] = segment `seg` of the normalised, shifted, zero-padded track of item i, centred in a zero
+// segment (segment_inference, model_apply.cpp:250-288). The items of one launch may come from different tracks.
+struct TrackSegItem
+{
+    const float *audio; // interleaved [n][2]
+    const float *stats;
+    i64 n;
+    int shift;
+    int seg; // segment index within the track
+};
 struct TrackSegIdx
 {
-    static const int kMax = 64;
-    int v[kMax];
+    static const int kMax = 64; // = the largest max_batch (dmx_ctx_create)
+    TrackSegItem v[kMax];
 };
+void launch_track_gather(const TrackSegItem *items, int nIdx, i64 seg, i64 stride, float *mixes, hipStream_t s);
+// one track: segIdx is a HOST array
 void launch_track_gather(const float *audio, i64 n, const float *stats, int shiftOffset, i64 seg, i64 stride,
                          i64 len, const int *segIdx, int nIdx, float *mixes, hipStream_t s);
-// overlap-add of nSeg segment outputs [nSeg][S][2][seg] (segment ids 0..nSeg-1) into planes
-// [planeBase, planeBase + nPlanes) (plane = stem*2 + channel) and samples [i0, i1) of out.
+// overlap-add of segment outputs [.][S][2][seg] into planes [planeBase, planeBase + nPlanes) (plane = stem*2 + channel) and
+// samples [i0, i1) of out, per track of the table (grid z).
 // layout 0: planar [S][2][n]; layout 1: Eigen column-major image (s + S*(c + 2*i))
-// gBase: segOut[0] is segment gBase (a device that holds only a stretch of the segments; every segment the
-// samples [i0, i1) touch must be in the buffer)
+// Segment g of a track is block blk = slot0 + (g - gBase) of segOut, less `ring` when blk >= ring (a ring of segment
+// blocks shared by several tracks); every segment the samples [i0, i1) touch must be there.
+struct TrackOlaEntry
+{
+    const float *segOut;
+    const float *stats;
+    float *out;
+    i64 n, len, i0, i1; // len: shifted length (dmx_track_geometry)
+    i64 gBase, slot0;
+    int nSeg, shift;
+};
+struct TrackOlaTable
+{
+    static const int kMax = 32;
+    TrackOlaEntry e[kMax];
+};
+void launch_track_ola(const TrackOlaEntry *entries, int T, int S, i64 seg, i64 stride, i64 ring, int layout, int planeBase,
+                      int nPlanes, hipStream_t s);
+// one track; gBase: segOut[0] is segment gBase (a device that holds only a stretch of the segments)
 void launch_track_ola(const float *segOut, int nSeg, int S, i64 seg, i64 stride, i64 len, i64 n, int shiftOffset,
                       const float *stats, float *out, int layout, int planeBase, int nPlanes, i64 i0, i64 i1, hipStream_t s,
                       int gBase = 0);

@@ -238,11 +238,14 @@ void launch_gn_apply(const GnArgs &a, hipStream_t s)
 }
 
 // --------------------------------------------------------------------------- track level
-// ref = mean over channels; mean / unbiased std of ref (model_apply.cpp:72-82)
-__global__ __launch_bounds__(256) void track_stats_kernel(const float *audio, i64 n, double *partials)
+// ref = mean over channels; mean / unbiased std of ref (model_apply.cpp:72-82). Track blockIdx.y; every track gets the same
+// block decomposition and summation order whatever else shares the launch.
+__global__ __launch_bounds__(256) void track_stats_kernel(TrackStatsTable t, double *partials)
 {
     __shared__ double red[4][2];
-    const float2 *a = reinterpret_cast<const float2 *>(audio);
+    const int tr = blockIdx.y;
+    const float2 *a = reinterpret_cast<const float2 *>(t.audio[tr]);
+    const i64 n = t.n[tr];
     double s = 0.0, q = 0.0;
     const i64 per = (n + gridDim.x - 1) / gridDim.x;
     const i64 lo = (i64)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
@@ -267,51 +270,73 @@ __global__ __launch_bounds__(256) void track_stats_kernel(const float *audio, i6
     __syncthreads();
     if (threadIdx.x == 0)
     {
-        partials[blockIdx.x * 2] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        partials[blockIdx.x * 2 + 1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+        double *p = partials + (i64)tr * gridDim.x * 2;
+        p[blockIdx.x * 2] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+        p[blockIdx.x * 2 + 1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
     }
 }
-__global__ void track_stats_final_kernel(const double *partials, int nblk, i64 n, float *stats)
+// one block per track
+__global__ void track_stats_final_kernel(TrackStatsTable t, const double *partials, int nblk)
 {
-    if (threadIdx.x == 0 && blockIdx.x == 0)
+    if (threadIdx.x == 0)
     {
+        const int tr = blockIdx.x;
+        const double *p = partials + (i64)tr * nblk * 2;
+        const i64 n = t.n[tr];
         double s = 0.0, q = 0.0;
         for (int i = 0; i < nblk; ++i)
         {
-            s += partials[2 * i];
-            q += partials[2 * i + 1];
+            s += p[2 * i];
+            q += p[2 * i + 1];
         }
         const double mean = s / (double)n;
         double var = (q - (double)n * mean * mean) / (double)(n - 1);
         if (var < 0.0)
             var = 0.0;
-        stats[0] = (float)mean;
-        stats[1] = (float)sqrt(var);
+        t.stats[tr][0] = (float)mean;
+        t.stats[tr][1] = (float)sqrt(var);
     }
+}
+void launch_track_stats(const TrackStatsTable &t, int T, double *partials, int nblk, hipStream_t s)
+{
+    if (T > 0)
+        hipLaunchKernelGGL(track_stats_kernel, dim3(nblk, T), dim3(256), 0, s, t, partials);
+}
+void launch_track_stats_final(const TrackStatsTable &t, int T, const double *partials, int nblk, hipStream_t s)
+{
+    if (T > 0)
+        hipLaunchKernelGGL(track_stats_final_kernel, dim3(T), dim3(64), 0, s, t, partials, nblk);
 }
 void launch_track_stats(const float *audio, i64 n, double *partials, int nblk, hipStream_t s)
 {
-    hipLaunchKernelGGL(track_stats_kernel, dim3(nblk), dim3(256), 0, s, audio, n, partials);
+    TrackStatsTable t{};
+    t.audio[0] = audio, t.n[0] = n;
+    launch_track_stats(t, 1, partials, nblk, s);
 }
 void launch_track_stats_final(const double *partials, int nblk, i64 n, float *stats, hipStream_t s)
 {
-    hipLaunchKernelGGL(track_stats_final_kernel, dim3(1), dim3(64), 0, s, partials, nblk, n, stats);
+    TrackStatsTable t{};
+    t.n[0] = n, t.stats[0] = stats;
+    launch_track_stats_final(t, 1, partials, nblk, s);
 }
 
 // shift + zero pad + normalise + chunk + centre (model_apply.cpp:21-43,93-138,189-194,250-262).
-// The segment indices travel by value in the kernel arguments: no device index buffer, no host
+// The (track, segment) items travel by value in the kernel arguments: no device index buffer, no host
 // synchronisation between consecutive gathers.
-__global__ __launch_bounds__(256) void track_gather_kernel(const float *audio, i64 n, const float *stats, int shiftOffset,
-                                                           i64 seg, i64 stride, i64 len, TrackSegIdx segIdx, float *mixes)
+__global__ __launch_bounds__(256) void track_gather_kernel(TrackSegIdx items, i64 seg, i64 stride, float *mixes)
 {
     const int which = blockIdx.y;
-    const i64 off = (i64)segIdx.v[which] * stride;
+    const TrackSegItem &it = items.v[which];
+    const i64 maxShift = 22050;
+    const i64 n = it.n;
+    const int shiftOffset = it.shift;
+    const i64 len = n + maxShift - shiftOffset; // dmx_track_geometry
+    const i64 off = (i64)it.seg * stride;
     const i64 chunk = seg < len - off ? seg : len - off;
     const i64 left = (seg - chunk) / 2; // floor(total_padding / 2)
-    const float mean = stats[0], stdv = stats[1];
-    const float2 *a = reinterpret_cast<const float2 *>(audio);
+    const float mean = it.stats[0], stdv = it.stats[1];
+    const float2 *a = reinterpret_cast<const float2 *>(it.audio);
     float2 *dst = reinterpret_cast<float2 *>(mixes) + (i64)which * seg;
-    const i64 maxShift = 22050;
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < seg; i += (i64)gridDim.x * 256)
     {
         float2 v = make_float2(0.f, 0.f);
@@ -328,8 +353,7 @@ __global__ __launch_bounds__(256) void track_gather_kernel(const float *audio, i
         dst[i] = v;
     }
 }
-void launch_track_gather(const float *audio, i64 n, const float *stats, int shiftOffset, i64 seg, i64 stride, i64 len,
-                         const int *segIdx, int nIdx, float *mixes, hipStream_t s)
+void launch_track_gather(const TrackSegItem *items, int nIdx, i64 seg, i64 stride, float *mixes, hipStream_t s)
 {
     int gx = (int)((seg + 255) / 256);
     if (gx > 512)
@@ -339,30 +363,46 @@ void launch_track_gather(const float *audio, i64 n, const float *stats, int shif
         TrackSegIdx t{};
         const int nb = nIdx - i0 < TrackSegIdx::kMax ? nIdx - i0 : TrackSegIdx::kMax;
         for (int i = 0; i < nb; ++i)
-            t.v[i] = segIdx[i0 + i];
-        hipLaunchKernelGGL(track_gather_kernel, dim3(gx, nb), dim3(256), 0, s, audio, n, stats, shiftOffset, seg, stride, len, t,
-                           mixes + (i64)i0 * seg * 2);
+            t.v[i] = items[i0 + i];
+        hipLaunchKernelGGL(track_gather_kernel, dim3(gx, nb), dim3(256), 0, s, t, seg, stride, mixes + (i64)i0 * seg * 2);
+    }
+}
+void launch_track_gather(const float *audio, i64 n, const float *stats, int shiftOffset, i64 seg, i64 stride, i64 len,
+                         const int *segIdx, int nIdx, float *mixes, hipStream_t s)
+{
+    (void)len; // n + DMX_MAX_SHIFT - shiftOffset: the kernel derives it
+    for (int i0 = 0; i0 < nIdx; i0 += TrackSegIdx::kMax)
+    {
+        TrackSegItem it[TrackSegIdx::kMax];
+        const int nb = nIdx - i0 < TrackSegIdx::kMax ? nIdx - i0 : TrackSegIdx::kMax;
+        for (int i = 0; i < nb; ++i)
+            it[i] = TrackSegItem{audio, stats, n, shiftOffset, segIdx[i0 + i]};
+        launch_track_gather(it, nb, seg, stride, mixes + (i64)i0 * seg * 2, s);
     }
 }
 
 // weighted overlap-add in segment order, /sum_weight, trim, de-normalise
 // (model_apply.cpp:171-179,207-246,129-135,88). Each output sample is covered by at most
 // ceil(seg/stride) = 2 segments; they are accumulated in increasing segment index like the
-// reference loop, so the result does not depend on how segments were sharded over GPUs.
-// planes [planeBase, planeBase + gridDim.y) (plane = s*2 + ch) and samples [i0, i1) of the output are
+// reference loop, so the result does not depend on how segments were sharded over GPUs or batched with other tracks.
+// planes [planeBase, planeBase + gridDim.y) (plane = s*2 + ch) and samples [i0, i1) of the output of track blockIdx.z are
 // produced: the bag takes stem m from model m, and a track can be finished (and copied out) in pieces
 // as soon as the segments covering a piece are done.
-__global__ __launch_bounds__(256) void track_ola_kernel(const float *segOut, int nSeg, int S, i64 seg, i64 stride, i64 len,
-                                                        i64 n, int shiftOffset, const float *stats, float *out, int layout,
-                                                        int planeBase, i64 i0, i64 i1, int gBase)
+__global__ __launch_bounds__(256) void track_ola_kernel(TrackOlaTable t, int S, i64 seg, i64 stride, i64 ring, int layout,
+                                                        int planeBase)
 {
+    const TrackOlaEntry &e = t.e[blockIdx.z];
     const int plane = blockIdx.y + planeBase;
-    const float mean = stats[0], stdv = stats[1];
+    const float mean = e.stats[0], stdv = e.stats[1];
     const i64 maxShift = 22050;
     const float half = (float)(seg / 2);
-    for (i64 i = i0 + (i64)blockIdx.x * 256 + threadIdx.x; i < i1; i += (i64)gridDim.x * 256)
+    const i64 n = e.n, len = e.len;
+    const int nSeg = e.nSeg;
+    const float *segOut = e.segOut;
+    float *out = e.out;
+    for (i64 i = e.i0 + (i64)blockIdx.x * 256 + threadIdx.x; i < e.i1; i += (i64)gridDim.x * 256)
     {
-        const i64 j = i + maxShift - shiftOffset; // position in the shifted track
+        const i64 j = i + maxShift - e.shift; // position in the shifted track
         float acc = 0.f, sw = 0.f;
         i64 first = (j - seg + stride) / stride; // smallest g with g*stride + seg > j
         if (j - seg + 1 <= 0)
@@ -378,7 +418,10 @@ __global__ __launch_bounds__(256) void track_ola_kernel(const float *segOut, int
             // triangle weight, indexed from 0 even for short chunks (Q8)
             const i64 kk = k < seg / 2 ? k + 1 : seg - k;
             const float w = (float)kk / half;
-            acc += w * segOut[((i64)(g - gBase) * S * 2 + plane) * seg + left + k]; // segOut[0] holds segment gBase
+            i64 blk = e.slot0 + (g - e.gBase);
+            if (blk >= ring)
+                blk -= ring;
+            acc += w * segOut[(blk * S * 2 + plane) * seg + left + k];
             sw += w;
         }
         const float v = (acc / sw) * stdv + mean;
@@ -391,16 +434,37 @@ __global__ __launch_bounds__(256) void track_ola_kernel(const float *segOut, int
         }
     }
 }
+void launch_track_ola(const TrackOlaEntry *entries, int T, int S, i64 seg, i64 stride, i64 ring, int layout, int planeBase,
+                      int nPlanes, hipStream_t s)
+{
+    if (nPlanes <= 0)
+        return;
+    for (int t0 = 0; t0 < T; t0 += TrackOlaTable::kMax)
+    {
+        TrackOlaTable t{};
+        int nt = 0;
+        i64 span = 0;
+        for (int k = t0; k < T && k < t0 + TrackOlaTable::kMax; ++k)
+        {
+            t.e[nt++] = entries[k];
+            if (entries[k].i1 - entries[k].i0 > span)
+                span = entries[k].i1 - entries[k].i0;
+        }
+        if (span <= 0)
+            continue;
+        int gx = (int)((span + 255) / 256);
+        if (gx > 4096)
+            gx = 4096;
+        hipLaunchKernelGGL(track_ola_kernel, dim3(gx, nPlanes, nt), dim3(256), 0, s, t, S, seg, stride, ring, layout, planeBase);
+    }
+}
 void launch_track_ola(const float *segOut, int nSeg, int S, i64 seg, i64 stride, i64 len, i64 n, int shiftOffset,
                       const float *stats, float *out, int layout, int planeBase, int nPlanes, i64 i0, i64 i1, hipStream_t s, int gBase)
 {
-    if (i1 <= i0 || nPlanes <= 0)
+    if (i1 <= i0)
         return;
-    int gx = (int)((i1 - i0 + 255) / 256);
-    if (gx > 4096)
-        gx = 4096;
-    hipLaunchKernelGGL(track_ola_kernel, dim3(gx, nPlanes), dim3(256), 0, s, segOut, nSeg, S, seg, stride, len, n, shiftOffset,
-                       stats, out, layout, planeBase, i0, i1, gBase);
+    TrackOlaEntry e{segOut, stats, out, n, len, i0, i1, gBase, 0, nSeg, shiftOffset};
+    launch_track_ola(&e, 1, S, seg, stride, INT64_MAX, layout, planeBase, nPlanes, s);
 }
 
 // rows x width floats between two pitched images (packing / unpacking the segment tails the OWNER finish mode exchanges)

@@ -10,6 +10,8 @@
 //   bool  load_demucs_v3_model(const std::string&, demucs_v3_model*)                     :1396-1397
 //   <4,2,N> demucs_v3_inference(const demucs_v3_model&, <2,N>, ProgressCallback)          :1405-1408
 //   void  model_v3_inference(const demucs_v3_model&, demucs_v3_segment_buffers&, stft_buffers&, ...) :1410-1414
+// plus, with no reference counterpart (the reference's CLIs take one file), demucs_inference_batch /
+// demucs_v3_inference_batch: many tracks in one call, their segments sharing batches (dmx_tracks_infer).
 //
 // Eigen is not required: the two tensor types below have exactly the memory image of
 // the reference's column-major Eigen::MatrixXf(2,N) and Eigen::Tensor3dXf(S,2,N), so a
@@ -202,6 +204,41 @@ inline StemTensor demucs_inference(const demucs_model &model, const StereoMatrix
     return out;
 }
 
+namespace detail
+{
+// many tracks through dmx_tracks_infer on the model's first device (the root context of its engine); each result is
+// bit-identical to demucs_inference of that track alone. model.shift_offset applies to every track (-1: rand() % 22050
+// drawn per track, in order).
+inline std::vector<StemTensor> batch_call(const char *who, const engine_model &model, int S, const std::vector<StereoMatrix> &tracks,
+                                          const ProgressCallback &cb)
+{
+    const size_t T = tracks.size();
+    std::vector<StemTensor> out;
+    out.reserve(T);
+    if (T == 0)
+        return out;
+    std::vector<const float *> in(T);
+    std::vector<float *> dst(T);
+    std::vector<int64_t> n(T);
+    std::vector<int> shifts(T, model.shift_offset);
+    for (size_t t = 0; t < T; ++t)
+    {
+        out.emplace_back(S, tracks[t].cols());
+        in[t] = tracks[t].data.data(), dst[t] = out[t].data.data(), n[t] = tracks[t].cols();
+    }
+    CbThunk th{&cb};
+    std::lock_guard<std::mutex> guard(model.lock);
+    dmx_ctx *c = dmx_engine_root_ctx(model.engine, 0);
+    if (!c || dmx_tracks_infer(c, (int)T, in.data(), n.data(), shifts.data(), dst.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
+        die(who);
+    return out;
+}
+} // namespace detail
+inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb)
+{
+    return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb);
+}
+
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
 // reference runs four demucs_inference calls back to back; calling demucs_inference on four demucs_model
 // objects still works here, but one bag engine deals all (model, segment) items over the devices at once
@@ -383,6 +420,12 @@ inline StemTensor demucs_v3_inference(const demucs_v3_model &model, const Stereo
                                DMX_LAYOUT_EIGEN, demucscpp::detail::progress_thunk, &th) != DMX_OK)
         demucscpp::detail::die("demucs_v3_inference");
     return out;
+}
+
+inline std::vector<StemTensor> demucs_v3_inference_batch(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
+                                                         ProgressCallback cb)
+{
+    return demucscpp::detail::batch_call("demucs_v3_inference_batch", model, 4, tracks, cb);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

@@ -137,6 +137,23 @@ extern "C"
     int dmx_track_infer(dmx_ctx *c, const float *audio, int64_t n, int shift_offset, float *out, int layout,
                         dmx_progress_fn progress, void *user);
 
+    /* Several tracks in one call (no reference counterpart: replaces a loop of demucs_inference calls, one per input file).
+     * Track t: audio[t] 2 x n[t], out[t] S x 2 x n[t], both `layout`; shift_offsets NULL or -1 entries: rand() % 22050
+     * drawn in track order, like successive dmx_track_infer calls. Every out[t] is bit-identical to
+     * dmx_track_infer(c, audio[t], n[t], shift_offsets[t], out[t], layout, ...) on a context of the same max_batch.
+     * The tracks' segments are laid end to end in track order and dealt in batches of max_batch (a batch may mix tracks);
+     * every batch is enqueued without waiting on the one before, and each track - or each finished piece of a long one -
+     * is overlap-added and copied out underneath later batches. A track is uploaded when its first batch is enqueued.
+     * Device memory beyond the context's arena is bounded by max_batch and the longest track, whatever the number of tracks:
+     *   2 max_batch segment outputs (S x 2 x segment_samples floats each) + 2 max_batch segment inputs, and at most
+     *   2 max_batch track slots of (S x 2 + 4) x n_max floats (n_max = the longest track; 2 x n_max of it only for
+     *   the planar layout), held from the batch of a track's first segment until its last copy-out has completed.
+     * Arguments are checked before any GPU work (n_tracks >= 1, no null pointer, n[t] >= 2, shift in [-1, 22050)); the
+     * error message names the track. Progress is the fraction of all segments done (non-decreasing, last value 1).
+     * Copies into pageable memory block the calling thread, as in dmx_track_infer. dmx_track_infer is the n_tracks = 1 case. */
+    int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, const int *shift_offsets,
+                         float *const *out, int layout, dmx_progress_fn progress, void *user);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
