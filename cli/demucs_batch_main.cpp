@@ -1,11 +1,19 @@
 // demucs_batch.cpp.main — many tracks in one call (no reference counterpart: the reference's CLIs take one file):
-//   demucs_batch.cpp.main <model file> <out dir> <wav file>...
+//   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] <model file> <out dir> <wav file>...
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
 // byte-identical to what demucs.cpp.main / demucs_v3.cpp.main writes for that input alone. The model's architecture
 // (HTDemucs v4 4s / 6s, or Demucs v3) is read from the file; the segments of all tracks share batches
 // (dmx_tracks_infer through demucscpp::demucs_inference_batch / demucscpp_v3::demucs_v3_inference_batch).
 // Environment: DMX_DEVICE (GPU index), DMX_SHIFT_OFFSET (fixed shift instead of rand(), drawn per track in order),
 // DMX_BATCH (segments in flight), DMX_RESAMPLE (wav.hpp).
+// Options (demucs's --shifts / --overlap; dmx_tracks_infer_opts through the demucscpp::inference_options overloads):
+//   --shifts N               run each track as N shifted copies and average them (1 <= N <= 32; default 1)
+//   --overlap F              segment overlap, 0 <= F <= 0.9 (default 0.25)
+//   --shift-offsets a,b,...  the N copies' shift offsets in [0, 22050), applied to every track
+// With N > 1, DMX_SHIFT_OFFSET is ambiguous without --shift-offsets and is refused. Without options the call and its output
+// are those of the plain batch call.
+#include <cerrno>
+#include <cmath>
 #include <filesystem>
 #include <iomanip>
 
@@ -13,13 +21,84 @@
 
 using namespace demucscpp;
 
+[[noreturn]] static void usage(const char *argv0)
+{
+    std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] <model file> <out dir> <wav file>..."
+              << std::endl;
+    exit(1);
+}
+
+static bool parse_int(const std::string &s, long lo, long hi, int &v)
+{
+    if (s.empty())
+        return false;
+    char *end = nullptr;
+    errno = 0;
+    const long x = std::strtol(s.c_str(), &end, 10);
+    if (errno || *end || x < lo || x > hi)
+        return false;
+    v = (int)x;
+    return true;
+}
+
 int main(int argc, const char **argv)
 {
-    if (argc < 4)
+    inference_options opts;
+    bool with_opts = false;
+    int a = 1;
+    for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
-        std::cerr << "Usage: " << argv[0] << " <model file> <out dir> <wav file>..." << std::endl;
+        const std::string opt = argv[a];
+        if (a + 1 >= argc)
+            usage(argv[0]);
+        const std::string val = argv[a + 1];
+        with_opts = true;
+        if (opt == "--shifts")
+        {
+            if (!parse_int(val, 1, DMX_MAX_SHIFTS, opts.shifts))
+                usage(argv[0]);
+        }
+        else if (opt == "--overlap")
+        {
+            char *end = nullptr;
+            errno = 0;
+            opts.overlap = std::strtof(val.c_str(), &end);
+            if (val.empty() || errno || *end || !std::isfinite(opts.overlap) || opts.overlap < 0.0f || opts.overlap > DMX_MAX_OVERLAP)
+                usage(argv[0]);
+        }
+        else if (opt == "--shift-offsets")
+        {
+            // every comma separates two values: an empty value (leading, doubled or trailing comma) is an error
+            opts.shift_offsets.clear();
+            for (size_t pos = 0;;)
+            {
+                const size_t comma = val.find(',', pos);
+                int v = 0;
+                if (!parse_int(val.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos), 0, DMX_MAX_SHIFT - 1, v))
+                    usage(argv[0]);
+                opts.shift_offsets.push_back(v);
+                if (comma == std::string::npos)
+                    break;
+                pos = comma + 1;
+            }
+        }
+        else
+            usage(argv[0]);
+    }
+    if (argc - a < 3)
+        usage(argv[0]);
+    if (!opts.shift_offsets.empty() && (int)opts.shift_offsets.size() != opts.shifts)
+    {
+        std::cerr << "--shift-offsets: " << opts.shift_offsets.size() << " values for --shifts " << opts.shifts << std::endl;
+        usage(argv[0]);
+    }
+    if (opts.shifts > 1 && opts.shift_offsets.empty() && std::getenv("DMX_SHIFT_OFFSET"))
+    {
+        std::cerr << "DMX_SHIFT_OFFSET with --shifts " << opts.shifts << " is ambiguous: give the copies' offsets with --shift-offsets"
+                  << std::endl;
         exit(1);
     }
+    argv += a - 1, argc -= a - 1; // the positional arguments as without options
     std::cout << "demucs_batch.cpp Main driver program (MI355X HIP path)" << std::endl;
     const std::string model_file = argv[1], out_dir = argv[2];
     const int n_files = argc - 3;
@@ -56,7 +135,8 @@ int main(int argc, const char **argv)
             exit(1);
         }
         std::cout << "Starting Demucs v3 MMI inference of " << n_files << " tracks" << std::endl;
-        outs = demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb);
+        outs = with_opts ? demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb, opts)
+                         : demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb);
     }
     else
     {
@@ -68,7 +148,7 @@ int main(int argc, const char **argv)
         }
         nb_sources = model.is_4sources ? 4 : 6;
         std::cout << "Starting Demucs (" << nb_sources << "-source) inference of " << n_files << " tracks" << std::endl;
-        outs = demucs_inference_batch(model, tracks, cb);
+        outs = with_opts ? demucs_inference_batch(model, tracks, cb, opts) : demucs_inference_batch(model, tracks, cb);
     }
     static const char *names[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
     for (int f = 0; f < n_files; ++f)

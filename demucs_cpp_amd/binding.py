@@ -33,7 +33,7 @@ EXPORTS = [
     "dmx_resample_length", "dmx_resample_filter", "dmx_resample_device", "dmx_resample",
     "dmx_ctx_create_gemm", "dmx_ctx_gemm", "dmx_default_gemm", "dmx_set_default_gemm", "dmx_debug_split_weights", "dmx_debug_split_activations", "dmx_debug_split_activations_fp16",
     "dmx_model_arch", "dmx_engine_arch", "dmx_engine_transport", "dmx_engine_set_finish", "dmx_engine_finish", "dmx_engine_root_ctx", "dmx_engine_track_infer", "dmx_engine_partition",
-    "dmx_tracks_infer",
+    "dmx_tracks_infer", "dmx_tracks_infer_opts", "dmx_track_geometry_overlap",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -92,6 +92,8 @@ def lib():
         L.dmx_segment_infer_device.argtypes = [vp, fp, fp, ci]
         L.dmx_track_infer.argtypes = [vp, fp, i64, ci, fp, ci, vp, vp]
         L.dmx_tracks_infer.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp]
+        L.dmx_tracks_infer_opts.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp]
+        L.dmx_track_geometry_overlap.argtypes = [i64, i64, ci, ctypes.c_float, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
         L.dmx_track_gather_device.argtypes = [vp, fp, i64, fp, ci, vp, ci, fp]
@@ -277,6 +279,41 @@ class Context:
                 o[...] = img.transpose(2, 1, 0)
         return out
 
+    def tracks_opts(self, audios, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None, progress=None, out=None,
+                    layout: int = LAYOUT_PLANAR) -> List[np.ndarray]:
+        """tracks() with demucs's shifts ensemble and segment overlap (dmx_tracks_infer_opts): each track is run as n_shifts
+        copies, copy k shifted by shift_offsets[t, k], and the copies' normalised results are averaged before
+        de-normalisation. shift_offsets: None or an int array of shape (T, n_shifts), -1 entries drawn as rand() % 22050 in
+        (track, copy) order. n_shifts=1, overlap=0.25 gives the bits of tracks()."""
+        T = len(audios)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        if out is None:
+            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
+        assert len(out) == T
+        for o, n in zip(out, ns):
+            assert o.shape == (self.S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
+        if layout == LAYOUT_EIGEN:
+            src = [np.ascontiguousarray(a.T) for a in audios]
+            dst = [np.zeros((n, 2, self.S), np.float32) for n in ns]
+        else:
+            src, dst = audios, out
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            assert arr.shape == (T, n_shifts), f"shift_offsets: expected shape {(T, n_shifts)}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        _chk(lib().dmx_tracks_infer_opts(self.h, T, ap, na, int(n_shifts), float(overlap), so, op, layout, cbp, None))
+        if layout == LAYOUT_EIGEN:
+            for o, img in zip(out, dst):
+                o[...] = img.transpose(2, 1, 0)
+        return out
+
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:
         ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         _chk(lib().dmx_track_geometry(self.h, n, shift_offset, ctypes.byref(ln), ctypes.byref(ns), ctypes.byref(st)))
@@ -324,6 +361,14 @@ class Context:
             rows.append((nm, k, float(ms), float(fl), float(by)))
             self.profile_geometry[nm] = ln.split("\t")[5] if ln.count("\t") >= 5 else ""
         return rows
+
+
+def track_geometry(segment_samples: int, n: int, shift_offset: int, overlap: float = 0.25) -> Tuple[int, int, int]:
+    """(shifted length, number of segments, stride) of the segment loop at any overlap (dmx_track_geometry_overlap; no GPU)"""
+    ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+    _chk(lib().dmx_track_geometry_overlap(segment_samples, n, shift_offset, float(overlap), ctypes.byref(ln), ctypes.byref(ns),
+                                          ctypes.byref(st)))
+    return ln.value, ns.value, st.value
 
 
 def resample_length(n_in: int, rate_in: int, rate_out: int) -> int:

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <cctype>
 #include <cerrno>
+#include <climits>
 #include <fcntl.h>
 #include <pthread.h>
 #include <signal.h>
@@ -1314,14 +1315,20 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
 // and their device-to-host copy runs on a second stream underneath the kernels of the following batch (the 339 MB result
 // of a 4-minute track otherwise costs as much wall time after the last kernel as a dozen segments).
 //
-// Several tracks: their segments are laid end to end in track order (global segment index) and dealt in batches of
+// Several tracks: their segments are laid end to end in track order (global item index) and dealt in batches of
 // max_batch, so a batch may hold the tail of one track and the head of the next. Every kernel serves each of its tracks
 // exactly as it serves a track of its own (misc.hip), so every result is the bits of a call per track.
-//   * Segment outputs live in a ring of R = min(2 max_batch, total segments) blocks: global segment G is block G mod R.
-//     Batch k writes blocks [k B mod R, + nb) (contiguous: B divides R, or nothing wraps), and the overlap-add behind batch
-//     k reads segments >= k B - 1 only - the previous batch's last one at most - which batch k+1 does not overwrite; all
-//     of it is ordered on the context's stream.
-//   * A track holds a slot (upload, statistics, result) from the batch of its first segment until its last copy-out has
+// The shifts ensemble (N copies of each track, dmx_tracks_infer_opts): the items of a track are its copies' segments in
+// (row g, copy k) order, a copy absent from the rows past its last segment (the copies' segment counts differ when their
+// shifted lengths straddle a multiple of the stride), so the copies of one stretch of the track are adjacent.
+//   * Segment outputs live in a ring of R blocks: global item G is block G mod R. R is planned on the host before any GPU
+//     work: the largest distance from the first item an overlap-add reads to the end of its batch, rounded up to a multiple
+//     of max_batch, at least 2 max_batch, at most the total number of items. Batch k writes blocks [k B mod R, + nb)
+//     (contiguous: B divides R, or nothing wraps), which the overlap-adds behind batch k-1 and earlier no longer read; all
+//     of it is ordered on the context's stream. One copy at overlap 0.25 reads back one item at most: R = 2 max_batch.
+//   * A piece of a track is final when, for every copy, every segment covering it is done: its end is the minimum over the
+//     copies of "shifted positions below (segments done) * stride".
+//   * A track holds a slot (upload, statistics, result) from the batch of its first item until its last copy-out has
 //     completed. Batch k needs the slots of the tracks with first batch <= k and last batch >= k-1 (the copy-out of batch
 //     k-1 is issued after batch k has been enqueued); the call sizes that many slots for its longest track up front.
 //     A slot whose track finished in batch k-2 or earlier is taken over after a host wait on that track's copy-out event
@@ -1333,36 +1340,128 @@ struct TrackJob
 {
     const float *audio;
     float *out;
-    i64 n, len, g0, done;
-    int shift, nseg, kFirst, kLast, slot;
+    i64 n, g0, m, done; // g0: global index of the track's first item; m: its items (the sum of its copies' segment counts)
+    int c0, nMin, nMax, kFirst, kLast, slot; // c0: its first copy; nMin / nMax: the fewest / most segments of a copy
+};
+struct TrackCopy
+{
+    i64 len;
+    int shift, nseg, segDone;
 };
 struct TrackPiece
 {
     int t;
-    i64 lo, hi;
+    i64 lo, hi, itemLo; // itemLo: the first item (within the track) the piece's overlap-add reads
 };
+struct TrackItem
+{
+    int t, k, g;
+};
+// item index of (row g, copy k) within a track (misc.hip ens_item)
+i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
+{
+    if (g < nMin)
+        return g * N + k;
+    i64 it = 0;
+    for (int q = 0; q < N; ++q)
+    {
+        const i64 nq = cp[q].nseg;
+        it += std::min<i64>(g, nq);
+        if (q < k && nq > g)
+            ++it;
+    }
+    return it;
+}
 } // namespace
 
-static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, const int *shifts,
-                      float *const *out, int layout, dmx_progress_fn progress, void *user)
+// stride = (int)((1 - overlap) * segment), evaluated in fp32 (model_apply.cpp:162)
+static i64 overlap_stride(i64 seg, float overlap) { return (i64)((1.0f - overlap) * (float)seg); }
+
+// shifts: T x N, row-major; N == 1 launches track_ola_kernel, N >= 2 track_ola_ens_kernel
+static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
+                      const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user)
 {
     HIPCHK(hipSetDevice(c->m->device));
     const int S = c->m->pm.n_sources, B = c->maxBatch;
     const i64 seg = c->seg, blk = (i64)S * 2 * seg;
     std::vector<TrackJob> jobs((size_t)T);
-    i64 stride = 0, N = 0, nmax = 0;
+    std::vector<TrackCopy> copies((size_t)T * N);
+    i64 M = 0, nmax = 0;
     for (int t = 0; t < T; ++t)
     {
         TrackJob &j = jobs[(size_t)t];
-        j.audio = audio[t], j.out = out[t], j.n = n[t], j.shift = shifts[t], j.done = 0, j.slot = -1;
-        DMXCHK(dmx_track_geometry(c, j.n, j.shift, &j.len, &j.nseg, &stride));
-        j.g0 = N;
-        N += j.nseg;
-        j.kFirst = (int)(j.g0 / B), j.kLast = (int)((N - 1) / B);
+        j.audio = audio[t], j.out = out[t], j.n = n[t], j.done = 0, j.slot = -1, j.c0 = t * N, j.m = 0;
+        j.nMin = INT_MAX, j.nMax = 0;
+        for (int k = 0; k < N; ++k)
+        {
+            TrackCopy &cp = copies[(size_t)(j.c0 + k)];
+            cp.shift = shifts[j.c0 + k], cp.segDone = 0;
+            cp.len = j.n + DMX_MAX_SHIFT - cp.shift; // dmx_track_geometry_overlap
+            cp.nseg = (int)((cp.len + stride - 1) / stride);
+            j.nMin = std::min(j.nMin, cp.nseg), j.nMax = std::max(j.nMax, cp.nseg);
+            j.m += cp.nseg;
+        }
+        if ((j.nMax - j.nMin) * N > TrackEnsTable::kMaxTail) // cannot happen for a context's segment (>= 4096) and overlap <= 0.9
+            return fail(DMX_ERR_ARG, "%s: internal error (track %d: %d tail rows x %d shifts)", fn, t, j.nMax - j.nMin, N);
+        j.g0 = M;
+        M += j.m;
+        j.kFirst = (int)(j.g0 / B), j.kLast = (int)((M - 1) / B);
         nmax = std::max(nmax, j.n);
     }
-    const int nBatches = (int)((N + B - 1) / B);
-    const i64 R = std::min<i64>(2 * (i64)B, N);
+    std::vector<TrackItem> items;
+    items.reserve((size_t)M);
+    for (int t = 0; t < T; ++t)
+        for (int g = 0; g < jobs[(size_t)t].nMax; ++g)
+            for (int k = 0; k < N; ++k)
+                if (g < copies[(size_t)(t * N + k)].nseg)
+                    items.push_back(TrackItem{t, k, g});
+    const int nBatches = (int)((M + B - 1) / B);
+
+    // plan (host only): the pieces each batch makes final, and the ring they need
+    std::vector<std::vector<TrackPiece>> plan((size_t)nBatches);
+    i64 reach = 0;
+    {
+        int tLo = 0;
+        for (int k = 0; k < nBatches; ++k)
+        {
+            const i64 g0 = (i64)k * B, nb = std::min<i64>(B, M - g0);
+            while (jobs[(size_t)tLo].kLast < k)
+                ++tLo;
+            for (i64 g = g0; g < g0 + nb; ++g)
+                ++copies[(size_t)(jobs[(size_t)items[(size_t)g].t].c0 + items[(size_t)g].k)].segDone;
+            for (int t = tLo; t < T && jobs[(size_t)t].kFirst <= k; ++t)
+            {
+                TrackJob &j = jobs[(size_t)t];
+                const TrackCopy *cp = &copies[(size_t)j.c0];
+                // shifted-track positions below (segments done)*stride are covered only by segments done
+                i64 fin = j.n;
+                for (int q = 0; q < N; ++q)
+                    if (cp[q].segDone < cp[q].nseg)
+                        fin = std::min<i64>(fin, (i64)cp[q].segDone * stride - (DMX_MAX_SHIFT - cp[q].shift));
+                fin = std::max<i64>(j.done, fin);
+                TrackPiece pc{t, j.done, fin, 0};
+                if (fin > j.done)
+                {
+                    pc.itemLo = INT64_MAX;
+                    i64 itemHi = -1;
+                    for (int q = 0; q < N; ++q)
+                    {
+                        const i64 j0 = j.done + DMX_MAX_SHIFT - cp[q].shift; // first shifted position of the piece: its first segment
+                        const i64 gLo = j0 - seg + 1 <= 0 ? 0 : (j0 - seg + stride) / stride;
+                        const i64 gHi = std::min<i64>(cp[q].nseg - 1, (fin - 1 + DMX_MAX_SHIFT - cp[q].shift) / stride); // its last
+                        pc.itemLo = std::min(pc.itemLo, track_item(cp, N, j.nMin, gLo, q));
+                        itemHi = std::max(itemHi, track_item(cp, N, j.nMin, gHi, q));
+                    }
+                    if (pc.itemLo < 0 || itemHi >= g0 + nb - j.g0) // every segment the piece reads must be done
+                        return fail(DMX_ERR_ARG, "%s: internal error (track %d reads item %lld after batch %d)", fn, t, (long long)itemHi, k);
+                    reach = std::max(reach, g0 + nb - (j.g0 + pc.itemLo));
+                }
+                plan[(size_t)k].push_back(pc);
+                j.done = fin;
+            }
+        }
+    }
+    const i64 R = std::min<i64>(M, std::max<i64>(2 * (i64)B, (reach + B - 1) / B * B));
     // slots: track t is held during batches [kFirst, kLast + 1]
     int nSlots = 0;
     {
@@ -1398,13 +1497,12 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
 
     if (progress)
         progress(0.0f, "1., apply model w/ shift", user);
-    // pieces[k & 1]: the output samples [lo, hi) of the tracks of batch k that are final once batch k is done. Their copy
-    // is issued AFTER batch k+1 has been enqueued: a device-to-host copy into pageable memory blocks the calling thread
-    // until the data has left the GPU, and the GPU must have its next batch queued by then.
-    std::vector<TrackPiece> pieces[2];
+    // plan[k]: the output samples [lo, hi) of the tracks of batch k that are final once batch k is done. Their copy is
+    // issued AFTER batch k+1 has been enqueued: a device-to-host copy into pageable memory blocks the calling thread until
+    // the data has left the GPU, and the GPU must have its next batch queued by then.
     auto copy_piece = [&](int k) -> int {
         HIPCHK(hipStreamWaitEvent(c->copyStream, c->batchEvents[(size_t)k], 0));
-        for (const TrackPiece &pc : pieces[k & 1])
+        for (const TrackPiece &pc : plan[(size_t)k])
         {
             const TrackJob &j = jobs[(size_t)pc.t];
             const float *dOut = c->slots[(size_t)j.slot].out.p;
@@ -1424,22 +1522,24 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
         }
         if (progress)
         {
-            const i64 g0 = (i64)k * B, nb = std::min<i64>(B, N - g0);
+            const i64 g0 = (i64)k * B, nb = std::min<i64>(B, M - g0);
             HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
             char msg[128];
             snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %lld..%lld of %lld", (long long)g0, (long long)(g0 + nb - 1),
-                     (long long)N);
-            progress((float)(g0 + nb) / (float)N, msg, user);
+                     (long long)M);
+            progress((float)(g0 + nb) / (float)M, msg, user);
         }
         return DMX_OK;
     };
 
-    std::vector<TrackSegItem> items((size_t)B);
+    std::vector<TrackSegItem> batchItems((size_t)B);
     std::vector<TrackOlaEntry> ola;
+    std::vector<TrackEnsPiece> ens;
+    std::vector<TrackEnsCopy> ensCopies;
     int tLo = 0; // first track of the current batch
     for (int k = 0; k < nBatches; ++k)
     {
-        const i64 g0 = (i64)k * B, nb = std::min<i64>(B, N - g0);
+        const i64 g0 = (i64)k * B, nb = std::min<i64>(B, M - g0);
         while (jobs[(size_t)tLo].kLast < k)
             ++tLo;
         int tHi = tLo; // one past the last track of the batch
@@ -1489,43 +1589,42 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
                 nSt = 0;
             }
         }
-        // gather the batch: global segments [g0, g0 + nb)
+        // gather the batch: global items [g0, g0 + nb)
+        for (i64 g = g0; g < g0 + nb; ++g)
         {
-            int t = tLo;
-            for (i64 g = g0; g < g0 + nb; ++g)
-            {
-                while (jobs[(size_t)t].g0 + jobs[(size_t)t].nseg <= g)
-                    ++t;
-                const TrackJob &j = jobs[(size_t)t];
-                items[(size_t)(g - g0)] = TrackSegItem{c->slots[(size_t)j.slot].audio.p, c->slots[(size_t)j.slot].stats.p, j.n, j.shift,
-                                                       (int)(g - j.g0)};
-            }
+            const TrackItem &it = items[(size_t)g];
+            const TrackJob &j = jobs[(size_t)it.t];
+            const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
+            batchItems[(size_t)(g - g0)] = TrackSegItem{sl.audio.p, sl.stats.p, j.n, copies[(size_t)(j.c0 + it.k)].shift, it.g};
         }
-        launch_track_gather(items.data(), (int)nb, seg, stride, dMix, c->stream);
+        launch_track_gather(batchItems.data(), (int)nb, seg, stride, dMix, c->stream);
         HIPCHK(hipGetLastError());
         DMXCHK(dmx_segment_infer_device(c, dMix, ring + (g0 % R) * blk, (int)nb));
         // finish what this batch makes final
-        std::vector<TrackPiece> &pcs = pieces[k & 1];
-        pcs.clear();
-        ola.clear();
-        for (int t = tLo; t < tHi; ++t)
+        ola.clear(), ens.clear(), ensCopies.clear();
+        for (const TrackPiece &pc : plan[(size_t)k])
         {
-            TrackJob &j = jobs[(size_t)t];
-            const i64 off = DMX_MAX_SHIFT - j.shift;
-            // shifted-track positions below (segments done)*stride are covered only by segments done
-            i64 fin = j.kLast == k ? j.n : (g0 + nb - j.g0) * stride - off;
-            fin = std::max<i64>(j.done, std::min<i64>(fin, j.n));
-            pcs.push_back(TrackPiece{t, j.done, fin});
-            if (fin > j.done)
+            if (pc.hi <= pc.lo)
+                continue;
+            const TrackJob &j = jobs[(size_t)pc.t];
+            const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
+            const i64 slotLo = (j.g0 + pc.itemLo) % R;
+            if (N == 1)
             {
-                const i64 j0 = j.done + off; // first shifted position of the piece and the first segment covering it
-                const i64 gLo = j0 - seg + 1 <= 0 ? 0 : (j0 - seg + stride) / stride;
-                ola.push_back(TrackOlaEntry{ring, c->slots[(size_t)j.slot].stats.p, c->slots[(size_t)j.slot].out.p, j.n, j.len, j.done, fin,
-                                            gLo, (j.g0 + gLo) % R, j.nseg, j.shift});
+                const TrackCopy &cp = copies[(size_t)j.c0];
+                ola.push_back(TrackOlaEntry{ring, sl.stats.p, sl.out.p, j.n, cp.len, pc.lo, pc.hi, pc.itemLo, slotLo, cp.nseg, cp.shift});
             }
-            j.done = fin;
+            else
+            {
+                ens.push_back(TrackEnsPiece{sl.stats.p, sl.out.p, j.n, pc.lo, pc.hi, pc.itemLo, slotLo, j.nMin, j.nMax - j.nMin});
+                for (int q = 0; q < N; ++q)
+                    ensCopies.push_back(TrackEnsCopy{copies[(size_t)(j.c0 + q)].shift, copies[(size_t)(j.c0 + q)].nseg});
+            }
         }
-        launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, R, eigen, 0, 2 * S, c->stream);
+        if (N == 1)
+            launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, R, eigen, 0, 2 * S, c->stream);
+        else
+            launch_track_ola_ens(ens.data(), ensCopies.data(), (int)ens.size(), N, ring, S, seg, stride, R, eigen, 0, 2 * S, c->stream);
         HIPCHK(hipGetLastError());
         hipEvent_t ev = dmx_batch_event(c, (size_t)k);
         if (!ev)
@@ -1555,7 +1654,8 @@ extern "C" int dmx_track_infer(dmx_ctx *c, const float *audio, int64_t n, int sh
         shift_offset = rand() % DMX_MAX_SHIFT; // model_apply.cpp:114
     if (shift_offset >= DMX_MAX_SHIFT)
         return fail(DMX_ERR_ARG, "dmx_track_infer: shift_offset must be < %d", DMX_MAX_SHIFT);
-    return tracks_run(c, "dmx_track_infer", 1, &audio, &n, &shift_offset, &out, layout, progress, user);
+    return tracks_run(c, "dmx_track_infer", 1, &audio, &n, 1, overlap_stride(c->seg, 0.25f), &shift_offset, &out, layout, progress,
+                      user);
 }
 
 extern "C" int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, const int *shift_offsets,
@@ -1583,7 +1683,73 @@ extern "C" int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *au
     std::vector<int> shifts((size_t)n_tracks);
     for (int t = 0; t < n_tracks; ++t) // drawn in track order, like successive dmx_track_infer calls (model_apply.cpp:114)
         shifts[(size_t)t] = !shift_offsets || shift_offsets[t] < 0 ? rand() % DMX_MAX_SHIFT : shift_offsets[t];
-    return tracks_run(c, "dmx_tracks_infer", n_tracks, audio, n, shifts.data(), out, layout, progress, user);
+    return tracks_run(c, "dmx_tracks_infer", n_tracks, audio, n, 1, overlap_stride(c->seg, 0.25f), shifts.data(), out, layout,
+                      progress, user);
+}
+
+extern "C" int dmx_track_geometry_overlap(int64_t segment_samples, int64_t n, int shift_offset, float overlap, int64_t *shifted_len,
+                                          int *n_segments, int64_t *stride)
+{
+    if (segment_samples < 1 || n <= 0)
+        return fail(DMX_ERR_ARG, "dmx_track_geometry_overlap: invalid argument (segment_samples %lld, n %lld)",
+                    (long long)segment_samples, (long long)n);
+    if (shift_offset < 0 || shift_offset >= DMX_MAX_SHIFT)
+        return fail(DMX_ERR_ARG, "dmx_track_geometry_overlap: shift_offset %d not in [0, %d)", shift_offset, DMX_MAX_SHIFT);
+    if (!(overlap >= 0.0f && overlap <= DMX_MAX_OVERLAP)) // also NaN
+        return fail(DMX_ERR_ARG, "dmx_track_geometry_overlap: overlap %g not in [0, %g]", (double)overlap, (double)DMX_MAX_OVERLAP);
+    const i64 st = overlap_stride(segment_samples, overlap);
+    if (st < 1)
+        return fail(DMX_ERR_ARG, "dmx_track_geometry_overlap: stride %lld < 1", (long long)st);
+    const i64 len = n + DMX_MAX_SHIFT - shift_offset;
+    if (shifted_len)
+        *shifted_len = len;
+    if (stride)
+        *stride = st;
+    if (n_segments)
+        *n_segments = (int)((len + st - 1) / st);
+    return DMX_OK;
+}
+
+extern "C" int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts,
+                                     float overlap, const int *shift_offsets, float *const *out, int layout, dmx_progress_fn progress,
+                                     void *user)
+{
+    const char *fn = "dmx_tracks_infer_opts";
+    if (!c)
+        return fail(DMX_ERR_ARG, "%s: null context", fn);
+    if (n_tracks < 1)
+        return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
+    if (!audio || !n || !out)
+        return fail(DMX_ERR_ARG, "%s: null %s array", fn, !audio ? "audio" : !n ? "n" : "out");
+    if (layout != DMX_LAYOUT_EIGEN && layout != DMX_LAYOUT_PLANAR)
+        return fail(DMX_ERR_ARG, "%s: unknown layout %d", fn, layout);
+    if (n_shifts < 1 || n_shifts > DMX_MAX_SHIFTS)
+        return fail(DMX_ERR_ARG, "%s: n_shifts must be in [1, %d], got %d", fn, DMX_MAX_SHIFTS, n_shifts);
+    if (!(overlap >= 0.0f && overlap <= DMX_MAX_OVERLAP))
+        return fail(DMX_ERR_ARG, "%s: overlap %g not in [0, %g]", fn, (double)overlap, (double)DMX_MAX_OVERLAP);
+    const i64 stride = overlap_stride(c->seg, overlap);
+    if (stride < 1)
+        return fail(DMX_ERR_ARG, "%s: stride %lld < 1 (segment %lld, overlap %g)", fn, (long long)stride, (long long)c->seg, (double)overlap);
+    const int N = n_shifts;
+    for (int t = 0; t < n_tracks; ++t)
+    {
+        if (!audio[t])
+            return fail(DMX_ERR_ARG, "%s: track %d: null audio pointer", fn, t);
+        if (!out[t])
+            return fail(DMX_ERR_ARG, "%s: track %d: null out pointer", fn, t);
+        if (n[t] < 2)
+            return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be >= 2", fn, t, (long long)n[t]);
+        for (int k = 0; shift_offsets && k < N; ++k)
+        {
+            const int s = shift_offsets[(size_t)t * N + k];
+            if (s < -1 || s >= DMX_MAX_SHIFT)
+                return fail(DMX_ERR_ARG, "%s: track %d, shift %d: shift_offset %d not in [-1, %d)", fn, t, k, s, DMX_MAX_SHIFT);
+        }
+    }
+    std::vector<int> shifts((size_t)n_tracks * N);
+    for (size_t i = 0; i < shifts.size(); ++i) // drawn in (track, copy) order; N = 1: dmx_tracks_infer's order
+        shifts[i] = !shift_offsets || shift_offsets[i] < 0 ? rand() % DMX_MAX_SHIFT : shift_offsets[i];
+    return tracks_run(c, fn, n_tracks, audio, n, N, stride, shifts.data(), out, layout, progress, user);
 }
 
 // --------------------------------------------------------------------------- debug

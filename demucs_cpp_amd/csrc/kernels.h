@@ -302,6 +302,34 @@ void launch_track_ola(const TrackOlaEntry *entries, int T, int S, i64 seg, i64 s
 void launch_track_ola(const float *segOut, int nSeg, int S, i64 seg, i64 stride, i64 len, i64 n, int shiftOffset,
                       const float *stats, float *out, int layout, int planeBase, int nPlanes, i64 i0, i64 i1, hipStream_t s,
                       int gBase = 0);
+// the shifts ensemble (dmx_tracks_infer_opts, N >= 2 copies): per output sample, the normalised overlap-add value of each copy
+// k (track_ola_kernel's weights, order and skips, on copy k's own shifted geometry) is summed in increasing k, then
+// (e / N) * std + mean. A track's segments are items dealt in (row g, copy k) order, copies with nseg_k <= g absent:
+//   item(g, k) = sum_k' min(g, nseg_k') + #{k' < k : nseg_k' > g}   (= g N + k while g < min_k nseg_k).
+// Item `it` of a piece's track is ring block slotLo + (it - itemLo), less `ring` when that is >= ring.
+struct TrackEnsPiece
+{
+    const float *stats;
+    float *out;
+    i64 n, i0, i1;
+    i64 itemLo, slotLo; // the lowest item the piece reads, and its ring block
+    int nMin, nTail;    // rows g < nMin hold all N copies; rows [nMin, nMin + nTail) are the tail (nTail N <= kMaxTail)
+};
+struct TrackEnsCopy
+{
+    int shift, nseg;
+};
+struct TrackEnsTable
+{
+    static const int kMaxPieces = 16, kMaxCopies = 256; // a launch carries min(kMaxPieces, kMaxCopies / N) pieces
+    // tail rows x copies of a piece's track, tabulated in LDS per block: nTail <= ceil(22049 / stride) + 1 <= 55 at the
+    // smallest segment (4096) and overlap 0.9, times N <= 32
+    static const int kMaxTail = 2048;
+    TrackEnsPiece p[kMaxPieces];
+    TrackEnsCopy c[kMaxCopies]; // piece z's copies: c[z N + k]
+};
+void launch_track_ola_ens(const TrackEnsPiece *pieces, const TrackEnsCopy *copies, int P, int N, const float *segOut, int S,
+                          i64 seg, i64 stride, i64 ring, int layout, int planeBase, int nPlanes, hipStream_t s);
 // dst[r*dpitch + i] = src[r*spitch + i], r < rows, i < width (floats)
 void launch_copy_rows(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width, int rows, hipStream_t s);
 // dst[i] = fp16 bit pattern of src[i], round to nearest even (the opt-in fp16 weight plane, api.cpp dmx_model_fp16_plane)

@@ -467,6 +467,117 @@ void launch_track_ola(const float *segOut, int nSeg, int S, i64 seg, i64 stride,
     launch_track_ola(&e, 1, S, seg, stride, INT64_MAX, layout, planeBase, nPlanes, s);
 }
 
+// the shifts ensemble (apply_model(shifts=N): out += shifted_out; out /= shifts, then * std + mean in separate): for each
+// copy k in increasing k, exactly track_ola_kernel's normalised value acc / sw on copy k's shifted geometry, summed in fp32;
+// then (e / N) * std + mean, written like track_ola_kernel's (acc / sw) * stdv + mean so that both contract alike.
+// Grid (x, planes, pieces); the pieces and their copies travel by value (TrackEnsTable).
+static_assert(sizeof(TrackEnsTable) <= 3584, "TrackEnsTable must leave room in HIP's 4 KB kernel-argument limit");
+__device__ __forceinline__ i64 ens_item(const TrackEnsCopy *cp, int N, int nMin, i64 g, int k)
+{
+    if (g < nMin)
+        return g * N + k;
+    i64 it = 0; // the tail rows: copies with nseg <= g are absent
+    for (int q = 0; q < N; ++q)
+    {
+        const i64 nq = cp[q].nseg;
+        it += g < nq ? g : nq;
+        if (q < k && nq > g)
+            ++it;
+    }
+    return it;
+}
+__global__ __launch_bounds__(256) void track_ola_ens_kernel(TrackEnsTable t, int N, const float *segOut, int S, i64 seg,
+                                                            i64 stride, i64 ring, int layout, int planeBase)
+{
+    const TrackEnsPiece &p = t.p[blockIdx.z];
+    const TrackEnsCopy *cp = t.c + (i64)blockIdx.z * N;
+    const int plane = blockIdx.y + planeBase;
+    const float mean = p.stats[0], stdv = p.stats[1];
+    const i64 maxShift = 22050;
+    const float half = (float)(seg / 2);
+    const i64 n = p.n;
+    float *out = p.out;
+    // item(g, k) - nMin N of the tail rows, computed once per block instead of O(N) per segment read
+    __shared__ int tail[TrackEnsTable::kMaxTail];
+    const int nMin = p.nMin;
+    for (int idx = threadIdx.x; idx < p.nTail * N; idx += 256)
+        tail[idx] = (int)(ens_item(cp, N, nMin, nMin + idx / N, idx % N) - (i64)nMin * N);
+    __syncthreads();
+    for (i64 i = p.i0 + (i64)blockIdx.x * 256 + threadIdx.x; i < p.i1; i += (i64)gridDim.x * 256)
+    {
+        float e = 0.f;
+        for (int c = 0; c < N; ++c)
+        {
+            const int shift = cp[c].shift, nSeg = cp[c].nseg;
+            const i64 len = n + maxShift - shift; // dmx_track_geometry_overlap
+            const i64 j = i + maxShift - shift;   // position in copy c's shifted track
+            float acc = 0.f, sw = 0.f;
+            i64 first = (j - seg + stride) / stride; // smallest g with g*stride + seg > j
+            if (j - seg + 1 <= 0)
+                first = 0;
+            for (i64 g = first; g < nSeg && g * stride <= j; ++g)
+            {
+                const i64 off = g * stride;
+                const i64 chunk = seg < len - off ? seg : len - off;
+                const i64 k = j - off;
+                if (k >= chunk)
+                    continue;
+                const i64 left = (seg - chunk) / 2;
+                // triangle weight, indexed from 0 even for short chunks (Q8)
+                const i64 kk = k < seg / 2 ? k + 1 : seg - k;
+                const float w = (float)kk / half;
+                const i64 it = g < nMin ? g * N + c : (i64)nMin * N + tail[(g - nMin) * N + c];
+                i64 blk = p.slotLo + (it - p.itemLo);
+                if (blk >= ring)
+                    blk -= ring;
+                acc += w * segOut[(blk * S * 2 + plane) * seg + left + k];
+                sw += w;
+            }
+            const float v = acc / sw;
+            e = c == 0 ? v : e + v;
+        }
+        const float v = (e / (float)N) * stdv + mean;
+        if (layout == 0)
+            out[(i64)plane * n + i] = v;
+        else
+        {
+            const int sIdx = plane >> 1, c = plane & 1;
+            out[sIdx + (i64)S * (c + 2 * i)] = v;
+        }
+    }
+}
+void launch_track_ola_ens(const TrackEnsPiece *pieces, const TrackEnsCopy *copies, int P, int N, const float *segOut, int S,
+                          i64 seg, i64 stride, i64 ring, int layout, int planeBase, int nPlanes, hipStream_t s)
+{
+    if (nPlanes <= 0 || N < 1 || N > TrackEnsTable::kMaxCopies)
+        return;
+    for (int z = 0; z < P; ++z)
+        if (pieces[z].nTail < 0 || pieces[z].nTail * N > TrackEnsTable::kMaxTail)
+            return; // the host checks this before any GPU work (tracks_run)
+    const int per = TrackEnsTable::kMaxCopies / N < TrackEnsTable::kMaxPieces ? TrackEnsTable::kMaxCopies / N : TrackEnsTable::kMaxPieces;
+    for (int z0 = 0; z0 < P; z0 += per)
+    {
+        TrackEnsTable t{};
+        int nz = 0;
+        i64 span = 0;
+        for (int z = z0; z < P && z < z0 + per; ++z, ++nz)
+        {
+            t.p[nz] = pieces[z];
+            for (int k = 0; k < N; ++k)
+                t.c[nz * N + k] = copies[(i64)z * N + k];
+            if (pieces[z].i1 - pieces[z].i0 > span)
+                span = pieces[z].i1 - pieces[z].i0;
+        }
+        if (span <= 0)
+            continue;
+        int gx = (int)((span + 255) / 256);
+        if (gx > 4096)
+            gx = 4096;
+        hipLaunchKernelGGL(track_ola_ens_kernel, dim3(gx, nPlanes, nz), dim3(256), 0, s, t, N, segOut, S, seg, stride, ring, layout,
+                           planeBase);
+    }
+}
+
 // rows x width floats between two pitched images (packing / unpacking the segment tails the OWNER finish mode exchanges)
 __global__ __launch_bounds__(256) void copy_rows_kernel(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width)
 {

@@ -11,7 +11,8 @@
 //   <4,2,N> demucs_v3_inference(const demucs_v3_model&, <2,N>, ProgressCallback)          :1405-1408
 //   void  model_v3_inference(const demucs_v3_model&, demucs_v3_segment_buffers&, stft_buffers&, ...) :1410-1414
 // plus, with no reference counterpart (the reference's CLIs take one file), demucs_inference_batch /
-// demucs_v3_inference_batch: many tracks in one call, their segments sharing batches (dmx_tracks_infer).
+// demucs_v3_inference_batch: many tracks in one call, their segments sharing batches (dmx_tracks_infer), and their overloads
+// taking demucscpp::inference_options: demucs's shifts ensemble and segment overlap (dmx_tracks_infer_opts).
 //
 // Eigen is not required: the two tensor types below have exactly the memory image of
 // the reference's column-major Eigen::MatrixXf(2,N) and Eigen::Tensor3dXf(S,2,N), so a
@@ -239,6 +240,59 @@ inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model,
     return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb);
 }
 
+// demucs's inference-time quality options (PyTorch demucs apply_model(shifts=, overlap=); the reference fixes 1 and 0.25) for
+// the batch calls (dmx_tracks_infer_opts). shift_offsets: empty (model.shift_offset for every copy; -1: rand() % 22050 drawn
+// per (track, copy)), `shifts` values applied to every track, or tracks x shifts values, row-major.
+struct inference_options
+{
+    int shifts = 1;
+    float overlap = 0.25f;
+    std::vector<int> shift_offsets;
+};
+namespace detail
+{
+inline std::vector<StemTensor> batch_call(const char *who, const engine_model &model, int S, const std::vector<StereoMatrix> &tracks,
+                                          const ProgressCallback &cb, const inference_options &opts)
+{
+    const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
+    std::vector<StemTensor> out;
+    out.reserve(T);
+    if (T == 0)
+        return out;
+    std::vector<int> shifts(T * N, model.shift_offset);
+    if (opts.shift_offsets.size() == N)
+        for (size_t i = 0; i < shifts.size(); ++i)
+            shifts[i] = opts.shift_offsets[i % N];
+    else if (opts.shift_offsets.size() == T * N)
+        shifts = opts.shift_offsets;
+    else if (!opts.shift_offsets.empty())
+    {
+        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
+        std::exit(1);
+    }
+    std::vector<const float *> in(T);
+    std::vector<float *> dst(T);
+    std::vector<int64_t> n(T);
+    for (size_t t = 0; t < T; ++t)
+    {
+        out.emplace_back(S, tracks[t].cols());
+        in[t] = tracks[t].data.data(), dst[t] = out[t].data.data(), n[t] = tracks[t].cols();
+    }
+    CbThunk th{&cb};
+    std::lock_guard<std::mutex> guard(model.lock);
+    dmx_ctx *c = dmx_engine_root_ctx(model.engine, 0);
+    if (!c || dmx_tracks_infer_opts(c, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), dst.data(), DMX_LAYOUT_EIGEN,
+                                    progress_thunk, &th) != DMX_OK)
+        die(who);
+    return out;
+}
+} // namespace detail
+inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                                      const inference_options &opts)
+{
+    return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb, opts);
+}
+
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
 // reference runs four demucs_inference calls back to back; calling demucs_inference on four demucs_model
 // objects still works here, but one bag engine deals all (model, segment) items over the devices at once
@@ -426,6 +480,11 @@ inline std::vector<StemTensor> demucs_v3_inference_batch(const demucs_v3_model &
                                                          ProgressCallback cb)
 {
     return demucscpp::detail::batch_call("demucs_v3_inference_batch", model, 4, tracks, cb);
+}
+inline std::vector<StemTensor> demucs_v3_inference_batch(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
+                                                         ProgressCallback cb, const demucscpp::inference_options &opts)
+{
+    return demucscpp::detail::batch_call("demucs_v3_inference_batch", model, 4, tracks, cb, opts);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

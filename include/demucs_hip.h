@@ -35,6 +35,8 @@ extern "C"
 
 #define DMX_SEGMENT_SAMPLES 343980 /* 7.8 s @ 44.1 kHz, src/model.hpp:652, :20        */
 #define DMX_MAX_SHIFT 22050        /* 0.5 s, src/model.hpp:654                         */
+#define DMX_MAX_SHIFTS 32          /* copies of the shifts ensemble (dmx_tracks_infer_opts) */
+#define DMX_MAX_OVERLAP 0.9f       /* largest segment overlap (10 segments per sample)  */
 
 /* Audio memory layouts at the boundary.
  * DMX_LAYOUT_EIGEN : the exact memory image of the reference's Eigen types
@@ -154,12 +156,37 @@ extern "C"
     int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, const int *shift_offsets,
                          float *const *out, int layout, dmx_progress_fn progress, void *user);
 
+    /* dmx_tracks_infer with demucs's two inference-time quality options (apply_model(shifts=, overlap=); the reference fixes
+     * shifts = 1 and overlap = 0.25). Each track is run as n_shifts copies, copy k shifted by shift_offsets[t*n_shifts + k]
+     * (NULL or -1 entries: rand() % 22050, drawn in row-major (track, copy) order), each cut into segments at the stride
+     * (int64)((1 - overlap) * segment_samples) evaluated in fp32. Per output sample, each copy's normalised overlap-add value
+     * (the triangle-weighted sum over its segments in segment order, divided by the weight sum) is summed in fp32 in
+     * increasing copy order, then out = (sum / n_shifts) * std + mean: demucs's `out += shifted_out; out /= shifts` before
+     * de-normalisation. n_shifts = 1 and overlap = 0.25 give the bits of dmx_tracks_infer.
+     *   1 <= n_shifts <= DMX_MAX_SHIFTS, 0 <= overlap <= DMX_MAX_OVERLAP (finite), shift_offsets in [-1, 22050).
+     * Arguments are checked before any GPU work and nothing is written on error; the message names the track and the copy
+     * ("track 2, shift 1: ..."). The (track, copy, segment) items are dealt in batches of max_batch in (track, segment,
+     * copy) order, so the copies of one stretch of a track are adjacent and a piece of output is finished as soon as every
+     * copy's segments covering it are done. Progress is the fraction of all items done (one report per batch, last value 1).
+     * Device memory beyond the context's arena is bounded as for dmx_tracks_infer, except the ring of segment outputs:
+     *   R segment outputs (S x 2 x segment_samples floats each), R = the longest reach of an overlap-add back from the end
+     *   of its batch rounded up to a multiple of max_batch, at least 2 max_batch and at most the total number of items;
+     *   about max_batch + n_shifts (ceil((segment_samples + 22050) / stride) + 1) - independent of the number and the
+     *   length of the tracks. 2 max_batch at n_shifts = 1 and overlap 0.25, and while n_shifts stays below about
+     *   max_batch / 3 at the production segment and overlap 0.25. */
+    int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts, float overlap,
+                              const int *shift_offsets, float *const *out, int layout, dmx_progress_fn progress, void *user);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
     /* 0. geometry of the segment loop (src/model_apply.cpp:145-189) */
     int dmx_track_geometry(const dmx_ctx *c, int64_t n, int shift_offset, int64_t *shifted_len, int *n_segments,
                            int64_t *stride);
+    /*    pure host function, no device: the segment-loop geometry for any overlap in [0, DMX_MAX_OVERLAP]
+     *    (dmx_track_geometry is overlap = 0.25 on a context's segment) */
+    int dmx_track_geometry_overlap(int64_t segment_samples, int64_t n, int shift_offset, float overlap, int64_t *shifted_len,
+                                   int *n_segments, int64_t *stride);
     /* 1. mean / unbiased std of the mono reference (src/model_apply.cpp:72-78);
      *    d_audio interleaved [n][2]; d_stats: 2 floats */
     int dmx_track_stats_device(dmx_ctx *c, const float *d_audio, int64_t n, float *d_stats);
