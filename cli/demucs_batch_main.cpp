@@ -1,5 +1,6 @@
 // demucs_batch.cpp.main — many tracks in one call (no reference counterpart: the reference's CLIs take one file):
-//   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] <model file> <out dir> <wav file>...
+//   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
+//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] <model file> <out dir> <wav file>...
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
 // byte-identical to what demucs.cpp.main / demucs_v3.cpp.main writes for that input alone. The model's architecture
 // (HTDemucs v4 4s / 6s, or Demucs v3) is read from the file; the segments of all tracks share batches
@@ -10,6 +11,14 @@
 //   --shifts N               run each track as N shifted copies and average them (1 <= N <= 32; default 1)
 //   --overlap F              segment overlap, 0 <= F <= 0.9 (default 0.25)
 //   --shift-offsets a,b,...  the N copies' shift offsets in [0, 22050), applied to every track
+// Output options (demucs's; the stems are encoded on the GPU and leave it as WAV data: dmx_tracks_infer_pcm through
+// demucscpp::demucs_inference_batch_pcm):
+//   --two-stems NAME         write target_0_NAME.wav and target_1_no_NAME.wav (the sum of the other stems); NAME is a stem
+//                            of the loaded model
+//   --clip-mode MODE         rescale (divide a stem whose peak exceeds 1 / 1.01 by 1.01 peak), clamp (to +-0.99) or none
+//   --int16 --int24 --float32  sample format of the files (these take no value)
+// With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
+// They are refused for a track that DMX_RESAMPLE=1 converted: converting the stems back needs them in fp32.
 // With N > 1, DMX_SHIFT_OFFSET is ambiguous without --shift-offsets and is refused. Without options the call and its output
 // are those of the plain batch call.
 #include <cerrno>
@@ -23,8 +32,8 @@ using namespace demucscpp;
 
 [[noreturn]] static void usage(const char *argv0)
 {
-    std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] <model file> <out dir> <wav file>..."
-              << std::endl;
+    std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
+              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] <model file> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
 
@@ -44,14 +53,43 @@ static bool parse_int(const std::string &s, long lo, long hi, int &v)
 int main(int argc, const char **argv)
 {
     inference_options opts;
-    bool with_opts = false;
+    output_options out_opts; // demucs's defaults: 16 bit, rescale
+    bool with_opts = false, with_out_opts = false;
+    std::string two_stems;
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
         const std::string opt = argv[a];
+        if (opt == "--int16" || opt == "--int24" || opt == "--float32") // no value: step back so that a += 2 moves by one
+        {
+            out_opts.encoding = opt == "--int16" ? DMX_PCM_S16 : opt == "--int24" ? DMX_PCM_S24 : DMX_PCM_F32;
+            with_out_opts = true;
+            --a;
+            continue;
+        }
         if (a + 1 >= argc)
             usage(argv[0]);
         const std::string val = argv[a + 1];
+        if (opt == "--two-stems")
+        {
+            if (stem_index(val) < 0)
+                usage(argv[0]);
+            two_stems = val, out_opts.two_stems = stem_index(val), with_out_opts = true;
+            continue;
+        }
+        if (opt == "--clip-mode")
+        {
+            if (val == "rescale")
+                out_opts.clip = DMX_CLIP_RESCALE;
+            else if (val == "clamp")
+                out_opts.clip = DMX_CLIP_CLAMP;
+            else if (val == "none")
+                out_opts.clip = DMX_CLIP_NONE;
+            else
+                usage(argv[0]);
+            with_out_opts = true;
+            continue;
+        }
         with_opts = true;
         if (opt == "--shifts")
         {
@@ -120,11 +158,21 @@ int main(int argc, const char **argv)
     for (int i = 0; i < n_files; ++i)
         if (!wavio::load_audio_file(argv[3 + i], tracks[(size_t)i], &native_rate[(size_t)i], &native_frames[(size_t)i]))
             exit(1);
+    if (with_out_opts)
+        for (int i = 0; i < n_files; ++i)
+            if (native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE)
+            {
+                std::cerr << "--two-stems / --clip-mode / --int16 / --int24 / --float32 are not available for a track converted by "
+                          << "DMX_RESAMPLE=1 (" << argv[3 + i] << ", " << native_rate[(size_t)i]
+                          << " Hz): converting the stems back needs them in fp32" << std::endl;
+                exit(1);
+            }
     std::cout << std::fixed << std::setprecision(3);
     ProgressCallback cb = [](float progress, const std::string &msg) {
         std::cout << "(" << std::setw(3) << std::setfill(' ') << progress * 100.0f << "%) " << msg << std::endl;
     };
     std::vector<StemTensor> outs;
+    PcmOutputs pcm_outs;
     int nb_sources = 4;
     if (arch == 3)
     {
@@ -135,8 +183,16 @@ int main(int argc, const char **argv)
             exit(1);
         }
         std::cout << "Starting Demucs v3 MMI inference of " << n_files << " tracks" << std::endl;
-        outs = with_opts ? demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb, opts)
-                         : demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb);
+        if (with_out_opts && out_opts.two_stems >= nb_sources)
+        {
+            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
+            exit(1);
+        }
+        if (with_out_opts)
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_pcm(model, tracks, cb, opts, out_opts);
+        else
+            outs = with_opts ? demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb, opts)
+                             : demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb);
     }
     else
     {
@@ -148,15 +204,39 @@ int main(int argc, const char **argv)
         }
         nb_sources = model.is_4sources ? 4 : 6;
         std::cout << "Starting Demucs (" << nb_sources << "-source) inference of " << n_files << " tracks" << std::endl;
-        outs = with_opts ? demucs_inference_batch(model, tracks, cb, opts) : demucs_inference_batch(model, tracks, cb);
+        if (with_out_opts && out_opts.two_stems >= nb_sources)
+        {
+            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
+            exit(1);
+        }
+        if (with_out_opts)
+            pcm_outs = demucs_inference_batch_pcm(model, tracks, cb, opts, out_opts);
+        else
+            outs = with_opts ? demucs_inference_batch(model, tracks, cb, opts) : demucs_inference_batch(model, tracks, cb);
     }
     static const char *names[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
     for (int f = 0; f < n_files; ++f)
     {
         const StereoMatrix &audio = tracks[(size_t)f];
-        const StemTensor &out = outs[(size_t)f];
         std::filesystem::path p = std::filesystem::path(out_dir) / std::filesystem::path(argv[3 + f]).stem();
         std::filesystem::create_directories(p);
+        if (with_out_opts) // the bytes are WAV data already
+        {
+            const auto &po = pcm_outs[(size_t)f];
+            for (size_t target = 0; target < po.size(); ++target)
+            {
+                const std::string name = out_opts.two_stems < 0 ? names[target] : (target == 0 ? two_stems : "no_" + two_stems);
+                auto p_target = p / ("target_" + std::to_string(target) + "_" + name + ".wav");
+                std::cout << "Writing wav file " << p_target << std::endl;
+                if (!wavio::write_pcm_file(po[target].data(), audio.cols(), out_opts.encoding, p_target.string()))
+                {
+                    std::cerr << "Error writing " << p_target << std::endl;
+                    exit(1);
+                }
+            }
+            continue;
+        }
+        const StemTensor &out = outs[(size_t)f];
         std::vector<float> wave((size_t)(2 * audio.cols()));
         for (int target = 0; target < nb_sources; ++target)
         {

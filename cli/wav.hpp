@@ -3,7 +3,8 @@
 // the 8-bit G.711 companded encodings (A-law, mu-law; decode per ITU-T G.711, checked against Python's audioop),
 // skips unknown chunks (e.g. the LIST chunk of test/data/gspi_stereo*.wav), 44.1 kHz
 // mono (duplicated to both channels, demucs.cpp:56-64) or stereo only; writes stereo
-// float32 like the reference (PCM_FLT, demucs.cpp:100-102).
+// float32 like the reference (PCM_FLT, demucs.cpp:100-102), or, write_pcm_file, the 16-bit / 24-bit / float32 data chunk
+// that the PCM output stage encoded on the GPU, as it is.
 // Other sample rates are rejected with the reference's message (demucs.cpp:30-36) unless DMX_RESAMPLE=1 is set:
 // then the track is converted to 44.1 kHz on the GPU (dmx_resample) and the stems are
 // converted back and written at the file's own rate.
@@ -235,5 +236,32 @@ inline bool write_audio_file(const float *interleaved, int64_t N, const std::str
     fwrite(interleaved, 4, (size_t)(N * 2), f);
     fclose(f);
     return true;
+}
+
+// `data`: the bytes of a WAV data chunk as dmx_tracks_infer_pcm / demucs_inference_batch_pcm produce them (interleaved
+// stereo, little-endian; 24 bit packed in 3 bytes), written as they are behind the matching header: format tag 1 (PCM)
+// with 16 or 24 bits, tag 3 (IEEE float) with 32 bits. encoding: DMX_PCM_F32 / DMX_PCM_S16 / DMX_PCM_S24.
+inline bool write_pcm_file(const void *data, int64_t n_frames, int encoding, const std::string &filename, int rate = 44100)
+{
+    if (!data || n_frames < 0 || rate <= 0 || (encoding != DMX_PCM_F32 && encoding != DMX_PCM_S16 && encoding != DMX_PCM_S24))
+        return false;
+    const uint16_t tag = encoding == DMX_PCM_F32 ? 3 : 1, nch = 2;
+    const uint16_t bits = encoding == DMX_PCM_F32 ? 32 : encoding == DMX_PCM_S16 ? 16 : 24;
+    const uint16_t align = (uint16_t)(nch * bits / 8);
+    const uint64_t bytes = (uint64_t)n_frames * align;
+    if (bytes > 0xffffffffull - 44) // a RIFF chunk holds 32-bit sizes
+        return false;
+    FILE *f = fopen(filename.c_str(), "wb");
+    if (!f)
+        return false;
+    const uint32_t dataBytes = (uint32_t)bytes, urate = (uint32_t)rate, byteRate = urate * align, fmtLen = 16;
+    const uint32_t pad = dataBytes & 1, riffLen = 4 + (8 + fmtLen) + (8 + dataBytes + pad);
+    bool ok = fwrite("RIFF", 1, 4, f) == 4 && fwrite(&riffLen, 4, 1, f) == 1 && fwrite("WAVE", 1, 4, f) == 4 && fwrite("fmt ", 1, 4, f) == 4 &&
+              fwrite(&fmtLen, 4, 1, f) == 1 && fwrite(&tag, 2, 1, f) == 1 && fwrite(&nch, 2, 1, f) == 1 && fwrite(&urate, 4, 1, f) == 1 &&
+              fwrite(&byteRate, 4, 1, f) == 1 && fwrite(&align, 2, 1, f) == 1 && fwrite(&bits, 2, 1, f) == 1 && fwrite("data", 1, 4, f) == 4 &&
+              fwrite(&dataBytes, 4, 1, f) == 1 && fwrite(data, 1, dataBytes, f) == dataBytes;
+    if (ok && pad) // chunks are word-aligned (never the case for stereo: 4, 6 or 8 bytes per frame)
+        ok = fputc(0, f) != EOF;
+    return fclose(f) == 0 && ok;
 }
 } // namespace wavio

@@ -34,12 +34,24 @@ EXPORTS = [
     "dmx_ctx_create_gemm", "dmx_ctx_gemm", "dmx_default_gemm", "dmx_set_default_gemm", "dmx_debug_split_weights", "dmx_debug_split_activations", "dmx_debug_split_activations_fp16",
     "dmx_model_arch", "dmx_engine_arch", "dmx_engine_transport", "dmx_engine_set_finish", "dmx_engine_finish", "dmx_engine_root_ctx", "dmx_engine_track_infer", "dmx_engine_partition",
     "dmx_tracks_infer", "dmx_tracks_infer_opts", "dmx_track_geometry_overlap",
+    "dmx_output_count", "dmx_output_bytes", "dmx_tracks_infer_pcm", "dmx_pcm_encode_device", "dmx_pcm_encode",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
 GEMM_F32, GEMM_BF16X3, GEMM_FP16X3 = 0, 1, 2  # include/demucs_hip.h DMX_GEMM_* (FP16X3: opt-in, linear layers with fp16 terms)
 GEMM_NAMES = {GEMM_F32: "f32", GEMM_BF16X3: "bf16x3", GEMM_FP16X3: "fp16x3"}
 FINISH_ROOT, FINISH_OWNER = 0, 1
+PCM_F32, PCM_S16, PCM_S24 = 0, 1, 2  # include/demucs_hip.h DMX_PCM_*
+CLIP_NONE, CLIP_RESCALE, CLIP_CLAMP = 0, 1, 2  # DMX_CLIP_*
+
+
+class OutputSpec(ctypes.Structure):
+    """dmx_output_spec: encoding PCM_*, clip CLIP_*, stem -1 (all stems) or the stem of two-stems mode.
+    The defaults are demucs's: 16 bit, rescale, all stems."""
+    _fields_ = [("encoding", ctypes.c_int), ("clip", ctypes.c_int), ("stem", ctypes.c_int)]
+
+    def __init__(self, encoding=PCM_S16, clip=CLIP_RESCALE, stem=-1):
+        super().__init__(int(encoding), int(clip), int(stem))
 
 _lib = None
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_float, ctypes.c_char_p, ctypes.c_void_p)
@@ -94,6 +106,12 @@ def lib():
         L.dmx_tracks_infer.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp]
         L.dmx_tracks_infer_opts.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp]
         L.dmx_track_geometry_overlap.argtypes = [i64, i64, ci, ctypes.c_float, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
+        L.dmx_output_count.argtypes = [vp, vp]
+        L.dmx_output_bytes.argtypes = [vp, i64]
+        L.dmx_output_bytes.restype = i64
+        L.dmx_tracks_infer_pcm.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ci, vp, vp]
+        L.dmx_pcm_encode_device.argtypes = [ci, vp, ci, i64, i64, vp, vp, vp, vp]
+        L.dmx_pcm_encode.argtypes = [ci, vp, ci, i64, vp, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
         L.dmx_track_gather_device.argtypes = [vp, fp, i64, fp, ci, vp, ci, fp]
@@ -314,6 +332,39 @@ class Context:
                 o[...] = img.transpose(2, 1, 0)
         return out
 
+    def tracks_pcm(self, audios, spec: Optional[OutputSpec] = None, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None,
+                   progress=None, layout: int = LAYOUT_PLANAR, out=None):
+        """tracks_opts() whose stems leave the GPU as WAV data (dmx_tracks_infer_pcm): two-stems, clip mode and sample
+        format are applied on the device. Returns (outs, peaks): outs[t] is a list of n_out arrays, np.int16 (n, 2),
+        np.uint8 (n, 2, 3) (packed little-endian 24 bit) or np.float32 (n, 2); peaks[t] is an np.float32 (n_out,) array.
+        `out`: a list of np.uint8 buffers of n_out * output_bytes(spec, n_t) bytes to reuse (the results are views of them)."""
+        spec = spec if spec is not None else OutputSpec()
+        T = len(audios)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        n_out = lib().dmx_output_count(self.model.h, ctypes.byref(spec))
+        if n_out < 0:
+            raise DmxError(5, lib().dmx_last_error().decode(errors="replace"))
+        bufs = out if out is not None else [np.zeros(n_out * output_bytes(spec, n), np.uint8) for n in ns]
+        assert len(bufs) == T
+        for b, n in zip(bufs, ns):
+            assert b.dtype == np.uint8 and b.ndim == 1 and b.size == n_out * output_bytes(spec, n) and b.flags.c_contiguous
+        peaks = np.zeros((max(T, 1), n_out), np.float32)
+        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            assert arr.shape == (T, n_shifts), f"shift_offsets: expected shape {(T, n_shifts)}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        _chk(lib().dmx_tracks_infer_pcm(self.h, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec), op,
+                                        peaks.ctypes.data, layout, cbp, None))
+        return [pcm_views(b, spec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t] for t in range(T)]
+
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:
         ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         _chk(lib().dmx_track_geometry(self.h, n, shift_offset, ctypes.byref(ln), ctypes.byref(ns), ctypes.byref(st)))
@@ -369,6 +420,37 @@ def track_geometry(segment_samples: int, n: int, shift_offset: int, overlap: flo
     _chk(lib().dmx_track_geometry_overlap(segment_samples, n, shift_offset, float(overlap), ctypes.byref(ln), ctypes.byref(ns),
                                           ctypes.byref(st)))
     return ln.value, ns.value, st.value
+
+
+def output_bytes(spec: OutputSpec, n: int) -> int:
+    """bytes of one output of n frames under `spec` (dmx_output_bytes; no GPU); raises on an invalid spec"""
+    b = lib().dmx_output_bytes(ctypes.byref(spec), n)
+    if b < 0:
+        raise DmxError(5, lib().dmx_last_error().decode(errors="replace"))
+    return b
+
+
+def pcm_views(buf: np.ndarray, spec: OutputSpec, n: int, n_out: int) -> List[np.ndarray]:
+    """the n_out consecutive chunks of a dmx_tracks_infer_pcm / dmx_pcm_encode result as typed arrays (views of buf)"""
+    per = output_bytes(spec, n)
+    chunks = [buf[o * per:(o + 1) * per] for o in range(n_out)]
+    if spec.encoding == PCM_S16:
+        return [c.view("<i2").reshape(n, 2) for c in chunks]
+    if spec.encoding == PCM_S24:
+        return [c.reshape(n, 2, 3) for c in chunks]
+    return [c.view("<f4").reshape(n, 2) for c in chunks]
+
+
+def pcm_encode(planes: np.ndarray, spec: OutputSpec, device: int = 0):
+    """The PCM output stage alone (dmx_pcm_encode): planes (S, 2, n) float32 -> (list of n_out arrays as tracks_pcm, peaks)."""
+    planes = np.ascontiguousarray(planes, np.float32)
+    S, two, n = planes.shape
+    assert two == 2
+    n_out = S if spec.stem < 0 else 2
+    buf = np.zeros(max(n_out * max(lib().dmx_output_bytes(ctypes.byref(spec), n), 0), 1), np.uint8)
+    peaks = np.zeros(n_out, np.float32)
+    _chk(lib().dmx_pcm_encode(device, planes.ctypes.data, S, n, ctypes.byref(spec), buf.ctypes.data, peaks.ctypes.data))
+    return pcm_views(buf, spec, n, n_out), peaks
 
 
 def resample_length(n_in: int, rate_in: int, rate_out: int) -> int:

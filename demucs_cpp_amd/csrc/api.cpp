@@ -724,7 +724,7 @@ dmx_ctx::~dmx_ctx()
     {
         if (sl.copied)
             (void)hipEventDestroy(sl.copied);
-        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats})
+        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks})
             if (b->p)
                 (void)hipFree(b->p);
     }
@@ -1334,6 +1334,13 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
 //     A slot whose track finished in batch k-2 or earlier is taken over after a host wait on that track's copy-out event
 //     (its batch is long done).
 //   * A track is uploaded (and its statistics computed) when the first batch that needs it is enqueued.
+// The PCM output stage (dmx_tracks_infer_pcm, pcm.hip): with an output spec the overlap-add writes the slot in the planar
+// layout whatever the caller's layout, the peak kernel runs on every finished piece right behind its overlap-add, and the
+// encode kernel turns the planes into interleaved PCM in the slot's staging buffer: per piece when the clip mode needs no
+// peak, for the whole track behind its last piece with DMX_CLIP_RESCALE. Pieces are encoded in whole groups of 4 frames (the
+// up to 3 frames left over go with the next piece; the last piece ends at n), and each (output, piece) leaves in ONE copy.
+// A slot then also holds n_out encoded outputs of n_max frames (each rounded up to 16 bytes; at most the size of its fp32
+// result) and n_out peaks. Without a spec nothing of this exists: the same launches and copies as before.
 namespace
 {
 struct TrackJob
@@ -1357,6 +1364,18 @@ struct TrackItem
 {
     int t, k, g;
 };
+struct PcmOut // the output spec of a call, checked (pcm_check_spec)
+{
+    dmx_output_spec spec;
+    void *const *out;
+    float *peaks;
+    int nOut, frameBytes;
+};
+struct PcmRange // frames [lo, hi) of track t encoded behind one batch
+{
+    int t;
+    i64 lo, hi;
+};
 // item index of (row g, copy k) within a track (misc.hip ens_item)
 i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
 {
@@ -1378,8 +1397,10 @@ i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
 static i64 overlap_stride(i64 seg, float overlap) { return (i64)((1.0f - overlap) * (float)seg); }
 
 // shifts: T x N, row-major; N == 1 launches track_ola_kernel, N >= 2 track_ola_ens_kernel
+// pcm: NULL (fp32 results into out[t]), else the results leave as PCM (pcm->out[t]) and `out` is not used
 static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
-                      const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user)
+                      const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user,
+                      const PcmOut *pcm = nullptr)
 {
     HIPCHK(hipSetDevice(c->m->device));
     const int S = c->m->pm.n_sources, B = c->maxBatch;
@@ -1390,7 +1411,7 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
     for (int t = 0; t < T; ++t)
     {
         TrackJob &j = jobs[(size_t)t];
-        j.audio = audio[t], j.out = out[t], j.n = n[t], j.done = 0, j.slot = -1, j.c0 = t * N, j.m = 0;
+        j.audio = audio[t], j.out = out ? out[t] : nullptr, j.n = n[t], j.done = 0, j.slot = -1, j.c0 = t * N, j.m = 0;
         j.nMin = INT_MAX, j.nMax = 0;
         for (int k = 0; k < N; ++k)
         {
@@ -1484,6 +1505,11 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
             DMXCHK(dmx_ensure_buf(sl.tmp, 2 * nmax));
         DMXCHK(dmx_ensure_buf(sl.out, (i64)S * 2 * nmax));
         DMXCHK(dmx_ensure_buf(sl.stats, 4));
+        if (pcm)
+        {
+            DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(nmax * pcm->frameBytes) / 4)));
+            DMXCHK(dmx_ensure_buf(sl.peaks, 8));
+        }
         if (!sl.copied)
             HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
         sl.holder = -1;
@@ -1494,6 +1520,11 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
         HIPCHK(hipEventCreateWithFlags(&c->evUpload, hipEventDisableTiming));
     float *dMix = c->bMix.p, *ring = c->bSegOut.p;
     const int eigen = layout == DMX_LAYOUT_EIGEN ? 1 : 0;
+    const int olaEigen = pcm ? 0 : eigen; // the PCM stage reads planes
+    const bool wholeTrack = pcm && pcm->spec.clip == DMX_CLIP_RESCALE; // encode when the track's peak is complete
+    std::vector<std::vector<PcmRange>> pcmPlan(pcm ? (size_t)nBatches : 0);
+    std::vector<i64> pcmDone(pcm ? (size_t)T : 0, 0);
+    std::vector<PcmPiece> pcmPieces, pcmWhole;
 
     if (progress)
         progress(0.0f, "1., apply model w/ shift", user);
@@ -1502,12 +1533,29 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
     // the data has left the GPU, and the GPU must have its next batch queued by then.
     auto copy_piece = [&](int k) -> int {
         HIPCHK(hipStreamWaitEvent(c->copyStream, c->batchEvents[(size_t)k], 0));
+        if (pcm)
+            for (const PcmRange &r : pcmPlan[(size_t)k])
+            {
+                const TrackJob &j = jobs[(size_t)r.t];
+                const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
+                const bool last = r.hi == j.n;
+                const i64 lo = wholeTrack ? 0 : r.lo, fb = pcm->frameBytes;
+                const i64 outBytes = j.n * fb, devStride = DMX_OUTPUT_STRIDE(outBytes);
+                if (!wholeTrack || last)
+                    for (int o = 0; o < pcm->nOut; ++o)
+                        HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[r.t] + (size_t)(o * outBytes + lo * fb),
+                                              (const unsigned char *)sl.pcm.p + (size_t)(o * devStride + lo * fb), (size_t)((r.hi - lo) * fb),
+                                              hipMemcpyDeviceToHost, c->copyStream));
+                if (last && pcm->peaks)
+                    HIPCHK(hipMemcpyAsync(pcm->peaks + (size_t)r.t * pcm->nOut, sl.peaks.p, sizeof(float) * (size_t)pcm->nOut,
+                                          hipMemcpyDeviceToHost, c->copyStream));
+            }
         for (const TrackPiece &pc : plan[(size_t)k])
         {
             const TrackJob &j = jobs[(size_t)pc.t];
             const float *dOut = c->slots[(size_t)j.slot].out.p;
             const i64 i0 = pc.lo, i1 = pc.hi;
-            if (i1 > i0)
+            if (i1 > i0 && !pcm)
             {
                 if (eigen)
                     HIPCHK(hipMemcpyAsync(j.out + (size_t)i0 * 2 * S, dOut + (size_t)i0 * 2 * S, sizeof(float) * (size_t)(i1 - i0) * 2 * S,
@@ -1572,6 +1620,8 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
             if (sl.holder >= 0) // the previous holder's copy-out (and every kernel that read the slot) is done
                 HIPCHK(hipEventSynchronize(sl.copied));
             sl.holder = t, j.slot = pick;
+            if (pcm)
+                HIPCHK(hipMemsetAsync(sl.peaks.p, 0, sizeof(float) * (size_t)pcm->nOut, c->stream));
             if (eigen)
                 HIPCHK(hipMemcpyAsync(sl.audio.p, j.audio, sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
             else
@@ -1622,10 +1672,37 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
             }
         }
         if (N == 1)
-            launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, R, eigen, 0, 2 * S, c->stream);
+            launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, R, olaEigen, 0, 2 * S, c->stream);
         else
-            launch_track_ola_ens(ens.data(), ensCopies.data(), (int)ens.size(), N, ring, S, seg, stride, R, eigen, 0, 2 * S, c->stream);
+            launch_track_ola_ens(ens.data(), ensCopies.data(), (int)ens.size(), N, ring, S, seg, stride, R, olaEigen, 0, 2 * S, c->stream);
         HIPCHK(hipGetLastError());
+        if (pcm)
+        {
+            pcmPieces.clear(), pcmWhole.clear();
+            for (const TrackPiece &pc : plan[(size_t)k])
+            {
+                const TrackJob &j = jobs[(size_t)pc.t];
+                i64 &done = pcmDone[(size_t)pc.t];
+                const i64 hi = pc.hi == j.n ? j.n : pc.hi & ~(i64)3; // whole groups of 4 frames, except at the end of the track
+                if (hi <= done)
+                    continue;
+                const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
+                const PcmPiece pp{sl.out.p, (unsigned char *)sl.pcm.p, (unsigned *)sl.peaks.p, j.n, j.n,
+                                  DMX_OUTPUT_STRIDE(j.n * pcm->frameBytes), done, hi};
+                pcmPieces.push_back(pp);
+                if (hi == j.n)
+                {
+                    pcmWhole.push_back(pp);
+                    pcmWhole.back().i0 = 0;
+                }
+                pcmPlan[(size_t)k].push_back(PcmRange{pc.t, done, hi});
+                done = hi;
+            }
+            launch_pcm_peak(pcmPieces.data(), (int)pcmPieces.size(), S, pcm->spec.stem, c->stream);
+            const std::vector<PcmPiece> &enc = wholeTrack ? pcmWhole : pcmPieces;
+            launch_pcm_encode(enc.data(), (int)enc.size(), S, pcm->spec.stem, pcm->spec.encoding, pcm->spec.clip, c->stream);
+            HIPCHK(hipGetLastError());
+        }
         hipEvent_t ev = dmx_batch_event(c, (size_t)k);
         if (!ev)
             return fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
@@ -1710,11 +1787,10 @@ extern "C" int dmx_track_geometry_overlap(int64_t segment_samples, int64_t n, in
     return DMX_OK;
 }
 
-extern "C" int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts,
-                                     float overlap, const int *shift_offsets, float *const *out, int layout, dmx_progress_fn progress,
-                                     void *user)
+// the argument checks shared by dmx_tracks_infer_opts and dmx_tracks_infer_pcm (before any GPU work); gives the stride
+static int check_tracks_opts(const char *fn, dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts,
+                             float overlap, const int *shift_offsets, void *const *out, int layout, i64 &stride)
 {
-    const char *fn = "dmx_tracks_infer_opts";
     if (!c)
         return fail(DMX_ERR_ARG, "%s: null context", fn);
     if (n_tracks < 1)
@@ -1727,7 +1803,7 @@ extern "C" int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *cons
         return fail(DMX_ERR_ARG, "%s: n_shifts must be in [1, %d], got %d", fn, DMX_MAX_SHIFTS, n_shifts);
     if (!(overlap >= 0.0f && overlap <= DMX_MAX_OVERLAP))
         return fail(DMX_ERR_ARG, "%s: overlap %g not in [0, %g]", fn, (double)overlap, (double)DMX_MAX_OVERLAP);
-    const i64 stride = overlap_stride(c->seg, overlap);
+    stride = overlap_stride(c->seg, overlap);
     if (stride < 1)
         return fail(DMX_ERR_ARG, "%s: stride %lld < 1 (segment %lld, overlap %g)", fn, (long long)stride, (long long)c->seg, (double)overlap);
     const int N = n_shifts;
@@ -1746,10 +1822,133 @@ extern "C" int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *cons
                 return fail(DMX_ERR_ARG, "%s: track %d, shift %d: shift_offset %d not in [-1, %d)", fn, t, k, s, DMX_MAX_SHIFT);
         }
     }
+    return DMX_OK;
+}
+// drawn in (track, copy) order; N = 1: dmx_tracks_infer's order
+static std::vector<int> draw_shifts(int n_tracks, int N, const int *shift_offsets)
+{
     std::vector<int> shifts((size_t)n_tracks * N);
-    for (size_t i = 0; i < shifts.size(); ++i) // drawn in (track, copy) order; N = 1: dmx_tracks_infer's order
+    for (size_t i = 0; i < shifts.size(); ++i)
         shifts[i] = !shift_offsets || shift_offsets[i] < 0 ? rand() % DMX_MAX_SHIFT : shift_offsets[i];
-    return tracks_run(c, fn, n_tracks, audio, n, N, stride, shifts.data(), out, layout, progress, user);
+    return shifts;
+}
+
+extern "C" int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts,
+                                     float overlap, const int *shift_offsets, float *const *out, int layout, dmx_progress_fn progress,
+                                     void *user)
+{
+    const char *fn = "dmx_tracks_infer_opts";
+    i64 stride = 0;
+    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, reinterpret_cast<void *const *>(out), layout, stride));
+    const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
+    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), out, layout, progress, user);
+}
+
+// --------------------------------------------------------------------------- PCM output (pcm.hip)
+// the spec's own fields; S < 0: the model is not known yet (the stem's upper bound is checked once it is)
+static int pcm_check_spec(const char *fn, const dmx_output_spec *spec, int S)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: output spec: null", fn);
+    if (spec->encoding != DMX_PCM_F32 && spec->encoding != DMX_PCM_S16 && spec->encoding != DMX_PCM_S24)
+        return fail(DMX_ERR_ARG, "%s: output spec: encoding %d (DMX_PCM_F32 0, DMX_PCM_S16 1, DMX_PCM_S24 2)", fn, spec->encoding);
+    if (spec->clip != DMX_CLIP_NONE && spec->clip != DMX_CLIP_RESCALE && spec->clip != DMX_CLIP_CLAMP)
+        return fail(DMX_ERR_ARG, "%s: output spec: clip %d (DMX_CLIP_NONE 0, DMX_CLIP_RESCALE 1, DMX_CLIP_CLAMP 2)", fn, spec->clip);
+    if (spec->stem < -1)
+        return fail(DMX_ERR_ARG, "%s: output spec: stem %d (-1: all stems)", fn, spec->stem);
+    if (S >= 0 && spec->stem >= S)
+        return fail(DMX_ERR_ARG, "%s: output spec: stem %d of a %d-source model", fn, spec->stem, S);
+    return DMX_OK;
+}
+static int pcm_frame_bytes(int encoding) { return encoding == DMX_PCM_F32 ? 8 : encoding == DMX_PCM_S16 ? 4 : 6; }
+
+extern "C" int dmx_output_count(const dmx_model *m, const dmx_output_spec *spec)
+{
+    if (!m || pcm_check_spec("dmx_output_count", spec, m->pm.n_sources) != DMX_OK)
+        return -1;
+    return spec->stem < 0 ? m->pm.n_sources : 2;
+}
+extern "C" int64_t dmx_output_bytes(const dmx_output_spec *spec, int64_t n)
+{
+    if (n < 0 || pcm_check_spec("dmx_output_bytes", spec, -1) != DMX_OK)
+        return -1;
+    return n * pcm_frame_bytes(spec->encoding);
+}
+
+extern "C" int dmx_tracks_infer_pcm(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts, float overlap,
+                                    const int *shift_offsets, const dmx_output_spec *spec, void *const *out, float *peaks, int layout,
+                                    dmx_progress_fn progress, void *user)
+{
+    const char *fn = "dmx_tracks_infer_pcm";
+    DMXCHK(pcm_check_spec(fn, spec, -1));
+    i64 stride = 0;
+    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride));
+    const int S = c->m->pm.n_sources;
+    DMXCHK(pcm_check_spec(fn, spec, S));
+    const PcmOut pcm{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
+    const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
+    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
+}
+
+extern "C" int dmx_pcm_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                     const dmx_output_spec *spec, void *d_out, float *d_peaks, void *stream)
+{
+    const char *fn = "dmx_pcm_encode_device";
+    if (n_sources < 1 || n_sources > 64)
+        return fail(DMX_ERR_ARG, "%s: n_sources %d", fn, n_sources);
+    DMXCHK(pcm_check_spec(fn, spec, n_sources));
+    if (!d_planes || !d_out || !d_peaks)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_planes ? "d_planes" : !d_out ? "d_out" : "d_peaks");
+    if (n < 1 || plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n <= plane_stride)", fn, (long long)n, (long long)plane_stride);
+    if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_planes & 3) != 0 || ((uintptr_t)d_peaks & 3) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_out must be 16-byte aligned, d_planes and d_peaks 4-byte aligned", fn);
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nOut = spec->stem < 0 ? n_sources : 2;
+    HIPCHK(hipMemsetAsync(d_peaks, 0, sizeof(float) * (size_t)nOut, s));
+    const PcmPiece pp{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
+                      DMX_OUTPUT_STRIDE(n * pcm_frame_bytes(spec->encoding)), 0, n};
+    launch_pcm_peak(&pp, 1, n_sources, spec->stem, s);
+    launch_pcm_encode(&pp, 1, n_sources, spec->stem, spec->encoding, spec->clip, s);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_pcm_encode(int device, const float *planes, int n_sources, int64_t n, const dmx_output_spec *spec, void *out,
+                              float *peaks)
+{
+    const char *fn = "dmx_pcm_encode";
+    if (n_sources < 1 || n_sources > 64)
+        return fail(DMX_ERR_ARG, "%s: n_sources %d", fn, n_sources);
+    DMXCHK(pcm_check_spec(fn, spec, n_sources));
+    if (!planes || !out || n < 1)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer or n < 1)", fn);
+    HIPCHK(hipSetDevice(device));
+    const int nOut = spec->stem < 0 ? n_sources : 2;
+    const i64 bytes = n * pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
+    const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n;
+    float *dIn = nullptr, *dPeaks = nullptr;
+    unsigned char *dOut = nullptr;
+    int rc = DMX_OK;
+    if (hipMalloc((void **)&dIn, inBytes) != hipSuccess || hipMalloc((void **)&dOut, (size_t)(nOut * devStride)) != hipSuccess ||
+        hipMalloc((void **)&dPeaks, sizeof(float) * (size_t)nOut) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK && hipMemcpy(dIn, planes, inBytes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    if (rc == DMX_OK)
+        rc = dmx_pcm_encode_device(device, dIn, n_sources, n, n, spec, dOut, dPeaks, nullptr);
+    if (rc == DMX_OK && hipDeviceSynchronize() != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    for (int o = 0; rc == DMX_OK && o < nOut; ++o)
+        if (hipMemcpy((unsigned char *)out + (size_t)(o * bytes), dOut + (size_t)(o * devStride), (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    if (rc == DMX_OK && peaks && hipMemcpy(peaks, dPeaks, sizeof(float) * (size_t)nOut, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    for (void *p : {(void *)dIn, (void *)dOut, (void *)dPeaks})
+        if (p)
+            (void)hipFree(p);
+    return rc;
 }
 
 // --------------------------------------------------------------------------- debug

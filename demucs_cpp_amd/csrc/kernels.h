@@ -330,6 +330,29 @@ struct TrackEnsTable
 };
 void launch_track_ola_ens(const TrackEnsPiece *pieces, const TrackEnsCopy *copies, int P, int N, const float *segOut, int S,
                           i64 seg, i64 stride, i64 ring, int layout, int planeBase, int nPlanes, hipStream_t s);
+// ---- the PCM output stage (pcm.hip; specification: DESIGN.md section 2.8, restated in tests/pcm_spec.py) ----
+// S x 2 fp32 planes (plane p = stem*2 + channel at planes + p*planeStride) -> nOut outputs of interleaved stereo PCM.
+// stem < 0: output o is stem o; else output 0 is stem `stem` and output 1 the sum of the other stems in increasing order.
+// Output o's bytes start at pcm + o*outStride (outStride a multiple of 16, pcm 16-byte aligned: the kernel stores whole
+// dwords only, and the last dword of an odd 24-bit track ends in two zero bytes of that padding). A piece is the frames
+// [i0, i1) of one track: i0 a multiple of 4, i1 a multiple of 4 or n.
+struct PcmPiece
+{
+    const float *planes;
+    unsigned char *pcm;
+    unsigned *peaks; // nOut bit patterns of non-negative floats, zeroed before the track's first piece
+    i64 n, planeStride, outStride, i0, i1;
+};
+struct PcmTable
+{
+    static const int kMax = 32;
+    PcmPiece p[kMax];
+};
+// peaks[o] = max(peaks[o], largest |x| of output o over the piece, NaN ignored), per piece of the table
+void launch_pcm_peak(const PcmPiece *pieces, int P, int S, int stem, hipStream_t s);
+// clip (DMX_CLIP_*; rescale reads peaks[o]: every piece of the track must have been through launch_pcm_peak) and
+// quantisation (DMX_PCM_*) of the pieces' frames
+void launch_pcm_encode(const PcmPiece *pieces, int P, int S, int stem, int encoding, int clip, hipStream_t s);
 // dst[r*dpitch + i] = src[r*spitch + i], r < rows, i < width (floats)
 void launch_copy_rows(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width, int rows, hipStream_t s);
 // dst[i] = fp16 bit pattern of src[i], round to nearest even (the opt-in fp16 weight plane, api.cpp dmx_model_fp16_plane)

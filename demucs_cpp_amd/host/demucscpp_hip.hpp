@@ -12,7 +12,9 @@
 //   void  model_v3_inference(const demucs_v3_model&, demucs_v3_segment_buffers&, stft_buffers&, ...) :1410-1414
 // plus, with no reference counterpart (the reference's CLIs take one file), demucs_inference_batch /
 // demucs_v3_inference_batch: many tracks in one call, their segments sharing batches (dmx_tracks_infer), and their overloads
-// taking demucscpp::inference_options: demucs's shifts ensemble and segment overlap (dmx_tracks_infer_opts).
+// taking demucscpp::inference_options: demucs's shifts ensemble and segment overlap (dmx_tracks_infer_opts); and
+// demucs_inference_batch_pcm / demucs_v3_inference_batch_pcm with demucscpp::output_options: the stems as 16-bit / 24-bit /
+// float32 WAV data, two-stems and clip mode applied on the GPU (dmx_tracks_infer_pcm).
 //
 // Eigen is not required: the two tensor types below have exactly the memory image of
 // the reference's column-major Eigen::MatrixXf(2,N) and Eigen::Tensor3dXf(S,2,N), so a
@@ -293,6 +295,91 @@ inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model,
     return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb, opts);
 }
 
+// Stems as WAV-ready PCM, encoded on the GPU (dmx_tracks_infer_pcm): demucs's --two-stems, --clip-mode and --int24 /
+// --float32. The defaults are demucs's: 16 bit, rescale, all stems. two_stems: -1, or the index of the stem to isolate
+// (stem_index("vocals")): output 0 is that stem, output 1 the sum of the others.
+struct output_options
+{
+    int encoding = DMX_PCM_S16;
+    int clip = DMX_CLIP_RESCALE;
+    int two_stems = -1;
+};
+// drums 0, bass 1, other 2, vocals 3, guitar 4, piano 5 (the order of the stems in every result); -1: no such stem
+inline int stem_index(const std::string &name)
+{
+    static const char *names[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
+    for (int i = 0; i < 6; ++i)
+        if (name == names[i])
+            return i;
+    return -1;
+}
+// result[t][o]: the bytes of the WAV data chunk of output o of track t (interleaved stereo, little-endian, 24 bit packed)
+using PcmOutputs = std::vector<std::vector<std::vector<unsigned char>>>;
+namespace detail
+{
+inline PcmOutputs batch_call_pcm(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks, const ProgressCallback &cb,
+                                 const inference_options &opts, const output_options &oo, std::vector<std::vector<float>> *peaks)
+{
+    const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
+    PcmOutputs out(T);
+    if (T == 0)
+        return out;
+    std::vector<int> shifts(T * N, model.shift_offset);
+    if (opts.shift_offsets.size() == N)
+        for (size_t i = 0; i < shifts.size(); ++i)
+            shifts[i] = opts.shift_offsets[i % N];
+    else if (opts.shift_offsets.size() == T * N)
+        shifts = opts.shift_offsets;
+    else if (!opts.shift_offsets.empty())
+    {
+        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
+        std::exit(1);
+    }
+    const dmx_output_spec spec{oo.encoding, oo.clip, oo.two_stems};
+    CbThunk th{&cb};
+    std::lock_guard<std::mutex> guard(model.lock);
+    dmx_ctx *c = dmx_engine_root_ctx(model.engine, 0);
+    const int n_out = oo.two_stems < 0 ? dmx_engine_n_sources(model.engine) : 2;
+    std::vector<const float *> in(T);
+    std::vector<std::vector<unsigned char>> flat(T); // a track's outputs are consecutive across the ABI
+    std::vector<void *> dst(T);
+    std::vector<int64_t> n(T);
+    for (size_t t = 0; t < T; ++t)
+    {
+        in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
+        const int64_t per = dmx_output_bytes(&spec, n[t]);
+        if (per < 0)
+            die(who);
+        flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
+        dst[t] = flat[t].data();
+    }
+    std::vector<float> pk(T * (size_t)n_out, 0.0f);
+    if (!c || dmx_tracks_infer_pcm(c, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(), pk.data(),
+                                   DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
+        die(who);
+    for (size_t t = 0; t < T; ++t)
+    {
+        const size_t per = (size_t)dmx_output_bytes(&spec, n[t]);
+        for (int o = 0; o < n_out; ++o)
+            out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)(o + 1) * per);
+        flat[t] = std::vector<unsigned char>();
+    }
+    if (peaks)
+    {
+        peaks->assign(T, std::vector<float>());
+        for (size_t t = 0; t < T; ++t)
+            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
+    }
+    return out;
+}
+} // namespace detail
+inline PcmOutputs demucs_inference_batch_pcm(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                             const inference_options &opts, const output_options &out_opts,
+                                             std::vector<std::vector<float>> *peaks = nullptr)
+{
+    return detail::batch_call_pcm("demucs_inference_batch_pcm", model, tracks, cb, opts, out_opts, peaks);
+}
+
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
 // reference runs four demucs_inference calls back to back; calling demucs_inference on four demucs_model
 // objects still works here, but one bag engine deals all (model, segment) items over the devices at once
@@ -485,6 +572,14 @@ inline std::vector<StemTensor> demucs_v3_inference_batch(const demucs_v3_model &
                                                          ProgressCallback cb, const demucscpp::inference_options &opts)
 {
     return demucscpp::detail::batch_call("demucs_v3_inference_batch", model, 4, tracks, cb, opts);
+}
+
+inline demucscpp::PcmOutputs demucs_v3_inference_batch_pcm(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
+                                                           ProgressCallback cb, const demucscpp::inference_options &opts,
+                                                           const demucscpp::output_options &out_opts,
+                                                           std::vector<std::vector<float>> *peaks = nullptr)
+{
+    return demucscpp::detail::batch_call_pcm("demucs_v3_inference_batch_pcm", model, tracks, cb, opts, out_opts, peaks);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

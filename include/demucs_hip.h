@@ -177,6 +177,59 @@ extern "C"
     int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts, float overlap,
                               const int *shift_offsets, float *const *out, int layout, dmx_progress_fn progress, void *user);
 
+    /* ---- stems as WAV-ready PCM (csrc/pcm.hip; no reference counterpart: the reference writes float32 only,
+     * cli-apps/demucs.cpp:100-102). demucs's --two-stems, --clip-mode and --int24 / --float32 applied on the GPU to the
+     * finished fp32 track, so that what leaves the device is the exact content of a WAV `data` chunk: interleaved stereo
+     * L0 R0 L1 R1 ..., little-endian. 24-bit output is PACKED, 3 bytes per sample, not padded to 4: a WAV writer fwrites it
+     * as it is. Specification (restated in tests/pcm_spec.py), all fp32, v[s][c][i] = the value
+     * dmx_tracks_infer_opts writes for stem s, channel c, frame i:
+     *   outputs  stem = -1: the S stems. 0 <= stem < S (two-stems): output 0 = v[stem]; output 1 = the other stems added in
+     *            increasing order, starting from the first of them (demucs's `other_stem += source`).
+     *   peak     per output, the largest |x| over both channels and all frames, NaN ignored, 0 if there is none.
+     *   clip     DMX_CLIP_NONE y = x; DMX_CLIP_CLAMP y = x < -0.99f ? -0.99f : x > 0.99f ? 0.99f : x (a NaN stays one);
+     *            DMX_CLIP_RESCALE d = max(1.01f * peak, 1.0f), y = x / d, correctly rounded (demucs's prevent_clip).
+     *   encode   DMX_PCM_F32 y; DMX_PCM_S16 rint(y * 32768.0f) saturated to [-32768, 32767]; DMX_PCM_S24
+     *            rint(y * 8388608.0f) saturated to [-8388608, 8388607]; ties to even, NaN -> 0, +-inf saturates, no dither. */
+#define DMX_PCM_F32 0
+#define DMX_PCM_S16 1
+#define DMX_PCM_S24 2
+#define DMX_CLIP_NONE 0
+#define DMX_CLIP_RESCALE 1
+#define DMX_CLIP_CLAMP 2
+    typedef struct dmx_output_spec
+    {
+        int encoding, clip, stem; /* DMX_PCM_*, DMX_CLIP_*, -1 (all stems) or the stem of two-stems */
+    } dmx_output_spec;
+    /* number of outputs of a model under a spec: its number of sources, or 2 in two-stems mode; -1: invalid argument */
+    int dmx_output_count(const dmx_model *m, const dmx_output_spec *spec);
+    /* bytes of ONE output of n frames: n * 2 * {4, 2, 3}; pure host function; -1: invalid argument */
+    int64_t dmx_output_bytes(const dmx_output_spec *spec, int64_t n);
+    /* dmx_tracks_infer_opts whose result is WAV data. out[t]: n_out = dmx_output_count() consecutive chunks of
+     * dmx_output_bytes(spec, n[t]) bytes. peaks: NULL or the peaks (of the specification above, in every clip mode) of all
+     * outputs, n_out floats per track in track order. audio[t] in `layout` as before. The fp32 track is the bits of
+     * dmx_tracks_infer_opts with the same arguments, whatever max_batch and the other tracks of the call.
+     * With DMX_CLIP_NONE / DMX_CLIP_CLAMP a piece of a track is encoded and copied out as soon as it is final (one contiguous
+     * copy per output and piece); with DMX_CLIP_RESCALE the pieces' peaks accumulate and the track is encoded and copied out
+     * when its last piece is done. Device memory: as dmx_tracks_infer_opts, plus per track slot the encoded outputs
+     * (n_out x dmx_output_bytes(spec, n_max), each rounded up to 16 bytes: never more than the slot's fp32 result) and n_out
+     * peaks. Arguments are checked before any GPU work and nothing is written on error; a message about the spec names the
+     * field ("output spec: stem 7 of a 4-source model").
+     * The engine (several GPUs, the fine-tuned bag) is out of scope: dmx_engine_track_infer returns fp32. */
+    int dmx_tracks_infer_pcm(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts, float overlap,
+                             const int *shift_offsets, const dmx_output_spec *spec, void *const *out, float *peaks, int layout,
+                             dmx_progress_fn progress, void *user);
+    /* the stage alone on device memory (a building block, as dmx_resample_device): n_sources x 2 planes of n >= 1 floats,
+     * plane p = stem * 2 + channel at d_planes + p * plane_stride (plane_stride >= n; any alignment of the planes is handled).
+     * d_out: 16-byte aligned; output o starts at d_out + o * DMX_OUTPUT_STRIDE(dmx_output_bytes(spec, n)) - the kernels store
+     * whole dwords, and up to 15 bytes behind an output are padding (written or not). d_peaks: n_out floats (required: the
+     * rescale mode reads them back on the device). Enqueued on `stream` (hipStream_t, may be NULL). */
+#define DMX_OUTPUT_STRIDE(bytes) (((bytes) + 15) / 16 * 16)
+    int dmx_pcm_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                              const dmx_output_spec *spec, void *d_out, float *d_peaks, void *stream);
+    /* host buffers: planes [n_sources][2][n]; out: n_out consecutive chunks of dmx_output_bytes(spec, n); peaks NULL or n_out */
+    int dmx_pcm_encode(int device, const float *planes, int n_sources, int64_t n, const dmx_output_spec *spec, void *out,
+                       float *peaks);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
