@@ -1,6 +1,7 @@
 // demucs_batch.cpp.main — many tracks in one call (no reference counterpart: the reference's CLIs take one file):
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
-//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] <model file> <out dir> <wav file>...
+//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--bag-weights w00,w01,...]
+//                         <model> <out dir> <wav file>...
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
 // byte-identical to what demucs.cpp.main / demucs_v3.cpp.main writes for that input alone. The model's architecture
 // (HTDemucs v4 4s / 6s, or Demucs v3) is read from the file; the segments of all tracks share batches
@@ -19,6 +20,14 @@
 //   --int16 --int24 --float32  sample format of the files (these take no value)
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
 // They are refused for a track that DMX_RESAMPLE=1 converted: converting the stems back needs them in fp32.
+// <model> may also be a bag of models (dmx_tracks_infer_bag through the demucscpp::demucs_bag overloads; every option
+// above still applies, and every model gets the same offsets, from --shift-offsets or DMX_SHIFT_OFFSET):
+//   a directory              scanned as demucs_ft.cpp.main scans it (file names containing htdemucs_ft_{drums,bass,other,
+//                            vocals}): the fine-tuned bag, stem i from model i; every file byte-identical to what
+//                            demucs_ft.cpp.main writes for that input alone
+//   file1,file2,...          up to 8 models of one architecture, averaged with equal weights, or with
+//   --bag-weights w00,w01,.. the weight of (model q, stem s) at position q * stems + s: finite, >= 0, every stem with a
+//                            model and every model with a weight (a single model file may be given with it, too)
 // With N > 1, DMX_SHIFT_OFFSET is ambiguous without --shift-offsets and is refused. Without options the call and its output
 // are those of the plain batch call.
 #include <cerrno>
@@ -33,7 +42,8 @@ using namespace demucscpp;
 [[noreturn]] static void usage(const char *argv0)
 {
     std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
-              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] <model file> <out dir> <wav file>..." << std::endl;
+              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--bag-weights w00,w01,...]"
+              << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
 
@@ -50,8 +60,26 @@ static bool parse_int(const std::string &s, long lo, long hi, int &v)
     return true;
 }
 
+// a comma-separated list, strictly: an empty value (leading, doubled or trailing comma) is an error
+static bool split_list(const std::string &val, std::vector<std::string> &items)
+{
+    items.clear();
+    for (size_t pos = 0;;)
+    {
+        const size_t comma = val.find(',', pos);
+        items.push_back(val.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos));
+        if (items.back().empty())
+            return false;
+        if (comma == std::string::npos)
+            return true;
+        pos = comma + 1;
+    }
+}
+
 int main(int argc, const char **argv)
 {
+    std::vector<float> bag_weights;
+    bool with_bag_weights = false;
     inference_options opts;
     output_options out_opts; // demucs's defaults: 16 bit, rescale
     bool with_opts = false, with_out_opts = false;
@@ -88,6 +116,24 @@ int main(int argc, const char **argv)
             else
                 usage(argv[0]);
             with_out_opts = true;
+            continue;
+        }
+        if (opt == "--bag-weights")
+        {
+            std::vector<std::string> items;
+            if (!split_list(val, items))
+                usage(argv[0]);
+            bag_weights.clear();
+            for (const std::string &it : items)
+            {
+                char *end = nullptr;
+                errno = 0;
+                const float w = std::strtof(it.c_str(), &end);
+                if (errno || *end || !std::isfinite(w) || w < 0.0f)
+                    usage(argv[0]);
+                bag_weights.push_back(w);
+            }
+            with_bag_weights = true;
             continue;
         }
         with_opts = true;
@@ -140,7 +186,51 @@ int main(int argc, const char **argv)
     std::cout << "demucs_batch.cpp Main driver program (MI355X HIP path)" << std::endl;
     const std::string model_file = argv[1], out_dir = argv[2];
     const int n_files = argc - 3;
+    // a bag: a directory of fine-tuned models, a comma-separated list of files, or --bag-weights
+    std::vector<std::string> bag_files;
+    bool ft_dir = false;
+    {
+        std::error_code ec;
+        if (std::filesystem::is_directory(model_file, ec))
+        {
+            if (with_bag_weights)
+            {
+                std::cerr << "--bag-weights: a directory is the fine-tuned bag (stem i from model i) and takes no weights" << std::endl;
+                usage(argv[0]);
+            }
+            static const char *keys[4] = {"htdemucs_ft_drums", "htdemucs_ft_bass", "htdemucs_ft_other", "htdemucs_ft_vocals"};
+            static const char *ft_names[4] = {"drums", "bass", "other", "vocals"};
+            bag_files.assign(4, std::string());
+            bool have[4] = {false, false, false, false};
+            for (const auto &entry : std::filesystem::directory_iterator(model_file))
+                for (int i = 0; i < 4; ++i)
+                    if (!have[i] && entry.path().string().find(keys[i]) != std::string::npos)
+                    {
+                        bag_files[(size_t)i] = entry.path().string();
+                        std::cout << "Loading ft model " << entry.path().string() << " for " << ft_names[i] << std::endl;
+                        have[i] = true;
+                        break;
+                    }
+            for (int i = 0; i < 4; ++i)
+                if (!have[i])
+                {
+                    std::cerr << "Error: no model file containing '" << keys[i] << "' in " << model_file << std::endl;
+                    exit(1);
+                }
+            ft_dir = true;
+        }
+        else if (model_file.find(',') != std::string::npos || with_bag_weights)
+        {
+            if (!split_list(model_file, bag_files) || bag_files.size() > (size_t)DMX_MAX_BAG)
+            {
+                std::cerr << "<model>: a list of 1 to " << DMX_MAX_BAG << " model files separated by single commas" << std::endl;
+                usage(argv[0]);
+            }
+        }
+    }
+    const bool bag_mode = !bag_files.empty();
     int arch = 0;
+    if (!bag_mode)
     {
         const char *d = std::getenv("DMX_DEVICE");
         dmx_model *m = nullptr;
@@ -174,7 +264,46 @@ int main(int argc, const char **argv)
     std::vector<StemTensor> outs;
     PcmOutputs pcm_outs;
     int nb_sources = 4;
-    if (arch == 3)
+    if (bag_mode)
+    {
+        demucs_bag bag;
+        if (!load_demucs_bag(bag_files, &bag))
+        {
+            std::cerr << "Error loading model" << std::endl;
+            exit(1);
+        }
+        nb_sources = bag.nb_sources;
+        std::vector<float> weights; // empty: the diagonal
+        if (with_bag_weights)
+        {
+            if (bag_weights.size() != bag_files.size() * (size_t)nb_sources)
+            {
+                std::cerr << "--bag-weights: " << bag_weights.size() << " values for " << bag_files.size() << " models x " << nb_sources
+                          << " stems" << std::endl;
+                usage(argv[0]);
+            }
+            weights = bag_weights;
+        }
+        else if (!ft_dir)
+            weights.assign(bag_files.size() * (size_t)nb_sources, 1.0f);
+        if (dmx_bag_weights((int)bag_files.size(), nb_sources, weights.empty() ? nullptr : weights.data(), nullptr, nullptr) != DMX_OK)
+        {
+            std::cerr << dmx_last_error() << std::endl;
+            usage(argv[0]);
+        }
+        std::cout << "Starting Demucs bag (" << bag_files.size() << " models, " << nb_sources << "-source) inference of " << n_files
+                  << " tracks" << std::endl;
+        if (with_out_opts && out_opts.two_stems >= nb_sources)
+        {
+            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
+            exit(1);
+        }
+        if (with_out_opts)
+            pcm_outs = demucs_inference_batch_pcm(bag, tracks, cb, weights, opts, out_opts);
+        else
+            outs = demucs_inference_batch(bag, tracks, cb, weights, opts);
+    }
+    else if (arch == 3)
     {
         demucscpp_v3::demucs_v3_model model;
         if (!demucscpp_v3::load_demucs_v3_model(model_file, &model))

@@ -20,6 +20,7 @@ LAYOUT_EIGEN = 0
 LAYOUT_PLANAR = 1
 SEGMENT_SAMPLES = 343980
 MAX_SHIFT = 22050
+MAX_BAG = 8  # include/demucs_hip.h DMX_MAX_BAG (and n_models * n_shifts <= 256)
 
 # every symbol include/demucs_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -35,6 +36,7 @@ EXPORTS = [
     "dmx_model_arch", "dmx_engine_arch", "dmx_engine_transport", "dmx_engine_set_finish", "dmx_engine_finish", "dmx_engine_root_ctx", "dmx_engine_track_infer", "dmx_engine_partition",
     "dmx_tracks_infer", "dmx_tracks_infer_opts", "dmx_track_geometry_overlap",
     "dmx_output_count", "dmx_output_bytes", "dmx_tracks_infer_pcm", "dmx_pcm_encode_device", "dmx_pcm_encode",
+    "dmx_bag_weights", "dmx_tracks_infer_bag",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -112,6 +114,8 @@ def lib():
         L.dmx_tracks_infer_pcm.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ci, vp, vp]
         L.dmx_pcm_encode_device.argtypes = [ci, vp, ci, i64, i64, vp, vp, vp, vp]
         L.dmx_pcm_encode.argtypes = [ci, vp, ci, i64, vp, vp, vp]
+        L.dmx_bag_weights.argtypes = [ci, ci, vp, vp, vp]
+        L.dmx_tracks_infer_bag.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
         L.dmx_track_gather_device.argtypes = [vp, fp, i64, fp, ci, vp, ci, fp]
@@ -365,6 +369,59 @@ class Context:
                                         peaks.ctypes.data, layout, cbp, None))
         return [pcm_views(b, spec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t] for t in range(T)]
 
+    def tracks_bag(self, models, audios, weights=None, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None,
+                   spec: Optional[OutputSpec] = None, progress=None, layout: int = LAYOUT_PLANAR, out=None):
+        """Several tracks through a bag of models in ONE call (dmx_tracks_infer_bag): `models` are Model objects of this
+        context's architecture, `weights` None (the diagonal, fine-tuned bag: stem i from model i) or a (Q, S) matrix of
+        weights >= 0 (equal weights: an ensemble). shift_offsets: None or an int array of shape (T, Q, n_shifts), -1
+        entries drawn as rand() % 22050 in that row-major order. spec None: a list of (S, 2, n_t) float32 arrays as
+        tracks_opts(); else (outs, peaks) as tracks_pcm(). The context stays bound to its own model."""
+        T, Q = len(audios), len(models)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models])
+        wp = None
+        if weights is not None:
+            warr = np.ascontiguousarray(weights, np.float32)
+            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
+            wp = warr.ctypes.data
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            assert arr.shape == (T, Q, n_shifts), f"shift_offsets: expected shape {(T, Q, n_shifts)}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        if spec is not None:
+            n_out = lib().dmx_output_count(self.model.h, ctypes.byref(spec))
+            if n_out < 0:
+                raise DmxError(5, lib().dmx_last_error().decode(errors="replace"))
+            bufs = out if out is not None else [np.zeros(n_out * output_bytes(spec, n), np.uint8) for n in ns]
+            assert len(bufs) == T
+            for b, n in zip(bufs, ns):
+                assert b.dtype == np.uint8 and b.ndim == 1 and b.size == n_out * output_bytes(spec, n) and b.flags.c_contiguous
+            peaks = np.zeros((max(T, 1), n_out), np.float32)
+            op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
+            _chk(lib().dmx_tracks_infer_bag(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec), op,
+                                            peaks.ctypes.data, layout, cbp, None))
+            return [pcm_views(b, spec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t] for t in range(T)]
+        if out is None:
+            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
+        assert len(out) == T
+        for o, n in zip(out, ns):
+            assert o.shape == (self.S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
+        dst = [np.zeros((n, 2, self.S), np.float32) for n in ns] if layout == LAYOUT_EIGEN else out
+        op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
+        _chk(lib().dmx_tracks_infer_bag(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, None, op, None, layout,
+                                        cbp, None))
+        if layout == LAYOUT_EIGEN:
+            for o, img in zip(out, dst):
+                o[...] = img.transpose(2, 1, 0)
+        return out
+
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:
         ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         _chk(lib().dmx_track_geometry(self.h, n, shift_offset, ctypes.byref(ln), ctypes.byref(ns), ctypes.byref(st)))
@@ -420,6 +477,22 @@ def track_geometry(segment_samples: int, n: int, shift_offset: int, overlap: flo
     _chk(lib().dmx_track_geometry_overlap(segment_samples, n, shift_offset, float(overlap), ctypes.byref(ln), ctypes.byref(ns),
                                           ctypes.byref(st)))
     return ln.value, ns.value, st.value
+
+
+def bag_weights(n_models: int, n_sources: int, weights=None):
+    """(effective weights (Q, S), their fp32 column sums (S,)) of a bag (dmx_bag_weights; no GPU): weights None is the
+    diagonal and needs n_models == n_sources; raises DmxError on an invalid matrix."""
+    wp = None
+    if weights is not None:
+        warr = np.ascontiguousarray(weights, np.float32)
+        assert warr.shape == (n_models, n_sources), f"weights: expected shape {(n_models, n_sources)}, got {warr.shape}"
+        wp = warr.ctypes.data
+    eff = np.zeros((max(n_models, 1), max(n_sources, 1)), np.float32)
+    sums = np.zeros(max(n_sources, 1), np.float32)
+    big = np.zeros((MAX_BAG, 8), np.float32)  # the library writes at most n_models x n_sources, both checked first
+    _chk(lib().dmx_bag_weights(int(n_models), int(n_sources), wp, big.ctypes.data, sums.ctypes.data if n_sources <= sums.size else None))
+    eff[...] = big.ravel()[:n_models * n_sources].reshape(n_models, n_sources)
+    return eff, sums
 
 
 def output_bytes(spec: OutputSpec, n: int) -> int:

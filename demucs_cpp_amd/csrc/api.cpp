@@ -1341,14 +1341,29 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
 // up to 3 frames left over go with the next piece; the last piece ends at n), and each (output, piece) leaves in ONE copy.
 // A slot then also holds n_out encoded outputs of n_max frames (each rounded up to 16 bytes; at most the size of its fp32
 // result) and n_out peaks. Without a spec nothing of this exists: the same launches and copies as before.
+// A bag of Q models (dmx_tracks_infer_bag): the call has a model dimension. A track is uploaded once
+// and its statistics are computed once; model q's items are the (track, row, copy) sequence above for its own shifts, in a
+// sequence and a ring of its own (each ring sized by the rule above from the reach of the overlap-adds into THAT model's
+// items); a batch holds items of one model, and the context is rebound (dmx_ctx_set_model) between batches. The next batch
+// is always dealt from the model that lags furthest behind - the one whose next item has the lowest (track, row), the lowest
+// q on a tie - so the models advance through the tracks abreast (round-robin when their shifts agree) and no ring has to
+// span more than the other models' batch in flight: the memory bound stays independent of the number and length of tracks.
+// A piece is final when every copy of every model has covered it; one launch of track_ola_bag_kernel combines the rings, and
+// the peak / encode stage and the copy-out follow unchanged. One model through the old entry points (no bag) is the
+// sequence of launches it was.
 namespace
 {
 struct TrackJob
 {
     const float *audio;
     float *out;
-    i64 n, g0, m, done; // g0: global index of the track's first item; m: its items (the sum of its copies' segment counts)
-    int c0, nMin, nMax, kFirst, kLast, slot; // c0: its first copy; nMin / nMax: the fewest / most segments of a copy
+    i64 n, done;
+    int kFirst, kLast, slot; // the first / last batch (of any model) holding an item of the track
+};
+struct TrackModel // one model's items of one track
+{
+    i64 g0, m; // g0: index of the track's first item in the model's sequence; m: its items (the sum of its copies' segment counts)
+    int c0, nMin, nMax; // c0: its first copy; nMin / nMax: the fewest / most segments of a copy
 };
 struct TrackCopy
 {
@@ -1358,11 +1373,24 @@ struct TrackCopy
 struct TrackPiece
 {
     int t;
-    i64 lo, hi, itemLo; // itemLo: the first item (within the track) the piece's overlap-add reads
+    i64 lo, hi;
+    size_t item0; // pieceItems[item0 + q]: the first item (within the track, of model q) the piece's overlap-add reads
 };
 struct TrackItem
 {
     int t, k, g;
+};
+struct TrackBatch
+{
+    int q;  // the model
+    i64 g0; // its first item, in the model's sequence
+    int nb;
+};
+struct BagRun // the models of a call and their effective weights [Q][S] (dmx_bag_weights)
+{
+    const dmx_model *const *models;
+    int Q;
+    const float *w;
 };
 struct PcmOut // the output spec of a call, checked (pcm_check_spec)
 {
@@ -1396,93 +1424,174 @@ i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
 // stride = (int)((1 - overlap) * segment), evaluated in fp32 (model_apply.cpp:162)
 static i64 overlap_stride(i64 seg, float overlap) { return (i64)((1.0f - overlap) * (float)seg); }
 
-// shifts: T x N, row-major; N == 1 launches track_ola_kernel, N >= 2 track_ola_ens_kernel
+// shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches track_ola_kernel and N >= 2
+// track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
 // pcm: NULL (fp32 results into out[t]), else the results leave as PCM (pcm->out[t]) and `out` is not used
-static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
-                      const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user,
-                      const PcmOut *pcm = nullptr)
+static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
+                           const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user, const PcmOut *pcm,
+                           const BagRun *bag)
 {
     HIPCHK(hipSetDevice(c->m->device));
-    const int S = c->m->pm.n_sources, B = c->maxBatch;
+    const int S = c->m->pm.n_sources, B = c->maxBatch, Q = bag ? bag->Q : 1;
     const i64 seg = c->seg, blk = (i64)S * 2 * seg;
     std::vector<TrackJob> jobs((size_t)T);
-    std::vector<TrackCopy> copies((size_t)T * N);
-    i64 M = 0, nmax = 0;
+    std::vector<TrackModel> tm((size_t)T * Q);
+    std::vector<TrackCopy> copies((size_t)T * Q * N);
+    std::vector<i64> M((size_t)Q, 0);
+    i64 Mtot = 0, nmax = 0;
     for (int t = 0; t < T; ++t)
     {
         TrackJob &j = jobs[(size_t)t];
-        j.audio = audio[t], j.out = out ? out[t] : nullptr, j.n = n[t], j.done = 0, j.slot = -1, j.c0 = t * N, j.m = 0;
-        j.nMin = INT_MAX, j.nMax = 0;
-        for (int k = 0; k < N; ++k)
+        j.audio = audio[t], j.out = out ? out[t] : nullptr, j.n = n[t], j.done = 0, j.slot = -1, j.kFirst = INT_MAX, j.kLast = -1;
+        for (int q = 0; q < Q; ++q)
         {
-            TrackCopy &cp = copies[(size_t)(j.c0 + k)];
-            cp.shift = shifts[j.c0 + k], cp.segDone = 0;
-            cp.len = j.n + DMX_MAX_SHIFT - cp.shift; // dmx_track_geometry_overlap
-            cp.nseg = (int)((cp.len + stride - 1) / stride);
-            j.nMin = std::min(j.nMin, cp.nseg), j.nMax = std::max(j.nMax, cp.nseg);
-            j.m += cp.nseg;
+            TrackModel &x = tm[(size_t)t * Q + q];
+            x.c0 = (t * Q + q) * N, x.m = 0, x.nMin = INT_MAX, x.nMax = 0;
+            for (int k = 0; k < N; ++k)
+            {
+                TrackCopy &cp = copies[(size_t)(x.c0 + k)];
+                cp.shift = shifts[x.c0 + k], cp.segDone = 0;
+                cp.len = j.n + DMX_MAX_SHIFT - cp.shift; // dmx_track_geometry_overlap
+                cp.nseg = (int)((cp.len + stride - 1) / stride);
+                x.nMin = std::min(x.nMin, cp.nseg), x.nMax = std::max(x.nMax, cp.nseg);
+                x.m += cp.nseg;
+            }
+            if (!bag && (x.nMax - x.nMin) * N > TrackEnsTable::kMaxTail) // cannot happen for a context's segment (>= 4096) and overlap <= 0.9
+                return fail(DMX_ERR_ARG, "%s: internal error (track %d: %d tail rows x %d shifts)", fn, t, x.nMax - x.nMin, N);
+            if (x.m > INT_MAX / 2)
+                return fail(DMX_ERR_ARG, "%s: track %d: too many segments (%lld)", fn, t, (long long)x.m);
+            x.g0 = M[(size_t)q];
+            M[(size_t)q] += x.m;
         }
-        if ((j.nMax - j.nMin) * N > TrackEnsTable::kMaxTail) // cannot happen for a context's segment (>= 4096) and overlap <= 0.9
-            return fail(DMX_ERR_ARG, "%s: internal error (track %d: %d tail rows x %d shifts)", fn, t, j.nMax - j.nMin, N);
-        j.g0 = M;
-        M += j.m;
-        j.kFirst = (int)(j.g0 / B), j.kLast = (int)((M - 1) / B);
         nmax = std::max(nmax, j.n);
     }
-    std::vector<TrackItem> items;
-    items.reserve((size_t)M);
-    for (int t = 0; t < T; ++t)
-        for (int g = 0; g < jobs[(size_t)t].nMax; ++g)
-            for (int k = 0; k < N; ++k)
-                if (g < copies[(size_t)(t * N + k)].nseg)
-                    items.push_back(TrackItem{t, k, g});
-    const int nBatches = (int)((M + B - 1) / B);
-
-    // plan (host only): the pieces each batch makes final, and the ring they need
-    std::vector<std::vector<TrackPiece>> plan((size_t)nBatches);
-    i64 reach = 0;
+    if (bag)
     {
+        // every cap of track_ola_bag_kernel (copies per piece, tail entries, LDS), on the tracks' whole tails
+        std::vector<TrackBagModel> whole((size_t)T * Q);
+        for (size_t i = 0; i < whole.size(); ++i)
+            whole[i] = TrackBagModel{0, 0, tm[i].nMin, tm[i].nMax - tm[i].nMin};
+        if (track_ola_bag_tail_entries(whole.data(), T, Q, N, S, bag->w) < 0)
+            return fail(DMX_ERR_ARG,
+                        "%s: the bag does not fit the overlap-add kernel (%d models x %d shifts of at most %d, %d stems of at most %d, or "
+                        "more than %d uneven tail rows x copies of one track and stem)",
+                        fn, Q, N, TrackBagTable::kMaxCopies, S, TrackBagTable::kMaxStems, TrackBagTable::kMaxTail);
+    }
+    std::vector<std::vector<TrackItem>> items((size_t)Q);
+    for (int q = 0; q < Q; ++q)
+    {
+        items[(size_t)q].reserve((size_t)M[(size_t)q]);
+        for (int t = 0; t < T; ++t)
+        {
+            const TrackModel &x = tm[(size_t)t * Q + q];
+            for (int g = 0; g < x.nMax; ++g)
+                for (int k = 0; k < N; ++k)
+                    if (g < copies[(size_t)(x.c0 + k)].nseg)
+                        items[(size_t)q].push_back(TrackItem{t, k, g});
+        }
+        Mtot += M[(size_t)q];
+    }
+    // the batches: each of one model, dealt from the model whose next item is the earliest (track, row)
+    std::vector<TrackBatch> batches;
+    std::vector<i64> cum; // items done after batch k, over all models
+    {
+        std::vector<i64> pos((size_t)Q, 0);
+        i64 all = 0;
+        for (;;)
+        {
+            int pick = -1;
+            for (int q = 0; q < Q; ++q)
+            {
+                if (pos[(size_t)q] >= M[(size_t)q])
+                    continue;
+                if (pick < 0)
+                {
+                    pick = q;
+                    continue;
+                }
+                const TrackItem &a = items[(size_t)q][(size_t)pos[(size_t)q]], &b = items[(size_t)pick][(size_t)pos[(size_t)pick]];
+                if (a.t < b.t || (a.t == b.t && a.g < b.g))
+                    pick = q;
+            }
+            if (pick < 0)
+                break;
+            const i64 g0 = pos[(size_t)pick];
+            const int nb = (int)std::min<i64>(B, M[(size_t)pick] - g0);
+            const int k = (int)batches.size();
+            for (i64 g = g0; g < g0 + nb; ++g)
+            {
+                TrackJob &j = jobs[(size_t)items[(size_t)pick][(size_t)g].t];
+                j.kFirst = std::min(j.kFirst, k), j.kLast = std::max(j.kLast, k);
+            }
+            batches.push_back(TrackBatch{pick, g0, nb});
+            cum.push_back(all += nb);
+            pos[(size_t)pick] += nb;
+        }
+    }
+    const int nBatches = (int)batches.size();
+
+    // plan (host only): the pieces each batch makes final, and the rings they need
+    std::vector<std::vector<TrackPiece>> plan((size_t)nBatches);
+    std::vector<i64> pieceItems;
+    std::vector<i64> reach((size_t)Q, 0);
+    {
+        std::vector<i64> dealt((size_t)Q, 0);
         int tLo = 0;
         for (int k = 0; k < nBatches; ++k)
         {
-            const i64 g0 = (i64)k * B, nb = std::min<i64>(B, M - g0);
+            const TrackBatch &bt = batches[(size_t)k];
             while (jobs[(size_t)tLo].kLast < k)
                 ++tLo;
-            for (i64 g = g0; g < g0 + nb; ++g)
-                ++copies[(size_t)(jobs[(size_t)items[(size_t)g].t].c0 + items[(size_t)g].k)].segDone;
+            for (i64 g = bt.g0; g < bt.g0 + bt.nb; ++g)
+            {
+                const TrackItem &it = items[(size_t)bt.q][(size_t)g];
+                ++copies[(size_t)(tm[(size_t)it.t * Q + bt.q].c0 + it.k)].segDone;
+            }
+            dealt[(size_t)bt.q] = bt.g0 + bt.nb;
             for (int t = tLo; t < T && jobs[(size_t)t].kFirst <= k; ++t)
             {
                 TrackJob &j = jobs[(size_t)t];
-                const TrackCopy *cp = &copies[(size_t)j.c0];
+                const TrackCopy *all = &copies[(size_t)t * Q * N];
                 // shifted-track positions below (segments done)*stride are covered only by segments done
                 i64 fin = j.n;
-                for (int q = 0; q < N; ++q)
-                    if (cp[q].segDone < cp[q].nseg)
-                        fin = std::min<i64>(fin, (i64)cp[q].segDone * stride - (DMX_MAX_SHIFT - cp[q].shift));
+                for (int x = 0; x < Q * N; ++x)
+                    if (all[x].segDone < all[x].nseg)
+                        fin = std::min<i64>(fin, (i64)all[x].segDone * stride - (DMX_MAX_SHIFT - all[x].shift));
                 fin = std::max<i64>(j.done, fin);
-                TrackPiece pc{t, j.done, fin, 0};
-                if (fin > j.done)
+                TrackPiece pc{t, j.done, fin, pieceItems.size()};
+                pieceItems.resize(pieceItems.size() + (size_t)Q, 0);
+                for (int q = 0; q < Q && fin > j.done; ++q)
                 {
-                    pc.itemLo = INT64_MAX;
-                    i64 itemHi = -1;
-                    for (int q = 0; q < N; ++q)
+                    const TrackModel &x = tm[(size_t)t * Q + q];
+                    const TrackCopy *cp = &copies[(size_t)x.c0];
+                    i64 itemLo = INT64_MAX, itemHi = -1;
+                    for (int r = 0; r < N; ++r)
                     {
-                        const i64 j0 = j.done + DMX_MAX_SHIFT - cp[q].shift; // first shifted position of the piece: its first segment
+                        const i64 j0 = j.done + DMX_MAX_SHIFT - cp[r].shift; // first shifted position of the piece: its first segment
                         const i64 gLo = j0 - seg + 1 <= 0 ? 0 : (j0 - seg + stride) / stride;
-                        const i64 gHi = std::min<i64>(cp[q].nseg - 1, (fin - 1 + DMX_MAX_SHIFT - cp[q].shift) / stride); // its last
-                        pc.itemLo = std::min(pc.itemLo, track_item(cp, N, j.nMin, gLo, q));
-                        itemHi = std::max(itemHi, track_item(cp, N, j.nMin, gHi, q));
+                        const i64 gHi = std::min<i64>(cp[r].nseg - 1, (fin - 1 + DMX_MAX_SHIFT - cp[r].shift) / stride); // its last
+                        itemLo = std::min(itemLo, track_item(cp, N, x.nMin, gLo, r));
+                        itemHi = std::max(itemHi, track_item(cp, N, x.nMin, gHi, r));
                     }
-                    if (pc.itemLo < 0 || itemHi >= g0 + nb - j.g0) // every segment the piece reads must be done
-                        return fail(DMX_ERR_ARG, "%s: internal error (track %d reads item %lld after batch %d)", fn, t, (long long)itemHi, k);
-                    reach = std::max(reach, g0 + nb - (j.g0 + pc.itemLo));
+                    if (itemLo < 0 || itemHi >= dealt[(size_t)q] - x.g0) // every segment the piece reads must be done
+                        return fail(DMX_ERR_ARG, "%s: internal error (track %d reads item %lld of model %d after batch %d)", fn, t,
+                                    (long long)itemHi, q, k);
+                    pieceItems[pc.item0 + (size_t)q] = itemLo;
+                    reach[(size_t)q] = std::max(reach[(size_t)q], dealt[(size_t)q] - (x.g0 + itemLo));
                 }
                 plan[(size_t)k].push_back(pc);
                 j.done = fin;
             }
         }
     }
-    const i64 R = std::min<i64>(M, std::max<i64>(2 * (i64)B, (reach + B - 1) / B * B));
+    std::vector<i64> R((size_t)Q), ringOff((size_t)Q);
+    i64 ringBlocks = 0;
+    for (int q = 0; q < Q; ++q)
+    {
+        R[(size_t)q] = std::min<i64>(M[(size_t)q], std::max<i64>(2 * (i64)B, (reach[(size_t)q] + B - 1) / B * B));
+        ringOff[(size_t)q] = ringBlocks;
+        ringBlocks += R[(size_t)q];
+    }
     // slots: track t is held during batches [kFirst, kLast + 1]
     int nSlots = 0;
     {
@@ -1494,7 +1603,7 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
             nSlots = std::max(nSlots, live += diff[(size_t)k]);
     }
     DMXCHK(dmx_ensure_buf(c->bMix, 2 * seg * B));
-    DMXCHK(dmx_ensure_buf(c->bSegOut, R * blk));
+    DMXCHK(dmx_ensure_buf(c->bSegOut, ringBlocks * blk));
     if ((int)c->slots.size() < nSlots)
         c->slots.resize((size_t)nSlots);
     for (int i = 0; i < nSlots; ++i)
@@ -1518,7 +1627,10 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
         HIPCHK(hipStreamCreateWithFlags(&c->uploadStream, hipStreamNonBlocking));
     if (!c->evUpload)
         HIPCHK(hipEventCreateWithFlags(&c->evUpload, hipEventDisableTiming));
-    float *dMix = c->bMix.p, *ring = c->bSegOut.p;
+    float *dMix = c->bMix.p;
+    std::vector<const float *> rings((size_t)Q);
+    for (int q = 0; q < Q; ++q)
+        rings[(size_t)q] = c->bSegOut.p + ringOff[(size_t)q] * blk;
     const int eigen = layout == DMX_LAYOUT_EIGEN ? 1 : 0;
     const int olaEigen = pcm ? 0 : eigen; // the PCM stage reads planes
     const bool wholeTrack = pcm && pcm->spec.clip == DMX_CLIP_RESCALE; // encode when the track's peak is complete
@@ -1570,12 +1682,12 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
         }
         if (progress)
         {
-            const i64 g0 = (i64)k * B, nb = std::min<i64>(B, M - g0);
+            const i64 hi = cum[(size_t)k], lo = hi - batches[(size_t)k].nb;
             HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
             char msg[128];
-            snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %lld..%lld of %lld", (long long)g0, (long long)(g0 + nb - 1),
-                     (long long)M);
-            progress((float)(g0 + nb) / (float)M, msg, user);
+            snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %lld..%lld of %lld", (long long)lo, (long long)(hi - 1),
+                     (long long)Mtot);
+            progress((float)hi / (float)Mtot, msg, user);
         }
         return DMX_OK;
     };
@@ -1584,10 +1696,16 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
     std::vector<TrackOlaEntry> ola;
     std::vector<TrackEnsPiece> ens;
     std::vector<TrackEnsCopy> ensCopies;
+    std::vector<TrackBagPiece> bagPieces;
+    std::vector<TrackBagModel> bagModels;
     int tLo = 0; // first track of the current batch
     for (int k = 0; k < nBatches; ++k)
     {
-        const i64 g0 = (i64)k * B, nb = std::min<i64>(B, M - g0);
+        const TrackBatch &bt = batches[(size_t)k];
+        const std::vector<TrackItem> &its = items[(size_t)bt.q];
+        const i64 g0 = bt.g0, nb = bt.nb, Rq = R[(size_t)bt.q];
+        if (bag)
+            DMXCHK(dmx_ctx_set_model(c, bag->models[bt.q]));
         while (jobs[(size_t)tLo].kLast < k)
             ++tLo;
         int tHi = tLo; // one past the last track of the batch
@@ -1639,42 +1757,63 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
                 nSt = 0;
             }
         }
-        // gather the batch: global items [g0, g0 + nb)
+        // gather the batch: the model's items [g0, g0 + nb)
         for (i64 g = g0; g < g0 + nb; ++g)
         {
-            const TrackItem &it = items[(size_t)g];
+            const TrackItem &it = its[(size_t)g];
             const TrackJob &j = jobs[(size_t)it.t];
             const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-            batchItems[(size_t)(g - g0)] = TrackSegItem{sl.audio.p, sl.stats.p, j.n, copies[(size_t)(j.c0 + it.k)].shift, it.g};
+            batchItems[(size_t)(g - g0)] =
+                TrackSegItem{sl.audio.p, sl.stats.p, j.n, copies[(size_t)(tm[(size_t)it.t * Q + bt.q].c0 + it.k)].shift, it.g};
         }
         launch_track_gather(batchItems.data(), (int)nb, seg, stride, dMix, c->stream);
         HIPCHK(hipGetLastError());
-        DMXCHK(dmx_segment_infer_device(c, dMix, ring + (g0 % R) * blk, (int)nb));
+        DMXCHK(dmx_segment_infer_device(c, dMix, const_cast<float *>(rings[(size_t)bt.q]) + (g0 % Rq) * blk, (int)nb));
         // finish what this batch makes final
-        ola.clear(), ens.clear(), ensCopies.clear();
+        ola.clear(), ens.clear(), ensCopies.clear(), bagPieces.clear(), bagModels.clear();
         for (const TrackPiece &pc : plan[(size_t)k])
         {
             if (pc.hi <= pc.lo)
                 continue;
             const TrackJob &j = jobs[(size_t)pc.t];
             const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-            const i64 slotLo = (j.g0 + pc.itemLo) % R;
+            if (bag)
+            {
+                bagPieces.push_back(TrackBagPiece{sl.stats.p, sl.out.p, j.n, pc.lo, pc.hi});
+                for (int q = 0; q < Q; ++q)
+                {
+                    const TrackModel &x = tm[(size_t)pc.t * Q + q];
+                    const i64 itemLo = pieceItems[pc.item0 + (size_t)q];
+                    bagModels.push_back(TrackBagModel{(int)itemLo, (int)((x.g0 + itemLo) % R[(size_t)q]), x.nMin, x.nMax - x.nMin});
+                    for (int r = 0; r < N; ++r)
+                        ensCopies.push_back(TrackEnsCopy{copies[(size_t)(x.c0 + r)].shift, copies[(size_t)(x.c0 + r)].nseg});
+                }
+                continue;
+            }
+            const TrackModel &x = tm[(size_t)pc.t];
+            const i64 itemLo = pieceItems[pc.item0], slotLo = (x.g0 + itemLo) % Rq;
             if (N == 1)
             {
-                const TrackCopy &cp = copies[(size_t)j.c0];
-                ola.push_back(TrackOlaEntry{ring, sl.stats.p, sl.out.p, j.n, cp.len, pc.lo, pc.hi, pc.itemLo, slotLo, cp.nseg, cp.shift});
+                const TrackCopy &cp = copies[(size_t)x.c0];
+                ola.push_back(TrackOlaEntry{rings[0], sl.stats.p, sl.out.p, j.n, cp.len, pc.lo, pc.hi, itemLo, slotLo, cp.nseg, cp.shift});
             }
             else
             {
-                ens.push_back(TrackEnsPiece{sl.stats.p, sl.out.p, j.n, pc.lo, pc.hi, pc.itemLo, slotLo, j.nMin, j.nMax - j.nMin});
-                for (int q = 0; q < N; ++q)
-                    ensCopies.push_back(TrackEnsCopy{copies[(size_t)(j.c0 + q)].shift, copies[(size_t)(j.c0 + q)].nseg});
+                ens.push_back(TrackEnsPiece{sl.stats.p, sl.out.p, j.n, pc.lo, pc.hi, itemLo, slotLo, x.nMin, x.nMax - x.nMin});
+                for (int r = 0; r < N; ++r)
+                    ensCopies.push_back(TrackEnsCopy{copies[(size_t)(x.c0 + r)].shift, copies[(size_t)(x.c0 + r)].nseg});
             }
         }
-        if (N == 1)
-            launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, R, olaEigen, 0, 2 * S, c->stream);
+        if (bag)
+        {
+            if (!launch_track_ola_bag(bagPieces.data(), bagModels.data(), ensCopies.data(), (int)bagPieces.size(), Q, N, bag->w, rings.data(),
+                                      R.data(), S, seg, stride, olaEigen, 0, 2 * S, c->stream))
+                return fail(DMX_ERR_ARG, "%s: internal error (the bag's overlap-add was refused in batch %d)", fn, k);
+        }
+        else if (N == 1)
+            launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, Rq, olaEigen, 0, 2 * S, c->stream);
         else
-            launch_track_ola_ens(ens.data(), ensCopies.data(), (int)ens.size(), N, ring, S, seg, stride, R, olaEigen, 0, 2 * S, c->stream);
+            launch_track_ola_ens(ens.data(), ensCopies.data(), (int)ens.size(), N, rings[0], S, seg, stride, Rq, olaEigen, 0, 2 * S, c->stream);
         HIPCHK(hipGetLastError());
         if (pcm)
         {
@@ -1718,6 +1857,22 @@ static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *aud
     if (rcSync != DMX_OK)
         return rcSync;
     return DMX_OK;
+}
+
+// a bag leaves the context bound to the model it entered with, on success and on error
+static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
+                      const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user,
+                      const PcmOut *pcm = nullptr, const BagRun *bag = nullptr)
+{
+    const dmx_model *entry = c->m;
+    const int rc = tracks_run_impl(c, fn, T, audio, n, N, stride, shifts, out, layout, progress, user, pcm, bag);
+    if (c->m == entry)
+        return rc;
+    const std::string err = rc != DMX_OK ? dmx_err_string() : std::string();
+    const int rcBind = dmx_ctx_set_model(c, entry);
+    if (rc != DMX_OK)
+        dmx_set_err_string(err);
+    return rc != DMX_OK ? rc : rcBind;
 }
 
 extern "C" int dmx_track_infer(dmx_ctx *c, const float *audio, int64_t n, int shift_offset, float *out, int layout,
@@ -1788,8 +1943,9 @@ extern "C" int dmx_track_geometry_overlap(int64_t segment_samples, int64_t n, in
 }
 
 // the argument checks shared by dmx_tracks_infer_opts and dmx_tracks_infer_pcm (before any GPU work); gives the stride
+// n_models: 0 without a bag (shift_offsets: tracks x shifts), else shift_offsets is tracks x models x shifts
 static int check_tracks_opts(const char *fn, dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts,
-                             float overlap, const int *shift_offsets, void *const *out, int layout, i64 &stride)
+                             float overlap, const int *shift_offsets, void *const *out, int layout, i64 &stride, int n_models = 0)
 {
     if (!c)
         return fail(DMX_ERR_ARG, "%s: null context", fn);
@@ -1815,11 +1971,18 @@ static int check_tracks_opts(const char *fn, dmx_ctx *c, int n_tracks, const flo
             return fail(DMX_ERR_ARG, "%s: track %d: null out pointer", fn, t);
         if (n[t] < 2)
             return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be >= 2", fn, t, (long long)n[t]);
-        for (int k = 0; shift_offsets && k < N; ++k)
+        for (int k = 0; shift_offsets && !n_models && k < N; ++k)
         {
             const int s = shift_offsets[(size_t)t * N + k];
             if (s < -1 || s >= DMX_MAX_SHIFT)
                 return fail(DMX_ERR_ARG, "%s: track %d, shift %d: shift_offset %d not in [-1, %d)", fn, t, k, s, DMX_MAX_SHIFT);
+        }
+        for (int x = 0; shift_offsets && x < n_models * N; ++x)
+        {
+            const int s = shift_offsets[(size_t)t * n_models * N + x];
+            if (s < -1 || s >= DMX_MAX_SHIFT)
+                return fail(DMX_ERR_ARG, "%s: track %d, model %d, shift %d: shift_offset %d not in [-1, %d)", fn, t, x / N, x % N, s,
+                            DMX_MAX_SHIFT);
         }
     }
     return DMX_OK;
@@ -1888,6 +2051,98 @@ extern "C" int dmx_tracks_infer_pcm(dmx_ctx *c, int n_tracks, const float *const
     const PcmOut pcm{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
     const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
     return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
+}
+
+// --------------------------------------------------------------------------- bags of models
+// the checks of dmx_bag_weights; eff (Q x S) and sums (S) may be NULL
+static int bag_weights_check(const char *fn, int Q, int S, const float *weights, float *eff, float *sums)
+{
+    if (Q < 1 || Q > DMX_MAX_BAG)
+        return fail(DMX_ERR_ARG, "%s: n_models must be in [1, %d], got %d", fn, DMX_MAX_BAG, Q);
+    if (S < 1 || S > TrackBagTable::kMaxStems)
+        return fail(DMX_ERR_ARG, "%s: n_sources must be in [1, %d], got %d", fn, TrackBagTable::kMaxStems, S);
+    if (!weights && Q != S)
+        return fail(DMX_ERR_ARG, "%s: weights: NULL (the diagonal bag) needs n_models == n_sources, got %d models of %d sources", fn, Q, S);
+    float w[DMX_MAX_BAG * TrackBagTable::kMaxStems];
+    for (int q = 0; q < Q; ++q)
+        for (int s = 0; s < S; ++s)
+        {
+            const float v = weights ? weights[q * S + s] : (q == s ? 1.0f : 0.0f);
+            if (!(v >= 0.0f) || std::isinf(v)) // also NaN
+                return fail(DMX_ERR_ARG, "%s: weights: model %d, stem %d: weight %g is negative or not finite", fn, q, s, (double)v);
+            w[q * S + s] = v;
+        }
+    float W[TrackBagTable::kMaxStems];
+    for (int s = 0; s < S; ++s)
+    {
+        bool have = false;
+        W[s] = 0.0f;
+        for (int q = 0; q < Q; ++q) // the kernel's order: the first contributing weight initialises the sum
+            if (w[q * S + s] != 0.0f)
+                W[s] = have ? W[s] + w[q * S + s] : w[q * S + s], have = true;
+        if (!have)
+            return fail(DMX_ERR_ARG, "%s: weights: stem %d has no model", fn, s);
+        if (std::isinf(W[s]))
+            return fail(DMX_ERR_ARG, "%s: weights: stem %d: the sum of the weights is not finite", fn, s);
+    }
+    for (int q = 0; q < Q; ++q)
+    {
+        bool any = false;
+        for (int s = 0; s < S; ++s)
+            any = any || w[q * S + s] != 0.0f;
+        if (!any)
+            return fail(DMX_ERR_ARG, "%s: weights: model %d has no non-zero weight", fn, q);
+    }
+    if (eff)
+        std::memcpy(eff, w, sizeof(float) * (size_t)(Q * S));
+    if (sums)
+        std::memcpy(sums, W, sizeof(float) * (size_t)S);
+    return DMX_OK;
+}
+
+extern "C" int dmx_bag_weights(int n_models, int n_sources, const float *weights, float *weights_out, float *sums_out)
+{
+    return bag_weights_check("dmx_bag_weights", n_models, n_sources, weights, weights_out, sums_out);
+}
+
+extern "C" int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                    const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                                    const dmx_output_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
+                                    void *user)
+{
+    const char *fn = "dmx_tracks_infer_bag";
+    if (!c)
+        return fail(DMX_ERR_ARG, "%s: null context", fn);
+    if (n_models < 1 || n_models > DMX_MAX_BAG)
+        return fail(DMX_ERR_ARG, "%s: n_models must be in [1, %d], got %d", fn, DMX_MAX_BAG, n_models);
+    if (!models)
+        return fail(DMX_ERR_ARG, "%s: null models array", fn);
+    const dmx_model *cm = c->m;
+    for (int q = 0; q < n_models; ++q)
+    {
+        const dmx_model *m = models[q];
+        if (!m)
+            return fail(DMX_ERR_ARG, "%s: model %d: null", fn, q);
+        if (m->device != cm->device || m->pm.arch != cm->pm.arch || m->pm.n_sources != cm->pm.n_sources || m->pm.dim != cm->pm.dim ||
+            m->blobFloats != cm->blobFloats || m->pm.index != cm->pm.index) // dmx_ctx_set_model's test
+            return fail(DMX_ERR_ARG, "%s: model %d: differs in architecture or device from the context's", fn, q);
+    }
+    const int S = cm->pm.n_sources;
+    float w[DMX_MAX_BAG * TrackBagTable::kMaxStems];
+    DMXCHK(bag_weights_check(fn, n_models, S, weights, w, nullptr));
+    if (spec)
+        DMXCHK(pcm_check_spec(fn, spec, S));
+    if (n_shifts >= 1 && (i64)n_models * n_shifts > TrackBagTable::kMaxCopies)
+        return fail(DMX_ERR_ARG, "%s: n_models * n_shifts must be <= %d, got %d x %d", fn, TrackBagTable::kMaxCopies, n_models, n_shifts);
+    i64 stride = 0;
+    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride, n_models));
+    const std::vector<int> shifts = draw_shifts(n_tracks * n_models, n_shifts, shift_offsets); // (track, model, copy) order
+    const BagRun bag{models, n_models, w};
+    if (!spec)
+        return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), reinterpret_cast<float *const *>(out), layout, progress,
+                          user, nullptr, &bag);
+    const PcmOut pcm{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
+    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm, &bag);
 }
 
 extern "C" int dmx_pcm_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,

@@ -330,6 +330,45 @@ struct TrackEnsTable
 };
 void launch_track_ola_ens(const TrackEnsPiece *pieces, const TrackEnsCopy *copies, int P, int N, const float *segOut, int S,
                           i64 seg, i64 stride, i64 ring, int layout, int planeBase, int nPlanes, hipStream_t s);
+// a bag of Q models (dmx_tracks_infer_bag; specification: DESIGN.md section 2.9, restated in tests/bag_spec.py): per output
+// sample of stem s, model q's value e_q is track_ola_ens_kernel's e / N on q's own copies (v_0 itself when N = 1), read from
+// q's own ring of segment blocks; over the models with w[q][s] != 0 in increasing q, a = w e_q for the first and
+// fmaf(w, e_q, a) after it, W the fp32 sum of those weights in the same order; out = (a / W) * std + mean. A model with
+// w[q][s] == 0 is not read for stem s: the diagonal bag moves the bytes of a plain overlap-add.
+// Model q's items of a piece's track follow launch_track_ola_ens's rule on q's copies c[(z Q + q) N + k]; item `it` is block
+// slotLo + (it - itemLo) of ring q, less ringBlocks[q] when that is >= ringBlocks[q].
+struct TrackBagPiece
+{
+    const float *stats;
+    float *out;
+    i64 n, i0, i1;
+};
+struct TrackBagModel // one model's view of a piece
+{
+    int itemLo, slotLo; // the lowest item of the model the piece reads, and its ring block
+    int nMin, nTail;    // as TrackEnsPiece, over the model's own copies
+};
+struct TrackBagTable
+{
+    // a launch carries min(kMaxPieces, kMaxModels / Q, kMaxCopies / (Q N)) pieces
+    static const int kMaxPieces = 8, kMaxModels = 32, kMaxCopies = 256, kMaxBag = 8, kMaxStems = 8;
+    // tail rows x copies, tabulated in LDS per block for the models that contribute to the block's stem only; the launch
+    // sizes the table (dynamic LDS) from its own pieces, so an ordinary bag (a few hundred entries) keeps full occupancy
+    static const int kMaxTail = 12288; // 48 KB
+    TrackBagPiece p[kMaxPieces];
+    TrackBagModel m[kMaxModels]; // piece z's models: m[z Q + q]
+    TrackEnsCopy c[kMaxCopies];  // piece z's copies: c[(z Q + q) N + k]
+    float w[kMaxBag * kMaxStems]; // w[q S + s]
+    const float *ring[kMaxBag];
+    i64 ringBlocks[kMaxBag];
+};
+// LDS entries a launch over these pieces needs (the largest, over pieces and stems, of the contributing models' nTail N);
+// -1: a cap of the kernel is exceeded (Q, S, Q N, a piece's tail). The host path checks this before any GPU work.
+i64 track_ola_bag_tail_entries(const TrackBagModel *models, int P, int Q, int N, int S, const float *w);
+// false: nothing was launched (a cap exceeded: see track_ola_bag_tail_entries)
+bool launch_track_ola_bag(const TrackBagPiece *pieces, const TrackBagModel *models, const TrackEnsCopy *copies, int P, int Q, int N,
+                          const float *w, const float *const *rings, const i64 *ringBlocks, int S, i64 seg, i64 stride, int layout,
+                          int planeBase, int nPlanes, hipStream_t s);
 // ---- the PCM output stage (pcm.hip; specification: DESIGN.md section 2.8, restated in tests/pcm_spec.py) ----
 // S x 2 fp32 planes (plane p = stem*2 + channel at planes + p*planeStride) -> nOut outputs of interleaved stereo PCM.
 // stem < 0: output o is stem o; else output 0 is stem `stem` and output 1 the sum of the other stems in increasing order.

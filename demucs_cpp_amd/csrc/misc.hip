@@ -578,6 +578,171 @@ void launch_track_ola_ens(const TrackEnsPiece *pieces, const TrackEnsCopy *copie
     }
 }
 
+// a bag of models (kernels.h TrackBagTable): track_ola_ens_kernel's per-model value from each
+// contributing model's own ring, combined with the stem's weights. Grid (x, planes, pieces); everything travels by value.
+// The tail tables of the contributing models lie one behind the other in dynamic LDS, in increasing q.
+static_assert(sizeof(TrackBagTable) <= 3584, "TrackBagTable must leave room in HIP's 4 KB kernel-argument limit");
+__global__ __launch_bounds__(256) void track_ola_bag_kernel(TrackBagTable t, int Q, int N, int S, i64 seg, i64 stride, int layout,
+                                                            int planeBase)
+{
+    extern __shared__ int bagTail[];
+    const TrackBagPiece &p = t.p[blockIdx.z];
+    const TrackBagModel *pm = t.m + (i64)blockIdx.z * Q;
+    const TrackEnsCopy *pc = t.c + (i64)blockIdx.z * Q * N;
+    const int plane = blockIdx.y + planeBase;
+    const int stem = plane >> 1;
+    const float mean = p.stats[0], stdv = p.stats[1];
+    const i64 maxShift = 22050;
+    const float half = (float)(seg / 2);
+    const i64 n = p.n;
+    float *out = p.out;
+    {
+        int toff = 0;
+        for (int q = 0; q < Q; ++q)
+        {
+            if (t.w[q * S + stem] == 0.f)
+                continue;
+            const TrackEnsCopy *cp = pc + q * N;
+            const int nMin = pm[q].nMin, cnt = pm[q].nTail * N;
+            for (int idx = threadIdx.x; idx < cnt; idx += 256)
+                bagTail[toff + idx] = (int)(ens_item(cp, N, nMin, nMin + idx / N, idx % N) - (i64)nMin * N);
+            toff += cnt;
+        }
+    }
+    __syncthreads();
+    for (i64 i = p.i0 + (i64)blockIdx.x * 256 + threadIdx.x; i < p.i1; i += (i64)gridDim.x * 256)
+    {
+        float a = 0.f, W = 0.f;
+        bool have = false;
+        int toff = 0;
+        for (int q = 0; q < Q; ++q)
+        {
+            const float wq = t.w[q * S + stem];
+            if (wq == 0.f)
+                continue;
+            const TrackEnsCopy *cp = pc + q * N;
+            const float *segOut = t.ring[q];
+            const i64 ring = t.ringBlocks[q];
+            const int nMin = pm[q].nMin;
+            const i64 itemLo = pm[q].itemLo, slotLo = pm[q].slotLo;
+            float e = 0.f;
+            for (int c = 0; c < N; ++c)
+            {
+                const int shift = cp[c].shift, nSeg = cp[c].nseg;
+                const i64 len = n + maxShift - shift; // dmx_track_geometry_overlap
+                const i64 j = i + maxShift - shift;   // position in copy c's shifted track
+                float acc = 0.f, sw = 0.f;
+                i64 first = (j - seg + stride) / stride; // smallest g with g*stride + seg > j
+                if (j - seg + 1 <= 0)
+                    first = 0;
+                for (i64 g = first; g < nSeg && g * stride <= j; ++g)
+                {
+                    const i64 off = g * stride;
+                    const i64 chunk = seg < len - off ? seg : len - off;
+                    const i64 k = j - off;
+                    if (k >= chunk)
+                        continue;
+                    const i64 left = (seg - chunk) / 2;
+                    // triangle weight, indexed from 0 even for short chunks (Q8)
+                    const i64 kk = k < seg / 2 ? k + 1 : seg - k;
+                    const float w = (float)kk / half;
+                    const i64 it = g < nMin ? g * N + c : (i64)nMin * N + bagTail[toff + (g - nMin) * N + c];
+                    i64 blk = slotLo + (it - itemLo);
+                    if (blk >= ring)
+                        blk -= ring;
+                    acc += w * segOut[(blk * S * 2 + plane) * seg + left + k];
+                    sw += w;
+                }
+                const float v = acc / sw;
+                e = c == 0 ? v : e + v;
+            }
+            if (N > 1)
+                e = e / (float)N;
+            if (!have)
+                a = wq * e, W = wq, have = true;
+            else
+                a = __fmaf_rn(wq, e, a), W = W + wq;
+            toff += pm[q].nTail * N;
+        }
+        const float v = (a / W) * stdv + mean;
+        if (layout == 0)
+            out[(i64)plane * n + i] = v;
+        else
+        {
+            const int sIdx = plane >> 1, c = plane & 1;
+            out[sIdx + (i64)S * (c + 2 * i)] = v;
+        }
+    }
+}
+i64 track_ola_bag_tail_entries(const TrackBagModel *models, int P, int Q, int N, int S, const float *w)
+{
+    if (Q < 1 || Q > TrackBagTable::kMaxBag || S < 1 || S > TrackBagTable::kMaxStems || N < 1 || (i64)Q * N > TrackBagTable::kMaxCopies)
+        return -1;
+    i64 most = 0;
+    for (int z = 0; z < P; ++z)
+        for (int s = 0; s < S; ++s)
+        {
+            i64 cnt = 0;
+            for (int q = 0; q < Q; ++q)
+            {
+                const TrackBagModel &m = models[(i64)z * Q + q];
+                if (m.nTail < 0)
+                    return -1;
+                if (w[q * S + s] != 0.f)
+                    cnt += (i64)m.nTail * N;
+            }
+            if (cnt > TrackBagTable::kMaxTail)
+                return -1;
+            most = cnt > most ? cnt : most;
+        }
+    return most;
+}
+bool launch_track_ola_bag(const TrackBagPiece *pieces, const TrackBagModel *models, const TrackEnsCopy *copies, int P, int Q, int N,
+                          const float *w, const float *const *rings, const i64 *ringBlocks, int S, i64 seg, i64 stride, int layout,
+                          int planeBase, int nPlanes, hipStream_t s)
+{
+    if (nPlanes <= 0 || P <= 0)
+        return true;
+    if (planeBase < 0 || planeBase + nPlanes > 2 * S || track_ola_bag_tail_entries(models, P, Q, N, S, w) < 0)
+        return false;
+    int per = TrackBagTable::kMaxPieces;
+    per = TrackBagTable::kMaxModels / Q < per ? TrackBagTable::kMaxModels / Q : per;
+    per = TrackBagTable::kMaxCopies / (Q * N) < per ? TrackBagTable::kMaxCopies / (Q * N) : per;
+    for (int z0 = 0; z0 < P; z0 += per)
+    {
+        TrackBagTable t{};
+        for (int q = 0; q < Q; ++q)
+        {
+            t.ring[q] = rings[q], t.ringBlocks[q] = ringBlocks[q];
+            for (int st = 0; st < S; ++st)
+                t.w[q * S + st] = w[q * S + st];
+        }
+        int nz = 0;
+        i64 span = 0;
+        for (int z = z0; z < P && z < z0 + per; ++z, ++nz)
+        {
+            t.p[nz] = pieces[z];
+            for (int q = 0; q < Q; ++q)
+            {
+                t.m[nz * Q + q] = models[(i64)z * Q + q];
+                for (int k = 0; k < N; ++k)
+                    t.c[(nz * Q + q) * N + k] = copies[((i64)z * Q + q) * N + k];
+            }
+            if (pieces[z].i1 - pieces[z].i0 > span)
+                span = pieces[z].i1 - pieces[z].i0;
+        }
+        if (span <= 0)
+            continue;
+        const i64 entries = track_ola_bag_tail_entries(models + (i64)z0 * Q, nz, Q, N, S, w);
+        int gx = (int)((span + 255) / 256);
+        if (gx > 4096)
+            gx = 4096;
+        hipLaunchKernelGGL(track_ola_bag_kernel, dim3(gx, nPlanes, nz), dim3(256), (size_t)entries * sizeof(int), s, t, Q, N, S, seg,
+                           stride, layout, planeBase);
+    }
+    return true;
+}
+
 // rows x width floats between two pitched images (packing / unpacking the segment tails the OWNER finish mode exchanges)
 __global__ __launch_bounds__(256) void copy_rows_kernel(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width)
 {

@@ -14,7 +14,8 @@
 // demucs_v3_inference_batch: many tracks in one call, their segments sharing batches (dmx_tracks_infer), and their overloads
 // taking demucscpp::inference_options: demucs's shifts ensemble and segment overlap (dmx_tracks_infer_opts); and
 // demucs_inference_batch_pcm / demucs_v3_inference_batch_pcm with demucscpp::output_options: the stems as 16-bit / 24-bit /
-// float32 WAV data, two-stems and clip mode applied on the GPU (dmx_tracks_infer_pcm).
+// float32 WAV data, two-stems and clip mode applied on the GPU (dmx_tracks_infer_pcm); and their overloads taking a
+// demucscpp::demucs_bag: several models with a weight per (model, stem) - the fine-tuned bag, ensembles (dmx_tracks_infer_bag).
 //
 // Eigen is not required: the two tensor types below have exactly the memory image of
 // the reference's column-major Eigen::MatrixXf(2,N) and Eigen::Tensor3dXf(S,2,N), so a
@@ -432,6 +433,171 @@ inline StemTensor demucs_ft_inference(const demucs_ft_bag &bag, const StereoMatr
     if (dmx_engine_track_infer(bag.engine, full_audio.data.data(), full_audio.cols(), bag.shift_offsets, out.data.data(), DMX_LAYOUT_EIGEN,
                                detail::progress_thunk, &th) != DMX_OK)
         detail::die("demucs_ft_inference");
+    return out;
+}
+
+// A bag of models on the batch path (dmx_tracks_infer_bag): Q models of one architecture on one
+// device, one context, a weight per (model, stem). The fine-tuned bag is the diagonal (no weights: stem i from model i);
+// equal weights average the models. shift_offset applies to every (track, model, copy); -1: rand() % 22050 drawn in that
+// order. The tracks' segments share batches per model, and every option of the single-model batch calls applies.
+struct demucs_bag
+{
+    int device = -1;       // -1: DMX_DEVICE, else 0
+    int shift_offset = -1; // DMX_SHIFT_OFFSET
+    int max_batch = 12;    // DMX_BATCH
+    int arch = 0, nb_sources = 0;
+    std::vector<dmx_model *> models;
+    dmx_ctx *ctx = nullptr;
+    mutable std::mutex lock;
+    demucs_bag() {}
+    demucs_bag(const demucs_bag &) = delete;
+    demucs_bag &operator=(const demucs_bag &) = delete;
+    ~demucs_bag()
+    {
+        if (ctx)
+            dmx_ctx_free(ctx);
+        for (dmx_model *m : models)
+            dmx_model_free(m);
+    }
+};
+inline bool load_demucs_bag(const std::vector<std::string> &model_files, demucs_bag *bag)
+{
+    if (model_files.empty() || model_files.size() > (size_t)DMX_MAX_BAG)
+    {
+        std::cerr << "load_demucs_bag: 1 to " << DMX_MAX_BAG << " model files are required, got " << model_files.size() << std::endl;
+        return false;
+    }
+    if (bag->device < 0)
+    {
+        const char *one = std::getenv("DMX_DEVICE");
+        bag->device = one ? std::atoi(one) : 0;
+    }
+    detail::read_env(bag->shift_offset, bag->max_batch);
+    for (const std::string &f : model_files)
+    {
+        dmx_model *m = nullptr;
+        if (dmx_model_load(f.c_str(), bag->device, &m) != DMX_OK)
+        {
+            std::cerr << "load_demucs_bag: " << f << ": " << dmx_last_error() << std::endl;
+            return false;
+        }
+        bag->models.push_back(m);
+    }
+    bag->arch = dmx_model_arch(bag->models[0]), bag->nb_sources = dmx_model_n_sources(bag->models[0]);
+    if (dmx_ctx_create(bag->models[0], 0, bag->max_batch, &bag->ctx) != DMX_OK)
+    {
+        std::cerr << "load_demucs_bag: " << dmx_last_error() << std::endl;
+        return false;
+    }
+    return true;
+}
+namespace detail
+{
+// tracks x models x shifts offsets from the options: empty (the bag's shift_offset everywhere), `shifts` values (for every
+// track and model) or all of them, row-major
+inline std::vector<int> bag_shifts(const char *who, const demucs_bag &bag, size_t T, const inference_options &opts)
+{
+    const size_t Q = bag.models.size(), N = (size_t)std::max(opts.shifts, 0);
+    std::vector<int> shifts(T * Q * N, bag.shift_offset);
+    if (opts.shift_offsets.size() == N)
+        for (size_t i = 0; i < shifts.size(); ++i)
+            shifts[i] = opts.shift_offsets[i % N];
+    else if (opts.shift_offsets.size() == T * Q * N)
+        shifts = opts.shift_offsets;
+    else if (!opts.shift_offsets.empty())
+    {
+        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << Q << " models x " << N
+                  << " shifts" << std::endl;
+        std::exit(1);
+    }
+    return shifts;
+}
+inline const float *bag_weights(const char *who, const demucs_bag &bag, const std::vector<float> &weights)
+{
+    if (weights.empty())
+        return nullptr;
+    if (weights.size() != bag.models.size() * (size_t)bag.nb_sources)
+    {
+        std::cerr << who << ": " << weights.size() << " weights for " << bag.models.size() << " models x " << bag.nb_sources << " stems"
+                  << std::endl;
+        std::exit(1);
+    }
+    return weights.data();
+}
+} // namespace detail
+// weights: empty (the diagonal: needs as many models as stems) or models x stems, row-major
+inline std::vector<StemTensor> demucs_inference_batch(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                                      const std::vector<float> &weights = std::vector<float>(),
+                                                      const inference_options &opts = inference_options())
+{
+    const char *who = "demucs_inference_batch (bag)";
+    const size_t T = tracks.size();
+    std::vector<StemTensor> out;
+    out.reserve(T);
+    if (T == 0)
+        return out;
+    const std::vector<int> shifts = detail::bag_shifts(who, bag, T, opts);
+    const float *w = detail::bag_weights(who, bag, weights);
+    std::vector<const float *> in(T);
+    std::vector<void *> dst(T);
+    std::vector<int64_t> n(T);
+    for (size_t t = 0; t < T; ++t)
+    {
+        out.emplace_back(bag.nb_sources, tracks[t].cols());
+        in[t] = tracks[t].data.data(), dst[t] = out[t].data.data(), n[t] = tracks[t].cols();
+    }
+    detail::CbThunk th{&cb};
+    std::lock_guard<std::mutex> guard(bag.lock);
+    if (dmx_tracks_infer_bag(bag.ctx, bag.models.data(), (int)bag.models.size(), w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap,
+                             shifts.data(), nullptr, dst.data(), nullptr, DMX_LAYOUT_EIGEN, detail::progress_thunk, &th) != DMX_OK)
+        detail::die(who);
+    return out;
+}
+inline PcmOutputs demucs_inference_batch_pcm(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                             const std::vector<float> &weights, const inference_options &opts, const output_options &oo,
+                                             std::vector<std::vector<float>> *peaks = nullptr)
+{
+    const char *who = "demucs_inference_batch_pcm (bag)";
+    const size_t T = tracks.size();
+    PcmOutputs out(T);
+    if (T == 0)
+        return out;
+    const std::vector<int> shifts = detail::bag_shifts(who, bag, T, opts);
+    const float *w = detail::bag_weights(who, bag, weights);
+    const dmx_output_spec spec{oo.encoding, oo.clip, oo.two_stems};
+    const int n_out = oo.two_stems < 0 ? bag.nb_sources : 2;
+    std::vector<const float *> in(T);
+    std::vector<std::vector<unsigned char>> flat(T); // a track's outputs are consecutive across the ABI
+    std::vector<void *> dst(T);
+    std::vector<int64_t> n(T);
+    for (size_t t = 0; t < T; ++t)
+    {
+        in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
+        const int64_t per = dmx_output_bytes(&spec, n[t]);
+        if (per < 0)
+            detail::die(who);
+        flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
+        dst[t] = flat[t].data();
+    }
+    std::vector<float> pk(T * (size_t)n_out, 0.0f);
+    detail::CbThunk th{&cb};
+    std::lock_guard<std::mutex> guard(bag.lock);
+    if (dmx_tracks_infer_bag(bag.ctx, bag.models.data(), (int)bag.models.size(), w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap,
+                             shifts.data(), &spec, dst.data(), pk.data(), DMX_LAYOUT_EIGEN, detail::progress_thunk, &th) != DMX_OK)
+        detail::die(who);
+    for (size_t t = 0; t < T; ++t)
+    {
+        const size_t per = (size_t)dmx_output_bytes(&spec, n[t]);
+        for (int o = 0; o < n_out; ++o)
+            out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)(o + 1) * per);
+        flat[t] = std::vector<unsigned char>();
+    }
+    if (peaks)
+    {
+        peaks->assign(T, std::vector<float>());
+        for (size_t t = 0; t < T; ++t)
+            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
+    }
     return out;
 }
 

@@ -218,6 +218,43 @@ extern "C"
     int dmx_tracks_infer_pcm(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts, float overlap,
                              const int *shift_offsets, const dmx_output_spec *spec, void *const *out, float *peaks, int layout,
                              dmx_progress_fn progress, void *user);
+    /* ---- bags of models on the track path (restated in tests/bag_spec.py; demucs's BagOfModels:
+     * cli-apps/demucs_ft.cpp:136-184 is its one-hot case). Q models of the context's architecture, S stems each, a weight
+     * w[q][s] >= 0 per (model, stem): the diagonal is the fine-tuned bag (stem i from model i), equal weights average the
+     * models (an ensemble). Per output sample of stem s, all fp32: model q's value e_q is what dmx_tracks_infer_opts forms
+     * before de-normalisation (each copy's normalised overlap-add value, summed in increasing copy order and divided by
+     * n_shifts; the one copy's value itself at n_shifts = 1), on q's own shifts. Over the models with w[q][s] != 0 in
+     * increasing q: a = w e_q for the first, a = fmaf(w, e_q, a) after it; W = the fp32 sum of those weights in the same
+     * order; out = (a / W) * std + mean. A model with w[q][s] == 0 is not read for stem s. With one contributing model at
+     * weight 1 - and with one model listed twice at equal weights and shifts - the bits are dmx_tracks_infer_opts's. */
+#define DMX_MAX_BAG 8 /* and n_models * n_shifts <= 256 */
+    /* validates a weight matrix (row-major n_models x n_sources) and gives the effective one: weights NULL needs
+     * n_models == n_sources and means the diagonal. Pure host function. weights_out (n_models x n_sources) and sums_out
+     * (n_sources: the fp32 column sums W above) may be NULL. Rejected: n_models outside [1, DMX_MAX_BAG], a negative or
+     * non-finite weight, a stem without a model, a model without a non-zero weight. */
+    int dmx_bag_weights(int n_models, int n_sources, const float *weights, float *weights_out, float *sums_out);
+    /* dmx_tracks_infer_opts (spec NULL: out[t] is S x 2 x n[t] floats in `layout`, peaks unused) or dmx_tracks_infer_pcm
+     * (spec given) through a bag. shift_offsets: n_tracks x n_models x n_shifts, the shift of track t, model q, copy k at
+     * [(t * n_models + q) * n_shifts + k]; NULL or -1 entries are rand() % 22050 drawn in that row-major order, so one
+     * track at one shift draws like dmx_engine_track_infer. The context may be bound to any model of the bag's
+     * architecture; it is bound to that model again on return, on success and on error.
+     * A track is uploaded once and its statistics are computed once. Model q's items are dmx_tracks_infer_opts's (track,
+     * row, copy) sequence for its own shifts; a batch holds items of one model and the context is rebound between batches
+     * (free when the models take the same exact-split decisions, as fine-tuned models do; otherwise the plans are rebuilt
+     * at every rebind). The next batch always comes from the model that lags furthest behind in (track, row), so that a
+     * piece of a track is final - overlap-added, encoded and copied out as for one model - as soon as every model's copies
+     * have covered it; no host wait between batches. Device memory beyond the arena: the track slots of
+     * dmx_tracks_infer (_pcm), and one ring of segment outputs PER MODEL, each sized by dmx_tracks_infer_opts's rule from the
+     * reach of the overlap-adds into that model's items: at most about 2 max_batch + n_shifts (ceil((segment_samples +
+     * 22050) / stride) + 1) blocks rounded up to a multiple of max_batch - independent of the number and the length of
+     * the tracks.
+     * Arguments are checked before any GPU work and nothing is written on error: "model 2: differs in architecture or
+     * device from the context's", "weights: stem 1 has no model", "weights: model 3 has no non-zero weight", "track 2,
+     * model 1, shift 0: ...". Progress is the fraction of all models' items done (one report per batch, last value 1). */
+    int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                             const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                             const dmx_output_spec *spec /* NULL: fp32 in `layout` */, void *const *out, float *peaks, int layout,
+                             dmx_progress_fn progress, void *user);
     /* the stage alone on device memory (a building block, as dmx_resample_device): n_sources x 2 planes of n >= 1 floats,
      * plane p = stem * 2 + channel at d_planes + p * plane_stride (plane_stride >= n; any alignment of the planes is handled).
      * d_out: 16-byte aligned; output o starts at d_out + o * DMX_OUTPUT_STRIDE(dmx_output_bytes(spec, n)) - the kernels store
