@@ -1,5 +1,6 @@
 // demucs_batch.cpp.main — many tracks in one call (no reference counterpart: the reference's CLIs take one file):
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
+//                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--bag-weights w00,w01,...]
 //                         <model> <out dir> <wav file>...
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
@@ -16,6 +17,16 @@
 // demucscpp::demucs_inference_batch_pcm):
 //   --two-stems NAME         write target_0_NAME.wav and target_1_no_NAME.wav (the sum of the other stems); NAME is a stem
 //                            of the loaded model
+//   --other-method METHOD    what --two-stems writes beside the stem (demucs's option; it needs --two-stems): add (the
+//                            default: the sum of the other stems), minus (target_1_no_NAME.wav = the original mixture minus
+//                            the stem: it keeps what the model attributed to no stem) or none (target_0_NAME.wav only)
+//   --remix NAME=TERMS[,NAME=TERMS...]   outputs mixed on the GPU from the stems and the original mixture, written as
+//                            target_{o}_{NAME}.wav (at most 8). TERMS is a sequence of [+|-][GAIN*]SOURCE; SOURCE is a stem
+//                            of the loaded model or mix (the input track); GAIN is a decimal number or NdB (10^(N/20)); behind
+//                            a term's sign a GAIN may carry a minus of its own:
+//                              --remix karaoke=mix-vocals,backing=drums+bass+other+-12dB*vocals
+//                            Not together with --two-stems. (minus, none and --remix go through dmx_tracks_infer_remix and
+//                            demucscpp::demucs_inference_batch_remix.)
 //   --clip-mode MODE         rescale (divide a stem whose peak exceeds 1 / 1.01 by 1.01 peak), clamp (to +-0.99) or none
 //   --int16 --int24 --float32  sample format of the files (these take no value)
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
@@ -42,6 +53,7 @@ using namespace demucscpp;
 [[noreturn]] static void usage(const char *argv0)
 {
     std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
+              << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--bag-weights w00,w01,...]"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
@@ -83,7 +95,8 @@ int main(int argc, const char **argv)
     inference_options opts;
     output_options out_opts; // demucs's defaults: 16 bit, rescale
     bool with_opts = false, with_out_opts = false;
-    std::string two_stems;
+    std::string two_stems, remix_text;
+    int other_method = -1; // DMX_OTHER_*, -1: not given
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -103,6 +116,28 @@ int main(int argc, const char **argv)
             if (stem_index(val) < 0)
                 usage(argv[0]);
             two_stems = val, out_opts.two_stems = stem_index(val), with_out_opts = true;
+            continue;
+        }
+        if (opt == "--other-method")
+        {
+            other_method = val == "add" ? DMX_OTHER_ADD : val == "minus" ? DMX_OTHER_MINUS : val == "none" ? DMX_OTHER_NONE : -1;
+            if (other_method < 0)
+                usage(argv[0]);
+            with_out_opts = true;
+            continue;
+        }
+        if (opt == "--remix")
+        {
+            try // the grammar now, against every stem name; against the loaded model's stems once it is known
+            {
+                parse_remix(val, 6);
+            }
+            catch (const std::exception &e)
+            {
+                std::cerr << "--remix: " << e.what() << std::endl;
+                usage(argv[0]);
+            }
+            remix_text = val, with_out_opts = true;
             continue;
         }
         if (opt == "--clip-mode")
@@ -171,6 +206,38 @@ int main(int argc, const char **argv)
     }
     if (argc - a < 3)
         usage(argv[0]);
+    if (other_method >= 0 && two_stems.empty())
+    {
+        std::cerr << "--other-method needs --two-stems" << std::endl;
+        usage(argv[0]);
+    }
+    if (!remix_text.empty() && !two_stems.empty())
+    {
+        std::cerr << "--remix and --two-stems exclude each other" << std::endl;
+        usage(argv[0]);
+    }
+    // minus, none and --remix leave through the remix entry points; everything else as before
+    const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE;
+    remix_options remix;
+    auto make_remix = [&](int nb_sources) { // once the model's stems are known
+        if (with_out_opts && out_opts.two_stems >= nb_sources)
+        {
+            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
+            exit(1);
+        }
+        if (!with_remix)
+            return;
+        try
+        {
+            remix = remix_text.empty() ? remix_two_stems(nb_sources, out_opts.two_stems, other_method) : parse_remix(remix_text, nb_sources);
+        }
+        catch (const std::exception &e)
+        {
+            std::cerr << (remix_text.empty() ? "--other-method: " : "--remix: ") << e.what() << std::endl;
+            exit(1);
+        }
+        remix.encoding = out_opts.encoding, remix.clip = out_opts.clip;
+    };
     if (!opts.shift_offsets.empty() && (int)opts.shift_offsets.size() != opts.shifts)
     {
         std::cerr << "--shift-offsets: " << opts.shift_offsets.size() << " values for --shifts " << opts.shifts << std::endl;
@@ -252,7 +319,7 @@ int main(int argc, const char **argv)
         for (int i = 0; i < n_files; ++i)
             if (native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE)
             {
-                std::cerr << "--two-stems / --clip-mode / --int16 / --int24 / --float32 are not available for a track converted by "
+                std::cerr << "--two-stems / --other-method / --remix / --clip-mode / --int16 / --int24 / --float32 are not available for a track converted by "
                           << "DMX_RESAMPLE=1 (" << argv[3 + i] << ", " << native_rate[(size_t)i]
                           << " Hz): converting the stems back needs them in fp32" << std::endl;
                 exit(1);
@@ -293,12 +360,10 @@ int main(int argc, const char **argv)
         }
         std::cout << "Starting Demucs bag (" << bag_files.size() << " models, " << nb_sources << "-source) inference of " << n_files
                   << " tracks" << std::endl;
-        if (with_out_opts && out_opts.two_stems >= nb_sources)
-        {
-            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
-            exit(1);
-        }
-        if (with_out_opts)
+        make_remix(nb_sources);
+        if (with_remix)
+            pcm_outs = demucs_inference_batch_remix(bag, tracks, cb, weights, opts, remix);
+        else if (with_out_opts)
             pcm_outs = demucs_inference_batch_pcm(bag, tracks, cb, weights, opts, out_opts);
         else
             outs = demucs_inference_batch(bag, tracks, cb, weights, opts);
@@ -312,12 +377,10 @@ int main(int argc, const char **argv)
             exit(1);
         }
         std::cout << "Starting Demucs v3 MMI inference of " << n_files << " tracks" << std::endl;
-        if (with_out_opts && out_opts.two_stems >= nb_sources)
-        {
-            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
-            exit(1);
-        }
-        if (with_out_opts)
+        make_remix(nb_sources);
+        if (with_remix)
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, cb, opts, remix);
+        else if (with_out_opts)
             pcm_outs = demucscpp_v3::demucs_v3_inference_batch_pcm(model, tracks, cb, opts, out_opts);
         else
             outs = with_opts ? demucscpp_v3::demucs_v3_inference_batch(model, tracks, cb, opts)
@@ -333,12 +396,10 @@ int main(int argc, const char **argv)
         }
         nb_sources = model.is_4sources ? 4 : 6;
         std::cout << "Starting Demucs (" << nb_sources << "-source) inference of " << n_files << " tracks" << std::endl;
-        if (with_out_opts && out_opts.two_stems >= nb_sources)
-        {
-            std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
-            exit(1);
-        }
-        if (with_out_opts)
+        make_remix(nb_sources);
+        if (with_remix)
+            pcm_outs = demucs_inference_batch_remix(model, tracks, cb, opts, remix);
+        else if (with_out_opts)
             pcm_outs = demucs_inference_batch_pcm(model, tracks, cb, opts, out_opts);
         else
             outs = with_opts ? demucs_inference_batch(model, tracks, cb, opts) : demucs_inference_batch(model, tracks, cb);
@@ -354,7 +415,9 @@ int main(int argc, const char **argv)
             const auto &po = pcm_outs[(size_t)f];
             for (size_t target = 0; target < po.size(); ++target)
             {
-                const std::string name = out_opts.two_stems < 0 ? names[target] : (target == 0 ? two_stems : "no_" + two_stems);
+                const std::string name = with_remix               ? remix.names[target]
+                                         : out_opts.two_stems < 0 ? names[target]
+                                                                  : (target == 0 ? two_stems : "no_" + two_stems);
                 auto p_target = p / ("target_" + std::to_string(target) + "_" + name + ".wav");
                 std::cout << "Writing wav file " << p_target << std::endl;
                 if (!wavio::write_pcm_file(po[target].data(), audio.cols(), out_opts.encoding, p_target.string()))

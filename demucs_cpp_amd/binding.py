@@ -37,6 +37,7 @@ EXPORTS = [
     "dmx_tracks_infer", "dmx_tracks_infer_opts", "dmx_track_geometry_overlap",
     "dmx_output_count", "dmx_output_bytes", "dmx_tracks_infer_pcm", "dmx_pcm_encode_device", "dmx_pcm_encode",
     "dmx_bag_weights", "dmx_tracks_infer_bag",
+    "dmx_remix_two_stems", "dmx_remix_check", "dmx_tracks_infer_remix", "dmx_remix_encode_device", "dmx_remix_encode",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -45,6 +46,8 @@ GEMM_NAMES = {GEMM_F32: "f32", GEMM_BF16X3: "bf16x3", GEMM_FP16X3: "fp16x3"}
 FINISH_ROOT, FINISH_OWNER = 0, 1
 PCM_F32, PCM_S16, PCM_S24 = 0, 1, 2  # include/demucs_hip.h DMX_PCM_*
 CLIP_NONE, CLIP_RESCALE, CLIP_CLAMP = 0, 1, 2  # DMX_CLIP_*
+MAX_OUTPUTS = 8  # DMX_MAX_OUTPUTS
+OTHER_ADD, OTHER_MINUS, OTHER_NONE = 0, 1, 2  # DMX_OTHER_*
 
 
 class OutputSpec(ctypes.Structure):
@@ -54,6 +57,29 @@ class OutputSpec(ctypes.Structure):
 
     def __init__(self, encoding=PCM_S16, clip=CLIP_RESCALE, stem=-1):
         super().__init__(int(encoding), int(clip), int(stem))
+
+
+class _RemixSpecC(ctypes.Structure):
+    _fields_ = [("encoding", ctypes.c_int), ("clip", ctypes.c_int), ("n_out", ctypes.c_int), ("gains", ctypes.c_void_p)]
+
+
+class RemixSpec:
+    """dmx_remix_spec: `gains` is an (n_out, S + 1) matrix over the S stems and, in the last column, the original mixture;
+    encoding PCM_*, clip CLIP_*. The object keeps the gain array alive for the C structure (`.c`) that points into it.
+    gains None builds a structure with a NULL matrix (for the error path)."""
+
+    def __init__(self, gains, encoding=PCM_S16, clip=CLIP_RESCALE, n_out=None):
+        self.gains = None if gains is None else np.ascontiguousarray(gains, np.float32)
+        if self.gains is not None:
+            assert self.gains.ndim == 2, "gains: expected an (n_out, S + 1) matrix"
+        self.encoding, self.clip = int(encoding), int(clip)
+        self.n_out = int(n_out) if n_out is not None else (0 if self.gains is None else self.gains.shape[0])
+        self.c = _RemixSpecC(self.encoding, self.clip, self.n_out, None if self.gains is None else self.gains.ctypes.data)
+
+    def output_spec(self) -> "OutputSpec":
+        """the encoding and clip mode as an OutputSpec (for output_bytes / pcm_views)"""
+        return OutputSpec(self.encoding, self.clip, -1)
+
 
 _lib = None
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_float, ctypes.c_char_p, ctypes.c_void_p)
@@ -116,6 +142,11 @@ def lib():
         L.dmx_pcm_encode.argtypes = [ci, vp, ci, i64, vp, vp, vp]
         L.dmx_bag_weights.argtypes = [ci, ci, vp, vp, vp]
         L.dmx_tracks_infer_bag.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ci, vp, vp]
+        L.dmx_remix_two_stems.argtypes = [ci, ci, ci, vp, vp]
+        L.dmx_remix_check.argtypes = [ci, vp]
+        L.dmx_tracks_infer_remix.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ci, vp, vp]
+        L.dmx_remix_encode_device.argtypes = [ci, vp, ci, i64, i64, vp, vp, vp, vp, vp]
+        L.dmx_remix_encode.argtypes = [ci, vp, ci, i64, vp, vp, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
         L.dmx_track_gather_device.argtypes = [vp, fp, i64, fp, ci, vp, ci, fp]
@@ -422,6 +453,48 @@ class Context:
                 o[...] = img.transpose(2, 1, 0)
         return out
 
+    def tracks_remix(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
+                     shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, out=None, peaks=None):
+        """tracks_pcm() whose outputs are rows of gains over the stems and the original mixture (dmx_tracks_infer_remix).
+        models None: this context's model, shift_offsets (T, n_shifts); else a bag as tracks_bag(), shift_offsets
+        (T, Q, n_shifts). Returns (outs, peaks) in the shapes of tracks_pcm(), n_out = spec.n_out. `out` / `peaks`: buffers
+        to reuse (np.uint8 of n_out * output_bytes bytes per track; a flat np.float32 array of at least T * n_out entries)."""
+        T = len(audios)
+        Q = 0 if models is None else len(models)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        n_out = max(spec.n_out, 0)
+        fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
+        bufs = out if out is not None else [np.zeros(n_out * n * fb, np.uint8) for n in ns]
+        assert len(bufs) == T
+        for b, n in zip(bufs, ns):
+            assert b.dtype == np.uint8 and b.ndim == 1 and b.size == n_out * n * fb and b.flags.c_contiguous
+        if peaks is None:
+            peaks = np.zeros(max(T * n_out, 1), np.float32)
+        assert peaks.dtype == np.float32 and peaks.ndim == 1 and peaks.size >= T * n_out and peaks.flags.c_contiguous
+        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
+        wp = None
+        if weights is not None:
+            warr = np.ascontiguousarray(weights, np.float32)
+            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
+            wp = warr.ctypes.data
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
+            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        _chk(lib().dmx_tracks_infer_remix(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), op,
+                                          peaks.ctypes.data, layout, cbp, None))
+        ospec = spec.output_spec()
+        return [pcm_views(b, ospec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:
         ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         _chk(lib().dmx_track_geometry(self.h, n, shift_offset, ctypes.byref(ln), ctypes.byref(ns), ctypes.byref(st)))
@@ -524,6 +597,41 @@ def pcm_encode(planes: np.ndarray, spec: OutputSpec, device: int = 0):
     peaks = np.zeros(n_out, np.float32)
     _chk(lib().dmx_pcm_encode(device, planes.ctypes.data, S, n, ctypes.byref(spec), buf.ctypes.data, peaks.ctypes.data))
     return pcm_views(buf, spec, n, n_out), peaks
+
+
+def remix_two_stems(n_sources: int, stem: int, method: int = OTHER_ADD) -> np.ndarray:
+    """the gain matrix (n_out, n_sources + 1) of demucs's --two-stems with --other-method add | minus | none
+    (dmx_remix_two_stems; no GPU): OTHER_ADD [stem; the other stems added], OTHER_MINUS [stem; mixture - stem], OTHER_NONE [stem]."""
+    g = np.zeros((2, 8), np.float32)  # the library writes at most 2 x (n_sources + 1), n_sources <= 6 checked first
+    n_out = ctypes.c_int(0)
+    _chk(lib().dmx_remix_two_stems(int(n_sources), int(stem), int(method), g.ctypes.data, ctypes.byref(n_out)))
+    return g.ravel()[:n_out.value * (n_sources + 1)].reshape(n_out.value, n_sources + 1).copy()
+
+
+def remix_check(n_sources: int, spec: RemixSpec):
+    """validates a RemixSpec for a model of n_sources sources (dmx_remix_check; no GPU); raises DmxError naming the field"""
+    if spec.gains is not None and spec.n_out >= 1:
+        assert spec.gains.size >= spec.n_out * (n_sources + 1), "gains: fewer than n_out x (n_sources + 1) entries"
+    _chk(lib().dmx_remix_check(int(n_sources), ctypes.byref(spec.c)))
+
+
+def remix_encode(planes: np.ndarray, mix: Optional[np.ndarray], spec: RemixSpec, device: int = 0):
+    """The remix output stage alone (dmx_remix_encode): planes (S, 2, n) float32, mix (2, n) float32 (the layout of the
+    audio that tracks_remix() takes) or None -> (list of n_out arrays as tracks_pcm, peaks)."""
+    planes = np.ascontiguousarray(planes, np.float32)
+    S, two, n = planes.shape
+    assert two == 2
+    mi = None
+    if mix is not None:
+        assert mix.shape == (2, n)
+        mi = np.ascontiguousarray(np.asarray(mix, np.float32).T)
+    n_out = max(spec.n_out, 0)
+    fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
+    buf = np.zeros(max(n_out * n * fb, 1), np.uint8)
+    peaks = np.zeros(max(n_out, 1), np.float32)
+    _chk(lib().dmx_remix_encode(device, planes.ctypes.data, S, n, None if mi is None else mi.ctypes.data, ctypes.byref(spec.c),
+                                buf.ctypes.data, peaks.ctypes.data))
+    return pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out]
 
 
 def resample_length(n_in: int, rate_in: int, rate_out: int) -> int:

@@ -1398,6 +1398,7 @@ struct PcmOut // the output spec of a call, checked (pcm_check_spec)
     void *const *out;
     float *peaks;
     int nOut, frameBytes;
+    const PcmGains *remix = nullptr; // dmx_tracks_infer_remix: the outputs are rows of gains over the stems and the mixture
 };
 struct PcmRange // frames [lo, hi) of track t encoded behind one batch
 {
@@ -1637,6 +1638,7 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
     std::vector<std::vector<PcmRange>> pcmPlan(pcm ? (size_t)nBatches : 0);
     std::vector<i64> pcmDone(pcm ? (size_t)T : 0, 0);
     std::vector<PcmPiece> pcmPieces, pcmWhole;
+    std::vector<RemixPiece> remixPieces, remixWhole; // instead of those under a remix spec: the mixture is the slot's upload
 
     if (progress)
         progress(0.0f, "1., apply model w/ shift", user);
@@ -1817,7 +1819,7 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
         HIPCHK(hipGetLastError());
         if (pcm)
         {
-            pcmPieces.clear(), pcmWhole.clear();
+            pcmPieces.clear(), pcmWhole.clear(), remixPieces.clear(), remixWhole.clear();
             for (const TrackPiece &pc : plan[(size_t)k])
             {
                 const TrackJob &j = jobs[(size_t)pc.t];
@@ -1828,18 +1830,39 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
                 const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
                 const PcmPiece pp{sl.out.p, (unsigned char *)sl.pcm.p, (unsigned *)sl.peaks.p, j.n, j.n,
                                   DMX_OUTPUT_STRIDE(j.n * pcm->frameBytes), done, hi};
-                pcmPieces.push_back(pp);
-                if (hi == j.n)
+                if (pcm->remix)
                 {
-                    pcmWhole.push_back(pp);
-                    pcmWhole.back().i0 = 0;
+                    remixPieces.push_back(RemixPiece{pp, sl.audio.p});
+                    if (hi == j.n)
+                    {
+                        remixWhole.push_back(remixPieces.back());
+                        remixWhole.back().i0 = 0;
+                    }
+                }
+                else
+                {
+                    pcmPieces.push_back(pp);
+                    if (hi == j.n)
+                    {
+                        pcmWhole.push_back(pp);
+                        pcmWhole.back().i0 = 0;
+                    }
                 }
                 pcmPlan[(size_t)k].push_back(PcmRange{pc.t, done, hi});
                 done = hi;
             }
-            launch_pcm_peak(pcmPieces.data(), (int)pcmPieces.size(), S, pcm->spec.stem, c->stream);
-            const std::vector<PcmPiece> &enc = wholeTrack ? pcmWhole : pcmPieces;
-            launch_pcm_encode(enc.data(), (int)enc.size(), S, pcm->spec.stem, pcm->spec.encoding, pcm->spec.clip, c->stream);
+            if (pcm->remix)
+            {
+                launch_remix_peak(remixPieces.data(), (int)remixPieces.size(), *pcm->remix, c->stream);
+                const std::vector<RemixPiece> &enc = wholeTrack ? remixWhole : remixPieces;
+                launch_remix_encode(enc.data(), (int)enc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, c->stream);
+            }
+            else
+            {
+                launch_pcm_peak(pcmPieces.data(), (int)pcmPieces.size(), S, pcm->spec.stem, c->stream);
+                const std::vector<PcmPiece> &enc = wholeTrack ? pcmWhole : pcmPieces;
+                launch_pcm_encode(enc.data(), (int)enc.size(), S, pcm->spec.stem, pcm->spec.encoding, pcm->spec.clip, c->stream);
+            }
             HIPCHK(hipGetLastError());
         }
         hipEvent_t ev = dmx_batch_event(c, (size_t)k);
@@ -2053,6 +2076,90 @@ extern "C" int dmx_tracks_infer_pcm(dmx_ctx *c, int n_tracks, const float *const
     return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
 }
 
+// --------------------------------------------------------------------------- remix outputs (pcm.hip)
+// the checks of dmx_remix_check; G (may be NULL): the kernels' table. noModel (S and G unused): the model is not known (no
+// context): the checks that do not need the width of the matrix
+static int remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, PcmGains *G, bool noModel = false)
+{
+    if (!noModel && (S < 1 || S > PcmGains::kMaxSrc - 1))
+        return fail(DMX_ERR_ARG, "%s: remix spec: n_sources must be in [1, %d], got %d", fn, PcmGains::kMaxSrc - 1, S);
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: remix spec: null", fn);
+    if (spec->n_out < 1 || spec->n_out > DMX_MAX_OUTPUTS)
+        return fail(DMX_ERR_ARG, "%s: remix spec: n_out must be in [1, %d], got %d", fn, DMX_MAX_OUTPUTS, spec->n_out);
+    if (!spec->gains)
+        return fail(DMX_ERR_ARG, "%s: remix spec: null gain matrix", fn);
+    for (int o = 0; !noModel && o < spec->n_out; ++o)
+    {
+        bool any = false;
+        for (int s = 0; s <= S; ++s)
+        {
+            const float g = spec->gains[o * (S + 1) + s];
+            if (!std::isfinite(g))
+            {
+                if (s < S)
+                    return fail(DMX_ERR_ARG, "%s: remix spec: output %d, source %d: gain %g is not finite", fn, o, s, (double)g);
+                return fail(DMX_ERR_ARG, "%s: remix spec: output %d, source %d (the mixture): gain %g is not finite", fn, o, s, (double)g);
+            }
+            any = any || g != 0.0f;
+        }
+        if (!any)
+            return fail(DMX_ERR_ARG, "%s: remix spec: output %d has no non-zero gain", fn, o);
+    }
+    if (spec->encoding != DMX_PCM_F32 && spec->encoding != DMX_PCM_S16 && spec->encoding != DMX_PCM_S24)
+        return fail(DMX_ERR_ARG, "%s: remix spec: encoding %d (DMX_PCM_F32 0, DMX_PCM_S16 1, DMX_PCM_S24 2)", fn, spec->encoding);
+    if (spec->clip != DMX_CLIP_NONE && spec->clip != DMX_CLIP_RESCALE && spec->clip != DMX_CLIP_CLAMP)
+        return fail(DMX_ERR_ARG, "%s: remix spec: clip %d (DMX_CLIP_NONE 0, DMX_CLIP_RESCALE 1, DMX_CLIP_CLAMP 2)", fn, spec->clip);
+    if (G && !noModel)
+    {
+        std::memset(G, 0, sizeof(*G));
+        G->nOut = spec->n_out, G->S = S;
+        for (int o = 0; o < spec->n_out; ++o)
+            for (int s = 0; s <= S; ++s)
+                G->g[o][s] = spec->gains[o * (S + 1) + s];
+    }
+    return DMX_OK;
+}
+static bool remix_uses_mix(const PcmGains &G)
+{
+    for (int o = 0; o < G.nOut; ++o)
+        if (G.g[o][G.S] != 0.0f)
+            return true;
+    return false;
+}
+
+extern "C" int dmx_remix_check(int n_sources, const dmx_remix_spec *spec)
+{
+    return remix_check_spec("dmx_remix_check", n_sources, spec, nullptr);
+}
+
+extern "C" int dmx_remix_two_stems(int n_sources, int stem, int method, float *gains_out, int *n_out)
+{
+    const char *fn = "dmx_remix_two_stems";
+    const int S = n_sources;
+    if (S < 1 || S > PcmGains::kMaxSrc - 1)
+        return fail(DMX_ERR_ARG, "%s: n_sources must be in [1, %d], got %d", fn, PcmGains::kMaxSrc - 1, S);
+    if (stem < 0 || stem >= S)
+        return fail(DMX_ERR_ARG, "%s: stem %d of a %d-source model", fn, stem, S);
+    if (method != DMX_OTHER_ADD && method != DMX_OTHER_MINUS && method != DMX_OTHER_NONE)
+        return fail(DMX_ERR_ARG, "%s: method %d (DMX_OTHER_ADD 0, DMX_OTHER_MINUS 1, DMX_OTHER_NONE 2)", fn, method);
+    if (method == DMX_OTHER_ADD && S < 2)
+        return fail(DMX_ERR_ARG, "%s: DMX_OTHER_ADD needs at least 2 sources", fn);
+    if (!gains_out || !n_out)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !gains_out ? "gains_out" : "n_out");
+    const int rows = method == DMX_OTHER_NONE ? 1 : 2;
+    for (int i = 0; i < rows * (S + 1); ++i)
+        gains_out[i] = 0.0f;
+    gains_out[stem] = 1.0f;
+    if (method == DMX_OTHER_ADD)
+        for (int s = 0; s < S; ++s)
+            gains_out[(S + 1) + s] = s == stem ? 0.0f : 1.0f;
+    else if (method == DMX_OTHER_MINUS)
+        gains_out[(S + 1) + stem] = -1.0f, gains_out[(S + 1) + S] = 1.0f;
+    *n_out = rows;
+    return DMX_OK;
+}
+
 // --------------------------------------------------------------------------- bags of models
 // the checks of dmx_bag_weights; eff (Q x S) and sums (S) may be NULL
 static int bag_weights_check(const char *fn, int Q, int S, const float *weights, float *eff, float *sums)
@@ -2105,12 +2212,12 @@ extern "C" int dmx_bag_weights(int n_models, int n_sources, const float *weights
     return bag_weights_check("dmx_bag_weights", n_models, n_sources, weights, weights_out, sums_out);
 }
 
-extern "C" int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
-                                    const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
-                                    const dmx_output_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
-                                    void *user)
+// dmx_tracks_infer_bag, and dmx_tracks_infer_remix with models: spec / remix (at most one) select the output stage
+static int tracks_bag_run(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                          const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                          const dmx_output_spec *spec, const dmx_remix_spec *remix, void *const *out, float *peaks, int layout,
+                          dmx_progress_fn progress, void *user)
 {
-    const char *fn = "dmx_tracks_infer_bag";
     if (!c)
         return fail(DMX_ERR_ARG, "%s: null context", fn);
     if (n_models < 1 || n_models > DMX_MAX_BAG)
@@ -2132,17 +2239,31 @@ extern "C" int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, 
     DMXCHK(bag_weights_check(fn, n_models, S, weights, w, nullptr));
     if (spec)
         DMXCHK(pcm_check_spec(fn, spec, S));
+    PcmGains G;
+    if (remix)
+        DMXCHK(remix_check_spec(fn, S, remix, &G));
     if (n_shifts >= 1 && (i64)n_models * n_shifts > TrackBagTable::kMaxCopies)
         return fail(DMX_ERR_ARG, "%s: n_models * n_shifts must be <= %d, got %d x %d", fn, TrackBagTable::kMaxCopies, n_models, n_shifts);
     i64 stride = 0;
     DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride, n_models));
     const std::vector<int> shifts = draw_shifts(n_tracks * n_models, n_shifts, shift_offsets); // (track, model, copy) order
     const BagRun bag{models, n_models, w};
-    if (!spec)
+    if (!spec && !remix)
         return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), reinterpret_cast<float *const *>(out), layout, progress,
                           user, nullptr, &bag);
-    const PcmOut pcm{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
+    const PcmOut pcm = remix ? PcmOut{dmx_output_spec{remix->encoding, remix->clip, -1}, out, peaks, remix->n_out,
+                                      pcm_frame_bytes(remix->encoding), &G}
+                             : PcmOut{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
     return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm, &bag);
+}
+
+extern "C" int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                    const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                                    const dmx_output_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
+                                    void *user)
+{
+    return tracks_bag_run("dmx_tracks_infer_bag", c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, spec,
+                          nullptr, out, peaks, layout, progress, user);
 }
 
 extern "C" int dmx_pcm_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
@@ -2201,6 +2322,96 @@ extern "C" int dmx_pcm_encode(int device, const float *planes, int n_sources, in
     if (rc == DMX_OK && peaks && hipMemcpy(peaks, dPeaks, sizeof(float) * (size_t)nOut, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
     for (void *p : {(void *)dIn, (void *)dOut, (void *)dPeaks})
+        if (p)
+            (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                      const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                                      const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
+                                      void *user)
+{
+    const char *fn = "dmx_tracks_infer_remix";
+    if (!c)
+    {
+        DMXCHK(remix_check_spec(fn, 0, spec, nullptr, true)); // what of the spec can be checked without a model
+        return fail(DMX_ERR_ARG, "%s: null context", fn);
+    }
+    const int S = c->m->pm.n_sources;
+    PcmGains G;
+    DMXCHK(remix_check_spec(fn, S, spec, &G));
+    if (models || n_models != 0)
+        return tracks_bag_run(fn, c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, nullptr, spec, out,
+                              peaks, layout, progress, user);
+    if (weights)
+        return fail(DMX_ERR_ARG, "%s: weights given without models", fn);
+    i64 stride = 0;
+    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride));
+    const PcmOut pcm{dmx_output_spec{spec->encoding, spec->clip, -1}, out, peaks, spec->n_out, pcm_frame_bytes(spec->encoding), &G};
+    const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
+    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
+}
+
+extern "C" int dmx_remix_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                       const float *d_mix, const dmx_remix_spec *spec, void *d_out, float *d_peaks, void *stream)
+{
+    const char *fn = "dmx_remix_encode_device";
+    PcmGains G;
+    DMXCHK(remix_check_spec(fn, n_sources, spec, &G));
+    if (!d_planes || !d_out || !d_peaks)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_planes ? "d_planes" : !d_out ? "d_out" : "d_peaks");
+    if (!d_mix && remix_uses_mix(G))
+        return fail(DMX_ERR_ARG, "%s: null d_mix pointer, and the mixture column of the gains is not all zero", fn);
+    if (n < 1 || plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n <= plane_stride)", fn, (long long)n, (long long)plane_stride);
+    if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_planes & 3) != 0 || ((uintptr_t)d_peaks & 3) != 0 || ((uintptr_t)d_mix & 3) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_out must be 16-byte aligned, d_planes, d_mix and d_peaks 4-byte aligned", fn);
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(d_peaks, 0, sizeof(float) * (size_t)G.nOut, s));
+    RemixPiece pp{PcmPiece{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
+                           DMX_OUTPUT_STRIDE(n * pcm_frame_bytes(spec->encoding)), 0, n},
+                  d_mix};
+    launch_remix_peak(&pp, 1, G, s);
+    launch_remix_encode(&pp, 1, G, spec->encoding, spec->clip, s);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_remix_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                                void *out, float *peaks)
+{
+    const char *fn = "dmx_remix_encode";
+    PcmGains G;
+    DMXCHK(remix_check_spec(fn, n_sources, spec, &G));
+    if (!planes || !out || n < 1)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer or n < 1)", fn);
+    if (!mix && remix_uses_mix(G))
+        return fail(DMX_ERR_ARG, "%s: null mix pointer, and the mixture column of the gains is not all zero", fn);
+    HIPCHK(hipSetDevice(device));
+    const int nOut = G.nOut;
+    const i64 bytes = n * pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
+    const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n, mixBytes = sizeof(float) * 2 * (size_t)n;
+    float *dIn = nullptr, *dPeaks = nullptr, *dMix = nullptr;
+    unsigned char *dOut = nullptr;
+    int rc = DMX_OK;
+    if (hipMalloc((void **)&dIn, inBytes) != hipSuccess || hipMalloc((void **)&dOut, (size_t)(nOut * devStride)) != hipSuccess ||
+        hipMalloc((void **)&dPeaks, sizeof(float) * (size_t)nOut) != hipSuccess || (mix && hipMalloc((void **)&dMix, mixBytes) != hipSuccess))
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK && (hipMemcpy(dIn, planes, inBytes, hipMemcpyHostToDevice) != hipSuccess ||
+                         (mix && hipMemcpy(dMix, mix, mixBytes, hipMemcpyHostToDevice) != hipSuccess)))
+        rc = fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    if (rc == DMX_OK)
+        rc = dmx_remix_encode_device(device, dIn, n_sources, n, n, dMix, spec, dOut, dPeaks, nullptr);
+    if (rc == DMX_OK && hipDeviceSynchronize() != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    for (int o = 0; rc == DMX_OK && o < nOut; ++o)
+        if (hipMemcpy((unsigned char *)out + (size_t)(o * bytes), dOut + (size_t)(o * devStride), (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    if (rc == DMX_OK && peaks && hipMemcpy(peaks, dPeaks, sizeof(float) * (size_t)nOut, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    for (void *p : {(void *)dIn, (void *)dOut, (void *)dPeaks, (void *)dMix})
         if (p)
             (void)hipFree(p);
     return rc;

@@ -392,6 +392,25 @@ void launch_pcm_peak(const PcmPiece *pieces, int P, int S, int stem, hipStream_t
 // clip (DMX_CLIP_*; rescale reads peaks[o]: every piece of the track must have been through launch_pcm_peak) and
 // quantisation (DMX_PCM_*) of the pieces' frames
 void launch_pcm_encode(const PcmPiece *pieces, int P, int S, int stem, int encoding, int clip, hipStream_t s);
+// the gain table of a remix (dmx_remix_spec, checked): output o = the sum over the sources with g[o][s] != 0, in increasing
+// s, of g[o][s] * source s; sources 0..S-1 are the stems, source S the mixture. Passed in the kernel arguments.
+struct PcmGains
+{
+    static const int kMaxOut = 8, kMaxSrc = 7; // DMX_MAX_OUTPUTS, and 6 stems + the mixture
+    float g[kMaxOut][kMaxSrc];
+    int nOut, S;
+};
+struct RemixPiece : PcmPiece
+{
+    const float *mix; // the track interleaved [n][2], any 4-byte alignment; may be NULL when no row uses the mixture
+};
+struct RemixTable
+{
+    static const int kMax = 32;
+    RemixPiece p[kMax];
+};
+void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s);
+void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
 // dst[r*dpitch + i] = src[r*spitch + i], r < rows, i < width (floats)
 void launch_copy_rows(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width, int rows, hipStream_t s);
 // dst[i] = fp16 bit pattern of src[i], round to nearest even (the opt-in fp16 weight plane, api.cpp dmx_model_fp16_plane)

@@ -16,6 +16,14 @@
 // plane) and as four dword loads otherwise, and stores 16 (S16), 24 (S24) or 32 (F32) bytes as whole dwords. The last
 // group of a track may hold 1-3 frames: the same lane takes the scalar edge path (guarded loads, dword stores; a 24-bit
 // track of odd length ends in two zero bytes of the output's padding).
+//
+// The remix pair (dmx_remix_spec; DESIGN.md section 2.10, restated in tests/remix_spec.py) shares everything above but the
+// gather: output o is a row of gains over the S stems and the mixture (the caller's track, interleaved, un-normalised).
+// Sources are visited in increasing index, a source with gain 0 is NOT read (a uniform branch: the table sits in the kernel
+// arguments), the first visited source gives a = g * x and each later one p = g * x, a = a + p - every product and every sum
+// its own correctly rounded fp32 operation. hipcc contracts device code by default, so the gather is compiled with
+// contraction off (remix_acc below); no fused multiply-add may appear in it. The mixture's 4 frames are 32 contiguous
+// bytes: two 16-byte loads when aligned, dword loads otherwise and in the edge group.
 #include "kernels.h"
 
 #include "../../include/demucs_hip.h"
@@ -70,6 +78,81 @@ __device__ __forceinline__ void pcm_gather(const PcmPiece &pc, int S, int stem, 
         first = false;
     }
 }
+// frames [i, i + cnt) of the interleaved mixture: L0 R0 L1 R1 ...
+__device__ __forceinline__ void pcm_load_mix4(const float *mix, i64 i, int cnt, float L[4], float R[4])
+{
+    const float *q = mix + 2 * i;
+    if (cnt == 4 && ((uintptr_t)q & 15) == 0)
+    {
+        const float4 t = reinterpret_cast<const float4 *>(q)[0], u = reinterpret_cast<const float4 *>(q)[1];
+        L[0] = t.x, R[0] = t.y, L[1] = t.z, R[1] = t.w;
+        L[2] = u.x, R[2] = u.y, L[3] = u.z, R[3] = u.w;
+    }
+    else
+    {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+        {
+            L[k] = k < cnt ? q[2 * k] : 0.0f;
+            R[k] = k < cnt ? q[2 * k + 1] : 0.0f;
+        }
+    }
+}
+// a = g x for the first visited source, then p = g x, a = a + p: two roundings, never one
+__device__ __forceinline__ void remix_acc(float g, const float x[4], bool first, float a[4])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const float p = g * x[k];
+        a[k] = first ? p : a[k] + p;
+    }
+}
+// the two channels of output o for frames [i, i + cnt) under a gain table
+__device__ __forceinline__ void remix_gather(const RemixPiece &pc, const PcmGains &G, int o, i64 i, int cnt, float L[4], float R[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        L[k] = R[k] = 0.0f; // a checked spec has a non-zero gain in every row: never what is used
+    bool first = true;
+    for (int s = 0; s < G.S; ++s)
+    {
+        const float g = G.g[o][s];
+        if (g == 0.0f) // uniform: the plane is not loaded
+            continue;
+        float a[4], b[4];
+        pcm_load4(pc.planes + (i64)(2 * s) * pc.planeStride, i, cnt, a);
+        pcm_load4(pc.planes + (i64)(2 * s + 1) * pc.planeStride, i, cnt, b);
+        remix_acc(g, a, first, L);
+        remix_acc(g, b, first, R);
+        first = false;
+    }
+    const float gm = G.g[o][G.S];
+    if (gm != 0.0f)
+    {
+        float a[4], b[4];
+        pcm_load_mix4(pc.mix, i, cnt, a, b);
+        remix_acc(gm, a, first, L);
+        remix_acc(gm, b, first, R);
+    }
+}
+struct GatherStems // dmx_output_spec: a stem, or the sum of the others
+{
+    int S, stem;
+    __device__ __forceinline__ void operator()(const PcmPiece &pc, int o, i64 i, int cnt, float L[4], float R[4]) const
+    {
+        pcm_gather(pc, S, stem, o, i, cnt, L, R);
+    }
+};
+struct GatherRemix // dmx_remix_spec: a row of gains
+{
+    const PcmGains &G;
+    __device__ __forceinline__ void operator()(const RemixPiece &pc, int o, i64 i, int cnt, float L[4], float R[4]) const
+    {
+        remix_gather(pc, G, o, i, cnt, L, R);
+    }
+};
 __device__ __forceinline__ int pcm_quant(float y, float scale, float lo, float hi)
 {
     float t = rintf(y * scale); // v_rndne_f32: ties to even
@@ -78,12 +161,11 @@ __device__ __forceinline__ int pcm_quant(float y, float scale, float lo, float h
     t = t > hi ? hi : t;
     return (int)t;
 }
-} // namespace
 
-// grid (blocks, nOut, pieces), block 256
-__global__ __launch_bounds__(256) void pcm_peak_kernel(PcmTable t, int S, int stem)
+template <class Table, class Gather>
+__device__ __forceinline__ void pcm_peak_body(const Table &t, const Gather &gather)
 {
-    const PcmPiece &pc = t.p[blockIdx.z];
+    const auto &pc = t.p[blockIdx.z];
     const int o = blockIdx.y;
     const i64 g0 = pc.i0 >> 2, g1 = (pc.i1 + 3) >> 2;
     float m = 0.0f;
@@ -92,7 +174,7 @@ __global__ __launch_bounds__(256) void pcm_peak_kernel(PcmTable t, int S, int st
         const i64 i = g << 2;
         const int cnt = pc.i1 - i < 4 ? (int)(pc.i1 - i) : 4;
         float L[4], R[4];
-        pcm_gather(pc, S, stem, o, i, cnt, L, R);
+        gather(pc, o, i, cnt, L, R);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
         {
@@ -122,10 +204,10 @@ __global__ __launch_bounds__(256) void pcm_peak_kernel(PcmTable t, int S, int st
     }
 }
 
-template <int ENC>
-__global__ __launch_bounds__(256) void pcm_encode_kernel(PcmTable t, int S, int stem, int clip)
+template <int ENC, class Table, class Gather>
+__device__ __forceinline__ void pcm_encode_body(const Table &t, int clip, const Gather &gather)
 {
-    const PcmPiece &pc = t.p[blockIdx.z];
+    const auto &pc = t.p[blockIdx.z];
     const int o = blockIdx.y;
     const i64 g0 = pc.i0 >> 2, g1 = (pc.i1 + 3) >> 2;
     float d = 1.0f;
@@ -141,7 +223,7 @@ __global__ __launch_bounds__(256) void pcm_encode_kernel(PcmTable t, int S, int 
         const i64 i = g << 2;
         const int cnt = pc.i1 - i < 4 ? (int)(pc.i1 - i) : 4;
         float L[4], R[4];
-        pcm_gather(pc, S, stem, o, i, cnt, L, R);
+        gather(pc, o, i, cnt, L, R);
         float y[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -219,17 +301,34 @@ __global__ __launch_bounds__(256) void pcm_encode_kernel(PcmTable t, int S, int 
     }
 }
 
+} // namespace
+
+// grid (blocks, nOut, pieces), block 256
+__global__ __launch_bounds__(256) void pcm_peak_kernel(PcmTable t, int S, int stem) { pcm_peak_body(t, GatherStems{S, stem}); }
+template <int ENC>
+__global__ __launch_bounds__(256) void pcm_encode_kernel(PcmTable t, int S, int stem, int clip)
+{
+    pcm_encode_body<ENC>(t, clip, GatherStems{S, stem});
+}
+// the same under a gain table: grid (blocks, G.nOut, pieces)
+__global__ __launch_bounds__(256) void remix_peak_kernel(RemixTable t, PcmGains G) { pcm_peak_body(t, GatherRemix{G}); }
+template <int ENC>
+__global__ __launch_bounds__(256) void remix_encode_kernel(RemixTable t, PcmGains G, int clip)
+{
+    pcm_encode_body<ENC>(t, clip, GatherRemix{G});
+}
+
 namespace
 {
-template <class F>
-void pcm_for_tables(const PcmPiece *pieces, int P, F launch)
+template <class Table, class Piece, class F>
+void pcm_for_tables(const Piece *pieces, int P, F launch)
 {
-    for (int p0 = 0; p0 < P; p0 += PcmTable::kMax)
+    for (int p0 = 0; p0 < P; p0 += Table::kMax)
     {
-        PcmTable t{};
+        Table t{};
         int nt = 0;
         i64 span = 0;
-        for (int k = p0; k < P && k < p0 + PcmTable::kMax; ++k)
+        for (int k = p0; k < P && k < p0 + Table::kMax; ++k)
         {
             if (pieces[k].i1 <= pieces[k].i0)
                 continue;
@@ -247,20 +346,38 @@ void pcm_for_tables(const PcmPiece *pieces, int P, F launch)
 void launch_pcm_peak(const PcmPiece *pieces, int P, int S, int stem, hipStream_t s)
 {
     const int nOut = stem < 0 ? S : 2;
-    pcm_for_tables(pieces, P, [&](const PcmTable &t, int nt, int gx) {
+    pcm_for_tables<PcmTable>(pieces, P, [&](const PcmTable &t, int nt, int gx) {
         hipLaunchKernelGGL(pcm_peak_kernel, dim3(gx, nOut, nt), dim3(256), 0, s, t, S, stem);
     });
 }
 void launch_pcm_encode(const PcmPiece *pieces, int P, int S, int stem, int encoding, int clip, hipStream_t s)
 {
     const int nOut = stem < 0 ? S : 2;
-    pcm_for_tables(pieces, P, [&](const PcmTable &t, int nt, int gx) {
+    pcm_for_tables<PcmTable>(pieces, P, [&](const PcmTable &t, int nt, int gx) {
         if (encoding == DMX_PCM_F32)
             hipLaunchKernelGGL(pcm_encode_kernel<DMX_PCM_F32>, dim3(gx, nOut, nt), dim3(256), 0, s, t, S, stem, clip);
         else if (encoding == DMX_PCM_S16)
             hipLaunchKernelGGL(pcm_encode_kernel<DMX_PCM_S16>, dim3(gx, nOut, nt), dim3(256), 0, s, t, S, stem, clip);
         else
             hipLaunchKernelGGL(pcm_encode_kernel<DMX_PCM_S24>, dim3(gx, nOut, nt), dim3(256), 0, s, t, S, stem, clip);
+    });
+}
+
+void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s)
+{
+    pcm_for_tables<RemixTable>(pieces, P, [&](const RemixTable &t, int nt, int gx) {
+        hipLaunchKernelGGL(remix_peak_kernel, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G);
+    });
+}
+void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s)
+{
+    pcm_for_tables<RemixTable>(pieces, P, [&](const RemixTable &t, int nt, int gx) {
+        if (encoding == DMX_PCM_F32)
+            hipLaunchKernelGGL(remix_encode_kernel<DMX_PCM_F32>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+        else if (encoding == DMX_PCM_S16)
+            hipLaunchKernelGGL(remix_encode_kernel<DMX_PCM_S16>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+        else
+            hipLaunchKernelGGL(remix_encode_kernel<DMX_PCM_S24>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
     });
 }
 

@@ -15,7 +15,9 @@
 // taking demucscpp::inference_options: demucs's shifts ensemble and segment overlap (dmx_tracks_infer_opts); and
 // demucs_inference_batch_pcm / demucs_v3_inference_batch_pcm with demucscpp::output_options: the stems as 16-bit / 24-bit /
 // float32 WAV data, two-stems and clip mode applied on the GPU (dmx_tracks_infer_pcm); and their overloads taking a
-// demucscpp::demucs_bag: several models with a weight per (model, stem) - the fine-tuned bag, ensembles (dmx_tracks_infer_bag).
+// demucscpp::demucs_bag: several models with a weight per (model, stem) - the fine-tuned bag, ensembles (dmx_tracks_infer_bag);
+// and demucs_inference_batch_remix / demucs_v3_inference_batch_remix with demucscpp::remix_options: outputs mixed on the GPU
+// from the stems and the original mixture - demucs's --other-method minus / none, stem gains, mix-minus (dmx_tracks_infer_remix).
 //
 // Eigen is not required: the two tensor types below have exactly the memory image of
 // the reference's column-major Eigen::MatrixXf(2,N) and Eigen::Tensor3dXf(S,2,N), so a
@@ -25,6 +27,7 @@
 #pragma once
 #include "demucs_hip.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <iostream>
@@ -32,6 +35,7 @@
 #include <memory>
 #include <mutex>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -381,6 +385,212 @@ inline PcmOutputs demucs_inference_batch_pcm(const demucs_model &model, const st
     return detail::batch_call_pcm("demucs_inference_batch_pcm", model, tracks, cb, opts, out_opts, peaks);
 }
 
+// Outputs mixed on the GPU from the stems and the original mixture (dmx_tracks_infer_remix; include/demucs_hip.h
+// dmx_remix_spec): output o is names[o], its row of gains is gains[o * (nb_sources + 1) ...], the last entry of a row the
+// gain of the mixture. The defaults are demucs's: 16 bit, rescale.
+struct remix_options
+{
+    int encoding = DMX_PCM_S16;
+    int clip = DMX_CLIP_RESCALE;
+    std::vector<std::string> names;
+    std::vector<float> gains;
+};
+// demucs's --two-stems NAME with --other-method add | minus | none (DMX_OTHER_*): outputs "NAME" and, except for none,
+// "no_NAME" (add: the other stems added; minus: mixture - stem). Throws std::invalid_argument with the library's message.
+inline remix_options remix_two_stems(int nb_sources, int stem, int method)
+{
+    static const char *stems[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
+    float g[2 * 8];
+    int n_out = 0;
+    if (nb_sources > 6 || dmx_remix_two_stems(nb_sources, stem, method, g, &n_out) != DMX_OK)
+        throw std::invalid_argument(nb_sources > 6 ? std::string("remix_two_stems: more than 6 sources") : std::string(dmx_last_error()));
+    remix_options ro;
+    ro.gains.assign(g, g + n_out * (nb_sources + 1));
+    ro.names.push_back(stems[stem]);
+    if (n_out == 2)
+        ro.names.push_back(std::string("no_") + stems[stem]);
+    return ro;
+}
+// The batch CLI's --remix grammar: NAME=TERMS[,NAME=TERMS...], TERMS a sequence of [+|-][GAIN*]SOURCE (the sign may be left
+// out in front of the first term only). SOURCE: a stem name of an nb_sources-source model, or "mix" (the original mixture).
+// GAIN: a decimal number (digits with at most one point), or NdB = 10^(N/20) evaluated in double and rounded to fp32; behind
+// a term's sign a GAIN may carry a minus of its own ("+-12dB*vocals": 12 dB down; "-12dB*vocals" is minus 12 dB UP).
+// "karaoke=mix-vocals,backing=drums+bass+other+-12dB*vocals" -> two outputs. A source may appear once per output; names
+// are file name parts: not empty, no '/', no duplicates. Throws std::invalid_argument naming the bad term.
+inline remix_options parse_remix(const std::string &text, int nb_sources)
+{
+    static const char *stems[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
+    auto bad = [](const std::string &what) -> std::invalid_argument { return std::invalid_argument("remix: " + what); };
+    if (nb_sources < 1 || nb_sources > 6)
+        throw bad("nb_sources " + std::to_string(nb_sources) + " (1 to 6)");
+    remix_options ro;
+    const size_t W = (size_t)nb_sources + 1;
+    for (size_t pos = 0;;)
+    {
+        const size_t comma = text.find(',', pos);
+        const std::string item = text.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos)
+            throw bad("'" + item + "': expected NAME=TERMS");
+        const std::string name = item.substr(0, eq), terms = item.substr(eq + 1);
+        if (name.empty())
+            throw bad("'" + item + "': empty output name");
+        if (name.find('/') != std::string::npos)
+            throw bad("output name '" + name + "' contains '/'");
+        if (std::find(ro.names.begin(), ro.names.end(), name) != ro.names.end())
+            throw bad("output name '" + name + "' given twice");
+        if (terms.empty())
+            throw bad("output '" + name + "': no terms");
+        if ((int)ro.names.size() == DMX_MAX_OUTPUTS)
+            throw bad("more than " + std::to_string(DMX_MAX_OUTPUTS) + " outputs");
+        std::vector<float> row(W, 0.0f);
+        std::vector<bool> seen(W, false);
+        for (size_t i = 0; i < terms.size();)
+        {
+            const size_t t0 = i;
+            float sign = 1.0f;
+            if (terms[i] == '+' || terms[i] == '-')
+                sign = terms[i++] == '-' ? -1.0f : 1.0f;
+            else if (i != 0)
+                throw bad("output '" + name + "': internal error"); // cannot happen: a term ends at a sign
+            bool gneg = false;
+            if (i < terms.size() && terms[i] == '-' && i > t0) // the gain's own minus, behind the term's sign
+                gneg = true, ++i;
+            size_t e = i;
+            while (e < terms.size() && terms[e] != '+' && terms[e] != '-')
+                ++e;
+            const std::string term = terms.substr(t0, e - t0), body = terms.substr(i, e - i);
+            const size_t star = body.find('*');
+            std::string source = body;
+            double gain = 1.0;
+            if (star != std::string::npos)
+            {
+                source = body.substr(star + 1);
+                std::string num = body.substr(0, star);
+                const bool db = num.size() >= 2 && num.compare(num.size() - 2, 2, "dB") == 0;
+                if (db)
+                    num.resize(num.size() - 2);
+                size_t digits = 0, points = 0;
+                for (char ch : num)
+                    digits += ch >= '0' && ch <= '9', points += ch == '.';
+                if (digits == 0 || points > 1 || digits + points != num.size())
+                    throw bad("output '" + name + "', term '" + term + "': bad gain '" + body.substr(0, star) + "'");
+                gain = std::strtod(num.c_str(), nullptr);
+                if (gneg)
+                    gain = -gain;
+                if (db)
+                    gain = std::pow(10.0, gain / 20.0);
+            }
+            else if (gneg)
+                throw bad("output '" + name + "', term '" + term + "': bad gain '-'");
+            const float g = sign * (float)gain;
+            if (!std::isfinite(g))
+                throw bad("output '" + name + "', term '" + term + "': the gain is not finite");
+            int src = -1;
+            if (source == "mix")
+                src = nb_sources;
+            else
+                for (int k = 0; k < nb_sources; ++k)
+                    if (source == stems[k])
+                        src = k;
+            if (src < 0)
+                throw bad("output '" + name + "', term '" + term + "': unknown source '" + source + "' (a stem of the " +
+                          std::to_string(nb_sources) + "-source model, or mix)");
+            if (seen[(size_t)src])
+                throw bad("output '" + name + "', term '" + term + "': source '" + source + "' appears twice");
+            seen[(size_t)src] = true, row[(size_t)src] = g;
+            i = e;
+        }
+        ro.names.push_back(name);
+        ro.gains.insert(ro.gains.end(), row.begin(), row.end());
+        if (comma == std::string::npos)
+            break;
+        pos = comma + 1;
+    }
+    return ro;
+}
+namespace detail
+{
+// one call of dmx_tracks_infer_remix: models NULL / Q 0 (the context's model) or a bag; shifts as the caller's path lays them out
+inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *models, int Q, const float *w, int S,
+                             const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts, const ProgressCallback &cb,
+                             const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks)
+{
+    const size_t T = tracks.size();
+    PcmOutputs out(T);
+    const int n_out = (int)ro.names.size();
+    if (ro.gains.size() != (size_t)n_out * (size_t)(S + 1))
+    {
+        std::cerr << who << ": " << ro.gains.size() << " gains for " << n_out << " outputs x (" << S << " stems + the mixture)" << std::endl;
+        std::exit(1);
+    }
+    const dmx_remix_spec spec{ro.encoding, ro.clip, n_out, ro.gains.data()};
+    if (dmx_remix_check(S, &spec) != DMX_OK)
+        die(who);
+    const dmx_output_spec ospec{ro.encoding, ro.clip, -1};
+    std::vector<const float *> in(T);
+    std::vector<std::vector<unsigned char>> flat(T); // a track's outputs are consecutive across the ABI
+    std::vector<void *> dst(T);
+    std::vector<int64_t> n(T);
+    for (size_t t = 0; t < T; ++t)
+    {
+        in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
+        const int64_t per = dmx_output_bytes(&ospec, n[t]);
+        if (per < 0)
+            die(who);
+        flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
+        dst[t] = flat[t].data();
+    }
+    std::vector<float> pk(T * (size_t)n_out, 0.0f);
+    CbThunk th{&cb};
+    if (!c || dmx_tracks_infer_remix(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(),
+                                     pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
+        die(who);
+    for (size_t t = 0; t < T; ++t)
+    {
+        const size_t per = (size_t)dmx_output_bytes(&ospec, n[t]);
+        for (int o = 0; o < n_out; ++o)
+            out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)(o + 1) * per);
+        flat[t] = std::vector<unsigned char>();
+    }
+    if (peaks)
+    {
+        peaks->assign(T, std::vector<float>());
+        for (size_t t = 0; t < T; ++t)
+            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
+    }
+    return out;
+}
+inline PcmOutputs batch_call_remix(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks,
+                                   const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
+                                   std::vector<std::vector<float>> *peaks)
+{
+    const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
+    if (T == 0)
+        return PcmOutputs();
+    std::vector<int> shifts(T * N, model.shift_offset);
+    if (opts.shift_offsets.size() == N)
+        for (size_t i = 0; i < shifts.size(); ++i)
+            shifts[i] = opts.shift_offsets[i % N];
+    else if (opts.shift_offsets.size() == T * N)
+        shifts = opts.shift_offsets;
+    else if (!opts.shift_offsets.empty())
+    {
+        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
+        std::exit(1);
+    }
+    std::lock_guard<std::mutex> guard(model.lock);
+    return remix_call(who, dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, dmx_engine_n_sources(model.engine), tracks, shifts, cb,
+                      opts, ro, peaks);
+}
+} // namespace detail
+inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                               const inference_options &opts, const remix_options &remix,
+                                               std::vector<std::vector<float>> *peaks = nullptr)
+{
+    return detail::batch_call_remix("demucs_inference_batch_remix", model, tracks, cb, opts, remix, peaks);
+}
+
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
 // reference runs four demucs_inference calls back to back; calling demucs_inference on four demucs_model
 // objects still works here, but one bag engine deals all (model, segment) items over the devices at once
@@ -600,6 +810,19 @@ inline PcmOutputs demucs_inference_batch_pcm(const demucs_bag &bag, const std::v
     }
     return out;
 }
+inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                               const std::vector<float> &weights, const inference_options &opts, const remix_options &remix,
+                                               std::vector<std::vector<float>> *peaks = nullptr)
+{
+    const char *who = "demucs_inference_batch_remix (bag)";
+    if (tracks.empty())
+        return PcmOutputs();
+    const std::vector<int> shifts = detail::bag_shifts(who, bag, tracks.size(), opts);
+    const float *w = detail::bag_weights(who, bag, weights);
+    std::lock_guard<std::mutex> guard(bag.lock);
+    return detail::remix_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, tracks, shifts, cb, opts, remix,
+                              peaks);
+}
 
 // segment-level surface; src/model.hpp:569-647 (only the boundary members are kept:
 // `mix` in, `targets_out` out - every intermediate lives in the HBM arena)
@@ -746,6 +969,13 @@ inline demucscpp::PcmOutputs demucs_v3_inference_batch_pcm(const demucs_v3_model
                                                            std::vector<std::vector<float>> *peaks = nullptr)
 {
     return demucscpp::detail::batch_call_pcm("demucs_v3_inference_batch_pcm", model, tracks, cb, opts, out_opts, peaks);
+}
+inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
+                                                             ProgressCallback cb, const demucscpp::inference_options &opts,
+                                                             const demucscpp::remix_options &remix,
+                                                             std::vector<std::vector<float>> *peaks = nullptr)
+{
+    return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix", model, tracks, cb, opts, remix, peaks);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

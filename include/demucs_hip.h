@@ -267,6 +267,59 @@ extern "C"
     int dmx_pcm_encode(int device, const float *planes, int n_sources, int64_t n, const dmx_output_spec *spec, void *out,
                        float *peaks);
 
+    /* ---- remixed outputs (csrc/pcm.hip; DESIGN.md section 2.10, restated in tests/remix_spec.py; no reference counterpart).
+     * The output stage generalised from "a stem, or the sum of the others" to a gain matrix over the stems and the original
+     * mixture: demucs's --other-method add | minus | none, and what a user mixes from the stems afterwards ("everything with
+     * the vocals 12 dB down", "the residual the model left over"), formed on the GPU so that only the wanted bytes leave it.
+     * Sources: src[0..S) the S stems exactly as dmx_tracks_infer_opts (dmx_tracks_infer_bag on the bag path) writes them;
+     * src[S] the MIXTURE: the caller's track as passed in, frames [0, n), not normalised and not shifted. A spec has n_out
+     * outputs and a row-major gain matrix g[n_out][S + 1] (last column: the mixture). Output o, channel c, frame i, all fp32:
+     * the sources are visited in increasing index; a source with g[o][s] == 0 is skipped and NOT READ (a NaN in a stem nobody
+     * asked for does not spread); the first visited source gives a = g * x, each later one p = g * x, a = a + p. Every product
+     * and every sum is its own correctly rounded fp32 operation: there is NO fused multiply-add, so plain float32 arithmetic
+     * restates it exactly. Peak, clip and encode of each output are then those of the specification above (peak over both
+     * channels and all frames with NaN ignored, the rescale divisor from that output's own peak, ties to even).
+     * Consequences: 0/1 gains give dmx_output_spec's outputs bit for bit (1 * x is exact); the row -1 on a stem, +1 on the
+     * mixture gives exactly the fp32 mixture - stem. */
+#define DMX_MAX_OUTPUTS 8
+#define DMX_OTHER_ADD 0   /* two outputs: the stem, the other stems added (dmx_output_spec's two-stems) */
+#define DMX_OTHER_MINUS 1 /* two outputs: the stem, mixture - stem                                    */
+#define DMX_OTHER_NONE 2  /* one output: the stem                                                     */
+    typedef struct dmx_remix_spec
+    {
+        int encoding, clip, n_out; /* DMX_PCM_*, DMX_CLIP_*, 1 .. DMX_MAX_OUTPUTS */
+        const float *gains;        /* n_out x (n_sources + 1), row-major, last column = the mixture */
+    } dmx_remix_spec;
+    /* the matrices of demucs's three --other-method's for `stem` of an n_sources-source model (n_sources <= 6): gains_out
+     * holds 2 x (n_sources + 1) floats, *n_out becomes 2 (add, minus) or 1 (none). Pure host function. */
+    int dmx_remix_two_stems(int n_sources, int stem, int method, float *gains_out, int *n_out);
+    /* validates a spec for a model of n_sources (1 .. 6) sources. Pure host function. Rejected, each with a message of its own
+     * ("remix spec: output 2 has no non-zero gain"): n_out outside [1, DMX_MAX_OUTPUTS], a NULL gain matrix, a non-finite gain
+     * (named by output and source), a row with no non-zero gain, a bad encoding, a bad clip mode. */
+    int dmx_remix_check(int n_sources, const dmx_remix_spec *spec);
+    /* dmx_tracks_infer_pcm under a remix spec. models == NULL and n_models == 0: the context's own model; the fp32 track
+     * behind the gains is the bits of dmx_tracks_infer_opts. Otherwise a bag exactly as dmx_tracks_infer_bag (models, weights,
+     * shift_offsets n_tracks x n_models x n_shifts, the context bound to its model again on return). out[t]: n_out consecutive
+     * chunks of dmx_output_bytes() for the spec's encoding; peaks: NULL or n_out floats per track. Pieces are encoded and
+     * copied out as soon as they are final under DMX_CLIP_NONE / DMX_CLIP_CLAMP and at the track's end under
+     * DMX_CLIP_RESCALE, as dmx_tracks_infer_pcm does. The mixture column reads the track's one upload (interleaved on the
+     * device for either `layout`): there is no second upload. The spec is checked before any GPU work and nothing is written
+     * on error. Device memory: as dmx_tracks_infer_pcm with n_out from the spec - per track slot n_out x dmx_output_bytes(spec,
+     * n_max), each rounded up to 16 bytes, and n_out peaks; with n_out > S at DMX_PCM_F32 the encoded outputs may exceed the
+     * slot's fp32 result (8 float32 outputs of a 4-source model: twice it). The engine stays out of scope. */
+    int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                               const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                               const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
+                               void *user);
+    /* the stage alone on device memory, as dmx_pcm_encode_device: d_mix is the mixture interleaved [n][2] at any 4-byte
+     * alignment; it may be NULL when the mixture column of the gains is all zero (an error, with a message, when it is NULL
+     * and the column is not). d_out, the outputs' stride and d_peaks (n_out floats) as there. */
+    int dmx_remix_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride, const float *d_mix,
+                                const dmx_remix_spec *spec, void *d_out, float *d_peaks, void *stream);
+    /* host buffers: planes [n_sources][2][n], mix [n][2] or NULL; out: n_out consecutive chunks; peaks NULL or n_out */
+    int dmx_remix_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                         void *out, float *peaks);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
