@@ -1,7 +1,7 @@
 // demucs_batch.cpp.main — many tracks in one call (no reference counterpart: the reference's CLIs take one file):
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
-//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--bag-weights w00,w01,...]
+//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--bag-weights w00,w01,...]
 //                         <model> <out dir> <wav file>...
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
 // byte-identical to what demucs.cpp.main / demucs_v3.cpp.main writes for that input alone. The model's architecture
@@ -29,6 +29,9 @@
 //                            demucscpp::demucs_inference_batch_remix.)
 //   --clip-mode MODE         rescale (divide a stem whose peak exceeds 1 / 1.01 by 1.01 peak), clamp (to +-0.99) or none
 //   --int16 --int24 --float32  sample format of the files (these take no value)
+//   --flac                   write target_*.flac instead of target_*.wav (demucs's option; it takes no value): the same samples,
+//                            losslessly coded on the GPU (dmx_tracks_infer_flac; csrc/flac.hip), 16 bit by default, 24 bit
+//                            with --int24; --float32 --flac is an error. It combines with every option above and with bags.
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
 // They are refused for a track that DMX_RESAMPLE=1 converted: converting the stems back needs them in fp32.
 // <model> may also be a bag of models (dmx_tracks_infer_bag through the demucscpp::demucs_bag overloads; every option
@@ -44,6 +47,7 @@
 #include <cerrno>
 #include <cmath>
 #include <filesystem>
+#include <fstream>
 #include <iomanip>
 
 #include "wav.hpp"
@@ -54,7 +58,7 @@ using namespace demucscpp;
 {
     std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
-              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--bag-weights w00,w01,...]"
+              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--bag-weights w00,w01,...]"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
@@ -94,7 +98,7 @@ int main(int argc, const char **argv)
     bool with_bag_weights = false;
     inference_options opts;
     output_options out_opts; // demucs's defaults: 16 bit, rescale
-    bool with_opts = false, with_out_opts = false;
+    bool with_opts = false, with_out_opts = false, flac = false, float32_given = false;
     std::string two_stems, remix_text;
     int other_method = -1; // DMX_OTHER_*, -1: not given
     int a = 1;
@@ -104,7 +108,14 @@ int main(int argc, const char **argv)
         if (opt == "--int16" || opt == "--int24" || opt == "--float32") // no value: step back so that a += 2 moves by one
         {
             out_opts.encoding = opt == "--int16" ? DMX_PCM_S16 : opt == "--int24" ? DMX_PCM_S24 : DMX_PCM_F32;
+            float32_given = opt == "--float32";
             with_out_opts = true;
+            --a;
+            continue;
+        }
+        if (opt == "--flac") // no value either
+        {
+            flac = with_out_opts = true;
             --a;
             continue;
         }
@@ -216,8 +227,13 @@ int main(int argc, const char **argv)
         std::cerr << "--remix and --two-stems exclude each other" << std::endl;
         usage(argv[0]);
     }
-    // minus, none and --remix leave through the remix entry points; everything else as before
-    const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE;
+    if (flac && (float32_given || out_opts.encoding == DMX_PCM_F32))
+    {
+        std::cerr << "--float32 and --flac exclude each other: FLAC holds integer samples (--int16, the default, or --int24)" << std::endl;
+        usage(argv[0]);
+    }
+    // minus, none, --remix and --flac leave through the remix entry points; everything else as before
+    const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE || flac;
     remix_options remix;
     auto make_remix = [&](int nb_sources) { // once the model's stems are known
         if (with_out_opts && out_opts.two_stems >= nb_sources)
@@ -229,14 +245,24 @@ int main(int argc, const char **argv)
             return;
         try
         {
-            remix = remix_text.empty() ? remix_two_stems(nb_sources, out_opts.two_stems, other_method) : parse_remix(remix_text, nb_sources);
+            if (!remix_text.empty())
+                remix = parse_remix(remix_text, nb_sources);
+            else if (out_opts.two_stems >= 0)
+                remix = remix_two_stems(nb_sources, out_opts.two_stems, other_method < 0 ? DMX_OTHER_ADD : other_method);
+            else // --flac alone: every stem, through 0 / 1 gains (the bytes of the output spec)
+            {
+                static const char *stems[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
+                remix.gains.assign((size_t)nb_sources * (size_t)(nb_sources + 1), 0.0f);
+                for (int s = 0; s < nb_sources; ++s)
+                    remix.names.push_back(stems[s]), remix.gains[(size_t)s * (size_t)(nb_sources + 1) + (size_t)s] = 1.0f;
+            }
         }
         catch (const std::exception &e)
         {
             std::cerr << (remix_text.empty() ? "--other-method: " : "--remix: ") << e.what() << std::endl;
             exit(1);
         }
-        remix.encoding = out_opts.encoding, remix.clip = out_opts.clip;
+        remix.encoding = out_opts.encoding, remix.clip = out_opts.clip, remix.flac = flac;
     };
     if (!opts.shift_offsets.empty() && (int)opts.shift_offsets.size() != opts.shifts)
     {
@@ -319,7 +345,7 @@ int main(int argc, const char **argv)
         for (int i = 0; i < n_files; ++i)
             if (native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE)
             {
-                std::cerr << "--two-stems / --other-method / --remix / --clip-mode / --int16 / --int24 / --float32 are not available for a track converted by "
+                std::cerr << "--two-stems / --other-method / --remix / --clip-mode / --int16 / --int24 / --float32 / --flac are not available for a track converted by "
                           << "DMX_RESAMPLE=1 (" << argv[3 + i] << ", " << native_rate[(size_t)i]
                           << " Hz): converting the stems back needs them in fp32" << std::endl;
                 exit(1);
@@ -418,9 +444,18 @@ int main(int argc, const char **argv)
                 const std::string name = with_remix               ? remix.names[target]
                                          : out_opts.two_stems < 0 ? names[target]
                                                                   : (target == 0 ? two_stems : "no_" + two_stems);
-                auto p_target = p / ("target_" + std::to_string(target) + "_" + name + ".wav");
-                std::cout << "Writing wav file " << p_target << std::endl;
-                if (!wavio::write_pcm_file(po[target].data(), audio.cols(), out_opts.encoding, p_target.string()))
+                auto p_target = p / ("target_" + std::to_string(target) + "_" + name + (flac ? ".flac" : ".wav"));
+                std::cout << "Writing " << (flac ? "flac" : "wav") << " file " << p_target << std::endl;
+                bool ok;
+                if (flac) // a complete file already
+                {
+                    std::ofstream f(p_target.string(), std::ios::binary);
+                    f.write(reinterpret_cast<const char *>(po[target].data()), (std::streamsize)po[target].size());
+                    ok = (bool)f;
+                }
+                else
+                    ok = wavio::write_pcm_file(po[target].data(), audio.cols(), out_opts.encoding, p_target.string());
+                if (!ok)
                 {
                     std::cerr << "Error writing " << p_target << std::endl;
                     exit(1);

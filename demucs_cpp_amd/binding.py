@@ -38,6 +38,7 @@ EXPORTS = [
     "dmx_output_count", "dmx_output_bytes", "dmx_tracks_infer_pcm", "dmx_pcm_encode_device", "dmx_pcm_encode",
     "dmx_bag_weights", "dmx_tracks_infer_bag",
     "dmx_remix_two_stems", "dmx_remix_check", "dmx_tracks_infer_remix", "dmx_remix_encode_device", "dmx_remix_encode",
+    "dmx_flac_bound", "dmx_flac_workspace_bytes", "dmx_flac_encode_device", "dmx_flac_encode", "dmx_tracks_infer_flac",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -147,6 +148,13 @@ def lib():
         L.dmx_tracks_infer_remix.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ci, vp, vp]
         L.dmx_remix_encode_device.argtypes = [ci, vp, ci, i64, i64, vp, vp, vp, vp, vp]
         L.dmx_remix_encode.argtypes = [ci, vp, ci, i64, vp, vp, vp, vp]
+        L.dmx_flac_bound.argtypes = [ci, i64]
+        L.dmx_flac_bound.restype = i64
+        L.dmx_flac_workspace_bytes.argtypes = [ci, i64]
+        L.dmx_flac_workspace_bytes.restype = i64
+        L.dmx_flac_encode_device.argtypes = [ci, vp, ci, i64, ci, vp, vp, vp, vp]
+        L.dmx_flac_encode.argtypes = [ci, vp, ci, i64, ci, vp, vp]
+        L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
         L.dmx_track_gather_device.argtypes = [vp, fp, i64, fp, ci, vp, ci, fp]
@@ -495,6 +503,52 @@ class Context:
         ospec = spec.output_spec()
         return [pcm_views(b, ospec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
 
+    def tracks_flac(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
+                    shift_offsets=None, sample_rate: int = 44100, progress=None, layout: int = LAYOUT_PLANAR, out=None, sizes=None,
+                    peaks=None):
+        """tracks_remix() whose outputs leave as .flac files (dmx_tracks_infer_flac): spec.encoding PCM_S16 or PCM_S24.
+        Returns (files, peaks): files[t][o] the bytes of track t's output o, peaks as tracks_remix(). `out`: buffers to reuse
+        (np.uint8 of n_out * flac_bound(bits, n) bytes per track); `sizes`: a flat np.int64 array of at least T * n_out."""
+        T = len(audios)
+        Q = 0 if models is None else len(models)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        n_out = max(spec.n_out, 0)
+        bits = 24 if spec.encoding == PCM_S24 else 16
+        bounds = [max(flac_bound(bits, n), 0) if n >= 1 else 0 for n in ns]
+        bufs = out if out is not None else [np.zeros(max(n_out * b, 1), np.uint8) for b in bounds]
+        assert len(bufs) == T
+        for b, bd in zip(bufs, bounds):
+            assert b.dtype == np.uint8 and b.ndim == 1 and b.size >= n_out * bd and b.flags.c_contiguous
+        if sizes is None:
+            sizes = np.zeros(max(T * n_out, 1), np.int64)
+        assert sizes.dtype == np.int64 and sizes.ndim == 1 and sizes.size >= T * n_out and sizes.flags.c_contiguous
+        if peaks is None:
+            peaks = np.zeros(max(T * n_out, 1), np.float32)
+        assert peaks.dtype == np.float32 and peaks.ndim == 1 and peaks.size >= T * n_out and peaks.flags.c_contiguous
+        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
+        wp = None
+        if weights is not None:
+            warr = np.ascontiguousarray(weights, np.float32)
+            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
+            wp = warr.ctypes.data
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
+            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        _chk(lib().dmx_tracks_infer_flac(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec.c),
+                                         int(sample_rate), op, sizes.ctypes.data, peaks.ctypes.data, layout, cbp, None))
+        files = [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))]
+        return files, [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:
         ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         _chk(lib().dmx_track_geometry(self.h, n, shift_offset, ctypes.byref(ln), ctypes.byref(ns), ctypes.byref(st)))
@@ -632,6 +686,29 @@ def remix_encode(planes: np.ndarray, mix: Optional[np.ndarray], spec: RemixSpec,
     _chk(lib().dmx_remix_encode(device, planes.ctypes.data, S, n, None if mi is None else mi.ctypes.data, ctypes.byref(spec.c),
                                 buf.ctypes.data, peaks.ctypes.data))
     return pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out]
+
+
+def flac_bound(bits: int, n: int) -> int:
+    """an upper bound of the .flac file of n frames of `bits` (16 | 24) bit stereo (dmx_flac_bound; no GPU); raises on a bad argument"""
+    b = lib().dmx_flac_bound(int(bits), int(n))
+    if b < 0:
+        raise DmxError(5, f"dmx_flac_bound: bad argument (bits {bits}, n {n})")
+    return b
+
+
+def flac_encode(pcm: np.ndarray, bits: int, sample_rate: int = 44100, device: int = 0) -> bytes:
+    """The FLAC stage alone (dmx_flac_encode): pcm as the PCM stage returns it - np.int16 (n, 2) for bits 16, np.uint8
+    (n, 2, 3) for bits 24 - -> the bytes of the .flac file."""
+    pcm = np.ascontiguousarray(pcm)
+    if bits == 16:
+        assert pcm.dtype == np.int16 and pcm.ndim == 2 and pcm.shape[1] == 2
+    else:
+        assert pcm.dtype == np.uint8 and pcm.ndim == 3 and pcm.shape[1:] == (2, 3)
+    n = pcm.shape[0]
+    out = np.zeros(max(lib().dmx_flac_bound(int(bits), n), 1), np.uint8)
+    size = ctypes.c_int64(0)
+    _chk(lib().dmx_flac_encode(device, pcm.ctypes.data, int(bits), n, int(sample_rate), out.ctypes.data, ctypes.byref(size)))
+    return bytes(out[:size.value])
 
 
 def resample_length(n_in: int, rate_in: int, rate_out: int) -> int:

@@ -724,7 +724,7 @@ dmx_ctx::~dmx_ctx()
     {
         if (sl.copied)
             (void)hipEventDestroy(sl.copied);
-        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks})
+        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes})
             if (b->p)
                 (void)hipFree(b->p);
     }
@@ -1399,6 +1399,9 @@ struct PcmOut // the output spec of a call, checked (pcm_check_spec)
     float *peaks;
     int nOut, frameBytes;
     const PcmGains *remix = nullptr; // dmx_tracks_infer_remix: the outputs are rows of gains over the stems and the mixture
+    // dmx_tracks_infer_flac (flacBits 16 | 24, else 0): out[t] takes n_out files at a stride of dmx_flac_bound, sizes their byte counts
+    int flacBits = 0, flacRate = 0;
+    int64_t *sizes = nullptr;
 };
 struct PcmRange // frames [lo, hi) of track t encoded behind one batch
 {
@@ -1619,6 +1622,12 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
         {
             DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(nmax * pcm->frameBytes) / 4)));
             DMXCHK(dmx_ensure_buf(sl.peaks, 8));
+            if (pcm->flacBits)
+            {
+                DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, nmax) / 4)));
+                DMXCHK(dmx_ensure_buf(sl.flacWork, (i64)pcm->nOut * (flac_workspace_bytes(pcm->flacBits, nmax) / 4)));
+                DMXCHK(dmx_ensure_buf(sl.flacSizes, 2 * DMX_MAX_OUTPUTS));
+            }
         }
         if (!sl.copied)
             HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
@@ -1655,7 +1664,28 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
                 const bool last = r.hi == j.n;
                 const i64 lo = wholeTrack ? 0 : r.lo, fb = pcm->frameBytes;
                 const i64 outBytes = j.n * fb, devStride = DMX_OUTPUT_STRIDE(outBytes);
-                if (!wholeTrack || last)
+                if (pcm->flacBits)
+                {
+                    if (!last)
+                        continue;
+                    // the files' byte counts first (the batch that made them is done once its event is; the next batch is
+                    // already enqueued), then one copy per output of exactly its length
+                    int64_t *sz = pcm->sizes + (size_t)r.t * pcm->nOut;
+                    HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
+                    HIPCHK(hipMemcpyAsync(sz, sl.flacSizes.p, sizeof(int64_t) * (size_t)pcm->nOut, hipMemcpyDeviceToHost, c->copyStream));
+                    HIPCHK(hipStreamSynchronize(c->copyStream));
+                    const i64 bound = flac_bound(pcm->flacBits, j.n);
+                    for (int o = 0; o < pcm->nOut; ++o)
+                    {
+                        if (sz[o] < 42 || sz[o] > bound)
+                            return fail(DMX_ERR_HIP, "%s: internal error (track %d, output %d: %lld encoded bytes, bound %lld)", fn, r.t, o,
+                                        (long long)sz[o], (long long)bound);
+                        HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[r.t] + (size_t)(o * bound),
+                                              (const unsigned char *)sl.flac.p + (size_t)(o * bound), (size_t)sz[o], hipMemcpyDeviceToHost,
+                                              c->copyStream));
+                    }
+                }
+                else if (!wholeTrack || last)
                     for (int o = 0; o < pcm->nOut; ++o)
                         HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[r.t] + (size_t)(o * outBytes + lo * fb),
                                               (const unsigned char *)sl.pcm.p + (size_t)(o * devStride + lo * fb), (size_t)((r.hi - lo) * fb),
@@ -1863,6 +1893,17 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
                 const std::vector<PcmPiece> &enc = wholeTrack ? pcmWhole : pcmPieces;
                 launch_pcm_encode(enc.data(), (int)enc.size(), S, pcm->spec.stem, pcm->spec.encoding, pcm->spec.clip, c->stream);
             }
+            if (pcm->flacBits) // a track whose PCM is complete: its files
+                for (const PcmRange &r : pcmPlan[(size_t)k])
+                {
+                    const TrackJob &j = jobs[(size_t)r.t];
+                    if (r.hi != j.n)
+                        continue;
+                    const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
+                    launch_flac_encode((const unsigned char *)sl.pcm.p, DMX_OUTPUT_STRIDE(j.n * pcm->frameBytes), pcm->flacBits, j.n,
+                                       pcm->flacRate, pcm->nOut, (unsigned char *)sl.flac.p, flac_bound(pcm->flacBits, j.n),
+                                       (long long *)sl.flacSizes.p, (unsigned char *)sl.flacWork.p, c->stream);
+                }
             HIPCHK(hipGetLastError());
         }
         hipEvent_t ev = dmx_batch_event(c, (size_t)k);
@@ -2216,7 +2257,7 @@ extern "C" int dmx_bag_weights(int n_models, int n_sources, const float *weights
 static int tracks_bag_run(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
                           const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
                           const dmx_output_spec *spec, const dmx_remix_spec *remix, void *const *out, float *peaks, int layout,
-                          dmx_progress_fn progress, void *user)
+                          dmx_progress_fn progress, void *user, int flacRate = 0, int64_t *flacSizes = nullptr)
 {
     if (!c)
         return fail(DMX_ERR_ARG, "%s: null context", fn);
@@ -2251,9 +2292,11 @@ static int tracks_bag_run(const char *fn, dmx_ctx *c, const dmx_model *const *mo
     if (!spec && !remix)
         return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), reinterpret_cast<float *const *>(out), layout, progress,
                           user, nullptr, &bag);
-    const PcmOut pcm = remix ? PcmOut{dmx_output_spec{remix->encoding, remix->clip, -1}, out, peaks, remix->n_out,
-                                      pcm_frame_bytes(remix->encoding), &G}
-                             : PcmOut{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
+    PcmOut pcm = remix ? PcmOut{dmx_output_spec{remix->encoding, remix->clip, -1}, out, peaks, remix->n_out,
+                                pcm_frame_bytes(remix->encoding), &G}
+                       : PcmOut{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
+    if (flacSizes)
+        pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = flacRate, pcm.sizes = flacSizes;
     return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm, &bag);
 }
 
@@ -2327,12 +2370,12 @@ extern "C" int dmx_pcm_encode(int device, const float *planes, int n_sources, in
     return rc;
 }
 
-extern "C" int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
-                                      const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
-                                      const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
-                                      void *user)
+// dmx_tracks_infer_remix, and dmx_tracks_infer_flac (flacSizes given: the outputs leave as .flac files)
+static int tracks_remix_run(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                            const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                            const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress, void *user,
+                            int flacRate = 0, int64_t *flacSizes = nullptr)
 {
-    const char *fn = "dmx_tracks_infer_remix";
     if (!c)
     {
         DMXCHK(remix_check_spec(fn, 0, spec, nullptr, true)); // what of the spec can be checked without a model
@@ -2343,14 +2386,25 @@ extern "C" int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models
     DMXCHK(remix_check_spec(fn, S, spec, &G));
     if (models || n_models != 0)
         return tracks_bag_run(fn, c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, nullptr, spec, out,
-                              peaks, layout, progress, user);
+                              peaks, layout, progress, user, flacRate, flacSizes);
     if (weights)
         return fail(DMX_ERR_ARG, "%s: weights given without models", fn);
     i64 stride = 0;
     DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride));
-    const PcmOut pcm{dmx_output_spec{spec->encoding, spec->clip, -1}, out, peaks, spec->n_out, pcm_frame_bytes(spec->encoding), &G};
+    PcmOut pcm{dmx_output_spec{spec->encoding, spec->clip, -1}, out, peaks, spec->n_out, pcm_frame_bytes(spec->encoding), &G};
+    if (flacSizes)
+        pcm.flacBits = spec->encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = flacRate, pcm.sizes = flacSizes;
     const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
     return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
+}
+
+extern "C" int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                      const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                                      const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
+                                      void *user)
+{
+    return tracks_remix_run("dmx_tracks_infer_remix", c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, spec,
+                            out, peaks, layout, progress, user);
 }
 
 extern "C" int dmx_remix_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
@@ -2415,6 +2469,93 @@ extern "C" int dmx_remix_encode(int device, const float *planes, int n_sources, 
         if (p)
             (void)hipFree(p);
     return rc;
+}
+
+// --------------------------------------------------------------------------- FLAC output (flac.hip)
+extern "C" int64_t dmx_flac_bound(int bits, int64_t n) { return flac_bound(bits, n); }
+extern "C" int64_t dmx_flac_workspace_bytes(int bits, int64_t n) { return flac_workspace_bytes(bits, n); }
+
+static int flac_check(const char *fn, int bits, int64_t n, int sample_rate)
+{
+    if (bits != 16 && bits != 24)
+        return fail(DMX_ERR_ARG, "%s: bits %d (16 or 24)", fn, bits);
+    if (n < 1 || n >= (int64_t)1 << 36)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, must be in [1, 2^36)", fn, (long long)n);
+    if (sample_rate < 1 || sample_rate > 655350)
+        return fail(DMX_ERR_ARG, "%s: sample_rate %d not in [1, 655350]", fn, sample_rate);
+    return DMX_OK;
+}
+
+extern "C" int dmx_flac_encode_device(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, void *d_out, int64_t *d_size,
+                                      void *d_work, void *stream)
+{
+    const char *fn = "dmx_flac_encode_device";
+    DMXCHK(flac_check(fn, bits, n, sample_rate));
+    if (!d_pcm || !d_out || !d_size || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_pcm ? "d_pcm" : !d_out ? "d_out" : !d_size ? "d_size" : "d_work");
+    if (((uintptr_t)d_pcm & 15) != 0 || ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_size & 7) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_pcm and d_work must be 16-byte aligned, d_size 8-byte aligned", fn);
+    HIPCHK(hipSetDevice(device));
+    launch_flac_encode((const unsigned char *)d_pcm, 0, bits, n, sample_rate, 1, (unsigned char *)d_out, 0, (long long *)d_size,
+                       (unsigned char *)d_work, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n, int sample_rate, void *out, int64_t *size)
+{
+    const char *fn = "dmx_flac_encode";
+    DMXCHK(flac_check(fn, bits, n, sample_rate));
+    if (!pcm || !out || !size)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !pcm ? "pcm" : !out ? "out" : "size");
+    HIPCHK(hipSetDevice(device));
+    const size_t inBytes = (size_t)n * 2 * (size_t)(bits / 8);
+    const i64 bound = flac_bound(bits, n), workBytes = flac_workspace_bytes(bits, n);
+    unsigned char *dIn = nullptr, *dOut = nullptr, *dWork = nullptr;
+    int64_t *dSize = nullptr;
+    int64_t got = 0;
+    int rc = DMX_OK;
+    if (hipMalloc((void **)&dIn, DMX_OUTPUT_STRIDE(inBytes)) != hipSuccess || hipMalloc((void **)&dOut, (size_t)bound) != hipSuccess ||
+        hipMalloc((void **)&dWork, (size_t)workBytes) != hipSuccess || hipMalloc((void **)&dSize, sizeof(int64_t)) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK && hipMemcpy(dIn, pcm, inBytes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    if (rc == DMX_OK)
+        rc = dmx_flac_encode_device(device, dIn, bits, n, sample_rate, dOut, dSize, dWork, nullptr);
+    if (rc == DMX_OK && hipDeviceSynchronize() != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (rc == DMX_OK && hipMemcpy(&got, dSize, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    if (rc == DMX_OK && (got < 42 || got > bound))
+        rc = fail(DMX_ERR_HIP, "%s: internal error (%lld encoded bytes, bound %lld)", fn, (long long)got, (long long)bound);
+    if (rc == DMX_OK && hipMemcpy(out, dOut, (size_t)got, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    for (void *p : {(void *)dIn, (void *)dOut, (void *)dWork, (void *)dSize})
+        if (p)
+            (void)hipFree(p);
+    if (rc == DMX_OK)
+        *size = got;
+    return rc;
+}
+
+extern "C" int dmx_tracks_infer_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                     const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                                     const dmx_remix_spec *spec, int sample_rate, void *const *out, int64_t *sizes, float *peaks, int layout,
+                                     dmx_progress_fn progress, void *user)
+{
+    const char *fn = "dmx_tracks_infer_flac";
+    DMXCHK(remix_check_spec(fn, 0, spec, nullptr, true)); // what of the spec can be checked without a model
+    if (spec->encoding == DMX_PCM_F32)
+        return fail(DMX_ERR_ARG, "%s: remix spec: encoding DMX_PCM_F32 has no FLAC form (DMX_PCM_S16 1 or DMX_PCM_S24 2)", fn);
+    if (!sizes)
+        return fail(DMX_ERR_ARG, "%s: null sizes array", fn);
+    if (sample_rate < 1 || sample_rate > 655350)
+        return fail(DMX_ERR_ARG, "%s: sample_rate %d not in [1, 655350]", fn, sample_rate);
+    for (int t = 0; n && t < n_tracks; ++t)
+        if (n[t] >= (int64_t)1 << 36)
+            return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be < 2^36", fn, t, (long long)n[t]);
+    return tracks_remix_run(fn, c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, spec, out, peaks, layout,
+                            progress, user, sample_rate, sizes);
 }
 
 // --------------------------------------------------------------------------- debug

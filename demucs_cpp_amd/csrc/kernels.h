@@ -411,6 +411,16 @@ struct RemixTable
 };
 void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s);
 void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// ---- the FLAC output stage (flac.hip; specification: DESIGN.md section 2.11, restated in tests/flac_spec.py) ----
+// an upper bound of the encoded stream of n frames of `bits` (16 | 24) bit stereo, a multiple of 16; -1: bad argument
+i64 flac_bound(int bits, i64 n);
+// the workspace ONE output needs (a multiple of 16): the table of frame lengths, their offsets, one bound-sized slot per frame
+i64 flac_workspace_bytes(int bits, i64 n);
+// nOut outputs of interleaved PCM as pcm.hip writes it (output o at pcm + o*pcmStride, 16-byte aligned) -> nOut .flac files
+// (output o at out + o*outStride, any alignment), their byte counts in sizes[o]; work: nOut * flac_workspace_bytes, 16-byte
+// aligned. Three launches on s, no host synchronisation.
+void launch_flac_encode(const unsigned char *pcm, i64 pcmStride, int bits, i64 n, int rate, int nOut, unsigned char *out, i64 outStride,
+                        long long *sizes, unsigned char *work, hipStream_t s);
 // dst[r*dpitch + i] = src[r*spitch + i], r < rows, i < width (floats)
 void launch_copy_rows(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width, int rows, hipStream_t s);
 // dst[i] = fp16 bit pattern of src[i], round to nearest even (the opt-in fp16 weight plane, api.cpp dmx_model_fp16_plane)

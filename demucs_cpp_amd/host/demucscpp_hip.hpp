@@ -394,6 +394,10 @@ struct remix_options
     int clip = DMX_CLIP_RESCALE;
     std::vector<std::string> names;
     std::vector<float> gains;
+    // demucs's --flac (dmx_tracks_infer_flac): the outputs are complete .flac files instead of WAV data, 16 bit for
+    // DMX_PCM_S16 and 24 bit for DMX_PCM_S24 (DMX_PCM_F32 is refused); sample_rate is written into their headers
+    bool flac = false;
+    int sample_rate = 44100;
 };
 // demucs's --two-stems NAME with --other-method add | minus | none (DMX_OTHER_*): outputs "NAME" and, except for none,
 // "no_NAME" (add: the other stems added; minus: mixture - stem). Throws std::invalid_argument with the library's message.
@@ -535,7 +539,16 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
     for (size_t t = 0; t < T; ++t)
     {
         in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
-        const int64_t per = dmx_output_bytes(&ospec, n[t]);
+        int64_t per = dmx_output_bytes(&ospec, n[t]);
+        if (ro.flac)
+        {
+            if (ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24)
+            {
+                std::cerr << who << ": remix_options.flac needs encoding DMX_PCM_S16 or DMX_PCM_S24" << std::endl;
+                std::exit(1);
+            }
+            per = dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]);
+        }
         if (per < 0)
             die(who);
         flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
@@ -543,10 +556,24 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
     }
     std::vector<float> pk(T * (size_t)n_out, 0.0f);
     CbThunk th{&cb};
-    if (!c || dmx_tracks_infer_remix(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(),
+    if (ro.flac)
+    {
+        std::vector<int64_t> sizes(T * (size_t)n_out, 0);
+        if (!c || dmx_tracks_infer_flac(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                        ro.sample_rate, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
+            die(who);
+        for (size_t t = 0; t < T; ++t)
+        {
+            const size_t per = (size_t)dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]);
+            for (int o = 0; o < n_out; ++o)
+                out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)o * per + (size_t)sizes[t * (size_t)n_out + o]);
+            flat[t] = std::vector<unsigned char>();
+        }
+    }
+    else if (!c || dmx_tracks_infer_remix(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(),
                                      pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
         die(who);
-    for (size_t t = 0; t < T; ++t)
+    for (size_t t = 0; !ro.flac && t < T; ++t)
     {
         const size_t per = (size_t)dmx_output_bytes(&ospec, n[t]);
         for (int o = 0; o < n_out; ++o)

@@ -320,6 +320,43 @@ extern "C"
     int dmx_remix_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
                          void *out, float *peaks);
 
+    /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
+     * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
+     * PCM as the stages above write it (16-bit pairs or packed 24 bit) -> a complete .flac file: "fLaC", one STREAMINFO block
+     * (block size 4096, the stream's smallest / largest frame, 36-bit total samples, MD5 all zero = not computed), frames
+     * of 4096 samples (the last: n mod 4096) with FIXED predictors of order 0..4, CONSTANT and VERBATIM subframes, partitioned
+     * Rice coding (partition order <= 4, no escape code) and the four stereo decorrelations - every choice by exact bit
+     * counts with stated tie-breaks, so the bytes are reproducible anywhere. sample_rate (1 .. 655350) is carried in the
+     * headers only; rates other than 44100 / 48000 are written as "from STREAMINFO", which is legal but outside the
+     * streamable subset. Out of scope: LPC predictors, wasted-bits detection, MD5, seek tables, tags, mono / multichannel. */
+    /* an upper bound of the file for n frames of `bits` (16 | 24): 42 + 18 * ceil(n / 4096) + n * 2 * bits / 8, rounded up to
+     * 16. Pure host function; -1 on a bad argument (bits, n < 1, n >= 2^36). */
+    int64_t dmx_flac_bound(int bits, int64_t n);
+    /* bytes of device workspace dmx_flac_encode_device needs for ONE stream (a table of frame lengths and offsets and one
+     * bound-sized slot per frame: a little more than dmx_flac_bound). Pure host function; -1 on a bad argument. */
+    int64_t dmx_flac_workspace_bytes(int bits, int64_t n);
+    /* the stage alone on device memory, asynchronous on `stream`, three launches: d_pcm (16-byte aligned; n frames) ->
+     * d_out (dmx_flac_bound bytes, any alignment), *d_size (an int64 ON THE DEVICE: the file's byte count), d_work
+     * (dmx_flac_workspace_bytes, 16-byte aligned). */
+    int dmx_flac_encode_device(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, void *d_out, int64_t *d_size,
+                               void *d_work, void *stream);
+    /* the same on host buffers: out holds dmx_flac_bound(bits, n) bytes, *size receives the file's byte count */
+    int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n, int sample_rate, void *out, int64_t *size);
+    /* dmx_tracks_infer_remix whose outputs leave as .flac files: the same arguments plus sample_rate and sizes. out[t]: n_out
+     * chunks at a stride of dmx_flac_bound(bits, n[t]); sizes[t * n_out + o]: the byte count of track t's output o; the PCM
+     * behind a file is the bytes dmx_tracks_infer_remix returns for the same arguments (bits 16 for DMX_PCM_S16, 24 for
+     * DMX_PCM_S24; DMX_PCM_F32 is rejected before any GPU work, as is a NULL sizes or a sample_rate outside [1, 655350];
+     * nothing is written on error). The PCM stage runs as there into the slot's buffer (piecewise under DMX_CLIP_NONE /
+     * DMX_CLIP_CLAMP, whole-track under DMX_CLIP_RESCALE); the FLAC stage runs once per track behind its last piece, and only
+     * FLAC bytes are copied out: one device-to-host copy per output of exactly its length, after the byte counts have reached
+     * the host (a wait on the batch's event, taken when the next batch is already enqueued). Device memory: per track slot,
+     * on top of dmx_tracks_infer_remix's, n_out x dmx_flac_bound(bits, n_max) bytes plus n_out x
+     * dmx_flac_workspace_bytes(bits, n_max). dmx_output_spec users go through dmx_remix_two_stems or 0/1 gains. */
+    int dmx_tracks_infer_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                              const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
+                              const dmx_remix_spec *spec, int sample_rate, void *const *out, int64_t *sizes, float *peaks, int layout,
+                              dmx_progress_fn progress, void *user);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
