@@ -6,6 +6,7 @@
 //   demucs_inference   -> dmx_track_infer       (src/model_apply.cpp:60-288)
 // No CPU fallback exists: without a usable HIP device every compute entry point fails.
 #include "api_internal.h"
+#include "tracks_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1237,16 +1238,15 @@ extern "C" int dmx_track_geometry(const dmx_ctx *c, int64_t n, int shift_offset,
 {
     if (!c || n <= 0 || shift_offset < 0 || shift_offset >= DMX_MAX_SHIFT)
         return fail(DMX_ERR_ARG, "dmx_track_geometry: invalid argument");
-    // shifted_audio length = length + max_shift - offset (model_apply.cpp:119-120);
-    // stride = (int)((1 - OVERLAP) * segment) (:162); loop `offset += stride` (:189)
-    const i64 len = n + DMX_MAX_SHIFT - shift_offset;
-    const i64 st = (i64)((1.0f - 0.25f) * (float)c->seg);
+    // OVERLAP = 0.25 (model_apply.cpp:162); the formulas: tracks_plan.h
+    const i64 len = track_shifted_len(n, shift_offset);
+    const i64 st = overlap_stride(c->seg, 0.25f);
     if (shifted_len)
         *shifted_len = len;
     if (stride)
         *stride = st;
     if (n_segments)
-        *n_segments = (int)((len + st - 1) / st);
+        *n_segments = track_n_segments(len, st);
     return DMX_OK;
 }
 
@@ -1315,25 +1315,8 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
 // and their device-to-host copy runs on a second stream underneath the kernels of the following batch (the 339 MB result
 // of a 4-minute track otherwise costs as much wall time after the last kernel as a dozen segments).
 //
-// Several tracks: their segments are laid end to end in track order (global item index) and dealt in batches of
-// max_batch, so a batch may hold the tail of one track and the head of the next. Every kernel serves each of its tracks
-// exactly as it serves a track of its own (misc.hip), so every result is the bits of a call per track.
-// The shifts ensemble (N copies of each track, dmx_tracks_infer_opts): the items of a track are its copies' segments in
-// (row g, copy k) order, a copy absent from the rows past its last segment (the copies' segment counts differ when their
-// shifted lengths straddle a multiple of the stride), so the copies of one stretch of the track are adjacent.
-//   * Segment outputs live in a ring of R blocks: global item G is block G mod R. R is planned on the host before any GPU
-//     work: the largest distance from the first item an overlap-add reads to the end of its batch, rounded up to a multiple
-//     of max_batch, at least 2 max_batch, at most the total number of items. Batch k writes blocks [k B mod R, + nb)
-//     (contiguous: B divides R, or nothing wraps), which the overlap-adds behind batch k-1 and earlier no longer read; all
-//     of it is ordered on the context's stream. One copy at overlap 0.25 reads back one item at most: R = 2 max_batch.
-//   * A piece of a track is final when, for every copy, every segment covering it is done: its end is the minimum over the
-//     copies of "shifted positions below (segments done) * stride".
-//   * A track holds a slot (upload, statistics, result) from the batch of its first item until its last copy-out has
-//     completed. Batch k needs the slots of the tracks with first batch <= k and last batch >= k-1 (the copy-out of batch
-//     k-1 is issued after batch k has been enqueued); the call sizes that many slots for its longest track up front.
-//     A slot whose track finished in batch k-2 or earlier is taken over after a host wait on that track's copy-out event
-//     (its batch is long done).
-//   * A track is uploaded (and its statistics computed) when the first batch that needs it is enqueued.
+// What is dealt into which batch, the pieces, the rings, the track slots and the PCM ranges are planned on the host before
+// any GPU work: tracks_plan.cpp (TracksPlan), which also explains them. The functions below enqueue a plan.
 // The PCM output stage (dmx_tracks_infer_pcm, pcm.hip): with an output spec the overlap-add writes the slot in the planar
 // layout whatever the caller's layout, the peak kernel runs on every finished piece right behind its overlap-add, and the
 // encode kernel turns the planes into interleaved PCM in the slot's staging buffer: per piece when the clip mode needs no
@@ -1341,51 +1324,11 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
 // up to 3 frames left over go with the next piece; the last piece ends at n), and each (output, piece) leaves in ONE copy.
 // A slot then also holds n_out encoded outputs of n_max frames (each rounded up to 16 bytes; at most the size of its fp32
 // result) and n_out peaks. Without a spec nothing of this exists: the same launches and copies as before.
-// A bag of Q models (dmx_tracks_infer_bag): the call has a model dimension. A track is uploaded once
-// and its statistics are computed once; model q's items are the (track, row, copy) sequence above for its own shifts, in a
-// sequence and a ring of its own (each ring sized by the rule above from the reach of the overlap-adds into THAT model's
-// items); a batch holds items of one model, and the context is rebound (dmx_ctx_set_model) between batches. The next batch
-// is always dealt from the model that lags furthest behind - the one whose next item has the lowest (track, row), the lowest
-// q on a tie - so the models advance through the tracks abreast (round-robin when their shifts agree) and no ring has to
-// span more than the other models' batch in flight: the memory bound stays independent of the number and length of tracks.
-// A piece is final when every copy of every model has covered it; one launch of track_ola_bag_kernel combines the rings, and
-// the peak / encode stage and the copy-out follow unchanged. One model through the old entry points (no bag) is the
-// sequence of launches it was.
+// A bag of Q models (dmx_tracks_infer_bag): a batch holds items of one model, and the context is
+// rebound (dmx_ctx_set_model) between batches; one launch of track_ola_bag_kernel combines the rings, and the peak / encode
+// stage and the copy-out follow unchanged. One model through the old entry points (no bag) is the sequence of launches it was.
 namespace
 {
-struct TrackJob
-{
-    const float *audio;
-    float *out;
-    i64 n, done;
-    int kFirst, kLast, slot; // the first / last batch (of any model) holding an item of the track
-};
-struct TrackModel // one model's items of one track
-{
-    i64 g0, m; // g0: index of the track's first item in the model's sequence; m: its items (the sum of its copies' segment counts)
-    int c0, nMin, nMax; // c0: its first copy; nMin / nMax: the fewest / most segments of a copy
-};
-struct TrackCopy
-{
-    i64 len;
-    int shift, nseg, segDone;
-};
-struct TrackPiece
-{
-    int t;
-    i64 lo, hi;
-    size_t item0; // pieceItems[item0 + q]: the first item (within the track, of model q) the piece's overlap-add reads
-};
-struct TrackItem
-{
-    int t, k, g;
-};
-struct TrackBatch
-{
-    int q;  // the model
-    i64 g0; // its first item, in the model's sequence
-    int nb;
-};
 struct BagRun // the models of a call and their effective weights [Q][S] (dmx_bag_weights)
 {
     const dmx_model *const *models;
@@ -1398,225 +1341,68 @@ struct PcmOut // the output spec of a call, checked (pcm_check_spec)
     void *const *out;
     float *peaks;
     int nOut, frameBytes;
-    const PcmGains *remix = nullptr; // dmx_tracks_infer_remix: the outputs are rows of gains over the stems and the mixture
+    const PcmGains *remix; // dmx_tracks_infer_remix: the outputs are rows of gains over the stems and the mixture, else NULL
     // dmx_tracks_infer_flac (flacBits 16 | 24, else 0): out[t] takes n_out files at a stride of dmx_flac_bound, sizes their byte counts
-    int flacBits = 0, flacRate = 0;
-    int64_t *sizes = nullptr;
+    int flacBits, flacRate;
+    int64_t *sizes;
 };
-struct PcmRange // frames [lo, hi) of track t encoded behind one batch
+// One call of the track path. shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches
+// track_ola_kernel and N >= 2 track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
+// pcm: NULL (fp32 results into out[t]), else the results leave as PCM (pcm->out[t]) and `out` is not used
+struct TracksRun
 {
-    int t;
-    i64 lo, hi;
+    dmx_ctx *c = nullptr;
+    const char *fn = nullptr;
+    int T = 0;
+    const float *const *audio = nullptr;
+    const int64_t *n = nullptr;
+    int N = 1;
+    i64 stride = 0;
+    const int *shifts = nullptr;
+    float *const *out = nullptr;
+    int layout = DMX_LAYOUT_EIGEN;
+    dmx_progress_fn progress = nullptr;
+    void *user = nullptr;
+    const PcmOut *pcm = nullptr;
+    const BagRun *bag = nullptr;
+    // set by tracks_run_impl
+    TracksPlan plan;
+    int S = 0, eigen = 0, olaEigen = 0;
+    i64 blk = 0;
+    bool wholeTrack = false; // encode when the track's peak is complete
+    std::vector<const float *> rings;
+    // the tables of the batch being enqueued
+    std::vector<TrackSegItem> batchItems;
+    std::vector<TrackOlaEntry> ola;
+    std::vector<TrackEnsPiece> ens;
+    std::vector<TrackEnsCopy> ensCopies;
+    std::vector<TrackBagPiece> bagPieces;
+    std::vector<TrackBagModel> bagModels;
+    std::vector<RemixPiece> pieces, whole; // the PCM stage's; under a remix spec the mixture is the slot's upload
+    std::vector<PcmPiece> pcmPeak, pcmEnc;  // the same without the mixture, for the kernels of an output spec
+
+    const dmx_ctx::TrackSlot &slot(int t) const { return c->slots[(size_t)plan.jobs[(size_t)t].slot]; }
 };
-// item index of (row g, copy k) within a track (misc.hip ens_item)
-i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
-{
-    if (g < nMin)
-        return g * N + k;
-    i64 it = 0;
-    for (int q = 0; q < N; ++q)
-    {
-        const i64 nq = cp[q].nseg;
-        it += std::min<i64>(g, nq);
-        if (q < k && nq > g)
-            ++it;
-    }
-    return it;
-}
 } // namespace
 
-// stride = (int)((1 - overlap) * segment), evaluated in fp32 (model_apply.cpp:162)
-static i64 overlap_stride(i64 seg, float overlap) { return (i64)((1.0f - overlap) * (float)seg); }
-
-// shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches track_ola_kernel and N >= 2
-// track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
-// pcm: NULL (fp32 results into out[t]), else the results leave as PCM (pcm->out[t]) and `out` is not used
-static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
-                           const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user, const PcmOut *pcm,
-                           const BagRun *bag)
+// the context's buffers, streams and events for the plan
+static int tracks_prepare(TracksRun &r)
 {
-    HIPCHK(hipSetDevice(c->m->device));
-    const int S = c->m->pm.n_sources, B = c->maxBatch, Q = bag ? bag->Q : 1;
-    const i64 seg = c->seg, blk = (i64)S * 2 * seg;
-    std::vector<TrackJob> jobs((size_t)T);
-    std::vector<TrackModel> tm((size_t)T * Q);
-    std::vector<TrackCopy> copies((size_t)T * Q * N);
-    std::vector<i64> M((size_t)Q, 0);
-    i64 Mtot = 0, nmax = 0;
-    for (int t = 0; t < T; ++t)
-    {
-        TrackJob &j = jobs[(size_t)t];
-        j.audio = audio[t], j.out = out ? out[t] : nullptr, j.n = n[t], j.done = 0, j.slot = -1, j.kFirst = INT_MAX, j.kLast = -1;
-        for (int q = 0; q < Q; ++q)
-        {
-            TrackModel &x = tm[(size_t)t * Q + q];
-            x.c0 = (t * Q + q) * N, x.m = 0, x.nMin = INT_MAX, x.nMax = 0;
-            for (int k = 0; k < N; ++k)
-            {
-                TrackCopy &cp = copies[(size_t)(x.c0 + k)];
-                cp.shift = shifts[x.c0 + k], cp.segDone = 0;
-                cp.len = j.n + DMX_MAX_SHIFT - cp.shift; // dmx_track_geometry_overlap
-                cp.nseg = (int)((cp.len + stride - 1) / stride);
-                x.nMin = std::min(x.nMin, cp.nseg), x.nMax = std::max(x.nMax, cp.nseg);
-                x.m += cp.nseg;
-            }
-            if (!bag && (x.nMax - x.nMin) * N > TrackEnsTable::kMaxTail) // cannot happen for a context's segment (>= 4096) and overlap <= 0.9
-                return fail(DMX_ERR_ARG, "%s: internal error (track %d: %d tail rows x %d shifts)", fn, t, x.nMax - x.nMin, N);
-            if (x.m > INT_MAX / 2)
-                return fail(DMX_ERR_ARG, "%s: track %d: too many segments (%lld)", fn, t, (long long)x.m);
-            x.g0 = M[(size_t)q];
-            M[(size_t)q] += x.m;
-        }
-        nmax = std::max(nmax, j.n);
-    }
-    if (bag)
-    {
-        // every cap of track_ola_bag_kernel (copies per piece, tail entries, LDS), on the tracks' whole tails
-        std::vector<TrackBagModel> whole((size_t)T * Q);
-        for (size_t i = 0; i < whole.size(); ++i)
-            whole[i] = TrackBagModel{0, 0, tm[i].nMin, tm[i].nMax - tm[i].nMin};
-        if (track_ola_bag_tail_entries(whole.data(), T, Q, N, S, bag->w) < 0)
-            return fail(DMX_ERR_ARG,
-                        "%s: the bag does not fit the overlap-add kernel (%d models x %d shifts of at most %d, %d stems of at most %d, or "
-                        "more than %d uneven tail rows x copies of one track and stem)",
-                        fn, Q, N, TrackBagTable::kMaxCopies, S, TrackBagTable::kMaxStems, TrackBagTable::kMaxTail);
-    }
-    std::vector<std::vector<TrackItem>> items((size_t)Q);
-    for (int q = 0; q < Q; ++q)
-    {
-        items[(size_t)q].reserve((size_t)M[(size_t)q]);
-        for (int t = 0; t < T; ++t)
-        {
-            const TrackModel &x = tm[(size_t)t * Q + q];
-            for (int g = 0; g < x.nMax; ++g)
-                for (int k = 0; k < N; ++k)
-                    if (g < copies[(size_t)(x.c0 + k)].nseg)
-                        items[(size_t)q].push_back(TrackItem{t, k, g});
-        }
-        Mtot += M[(size_t)q];
-    }
-    // the batches: each of one model, dealt from the model whose next item is the earliest (track, row)
-    std::vector<TrackBatch> batches;
-    std::vector<i64> cum; // items done after batch k, over all models
-    {
-        std::vector<i64> pos((size_t)Q, 0);
-        i64 all = 0;
-        for (;;)
-        {
-            int pick = -1;
-            for (int q = 0; q < Q; ++q)
-            {
-                if (pos[(size_t)q] >= M[(size_t)q])
-                    continue;
-                if (pick < 0)
-                {
-                    pick = q;
-                    continue;
-                }
-                const TrackItem &a = items[(size_t)q][(size_t)pos[(size_t)q]], &b = items[(size_t)pick][(size_t)pos[(size_t)pick]];
-                if (a.t < b.t || (a.t == b.t && a.g < b.g))
-                    pick = q;
-            }
-            if (pick < 0)
-                break;
-            const i64 g0 = pos[(size_t)pick];
-            const int nb = (int)std::min<i64>(B, M[(size_t)pick] - g0);
-            const int k = (int)batches.size();
-            for (i64 g = g0; g < g0 + nb; ++g)
-            {
-                TrackJob &j = jobs[(size_t)items[(size_t)pick][(size_t)g].t];
-                j.kFirst = std::min(j.kFirst, k), j.kLast = std::max(j.kLast, k);
-            }
-            batches.push_back(TrackBatch{pick, g0, nb});
-            cum.push_back(all += nb);
-            pos[(size_t)pick] += nb;
-        }
-    }
-    const int nBatches = (int)batches.size();
-
-    // plan (host only): the pieces each batch makes final, and the rings they need
-    std::vector<std::vector<TrackPiece>> plan((size_t)nBatches);
-    std::vector<i64> pieceItems;
-    std::vector<i64> reach((size_t)Q, 0);
-    {
-        std::vector<i64> dealt((size_t)Q, 0);
-        int tLo = 0;
-        for (int k = 0; k < nBatches; ++k)
-        {
-            const TrackBatch &bt = batches[(size_t)k];
-            while (jobs[(size_t)tLo].kLast < k)
-                ++tLo;
-            for (i64 g = bt.g0; g < bt.g0 + bt.nb; ++g)
-            {
-                const TrackItem &it = items[(size_t)bt.q][(size_t)g];
-                ++copies[(size_t)(tm[(size_t)it.t * Q + bt.q].c0 + it.k)].segDone;
-            }
-            dealt[(size_t)bt.q] = bt.g0 + bt.nb;
-            for (int t = tLo; t < T && jobs[(size_t)t].kFirst <= k; ++t)
-            {
-                TrackJob &j = jobs[(size_t)t];
-                const TrackCopy *all = &copies[(size_t)t * Q * N];
-                // shifted-track positions below (segments done)*stride are covered only by segments done
-                i64 fin = j.n;
-                for (int x = 0; x < Q * N; ++x)
-                    if (all[x].segDone < all[x].nseg)
-                        fin = std::min<i64>(fin, (i64)all[x].segDone * stride - (DMX_MAX_SHIFT - all[x].shift));
-                fin = std::max<i64>(j.done, fin);
-                TrackPiece pc{t, j.done, fin, pieceItems.size()};
-                pieceItems.resize(pieceItems.size() + (size_t)Q, 0);
-                for (int q = 0; q < Q && fin > j.done; ++q)
-                {
-                    const TrackModel &x = tm[(size_t)t * Q + q];
-                    const TrackCopy *cp = &copies[(size_t)x.c0];
-                    i64 itemLo = INT64_MAX, itemHi = -1;
-                    for (int r = 0; r < N; ++r)
-                    {
-                        const i64 j0 = j.done + DMX_MAX_SHIFT - cp[r].shift; // first shifted position of the piece: its first segment
-                        const i64 gLo = j0 - seg + 1 <= 0 ? 0 : (j0 - seg + stride) / stride;
-                        const i64 gHi = std::min<i64>(cp[r].nseg - 1, (fin - 1 + DMX_MAX_SHIFT - cp[r].shift) / stride); // its last
-                        itemLo = std::min(itemLo, track_item(cp, N, x.nMin, gLo, r));
-                        itemHi = std::max(itemHi, track_item(cp, N, x.nMin, gHi, r));
-                    }
-                    if (itemLo < 0 || itemHi >= dealt[(size_t)q] - x.g0) // every segment the piece reads must be done
-                        return fail(DMX_ERR_ARG, "%s: internal error (track %d reads item %lld of model %d after batch %d)", fn, t,
-                                    (long long)itemHi, q, k);
-                    pieceItems[pc.item0 + (size_t)q] = itemLo;
-                    reach[(size_t)q] = std::max(reach[(size_t)q], dealt[(size_t)q] - (x.g0 + itemLo));
-                }
-                plan[(size_t)k].push_back(pc);
-                j.done = fin;
-            }
-        }
-    }
-    std::vector<i64> R((size_t)Q), ringOff((size_t)Q);
-    i64 ringBlocks = 0;
-    for (int q = 0; q < Q; ++q)
-    {
-        R[(size_t)q] = std::min<i64>(M[(size_t)q], std::max<i64>(2 * (i64)B, (reach[(size_t)q] + B - 1) / B * B));
-        ringOff[(size_t)q] = ringBlocks;
-        ringBlocks += R[(size_t)q];
-    }
-    // slots: track t is held during batches [kFirst, kLast + 1]
-    int nSlots = 0;
-    {
-        std::vector<int> diff((size_t)nBatches + 2, 0);
-        for (const TrackJob &j : jobs)
-            ++diff[(size_t)j.kFirst], --diff[(size_t)j.kLast + 2];
-        int live = 0;
-        for (int k = 0; k <= nBatches; ++k)
-            nSlots = std::max(nSlots, live += diff[(size_t)k]);
-    }
-    DMXCHK(dmx_ensure_buf(c->bMix, 2 * seg * B));
-    DMXCHK(dmx_ensure_buf(c->bSegOut, ringBlocks * blk));
-    if ((int)c->slots.size() < nSlots)
-        c->slots.resize((size_t)nSlots);
-    for (int i = 0; i < nSlots; ++i)
+    dmx_ctx *c = r.c;
+    const TracksPlan &p = r.plan;
+    const PcmOut *pcm = r.pcm;
+    const i64 nmax = p.nmax;
+    DMXCHK(dmx_ensure_buf(c->bMix, 2 * p.seg * p.B));
+    DMXCHK(dmx_ensure_buf(c->bSegOut, p.ringBlocks * r.blk));
+    if ((int)c->slots.size() < p.nSlots)
+        c->slots.resize((size_t)p.nSlots);
+    for (int i = 0; i < p.nSlots; ++i)
     {
         dmx_ctx::TrackSlot &sl = c->slots[(size_t)i];
         DMXCHK(dmx_ensure_buf(sl.audio, 2 * nmax));
-        if (layout == DMX_LAYOUT_PLANAR)
+        if (r.layout == DMX_LAYOUT_PLANAR)
             DMXCHK(dmx_ensure_buf(sl.tmp, 2 * nmax));
-        DMXCHK(dmx_ensure_buf(sl.out, (i64)S * 2 * nmax));
+        DMXCHK(dmx_ensure_buf(sl.out, (i64)r.S * 2 * nmax));
         DMXCHK(dmx_ensure_buf(sl.stats, 4));
         if (pcm)
         {
@@ -1631,305 +1417,331 @@ static int tracks_run_impl(dmx_ctx *c, const char *fn, int T, const float *const
         }
         if (!sl.copied)
             HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-        sl.holder = -1;
     }
     if (!c->uploadStream)
         HIPCHK(hipStreamCreateWithFlags(&c->uploadStream, hipStreamNonBlocking));
     if (!c->evUpload)
         HIPCHK(hipEventCreateWithFlags(&c->evUpload, hipEventDisableTiming));
-    float *dMix = c->bMix.p;
-    std::vector<const float *> rings((size_t)Q);
-    for (int q = 0; q < Q; ++q)
-        rings[(size_t)q] = c->bSegOut.p + ringOff[(size_t)q] * blk;
-    const int eigen = layout == DMX_LAYOUT_EIGEN ? 1 : 0;
-    const int olaEigen = pcm ? 0 : eigen; // the PCM stage reads planes
-    const bool wholeTrack = pcm && pcm->spec.clip == DMX_CLIP_RESCALE; // encode when the track's peak is complete
-    std::vector<std::vector<PcmRange>> pcmPlan(pcm ? (size_t)nBatches : 0);
-    std::vector<i64> pcmDone(pcm ? (size_t)T : 0, 0);
-    std::vector<PcmPiece> pcmPieces, pcmWhole;
-    std::vector<RemixPiece> remixPieces, remixWhole; // instead of those under a remix spec: the mixture is the slot's upload
-
-    if (progress)
-        progress(0.0f, "1., apply model w/ shift", user);
-    // plan[k]: the output samples [lo, hi) of the tracks of batch k that are final once batch k is done. Their copy is
-    // issued AFTER batch k+1 has been enqueued: a device-to-host copy into pageable memory blocks the calling thread until
-    // the data has left the GPU, and the GPU must have its next batch queued by then.
-    auto copy_piece = [&](int k) -> int {
-        HIPCHK(hipStreamWaitEvent(c->copyStream, c->batchEvents[(size_t)k], 0));
-        if (pcm)
-            for (const PcmRange &r : pcmPlan[(size_t)k])
-            {
-                const TrackJob &j = jobs[(size_t)r.t];
-                const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-                const bool last = r.hi == j.n;
-                const i64 lo = wholeTrack ? 0 : r.lo, fb = pcm->frameBytes;
-                const i64 outBytes = j.n * fb, devStride = DMX_OUTPUT_STRIDE(outBytes);
-                if (pcm->flacBits)
-                {
-                    if (!last)
-                        continue;
-                    // the files' byte counts first (the batch that made them is done once its event is; the next batch is
-                    // already enqueued), then one copy per output of exactly its length
-                    int64_t *sz = pcm->sizes + (size_t)r.t * pcm->nOut;
-                    HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
-                    HIPCHK(hipMemcpyAsync(sz, sl.flacSizes.p, sizeof(int64_t) * (size_t)pcm->nOut, hipMemcpyDeviceToHost, c->copyStream));
-                    HIPCHK(hipStreamSynchronize(c->copyStream));
-                    const i64 bound = flac_bound(pcm->flacBits, j.n);
-                    for (int o = 0; o < pcm->nOut; ++o)
-                    {
-                        if (sz[o] < 42 || sz[o] > bound)
-                            return fail(DMX_ERR_HIP, "%s: internal error (track %d, output %d: %lld encoded bytes, bound %lld)", fn, r.t, o,
-                                        (long long)sz[o], (long long)bound);
-                        HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[r.t] + (size_t)(o * bound),
-                                              (const unsigned char *)sl.flac.p + (size_t)(o * bound), (size_t)sz[o], hipMemcpyDeviceToHost,
-                                              c->copyStream));
-                    }
-                }
-                else if (!wholeTrack || last)
-                    for (int o = 0; o < pcm->nOut; ++o)
-                        HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[r.t] + (size_t)(o * outBytes + lo * fb),
-                                              (const unsigned char *)sl.pcm.p + (size_t)(o * devStride + lo * fb), (size_t)((r.hi - lo) * fb),
-                                              hipMemcpyDeviceToHost, c->copyStream));
-                if (last && pcm->peaks)
-                    HIPCHK(hipMemcpyAsync(pcm->peaks + (size_t)r.t * pcm->nOut, sl.peaks.p, sizeof(float) * (size_t)pcm->nOut,
-                                          hipMemcpyDeviceToHost, c->copyStream));
-            }
-        for (const TrackPiece &pc : plan[(size_t)k])
-        {
-            const TrackJob &j = jobs[(size_t)pc.t];
-            const float *dOut = c->slots[(size_t)j.slot].out.p;
-            const i64 i0 = pc.lo, i1 = pc.hi;
-            if (i1 > i0 && !pcm)
-            {
-                if (eigen)
-                    HIPCHK(hipMemcpyAsync(j.out + (size_t)i0 * 2 * S, dOut + (size_t)i0 * 2 * S, sizeof(float) * (size_t)(i1 - i0) * 2 * S,
-                                          hipMemcpyDeviceToHost, c->copyStream));
-                else
-                    for (int pl = 0; pl < 2 * S; ++pl)
-                        HIPCHK(hipMemcpyAsync(j.out + (size_t)pl * j.n + i0, dOut + (size_t)pl * j.n + i0, sizeof(float) * (size_t)(i1 - i0),
-                                              hipMemcpyDeviceToHost, c->copyStream));
-            }
-            if (j.kLast == k)
-                HIPCHK(hipEventRecord(c->slots[(size_t)j.slot].copied, c->copyStream));
-        }
-        if (progress)
-        {
-            const i64 hi = cum[(size_t)k], lo = hi - batches[(size_t)k].nb;
-            HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
-            char msg[128];
-            snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %lld..%lld of %lld", (long long)lo, (long long)(hi - 1),
-                     (long long)Mtot);
-            progress((float)hi / (float)Mtot, msg, user);
-        }
-        return DMX_OK;
-    };
-
-    std::vector<TrackSegItem> batchItems((size_t)B);
-    std::vector<TrackOlaEntry> ola;
-    std::vector<TrackEnsPiece> ens;
-    std::vector<TrackEnsCopy> ensCopies;
-    std::vector<TrackBagPiece> bagPieces;
-    std::vector<TrackBagModel> bagModels;
-    int tLo = 0; // first track of the current batch
-    for (int k = 0; k < nBatches; ++k)
-    {
-        const TrackBatch &bt = batches[(size_t)k];
-        const std::vector<TrackItem> &its = items[(size_t)bt.q];
-        const i64 g0 = bt.g0, nb = bt.nb, Rq = R[(size_t)bt.q];
-        if (bag)
-            DMXCHK(dmx_ctx_set_model(c, bag->models[bt.q]));
-        while (jobs[(size_t)tLo].kLast < k)
-            ++tLo;
-        int tHi = tLo; // one past the last track of the batch
-        while (tHi < T && jobs[(size_t)tHi].kFirst <= k)
-            ++tHi;
-        // upload the tracks that start in this batch
-        TrackStatsTable st{};
-        int nSt = 0;
-        for (int t = tLo; t < tHi; ++t)
-        {
-            TrackJob &j = jobs[(size_t)t];
-            if (j.kFirst != k || j.slot >= 0)
-                continue;
-            // a free slot, else the one whose track finished first (in batch k-2 or earlier: its copy-out has been issued)
-            int pick = -1;
-            for (int i = 0; i < nSlots; ++i)
-            {
-                const int h = c->slots[(size_t)i].holder;
-                if (h < 0)
-                {
-                    pick = i;
-                    break;
-                }
-                if (jobs[(size_t)h].kLast <= k - 2 && (pick < 0 || jobs[(size_t)h].kLast < jobs[(size_t)c->slots[(size_t)pick].holder].kLast))
-                    pick = i;
-            }
-            if (pick < 0)
-                return fail(DMX_ERR_ARG, "%s: internal error (no free track slot in batch %d)", fn, k);
-            dmx_ctx::TrackSlot &sl = c->slots[(size_t)pick];
-            if (sl.holder >= 0) // the previous holder's copy-out (and every kernel that read the slot) is done
-                HIPCHK(hipEventSynchronize(sl.copied));
-            sl.holder = t, j.slot = pick;
-            if (pcm)
-                HIPCHK(hipMemsetAsync(sl.peaks.p, 0, sizeof(float) * (size_t)pcm->nOut, c->stream));
-            if (eigen)
-                HIPCHK(hipMemcpyAsync(sl.audio.p, j.audio, sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
-            else
-            {
-                HIPCHK(hipMemcpyAsync(sl.tmp.p, j.audio, sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
-                launch_planar_to_interleaved(sl.tmp.p, sl.audio.p, j.n, c->uploadStream);
-            }
-            st.audio[nSt] = sl.audio.p, st.n[nSt] = j.n, st.stats[nSt] = sl.stats.p;
-            if (++nSt == TrackStatsTable::kMax || t == tHi - 1)
-            {
-                HIPCHK(hipEventRecord(c->evUpload, c->uploadStream));
-                HIPCHK(hipStreamWaitEvent(c->stream, c->evUpload, 0));
-                launch_track_stats(st, nSt, c->dPartials, dmx_ctx::kStatBlocks, c->stream);
-                launch_track_stats_final(st, nSt, c->dPartials, dmx_ctx::kStatBlocks, c->stream);
-                nSt = 0;
-            }
-        }
-        // gather the batch: the model's items [g0, g0 + nb)
-        for (i64 g = g0; g < g0 + nb; ++g)
-        {
-            const TrackItem &it = its[(size_t)g];
-            const TrackJob &j = jobs[(size_t)it.t];
-            const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-            batchItems[(size_t)(g - g0)] =
-                TrackSegItem{sl.audio.p, sl.stats.p, j.n, copies[(size_t)(tm[(size_t)it.t * Q + bt.q].c0 + it.k)].shift, it.g};
-        }
-        launch_track_gather(batchItems.data(), (int)nb, seg, stride, dMix, c->stream);
-        HIPCHK(hipGetLastError());
-        DMXCHK(dmx_segment_infer_device(c, dMix, const_cast<float *>(rings[(size_t)bt.q]) + (g0 % Rq) * blk, (int)nb));
-        // finish what this batch makes final
-        ola.clear(), ens.clear(), ensCopies.clear(), bagPieces.clear(), bagModels.clear();
-        for (const TrackPiece &pc : plan[(size_t)k])
-        {
-            if (pc.hi <= pc.lo)
-                continue;
-            const TrackJob &j = jobs[(size_t)pc.t];
-            const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-            if (bag)
-            {
-                bagPieces.push_back(TrackBagPiece{sl.stats.p, sl.out.p, j.n, pc.lo, pc.hi});
-                for (int q = 0; q < Q; ++q)
-                {
-                    const TrackModel &x = tm[(size_t)pc.t * Q + q];
-                    const i64 itemLo = pieceItems[pc.item0 + (size_t)q];
-                    bagModels.push_back(TrackBagModel{(int)itemLo, (int)((x.g0 + itemLo) % R[(size_t)q]), x.nMin, x.nMax - x.nMin});
-                    for (int r = 0; r < N; ++r)
-                        ensCopies.push_back(TrackEnsCopy{copies[(size_t)(x.c0 + r)].shift, copies[(size_t)(x.c0 + r)].nseg});
-                }
-                continue;
-            }
-            const TrackModel &x = tm[(size_t)pc.t];
-            const i64 itemLo = pieceItems[pc.item0], slotLo = (x.g0 + itemLo) % Rq;
-            if (N == 1)
-            {
-                const TrackCopy &cp = copies[(size_t)x.c0];
-                ola.push_back(TrackOlaEntry{rings[0], sl.stats.p, sl.out.p, j.n, cp.len, pc.lo, pc.hi, itemLo, slotLo, cp.nseg, cp.shift});
-            }
-            else
-            {
-                ens.push_back(TrackEnsPiece{sl.stats.p, sl.out.p, j.n, pc.lo, pc.hi, itemLo, slotLo, x.nMin, x.nMax - x.nMin});
-                for (int r = 0; r < N; ++r)
-                    ensCopies.push_back(TrackEnsCopy{copies[(size_t)(x.c0 + r)].shift, copies[(size_t)(x.c0 + r)].nseg});
-            }
-        }
-        if (bag)
-        {
-            if (!launch_track_ola_bag(bagPieces.data(), bagModels.data(), ensCopies.data(), (int)bagPieces.size(), Q, N, bag->w, rings.data(),
-                                      R.data(), S, seg, stride, olaEigen, 0, 2 * S, c->stream))
-                return fail(DMX_ERR_ARG, "%s: internal error (the bag's overlap-add was refused in batch %d)", fn, k);
-        }
-        else if (N == 1)
-            launch_track_ola(ola.data(), (int)ola.size(), S, seg, stride, Rq, olaEigen, 0, 2 * S, c->stream);
-        else
-            launch_track_ola_ens(ens.data(), ensCopies.data(), (int)ens.size(), N, rings[0], S, seg, stride, Rq, olaEigen, 0, 2 * S, c->stream);
-        HIPCHK(hipGetLastError());
-        if (pcm)
-        {
-            pcmPieces.clear(), pcmWhole.clear(), remixPieces.clear(), remixWhole.clear();
-            for (const TrackPiece &pc : plan[(size_t)k])
-            {
-                const TrackJob &j = jobs[(size_t)pc.t];
-                i64 &done = pcmDone[(size_t)pc.t];
-                const i64 hi = pc.hi == j.n ? j.n : pc.hi & ~(i64)3; // whole groups of 4 frames, except at the end of the track
-                if (hi <= done)
-                    continue;
-                const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-                const PcmPiece pp{sl.out.p, (unsigned char *)sl.pcm.p, (unsigned *)sl.peaks.p, j.n, j.n,
-                                  DMX_OUTPUT_STRIDE(j.n * pcm->frameBytes), done, hi};
-                if (pcm->remix)
-                {
-                    remixPieces.push_back(RemixPiece{pp, sl.audio.p});
-                    if (hi == j.n)
-                    {
-                        remixWhole.push_back(remixPieces.back());
-                        remixWhole.back().i0 = 0;
-                    }
-                }
-                else
-                {
-                    pcmPieces.push_back(pp);
-                    if (hi == j.n)
-                    {
-                        pcmWhole.push_back(pp);
-                        pcmWhole.back().i0 = 0;
-                    }
-                }
-                pcmPlan[(size_t)k].push_back(PcmRange{pc.t, done, hi});
-                done = hi;
-            }
-            if (pcm->remix)
-            {
-                launch_remix_peak(remixPieces.data(), (int)remixPieces.size(), *pcm->remix, c->stream);
-                const std::vector<RemixPiece> &enc = wholeTrack ? remixWhole : remixPieces;
-                launch_remix_encode(enc.data(), (int)enc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, c->stream);
-            }
-            else
-            {
-                launch_pcm_peak(pcmPieces.data(), (int)pcmPieces.size(), S, pcm->spec.stem, c->stream);
-                const std::vector<PcmPiece> &enc = wholeTrack ? pcmWhole : pcmPieces;
-                launch_pcm_encode(enc.data(), (int)enc.size(), S, pcm->spec.stem, pcm->spec.encoding, pcm->spec.clip, c->stream);
-            }
-            if (pcm->flacBits) // a track whose PCM is complete: its files
-                for (const PcmRange &r : pcmPlan[(size_t)k])
-                {
-                    const TrackJob &j = jobs[(size_t)r.t];
-                    if (r.hi != j.n)
-                        continue;
-                    const dmx_ctx::TrackSlot &sl = c->slots[(size_t)j.slot];
-                    launch_flac_encode((const unsigned char *)sl.pcm.p, DMX_OUTPUT_STRIDE(j.n * pcm->frameBytes), pcm->flacBits, j.n,
-                                       pcm->flacRate, pcm->nOut, (unsigned char *)sl.flac.p, flac_bound(pcm->flacBits, j.n),
-                                       (long long *)sl.flacSizes.p, (unsigned char *)sl.flacWork.p, c->stream);
-                }
-            HIPCHK(hipGetLastError());
-        }
-        hipEvent_t ev = dmx_batch_event(c, (size_t)k);
-        if (!ev)
-            return fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
-        HIPCHK(hipEventRecord(ev, c->stream));
-        if (k > 0)
-            DMXCHK(copy_piece(k - 1));
-    }
-    DMXCHK(copy_piece(nBatches - 1));
-    const int rcSync = dmx_ctx_sync_checked(c);
-    HIPCHK(hipStreamSynchronize(c->copyStream));
-    for (int i = 0; i < nSlots; ++i)
-        c->slots[(size_t)i].holder = -1;
-    if (rcSync != DMX_OK)
-        return rcSync;
+    r.rings.resize((size_t)p.Q);
+    for (int q = 0; q < p.Q; ++q)
+        r.rings[(size_t)q] = c->bSegOut.p + p.ringOff[(size_t)q] * r.blk;
+    r.batchItems.resize((size_t)p.B);
     return DMX_OK;
 }
 
-// a bag leaves the context bound to the model it entered with, on success and on error
-static int tracks_run(dmx_ctx *c, const char *fn, int T, const float *const *audio, const int64_t *n, int N, i64 stride,
-                      const int *shifts, float *const *out, int layout, dmx_progress_fn progress, void *user,
-                      const PcmOut *pcm = nullptr, const BagRun *bag = nullptr)
+// upload the tracks [tLo, tHi) that start in batch k into their slots, and their statistics
+static int tracks_upload(TracksRun &r, int k, int tLo, int tHi)
 {
+    dmx_ctx *c = r.c;
+    TrackStatsTable st{};
+    int nSt = 0;
+    for (int t = tLo; t < tHi; ++t)
+    {
+        const TrackJob &j = r.plan.jobs[(size_t)t];
+        if (j.kFirst != k)
+            continue;
+        const dmx_ctx::TrackSlot &sl = r.slot(t);
+        if (j.takeover) // the previous holder's copy-out (and every kernel that read the slot) is done
+            HIPCHK(hipEventSynchronize(sl.copied));
+        if (r.pcm)
+            HIPCHK(hipMemsetAsync(sl.peaks.p, 0, sizeof(float) * (size_t)r.pcm->nOut, c->stream));
+        if (r.eigen)
+            HIPCHK(hipMemcpyAsync(sl.audio.p, r.audio[t], sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
+        else
+        {
+            HIPCHK(hipMemcpyAsync(sl.tmp.p, r.audio[t], sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
+            launch_planar_to_interleaved(sl.tmp.p, sl.audio.p, j.n, c->uploadStream);
+        }
+        st.audio[nSt] = sl.audio.p, st.n[nSt] = j.n, st.stats[nSt] = sl.stats.p;
+        if (++nSt == TrackStatsTable::kMax || t == tHi - 1)
+        {
+            HIPCHK(hipEventRecord(c->evUpload, c->uploadStream));
+            HIPCHK(hipStreamWaitEvent(c->stream, c->evUpload, 0));
+            launch_track_stats(st, nSt, c->dPartials, dmx_ctx::kStatBlocks, c->stream);
+            launch_track_stats_final(st, nSt, c->dPartials, dmx_ctx::kStatBlocks, c->stream);
+            nSt = 0;
+        }
+    }
+    return DMX_OK;
+}
+
+// gather batch k (its model's items [g0, g0 + nb)) and run the model on it, into the model's ring
+static int tracks_infer(TracksRun &r, int k)
+{
+    dmx_ctx *c = r.c;
+    const TracksPlan &p = r.plan;
+    const TrackBatch &bt = p.batches[(size_t)k];
+    for (i64 g = bt.g0; g < bt.g0 + bt.nb; ++g)
+    {
+        const TrackItem &it = p.items[(size_t)bt.q][(size_t)g];
+        const dmx_ctx::TrackSlot &sl = r.slot(it.t);
+        r.batchItems[(size_t)(g - bt.g0)] = TrackSegItem{sl.audio.p, sl.stats.p, p.jobs[(size_t)it.t].n, p.copy(it.t, bt.q, it.k).shift, it.g};
+    }
+    launch_track_gather(r.batchItems.data(), bt.nb, p.seg, p.stride, c->bMix.p, c->stream);
+    HIPCHK(hipGetLastError());
+    return dmx_segment_infer_device(c, c->bMix.p, const_cast<float *>(r.rings[(size_t)bt.q]) + (bt.g0 % p.R[(size_t)bt.q]) * r.blk, bt.nb);
+}
+
+// the overlap-add of what batch k makes final: one of three kernels (N == 1, the shifts ensemble, a bag)
+static int tracks_ola(TracksRun &r, int k)
+{
+    const TracksPlan &p = r.plan;
+    const int Q = p.Q, N = p.N, S = r.S;
+    const i64 Rq = p.R[(size_t)p.batches[(size_t)k].q];
+    hipStream_t s = r.c->stream;
+    r.ola.clear(), r.ens.clear(), r.ensCopies.clear(), r.bagPieces.clear(), r.bagModels.clear();
+    for (const TrackPiece &pc : p.pieces[(size_t)k])
+    {
+        if (pc.hi <= pc.lo)
+            continue;
+        const i64 n = p.jobs[(size_t)pc.t].n;
+        const dmx_ctx::TrackSlot &sl = r.slot(pc.t);
+        if (r.bag)
+        {
+            r.bagPieces.push_back(TrackBagPiece{sl.stats.p, sl.out.p, n, pc.lo, pc.hi});
+            for (int q = 0; q < Q; ++q)
+            {
+                const TrackModel &x = p.tm[(size_t)pc.t * Q + q];
+                const i64 itemLo = p.pieceItems[pc.item0 + (size_t)q];
+                r.bagModels.push_back(TrackBagModel{(int)itemLo, (int)((x.g0 + itemLo) % p.R[(size_t)q]), x.nMin, x.nMax - x.nMin});
+                for (int k2 = 0; k2 < N; ++k2)
+                    r.ensCopies.push_back(TrackEnsCopy{p.copy(pc.t, q, k2).shift, p.copy(pc.t, q, k2).nseg});
+            }
+            continue;
+        }
+        const TrackModel &x = p.tm[(size_t)pc.t];
+        const i64 itemLo = p.pieceItems[pc.item0], slotLo = (x.g0 + itemLo) % Rq;
+        if (N == 1)
+        {
+            const TrackCopy &cp = p.copy(pc.t, 0, 0);
+            r.ola.push_back(TrackOlaEntry{r.rings[0], sl.stats.p, sl.out.p, n, cp.len, pc.lo, pc.hi, itemLo, slotLo, cp.nseg, cp.shift});
+        }
+        else
+        {
+            r.ens.push_back(TrackEnsPiece{sl.stats.p, sl.out.p, n, pc.lo, pc.hi, itemLo, slotLo, x.nMin, x.nMax - x.nMin});
+            for (int k2 = 0; k2 < N; ++k2)
+                r.ensCopies.push_back(TrackEnsCopy{p.copy(pc.t, 0, k2).shift, p.copy(pc.t, 0, k2).nseg});
+        }
+    }
+    if (r.bag)
+    {
+        if (!launch_track_ola_bag(r.bagPieces.data(), r.bagModels.data(), r.ensCopies.data(), (int)r.bagPieces.size(), Q, N, r.bag->w,
+                                  r.rings.data(), p.R.data(), S, p.seg, p.stride, r.olaEigen, 0, 2 * S, s))
+            return fail(DMX_ERR_ARG, "%s: internal error (the bag's overlap-add was refused in batch %d)", r.fn, k);
+    }
+    else if (N == 1)
+        launch_track_ola(r.ola.data(), (int)r.ola.size(), S, p.seg, p.stride, Rq, r.olaEigen, 0, 2 * S, s);
+    else
+        launch_track_ola_ens(r.ens.data(), r.ensCopies.data(), (int)r.ens.size(), N, r.rings[0], S, p.seg, p.stride, Rq, r.olaEigen, 0,
+                             2 * S, s);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+// the PCM stage behind batch k's overlap-add: the peaks of its ranges, their encoding (the whole track behind its last
+// range when the clip mode needs the peak), and the files of a track whose PCM is complete
+static int tracks_output_stage(TracksRun &r, int k)
+{
+    const TracksPlan &p = r.plan;
+    const PcmOut *pcm = r.pcm;
+    hipStream_t s = r.c->stream;
+    r.pieces.clear(), r.whole.clear();
+    for (const PcmRange &g : p.pcm[(size_t)k])
+    {
+        const i64 n = p.jobs[(size_t)g.t].n;
+        const dmx_ctx::TrackSlot &sl = r.slot(g.t);
+        RemixPiece pp{PcmPiece{sl.out.p, (unsigned char *)sl.pcm.p, (unsigned *)sl.peaks.p, n, n, DMX_OUTPUT_STRIDE(n * pcm->frameBytes), g.lo, g.hi},
+                      pcm->remix ? sl.audio.p : nullptr};
+        r.pieces.push_back(pp);
+        if (g.hi == n)
+        {
+            pp.i0 = 0;
+            r.whole.push_back(pp);
+        }
+    }
+    const std::vector<RemixPiece> &enc = r.wholeTrack ? r.whole : r.pieces;
+    if (pcm->remix)
+    {
+        launch_remix_peak(r.pieces.data(), (int)r.pieces.size(), *pcm->remix, s);
+        launch_remix_encode(enc.data(), (int)enc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
+    }
+    else
+    {
+        r.pcmPeak.assign(r.pieces.begin(), r.pieces.end());
+        r.pcmEnc.assign(enc.begin(), enc.end());
+        launch_pcm_peak(r.pcmPeak.data(), (int)r.pcmPeak.size(), r.S, pcm->spec.stem, s);
+        launch_pcm_encode(r.pcmEnc.data(), (int)r.pcmEnc.size(), r.S, pcm->spec.stem, pcm->spec.encoding, pcm->spec.clip, s);
+    }
+    if (pcm->flacBits)
+        for (const PcmRange &g : p.pcm[(size_t)k])
+        {
+            const i64 n = p.jobs[(size_t)g.t].n;
+            if (g.hi != n)
+                continue;
+            const dmx_ctx::TrackSlot &sl = r.slot(g.t);
+            launch_flac_encode((const unsigned char *)sl.pcm.p, DMX_OUTPUT_STRIDE(n * pcm->frameBytes), pcm->flacBits, n, pcm->flacRate,
+                               pcm->nOut, (unsigned char *)sl.flac.p, flac_bound(pcm->flacBits, n), (long long *)sl.flacSizes.p,
+                               (unsigned char *)sl.flacWork.p, s);
+        }
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+// the encoded outputs of range g of batch k leave: PCM per range (the whole track behind its last range with
+// DMX_CLIP_RESCALE), FLAC files and the peaks behind the track's last range
+static int tracks_copy_pcm(TracksRun &r, int k, const PcmRange &g)
+{
+    dmx_ctx *c = r.c;
+    const PcmOut *pcm = r.pcm;
+    const i64 n = r.plan.jobs[(size_t)g.t].n;
+    const dmx_ctx::TrackSlot &sl = r.slot(g.t);
+    const bool last = g.hi == n;
+    const i64 lo = r.wholeTrack ? 0 : g.lo, fb = pcm->frameBytes;
+    const i64 outBytes = n * fb, devStride = DMX_OUTPUT_STRIDE(outBytes);
+    if (pcm->flacBits)
+    {
+        if (!last)
+            return DMX_OK;
+        // the files' byte counts first (the batch that made them is done once its event is; the next batch is
+        // already enqueued), then one copy per output of exactly its length
+        int64_t *sz = pcm->sizes + (size_t)g.t * pcm->nOut;
+        HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
+        HIPCHK(hipMemcpyAsync(sz, sl.flacSizes.p, sizeof(int64_t) * (size_t)pcm->nOut, hipMemcpyDeviceToHost, c->copyStream));
+        HIPCHK(hipStreamSynchronize(c->copyStream));
+        const i64 bound = flac_bound(pcm->flacBits, n);
+        for (int o = 0; o < pcm->nOut; ++o)
+        {
+            if (sz[o] < 42 || sz[o] > bound)
+                return fail(DMX_ERR_HIP, "%s: internal error (track %d, output %d: %lld encoded bytes, bound %lld)", r.fn, g.t, o,
+                            (long long)sz[o], (long long)bound);
+            HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[g.t] + (size_t)(o * bound), (const unsigned char *)sl.flac.p + (size_t)(o * bound),
+                                  (size_t)sz[o], hipMemcpyDeviceToHost, c->copyStream));
+        }
+    }
+    else if (!r.wholeTrack || last)
+        for (int o = 0; o < pcm->nOut; ++o)
+            HIPCHK(hipMemcpyAsync((unsigned char *)pcm->out[g.t] + (size_t)(o * outBytes + lo * fb),
+                                  (const unsigned char *)sl.pcm.p + (size_t)(o * devStride + lo * fb), (size_t)((g.hi - lo) * fb),
+                                  hipMemcpyDeviceToHost, c->copyStream));
+    if (last && pcm->peaks)
+        HIPCHK(hipMemcpyAsync(pcm->peaks + (size_t)g.t * pcm->nOut, sl.peaks.p, sizeof(float) * (size_t)pcm->nOut, hipMemcpyDeviceToHost,
+                              c->copyStream));
+    return DMX_OK;
+}
+
+// What batch k made final leaves on the copy stream. It is issued AFTER batch k+1 has been enqueued: a device-to-host copy
+// into pageable memory blocks the calling thread until the data has left the GPU, and the GPU must have its next batch
+// queued by then.
+static int tracks_copy_out(TracksRun &r, int k)
+{
+    dmx_ctx *c = r.c;
+    const TracksPlan &p = r.plan;
+    const int S = r.S;
+    HIPCHK(hipStreamWaitEvent(c->copyStream, c->batchEvents[(size_t)k], 0));
+    if (r.pcm)
+        for (const PcmRange &g : p.pcm[(size_t)k])
+            DMXCHK(tracks_copy_pcm(r, k, g));
+    for (const TrackPiece &pc : p.pieces[(size_t)k])
+    {
+        const TrackJob &j = p.jobs[(size_t)pc.t];
+        const dmx_ctx::TrackSlot &sl = r.slot(pc.t);
+        const float *dOut = sl.out.p;
+        float *out = r.out ? r.out[pc.t] : nullptr;
+        const i64 i0 = pc.lo, i1 = pc.hi;
+        if (i1 > i0 && !r.pcm)
+        {
+            if (r.eigen)
+                HIPCHK(hipMemcpyAsync(out + (size_t)i0 * 2 * S, dOut + (size_t)i0 * 2 * S, sizeof(float) * (size_t)(i1 - i0) * 2 * S,
+                                      hipMemcpyDeviceToHost, c->copyStream));
+            else
+                for (int pl = 0; pl < 2 * S; ++pl)
+                    HIPCHK(hipMemcpyAsync(out + (size_t)pl * j.n + i0, dOut + (size_t)pl * j.n + i0, sizeof(float) * (size_t)(i1 - i0),
+                                          hipMemcpyDeviceToHost, c->copyStream));
+        }
+        if (j.kLast == k)
+            HIPCHK(hipEventRecord(sl.copied, c->copyStream));
+    }
+    if (r.progress)
+    {
+        const i64 hi = p.cum[(size_t)k], lo = hi - p.batches[(size_t)k].nb;
+        HIPCHK(hipEventSynchronize(c->batchEvents[(size_t)k]));
+        char msg[128];
+        snprintf(msg, sizeof(msg), "2., apply model w/ split, segments %lld..%lld of %lld", (long long)lo, (long long)(hi - 1),
+                 (long long)p.Mtot);
+        r.progress((float)hi / (float)p.Mtot, msg, r.user);
+    }
+    return DMX_OK;
+}
+
+// every cap of track_ola_bag_kernel (copies per piece, tail entries, LDS), on the tracks' whole tails
+static int tracks_check_bag_caps(const TracksRun &r)
+{
+    const TracksPlan &p = r.plan;
+    std::vector<TrackBagModel> whole(p.tm.size());
+    for (size_t i = 0; i < whole.size(); ++i)
+        whole[i] = TrackBagModel{0, 0, p.tm[i].nMin, p.tm[i].nMax - p.tm[i].nMin};
+    if (track_ola_bag_tail_entries(whole.data(), p.T, p.Q, p.N, r.S, r.bag->w) < 0)
+        return fail(DMX_ERR_ARG,
+                    "%s: the bag does not fit the overlap-add kernel (%d models x %d shifts of at most %d, %d stems of at most %d, or "
+                    "more than %d uneven tail rows x copies of one track and stem)",
+                    r.fn, p.Q, p.N, TrackBagTable::kMaxCopies, r.S, TrackBagTable::kMaxStems, TrackBagTable::kMaxTail);
+    return DMX_OK;
+}
+
+static int tracks_run_impl(TracksRun &r)
+{
+    dmx_ctx *c = r.c;
+    HIPCHK(hipSetDevice(c->m->device));
+    r.S = c->m->pm.n_sources;
+    r.blk = (i64)r.S * 2 * c->seg;
+    r.eigen = r.layout == DMX_LAYOUT_EIGEN ? 1 : 0;
+    r.olaEigen = r.pcm ? 0 : r.eigen; // the PCM stage reads planes
+    r.wholeTrack = r.pcm && r.pcm->spec.clip == DMX_CLIP_RESCALE;
+    std::string why;
+    const int rcPlan = tracks_plan_build(r.plan, r.T, r.n, r.bag ? r.bag->Q : 1, r.N, r.shifts, c->seg, r.stride, c->maxBatch, r.pcm != nullptr,
+                                         r.bag ? -1 : TrackEnsTable::kMaxTail, why);
+    if (rcPlan != DMX_OK)
+        return fail(rcPlan, "%s: %s", r.fn, why.c_str());
+    if (r.bag)
+        DMXCHK(tracks_check_bag_caps(r));
+    DMXCHK(tracks_prepare(r));
+    const TracksPlan &p = r.plan;
+    if (r.progress)
+        r.progress(0.0f, "1., apply model w/ shift", r.user);
+    int tLo = 0; // first track of the current batch
+    for (int k = 0; k < p.nBatches(); ++k)
+    {
+        if (r.bag)
+            DMXCHK(dmx_ctx_set_model(c, r.bag->models[p.batches[(size_t)k].q]));
+        while (p.jobs[(size_t)tLo].kLast < k)
+            ++tLo;
+        int tHi = tLo; // one past the last track of the batch
+        while (tHi < p.T && p.jobs[(size_t)tHi].kFirst <= k)
+            ++tHi;
+        DMXCHK(tracks_upload(r, k, tLo, tHi));
+        DMXCHK(tracks_infer(r, k));
+        DMXCHK(tracks_ola(r, k));
+        if (r.pcm)
+            DMXCHK(tracks_output_stage(r, k));
+        hipEvent_t ev = dmx_batch_event(c, (size_t)k);
+        if (!ev)
+            return fail(DMX_ERR_HIP, "%s: hipEventCreate failed", r.fn);
+        HIPCHK(hipEventRecord(ev, c->stream));
+        if (k > 0)
+            DMXCHK(tracks_copy_out(r, k - 1));
+    }
+    DMXCHK(tracks_copy_out(r, p.nBatches() - 1));
+    const int rcSync = dmx_ctx_sync_checked(c);
+    HIPCHK(hipStreamSynchronize(c->copyStream));
+    return rcSync;
+}
+
+// a bag leaves the context bound to the model it entered with, on success and on error
+static int tracks_run(TracksRun &r)
+{
+    dmx_ctx *c = r.c;
     const dmx_model *entry = c->m;
-    const int rc = tracks_run_impl(c, fn, T, audio, n, N, stride, shifts, out, layout, progress, user, pcm, bag);
+    const int rc = tracks_run_impl(r);
     if (c->m == entry)
         return rc;
     const std::string err = rc != DMX_OK ? dmx_err_string() : std::string();
@@ -1950,8 +1762,10 @@ extern "C" int dmx_track_infer(dmx_ctx *c, const float *audio, int64_t n, int sh
         shift_offset = rand() % DMX_MAX_SHIFT; // model_apply.cpp:114
     if (shift_offset >= DMX_MAX_SHIFT)
         return fail(DMX_ERR_ARG, "dmx_track_infer: shift_offset must be < %d", DMX_MAX_SHIFT);
-    return tracks_run(c, "dmx_track_infer", 1, &audio, &n, 1, overlap_stride(c->seg, 0.25f), &shift_offset, &out, layout, progress,
-                      user);
+    TracksRun r;
+    r.c = c, r.fn = "dmx_track_infer", r.T = 1, r.audio = &audio, r.n = &n, r.N = 1, r.stride = overlap_stride(c->seg, 0.25f);
+    r.shifts = &shift_offset, r.out = &out, r.layout = layout, r.progress = progress, r.user = user;
+    return tracks_run(r);
 }
 
 extern "C" int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, const int *shift_offsets,
@@ -1979,8 +1793,10 @@ extern "C" int dmx_tracks_infer(dmx_ctx *c, int n_tracks, const float *const *au
     std::vector<int> shifts((size_t)n_tracks);
     for (int t = 0; t < n_tracks; ++t) // drawn in track order, like successive dmx_track_infer calls (model_apply.cpp:114)
         shifts[(size_t)t] = !shift_offsets || shift_offsets[t] < 0 ? rand() % DMX_MAX_SHIFT : shift_offsets[t];
-    return tracks_run(c, "dmx_tracks_infer", n_tracks, audio, n, 1, overlap_stride(c->seg, 0.25f), shifts.data(), out, layout,
-                      progress, user);
+    TracksRun r;
+    r.c = c, r.fn = "dmx_tracks_infer", r.T = n_tracks, r.audio = audio, r.n = n, r.N = 1, r.stride = overlap_stride(c->seg, 0.25f);
+    r.shifts = shifts.data(), r.out = out, r.layout = layout, r.progress = progress, r.user = user;
+    return tracks_run(r);
 }
 
 extern "C" int dmx_track_geometry_overlap(int64_t segment_samples, int64_t n, int shift_offset, float overlap, int64_t *shifted_len,
@@ -1996,54 +1812,89 @@ extern "C" int dmx_track_geometry_overlap(int64_t segment_samples, int64_t n, in
     const i64 st = overlap_stride(segment_samples, overlap);
     if (st < 1)
         return fail(DMX_ERR_ARG, "dmx_track_geometry_overlap: stride %lld < 1", (long long)st);
-    const i64 len = n + DMX_MAX_SHIFT - shift_offset;
+    const i64 len = track_shifted_len(n, shift_offset);
     if (shifted_len)
         *shifted_len = len;
     if (stride)
         *stride = st;
     if (n_segments)
-        *n_segments = (int)((len + st - 1) / st);
+        *n_segments = track_n_segments(len, st);
     return DMX_OK;
 }
 
-// the argument checks shared by dmx_tracks_infer_opts and dmx_tracks_infer_pcm (before any GPU work); gives the stride
-// n_models: 0 without a bag (shift_offsets: tracks x shifts), else shift_offsets is tracks x models x shifts
-static int check_tracks_opts(const char *fn, dmx_ctx *c, int n_tracks, const float *const *audio, const int64_t *n, int n_shifts,
-                             float overlap, const int *shift_offsets, void *const *out, int layout, i64 &stride, int n_models = 0)
+// One request of dmx_tracks_infer_{opts,pcm,bag,remix,flac}: the entry points fill it, tracks_call checks and runs it
+enum // TracksCall::kind
 {
-    if (!c)
+    TRACKS_OUT_F32,   // fp32 stems into out[t]
+    TRACKS_OUT_PCM,   // an output spec
+    TRACKS_OUT_REMIX, // a remix spec
+    TRACKS_OUT_FLAC   // a remix spec, and the outputs leave as .flac files
+};
+struct TracksCall
+{
+    const char *fn;
+    dmx_ctx *c;
+    int n_tracks;
+    const float *const *audio;
+    const int64_t *n;
+    int n_shifts;
+    float overlap;
+    const int *shift_offsets; // tracks x shifts; with models: tracks x models x shifts
+    bool bag;                 // the call has a model dimension: models, n_models, weights
+    const dmx_model *const *models;
+    int n_models;
+    const float *weights;
+    int kind; // TRACKS_OUT_*: which of spec, remix, flacRate and flacSizes are read
+    const dmx_output_spec *spec;
+    const dmx_remix_spec *remix;
+    int flacRate;
+    int64_t *flacSizes;
+    void *const *out;
+    float *peaks;
+    int layout;
+    dmx_progress_fn progress;
+    void *user;
+};
+static int tracks_call(const TracksCall &a);
+
+// the argument checks every such request shares (before any GPU work); gives the stride
+static int check_tracks_opts(const TracksCall &a, i64 &stride)
+{
+    const char *fn = a.fn;
+    const int n_models = a.bag ? a.n_models : 0, N = a.n_shifts;
+    if (!a.c)
         return fail(DMX_ERR_ARG, "%s: null context", fn);
-    if (n_tracks < 1)
-        return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
-    if (!audio || !n || !out)
-        return fail(DMX_ERR_ARG, "%s: null %s array", fn, !audio ? "audio" : !n ? "n" : "out");
-    if (layout != DMX_LAYOUT_EIGEN && layout != DMX_LAYOUT_PLANAR)
-        return fail(DMX_ERR_ARG, "%s: unknown layout %d", fn, layout);
-    if (n_shifts < 1 || n_shifts > DMX_MAX_SHIFTS)
-        return fail(DMX_ERR_ARG, "%s: n_shifts must be in [1, %d], got %d", fn, DMX_MAX_SHIFTS, n_shifts);
-    if (!(overlap >= 0.0f && overlap <= DMX_MAX_OVERLAP))
-        return fail(DMX_ERR_ARG, "%s: overlap %g not in [0, %g]", fn, (double)overlap, (double)DMX_MAX_OVERLAP);
-    stride = overlap_stride(c->seg, overlap);
+    if (a.n_tracks < 1)
+        return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, a.n_tracks);
+    if (!a.audio || !a.n || !a.out)
+        return fail(DMX_ERR_ARG, "%s: null %s array", fn, !a.audio ? "audio" : !a.n ? "n" : "out");
+    if (a.layout != DMX_LAYOUT_EIGEN && a.layout != DMX_LAYOUT_PLANAR)
+        return fail(DMX_ERR_ARG, "%s: unknown layout %d", fn, a.layout);
+    if (N < 1 || N > DMX_MAX_SHIFTS)
+        return fail(DMX_ERR_ARG, "%s: n_shifts must be in [1, %d], got %d", fn, DMX_MAX_SHIFTS, N);
+    if (!(a.overlap >= 0.0f && a.overlap <= DMX_MAX_OVERLAP))
+        return fail(DMX_ERR_ARG, "%s: overlap %g not in [0, %g]", fn, (double)a.overlap, (double)DMX_MAX_OVERLAP);
+    stride = overlap_stride(a.c->seg, a.overlap);
     if (stride < 1)
-        return fail(DMX_ERR_ARG, "%s: stride %lld < 1 (segment %lld, overlap %g)", fn, (long long)stride, (long long)c->seg, (double)overlap);
-    const int N = n_shifts;
-    for (int t = 0; t < n_tracks; ++t)
+        return fail(DMX_ERR_ARG, "%s: stride %lld < 1 (segment %lld, overlap %g)", fn, (long long)stride, (long long)a.c->seg,
+                    (double)a.overlap);
+    for (int t = 0; t < a.n_tracks; ++t)
     {
-        if (!audio[t])
+        if (!a.audio[t])
             return fail(DMX_ERR_ARG, "%s: track %d: null audio pointer", fn, t);
-        if (!out[t])
+        if (!a.out[t])
             return fail(DMX_ERR_ARG, "%s: track %d: null out pointer", fn, t);
-        if (n[t] < 2)
-            return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be >= 2", fn, t, (long long)n[t]);
-        for (int k = 0; shift_offsets && !n_models && k < N; ++k)
+        if (a.n[t] < 2)
+            return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be >= 2", fn, t, (long long)a.n[t]);
+        for (int k = 0; a.shift_offsets && !n_models && k < N; ++k)
         {
-            const int s = shift_offsets[(size_t)t * N + k];
+            const int s = a.shift_offsets[(size_t)t * N + k];
             if (s < -1 || s >= DMX_MAX_SHIFT)
                 return fail(DMX_ERR_ARG, "%s: track %d, shift %d: shift_offset %d not in [-1, %d)", fn, t, k, s, DMX_MAX_SHIFT);
         }
-        for (int x = 0; shift_offsets && x < n_models * N; ++x)
+        for (int x = 0; a.shift_offsets && x < n_models * N; ++x)
         {
-            const int s = shift_offsets[(size_t)t * n_models * N + x];
+            const int s = a.shift_offsets[(size_t)t * n_models * N + x];
             if (s < -1 || s >= DMX_MAX_SHIFT)
                 return fail(DMX_ERR_ARG, "%s: track %d, model %d, shift %d: shift_offset %d not in [-1, %d)", fn, t, x / N, x % N, s,
                             DMX_MAX_SHIFT);
@@ -2064,11 +1915,11 @@ extern "C" int dmx_tracks_infer_opts(dmx_ctx *c, int n_tracks, const float *cons
                                      float overlap, const int *shift_offsets, float *const *out, int layout, dmx_progress_fn progress,
                                      void *user)
 {
-    const char *fn = "dmx_tracks_infer_opts";
-    i64 stride = 0;
-    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, reinterpret_cast<void *const *>(out), layout, stride));
-    const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
-    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), out, layout, progress, user);
+    TracksCall a{};
+    a.fn = "dmx_tracks_infer_opts", a.c = c, a.n_tracks = n_tracks, a.audio = audio, a.n = n;
+    a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.kind = TRACKS_OUT_F32, a.out = reinterpret_cast<void *const *>(out), a.layout = layout, a.progress = progress, a.user = user;
+    return tracks_call(a);
 }
 
 // --------------------------------------------------------------------------- PCM output (pcm.hip)
@@ -2106,21 +1957,17 @@ extern "C" int dmx_tracks_infer_pcm(dmx_ctx *c, int n_tracks, const float *const
                                     const int *shift_offsets, const dmx_output_spec *spec, void *const *out, float *peaks, int layout,
                                     dmx_progress_fn progress, void *user)
 {
-    const char *fn = "dmx_tracks_infer_pcm";
-    DMXCHK(pcm_check_spec(fn, spec, -1));
-    i64 stride = 0;
-    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride));
-    const int S = c->m->pm.n_sources;
-    DMXCHK(pcm_check_spec(fn, spec, S));
-    const PcmOut pcm{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
-    const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
-    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
+    TracksCall a{};
+    a.fn = "dmx_tracks_infer_pcm", a.c = c, a.n_tracks = n_tracks, a.audio = audio, a.n = n;
+    a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.kind = TRACKS_OUT_PCM, a.spec = spec, a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
+    return tracks_call(a);
 }
 
 // --------------------------------------------------------------------------- remix outputs (pcm.hip)
 // the checks of dmx_remix_check; G (may be NULL): the kernels' table. noModel (S and G unused): the model is not known (no
 // context): the checks that do not need the width of the matrix
-static int remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, PcmGains *G, bool noModel = false)
+static int remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, PcmGains *G, bool noModel)
 {
     if (!noModel && (S < 1 || S > PcmGains::kMaxSrc - 1))
         return fail(DMX_ERR_ARG, "%s: remix spec: n_sources must be in [1, %d], got %d", fn, PcmGains::kMaxSrc - 1, S);
@@ -2171,7 +2018,7 @@ static bool remix_uses_mix(const PcmGains &G)
 
 extern "C" int dmx_remix_check(int n_sources, const dmx_remix_spec *spec)
 {
-    return remix_check_spec("dmx_remix_check", n_sources, spec, nullptr);
+    return remix_check_spec("dmx_remix_check", n_sources, spec, nullptr, false);
 }
 
 extern "C" int dmx_remix_two_stems(int n_sources, int stem, int method, float *gains_out, int *n_out)
@@ -2253,51 +2100,106 @@ extern "C" int dmx_bag_weights(int n_models, int n_sources, const float *weights
     return bag_weights_check("dmx_bag_weights", n_models, n_sources, weights, weights_out, sums_out);
 }
 
-// dmx_tracks_infer_bag, and dmx_tracks_infer_remix with models: spec / remix (at most one) select the output stage
-static int tracks_bag_run(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
-                          const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
-                          const dmx_output_spec *spec, const dmx_remix_spec *remix, void *const *out, float *peaks, int layout,
-                          dmx_progress_fn progress, void *user, int flacRate = 0, int64_t *flacSizes = nullptr)
+// the model dimension of a request: the models against the context's, and the weights -> w (Q x S)
+static int check_tracks_bag(const TracksCall &a, float *w)
 {
-    if (!c)
+    const char *fn = a.fn;
+    if (!a.c)
         return fail(DMX_ERR_ARG, "%s: null context", fn);
-    if (n_models < 1 || n_models > DMX_MAX_BAG)
-        return fail(DMX_ERR_ARG, "%s: n_models must be in [1, %d], got %d", fn, DMX_MAX_BAG, n_models);
-    if (!models)
+    if (a.n_models < 1 || a.n_models > DMX_MAX_BAG)
+        return fail(DMX_ERR_ARG, "%s: n_models must be in [1, %d], got %d", fn, DMX_MAX_BAG, a.n_models);
+    if (!a.models)
         return fail(DMX_ERR_ARG, "%s: null models array", fn);
-    const dmx_model *cm = c->m;
-    for (int q = 0; q < n_models; ++q)
+    const dmx_model *cm = a.c->m;
+    for (int q = 0; q < a.n_models; ++q)
     {
-        const dmx_model *m = models[q];
+        const dmx_model *m = a.models[q];
         if (!m)
             return fail(DMX_ERR_ARG, "%s: model %d: null", fn, q);
         if (m->device != cm->device || m->pm.arch != cm->pm.arch || m->pm.n_sources != cm->pm.n_sources || m->pm.dim != cm->pm.dim ||
             m->blobFloats != cm->blobFloats || m->pm.index != cm->pm.index) // dmx_ctx_set_model's test
             return fail(DMX_ERR_ARG, "%s: model %d: differs in architecture or device from the context's", fn, q);
     }
-    const int S = cm->pm.n_sources;
-    float w[DMX_MAX_BAG * TrackBagTable::kMaxStems];
-    DMXCHK(bag_weights_check(fn, n_models, S, weights, w, nullptr));
-    if (spec)
-        DMXCHK(pcm_check_spec(fn, spec, S));
+    return bag_weights_check(fn, a.n_models, cm->pm.n_sources, a.weights, w, nullptr);
+}
+
+// what dmx_tracks_infer_flac asks of its own arguments
+static int check_tracks_flac(const TracksCall &a)
+{
+    const char *fn = a.fn;
+    DMXCHK(remix_check_spec(fn, 0, a.remix, nullptr, true)); // what of the spec can be checked without a model
+    if (a.remix->encoding == DMX_PCM_F32)
+        return fail(DMX_ERR_ARG, "%s: remix spec: encoding DMX_PCM_F32 has no FLAC form (DMX_PCM_S16 1 or DMX_PCM_S24 2)", fn);
+    if (!a.flacSizes)
+        return fail(DMX_ERR_ARG, "%s: null sizes array", fn);
+    if (a.flacRate < 1 || a.flacRate > 655350)
+        return fail(DMX_ERR_ARG, "%s: sample_rate %d not in [1, 655350]", fn, a.flacRate);
+    for (int t = 0; a.n && t < a.n_tracks; ++t)
+        if (a.n[t] >= (int64_t)1 << 36)
+            return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be < 2^36", fn, t, (long long)a.n[t]);
+    return DMX_OK;
+}
+
+// The checks of a request, in the order that decides which error a doubly-wrong call reports, then the run.
+// With a remix spec the spec comes before the context's other uses; with models, the models, the weights and the output
+// spec come before the arguments every request shares; without models an output spec is checked before them (the stem's
+// upper bound after them, once the model is known).
+static int tracks_call(const TracksCall &a)
+{
+    const char *fn = a.fn;
+    const bool remix = a.kind == TRACKS_OUT_REMIX || a.kind == TRACKS_OUT_FLAC;
+    if (a.kind == TRACKS_OUT_FLAC)
+        DMXCHK(check_tracks_flac(a));
     PcmGains G;
     if (remix)
-        DMXCHK(remix_check_spec(fn, S, remix, &G));
-    if (n_shifts >= 1 && (i64)n_models * n_shifts > TrackBagTable::kMaxCopies)
-        return fail(DMX_ERR_ARG, "%s: n_models * n_shifts must be <= %d, got %d x %d", fn, TrackBagTable::kMaxCopies, n_models, n_shifts);
+    {
+        if (!a.c)
+        {
+            DMXCHK(remix_check_spec(fn, 0, a.remix, nullptr, true)); // what of the spec can be checked without a model
+            return fail(DMX_ERR_ARG, "%s: null context", fn);
+        }
+        DMXCHK(remix_check_spec(fn, a.c->m->pm.n_sources, a.remix, &G, false));
+        if (!a.bag && a.weights)
+            return fail(DMX_ERR_ARG, "%s: weights given without models", fn);
+    }
+    float w[DMX_MAX_BAG * TrackBagTable::kMaxStems];
+    if (a.bag)
+    {
+        DMXCHK(check_tracks_bag(a, w));
+        if (a.kind == TRACKS_OUT_PCM)
+            DMXCHK(pcm_check_spec(fn, a.spec, a.c->m->pm.n_sources));
+        if (a.n_shifts >= 1 && (i64)a.n_models * a.n_shifts > TrackBagTable::kMaxCopies)
+            return fail(DMX_ERR_ARG, "%s: n_models * n_shifts must be <= %d, got %d x %d", fn, TrackBagTable::kMaxCopies, a.n_models,
+                        a.n_shifts);
+    }
+    else if (a.kind == TRACKS_OUT_PCM)
+        DMXCHK(pcm_check_spec(fn, a.spec, -1));
     i64 stride = 0;
-    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride, n_models));
-    const std::vector<int> shifts = draw_shifts(n_tracks * n_models, n_shifts, shift_offsets); // (track, model, copy) order
-    const BagRun bag{models, n_models, w};
-    if (!spec && !remix)
-        return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), reinterpret_cast<float *const *>(out), layout, progress,
-                          user, nullptr, &bag);
-    PcmOut pcm = remix ? PcmOut{dmx_output_spec{remix->encoding, remix->clip, -1}, out, peaks, remix->n_out,
-                                pcm_frame_bytes(remix->encoding), &G}
-                       : PcmOut{*spec, out, peaks, spec->stem < 0 ? S : 2, pcm_frame_bytes(spec->encoding)};
-    if (flacSizes)
-        pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = flacRate, pcm.sizes = flacSizes;
-    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm, &bag);
+    DMXCHK(check_tracks_opts(a, stride));
+    const int S = a.c->m->pm.n_sources;
+    if (!a.bag && a.kind == TRACKS_OUT_PCM)
+        DMXCHK(pcm_check_spec(fn, a.spec, S));
+    const BagRun bag{a.models, a.n_models, w};
+    PcmOut pcm{};
+    if (remix)
+        pcm = PcmOut{dmx_output_spec{a.remix->encoding, a.remix->clip, -1}, a.out, a.peaks, a.remix->n_out, pcm_frame_bytes(a.remix->encoding),
+                     &G, 0, 0, nullptr};
+    else if (a.kind == TRACKS_OUT_PCM)
+        pcm = PcmOut{*a.spec, a.out, a.peaks, a.spec->stem < 0 ? S : 2, pcm_frame_bytes(a.spec->encoding), nullptr, 0, 0, nullptr};
+    if (a.kind == TRACKS_OUT_FLAC)
+        pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = a.flacRate, pcm.sizes = a.flacSizes;
+    // (track, copy) order; with models (track, model, copy) order
+    const std::vector<int> shifts = draw_shifts(a.bag ? a.n_tracks * a.n_models : a.n_tracks, a.n_shifts, a.shift_offsets);
+    TracksRun r;
+    r.c = a.c, r.fn = fn, r.T = a.n_tracks, r.audio = a.audio, r.n = a.n, r.N = a.n_shifts, r.stride = stride, r.shifts = shifts.data();
+    r.layout = a.layout, r.progress = a.progress, r.user = a.user;
+    if (a.kind == TRACKS_OUT_F32)
+        r.out = reinterpret_cast<float *const *>(a.out);
+    else
+        r.pcm = &pcm;
+    if (a.bag)
+        r.bag = &bag;
+    return tracks_run(r);
 }
 
 extern "C" int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
@@ -2305,8 +2207,13 @@ extern "C" int dmx_tracks_infer_bag(dmx_ctx *c, const dmx_model *const *models, 
                                     const dmx_output_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
                                     void *user)
 {
-    return tracks_bag_run("dmx_tracks_infer_bag", c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, spec,
-                          nullptr, out, peaks, layout, progress, user);
+    TracksCall a{};
+    a.fn = "dmx_tracks_infer_bag", a.c = c, a.n_tracks = n_tracks, a.audio = audio, a.n = n;
+    a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.bag = true, a.models = models, a.n_models = n_models, a.weights = weights;
+    a.kind = spec ? TRACKS_OUT_PCM : TRACKS_OUT_F32, a.spec = spec;
+    a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
+    return tracks_call(a);
 }
 
 extern "C" int dmx_pcm_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
@@ -2370,32 +2277,14 @@ extern "C" int dmx_pcm_encode(int device, const float *planes, int n_sources, in
     return rc;
 }
 
-// dmx_tracks_infer_remix, and dmx_tracks_infer_flac (flacSizes given: the outputs leave as .flac files)
-static int tracks_remix_run(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
-                            const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,
-                            const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress, void *user,
-                            int flacRate = 0, int64_t *flacSizes = nullptr)
+// dmx_tracks_infer_remix and dmx_tracks_infer_flac: the request has a model dimension when models are given
+static TracksCall remix_call(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights,
+                             const dmx_remix_spec *spec)
 {
-    if (!c)
-    {
-        DMXCHK(remix_check_spec(fn, 0, spec, nullptr, true)); // what of the spec can be checked without a model
-        return fail(DMX_ERR_ARG, "%s: null context", fn);
-    }
-    const int S = c->m->pm.n_sources;
-    PcmGains G;
-    DMXCHK(remix_check_spec(fn, S, spec, &G));
-    if (models || n_models != 0)
-        return tracks_bag_run(fn, c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, nullptr, spec, out,
-                              peaks, layout, progress, user, flacRate, flacSizes);
-    if (weights)
-        return fail(DMX_ERR_ARG, "%s: weights given without models", fn);
-    i64 stride = 0;
-    DMXCHK(check_tracks_opts(fn, c, n_tracks, audio, n, n_shifts, overlap, shift_offsets, out, layout, stride));
-    PcmOut pcm{dmx_output_spec{spec->encoding, spec->clip, -1}, out, peaks, spec->n_out, pcm_frame_bytes(spec->encoding), &G};
-    if (flacSizes)
-        pcm.flacBits = spec->encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = flacRate, pcm.sizes = flacSizes;
-    const std::vector<int> shifts = draw_shifts(n_tracks, n_shifts, shift_offsets);
-    return tracks_run(c, fn, n_tracks, audio, n, n_shifts, stride, shifts.data(), nullptr, layout, progress, user, &pcm);
+    TracksCall a{};
+    a.fn = fn, a.c = c, a.bag = models || n_models != 0, a.models = models, a.n_models = n_models, a.weights = weights;
+    a.kind = TRACKS_OUT_REMIX, a.remix = spec;
+    return a;
 }
 
 extern "C" int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
@@ -2403,8 +2292,10 @@ extern "C" int dmx_tracks_infer_remix(dmx_ctx *c, const dmx_model *const *models
                                       const dmx_remix_spec *spec, void *const *out, float *peaks, int layout, dmx_progress_fn progress,
                                       void *user)
 {
-    return tracks_remix_run("dmx_tracks_infer_remix", c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, spec,
-                            out, peaks, layout, progress, user);
+    TracksCall a = remix_call("dmx_tracks_infer_remix", c, models, n_models, weights, spec);
+    a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
+    return tracks_call(a);
 }
 
 extern "C" int dmx_remix_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
@@ -2412,7 +2303,7 @@ extern "C" int dmx_remix_encode_device(int device, const float *d_planes, int n_
 {
     const char *fn = "dmx_remix_encode_device";
     PcmGains G;
-    DMXCHK(remix_check_spec(fn, n_sources, spec, &G));
+    DMXCHK(remix_check_spec(fn, n_sources, spec, &G, false));
     if (!d_planes || !d_out || !d_peaks)
         return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_planes ? "d_planes" : !d_out ? "d_out" : "d_peaks");
     if (!d_mix && remix_uses_mix(G))
@@ -2438,7 +2329,7 @@ extern "C" int dmx_remix_encode(int device, const float *planes, int n_sources, 
 {
     const char *fn = "dmx_remix_encode";
     PcmGains G;
-    DMXCHK(remix_check_spec(fn, n_sources, spec, &G));
+    DMXCHK(remix_check_spec(fn, n_sources, spec, &G, false));
     if (!planes || !out || n < 1)
         return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer or n < 1)", fn);
     if (!mix && remix_uses_mix(G))
@@ -2543,19 +2434,11 @@ extern "C" int dmx_tracks_infer_flac(dmx_ctx *c, const dmx_model *const *models,
                                      const dmx_remix_spec *spec, int sample_rate, void *const *out, int64_t *sizes, float *peaks, int layout,
                                      dmx_progress_fn progress, void *user)
 {
-    const char *fn = "dmx_tracks_infer_flac";
-    DMXCHK(remix_check_spec(fn, 0, spec, nullptr, true)); // what of the spec can be checked without a model
-    if (spec->encoding == DMX_PCM_F32)
-        return fail(DMX_ERR_ARG, "%s: remix spec: encoding DMX_PCM_F32 has no FLAC form (DMX_PCM_S16 1 or DMX_PCM_S24 2)", fn);
-    if (!sizes)
-        return fail(DMX_ERR_ARG, "%s: null sizes array", fn);
-    if (sample_rate < 1 || sample_rate > 655350)
-        return fail(DMX_ERR_ARG, "%s: sample_rate %d not in [1, 655350]", fn, sample_rate);
-    for (int t = 0; n && t < n_tracks; ++t)
-        if (n[t] >= (int64_t)1 << 36)
-            return fail(DMX_ERR_ARG, "%s: track %d: n = %lld, must be < 2^36", fn, t, (long long)n[t]);
-    return tracks_remix_run(fn, c, models, n_models, weights, n_tracks, audio, n, n_shifts, overlap, shift_offsets, spec, out, peaks, layout,
-                            progress, user, sample_rate, sizes);
+    TracksCall a = remix_call("dmx_tracks_infer_flac", c, models, n_models, weights, spec);
+    a.kind = TRACKS_OUT_FLAC, a.flacRate = sample_rate, a.flacSizes = sizes;
+    a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
+    return tracks_call(a);
 }
 
 // --------------------------------------------------------------------------- debug
