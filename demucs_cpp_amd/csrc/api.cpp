@@ -164,8 +164,8 @@ extern "C" int dmx_debug_split_activations_fp16(int device, const float *x, int6
     return DMX_OK;
 }
 
-// the geometry of an op as the kernels see it (no pointers): what launch_op passes and what the launchers' own predicates
-// (linear-layer addressing, ...) read when they are asked whether a kernel exists
+// the geometry of an op as the kernels see it (no pointers): launch_op adds the pointers; the launchers' existence queries
+// (validate_plan) read only this
 static void fill_gemm_geometry(GemmArgs &k, const IGemm &g)
 {
     k.xBS = g.xBatchStride;
@@ -177,48 +177,19 @@ static void fill_gemm_geometry(GemmArgs &k, const IGemm &g)
     k.epi = g.epi, k.act = g.act, k.yBS = g.yBatchStride, k.ldy = g.ldy;
     k.NB = g.NB, k.tableScale = g.tableScale;
     k.Lout = g.Lout, k.Cout = g.Cout, k.trS = g.trS, k.trOff = g.trOff;
-    k.kvCol0 = g.kvCol0, k.kvT = g.kvT, k.kvH = g.kvH, k.kvHs = g.kvHs;
+    k.kvPlane = (i64)g.B * g.kvT * g.kvH * g.kvHs, k.kvCol0 = g.kvCol0, k.kvT = g.kvT, k.kvH = g.kvH, k.kvHs = g.kvHs;
     k.M = (i64)g.B * g.P1 * g.P0;
 }
 
-// an op may use the split kernel when a kernel exists for its (tile, prologue, epilogue) and every weight it reads is the
-// exact sum of its two bf16 planes (true for tensors that come straight from the fp16 file; derived ones keep fp32)
-static bool split_ok_model(const dmx_ctx *c, const dmx_model *m, const IGemm &g);
-static bool split_ok(const dmx_ctx *c, const IGemm &g) { return split_ok_model(c, c->m, g); }
-static bool split_ok_model(const dmx_ctx *c, const dmx_model *m, const IGemm &g)
+// what the kernel selection reads of a model (gemm_select.h)
+static GemmModelFacts model_facts(const dmx_model *m)
 {
-    if (c->gemm == DMX_GEMM_F32 || !m->dWb)
-        return false;
-    GemmArgs k{};
-    fill_gemm_geometry(k, g); // (the K / V plane projections are decided from the whole geometry: linear addressing, 32-bit offsets)
-    k.Wb1 = m->dWb + g.w_w, k.Wb2 = m->dWb + m->blobFloats + 512 + g.w_w; // the planes as launch_op passes them
-    if (launch_igemm_split(g.cfg, k, nullptr, true) != 0)
-        return false;
-    // any inexact element inside [w_w, w_w + Np * Kp)? (the list is computed when the weights are uploaded: the same for the
-    // model and every replica of it, so all devices of an engine take the same decision)
-    const i64 lo = g.w_w, hi = g.w_w + (i64)g.Np * g.Kp;
-    auto it = std::lower_bound(m->inexactW.begin(), m->inexactW.end(), lo);
-    return it == m->inexactW.end() || *it >= hi;
+    GemmModelFacts f;
+    f.bf16Planes = m->dWb != nullptr, f.fp16Plane = m->dWh != nullptr;
+    f.planeDelta = (i64)m->blobFloats + 512; // (dmx_model_upload)
+    f.inexactW = &m->inexactW, f.inexactH = &m->inexactH;
+    return f;
 }
-
-// 0: the op keeps its fp32 kernel; 1: bf16 terms (split_ok); 2: fp16 terms - contexts of DMX_GEMM_FP16X3, ops for which the
-// fp16-term kernel exists (the linear-layer kernel, igemm_split.hip) and whose weights are all fp16 numbers
-static int split_kind_model(const dmx_ctx *c, const dmx_model *m, const IGemm &g)
-{
-    if (!split_ok_model(c, m, g))
-        return 0;
-    if (c->gemm != DMX_GEMM_FP16X3 || !m->dWh || !g.hterms)
-        return 1;
-    GemmArgs k{};
-    fill_gemm_geometry(k, g);
-    k.Wb1 = k.Wb2 = m->dWh;
-    if (launch_igemm_split(g.cfg, k, nullptr, true, 1) != 0)
-        return 1;
-    const i64 lo = g.w_w, hi = g.w_w + (i64)g.Np * g.Kp;
-    auto it = std::lower_bound(m->inexactH.begin(), m->inexactH.end(), lo);
-    return (it == m->inexactH.end() || *it >= hi) ? 2 : 1;
-}
-static int split_kind(const dmx_ctx *c, const IGemm &g) { return split_kind_model(c, c->m, g); }
 
 // a failed upload leaves nothing on the device (the caller drops the half-built model without calling dmx_model_free)
 static int upload_failed(dmx_model *m, hipError_t e)
@@ -244,7 +215,7 @@ int dmx_model_upload(dmx_model *m, const float *blob)
     {
         // igemm_split.hip: every blob element as two bf16 terms by round-to-nearest splits, w1 = bf16(w), w2 = bf16(w - w1).
         // Exact for fp16-representable values (11 significand bits <= 8 + 8, fp16 subnormals included: bf16 has the fp32
-        // exponent range); whether an op's weights ARE exact is checked per op when the plan is built (split_ok).
+        // exponent range); whether an op's weights ARE exact is checked per op when the plan is built (gemm_select.h).
         std::vector<unsigned short> planes(2 * m->blobFloats + 1024, 0);
         m->inexactW.clear();
         for (size_t i = 0; i < m->blobFloats; ++i)
@@ -258,7 +229,7 @@ int dmx_model_upload(dmx_model *m, const float *blob)
     }
     // DMX_GEMM_FP16X3 (opt-in): every blob element as ONE fp16 number (round to nearest). Exact for everything that comes
     // straight from the fp16 weight file; the rest is listed here, and an op that touches a listed element keeps bf16 terms
-    // (split_kind). The plane itself is only built when a context of that mode binds the model (dmx_model_fp16_plane).
+    // (gemm_select.h). The plane itself is only built when a context of that mode binds the model (dmx_model_fp16_plane).
     m->inexactH.clear();
     for (size_t i = 0; i < m->blobFloats; ++i)
         if (!((float)(_Float16)blob[i] == blob[i]))
@@ -342,12 +313,20 @@ static bool validate_plan(const Plan &p, std::string &why)
         const bool al = ((i64)g.L0 * g.Cin) % 4 == 0 && (g.stride0 * g.Cin) % 4 == 0 && (g.pad0 * g.Cin) % 4 == 0 &&
                         g.seg0 % 4 == 0 && g.K % 4 == 0 && g.xBatchStride % 4 == 0 && (g.S1 == 1 || g.seg0 % 16 == 0) &&
                         (g.cfg == kDirectCfg || (g.Cin % 4 == 0 && g.seg0 % g.Cin == 0 && g.S1 * (g.seg0 / g.Cin) <= 31)); // one validity bit per tap (igemm.hip)
-        GemmArgs k{};
-        k.pro = g.pro, k.epi = g.epi;
-        k.N = g.N, k.S1 = g.S1, k.seg0 = g.seg0, k.M = (i64)g.B * g.P1 * g.P0, k.L0 = g.L0, k.Cin = g.Cin;
-        if (g.epi == EPI_KPL || g.epi == EPI_VT) // exist on the exact-split kernels only; get_plan has checked split_ok
+        if (g.epi == EPI_KPL || g.epi == EPI_VT) // exist on the exact-split kernels only; build_chosen_plan keeps them only there
+        {
+            if (g.choice.arith == 0)
+            {
+                why = "op " + op.name + ": K / V plane projection without its exact-split kernel";
+                return false;
+            }
             continue;
-        if (!al || (g.cfg == kDirectCfg ? launch_dgemm(k, nullptr, true) : launch_igemm(g.cfg, k, nullptr, true)) != 0)
+        }
+        // the fp32 kernel must exist for split ops too: dmx_ctx_set_model may bind a model whose weights turn them to fp32
+        GemmArgs k{};
+        fill_gemm_geometry(k, g);
+        const bool exists = (g.cfg == kDirectCfg ? launch_dgemm(k, nullptr, true) : launch_igemm(g.cfg, k, nullptr, true)) == 0;
+        if (!al || !exists)
         {
             why = "op " + op.name + (al ? ": no kernel instantiated for its (tile, prologue, epilogue)" : ": staging alignment contract violated");
             return false;
@@ -362,41 +341,20 @@ static Plan *get_plan(dmx_ctx *c, int batch)
     if (it != c->plans.end())
         return it->second.get();
     auto p = std::make_unique<Plan>();
-    PlanOpts opts;
-    opts.gemm = c->gemm;
-    // K / V projections write the attention kernel's bf16 operand planes (plan.cpp plane_linear; DMX_KV_PLANES=0: A/B). All or
-    // nothing: if any such op cannot take its exact-split kernel (weights not two-plane exact, kernels switched off) the
-    // plan is rebuilt in the fp32-K/V form.
+    // K / V projections write the attention kernel's bf16 operand planes (plan.cpp plane_linear; DMX_KV_PLANES=0: A/B) where the
+    // attention kernel that reads them exists and every such op can take its exact-split kernel (build_chosen_plan)
     const bool planesOff = getenv("DMX_KV_PLANES") && atoi(getenv("DMX_KV_PLANES")) == 0; // (read per plan: tests switch it)
-    opts.kvPlanes = c->gemm != DMX_GEMM_F32 && !planesOff && c->m->pm.arch != 3 ? 1 : 0;
-    build_plan(c->m->pm, c->seg, batch, *p, opts);
-    if (opts.kvPlanes)
-    {
-        bool ok = true;
-        AttnArgs t{};
-        t.hs = c->m->pm.dim / 8;
-        ok = launch_attention_split(t, nullptr, true) == 0;
-        for (const Op &op : p->ops)
-            if (op.kind == OP_IGEMM && (op.g.epi == EPI_KPL || op.g.epi == EPI_VT) && !split_ok(c, op.g))
-                ok = false;
-        if (!ok)
-        {
-            opts.kvPlanes = 0;
-            p = std::make_unique<Plan>();
-            build_plan(c->m->pm, c->seg, batch, *p, opts);
-        }
-    }
+    AttnArgs kv{};
+    kv.hs = c->m->pm.dim / 8;
+    const bool kvPlanes = c->gemm != DMX_GEMM_F32 && !planesOff && c->m->pm.arch != 3 && launch_attention_split(kv, nullptr, true) == 0;
+    build_chosen_plan(c->m->pm, c->seg, batch, c->gemm, kvPlanes, model_facts(c->m), split_lin_mode(), *p);
     for (Op &op : p->ops)
-    {
-        if (op.kind == OP_IGEMM)
-            op.g.split = split_kind(c, op.g);
         if (op.kind == OP_ATTENTION)
         {
             AttnArgs t{};
             t.hs = op.at.hs;
             op.at.split = c->gemm != DMX_GEMM_F32 && launch_attention_split(t, nullptr, true) == 0 ? 1 : 0;
         }
-    }
     Plan *raw = p.get();
     c->plans[batch] = std::move(p);
     return raw;
@@ -756,10 +714,11 @@ extern "C" int dmx_ctx_set_model(dmx_ctx *c, const dmx_model *m)
         DMXCHK(dmx_model_fp16_plane(m));
     }
     bool sameDecisions = true; // (the lists differ between the models of a bag - derived tensors - without changing any decision)
+    const GemmModelFacts facts = model_facts(m);
     if (m->inexactW != c->m->inexactW || m->inexactH != c->m->inexactH)
         for (const auto &kv : c->plans)
             for (const Op &op : kv.second->ops)
-                if (op.kind == OP_IGEMM && split_kind_model(c, m, op.g) != op.g.split)
+                if (op.kind == OP_IGEMM && select_gemm(op.g, c->gemm, facts, split_lin_mode()) != op.g.choice)
                     sameDecisions = false;
     if (!sameDecisions)
     {
@@ -858,47 +817,50 @@ static int launch_op(const dmx_ctx *c, const Op &op, hipStream_t s, i64 zeroOff)
     case OP_IGEMM:
     {
         const IGemm &g = op.g;
-        GemmArgs k;
-        k.X = a(g.x), k.xBS = g.xBatchStride;
-        k.B = g.B, k.P1 = g.P1, k.P0 = g.P0, k.L1 = g.L1, k.L0 = g.L0, k.Cin = g.Cin;
-        k.S1 = g.S1, k.stride1 = g.stride1, k.dil1 = g.dil1, k.pad1 = g.pad1;
-        k.seg0 = g.seg0, k.stride0 = g.stride0, k.pad0 = g.pad0, k.K = g.K, k.Kp = g.Kp;
-        k.pro = g.pro, k.proStats = a(g.proStats), k.proW = w(g.proW_w), k.proB = w(g.proB_w), k.G0 = g.G0;
-        k.Wt = w(g.w_w), k.bias = w(g.bias_w), k.N = g.N, k.Np = g.Np;
-        k.epi = g.epi, k.act = g.act, k.Y = a(g.y), k.yBS = g.yBatchStride, k.ldy = g.ldy;
+        GemmArgs k{};
+        fill_gemm_geometry(k, g);
+        k.X = a(g.x), k.proStats = a(g.proStats), k.proW = w(g.proW_w), k.proB = w(g.proB_w);
+        k.Wt = w(g.w_w), k.bias = w(g.bias_w), k.Y = a(g.y);
         k.res = a(g.res), k.scale = w(g.scale_w), k.epiStats = a(g.epiStats), k.epiW = w(g.epiW_w), k.epiB = w(g.epiB_w);
-        k.rowstat = a(g.rowstat), k.NB = g.NB, k.table = w(g.table_w), k.tableScale = g.tableScale;
-        k.Lout = g.Lout, k.Cout = g.Cout, k.trS = g.trS, k.trOff = g.trOff;
+        k.rowstat = a(g.rowstat), k.table = w(g.table_w);
         k.kvPl = g.kv >= 0 ? reinterpret_cast<unsigned short *>(A + g.kv) : nullptr;
-        k.kvPlane = (i64)g.B * g.kvT * g.kvH * g.kvHs, k.kvCol0 = g.kvCol0, k.kvT = g.kvT, k.kvH = g.kvH, k.kvHs = g.kvHs;
-        k.M = (i64)g.B * g.P1 * g.P0;
         k.zero = A + zeroOff;
-        k.Wb1 = k.Wb2 = nullptr;
-        k.rowScale = nullptr;
-        if (g.split == 2 && c->m->dWh && c->dRowScale[op.stream ? 1 : 0])
+        int rc = -1;
+        switch (g.choice.family)
+        {
+        case GF_DIRECT:
+            rc = launch_dgemm(k, s);
+            break;
+        case GF_TILE:
+        case GF_LIN256:
+            rc = launch_igemm(g.cfg, k, s);
+            break;
+        case GF_SPLIT_LINH:
         {
             // fp16 terms (opt-in DMX_GEMM_FP16X3): the row scales of this op's A operand first, then the linear-layer kernel on
             // one fp16 weight plane
             float *rs = c->dRowScale[op.stream ? 1 : 0];
+            if (!c->m->dWh || !rs)
+                break;
             launch_rowscale(k, rs, s);
             k.rowScale = rs;
             k.Wb1 = k.Wb2 = c->m->dWh + g.w_w;
-            if (launch_igemm_split(g.cfg, k, s, false, 1) == 0)
-                break;
-            k.rowScale = nullptr;
+            rc = launch_igemm_split(g.choice, g.cfg, k, s);
+            break;
         }
-        if (g.split && c->m->dWb)
-        {
+        case GF_NONE:
+            break;
+        default: // the bf16-term families
+            if (!c->m->dWb)
+                break;
             k.Wb1 = c->m->dWb + g.w_w;
             k.Wb2 = c->m->dWb + c->m->blobFloats + 512 + g.w_w;
-            if (launch_igemm_split(g.cfg, k, s) == 0)
-                break;
+            rc = launch_igemm_split(g.choice, g.cfg, k, s);
+            break;
         }
-        if (g.epi == EPI_KPL || g.epi == EPI_VT) // (get_plan only keeps such ops when the split kernel takes them)
-            return fail(DMX_ERR_ARG, "internal error: K/V plane projection %s without its exact-split kernel", op.name.c_str());
-        if ((g.cfg == kDirectCfg ? launch_dgemm(k, s) : launch_igemm(g.cfg, k, s)) != 0)
-            return fail(DMX_ERR_ARG, "internal error: no igemm kernel for op %s (cfg %d pro %d epi %d)", op.name.c_str(), g.cfg, g.pro,
-                        g.epi);
+        if (rc != 0) // never another arithmetic than the one the plan chose
+            return fail(DMX_ERR_ARG, "internal error: the kernel chosen for op %s does not exist (%s: family %d, cfg %d pro %d epi %d)", op.name.c_str(),
+                        g.choice.label ? g.choice.label : "none", g.choice.family, g.cfg, g.pro, g.epi);
         break;
     }
     case OP_DCONV_ROW:
@@ -1028,20 +990,15 @@ static int launch_op(const dmx_ctx *c, const Op &op, hipStream_t s, i64 zeroOff)
         const LocalAttn &l = op.la;
         // default: the flash attention kernel with the decay penalty (fp32 MFMA; csrc/attention.hip LOC);
         // shapes it does not cover: the reference-order VALU kernel of csrc/v3.hip
-        const bool valu = false;
         const int hd = l.H / 4;
-        int rc = -1;
-        if (!valu)
-        {
-            AttnArgs t{};
-            t.q = a(l.qkvd), t.k = a(l.qkvd) + l.H, t.v = a(l.qkvd) + 2 * l.H, t.o = a(l.out);
-            t.ldq = t.ldk = t.ldv = l.ld, t.ldo = l.H;
-            t.qB = t.kB = t.vB = (i64)l.T * l.ld, t.oB = (i64)l.T * l.H;
-            t.B = l.B, t.Tq = t.Tk = l.T, t.H = 4, t.hs = hd;
-            t.scale = 1.0f / std::sqrt((float)hd);
-            t.decay = a(l.qkvd) + 3 * l.H, t.ldd = l.ld, t.dB = (i64)l.T * l.ld;
-            rc = launch_attention_local(t, s);
-        }
+        AttnArgs t{};
+        t.q = a(l.qkvd), t.k = a(l.qkvd) + l.H, t.v = a(l.qkvd) + 2 * l.H, t.o = a(l.out);
+        t.ldq = t.ldk = t.ldv = l.ld, t.ldo = l.H;
+        t.qB = t.kB = t.vB = (i64)l.T * l.ld, t.oB = (i64)l.T * l.H;
+        t.B = l.B, t.Tq = t.Tk = l.T, t.H = 4, t.hs = hd;
+        t.scale = 1.0f / std::sqrt((float)hd);
+        t.decay = a(l.qkvd) + 3 * l.H, t.ldd = l.ld, t.dB = (i64)l.T * l.ld;
+        const int rc = launch_attention_local(t, s);
         if (rc != 0 && launch_local_attn(LocalAttnArgs{a(l.qkvd), a(l.out), l.B, l.T, l.H, l.ld}, s) != 0)
             return fail(DMX_ERR_ARG, "internal error: no LocalState kernel for op %s (T = %d, H = %d)", op.name.c_str(), l.T, l.H);
         break;
@@ -2483,10 +2440,6 @@ extern "C" int dmx_debug_n_ops(const dmx_ctx *c)
 // algorithmic work of one op: 2*MAC flops, and bytes with every operand read / result written once
 static void op_work(const Op &op, const char *&kernel, double &flops, double &bytes)
 {
-    static const char *cfgNames[] = {"igemm_128x128", "igemm_64x64", "igemm_128x96", "igemm_128x48", "igemm_256x16", "igemm_128x32",
-                                     "igemm_128x64",  "igemm_64x128", "dgemm_direct", "igemm_64x64", "igemm_64x96", "igemm_64x48",
-                                     "igemm_64x32",   "igemm_64x64",  "igemm_128x16", "igemm_32x128", "igemm_32x64", "igemm_256x128", "igemm_256x128w4", "igemm_lin256x128", "igemm_256x96"};
-    static_assert(sizeof(cfgNames) / sizeof(cfgNames[0]) == kNumTileCfgs, "one label per tile configuration");
     flops = bytes = 0;
     kernel = "?";
     switch (op.kind)
@@ -2495,27 +2448,7 @@ static void op_work(const Op &op, const char *&kernel, double &flops, double &by
     {
         const IGemm &g = op.g;
         const double M = (double)g.B * g.P1 * g.P0;
-        kernel = cfgNames[g.cfg];
-        if (g.split) // exact bf16 operand-split kernel of the same tile (igemm_split.hip): its own roofline class
-        {
-            static const char *splitNames[kNumTileCfgs] = {"igemm_split_128x128", nullptr, "igemm_split_128x96", "igemm_split_128x48", nullptr, "igemm_split_128x32d", "igemm_split_128x64d",
-                                                            "igemm_split_64x128", nullptr, "igemm_split_64x64", "igemm_split_64x96", "igemm_split_64x48",
-                                                            "igemm_split_128x32d", "igemm_split_128x64d", nullptr, "igemm_split_32x128", "igemm_split_32x64", nullptr, nullptr,
-                                                            nullptr, nullptr};
-            if (splitNames[g.cfg])
-                kernel = splitNames[g.cfg];
-            if (g.split == 2) // fp16 terms (+ the row-scale pre-pass): its own roofline class (2516.6 / 3)
-                kernel = g.cfg == 0 ? "igemm_splith_128x128" : g.cfg == 7 ? "igemm_splith_64x128" : kernel;
-            else if (g.cfg == 0 || g.cfg == 2)
-            {
-                GemmArgs k{};
-                fill_gemm_geometry(k, g);
-                k.rowstat = g.rowstat >= 0 ? reinterpret_cast<float *>(1) : nullptr; // (only tested against null)
-                const int wide = igemm_split_is_wide(g.cfg, k);
-                if (wide) // (96: the same tile as cfg 2 with the activation fragments loaded straight into registers)
-                    kernel = wide == 256 ? "igemm_split_128x256" : wide == 192 ? "igemm_split_128x192" : "igemm_split_128x96d";
-            }
-        }
+        kernel = g.choice.label; // (each exact-split tile is its own roofline class; fp16 terms + the row-scale pre-pass: 2516.6 / 3)
         flops = 2.0 * M * g.N * g.K;
         double in = (double)g.B * g.L1 * g.L0 * g.Cin, w = (double)g.N * g.K, out = 0;
         if (g.epi == EPI_LINEAR || g.epi == EPI_SCALE_RES)

@@ -407,18 +407,6 @@ int launch_igemm(int cfg, const GemmArgs &a, hipStream_t s, bool dry)
         DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
         DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_STATS_ONLY)
         DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_STATS_FACT) // Demucs v3 level 3: hidden 96 -> 98 factor columns
-        // cfg 17: 256x128 = the double-height sibling of 0 (4 x 2 waves of 64x64, one workgroup per CU: 6 instead of 8
-        // staged float4 per lane and K-tile; same column decomposition, bit-identical). Experiment, DMX_TALL=1.
-        DMX_CASE(17, 4, 2, 4, 4, 2, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(17, 4, 2, 4, 4, 2, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(17, 4, 2, 4, 4, 2, PRO_NONE, EPI_GLU)
-        DMX_CASE(17, 4, 2, 4, 4, 2, PRO_NONE, EPI_TRCONV)
-        // cfg 18: 256x128 with FOUR waves of 128x64 and 16-deep K-tiles (two workgroups per CU stay independent; 12 instead
-        // of 16 fragment reads and 6 instead of 8 staged float4 per 128 MFMAs). Experiment, DMX_TALL=2; plain loop only.
-        DMX_CASE(18, 2, 2, 8, 4, 1, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(18, 2, 2, 8, 4, 1, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(18, 2, 2, 8, 4, 1, PRO_NONE, EPI_GLU)
-        DMX_CASE(18, 2, 2, 8, 4, 1, PRO_NONE, EPI_TRCONV)
         // cfg 20: 256x96 with four waves of 64x96 and 16-deep K-tiles, plain loop: the short-K ops of the 128x96 family
         DMX_CASE(20, 4, 1, 4, 6, 1, PRO_NONE, EPI_LINEAR)
         DMX_CASE(20, 4, 1, 4, 6, 1, PRO_NONE, EPI_GLU)

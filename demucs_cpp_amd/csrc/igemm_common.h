@@ -802,12 +802,4 @@ __device__ __forceinline__ void igemm_epilogue(const GemmArgs &p, f32x4 (&acc)[W
         }
 }
 
-// "linear layer" addressing applies (StageWalk LIN): one contiguous run of K floats per row, K a multiple of the K-tile
-inline bool gemm_is_linear(const GemmArgs &a, int pro, int epi, int ktile)
-{
-    return pro == PRO_NONE && (epi == EPI_LINEAR || epi == EPI_SCALE_RES || epi == EPI_GLU || epi == EPI_KPL || epi == EPI_VT) && a.S1 == 1 && a.pad0 == 0 &&
-           a.seg0 == a.K && a.K == a.Kp && a.K % ktile == 0 && a.Np % 4 == 0 &&
-           (i64)(a.P0 - 1) * a.stride0 * a.Cin + a.seg0 <= (i64)a.L0 * a.Cin && a.P1 == a.L1 && a.stride1 == 1 && a.pad1 == 0;
-}
-
 } // namespace dmx

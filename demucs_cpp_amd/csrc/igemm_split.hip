@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void igemm_split_kernel(const GemmArgs p)
     // LIN: a row is one contiguous run of K floats, so a staging address is (uniform base) + (32-bit byte offset that
     // advances by one K-tile): the loads take the scalar-base form (global_load ... v_off, s[base]) - one address register
     // per lane instead of a 64-bit pointer pair, one 32-bit add per row and tile. Rows beyond M / columns beyond Np read
-    // the last valid row instead of the zero page: their accumulators are never stored (the launcher takes this path
+    // the last valid row instead of the zero page: their accumulators are never stored (the selection takes this path
     // only when every offset fits 32 bits).
     unsigned aOff[AR], bOff[BR];
     if constexpr (LIN)
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(256, 2) void igemm_split_lin_kernel(const GemmArgs 
 // accumulators: the weight planes go global -> LDS directly (global_load_lds_dwordx4, the XOR swizzle applied to the SOURCE
 // octet: no staging registers, no ds_write), one K-tile ahead into the other image (2 x 32 KB per workgroup), and the weight
 // fragments are read two column fragments at a time into two alternating register sets.
-// Same operands in the same order per accumulator as every other exact-split tile: identical bits (the launcher takes this
+// Same operands in the same order per accumulator as every other exact-split tile: identical bits (the selection takes this
 // kernel per LAUNCH, by the row count - batching and sharding still cannot change a bit). N a multiple of 256; row statistics
 // (linear2's LayerNorm partials) are written per 128 columns, as the 128-wide tiles write them.
 //
@@ -545,8 +545,8 @@ __global__ __launch_bounds__(256, 2) void igemm_split_lin_kernel(const GemmArgs 
 // here a row is fetched and split once per 192 / 256 columns and never passes through LDS. K-tile order, chunk -> (run, tap)
 // walk and term order are those of igemm_split_kernel: the same bits (per-launch choice, tools/gpu_lin_ab.py).
 // The narrow forms (WNF = 6 / 4 / 2: 96 / 64 / 32 columns) have the staged tiles' workgroup count; what they drop is the LDS round
-// trip of the activations, and their small register files fit three to four workgroups per CU (launch_wide_conv /
-// launch_split_narrow; measured per form: profiles/r06_experiments/).
+// trip of the activations, and their small register files fit three to four workgroups per CU (gemm_select.cpp wide_conv_width /
+// narrow_split_ok; measured per form: profiles/r06_experiments/).
 template <int WNF, int EPI, bool GEN>
 __global__ __launch_bounds__(256, WNF == 2 ? 4 : WNF <= 6 ? 3 : 2) void igemm_split_linw_kernel(const GemmArgs p)
 {
@@ -660,7 +660,7 @@ __global__ __launch_bounds__(256, WNF == 2 ? 4 : WNF <= 6 ? 3 : 2) void igemm_sp
                 aRaw[SET][i][1] = *reinterpret_cast<const f32x4 *>(src + 4);
             }
             gOffb += KT;
-            if (p.S1 > 1 && gOffb >= p.seg0) // (seg0 >= 32: the launcher checks)
+            if (p.S1 > 1 && gOffb >= p.seg0) // (seg0 >= 32: the selection checks)
             {
                 gOffb -= p.seg0;
                 ++gS1;
@@ -792,7 +792,7 @@ __global__ __launch_bounds__(256, WNF == 2 ? 4 : WNF <= 6 ? 3 : 2) void igemm_sp
     else if constexpr (GEN || WNF != 16)
     {
         // the shared epilogue (igemm_common.h), four column fragments at a time: GLU pairs are adjacent fragments, the
-        // transposed-conv scatter and the linear epilogue are per fragment. No row statistics on this path (the launcher checks).
+        // transposed-conv scatter and the linear epilogue are per fragment. No row statistics on this path (the selection checks).
         float2(*none)[1] = nullptr;
         constexpr int JC = WNF % 4 == 0 ? 4 : 6;
 #pragma unroll
@@ -981,272 +981,110 @@ void launch_split3h_debug(const float *d_x, i64 n, int sexp, unsigned short *d_p
     hipLaunchKernelGGL(split3h_debug_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, d_x, n, ldexpf(1.0f, sexp), d_planes);
 }
 
-// arith 0: bf16 terms (every tile of the table below); arith 1: fp16 terms - only where igemm_split_lin_kernel applies
-// (linear-layer addressing, 128-wide tiles of at least 64 rows); returns -1 where it does not (the caller falls back to
-// arith 0). dry: decide only (needs the op's full geometry for arith 1).
-// The 128 x 256 linear-layer tile (igemm_split_linw_kernel) is taken per LAUNCH - it produces the bits of the 128-wide tiles -
-// where it pays: N a multiple of 256 and enough row tiles that the half as many, twice as large workgroups
-// still fill the 64 slots of an XCD at least `kWideMinRounds` times (the tile map deals row tiles to XCDs). DMX_SPLIT_LIN: 0 = the
-// staged 2 x 2-wave kernel, 2 = never the wide tile, 3 = the wide tile wherever it exists (bitwise A/B: tools/gpu_lin_ab.py).
-static constexpr double kWideMinRounds = 2.5; // (2.62 rounds: linear1 1 - 3 % faster on the wide tile; 1.75: level)
-static bool wide_tile_pays(const GemmArgs &a, int mode)
-{
-    if (a.N % 256 != 0 || a.Np != a.N || a.Kp % 32 != 0 || mode == 2 || mode == 0 || (a.rowstat && a.NB != a.N / 128))
-        return false;
-    if (mode == 3)
-        return true;
-    const i64 tm = (a.M + 127) / 128;
-    return (double)(((tm + 7) / 8) * (a.N / 256)) / 64.0 >= kWideMinRounds;
-}
+// ---- launchers: which kernel runs an op is decided on the host when its plan is built (gemm_select.h); here the chosen family is
+// launched. A family that is not instantiated for the op's (tile, prologue, epilogue) answers -1.
+static dim3 grid_of(const GemmArgs &a) { return dim3(8u * ((a.tilesM + 7u) / 8u) * a.tilesN); } // (XCD-aware tile map: whole groups of 8 row tiles)
 
-// The conv-addressed wide tiles (igemm_split_linw_kernel<WNF, EPI, true>): column fragments per wave (16 = 128 x 256, 12 =
-// 128 x 192) this launch takes, or 0. Ops of the full-height 128 x 128 / 128 x 96 tiles without prologue and row statistics whose
-// A rows are runs of whole 8-float pieces (Cin a multiple of 8) and whose width is whole wide tiles; per LAUNCH, by the same
-// occupancy rule as wide_tile_pays (the results are the bits of the narrow tiles). mode = DMX_SPLIT_LIN (0 / 2: never, 3: always).
-static int wide_conv_width(const GemmArgs &a, int pro, int epi, int mode)
-{
-    if (mode == 0 || mode == 2 || pro != PRO_NONE || !(epi == EPI_LINEAR || epi == EPI_GLU || epi == EPI_TRCONV) || a.rowstat)
-        return 0;
-    const int wnf = a.N % 256 == 0 ? 16 : a.N % 192 == 0 ? 12 : a.N == 96 ? 6 : 0;
-    if (!wnf || a.Np != a.N || a.Kp % 16 != 0 || a.Cin % 8 != 0 || a.seg0 % a.Cin != 0 || a.seg0 < 32 || a.S1 * (a.seg0 / a.Cin) > 32 ||
-        (i64)a.S1 * a.dil1 * a.L0 * a.Cin + a.seg0 >= (1ll << 31) || (epi == EPI_TRCONV && a.Cout % 4 != 0))
-        return 0;
-    if (mode == 3)
-        return wnf;
-    if (mode == 4 && wnf == 6) // (A/B switch: the 96-wide layers stay on the staged tile)
-        return 0;
-    // Measured at 1 - 42 segments per call against the narrow tile the plan chose (profiles/r06_experiments/wide_tile_rounds.txt):
-    // the 96-wide form has the narrow tile's workgroup count and wins everywhere (13 - 24 %); an N = 192 layer replaces TWO 96-wide
-    // tiles and is never slower from 0.66 rounds of an XCD's 64 slots on; the others pay from about one round (N = 768 at 0.98
-    // rounds: 5 - 14 % faster; N = 384 / 512 at 0.66 rounds: 10 - 25 % slower)
-    if (wnf == 6)
-        return wnf;
-    const i64 tm = (a.M + 127) / 128;
-    return (double)(((tm + 7) / 8) * (a.N / (16 * wnf))) / 64.0 >= (a.N == 192 ? 0.6 : 0.9) ? wnf : 0;
-}
-template <int EPI>
-static void launch_wide_conv(GemmArgs a, int wnf, hipStream_t s)
+// the direct-fragment kernel on its narrow tiles (128 x 32 / 64) and its conv-addressed wide ones (128 x 256 / 192 / 96): wnf column
+// fragments per wave, 128-row tiles whatever the op's tile cfg
+static int launch_linw_conv(int wnf, GemmArgs a, hipStream_t s)
 {
     a.tilesM = (unsigned)((a.M + 127) / 128);
-    a.tilesN = (unsigned)(a.N / (16 * wnf));
-    const dim3 grid(8u * ((a.tilesM + 7u) / 8u) * a.tilesN);
-    if (wnf == 16)
-        hipLaunchKernelGGL((igemm_split_linw_kernel<16, EPI, true>), grid, dim3(256), 0, s, a);
-    else if (wnf == 12)
-        hipLaunchKernelGGL((igemm_split_linw_kernel<12, EPI, true>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((igemm_split_linw_kernel<6, EPI, true>), grid, dim3(256), 0, s, a);
-}
-
-// The narrow layers in exact-split arithmetic on the direct-fragment kernel, taken at EVERY batch size (full-height tile cfg and
-// its half-height sibling alike: one arithmetic per op); -1 where the conditions fail - the op keeps its fp32 kernel. dry: decided
-// from the op's whole geometry (api.cpp split_ok fills it).
-//   cfg 5 / 12, N <= 32 (128 x 32, four workgroups per CU): the DConv K1 of the C = 192 levels (Conv1d(192 -> 24, k3): K = 576; row
-//     statistics) - its fp32 tile (igemm_128x32) fetched every input row three times through LDS staging at 2.7x the algorithmic
-//     HBM traffic; here the 88 split operations per 20 MFMAs that kept the staged split tile level with fp32 (round 4) are spread
-//     over four workgroups per CU with nothing else to do (1.10 -> 1.03 ms per 42-segment step: the op is bound by its fragment loads);
-//   cfg 6 / 13, N = 64 (128 x 64, three workgroups per CU): the frequency branch's last transposed conv of a 4-source model
-//     (48 -> 4 x 16, K = 96), which sat on the fp32 matrix pipe at 60 % of its peak in the direct kernel (plan.cpp finish).
-static int launch_split_narrow(int cfg, const GemmArgs &a0, hipStream_t s, int arith, bool dry)
-{
-    const GemmArgs &a = a0;
-    const int np = (cfg == 5 || cfg == 12) ? 32 : 64;
-    if (arith != 0 || a.pro != PRO_NONE || !(a.epi == EPI_LINEAR || (a.epi == EPI_TRCONV && np == 64)) || (a.epi == EPI_LINEAR && a.res) || a.N > np || a.Np != np ||
-        a.Kp % 16 != 0 || a.Cin % 8 != 0 || a.Cin <= 0 || a.seg0 % a.Cin != 0 || a.seg0 < 32 || a.S1 * (a.seg0 / a.Cin) > 32 ||
-        (i64)a.S1 * a.dil1 * a.L0 * a.Cin + a.seg0 >= (1ll << 31) || a.NB != 1 || (a.epi == EPI_TRCONV && (a.rowstat || a.Cout % 4 != 0)) ||
-        (np == 64 && a.rowstat))
-        return -1;
-    if (dry)
+    a.tilesN = (unsigned)((a.N + 16 * wnf - 1) / (16 * wnf));
+#define DMX_LINW(WNF, EPI)                                                                                   \
+    case (WNF * 10 + EPI):                                                                                   \
+        hipLaunchKernelGGL((igemm_split_linw_kernel<WNF, EPI, true>), grid_of(a), dim3(256), 0, s, a); \
         return 0;
-    GemmArgs k = a;
-    k.tilesM = (unsigned)((k.M + 127) / 128);
-    k.tilesN = 1;
-    k.xcdMap = 1;
-    k.dP0 = make_fastdiv((unsigned)k.P0), k.dP1 = make_fastdiv((unsigned)k.P1);
-    const dim3 grid(8u * ((k.tilesM + 7u) / 8u));
-    if (np == 32)
-        hipLaunchKernelGGL((igemm_split_linw_kernel<2, EPI_LINEAR, true>), grid, dim3(256), 0, s, k);
-    else if (a.epi == EPI_LINEAR)
-        hipLaunchKernelGGL((igemm_split_linw_kernel<4, EPI_LINEAR, true>), grid, dim3(256), 0, s, k);
-    else
-        hipLaunchKernelGGL((igemm_split_linw_kernel<4, EPI_TRCONV, true>), grid, dim3(256), 0, s, k);
-    return 0;
+    switch (wnf * 10 + a.epi)
+    {
+        DMX_LINW(16, EPI_LINEAR)
+        DMX_LINW(16, EPI_GLU)
+        DMX_LINW(16, EPI_TRCONV)
+        DMX_LINW(12, EPI_LINEAR)
+        DMX_LINW(12, EPI_GLU)
+        DMX_LINW(12, EPI_TRCONV)
+        DMX_LINW(6, EPI_LINEAR)
+        DMX_LINW(6, EPI_GLU)
+        DMX_LINW(6, EPI_TRCONV)
+        DMX_LINW(4, EPI_LINEAR)
+        DMX_LINW(4, EPI_TRCONV)
+        DMX_LINW(2, EPI_LINEAR)
+    default:
+        return -1;
+    }
+#undef DMX_LINW
 }
 
 template <int WM_, int WN_, int MF, int NF, int PRO, int EPI>
-static int launch_split_one(const GemmArgs &a0, hipStream_t s, int arith, bool dry)
+static int launch_split_one(int family, GemmArgs a, hipStream_t s)
 {
-    // (the K / V plane projections exist only where linear addressing applies: decided below, in dry mode too, from the op's
-    // whole geometry - api.cpp split_ok fills it)
-    if (dry && arith == 0 && EPI != EPI_KPL && EPI != EPI_VT)
-        return 0;
     constexpr int BM = WM_ * MF * 16, BN = WN_ * NF * 16;
-    GemmArgs a = a0;
+    // what is instantiated: linear-layer staging for the epilogues linear layers have; igemm_split_lin_kernel for the 128-wide tiles
+    // of at least 64 rows (cfg 0 / 7), the only kernel of the K / V plane projections besides the 128 x 256 tile of cfg 0
+    constexpr bool kPlanes = EPI == EPI_KPL || EPI == EPI_VT;
+    constexpr bool kLinEpi = PRO == PRO_NONE && (EPI == EPI_LINEAR || EPI == EPI_SCALE_RES || EPI == EPI_GLU);
+    constexpr bool kLinTile = PRO == PRO_NONE && (kLinEpi || kPlanes) && WM_ == 2 && WN_ == 2 && NF == 4 && MF >= 2;
     a.tilesM = (unsigned)((a.M + BM - 1) / BM);
     a.tilesN = (unsigned)((a.N + BN - 1) / BN);
+    switch (family)
+    {
+    case GF_SPLIT_STAGED:
+        if constexpr (!kPlanes)
+        {
+            hipLaunchKernelGGL((igemm_split_kernel<WM_, WN_, MF, NF, PRO, EPI, false>), grid_of(a), dim3(256), 0, s, a);
+            return 0;
+        }
+        break;
+    case GF_SPLIT_STAGED_LIN:
+        if constexpr (kLinEpi)
+        {
+            hipLaunchKernelGGL((igemm_split_kernel<WM_, WN_, MF, NF, PRO, EPI, true>), grid_of(a), dim3(256), 0, s, a);
+            return 0;
+        }
+        break;
+    case GF_SPLIT_LIN:
+        if constexpr (kLinTile)
+        {
+            hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI>), grid_of(a), dim3(256), 0, s, a);
+            return 0;
+        }
+        break;
+    case GF_SPLIT_LINH:
+        if constexpr (kLinTile)
+        {
+            hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI, 1>), grid_of(a), dim3(256), 0, s, a);
+            return 0;
+        }
+        break;
+    case GF_SPLIT_LINW:
+        if constexpr (kLinTile && MF == 4 && EPI != EPI_GLU)
+        {
+            a.tilesN = (unsigned)(a.N / 256);
+            hipLaunchKernelGGL((igemm_split_linw_kernel<16, EPI, false>), grid_of(a), dim3(256), 0, s, a);
+            return 0;
+        }
+        break;
+    default:
+        break;
+    }
+    return -1;
+}
+
+int launch_igemm_split(const GemmChoice &ch, int cfg, const GemmArgs &a0, hipStream_t s)
+{
+    if (!a0.Wb1 || !a0.Wb2)
+        return -1;
+    GemmArgs a = a0;
     a.xcdMap = 1;
     a.dP0 = make_fastdiv((unsigned)a.P0), a.dP1 = make_fastdiv((unsigned)a.P1);
-    const unsigned blocks = 8u * ((a.tilesM + 7u) / 8u) * a.tilesN;
-    // (LIN also requires every staging offset to fit 32 bits: the kernel addresses a row as base + 32-bit byte offset)
-    const bool lin = gemm_is_linear(a, PRO, EPI, 32) && ((i64)a.B * a.xBS + 64) * 4 < (1ll << 32) &&
-                     ((i64)(a.Wb2 - a.Wb1) + (i64)a.Np * a.Kp + 64) * 2 < (1ll << 32);
-    if constexpr (EPI == EPI_KPL || EPI == EPI_VT)
-    {
-        // the K / V plane projections exist on the linear-layer kernel only (plan.cpp plane_linear keeps them on 128- / 64-row
-        // tiles; the V^T form needs its transposed MFMAs)
-        if constexpr (PRO == PRO_NONE && WM_ == 2 && WN_ == 2 && NF == 4 && MF >= 2)
-            if (lin)
-            {
-                if (dry)
-                    return 0;
-                static const int mode = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
-                if (arith == 1)
-                    hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI, 1>), dim3(blocks), dim3(256), 0, s, a);
-                else if (MF == 4 && wide_tile_pays(a, mode == 0 ? 1 : mode))
-                {
-                    a.tilesN = (unsigned)(a.N / 256);
-                    hipLaunchKernelGGL((igemm_split_linw_kernel<16, EPI, false>), dim3(8u * ((a.tilesM + 7u) / 8u) * a.tilesN), dim3(256), 0, s, a);
-                }
-                else
-                    hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI>), dim3(blocks), dim3(256), 0, s, a);
-                return 0;
-            }
-        (void)BM;
-        return -1; // dry: get_plan rebuilds the plan in the fp32-K/V form; a real launch: launch_op reports the error
-    }
-    else if constexpr (PRO == PRO_NONE && (EPI == EPI_LINEAR || EPI == EPI_SCALE_RES || EPI == EPI_GLU))
-    {
-        // plain linear layers of a width the 128 x 256 linear tile takes go there (below); every other full-height op of these
-        // epilogues - strided convs, 3x3 / k3 / 1x1 rewrites - to the conv-addressed wide tiles where they exist and pay
-        if constexpr (EPI != EPI_SCALE_RES && ((WM_ == 2 && WN_ == 2 && MF == 4 && NF == 4) || (WM_ == 4 && WN_ == 1 && MF == 2 && NF == 6)))
-            if (arith == 0 && !(lin && EPI == EPI_LINEAR && a.N % 256 == 0))
-            {
-                static const int mode = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
-                if (const int wnf = wide_conv_width(a, PRO, EPI, mode))
-                {
-                    launch_wide_conv<EPI>(a, wnf, s);
-                    return 0;
-                }
-            }
-        if (lin)
-        {
-            // 128-wide tiles of at least 64 rows: activation fragments straight into registers (igemm_split_lin_kernel);
-            // same tile size and map, same bits. DMX_SPLIT_LIN=0 keeps the staged form (A/B comparison). Measured at 42
-            // segments (profiles/DESIGN_history_r1-r4.md 7.6): the 34 linear-layer launches 24.62 -> 24.44 ms - the loop is bound by the energy
-            // of the bytes it moves from L2, which this form does not change; a 256 x 128 tile with one workgroup per
-            // CU (one wave per SIMD, 445 registers) was 15 % slower and is not kept.
-            if constexpr (WM_ == 2 && WN_ == 2 && NF == 4 && MF >= 2)
-            {
-                static const int mode = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
-                if (arith == 1) // fp16 terms exist on this kernel only
-                {
-                    if (!dry)
-                        hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI, 1>), dim3(blocks), dim3(256), 0, s, a);
-                    return 0;
-                }
-                if constexpr (MF == 4 && EPI != EPI_GLU)
-                    if (wide_tile_pays(a, mode))
-                    {
-                        a.tilesN = (unsigned)(a.N / 256);
-                        hipLaunchKernelGGL((igemm_split_linw_kernel<16, EPI, false>), dim3(8u * ((a.tilesM + 7u) / 8u) * a.tilesN), dim3(256), 0, s, a);
-                        return 0;
-                    }
-                if (mode != 0)
-                {
-                    hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI>), dim3(blocks), dim3(256), 0, s, a);
-                    return 0;
-                }
-            }
-            if (arith == 1)
-                return -1;
-            hipLaunchKernelGGL((igemm_split_kernel<WM_, WN_, MF, NF, PRO, EPI, true>), dim3(blocks), dim3(256), 0, s, a);
-            return 0;
-        }
-    }
-    if (arith == 1)
-        return -1;
-    if constexpr (PRO == PRO_NONE && EPI == EPI_TRCONV && ((WM_ == 2 && WN_ == 2 && MF == 4 && NF == 4) || (WM_ == 4 && WN_ == 1 && MF == 2 && NF == 6)))
-    {
-        static const int mode = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
-        if (const int wnf = wide_conv_width(a, PRO, EPI, mode))
-        {
-            launch_wide_conv<EPI>(a, wnf, s);
-            return 0;
-        }
-    }
-    if constexpr (EPI != EPI_KPL && EPI != EPI_VT)
-        hipLaunchKernelGGL((igemm_split_kernel<WM_, WN_, MF, NF, PRO, EPI, false>), dim3(blocks), dim3(256), 0, s, a);
-    return 0;
-}
-
-// does launch_igemm_split run this op (tile cfg, geometry as api.cpp fill_gemm_geometry fills it) on a wide tile of
-// igemm_split_linw_kernel? 0, or the tile's width 256 / 192 (the per-op profile labels such launches igemm_split_128x256 /
-// igemm_split_128x192: dmx_debug_profile, bench.py)
-int igemm_split_is_wide(int cfg, const GemmArgs &a)
-{
-    static const int mode = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
-    if (cfg != 0 && cfg != 2)
-        return 0;
-    const bool lin = gemm_is_linear(a, a.pro, a.epi, 32) && ((i64)a.B * a.xBS + 64) * 4 < (1ll << 32);
-    if (cfg == 0 && lin && (a.epi == EPI_LINEAR || a.epi == EPI_SCALE_RES || a.epi == EPI_KPL || a.epi == EPI_VT) &&
-        wide_tile_pays(a, (a.epi == EPI_KPL || a.epi == EPI_VT) && mode == 0 ? 1 : mode))
-        return 256;
-    if (lin && a.epi == EPI_LINEAR && a.N % 256 == 0) // (launch_split_one: these stay with the linear-layer kernels)
-        return 0;
-    return 16 * wide_conv_width(a, a.pro, a.epi, mode);
-}
-
-// The MFMA-bound tile families only (plan.h kTileCfgs): 0 / 7 / 15 (2x2 waves, 4 column fragments), 9 / 16 (2 column
-// fragments), 2 / 10 (4x1 waves, 6 column fragments), 3 / 11 (4x1 waves, 3 column fragments, plain convs only).
-// Returns -1 for anything else: the op keeps its fp32 kernel.
-int launch_igemm_split(int cfg, const GemmArgs &a, hipStream_t s, bool dry, int arith)
-{
-    if (a.M >= (1ll << 31) - 256 || !a.Wb1 || !a.Wb2)
-        return -1;
+    if (ch.family == GF_SPLIT_WIDE_CONV || ch.family == GF_SPLIT_NARROW)
+        return launch_linw_conv(ch.wnf, a, s);
 #define DMX_CASE(cfgid, WM_, WN_, MF, NF, PRO, EPI) \
     case (cfgid * 100 + PRO * 10 + EPI):           \
-        return launch_split_one<WM_, WN_, MF, NF, PRO, EPI>(a, s, arith, dry);
-    if (cfg == 5 || cfg == 12 || cfg == 6 || cfg == 13) // 128x32 / 64x32, 128x64 / 64x64 (4 x 1 waves)
-        return launch_split_narrow(cfg, a, s, arith, dry);
+        return launch_split_one<WM_, WN_, MF, NF, PRO, EPI>(ch.family, a, s);
     switch (cfg * 100 + a.pro * 10 + a.epi)
     {
-        DMX_CASE(0, 2, 2, 4, 4, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(0, 2, 2, 4, 4, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(0, 2, 2, 4, 4, PRO_NONE, EPI_GLU)
-        DMX_CASE(0, 2, 2, 4, 4, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(7, 2, 2, 2, 4, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(7, 2, 2, 2, 4, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(7, 2, 2, 2, 4, PRO_NONE, EPI_GLU)
-        DMX_CASE(7, 2, 2, 2, 4, PRO_NONE, EPI_TRCONV)
-        // K / V projections that write the attention kernel's operand planes (plan.cpp plane_linear)
-        DMX_CASE(0, 2, 2, 4, 4, PRO_NONE, EPI_KPL)
-        DMX_CASE(0, 2, 2, 4, 4, PRO_NONE, EPI_VT)
-        DMX_CASE(7, 2, 2, 2, 4, PRO_NONE, EPI_KPL)
-        DMX_CASE(7, 2, 2, 2, 4, PRO_NONE, EPI_VT)
-        DMX_CASE(2, 4, 1, 2, 6, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(2, 4, 1, 2, 6, PRO_NONE, EPI_GLU)
-        DMX_CASE(2, 4, 1, 2, 6, PRO_NONE, EPI_TRCONV)
-        // half / quarter-height siblings (few segments in flight): same column decomposition, same bits as their parents
-        DMX_CASE(15, 2, 2, 1, 4, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(15, 2, 2, 1, 4, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(15, 2, 2, 1, 4, PRO_NONE, EPI_GLU)
-        DMX_CASE(15, 2, 2, 1, 4, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(9, 2, 2, 2, 2, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(9, 2, 2, 2, 2, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(9, 2, 2, 2, 2, PRO_NONE, EPI_GLU)
-        DMX_CASE(9, 2, 2, 2, 2, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(16, 2, 2, 1, 2, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(16, 2, 2, 1, 2, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(16, 2, 2, 1, 2, PRO_NONE, EPI_GLU)
-        DMX_CASE(16, 2, 2, 1, 2, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(10, 4, 1, 1, 6, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(10, 4, 1, 1, 6, PRO_NONE, EPI_GLU)
-        DMX_CASE(10, 4, 1, 1, 6, PRO_NONE, EPI_TRCONV)
-        // 48-wide tiles (4 x 1 waves, 3 column fragments): the deepest DConv K1 convs (K = 3 C = 1152, N = C / 8 = 48: 72 flops
-        // per byte, above what the fp32 MFMA feeds at HBM speed): 96-102 -> 118-143 TFLOP/s. The 32-wide tiles of the
-        // level below (N = 24) were measured on this path too: no change (88 split operations per 20 MFMAs), they keep fp32.
-        DMX_CASE(3, 4, 1, 2, 3, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(11, 4, 1, 1, 3, PRO_NONE, EPI_LINEAR)
+        DMX_SPLIT_COMBOS(DMX_CASE)
     default:
         return -1;
     }

@@ -1,7 +1,7 @@
 // kernels.h — launch interface of the hand-written gfx950 kernels (device pointers resolved).
 // Semantics of every op are specified by plan.h and, executable, by tests/cpu_interp.cpp.
 #pragma once
-#include "plan.h"
+#include "gemm_select.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -93,13 +93,10 @@ int launch_dconv_row(const DconvRowArgs &a, hipStream_t s, bool dry = false);
 int launch_igemm(int cfg, const GemmArgs &a, hipStream_t s, bool dry = false);
 // linear layers on a 256x128 tile with four waves of 128x64 (igemm_lin256.hip); -1 when the op is not a plain linear layer
 int launch_igemm_lin256(const GemmArgs &a, hipStream_t s, bool dry = false);
-// GEMM_BF16X3 contexts: the same tiles with exact bf16 operand splits on the bf16 matrix pipe (igemm_split.hip); -1 = not available
-// arith 0: bf16 terms (DMX_GEMM_BF16X3); 1: fp16 terms (DMX_GEMM_FP16X3: Wb1 = the fp16 plane, rowScale set) - exists for the
-// linear-layer kernel only, returns -1 elsewhere; a dry call with arith 1 needs the op's whole geometry in `a`
-int launch_igemm_split(int cfg, const GemmArgs &a, hipStream_t s, bool dry = false, int arith = 0);
-// 256 / 192: that launch takes a wide tile of igemm_split_linw_kernel (128 x 256 / 128 x 192), decided per launch; 0: it does not.
-// Same bits either way
-int igemm_split_is_wide(int cfg, const GemmArgs &a);
+// the exact-split kernel family `ch` chose for the op (gemm_select.h; igemm_split.hip): bf16 terms on the two planes Wb1 / Wb2, or
+// (GF_SPLIT_LINH) fp16 terms with Wb1 = the fp16 plane and rowScale set. -1: the family does not exist for the op's (tile,
+// prologue, epilogue) - an internal error, the selection only names kernels that exist
+int launch_igemm_split(const GemmChoice &ch, int cfg, const GemmArgs &a, hipStream_t s);
 // per-row scales of a linear layer's A operand (rows of K contiguous floats, the addressing of `a`): out[m] = rowscale_of(max |a|)
 void launch_rowscale(const GemmArgs &a, float *out, hipStream_t s);
 // the fp16 three-term split applied to an array under ONE scale 2^sexp: planes [3][n] fp16 bit patterns (unit test of the split)

@@ -263,7 +263,7 @@ struct Builder
         // sits on the fp32 matrix pipe's ridge; an fp32 context keeps the direct kernel (its tiled fp32 form is 20 % slower)
         const bool rewrite0Split = opts.gemm != GEMM_F32 && g.pro == PRO_NONE && g.epi == EPI_GLU && g.S1 == 1 && g.seg0 == 48 && g.N == 96;
         // likewise the frequency branch's last transposed conv (48 -> 4 x Cout, K = 96): N = 64 (4 sources; igemm_split.hip
-        // launch_split_narrow: 0.947 -> 0.917 ms) and N = 96 (6 sources: 1.57 -> 1.22 ms). The time branch's (N = 32 / 48) stays on
+        // narrow tile, gemm_select.cpp: 0.947 -> 0.917 ms) and N = 96 (6 sources: 1.57 -> 1.22 ms). The time branch's (N = 32 / 48) stays on
         // the direct kernel (N = 32 measured: 0.286 -> 0.293 ms)
         const bool lastTrSplit = opts.gemm != GEMM_F32 && g.pro == PRO_NONE && g.epi == EPI_TRCONV && g.S1 == 1 && g.seg0 == 96 &&
                                  (g.N == 64 || g.N == 96);

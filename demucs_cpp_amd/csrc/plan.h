@@ -81,6 +81,30 @@ enum StatsMode
     MODE_ZNORM = 1,
 };
 
+// Which kernel runs an OP_IGEMM (gemm_select.h select_gemm decides, api.cpp get_plan stores it in the op)
+enum GemmFamily
+{
+    GF_NONE = 0,         // not chosen: plans outside a context (tests/cpu_interp.cpp)
+    GF_DIRECT,           // dgemm.hip: register-resident weights (kDirectCfg)
+    GF_TILE,             // igemm.hip: the LDS-tiled fp32 kernel of the op's tile cfg
+    GF_LIN256,           // igemm_lin256.hip (cfg 19)
+    // ---- exact operand splits (igemm_split.hip)
+    GF_SPLIT_STAGED,     // igemm_split_kernel of the op's tile cfg, conv addressing
+    GF_SPLIT_STAGED_LIN, // the same with linear-layer staging (LIN)
+    GF_SPLIT_LIN,        // igemm_split_lin_kernel: linear layers, activation fragments straight into registers (cfg 0 / 7)
+    GF_SPLIT_LINH,       // its fp16-term form
+    GF_SPLIT_LINW,       // igemm_split_linw_kernel<16, ., false>: the 128 x 256 linear-layer tile
+    GF_SPLIT_WIDE_CONV,  // igemm_split_linw_kernel<wnf, ., true>, wnf = 16 / 12 / 6: the conv-addressed 128 x 256 / 192 / 96 tiles
+    GF_SPLIT_NARROW,     // igemm_split_linw_kernel<wnf, ., true>, wnf = 2 / 4: 128 x 32 / 64 (cfg 5 / 12, 6 / 13)
+};
+struct GemmChoice
+{
+    int family;        // GemmFamily
+    int arith;         // 0: fp32 operands; 1: bf16 terms (exact); 2: fp16 terms under a per-row scale (bounded)
+    int wnf;           // column fragments per wave of igemm_split_linw_kernel (GF_SPLIT_WIDE_CONV / GF_SPLIT_NARROW), else 0
+    const char *label; // the op's kernel in dmx_debug_profile = bench.py's roofline class (a string literal)
+};
+
 struct IGemm
 {
     // ---- rows: m -> (b, p1, p0), M = B*P1*P0
@@ -118,7 +142,7 @@ struct IGemm
     int trS, trOff;           // EPI_TRCONV: n = (r, co), r < trS; output position j = trS*p0 + r - trOff
                               // (k8/s4 with the 2-sample crop: 4, 2; v3's uncropped k8/s4: 4, 0; k4/s2: 2, 0)
     int cfg;                  // tile configuration index (engine)
-    int split;                // GEMM_BF16X3 / GEMM_FP16X3 contexts (api.cpp split_kind): 1 = run on the exact-split bf16 kernel (igemm_split.hip); 2 = on its fp16-term form
+    GemmChoice choice;        // the kernel that runs the op in its context (api.cpp get_plan)
     // EPI_KPL / EPI_VT: A (float offset) of three bf16 planes of B*kvT*(kvH*kvHs) elements each; rows are tokens (P1 = kvT,
     // P0 = 1), kvT a multiple of 64; -1 otherwise
     i64 kv;
@@ -364,12 +388,11 @@ static const TileCfg kTileCfgs[] = {
     // leave most CUs with a single workgroup)
     {32, 128},  // 15  of 7 (2 x 2 waves, 1 x 4 fragments: the column decomposition of 0 and 7, row statistics identical)
     {32, 64},   // 16  of 9
-    {256, 128}, // 17  double-height sibling of 0 (8 waves, one workgroup per CU); experiment behind DMX_TALL=1
-    {256, 128}, // 18  the same tile with FOUR waves of 128x64 and 16-deep K-tiles (two workgroups per CU); experiment, DMX_TALL=2
-    {256, 128}, // 19  igemm_lin256.hip: that tile with its own pipelined loop, linear layers only
+    {256, 128}, // 17  unused (no kernel, never chosen; the slot keeps the numbering)
+    {256, 128}, // 18  unused
+    {256, 128}, // 19  igemm_lin256.hip: four waves of 128x64 with their own pipelined loop, linear layers only
                 //     (same column decomposition as 0 / 7, bit-identical results)
-    {256, 96},  // 20  four waves of 64x96, 16-deep K-tiles, plain loop: the short-K ops of the 128x96 family (plan.cpp); all of
-                //     that family with DMX_TALL=3 (probe)
+    {256, 96},  // 20  four waves of 64x96, 16-deep K-tiles, plain loop: the short-K ops of the 128x96 family (plan.cpp, DMX_SHORTK)
 };
 static const int kNumTileCfgs = 21;
 static const int kDirectCfg = 8;
@@ -390,7 +413,7 @@ enum GemmMode
     GEMM_F32 = 0,    // v_mfma_f32_16x16x4_f32: fp32 operands, one k-ordered fmaf chain per output
     GEMM_BF16X3 = 1, // exact operand splits a = a1 + a2 + a3, w = w1 + w2 (bf16 terms) on the bf16 matrix pipe, fp32 accumulate
     GEMM_FP16X3 = 2, // opt-in: as GEMM_BF16X3 (same plan), except that the linear layers run with fp16 terms under a per-row
-                     // power-of-two scale where their weights allow (api.cpp split_kind): bounded, not exact
+                     // power-of-two scale where their weights allow (gemm_select.h): bounded, not exact
 };
 struct PlanOpts
 {

@@ -7,6 +7,7 @@
 // it, and the product fails loudly without a GPU.
 #include "../demucs_cpp_amd/csrc/model_pack.cpp"
 #include "../demucs_cpp_amd/csrc/plan.cpp"
+#include "../demucs_cpp_amd/csrc/gemm_select.cpp"
 
 #include <complex>
 
@@ -53,6 +54,8 @@ struct Interp
     Plan pl;
     std::vector<float> A;
     const float *W;
+    std::vector<i64> notFp16; // interp_select_dump: blob offsets of the weights that are not fp16 numbers (filled on first use)
+    bool scanned = false;
 
     void run_igemm(const IGemm &g)
     {
@@ -796,4 +799,101 @@ extern "C" int interp_plan_dump(void *h, char *buf, int cap)
         return -1;
     memcpy(buf, all.c_str(), all.size() + 1);
     return (int)all.size();
+}
+
+// ---- the kernel selection (csrc/gemm_select.cpp: host arithmetic), driven without a GPU by tests/test_gemm_select_cpu.py
+static void print_choice(std::string &all, const std::string &name, const IGemm &g, const GemmChoice &c)
+{
+    char line[320];
+    snprintf(line, sizeof(line), "%s %d %d %d %d %d %d %s\n", name.c_str(), g.cfg, g.epi, g.hterms, c.family, c.arith, c.wnf, c.label ? c.label : "-");
+    all += line;
+}
+static int copy_out(const std::string &all, char *buf, int cap)
+{
+    if ((int)all.size() + 1 > cap)
+        return -1;
+    memcpy(buf, all.c_str(), all.size() + 1);
+    return (int)all.size();
+}
+// is x an fp16 number (subnormals included)? What dmx_model_upload lists for the fp16 plane
+static bool is_fp16_number(float x)
+{
+    if (x == 0.f)
+        return true;
+    int e;
+    (void)std::frexp(x, &e); // |x| in [2^(e-1), 2^e)
+    if (!std::isfinite(x) || e > 16)
+        return false;
+    const float q = std::ldexp(x, -std::max(e - 11, -24)); // in units of the fp16 ulp at x
+    return q == std::floor(q);
+}
+
+// The plan a context of GEMM mode `gemm` builds for the handle's model at segment length seg and batch B (gemm_select.h build_chosen_plan, as
+// api.cpp get_plan calls it), one line per OP_IGEMM: name, tile cfg, epilogue, hterms, family, arithmetic, wnf, label.
+// Model facts: both kinds of weight planes exist; BOTH inexact lists hold the blob elements that are not fp16 numbers (the fp16 list
+// of dmx_model_upload; every fp16 number is two-bf16-term exact, so it contains the bf16 list) plus all weights of the op named
+// `inexact` ("" = none).
+extern "C" int interp_select_dump(void *h, int64_t seg, int B, int gemm, int linMode, const char *inexact, char *buf, int cap)
+{
+    Interp *it = (Interp *)h;
+    if (!it->scanned)
+        for (size_t i = 0; i < it->pm.blob.size(); ++i)
+            if (!is_fp16_number(it->pm.blob[i]))
+                it->notFp16.push_back((i64)i);
+    it->scanned = true;
+    std::vector<i64> bad = it->notFp16;
+    GemmModelFacts f;
+    f.bf16Planes = f.fp16Plane = true;
+    f.planeDelta = (i64)it->pm.blob.size() + 512;
+    f.inexactW = f.inexactH = &bad;
+    const bool kvPlanes = gemm != GEMM_F32 && it->pm.arch != 3;
+    Plan pl;
+    build_chosen_plan(it->pm, seg, B, gemm, kvPlanes, f, linMode, pl);
+    if (inexact && *inexact)
+    {
+        bool found = false;
+        for (const Op &op : pl.ops)
+            if (op.kind == OP_IGEMM && op.name == inexact)
+            {
+                for (i64 i = 0; i < (i64)op.g.Np * op.g.Kp; ++i)
+                    bad.push_back(op.g.w_w + i);
+                found = true;
+            }
+        if (!found)
+            return -2;
+        std::sort(bad.begin(), bad.end());
+        pl = Plan();
+        build_chosen_plan(it->pm, seg, B, gemm, kvPlanes, f, linMode, pl);
+    }
+    std::string all;
+    for (const Op &op : pl.ops)
+        if (op.kind == OP_IGEMM)
+        {
+            print_choice(all, op.name, op.g, op.g.choice);
+            const GemmChoice again = select_gemm(op.g, gemm, f, linMode); // (a second call gives the same choice)
+            if (again != op.g.choice || again.label != op.g.choice.label)
+                return -3;
+        }
+    return copy_out(all, buf, cap);
+}
+
+// The choice for a hand-made op: a copy of op `name` of the handle's plan with tile cfg, epilogue, N, Np, residual offset and
+// row-statistics offset replaced (-2 keeps a field); every weight counts as exact. One line as interp_select_dump prints it.
+extern "C" int interp_select_one(void *h, const char *name, int gemm, int linMode, int cfg, int epi, int N, int Np, int res, int rowstat, char *buf, int cap)
+{
+    Interp *it = (Interp *)h;
+    GemmModelFacts f;
+    f.bf16Planes = f.fp16Plane = true;
+    f.planeDelta = (i64)it->pm.blob.size() + 512;
+    for (const Op &op : it->pl.ops)
+        if (op.kind == OP_IGEMM && op.name == name)
+        {
+            IGemm g = op.g;
+            g.cfg = cfg != -2 ? cfg : g.cfg, g.epi = epi != -2 ? epi : g.epi, g.N = N != -2 ? N : g.N, g.Np = Np != -2 ? Np : g.Np;
+            g.res = res != -2 ? res : g.res, g.rowstat = rowstat != -2 ? rowstat : g.rowstat;
+            std::string all;
+            print_choice(all, op.name, g, select_gemm(g, gemm, f, linMode));
+            return copy_out(all, buf, cap);
+        }
+    return -2;
 }

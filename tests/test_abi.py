@@ -148,7 +148,7 @@ def test_weight_split_is_exact_for_every_fp16_value(dmx):
     (/root/reference/scripts/convert-pth-to-ggml.py:111-140) - is the sum of two bf16 terms by round-to-nearest splits.
     Pure host function: checked here for EVERY finite fp16 bit pattern (subnormals included - bf16 has the fp32 exponent
     range), with the bound |w2| <= 2^-8 |w| that makes the dropped a3 w2 product <= 2^-24 |a w|; values that are not
-    fp16-exact are reported (such ops keep the fp32 kernel, api.cpp split_ok)."""
+    fp16-exact are reported (such ops keep the fp32 kernel, csrc/gemm_select.cpp)."""
     h = np.arange(0, 1 << 16, dtype=np.uint16).view(np.float16)
     w = h[np.isfinite(h)].astype(np.float32)
     w1, w2, bad = dmx.split_weights(w)

@@ -139,7 +139,7 @@ def test_two_stream_waits_cover_every_hazard(ns, interp, tmp_models):
 
 TILES = {0: (128, 128), 1: (64, 64), 2: (128, 96), 3: (128, 48), 4: (256, 16), 5: (128, 32), 6: (128, 64), 7: (64, 128), 8: (16, 256),
          9: (64, 64), 10: (64, 96), 11: (64, 48), 12: (64, 32), 13: (64, 64), 14: (128, 16), 15: (32, 128), 16: (32, 64),
-         17: (256, 128), 18: (256, 128), 19: (256, 128), 20: (256, 96)}  # 17 / 18: experiment tiles (DMX_TALL); 19: igemm_lin256.hip, linear layers
+         17: (256, 128), 18: (256, 128), 19: (256, 128), 20: (256, 96)}  # 17 / 18: unused slots (no kernel); 19: igemm_lin256.hip, linear layers
 # cfg -> family (column decomposition: waves x fragments along N); siblings of a family give identical bits,
 # the families with row statistics never cross (plan.h)
 FAMILY = {0: "2x4", 7: "2x4", 15: "2x4", 17: "2x4", 18: "2x4", 19: "2x4", 20: "1x6", 9: "2x2", 16: "2x2", 2: "1x6", 10: "1x6", 3: "1x3", 11: "1x3", 5: "1x2", 12: "1x2",
@@ -232,7 +232,7 @@ def test_tile_choice_counts_workgroups_per_xcd(interp, tmp_models):
     """The igemm tile map deals ROW tiles round-robin to the 8 XCDs (all column tiles of a row tile on one XCD), so the
     cost model counts the workgroups of the busiest XCD: decoder.0.rewrite at 4 segments is 84 x 6 tiles of 128x128 =
     11 row tiles on four of the XCDs = 66 workgroups for 64 slots; measured 617 us against 428 us with the 64x128 sibling
-    (profiles/DESIGN_history_r1-r4.md 7.1). The double-height experiment tile (cfg 17) is never chosen without DMX_TALL."""
+    (profiles/DESIGN_history_r1-r4.md 7.1). The unused slot cfg 17 (once a double-height experiment tile) is never chosen."""
     interp.interp_plan_dump.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
     interp.interp_create_plan.restype = ctypes.c_void_p
     interp.interp_create_plan.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int]
