@@ -16,12 +16,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
 OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o attention.o attention_split.o resample.o pcm.o flac.o v3.o api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp plan_harness harness micro
+all: $(LIB) cli oracle interp op_step plan_harness harness micro
 
 build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@ $(QUIET)
-build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
+build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@ $(QUIET)
 
@@ -38,6 +38,13 @@ oracle:
 interp:
 	@mkdir -p tests/_build
 	g++ -O2 -march=native -fopenmp -std=c++17 -fPIC -shared -o tests/_build/libcpu_interp.so tests/cpu_interp.cpp
+# the interpreter's step interface as a stand-alone program (tests/test_op_reference_cpu.py; CXXFLAGS_OP_STEP=-fsanitize=address,undefined
+# OP_STEP_OUT=... builds the sanitizer form)
+OP_STEP_OUT ?= tests/_build/op_step_main
+op_step: $(OP_STEP_OUT)
+$(OP_STEP_OUT): tests/op_step_main.cpp tests/cpu_interp.cpp $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp
+	@mkdir -p $(dir $@)
+	g++ -O2 -g -std=c++17 -fopenmp $(CXXFLAGS_OP_STEP) -o $@ tests/op_step_main.cpp
 # the multi-track plan (csrc/tracks_plan.cpp: host arithmetic, no HIP) as a stand-alone CPU program that prints it as JSON
 plan_harness: tests/_build/tracks_plan_harness
 tests/_build/tracks_plan_harness: tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp $(CSRC)/tracks_plan.h include/demucs_hip.h
@@ -82,7 +89,7 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp plan_harness harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:

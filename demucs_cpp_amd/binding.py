@@ -30,6 +30,8 @@ EXPORTS = [
     "dmx_segment_infer_device", "dmx_track_infer", "dmx_track_geometry", "dmx_track_stats_device",
     "dmx_track_gather_device", "dmx_track_overlap_add_device", "dmx_debug_tap", "dmx_debug_n_ops",
     "dmx_debug_profile", "dmx_ctx_set_model", "dmx_model_clone",
+    "dmx_debug_plan_info", "dmx_debug_op_info", "dmx_debug_arena_fill", "dmx_debug_arena_io", "dmx_debug_run_op", "dmx_debug_op_cfgs",
+    "dmx_debug_run_op_as",
     "dmx_engine_create", "dmx_engine_free", "dmx_engine_n_devices", "dmx_engine_n_models", "dmx_engine_n_sources",
     "dmx_resample_length", "dmx_resample_filter", "dmx_resample_device", "dmx_resample",
     "dmx_ctx_create_gemm", "dmx_ctx_gemm", "dmx_default_gemm", "dmx_set_default_gemm", "dmx_debug_split_weights", "dmx_debug_split_activations", "dmx_debug_split_activations_fp16",
@@ -162,6 +164,13 @@ def lib():
         L.dmx_debug_tap.argtypes = [vp, ctypes.c_char_p, vp, fp]
         L.dmx_debug_n_ops.argtypes = [vp]
         L.dmx_debug_profile.argtypes = [vp, ci, ci, ctypes.c_char_p, ci]
+        L.dmx_debug_plan_info.argtypes = [vp, ci, vp, vp, vp, vp]
+        L.dmx_debug_op_info.argtypes = [vp, ci, ci, ctypes.c_char_p, ci]
+        L.dmx_debug_arena_fill.argtypes = [vp, ci, ctypes.c_uint]
+        L.dmx_debug_arena_io.argtypes = [vp, i64, i64, fp, ci]
+        L.dmx_debug_run_op.argtypes = [vp, ci, ci]
+        L.dmx_debug_op_cfgs.argtypes = [vp, ci, ci, vp, ci]
+        L.dmx_debug_run_op_as.argtypes = [vp, ci, ci, ci, ci, ctypes.c_char_p, ci]
         L.dmx_ctx_set_model.argtypes = [vp, vp]
         L.dmx_engine_create.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, ctypes.POINTER(ci), ci, ci, ci, ctypes.POINTER(vp)]
         L.dmx_engine_free.argtypes = [vp]
@@ -178,6 +187,23 @@ def lib():
 def _chk(rc):
     if rc != 0:
         raise DmxError(rc, lib().dmx_last_error().decode(errors="replace"))
+
+
+DEBUG_NO_KERNEL = 6  # dmx_debug_run_op_as: no such kernel, nothing launched
+
+
+def parse_op_info(text: str) -> dict:
+    """key=value words of dmx_debug_op_info / dmx_debug_run_op_as -> dict: integers as int, 'lo:hi,' lists as [(lo, hi)]"""
+    d = {}
+    for word in text.split():
+        k, _, v = word.partition("=")
+        if k in ("reads", "writes", "scratch", "rowstat"):
+            d[k] = [tuple(int(x) for x in r.split(":")) for r in v.split(",") if r]
+        elif k in ("name", "label"):
+            d[k] = v
+        else:
+            d[k] = int(v)
+    return d
 
 
 def device_count() -> int:
@@ -579,6 +605,51 @@ class Context:
         out = np.zeros(shp, np.float32)
         lib().dmx_debug_tap(self.h, name.encode(), shape, out.ctypes.data)
         return out
+
+    # ---- one op at a time (include/demucs_hip.h; tests/test_gpu_op_parity.py)
+    def plan_info(self, batch: int):
+        """(number of ops, floats of the arena, floats the plan of `batch` uses, floats of its leading constants)"""
+        n, a, p, k = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _chk(lib().dmx_debug_plan_info(self.h, batch, ctypes.byref(n), ctypes.byref(a), ctypes.byref(p), ctypes.byref(k)))
+        return n.value, a.value, p.value, k.value
+
+    def op_info(self, batch: int, i: int) -> dict:
+        """the key=value words of dmx_debug_op_info; ranges as lists of (lo, hi)"""
+        buf = ctypes.create_string_buffer(4096)
+        if lib().dmx_debug_op_info(self.h, batch, i, buf, 4096) < 0:
+            raise RuntimeError(f"no op {i}")
+        return parse_op_info(buf.value.decode())
+
+    def arena_fill(self, batch: int, pattern: int):
+        _chk(lib().dmx_debug_arena_fill(self.h, batch, pattern & 0xFFFFFFFF))
+
+    def arena_write(self, off: int, values: np.ndarray):
+        v = np.ascontiguousarray(values, np.float32)
+        _chk(lib().dmx_debug_arena_io(self.h, off, v.size, v.ctypes.data, 1))
+
+    def arena_read(self, off: int, n: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        out = np.empty(n, np.float32) if out is None else out
+        _chk(lib().dmx_debug_arena_io(self.h, off, n, out.ctypes.data, 0))
+        return out
+
+    def run_op(self, batch: int, i: int):
+        _chk(lib().dmx_debug_run_op(self.h, batch, i))
+
+    def op_cfgs(self, batch: int, i: int):
+        arr = (ctypes.c_int * 16)()
+        n = lib().dmx_debug_op_cfgs(self.h, batch, i, arr, 16)
+        if n < 0:
+            raise RuntimeError(f"op {i} is no GEMM of the plan")
+        return [arr[k] for k in range(n)]
+
+    def run_op_as(self, batch: int, i: int, cfg: int, lin_mode: int) -> Optional[dict]:
+        """runs GEMM i on tile cfg; None where no such kernel exists (nothing launched), else the copy's choice"""
+        buf = ctypes.create_string_buffer(512)
+        rc = lib().dmx_debug_run_op_as(self.h, batch, i, cfg, lin_mode, buf, 512)
+        if rc == DEBUG_NO_KERNEL:
+            return None
+        _chk(rc)
+        return parse_op_info(buf.value.decode())
 
     def profile(self, batch: int = 1, reps: int = 3):
         """[(op name, kernel, ms per launch, algorithmic flops, algorithmic bytes)]"""

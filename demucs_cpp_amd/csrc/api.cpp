@@ -7,6 +7,7 @@
 // No CPU fallback exists: without a usable HIP device every compute entry point fails.
 #include "api_internal.h"
 #include "tracks_plan.h"
+#include "plan_describe.h"
 
 #include <algorithm>
 #include <atomic>
@@ -302,36 +303,38 @@ extern "C" int dmx_model_n_tensors(const dmx_model *m) { return m ? m->pm.n_tens
 extern "C" int dmx_model_device(const dmx_model *m) { return m ? m->device : -1; }
 extern "C" int dmx_model_arch(const dmx_model *m) { return m ? m->pm.arch : 0; }
 
-// alignment contract of the igemm staging loads (igemm.hip header) + kernel availability
+// alignment contract of the igemm staging loads (igemm.hip header) + kernel availability, one OP_IGEMM
+static bool validate_gemm(const Op &op, std::string &why)
+{
+    const IGemm &g = op.g;
+    const bool al = ((i64)g.L0 * g.Cin) % 4 == 0 && (g.stride0 * g.Cin) % 4 == 0 && (g.pad0 * g.Cin) % 4 == 0 &&
+                    g.seg0 % 4 == 0 && g.K % 4 == 0 && g.xBatchStride % 4 == 0 && (g.S1 == 1 || g.seg0 % 16 == 0) &&
+                    (g.cfg == kDirectCfg || (g.Cin % 4 == 0 && g.seg0 % g.Cin == 0 && g.S1 * (g.seg0 / g.Cin) <= 31)); // one validity bit per tap (igemm.hip)
+    if (g.epi == EPI_KPL || g.epi == EPI_VT) // exist on the exact-split kernels only; build_chosen_plan keeps them only there
+    {
+        if (g.choice.arith == 0)
+        {
+            why = "op " + op.name + ": K / V plane projection without its exact-split kernel";
+            return false;
+        }
+        return true;
+    }
+    // the fp32 kernel must exist for split ops too: dmx_ctx_set_model may bind a model whose weights turn them to fp32
+    GemmArgs k{};
+    fill_gemm_geometry(k, g);
+    const bool exists = (g.cfg == kDirectCfg ? launch_dgemm(k, nullptr, true) : launch_igemm(g.cfg, k, nullptr, true)) == 0;
+    if (!al || !exists)
+    {
+        why = "op " + op.name + (al ? ": no kernel instantiated for its (tile, prologue, epilogue)" : ": staging alignment contract violated");
+        return false;
+    }
+    return true;
+}
 static bool validate_plan(const Plan &p, std::string &why)
 {
     for (const Op &op : p.ops)
-    {
-        if (op.kind != OP_IGEMM)
-            continue;
-        const IGemm &g = op.g;
-        const bool al = ((i64)g.L0 * g.Cin) % 4 == 0 && (g.stride0 * g.Cin) % 4 == 0 && (g.pad0 * g.Cin) % 4 == 0 &&
-                        g.seg0 % 4 == 0 && g.K % 4 == 0 && g.xBatchStride % 4 == 0 && (g.S1 == 1 || g.seg0 % 16 == 0) &&
-                        (g.cfg == kDirectCfg || (g.Cin % 4 == 0 && g.seg0 % g.Cin == 0 && g.S1 * (g.seg0 / g.Cin) <= 31)); // one validity bit per tap (igemm.hip)
-        if (g.epi == EPI_KPL || g.epi == EPI_VT) // exist on the exact-split kernels only; build_chosen_plan keeps them only there
-        {
-            if (g.choice.arith == 0)
-            {
-                why = "op " + op.name + ": K / V plane projection without its exact-split kernel";
-                return false;
-            }
-            continue;
-        }
-        // the fp32 kernel must exist for split ops too: dmx_ctx_set_model may bind a model whose weights turn them to fp32
-        GemmArgs k{};
-        fill_gemm_geometry(k, g);
-        const bool exists = (g.cfg == kDirectCfg ? launch_dgemm(k, nullptr, true) : launch_igemm(g.cfg, k, nullptr, true)) == 0;
-        if (!al || !exists)
-        {
-            why = "op " + op.name + (al ? ": no kernel instantiated for its (tile, prologue, epilogue)" : ": staging alignment contract violated");
+        if (op.kind == OP_IGEMM && !validate_gemm(op, why))
             return false;
-        }
-    }
     return true;
 }
 
@@ -2603,4 +2606,149 @@ extern "C" int dmx_debug_profile(dmx_ctx *c, int batch, int reps, char *report, 
         report[k] = 0;
     }
     return n;
+}
+
+// --------------------------------------------------------------------------- one op at a time (tests/test_gpu_op_parity.py)
+// The entry points below act on the context's own plan for `batch` and launch through launch_op on the context's stream, one op
+// per call, each followed by a checked synchronisation: a kernel can be put next to its specification (tests/cpu_interp.cpp
+// interp_step) on inputs the caller wrote into the arena.
+static const Op *debug_op(dmx_ctx *c, int batch, int i, Plan **plan)
+{
+    if (!c || batch < 1 || batch > c->maxBatch)
+        return nullptr;
+    (void)hipSetDevice(c->m->device);
+    Plan *p = get_plan(c, batch);
+    if (i < 0 || i >= (int)p->ops.size())
+        return nullptr;
+    *plan = p;
+    return &p->ops[(size_t)i];
+}
+static bool debug_launches(const dmx_ctx *c, const Op &op)
+{
+    return op.kind != OP_TAP && !(op.kind == OP_ISTFT && op.istft.fused && c->fuseIstft);
+}
+static int debug_copy_out(const std::string &all, char *buf, int cap)
+{
+    if (!buf || (int)all.size() + 1 > cap)
+        return -1;
+    std::memcpy(buf, all.c_str(), all.size() + 1);
+    return (int)all.size();
+}
+
+extern "C" int dmx_debug_plan_info(dmx_ctx *c, int batch, int *n_ops, int64_t *arena_floats, int64_t *plan_floats, int64_t *const_floats)
+{
+    if (!c || batch < 1 || batch > c->maxBatch)
+        return fail(DMX_ERR_ARG, "dmx_debug_plan_info: bad arguments");
+    HIPCHK(hipSetDevice(c->m->device));
+    Plan *p = get_plan(c, batch);
+    if (n_ops)
+        *n_ops = (int)p->ops.size();
+    if (arena_floats)
+        *arena_floats = c->arenaFloats;
+    if (plan_floats)
+        *plan_floats = p->arenaFloats;
+    if (const_floats)
+        *const_floats = (int64_t)p->constants.size();
+    return DMX_OK;
+}
+
+extern "C" int dmx_debug_op_info(dmx_ctx *c, int batch, int i, char *buf, int cap)
+{
+    Plan *p = nullptr;
+    const Op *opp = debug_op(c, batch, i, &p);
+    if (!opp)
+        return -1;
+    const Op &op = *opp;
+    const std::string all = describe_op(op) + " launches=" + std::to_string(debug_launches(c, op) ? 1 : 0);
+    return debug_copy_out(all, buf, cap);
+}
+
+extern "C" int dmx_debug_arena_fill(dmx_ctx *c, int batch, unsigned pattern)
+{
+    if (!c || batch < 1 || batch > c->maxBatch)
+        return fail(DMX_ERR_ARG, "dmx_debug_arena_fill: bad arguments");
+    HIPCHK(hipSetDevice(c->m->device));
+    Plan *p = get_plan(c, batch);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->dA, (int)pattern, (size_t)c->arenaFloats, c->stream));
+    HIPCHK(hipMemcpyAsync(c->dA, p->constants.data(), p->constants.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return dmx_ctx_sync_checked(c);
+}
+
+extern "C" int dmx_debug_arena_io(dmx_ctx *c, int64_t off, int64_t n, float *host, int write)
+{
+    if (!c || !host || off < 0 || n < 0 || off + n > c->arenaFloats)
+        return fail(DMX_ERR_ARG, "dmx_debug_arena_io: range outside the arena");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (write)
+        HIPCHK(hipMemcpy(c->dA + off, host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    else
+        HIPCHK(hipMemcpy(host, c->dA + off, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmx_debug_run_op(dmx_ctx *c, int batch, int i)
+{
+    Plan *p = nullptr;
+    const Op *op = debug_op(c, batch, i, &p);
+    if (!op)
+        return fail(DMX_ERR_ARG, "dmx_debug_run_op: no such op");
+    DMXCHK(launch_op(c, *op, c->stream, p->zeroOff));
+    return dmx_ctx_sync_checked(c);
+}
+
+// the tile cfgs op i can be asked to run on: the chain choose_cfg -> half_cfg -> ... of its shape, and cfg 19 / 20 where their
+// shape conditions hold (fp32 contexts: plan.cpp finish); returns the count, -1 if op i is no OP_IGEMM of the plan
+extern "C" int dmx_debug_op_cfgs(dmx_ctx *c, int batch, int i, int *cfgs, int cap)
+{
+    Plan *p = nullptr;
+    const Op *op = debug_op(c, batch, i, &p);
+    if (!op || op->kind != OP_IGEMM || !cfgs)
+        return -1;
+    const IGemm &g = op->g;
+    const bool paired = g.epi == EPI_GLU || g.epi == EPI_GN_GLU_SCALE_RES;
+    int n = 0;
+    for (int cfg = choose_cfg((i64)g.P1 * g.P0, g.N, paired); cfg >= 0 && n < cap; cfg = half_cfg(cfg, g.rowstat >= 0))
+        cfgs[n++] = cfg;
+    if (c->gemm == DMX_GEMM_F32 && lin256_shape(g) && n < cap)
+        cfgs[n++] = 19;
+    if (c->gemm == DMX_GEMM_F32 && shortk_shape(g) && kTileCfgs[g.cfg].BN == 96 && n < cap)
+        cfgs[n++] = 20;
+    return n;
+}
+
+// Runs a COPY of OP_IGEMM i on tile cfg `cfg`: NB from the tile, the kernel select_gemm gives for the context's GEMM mode, the
+// model's facts and lin_mode (gemm_select.h). The copy passes the per-op checks of validate_plan; DMX_DEBUG_NO_KERNEL (nothing
+// launched) where they fail, where the tile is not one of the op's (dmx_debug_op_cfgs), where an op with row statistics would
+// change the layout of its partials (another column block width, unless one block covers the row in both), or where a K / V plane
+// projection would lose its exact-split kernel. `choice` receives the copy's
+// "cfg= family= arith= wnf= label= BM= BN= NB=".
+extern "C" int dmx_debug_run_op_as(dmx_ctx *c, int batch, int i, int cfg, int lin_mode, char *choice, int cap)
+{
+    Plan *p = nullptr;
+    const Op *src = debug_op(c, batch, i, &p);
+    if (!src || src->kind != OP_IGEMM)
+        return fail(DMX_ERR_ARG, "dmx_debug_run_op_as: op %d is no OP_IGEMM of the plan", i);
+    int cfgs[16];
+    const int nc = dmx_debug_op_cfgs(c, batch, i, cfgs, 16);
+    if (cfg != src->g.cfg && std::find(cfgs, cfgs + nc, cfg) == cfgs + nc)
+        return fail(DMX_DEBUG_NO_KERNEL, "op %s: tile cfg %d is not one of its shape's", src->name.c_str(), cfg);
+    Op op = *src;
+    IGemm &g = op.g;
+    // row statistics are [M][NB][2] partials per column block: a tile of another block width keeps the layout (and the op's write
+    // range) only where both cover the row with ONE block
+    const int nbNew = (g.N + kTileCfgs[cfg].BN - 1) / kTileCfgs[cfg].BN;
+    if (g.rowstat >= 0 && kTileCfgs[cfg].BN != kTileCfgs[g.cfg].BN && !(nbNew == 1 && g.NB == 1))
+        return fail(DMX_DEBUG_NO_KERNEL, "op %s: row statistics in column blocks of %d, tile cfg %d has %d", op.name.c_str(), kTileCfgs[g.cfg].BN, cfg,
+                    kTileCfgs[cfg].BN);
+    g.cfg = cfg;
+    g.NB = (g.N + kTileCfgs[cfg].BN - 1) / kTileCfgs[cfg].BN;
+    g.choice = select_gemm(g, c->gemm, model_facts(c->m), lin_mode);
+    std::string why;
+    if (g.choice.family == GF_NONE || !validate_gemm(op, why))
+        return fail(DMX_DEBUG_NO_KERNEL, "%s", why.c_str());
+    if (choice && debug_copy_out(describe_choice(g), choice, cap) < 0)
+        return fail(DMX_ERR_ARG, "dmx_debug_run_op_as: choice buffer too small");
+    DMXCHK(launch_op(c, op, c->stream, p->zeroOff));
+    return dmx_ctx_sync_checked(c);
 }

@@ -120,6 +120,23 @@ int refine_cfg(int cfg, i64 M, int N, bool stat)
     return best;
 }
 
+// The shapes of the two tiles finish() reaches from another tile by the ROW COUNT of a launch: everything but that count (the
+// debug entry points of api.cpp run an op on them at small sizes).
+// cfg 19 (igemm_lin256.hip, same conditions as its lin256_ok): plain linear layers; N a multiple of 512 only: with three column
+// tiles (N = 384: the channel up / down samplers) half as many, twice as large workgroups quantise worse on the 64 slots of an XCD
+// than they gain (measured 126 -> 115, 121 -> 111 TFLOP/s)
+bool lin256_shape(const IGemm &g)
+{
+    return g.pro == PRO_NONE && (g.epi == EPI_LINEAR || g.epi == EPI_SCALE_RES) && g.S1 == 1 && g.pad0 == 0 && g.seg0 == g.K && g.K == g.Kp &&
+           g.K % 16 == 0 && g.N % 4 == 0 && (i64)(g.P0 - 1) * g.stride0 * g.Cin + g.seg0 <= (i64)g.L0 * g.Cin && g.P1 == g.L1 && g.stride1 == 1 &&
+           g.pad1 == 0 && (g.epi != EPI_SCALE_RES || (g.res >= 0 && g.scale_w >= 0)) && g.N % 512 == 0;
+}
+// cfg 20: the short-K ops of the 128x96 family, no row statistics
+bool shortk_shape(const IGemm &g)
+{
+    return g.rowstat < 0 && g.pro == PRO_NONE && (g.epi == EPI_LINEAR || g.epi == EPI_GLU || g.epi == EPI_TRCONV) && g.K <= 160;
+}
+
 bool direct_available(int N, int S1, int seg0, int pro, int epi)
 {
     // deep-level DConv k3 in column chunks of 192 (dgemm.hip launch_dgemm)
@@ -232,17 +249,11 @@ struct Builder
             const bool splitMode = opts.gemm != GEMM_F32;
             // (the operand-split path has no 256x128 form: its linears stay on the tiles igemm_split.hip instantiates)
             const bool on = (!e || atoi(e) != 0) && !splitMode;
-            const bool lin = g.pro == PRO_NONE && (g.epi == EPI_LINEAR || g.epi == EPI_SCALE_RES) && g.S1 == 1 && g.pad0 == 0 &&
-                             g.seg0 == g.K && g.K == g.Kp && g.K % 16 == 0 && g.N % 4 == 0 &&
-                             (i64)(g.P0 - 1) * g.stride0 * g.Cin + g.seg0 <= (i64)g.L0 * g.Cin && g.P1 == g.L1 && g.stride1 == 1 && g.pad1 == 0 &&
-                             (g.epi != EPI_SCALE_RES || (g.res >= 0 && g.scale_w >= 0));
-            // N a multiple of 512 only: with three column tiles (N = 384: the channel up / down samplers) half as many, twice as
-            // large workgroups quantise worse on the 64 slots of an XCD than they gain (measured 126 -> 115, 121 -> 111 TFLOP/s)
-            // ... and at least three rounds of its workgroups on the 64 slots of an XCD (the tile map deals row tiles to XCDs): at
+            // the shape (lin256_shape) and at least three rounds of its workgroups on the 64 slots of an XCD (the tile map deals row tiles to XCDs): at
             // 1.75 rounds (time-branch linears with N = 512 at 42 segments) the 128x128 tile is 10 % faster
             const i64 M = (i64)g.B * g.P1 * g.P0;
             const i64 perXcd = (((M + 255) / 256 + 7) / 8) * ((g.N + 127) / 128);
-            if (on && lin && g.cfg == 0 && g.N % 512 == 0 && perXcd >= 192)
+            if (on && lin256_shape(g) && g.cfg == 0 && perXcd >= 192)
                 g.cfg = 19;
             // short-K ops of the 128x96 family (K <= 160: the level-1 1x1 rewrites, K = 96, and the time branch's last k3
             // rewrite, K = 144) run on the 256x96 tile with 16-deep K-tiles (cfg 20, plain loop): no half-empty last K-tile
@@ -251,8 +262,7 @@ struct Builder
             // decomposition and k order: identical bits. DMX_SHORTK=0 switches it off (A/B).
             const char *sk = getenv("DMX_SHORTK");
             // (the operand-split path keeps the tiles it instantiates)
-            if ((!sk || atoi(sk) != 0) && !splitMode && g.cfg == 2 && g.rowstat < 0 && g.pro == PRO_NONE &&
-                (g.epi == EPI_LINEAR || g.epi == EPI_GLU || g.epi == EPI_TRCONV) && g.K <= 160 && M >= 65536)
+            if ((!sk || atoi(sk) != 0) && !splitMode && g.cfg == 2 && shortk_shape(g) && M >= 65536)
                 g.cfg = 20;
         }
         // the DConv k3 op is a copy of k2 with another epilogue: both are in the direct table

@@ -401,6 +401,9 @@ int half_cfg(int cfg, bool stat);
 // tile for an op at the ACTUAL number of rows M (all segments in flight): the largest tile of the chain
 // cfg -> half_cfg(cfg) -> ... that keeps the 256 CUs evenly busy
 int refine_cfg(int cfg, i64 M, int N, bool stat);
+// the shape conditions (everything but the row count) under which plan.cpp finish() moves an op to cfg 19 / cfg 20
+bool lin256_shape(const IGemm &g);
+bool shortk_shape(const IGemm &g);
 // shapes served by the direct kernels (must match the table in dgemm.hip)
 bool direct_available(int N, int S1, int seg0, int pro, int epi);
 // M1 = rows per batch element: the choice never depends on the batch size, so results are

@@ -32,6 +32,7 @@ extern "C"
 #define DMX_ERR_NO_DEVICE 3   /* no usable HIP device (there is no CPU fallback)      */
 #define DMX_ERR_HIP 4         /* HIP runtime error                                    */
 #define DMX_ERR_ARG 5         /* invalid argument                                     */
+#define DMX_DEBUG_NO_KERNEL 6 /* dmx_debug_run_op_as: no such kernel, nothing launched */
 
 #define DMX_SEGMENT_SAMPLES 343980 /* 7.8 s @ 44.1 kHz, src/model.hpp:652, :20        */
 #define DMX_MAX_SHIFT 22050        /* 0.5 s, src/model.hpp:654                         */
@@ -458,6 +459,26 @@ extern "C"
      * `report` with lines "name\tkernel\tms_per_launch\talgorithmic_flops\talgorithmic_bytes".
      * Returns the number of ops or -1. Leaves the activations undefined.                   */
     int dmx_debug_profile(dmx_ctx *c, int batch, int reps, char *report, int report_cap);
+    /* ---- one op at a time (op-level parity tests). All act on the context's own plan for `batch` (1 .. max batch) and launch
+     * on the context's stream; every launch is followed by a checked synchronisation and returns its error.
+     * dmx_debug_plan_info: number of ops, floats of the context's arena, of the plan's part of it, and of its leading constants.
+     * dmx_debug_op_info: one line of key=value words for op i: name kind stream reads= writes= scratch= (arena ranges lo:hi, ...
+     *   as the plan's dependency analysis sees them; scratch: what the kernel may write beyond its results) launches= (0: a
+     *   marker, or an inverse STFT that runs inside the following overlap-add) and, for a GEMM, K N M pro epi act res stat hterms
+     *   y ldy Kp w_w bias_w kvCol0 cfg family arith wnf label BM BN NB (rowstat= kv= kvPlane=). Returns the length or -1.
+     * dmx_debug_arena_fill: every float of the arena = the 32-bit pattern, then the plan's constants restored.
+     * dmx_debug_arena_io: copies n floats at arena offset off from (write != 0) or to the host.
+     * dmx_debug_run_op: launches op i alone.
+     * dmx_debug_op_cfgs / dmx_debug_run_op_as: the tile configurations GEMM i may be asked to run on, and a run of a copy of it
+     *   on one of them with the kernel the selection gives under lin_mode (DMX_SPLIT_LIN); DMX_DEBUG_NO_KERNEL, nothing
+     *   launched, where that kernel does not exist; `choice` receives "cfg= family= arith= wnf= label= BM= BN= NB=".        */
+    int dmx_debug_plan_info(dmx_ctx *c, int batch, int *n_ops, int64_t *arena_floats, int64_t *plan_floats, int64_t *const_floats);
+    int dmx_debug_op_info(dmx_ctx *c, int batch, int i, char *buf, int cap);
+    int dmx_debug_arena_fill(dmx_ctx *c, int batch, unsigned pattern);
+    int dmx_debug_arena_io(dmx_ctx *c, int64_t off, int64_t n, float *host, int write);
+    int dmx_debug_run_op(dmx_ctx *c, int batch, int i);
+    int dmx_debug_op_cfgs(dmx_ctx *c, int batch, int i, int *cfgs, int cap);
+    int dmx_debug_run_op_as(dmx_ctx *c, int batch, int i, int cfg, int lin_mode, char *choice, int cap);
     /* the operand splits of DMX_GEMM_BF16X3, exposed for their unit tests. Weights (pure host function): w[i] -> bf16 bit
      * patterns w1[i], w2[i]; returns the number of elements with w1 + w2 != w. Activations (runs the kernels' own device
      * function on `device`): x[i] -> planes[0..n), [n..2n), [2n..3n) = a1, a2, a3; host pointers. */

@@ -5,18 +5,132 @@
 // the oracle, and serve as the executable specification of every op the HIP kernels
 // implement. It is NOT part of the product: nothing under demucs_cpp_amd/ or cli/ links
 // it, and the product fails loudly without a GPU.
+//
+// Every op is ONE template over its arithmetic T:
+//   T = float : the fp32 arithmetic the interpreter always had (interp_run*, interp_step mode 0), bit for bit;
+//   T = P     : the same op on the same fp32 inputs evaluated in double (interp_step mode 1). A P carries the value v and a
+//               magnitude m >= |v|: the sum of the absolute values of the terms added to form it (a GEMM output: sum |a_k w_k| +
+//               |bias| (+ |res|)), carried through products and quotients to first order (|a| m_b + |b| m_a - |a b|) and through
+//               the non-linear functions by their local Lipschitz constants. An fp32 evaluation that makes c roundings on the longest path to an element is within
+//               c 2^-24 m of v: the bound tests/test_gpu_op_parity.py holds each HIP kernel to.
 #include "../demucs_cpp_amd/csrc/model_pack.cpp"
 #include "../demucs_cpp_amd/csrc/plan.cpp"
 #include "../demucs_cpp_amd/csrc/gemm_select.cpp"
+#include "../demucs_cpp_amd/csrc/plan_describe.h"
 
 #include <complex>
+#include <type_traits>
 
 using namespace dmx;
 
 namespace
 {
+struct P
+{
+    double v, m;
+    P() : v(0), m(0) {}
+    P(double x) : v(x), m(std::fabs(x)) {}
+    P(double x, double mm) : v(x), m(mm) {}
+};
+inline P operator+(P a, P b) { return P(a.v + b.v, a.m + b.m); }
+inline P operator-(P a, P b) { return P(a.v - b.v, a.m + b.m); }
+inline P operator-(P a) { return P(-a.v, a.m); }
+// first order: (|a| + ea)(|b| + eb) without the ea eb term, which is second order in the roundings and, carried through a chain
+// of normalisations or a recurrence, would grow until the magnitude bounds nothing. Exact for operands that are plain numbers
+inline P operator*(P a, P b) { return P(a.v * b.v, std::fabs(a.v) * b.m + std::fabs(b.v) * a.m - std::fabs(a.v * b.v)); }
+inline P operator/(P a, P b)
+{
+    const double q = a.v / b.v, ab = std::fabs(b.v);
+    return P(q, a.m / ab + std::fabs(q) * (b.m - ab) / ab);
+}
+inline P &operator+=(P &a, P b) { return a = a + b; }
+inline P &operator*=(P &a, P b) { return a = a * b; }
+inline P &operator/=(P &a, P b) { return a = a / b; }
+inline bool operator<(P a, P b) { return a.v < b.v; }
+
 inline float gelu(float v) { return 0.5f * v * (1.0f + std::erf(v / std::sqrt(2.0f))); }
 inline float sigmoidf(float v) { return 1.0f / (1.0f + std::exp(-v)); }
+inline float exp_(float v) { return std::exp(v); }
+inline float tanh_(float v) { return std::tanh(v); }
+inline double sqrt_(double v) { return std::sqrt(v); }
+inline float fma_(float a, float b, float c) { return std::fmaf(a, b, c); }
+inline float max_(float a, float b) { return std::max(a, b); }
+inline double max_(double a, double b) { return std::max(a, b); }
+// |gelu'| <= 1.13, |sigmoid'| <= 1 / 4, |tanh'| <= 1, exp' = exp, sqrt' = 1 / (2 sqrt)
+inline P gelu(P x)
+{
+    const double f = 0.5 * x.v * (1.0 + std::erf(x.v / std::sqrt(2.0)));
+    return P(f, std::fabs(f) + 1.13 * x.m);
+}
+inline P sigmoidf(P x)
+{
+    const double f = 1.0 / (1.0 + std::exp(-x.v));
+    return P(f, f + 0.25 * x.m);
+}
+inline P exp_(P x)
+{
+    const double f = std::exp(x.v);
+    return P(f, f * (1.0 + x.m));
+}
+// (tanh is the LSTM's only: the device evaluates it as 2 sigmoid(2 v) - 1 (v3.hip lstm_tanh), whose error is a few u of ONE whatever
+// |v| - the "< 2e-7 absolute" its header states. The magnitude therefore carries 1, not |tanh v|)
+inline P tanh_(P x)
+{
+    const double f = std::tanh(x.v);
+    return P(f, 1.0 + x.m);
+}
+inline P sqrt_(P x)
+{
+    const double f = std::sqrt(x.v);
+    return P(f, f + (f > 0 ? 0.5 * x.m / f : 0.0));
+}
+inline P fma_(P a, P b, P c) { return a * b + c; }
+inline P max_(P a, P b) { return a.v < b.v ? b : a; }
+
+// W: the type of the sums the fp32 arithmetic keeps in double; rf: a double result rounded to the arithmetic; wd: widened;
+// val: the plain number
+template <class T>
+struct Tr;
+template <>
+struct Tr<float>
+{
+    typedef double W;
+    static float rf(double x) { return (float)x; }
+    static double wd(float x) { return (double)x; }
+    static double val(float x) { return (double)x; }
+    static double mag(float x) { return std::fabs((double)x); }
+    static float mk(double v, double) { return (float)v; }
+    static float rebase(float x) { return x; }
+};
+template <>
+struct Tr<P>
+{
+    typedef P W;
+    static P rf(P x) { return x; }
+    static P wd(P x) { return x; }
+    static double val(P x) { return x.v; }
+    static double mag(P x) { return x.m; }
+    static P mk(double v, double m) { return P(v, m); }
+    static P rebase(P x) { return P(x.v); } // a state taken as a number of its own: its magnitude starts again at |v|
+};
+
+// GroupNorm statistics INSIDE an op (OP_DCONV_ROW) of the values with sums s, q in the wide type: mean and 1 / sqrt(var + eps).
+// fp32 arithmetic: the one-pass formula in double, rounded (what the interpreter always did). Precise: the same two numbers, taken
+// as numbers of their own (magnitude |v|), exactly as the unfused chain K1 / r1 / K2 / r2 / K3 takes them: there the statistics
+// reach the next op as fp32 arena values. The device forms them in double, so their own rounding is one fp32 rounding; what the
+// errors of the values do to them is an AVERAGE over >= 100 independent roundings, while carrying magnitudes through
+// q - n mean^2 (or its worst-case perturbation) multiplies the bound by the conditioning at every normalisation until it bounds
+// nothing (measured: s / |r| of 1e5 and more). The RMS rule of tests/test_gpu_op_parity.py holds the op to what fp32 really gives.
+inline void inner_stats(double s, double q, double cnt, float eps, float &mean, float &rstd)
+{
+    const double m = s / cnt, var = std::max((q - cnt * m * m) / (cnt - 1.0), 0.0);
+    mean = (float)m, rstd = (float)(1.0 / std::sqrt(var + (double)eps));
+}
+inline void inner_stats(P s, P q, double cnt, float eps, P &mean, P &rstd)
+{
+    const double m = s.v / cnt, var = std::max((q.v - cnt * m * m) / (cnt - 1.0), 0.0);
+    mean = P(m), rstd = P(1.0 / std::sqrt(var + (double)eps));
+}
 
 void fft(std::vector<std::complex<double>> &a, int sign)
 {
@@ -48,6 +162,30 @@ void fft(std::vector<std::complex<double>> &a, int sign)
     }
 }
 
+// round-to-nearest-even bf16 of a finite float, and the three-term split of igemm_common.h split3_pk
+inline unsigned short bf16_rn(float x)
+{
+    unsigned u;
+    std::memcpy(&u, &x, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (unsigned short)(u >> 16);
+}
+inline float bf16_f(unsigned short h)
+{
+    unsigned u = (unsigned)h << 16;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+inline void split3(float x, unsigned short h[3])
+{
+    h[0] = bf16_rn(x);
+    const float r = x - bf16_f(h[0]);
+    h[1] = bf16_rn(r);
+    const float s = r - bf16_f(h[1]);
+    h[2] = bf16_rn(s);
+}
+
 struct Interp
 {
     PackedModel pm;
@@ -56,25 +194,69 @@ struct Interp
     const float *W;
     std::vector<i64> notFp16; // interp_select_dump: blob offsets of the weights that are not fp16 numbers (filled on first use)
     bool scanned = false;
+    // ---- the step interface (interp_step): what the last step wrote, and in the precise arithmetic its unrounded results
+    std::vector<unsigned char> mask; // [arenaFloats] 1 = written by the last step (empty: whole-plan runs keep no record)
+    std::vector<double> R;           // [arenaFloats] precise result before its one rounding to fp32
+    std::vector<float> S;            // [arenaFloats] its magnitude
+    std::vector<double> kvR;         // K / V operand planes of the last step (EPI_KPL / EPI_VT): the value whose exact split the
+    std::vector<float> kvS;          // planes hold, and its magnitude, indexed like the elements of plane 0
+    bool hterms = false;             // the step's GEMM runs on fp16 terms under a per-row scale: the mode's documented allowance
+                                     // (2^-39 of the row maximum per dropped remainder, one per k) joins the magnitude
+    bool chained = false;            // the step's OP_OLA takes the frames of the OP_ISTFT before it unrounded (the fused GPU kernel)
 
+    void st(i64 off, float v)
+    {
+        A[(size_t)off] = v;
+        if (!mask.empty())
+            mask[(size_t)off] = 1;
+    }
+    void st(i64 off, P v)
+    {
+        A[(size_t)off] = (float)v.v;
+        mask[(size_t)off] = 1, R[(size_t)off] = v.v, S[(size_t)off] = (float)std::min(v.m, 3e38);
+    }
+    // the bf16 element e of the plane area at float offset kv
+    void st_bf16(i64 kv, i64 e, unsigned short h)
+    {
+        reinterpret_cast<unsigned short *>(&A[(size_t)kv])[e] = h;
+        if (!mask.empty())
+            mask[(size_t)(kv + e / 2)] = 1;
+    }
+    float ld_bf16(i64 kv, i64 e) const { return bf16_f(reinterpret_cast<const unsigned short *>(&A[(size_t)kv])[e]); }
+
+    template <class T>
     void run_igemm(const IGemm &g)
     {
         const i64 M = (i64)g.B * g.P1 * g.P0;
         const int BN = kTileCfgs[g.cfg].BN;
         const bool paired = g.epi == EPI_GLU || g.epi == EPI_GN_GLU_SCALE_RES;
+        const bool planes = g.epi == EPI_KPL || g.epi == EPI_VT;
+        const bool precise = !std::is_same<T, float>::value;
         const i64 rowLen = (i64)g.L0 * g.Cin;
+        const i64 kvPlane = (i64)g.B * g.kvT * g.kvH * g.kvHs;
+        std::vector<double> wabs; // sum_k |w[n][k]| (fp16-term allowance)
+        if (precise && hterms)
+        {
+            wabs.assign((size_t)g.N, 0.0);
+            for (int n = 0; n < g.N; ++n)
+                for (int k = 0; k < g.K; ++k)
+                    wabs[(size_t)n] += std::fabs((double)W[g.w_w + (i64)n * g.Kp + k]);
+        }
+        if (precise && planes)
+            kvR.assign((size_t)kvPlane, 0.0), kvS.assign((size_t)kvPlane, 0.f);
 #pragma omp parallel for schedule(static)
         for (i64 m = 0; m < M; ++m)
         {
             int p0 = (int)(m % g.P0), p1 = (int)((m / g.P0) % g.P1), bb = (int)(m / ((i64)g.P0 * g.P1));
             int grp = bb * g.G0 + (g.G0 > 1 ? p0 : 0);
-            std::vector<float> arow((size_t)g.K);
+            std::vector<T> arow((size_t)g.K);
+            double rowmax = 0;
             for (int k = 0; k < g.K; ++k)
             {
                 int s1 = k / g.seg0, off = k % g.seg0;
                 int in1 = p1 * g.stride1 + s1 * g.dil1 - g.pad1;
                 i64 e = (i64)(p0 * g.stride0 - g.pad0) * g.Cin + off;
-                float a = 0.f;
+                T a = 0.f;
                 if (in1 >= 0 && in1 < g.L1 && e >= 0 && e < rowLen)
                 {
                     a = A[(size_t)(g.x + bb * g.xBatchStride + (i64)in1 * rowLen + e)];
@@ -90,58 +272,61 @@ struct Interp
                     }
                 }
                 arow[(size_t)k] = a;
+                rowmax = std::max(rowmax, std::fabs(Tr<T>::val(a)));
             }
-            std::vector<float> v((size_t)g.N);
+            std::vector<T> v((size_t)g.N);
             for (int n = 0; n < g.N; ++n)
             {
                 const float *wr = W + g.w_w + (i64)n * g.Kp;
-                float acc = 0.f;
+                T acc = 0.f;
                 for (int k = 0; k < g.K; ++k)
                     acc += arow[(size_t)k] * wr[k];
                 v[(size_t)n] = acc + W[g.bias_w + n];
+                if (precise && hterms)
+                    v[(size_t)n] = Tr<T>::mk(Tr<T>::val(v[(size_t)n]), Tr<T>::mag(v[(size_t)n]) + std::ldexp(rowmax * wabs[(size_t)n], -15));
             }
             const i64 yrow = g.y + bb * g.yBatchStride + ((i64)p1 * g.P0 + p0) * g.ldy;
             if (g.epi == EPI_LINEAR)
             {
                 for (int n = 0; n < g.N; ++n)
                 {
-                    float t = v[(size_t)n];
+                    T t = v[(size_t)n];
                     if (g.act)
                         t = gelu(t);
                     if (g.res >= 0)
                         t += A[(size_t)(g.res + (yrow - g.y) + n)];
                     v[(size_t)n] = t;
-                    A[(size_t)(yrow + n)] = t;
+                    st(yrow + n, t);
                 }
             }
             else if (g.epi == EPI_SCALE_RES)
             {
                 for (int n = 0; n < g.N; ++n)
                 {
-                    float t = A[(size_t)(g.res + (yrow - g.y) + n)] + v[(size_t)n] * W[g.scale_w + n];
+                    T t = A[(size_t)(g.res + (yrow - g.y) + n)] + v[(size_t)n] * W[g.scale_w + n];
                     v[(size_t)n] = t;
-                    A[(size_t)(yrow + n)] = t;
+                    st(yrow + n, t);
                 }
             }
             else if (paired)
             {
                 int C = g.N / 2;
-                const float *st = g.epi == EPI_GN_GLU_SCALE_RES ? &A[(size_t)(g.epiStats + (i64)grp * 4)] : nullptr;
+                const float *st4 = g.epi == EPI_GN_GLU_SCALE_RES ? &A[(size_t)(g.epiStats + (i64)grp * 4)] : nullptr;
                 for (int c = 0; c < C; ++c)
                 {
                     int na = (c / 16) * 32 + (c % 16), nb = na + 16;
-                    float a = v[(size_t)na], bq = v[(size_t)nb];
-                    if (st)
+                    T a = v[(size_t)na], bq = v[(size_t)nb];
+                    if (st4)
                     {
-                        a = (a - st[0]) * st[1] * W[g.epiW_w + na] + W[g.epiB_w + na];
-                        bq = (bq - st[0]) * st[1] * W[g.epiW_w + nb] + W[g.epiB_w + nb];
+                        a = (a - st4[0]) * st4[1] * W[g.epiW_w + na] + W[g.epiB_w + na];
+                        bq = (bq - st4[0]) * st4[1] * W[g.epiW_w + nb] + W[g.epiB_w + nb];
                     }
-                    float t = a * sigmoidf(bq);
+                    T t = a * sigmoidf(bq);
                     if (g.epi == EPI_GN_GLU_SCALE_RES)
                         t = A[(size_t)(g.res + (yrow - g.y) + c)] + W[g.scale_w + c] * t;
                     else if (g.table_w >= 0)
                         t += g.tableScale * W[g.table_w + (i64)p0 * C + c];
-                    A[(size_t)(yrow + c)] = t;
+                    st(yrow + c, t);
                 }
             }
             else if (g.epi == EPI_TRCONV)
@@ -152,19 +337,50 @@ struct Interp
                     int j = g.trS * p0 + r - g.trOff;
                     if (j < 0 || j >= g.Lout)
                         continue;
-                    float t = v[(size_t)n];
+                    T t = v[(size_t)n];
                     if (g.act)
                         t = gelu(t);
                     i64 o = bb * g.yBatchStride + ((i64)p1 * g.Lout + j) * g.ldy + co;
                     if (g.res >= 0)
                         t += A[(size_t)(g.res + o)];
-                    A[(size_t)(g.y + o)] = t;
+                    st(g.y + o, t);
+                }
+            }
+            else if (planes)
+            {
+                // rows are tokens m = b kvT + t. EPI_KPL: columns below kvCol0 fp32 [row][n]; from kvCol0 on plane element
+                // m (kvH kvHs) + n - kvCol0. EPI_VT (kvCol0 = 0): the V^T tile image of attention_split.hip, element
+                // (((b kvH + head) nt + t / 64) kvHs + dim) 64 + 8 slot + 4 half + t % 4 with, for tt = t % 64,
+                // slot = 4 (tt / 32) + (tt / 4) % 4, half = (tt / 16) % 2 (igemm_common.h igemm_epilogue)
+                const int b = (int)(m / g.kvT), t = (int)(m % g.kvT), nt = g.kvT / 64;
+                for (int n = 0; n < g.N; ++n)
+                {
+                    if (g.epi == EPI_KPL && n < g.kvCol0)
+                    {
+                        st(yrow + n, v[(size_t)n]);
+                        continue;
+                    }
+                    i64 e;
+                    if (g.epi == EPI_KPL)
+                        e = m * (i64)(g.kvH * g.kvHs) + (n - g.kvCol0);
+                    else
+                    {
+                        const int head = n / g.kvHs, dim = n % g.kvHs, tt = t & 63;
+                        const int slot = 4 * (tt >> 5) + ((tt >> 2) & 3), half = (tt >> 4) & 1;
+                        e = ((((i64)b * g.kvH + head) * nt + (t >> 6)) * g.kvHs + dim) * 64 + slot * 8 + half * 4 + (tt & 3);
+                    }
+                    unsigned short h[3];
+                    split3((float)Tr<T>::val(v[(size_t)n]), h);
+                    for (int q = 0; q < 3; ++q)
+                        st_bf16(g.kv, q * kvPlane + e, h[q]);
+                    if (precise)
+                        kvR[(size_t)e] = Tr<T>::val(v[(size_t)n]), kvS[(size_t)e] = (float)Tr<T>::mag(v[(size_t)n]);
                 }
             }
             if (g.rowstat >= 0)
                 for (int nb = 0; nb < g.NB; ++nb)
                 {
-                    float s = 0.f, ss = 0.f;
+                    T s = 0.f, ss = 0.f;
                     for (int n = nb * BN; n < std::min(g.N, (nb + 1) * BN); ++n)
                     {
                         if (g.epi == EPI_STATS_FACT) // factorised statistics: roles of the columns, plan.h
@@ -180,19 +396,21 @@ struct Interp
                         s += v[(size_t)n];
                         ss += v[(size_t)n] * v[(size_t)n];
                     }
-                    A[(size_t)(g.rowstat + (m * g.NB + nb) * 2)] = s;
-                    A[(size_t)(g.rowstat + (m * g.NB + nb) * 2 + 1)] = ss;
+                    st(g.rowstat + (m * g.NB + nb) * 2, s);
+                    st(g.rowstat + (m * g.NB + nb) * 2 + 1, ss);
                 }
         }
     }
 
+    template <class T>
     void run_reduce(const StatsReduce &s)
     {
+        typedef typename Tr<T>::W Wd;
         int G = s.G0 > 1 ? s.G0 : 1;
         for (int b = 0; b < s.B; ++b)
             for (int gi = 0; gi < G; ++gi)
             {
-                double sum = 0, sq = 0;
+                Wd sum = 0, sq = 0;
                 for (int r = gi; r < s.R; r += G)
                     for (int nb = 0; nb < s.NB; ++nb)
                     {
@@ -200,29 +418,31 @@ struct Interp
                         sum += p[0];
                         sq += p[1];
                     }
-                double mean = sum / s.count;
-                double var = (sq - s.count * mean * mean) / (s.count - 1.0);
-                if (var < 0)
+                Wd mean = sum / s.count;
+                Wd var = (sq - s.count * mean * mean) / (s.count - 1.0);
+                if (var < Wd(0))
                     var = 0;
-                float *o = &A[(size_t)(s.out + ((i64)b * G + gi) * 4)];
-                o[0] = (float)mean;
-                o[2] = (float)std::sqrt(var);
-                o[1] = s.mode == MODE_RSTD ? (float)(1.0 / std::sqrt(var + (double)s.eps))
-                                           : (float)(1.0 / (std::sqrt(var) + (double)s.eps));
-                o[3] = 0.f;
+                const i64 o = s.out + ((i64)b * G + gi) * 4;
+                st(o, Tr<T>::rf(mean));
+                st(o + 2, Tr<T>::rf(sqrt_(var)));
+                st(o + 1, s.mode == MODE_RSTD ? Tr<T>::rf(1.0 / sqrt_(var + (double)s.eps)) : Tr<T>::rf(1.0 / (sqrt_(var) + (double)s.eps)));
+                st(o + 3, T(0.f));
             }
     }
 
+    template <class T>
     void run_stft(const Stft &s)
     {
+        typedef typename Tr<T>::W Wd;
         const float *win = &A[(size_t)s.window];
         for (int b = 0; b < s.B; ++b)
             for (int t = 0; t < s.T; ++t)
             {
-                double sum = 0, sq = 0, sumT = 0, sqT = 0;
+                Wd sum = 0, sq = 0, sumT = 0, sqT = 0;
                 for (int ch = 0; ch < 2; ++ch)
                 {
                     std::vector<std::complex<double>> buf(4096);
+                    double l1 = 0; // sum of the absolute values of the terms of every bin
                     for (int i = 0; i < 4096; ++i)
                     {
                         // model-level symmetric padding (Q2), model_inference.cpp:22-46; reference
@@ -232,153 +452,193 @@ struct Interp
                             j = -1 - j;
                         if (j >= s.seg)
                             j = 2 * (i64)s.seg - 1 - j;
-                        float x = A[(size_t)(s.mix + ((i64)b * s.seg + j) * 2 + ch)];
-                        buf[i] = (double)(x * win[i]);
+                        T x = A[(size_t)(s.mix + ((i64)b * s.seg + j) * 2 + ch)];
+                        buf[i] = Tr<T>::val(x * win[i]);
+                        l1 += std::fabs(buf[i].real());
                     }
                     fft(buf, -1);
                     for (int f = 0; f < 2048; ++f)
                     {
-                        float re = (float)(buf[f].real() / 64.0), im = (float)(buf[f].imag() / 64.0);
-                        float *o = &A[(size_t)(s.x + (((i64)b * s.T + t) * 2048 + f) * 4 + 2 * ch)];
-                        o[0] = re, o[1] = im;
+                        T re = Tr<T>::mk(buf[f].real() / 64.0, l1 / 64.0), im = Tr<T>::mk(buf[f].imag() / 64.0, l1 / 64.0);
+                        const i64 o = s.x + (((i64)b * s.T + t) * 2048 + f) * 4 + 2 * ch;
+                        st(o, re), st(o + 1, im);
                         sum += re + im;
-                        sq += (double)re * re + (double)im * im;
+                        sq += Tr<T>::wd(re) * re + Tr<T>::wd(im) * im;
                     }
                     for (i64 j = (i64)t * 1024; j < std::min((i64)s.seg, (i64)(t + 1) * 1024); ++j)
                     {
-                        float x = A[(size_t)(s.mix + ((i64)b * s.seg + j) * 2 + ch)];
+                        T x = A[(size_t)(s.mix + ((i64)b * s.seg + j) * 2 + ch)];
                         sumT += x;
-                        sqT += (double)x * x;
+                        sqT += Tr<T>::wd(x) * x;
                     }
                 }
-                A[(size_t)(s.rowstat + ((i64)b * s.T + t) * 2)] = (float)sum;
-                A[(size_t)(s.rowstat + ((i64)b * s.T + t) * 2 + 1)] = (float)sq;
-                A[(size_t)(s.rowstatT + ((i64)b * s.T + t) * 2)] = (float)sumT;
-                A[(size_t)(s.rowstatT + ((i64)b * s.T + t) * 2 + 1)] = (float)sqT;
+                st(s.rowstat + ((i64)b * s.T + t) * 2, Tr<T>::rf(sum));
+                st(s.rowstat + ((i64)b * s.T + t) * 2 + 1, Tr<T>::rf(sq));
+                st(s.rowstatT + ((i64)b * s.T + t) * 2, Tr<T>::rf(sumT));
+                st(s.rowstatT + ((i64)b * s.T + t) * 2 + 1, Tr<T>::rf(sqT));
             }
     }
 
+    template <class T>
     void run_ln(const LayerNorm &l)
     {
+        typedef typename Tr<T>::W Wd;
 #pragma omp parallel for schedule(static)
         for (int r = 0; r < l.rows; ++r)
         {
             const float *x = &A[(size_t)(l.x + (i64)r * l.D)];
-            double s = 0;
+            Wd s = 0;
             for (int c = 0; c < l.D; ++c)
                 s += x[c];
-            float mean = (float)(s / l.D);
-            double ss = 0;
+            T mean = Tr<T>::rf(s / l.D);
+            Wd ss = 0;
             for (int c = 0; c < l.D; ++c)
-                ss += ((double)x[c] - mean) * ((double)x[c] - mean);
-            float rstd = (float)(1.0 / std::sqrt(ss / (l.D - 1) + (double)l.eps));
-            std::vector<float> tmp((size_t)l.D);
+                ss += (Tr<T>::wd(x[c]) - mean) * (Tr<T>::wd(x[c]) - mean);
+            T rstd = Tr<T>::rf(1.0 / sqrt_(ss / (l.D - 1) + (double)l.eps));
+            std::vector<T> tmp((size_t)l.D);
             for (int c = 0; c < l.D; ++c)
             {
-                float v = (x[c] - mean) * rstd * W[l.w_w + c] + W[l.b_w + c];
+                T v = (x[c] - mean) * rstd * W[l.w_w + c] + W[l.b_w + c];
                 if (l.pe >= 0)
                     v += A[(size_t)(l.pe + (i64)(r % l.rowsPerBatch) * l.D + c)];
                 tmp[(size_t)c] = v;
             }
             for (int c = 0; c < l.D; ++c)
-                A[(size_t)(l.y + (i64)r * l.D + c)] = tmp[(size_t)c];
+                st(l.y + (i64)r * l.D + c, tmp[(size_t)c]);
         }
     }
 
+    template <class T>
     void run_gn(const GnApply &g)
     {
         for (int b = 0; b < g.B; ++b)
             for (i64 i = 0; i < (i64)g.rows * g.C; ++i)
             {
                 i64 o = (i64)b * g.rows * g.C + i;
-                float v = A[(size_t)(g.x + o)];
+                T v = A[(size_t)(g.x + o)];
                 if (g.stats >= 0)
                 {
-                    const float *st = &A[(size_t)(g.stats + (i64)b * 4)];
+                    const float *st4 = &A[(size_t)(g.stats + (i64)b * 4)];
                     int c = (int)(i % g.C);
-                    v = (v - st[0]) * st[1] * W[g.w_w + c] + W[g.b_w + c];
+                    v = (v - st4[0]) * st4[1] * W[g.w_w + c] + W[g.b_w + c];
                 }
                 if (g.res >= 0)
                     v += A[(size_t)(g.res + o)];
-                A[(size_t)(g.y + o)] = v;
+                st(g.y + o, v);
             }
     }
 
+    // K / V as the attention kernel sees them: fp32 rows, or the sum of the three bf16 planes (= the projected fp32 value: the
+    // split is exact; EPI_KPL / EPI_VT layouts as in run_igemm)
+    float attn_k(const Attention &a, int b, int s, int c) const
+    {
+        if (a.kpl < 0)
+            return A[(size_t)(a.k + b * a.kBatch + (i64)s * a.ldk + c)];
+        const i64 plane = (i64)a.B * a.Tk * a.H * a.hs, e = ((i64)b * a.Tk + s) * (a.H * a.hs) + c;
+        return ld_bf16(a.kpl, e) + ld_bf16(a.kpl, plane + e) + ld_bf16(a.kpl, 2 * plane + e);
+    }
+    float attn_v(const Attention &a, int b, int s, int c) const
+    {
+        if (a.vt < 0)
+            return A[(size_t)(a.v + b * a.vBatch + (i64)s * a.ldv + c)];
+        const i64 plane = (i64)a.B * a.Tk * a.H * a.hs;
+        const int head = c / a.hs, dim = c % a.hs, tt = s & 63, nt = a.Tk / 64;
+        const int slot = 4 * (tt >> 5) + ((tt >> 2) & 3), half = (tt >> 4) & 1;
+        const i64 e = ((((i64)b * a.H + head) * nt + (s >> 6)) * a.hs + dim) * 64 + slot * 8 + half * 4 + (tt & 3);
+        return ld_bf16(a.vt, e) + ld_bf16(a.vt, plane + e) + ld_bf16(a.vt, 2 * plane + e);
+    }
+
+    template <class T>
     void run_attention(const Attention &a)
     {
 #pragma omp parallel for collapse(2) schedule(static)
         for (int b = 0; b < a.B; ++b)
             for (int h = 0; h < a.H; ++h)
             {
-                std::vector<float> sc((size_t)a.Tk);
+                std::vector<T> sc((size_t)a.Tk), o((size_t)a.hs);
+                std::vector<float> kk((size_t)a.Tk * a.hs), vv((size_t)a.Tk * a.hs);
+                for (int s = 0; s < a.Tk; ++s)
+                    for (int j = 0; j < a.hs; ++j)
+                        kk[(size_t)s * a.hs + j] = attn_k(a, b, s, h * a.hs + j), vv[(size_t)s * a.hs + j] = attn_v(a, b, s, h * a.hs + j);
                 for (int t = 0; t < a.Tq; ++t)
                 {
                     const float *q = &A[(size_t)(a.q + b * a.qBatch + (i64)t * a.ldq + h * a.hs)];
-                    float mx = -INFINITY;
+                    T mx = -INFINITY;
                     for (int s = 0; s < a.Tk; ++s)
                     {
-                        const float *k = &A[(size_t)(a.k + b * a.kBatch + (i64)s * a.ldk + h * a.hs)];
-                        float d = 0;
+                        const float *k = &kk[(size_t)s * a.hs];
+                        T d = 0;
                         for (int j = 0; j < a.hs; ++j)
-                            d += q[j] * k[j];
+                            d += T(q[j]) * k[j];
                         sc[(size_t)s] = d * a.scale;
-                        mx = std::max(mx, sc[(size_t)s]);
+                        mx = max_(mx, sc[(size_t)s]);
                     }
-                    float sum = 0;
+                    T sum = 0;
                     for (int s = 0; s < a.Tk; ++s)
                     {
-                        sc[(size_t)s] = std::exp(sc[(size_t)s] - mx);
+                        sc[(size_t)s] = exp_(sc[(size_t)s] - mx);
                         sum += sc[(size_t)s];
                     }
-                    float *o = &A[(size_t)(a.o + b * a.oBatch + (i64)t * a.ldo + h * a.hs)];
                     for (int j = 0; j < a.hs; ++j)
-                        o[j] = 0;
+                        o[(size_t)j] = 0;
                     for (int s = 0; s < a.Tk; ++s)
                     {
-                        const float *v = &A[(size_t)(a.v + b * a.vBatch + (i64)s * a.ldv + h * a.hs)];
-                        float p = sc[(size_t)s] / sum;
+                        const float *v = &vv[(size_t)s * a.hs];
+                        T p = sc[(size_t)s] / sum;
                         for (int j = 0; j < a.hs; ++j)
-                            o[j] += p * v[j];
+                            o[(size_t)j] += p * v[j];
                     }
+                    for (int j = 0; j < a.hs; ++j)
+                        st(a.o + b * a.oBatch + (i64)t * a.ldo + h * a.hs + j, o[(size_t)j]);
                 }
             }
     }
 
+    template <class T>
     void run_istft(const Istft &s)
     {
         const float *win = &A[(size_t)s.window];
         const int CS = 4 * s.S;
         for (int b = 0; b < s.B; ++b)
         {
-            const float *st = &A[(size_t)(s.stats + (i64)b * 4)];
-            float mean = st[0], stdv = st[2];
+            const float *st4 = &A[(size_t)(s.stats + (i64)b * 4)];
+            float mean = st4[0], stdv = st4[2];
             for (int src = 0; src < s.S; ++src)
                 for (int ch = 0; ch < 2; ++ch)
                     for (int t = 0; t < s.T; ++t)
                     {
                         std::vector<std::complex<double>> buf(4096, {0, 0});
+                        double l1 = 0;
                         for (int f = 0; f < 2048; ++f)
                         {
                             const float *x = &A[(size_t)(s.x + (((i64)b * s.T + t) * 2048 + f) * CS + src * 4 + 2 * ch)];
-                            float re = stdv * x[0] + mean, im = stdv * x[1] + mean; // model_inference.cpp:380-393
-                            buf[f] = std::complex<double>((double)(re * 64.0f), (double)(im * 64.0f));
+                            T re = T(stdv) * x[0] + mean, im = T(stdv) * x[1] + mean; // model_inference.cpp:380-393
+                            buf[f] = std::complex<double>(Tr<T>::val(re * 64.0f), Tr<T>::val(im * 64.0f));
+                            l1 += 2.0 * 64.0 * (Tr<T>::mag(re) + Tr<T>::mag(im));
                         }
                         buf[0] = {buf[0].real(), 0};
                         for (int f = 1; f < 2048; ++f)
                             buf[4096 - f] = std::conj(buf[f]);
                         fft(buf, +1);
-                        float *o = &A[(size_t)(s.frames + ((((i64)b * s.S + src) * 2 + ch) * s.T + t) * 4096)];
+                        const i64 o = s.frames + ((((i64)b * s.S + src) * 2 + ch) * s.T + t) * 4096;
                         for (int i = 0; i < 4096; ++i)
-                            o[i] = (float)buf[i].real() * win[i];
+                            st(o + i, Tr<T>::rf(Tr<T>::mk(buf[i].real(), l1)) * win[i]);
                     }
         }
     }
 
+    template <class T>
+    T frame_at(i64 off) const
+    {
+        return A[(size_t)off];
+    }
+
+    template <class T>
     void run_ola(const Ola &o)
     {
         for (int b = 0; b < o.B; ++b)
         {
-            const float *st = &A[(size_t)(o.statsT + (i64)b * 4)];
+            const float *st4 = &A[(size_t)(o.statsT + (i64)b * 4)];
             for (int src = 0; src < o.S; ++src)
                 for (int ch = 0; ch < 2; ++ch)
                     for (int i = 0; i < o.seg; ++i)
@@ -386,17 +646,17 @@ struct Interp
                         // sample n of the (T+4)-frame overlap-add buffer; reference frame f starts at f*1024;
                         // kept waveform drops 2048 (dsp.cpp:113-116) then `pad` (model_inference.cpp:454-455)
                         i64 n = 2048 + o.pad + i;
-                        float acc = 0.f;
+                        T acc = 0.f;
                         for (i64 f = n / 1024 - 3; f <= n / 1024; ++f)
                         {
                             i64 t = f - 2; // frames 0,1 and T+2,T+3 are zero (model_inference.cpp:439-444)
                             if (t < 0 || t >= o.T)
                                 continue;
-                            float yv = A[(size_t)(o.frames + ((((i64)b * o.S + src) * 2 + ch) * o.T + t) * 4096 + (n - f * 1024))];
+                            T yv = frame_at<T>(o.frames + ((((i64)b * o.S + src) * 2 + ch) * o.T + t) * 4096 + (n - f * 1024));
                             acc += yv * 1.0f / 4096.0f / (A[(size_t)(o.wss + n)] + 1e-8f);
                         }
-                        float tb = st[2] * A[(size_t)(o.xt + ((i64)b * o.seg + i) * (2 * o.S) + src * 2 + ch)] + st[0];
-                        A[(size_t)(o.out + (((i64)b * o.S + src) * 2 + ch) * o.seg + i)] = acc + tb;
+                        T tb = T(st4[2]) * A[(size_t)(o.xt + ((i64)b * o.seg + i) * (2 * o.S) + src * 2 + ch)] + st4[0];
+                        st(o.out + (((i64)b * o.S + src) * 2 + ch) * o.seg + i, acc + tb);
                     }
         }
     }
@@ -445,33 +705,36 @@ struct Interp
     }
 
     // ---- Demucs v3 ops (plan.h)
+    template <class T>
     void run_group_stats(const GroupStats &g)
     {
+        typedef typename Tr<T>::W Wd;
         const int gs = g.C / g.G;
         for (int b = 0; b < g.B; ++b)
             for (int gi = 0; gi < g.G; ++gi)
             {
                 const double cnt = (double)g.rows * gs;
-                double sum = 0;
+                Wd sum = 0;
                 for (int r = 0; r < g.rows; ++r)
                     for (int c = gi * gs; c < (gi + 1) * gs; ++c)
                         sum += A[(size_t)(g.x + ((i64)b * g.rows + r) * g.C + c)];
-                const float mean = (float)(sum / cnt);
-                double ss = 0;
+                const T mean = Tr<T>::rf(sum / cnt);
+                Wd ss = 0;
                 for (int r = 0; r < g.rows; ++r)
                     for (int c = gi * gs; c < (gi + 1) * gs; ++c)
                     {
-                        const double d = (double)A[(size_t)(g.x + ((i64)b * g.rows + r) * g.C + c)] - (double)mean;
+                        const Wd d = Tr<T>::wd(A[(size_t)(g.x + ((i64)b * g.rows + r) * g.C + c)]) - Tr<T>::wd(mean);
                         ss += d * d;
                     }
-                const double var = ss / (cnt - 1.0);
-                float *o = &A[(size_t)(g.out + ((i64)b * g.G + gi) * 4)];
-                o[0] = mean;
-                o[1] = (float)(1.0 / std::sqrt(var + (double)g.eps));
-                o[2] = (float)std::sqrt(var);
-                o[3] = 0.f;
+                const Wd var = ss / (cnt - 1.0);
+                const i64 o = g.out + ((i64)b * g.G + gi) * 4;
+                st(o, mean);
+                st(o + 1, Tr<T>::rf(1.0 / sqrt_(var + (double)g.eps)));
+                st(o + 2, Tr<T>::rf(sqrt_(var)));
+                st(o + 3, T(0.f));
             }
     }
+    template <class T>
     void run_gn_act(const GnAct &g)
     {
         const int gs = g.C / g.G, Co = g.mode == 2 ? g.C / 2 : g.C;
@@ -479,14 +742,14 @@ struct Interp
             for (int r = 0; r < g.rowsOut; ++r)
             {
                 const float *x = &A[(size_t)(g.x + ((i64)b * g.rowsIn + r + g.rowOff) * g.C)];
-                auto gn = [&](int c) {
-                    const float *st = &A[(size_t)(g.stats + ((i64)b * g.G + c / gs) * 4)];
-                    return (x[c] - st[0]) * st[1] * W[g.w_w + c] + W[g.b_w + c];
+                auto gn = [&](int c) -> T {
+                    const float *st4 = &A[(size_t)(g.stats + ((i64)b * g.G + c / gs) * 4)];
+                    return (T(x[c]) - st4[0]) * st4[1] * W[g.w_w + c] + W[g.b_w + c];
                 };
-                std::vector<float> tmp((size_t)Co);
+                std::vector<T> tmp((size_t)Co);
                 for (int c = 0; c < Co; ++c)
                 {
-                    float v = gn(c);
+                    T v = gn(c);
                     if (g.mode == 1)
                         v = gelu(v);
                     else if (g.mode == 2)
@@ -498,180 +761,203 @@ struct Interp
                     tmp[(size_t)c] = v;
                 }
                 for (int c = 0; c < Co; ++c)
-                    A[(size_t)(g.y + ((i64)b * g.rowsOut + r) * Co + c)] = tmp[(size_t)c];
+                    st(g.y + ((i64)b * g.rowsOut + r) * Co + c, tmp[(size_t)c]);
             }
     }
+    template <class T>
     void run_lstm(const Lstm &l)
     {
-        const int H = l.H, T = l.T;
+        const int H = l.H, Tn = l.T;
 #pragma omp parallel for collapse(2) schedule(static)
         for (int b = 0; b < l.B; ++b)
             for (int dir = 0; dir < 2; ++dir)
             {
-                std::vector<float> h((size_t)H, 0.f), c((size_t)H, 0.f), hn((size_t)H);
+                std::vector<T> h((size_t)H, T(0.f)), c((size_t)H, T(0.f)), hn((size_t)H);
                 const float *U = W + l.whh_w + (i64)dir * 4 * H * H;
-                for (int step = 0; step < T; ++step)
+                for (int step = 0; step < Tn; ++step)
                 {
-                    const int t = dir == 0 ? step : T - 1 - step;
-                    const float *xp = &A[(size_t)(l.xproj + ((i64)b * T + t) * 8 * H + (i64)dir * 4 * H)];
+                    const int t = dir == 0 ? step : Tn - 1 - step;
+                    const float *xp = &A[(size_t)(l.xproj + ((i64)b * Tn + t) * 8 * H + (i64)dir * 4 * H)];
                     for (int j = 0; j < H; ++j)
                     {
-                        float gt[4];
+                        T gt[4];
                         for (int q = 0; q < 4; ++q)
                         {
                             const float *u = U + (i64)(4 * j + q) * H;
-                            float acc = xp[4 * j + q]; // the MFMA accumulates onto the input projection, k ascending
+                            T acc = xp[4 * j + q]; // the MFMA accumulates onto the input projection, k ascending
                             for (int k = 0; k < H; ++k)
-                                acc = std::fmaf(u[k], h[(size_t)k], acc);
+                                acc = fma_(T(u[k]), h[(size_t)k], acc);
                             gt[q] = acc;
                         }
-                        const float ig = sigmoidf(gt[0]), fg = sigmoidf(gt[1]), gg = std::tanh(gt[2]), og = sigmoidf(gt[3]);
-                        const float cn = fg * c[(size_t)j] + ig * gg;
-                        c[(size_t)j] = cn;
-                        hn[(size_t)j] = og * std::tanh(cn);
+                        const T ig = sigmoidf(gt[0]), fg = sigmoidf(gt[1]), gg = tanh_(gt[2]), og = sigmoidf(gt[3]);
+                        const T cn = fg * c[(size_t)j] + ig * gg;
+                        c[(size_t)j] = Tr<T>::rebase(cn);
+                        hn[(size_t)j] = og * tanh_(cn);
                     }
-                    h = hn;
+                    // The magnitude of an output is that of ITS step from the state before it, the state taken as numbers of their
+                    // own (rebase): the errors of earlier steps enter the bound as one allowance per step (op_reference.bound_c:
+                    // c grows with T), not as magnitudes multiplied through the recurrence, which grow without bound
                     for (int j = 0; j < H; ++j)
-                        A[(size_t)(l.out + ((i64)b * T + t) * 2 * H + (i64)dir * H + j)] = h[(size_t)j];
+                        st(l.out + ((i64)b * Tn + t) * 2 * H + (i64)dir * H + j, hn[(size_t)j]);
+                    for (int j = 0; j < H; ++j)
+                        h[(size_t)j] = Tr<T>::rebase(hn[(size_t)j]);
                 }
             }
     }
+    template <class T>
     void run_local_attn(const LocalAttn &a)
     {
-        const int heads = 4, nd = 4, hd = a.H / heads, T = a.T;
+        const int heads = 4, nd = 4, hd = a.H / heads, Tn = a.T;
         const float sq = std::sqrt((float)hd);
 #pragma omp parallel for collapse(2) schedule(static)
         for (int b = 0; b < a.B; ++b)
             for (int h = 0; h < heads; ++h)
             {
-                std::vector<float> w((size_t)T);
-                for (int s = 0; s < T; ++s)
+                std::vector<T> w((size_t)Tn);
+                for (int s = 0; s < Tn; ++s)
                 {
-                    const float *row = &A[(size_t)(a.qkvd + ((i64)b * T + s) * a.ld)];
+                    const float *row = &A[(size_t)(a.qkvd + ((i64)b * Tn + s) * a.ld)];
                     const float *q = row + h * hd;
-                    float dq[4];
+                    T dq[4];
                     for (int n = 0; n < nd; ++n)
-                        dq[n] = 0.5f * sigmoidf(row[3 * a.H + h * nd + n]);
-                    float mx = -INFINITY;
-                    for (int t = 0; t < T; ++t)
+                        dq[n] = 0.5f * sigmoidf(T(row[3 * a.H + h * nd + n]));
+                    T mx = -INFINITY;
+                    for (int t = 0; t < Tn; ++t)
                     {
-                        const float *k = &A[(size_t)(a.qkvd + ((i64)b * T + t) * a.ld + a.H + h * hd)];
-                        float dot = 0.f;
+                        const float *k = &A[(size_t)(a.qkvd + ((i64)b * Tn + t) * a.ld + a.H + h * hd)];
+                        T dot = 0.f;
                         for (int c = 0; c < hd; ++c)
-                            dot += q[c] * k[c];
-                        float v = dot / sq, decay = 0.f;
+                            dot += T(q[c]) * k[c];
+                        T v = dot / sq, decay = 0.f;
                         const float delta = (float)std::abs(t - s);
                         for (int n = 0; n < nd; ++n)
                             decay += (-(float)(n + 1) * delta / 2.0f) * dq[n];
-                        w[(size_t)t] = t != s ? v + decay : -100.0f;
-                        mx = std::max(mx, w[(size_t)t]);
+                        w[(size_t)t] = t != s ? v + decay : T(-100.0f);
+                        mx = max_(mx, w[(size_t)t]);
                     }
-                    float sum = 0.f;
-                    for (int t = 0; t < T; ++t)
+                    T sum = 0.f;
+                    for (int t = 0; t < Tn; ++t)
                     {
-                        w[(size_t)t] = std::exp(w[(size_t)t] - mx);
+                        w[(size_t)t] = exp_(w[(size_t)t] - mx);
                         sum += w[(size_t)t];
                     }
-                    for (int t = 0; t < T; ++t)
+                    for (int t = 0; t < Tn; ++t)
                         w[(size_t)t] /= sum;
-                    float *o = &A[(size_t)(a.out + ((i64)b * T + s) * a.H + h * hd)];
                     for (int c = 0; c < hd; ++c)
                     {
-                        float acc = 0.f;
-                        for (int t = 0; t < T; ++t)
-                            acc += w[(size_t)t] * A[(size_t)(a.qkvd + ((i64)b * T + t) * a.ld + 2 * a.H + h * hd + c)];
-                        o[c] = acc;
+                        T acc = 0.f;
+                        for (int t = 0; t < Tn; ++t)
+                            acc += w[(size_t)t] * A[(size_t)(a.qkvd + ((i64)b * Tn + t) * a.ld + 2 * a.H + h * hd + c)];
+                        st(a.out + ((i64)b * Tn + s) * a.H + h * hd + c, acc);
                     }
                 }
             }
     }
 
     // OP_DCONV_ROW: the unfused definition (plan.h), statistics in double from the formed tensors (no factor)
+    template <class T>
     void run_dconv_row(const DconvRow &r)
     {
-        const int T = r.T, F = r.F, C = r.C, H = r.hid;
+        typedef typename Tr<T>::W Wd;
+        const int Tn = r.T, F = r.F, C = r.C, H = r.hid;
 #pragma omp parallel for schedule(static)
         for (i64 row = 0; row < (i64)r.B * F; ++row)
         {
             const int b = (int)(row / F), f = (int)(row % F);
-            auto X = [&](int t, int c) -> float & { return A[(size_t)(r.x + (((i64)b * T + t) * F + f) * C + c)]; };
-            std::vector<float> h((size_t)T * H), y((size_t)T * 2 * C);
+            std::vector<T> xs((size_t)Tn * C); // the row, updated in place by both layers
+            for (int t = 0; t < Tn; ++t)
+                for (int c = 0; c < C; ++c)
+                    xs[(size_t)t * C + c] = A[(size_t)(r.x + (((i64)b * Tn + t) * F + f) * C + c)];
+            auto X = [&](int t, int c) -> T & { return xs[(size_t)t * C + c]; };
+            std::vector<T> h((size_t)Tn * H), y((size_t)Tn * 2 * C);
             for (int j = 0; j < 2; ++j)
             {
                 const int d = j + 1;
                 const float *k1 = W + r.k1_w[j], *k1b = W + r.k1_b[j], *k2 = W + r.k2_w[j], *k2b = W + r.k2_b[j];
-                double s = 0, q = 0;
-                for (int t = 0; t < T; ++t)
+                Wd s = 0, q = 0;
+                for (int t = 0; t < Tn; ++t)
                     for (int n = 0; n < H; ++n)
                     {
-                        float acc = 0.f;
+                        T acc = 0.f;
                         for (int tap = 0; tap < 3; ++tap)
                         {
                             const int ti = t + (tap - 1) * d;
-                            if (ti < 0 || ti >= T)
+                            if (ti < 0 || ti >= Tn)
                                 continue;
                             for (int c = 0; c < C; ++c)
                                 acc += X(ti, c) * k1[(i64)n * 3 * C + tap * C + c];
                         }
-                        const float v = acc + k1b[n];
+                        const T v = acc + k1b[n];
                         h[(size_t)t * H + n] = v;
-                        s += v, q += (double)v * v;
+                        s += v, q += Tr<T>::wd(v) * v;
                     }
-                double cnt = (double)H * T, mean = s / cnt, var = std::max((q - cnt * mean * mean) / (cnt - 1.0), 0.0);
-                const float m1 = (float)mean, r1 = (float)(1.0 / std::sqrt(var + (double)r.eps));
-                for (int t = 0; t < T; ++t)
+                T m1, r1, m2, r2;
+                inner_stats(s, q, (double)H * Tn, r.eps, m1, r1);
+                for (int t = 0; t < Tn; ++t)
                     for (int n = 0; n < H; ++n)
                         h[(size_t)t * H + n] = gelu((h[(size_t)t * H + n] - m1) * r1 * W[r.gn1_w[j] + n] + W[r.gn1_b[j] + n]);
                 s = q = 0;
-                for (int t = 0; t < T; ++t)
+                for (int t = 0; t < Tn; ++t)
                     for (int n = 0; n < 2 * C; ++n)
                     {
-                        float acc = 0.f;
+                        T acc = 0.f;
                         for (int k = 0; k < H; ++k)
                             acc += h[(size_t)t * H + k] * k2[(i64)n * 16 + k];
-                        const float v = acc + k2b[n];
+                        const T v = acc + k2b[n];
                         y[(size_t)t * 2 * C + n] = v;
-                        s += v, q += (double)v * v;
+                        s += v, q += Tr<T>::wd(v) * v;
                     }
-                cnt = 2.0 * C * T, mean = s / cnt, var = std::max((q - cnt * mean * mean) / (cnt - 1.0), 0.0);
-                const float m2 = (float)mean, r2 = (float)(1.0 / std::sqrt(var + (double)r.eps));
-                for (int t = 0; t < T; ++t)
+                inner_stats(s, q, 2.0 * C * Tn, r.eps, m2, r2);
+                for (int t = 0; t < Tn; ++t)
                     for (int c = 0; c < C; ++c)
                     {
                         const int na = (c / 16) * 32 + c % 16, ng = na + 16; // packed GLU pair (model_pack.cpp paired_row)
-                        const float a = (y[(size_t)t * 2 * C + na] - m2) * r2 * W[r.gn2_w[j] + na] + W[r.gn2_b[j] + na];
-                        const float g = (y[(size_t)t * 2 * C + ng] - m2) * r2 * W[r.gn2_w[j] + ng] + W[r.gn2_b[j] + ng];
+                        const T a = (y[(size_t)t * 2 * C + na] - m2) * r2 * W[r.gn2_w[j] + na] + W[r.gn2_b[j] + na];
+                        const T g = (y[(size_t)t * 2 * C + ng] - m2) * r2 * W[r.gn2_w[j] + ng] + W[r.gn2_b[j] + ng];
                         X(t, c) += W[r.scale_w[j] + c] * (a * sigmoidf(g));
                     }
             }
+            for (int t = 0; t < Tn; ++t)
+                for (int c = 0; c < C; ++c)
+                    st(r.x + (((i64)b * Tn + t) * F + f) * C + c, X(t, c));
+        }
+    }
+
+    template <class T>
+    void run_op(const Op &op)
+    {
+        switch (op.kind)
+        {
+        case OP_IGEMM: run_igemm<T>(op.g); break;
+        case OP_STATS_REDUCE: run_reduce<T>(op.sr); break;
+        case OP_STFT: run_stft<T>(op.stft); break;
+        case OP_LAYERNORM: run_ln<T>(op.ln); break;
+        case OP_GN_APPLY: run_gn<T>(op.gn); break;
+        case OP_ATTENTION: run_attention<T>(op.at); break;
+        case OP_ISTFT: run_istft<T>(op.istft); break;
+        case OP_OLA: run_ola<T>(op.ola); break;
+        case OP_GROUP_STATS: run_group_stats<T>(op.gs); break;
+        case OP_GN_ACT: run_gn_act<T>(op.ga); break;
+        case OP_LSTM: run_lstm<T>(op.lstm); break;
+        case OP_LOCAL_ATTN: run_local_attn<T>(op.la); break;
+        case OP_DCONV_ROW: run_dconv_row<T>(op.dr); break;
+        default: break;
         }
     }
 
     void run(int order = 0)
     {
         for (int idx : schedule(order))
-        {
-            const Op &op = pl.ops[idx];
-            switch (op.kind)
-            {
-            case OP_IGEMM: run_igemm(op.g); break;
-            case OP_STATS_REDUCE: run_reduce(op.sr); break;
-            case OP_STFT: run_stft(op.stft); break;
-            case OP_LAYERNORM: run_ln(op.ln); break;
-            case OP_GN_APPLY: run_gn(op.gn); break;
-            case OP_ATTENTION: run_attention(op.at); break;
-            case OP_ISTFT: run_istft(op.istft); break;
-            case OP_OLA: run_ola(op.ola); break;
-            case OP_GROUP_STATS: run_group_stats(op.gs); break;
-            case OP_GN_ACT: run_gn_act(op.ga); break;
-            case OP_LSTM: run_lstm(op.lstm); break;
-            case OP_LOCAL_ATTN: run_local_attn(op.la); break;
-            case OP_DCONV_ROW: run_dconv_row(op.dr); break;
-            default: break;
-            }
-        }
+            run_op<float>(pl.ops[idx]);
     }
 };
+
+// the fused GPU kernel never rounds the frames: a chained precise OP_OLA takes them as the OP_ISTFT step left them
+template <>
+P Interp::frame_at<P>(i64 off) const
+{
+    return chained ? P(R[(size_t)off], (double)S[(size_t)off]) : P((double)A[(size_t)off]);
+}
 } // namespace
 
 extern "C"
@@ -897,3 +1183,87 @@ extern "C" int interp_select_one(void *h, const char *name, int gemm, int linMod
         }
     return -2;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The step interface: one op at a time on the interpreter's arena, in fp32 (mode 0: what interp_run does, op by op) or in double
+// (mode 1; + 2: the op's GEMM runs on fp16 terms on the device, the magnitudes carry that mode's allowance; + 4: an OP_OLA takes
+// the frames of the OP_ISTFT stepped just before it unrounded, as the fused GPU kernel does). tests/test_gpu_op_parity.py puts
+// each HIP kernel next to it; tests/test_op_reference_cpu.py checks the harness itself.
+
+// The plan a context of GEMM mode `gemm` builds (gemm_select.h build_chosen_plan, as api.cpp get_plan calls it: every weight of
+// the synthetic test models is an fp16 number, derived ones are listed as inexact), with an arena.
+extern "C" void *interp_create_chosen(const char *model_path, int64_t seg, int B, int gemm, int kvPlanes)
+{
+    auto *it = new Interp();
+    std::string err;
+    if (!load_and_pack(model_path, it->pm, err))
+    {
+        fprintf(stderr, "%s\n", err.c_str());
+        delete it;
+        return nullptr;
+    }
+    for (size_t i = 0; i < it->pm.blob.size(); ++i)
+        if (!is_fp16_number(it->pm.blob[i]))
+            it->notFp16.push_back((i64)i);
+    it->scanned = true;
+    GemmModelFacts f;
+    f.bf16Planes = f.fp16Plane = true;
+    f.planeDelta = (i64)it->pm.blob.size() + 512;
+    f.inexactW = f.inexactH = &it->notFp16;
+    build_chosen_plan(it->pm, seg, B, gemm, kvPlanes != 0, f, 1, it->pl);
+    it->A.assign((size_t)it->pl.arenaFloats, 0.f);
+    std::copy(it->pl.constants.begin(), it->pl.constants.end(), it->A.begin());
+    it->W = it->pm.blob.data();
+    return it;
+}
+
+extern "C" int64_t interp_arena_floats(void *h) { return ((Interp *)h)->pl.arenaFloats; }
+extern "C" int64_t interp_const_floats(void *h) { return (int64_t)((Interp *)h)->pl.constants.size(); }
+extern "C" int64_t interp_mix_off(void *h) { return ((Interp *)h)->pl.mixOff; }
+extern "C" int64_t interp_out_off(void *h) { return ((Interp *)h)->pl.outOff; }
+extern "C" float *interp_arena(void *h) { return ((Interp *)h)->A.data(); }
+// the packed weights (W space; the w_w= / bias_w= words of interp_op_info are offsets into it)
+extern "C" const float *interp_weights(void *h) { return ((Interp *)h)->W; }
+extern "C" int64_t interp_weight_floats(void *h) { return (int64_t)((Interp *)h)->pm.blob.size(); }
+// valid after the first interp_step of the handle; precise / magnitude / planes after a step in double
+extern "C" unsigned char *interp_mask(void *h) { return ((Interp *)h)->mask.data(); }
+extern "C" double *interp_precise(void *h) { return ((Interp *)h)->R.data(); }
+extern "C" float *interp_magnitude(void *h) { return ((Interp *)h)->S.data(); }
+extern "C" int64_t interp_planes(void *h, double **r, float **s)
+{
+    Interp *it = (Interp *)h;
+    *r = it->kvR.data(), *s = it->kvS.data();
+    return (int64_t)it->kvR.size();
+}
+
+// op i in the words of dmx_debug_op_info (csrc/plan_describe.h): the two plans are compared as text
+extern "C" int interp_op_info(void *h, int i, char *buf, int cap)
+{
+    Interp *it = (Interp *)h;
+    if (i < 0 || i >= (int)it->pl.ops.size())
+        return -1;
+    const Op &op = it->pl.ops[(size_t)i];
+    const std::string all = describe_op(op);
+    return copy_out(all, buf, cap);
+}
+
+extern "C" int interp_step(void *h, int i, int mode)
+{
+    Interp *it = (Interp *)h;
+    if (i < 0 || i >= (int)it->pl.ops.size())
+        return -1;
+    const size_t n = (size_t)it->pl.arenaFloats;
+    it->mask.assign(n, 0);
+    it->kvR.clear(), it->kvS.clear();
+    it->hterms = (mode & 2) != 0, it->chained = (mode & 4) != 0;
+    if (mode & 1)
+    {
+        if (it->R.size() != n)
+            it->R.assign(n, 0.0), it->S.assign(n, 0.f);
+        it->run_op<P>(it->pl.ops[(size_t)i]);
+    }
+    else
+        it->run_op<float>(it->pl.ops[(size_t)i]);
+    return 0;
+}
+

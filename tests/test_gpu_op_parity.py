@@ -1,0 +1,323 @@
+"""Every op of a plan, alone, on known inputs: the HIP kernel the context would launch against an fp64 evaluation of the same op
+(tests/cpu_interp.cpp interp_step in double; tests/op_reference.py holds the bound and the check, tests/test_op_reference_cpu.py
+tests the harness itself without a GPU).
+
+Per launching op, in plan order: the device arena is filled with canary A (a quiet NaN), the reference chain's values are
+uploaded over the op's read ranges, the op is launched alone (dmx_debug_run_op: launch_op on the context's stream, then a checked
+synchronisation), and the arena comes back. Then
+  values       every element the reference wrote is within c u s of the fp64 value (op_reference.bound_c); K / V operand planes
+               by the fp64 sum of their three bf16 terms, which must be an fp32 number split in order;
+  containment  every other float of the arena - outside the write ranges, row padding and cropped positions inside them, the
+               constants, the inputs - is bit for bit what it was (the scratch ranges an op declares are exempt);
+  reads        a second launch with canary B (a large finite value) in the unread part writes the same bits: the op_access read
+               ranges the two-stream waits are derived from are the only reads;
+  rms          wherever the worst-case bound is loose (every op whose c exceeds op_reference.RMS_MIN_C: GEMMs, attention, LayerNorm,
+               STFT / inverse STFT, LSTM, LocalState, the row-resident DConv, ...) the RMS of (g - r) / (u s) is at most 4 x that
+               of the interpreter's fp32 arithmetic on the same inputs (op_reference.rms_rule_ok: no floor, no exception).
+The constants (window, twiddles, window sums, positional tables) are restored by both fills: a read of a constant the op does not
+declare is NOT detected by the second launch (constants are never written after context creation, so no wait depends on them).
+Inputs always come from the reference chain, so one wrong kernel cannot mask or poison the next. On a HIP error the binding
+raises and the test ends there: nothing more is launched.
+
+The variant sweep runs every GEMM of two cases on every tile of its shape's chain (dmx_debug_run_op_as), see
+test_every_tile_and_family_*.
+
+DMX_OP_PARITY_RECORD=<dir> writes the per-op figures (profiles/op_parity_*.txt are such records)."""
+import os
+
+import numpy as np
+import pytest
+
+import op_reference as R
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def L():
+    return R.lib()
+
+
+@pytest.fixture(scope="module")
+def dmxb():
+    from demucs_cpp_amd import binding
+
+    assert binding.device_count() >= 1, "no HIP device: the product has no CPU fallback"
+    return binding
+
+
+DEVICE_ERROR = []  # the first error the library reported from the device: after it no test of this module launches anything
+
+
+class Pair:
+    """a context and the interpreter handle of the same plan"""
+
+    def __init__(self, dmxb, L, tmp_models, case, mode, zero_segment=False):
+        assert not DEVICE_ERROR, f"an earlier launch failed on the device, nothing more is launched: {DEVICE_ERROR[0]}"
+        self.dmxb = dmxb
+        key, seg, B, _ = R.CASES[case]
+        self.B, self.mode, self.case = B, mode, case
+        self.model = dmxb.Model(tmp_models[key], 0)
+        self.ctx = dmxb.Context(self.model, seg, B, gemm=R.GEMM[mode])
+        self.n_ops, self.ctx_floats, self.floats, self.consts = self.ctx.plan_info(B)
+        self.gops = [self.ctx.op_info(B, i) for i in range(self.n_ops)]
+        # a split context of a v4 model asks for K / V operand planes and falls back to the fp32-K/V form where a projection cannot
+        # take its exact-split kernel (api.cpp get_plan): the reference is built the same way
+        self.ref = R.Ref(L, tmp_models[key], seg, B, mode, mode != "f32" and key != 3)
+        if self.ref.floats != self.floats and not any(o["kind"] == R.OP_ATTENTION and o.get("planes") for o in self.gops):
+            self.ref.close()
+            self.ref = R.Ref(L, tmp_models[key], seg, B, mode, False)
+        rng = np.random.default_rng(seg + B)
+        mix = (0.1 * rng.standard_normal((B, 2, seg))).astype(np.float32)
+        if zero_segment:
+            mix[B - 1] = 0.0
+        self.ref.set_mix(mix)
+        # the constants as the LIBRARY computed them (the interpreter's come from another compiler: window sums differ in the last bit)
+        self.ctx.arena_fill(B, R.CANARY_A)
+        self.consts_u32 = self.ctx.arena_read(0, self.consts).view(np.uint32).copy()
+        self.buf = np.empty(self.ctx_floats, np.float32)
+
+    def assert_same_plan(self):
+        ref = self.ref
+        assert ref.n_ops == self.n_ops and ref.floats == self.floats and ref.consts == self.consts
+        for a, b in zip(ref.ops, self.gops):
+            assert (a["name"], a["kind"], a["reads"], a["writes"], a["scratch"]) == (b["name"], b["kind"], b["reads"], b["writes"], b["scratch"])
+
+    def prepare(self, canary, reads, values):
+        self.ctx.arena_fill(self.B, canary)
+        for (lo, hi), v in zip(reads, values):
+            self.ctx.arena_write(lo, v)
+
+    def close(self):
+        self.ref.close()
+        self.ctx.close()
+        self.model.close()
+
+
+def float_rms(ref, i, j, snap, op):
+    """RMS ratio of the interpreter's fp32 arithmetic for ops i .. j on the current inputs; leaves the arena as it was"""
+    hull = [rg for k in range(i, j + 1) for rg in ref.ops[k]["writes"]]
+    saved = [ref.A[lo:hi].copy() for lo, hi in hull]
+    for k in range(i, j + 1):
+        ref.step(k, False)
+    q = [R.ratios(ref.A[snap["idx"]], snap["r"], snap["s"])]
+    pr = R.plane_range(op)
+    if pr:
+        total, _ = R.bf16_planes_sum(ref.A[pr[0]:pr[1]].view(np.uint16), op["kvPlane"])
+        q.append(R.ratios(total, *snap["planes"]))
+    for (lo, hi), v in zip(hull, saved):
+        ref.A[lo:hi] = v
+    return R.rms(np.concatenate(q))
+
+
+def written_bits(fetch, op, snap):
+    """the bits of everything the op wrote; fetch(lo, hi) -> the arena's uint32 words [lo, hi) (write ranges only are asked for)"""
+    pr, idx, out = R.plane_range(op), snap["idx"], []
+    for lo, hi in op["writes"]:
+        words = fetch(lo, hi)
+        out.append(words[idx[(idx >= lo) & (idx < hi)] - lo])
+        if pr and lo <= pr[0] and pr[1] <= hi:
+            out.append(words[pr[0] - lo:pr[1] - lo])
+    return np.concatenate(out)
+
+
+def check_launch(pair, i, j, op, reads, values, snap, rows, launched, variants):
+    ref, ctx, B, mode = pair.ref, pair.ctx, pair.B, pair.mode
+    # ---- the kernel on canary A
+    pair.prepare(R.CANARY_A, reads, values)
+    ctx.run_op(B, j)
+    got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
+    before = R.expected_arena(pair.ctx_floats, R.CANARY_A, pair.consts_u32, reads, values)
+    worst, q = R.check_op(op, mode, got, before, snap)
+    bits_a = written_bits(lambda lo, hi: got[lo:hi], op, snap)
+    launched.append((op.get("cfg", -1), op.get("family", -1), op.get("label")))
+    # ---- the same launch with canary B in everything it does not declare to read
+    pair.prepare(R.CANARY_B, reads, values)
+    ctx.run_op(B, j)
+    bits_b = written_bits(lambda lo, hi: ctx.arena_read(lo, hi - lo).view(np.uint32), op, snap)
+    if not np.array_equal(bits_b, bits_a):
+        k = int(np.flatnonzero(bits_b != bits_a)[0])
+        raise R.OpMismatch(f"{op['name']}: the result depends on arena contents outside its declared read ranges (first at written element {k})")
+    rms_g = R.rms(q)
+    rms_f = None
+    if R.rms_rule_applies(op, mode):
+        # the interpreter's fp32 arithmetic on the same inputs (restored: the precise step may have worked in place)
+        after = [ref.A[lo:hi].copy() for lo, hi in reads]
+        for (lo, hi), v in zip(reads, values):
+            ref.A[lo:hi] = v
+        rms_f = float_rms(ref, i, j, snap, op)
+        for (lo, hi), v in zip(reads, after):
+            ref.A[lo:hi] = v
+        # the precise results are the chain: put them back over what the fp32 step restored
+        ref.A[snap["idx"]] = snap["r"].astype(np.float32)
+        if not R.rms_rule_ok(rms_g, rms_f):
+            raise R.OpMismatch(f"{op['name']}: RMS of (g - r) / (u s) = {rms_g:.4f}, the fp32 interpreter's is {rms_f:.4f} (cap {R.RMS_CAP} x)")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        loose = float(np.nanmedian(snap["s"] / np.abs(snap["r"]))) if snap["idx"].size else 0.0  # how far s is above |r|: the bound's slack
+    rows.append((op["name"], op.get("label"), op.get("K", 0), R.bound_c(op, mode), worst, rms_g, rms_f, loose))
+    if variants is not None and op["kind"] == R.OP_IGEMM:
+        run_variants(pair, j, op, reads, values, snap, bits_a, variants, launched)
+
+
+def sweep(pair, variants=None):
+    try:
+        return sweep_ops(pair, variants)
+    except pair.dmxb.DmxError as e:
+        DEVICE_ERROR.append(str(e))
+        raise
+
+
+def sweep_ops(pair, variants):
+    """the whole plan, op by op. variants: run every GEMM on every tile / family of its shape as well (run_variants) - the other ops
+    then only advance the reference chain (test_every_op_against_fp64 checks them)"""
+    ref, ctx, B, mode = pair.ref, pair.ctx, pair.B, pair.mode
+    rows, launched, failures = [], [], []
+    i = 0
+    while i < ref.n_ops:
+        gop = pair.gops[i]
+        if gop["kind"] == R.OP_TAP:
+            i += 1
+            continue
+        fused = gop["kind"] == R.OP_ISTFT and not gop["launches"]
+        j = i + 1 if fused else i
+        op = pair.gops[j]
+        assert op["launches"]
+        reads = op["reads"]
+        values = [ref.A[lo:hi].copy() for lo, hi in reads]  # before the step: in-place ops overwrite them
+        hterms = op["kind"] == R.OP_IGEMM and op["arith"] == 2
+        # ---- the reference: fp32 interpreter (the yardstick of the RMS rule), then the precise step the chain continues from
+        if fused:
+            ref.step(i, True)
+            ref.step(j, True, chained=True)
+        else:
+            ref.step(i, True, hterms=hterms)
+        if variants is not None and op["kind"] != R.OP_IGEMM:
+            i = j + 1
+            continue
+        snap = R.snapshot(ref, op)
+        try:
+            check_launch(pair, i, j, op, reads, values, snap, rows, launched, variants)
+        except R.OpMismatch as e:  # (every op is reported, not the first only: the chain does not depend on the device's results)
+            failures.append(str(e))
+        i = j + 1
+    return rows, launched, failures
+
+
+def run_variants(pair, j, op, reads, values, snap, bits_plan, variants, launched):
+    """GEMM j on every tile cfg of its shape (dmx_debug_op_cfgs) under lin_mode 0 / 1 / 3: each distinct (cfg, family, wnf) meets the
+    op's bound; results of one arithmetic are bit-identical whatever the tile or family (plan.h kTileCfgs: siblings keep the column
+    decomposition; gemm_select.h: all families of one arithmetic give the same bits) - row-statistics partials included, among
+    tiles of one column block width. The direct kernels (cfg 8, chosen by shape alone, with a k order of their own: dgemm.hip) are
+    outside that claim: where the plan's kernel is one, the tile variants are compared with each other."""
+    ctx, B = pair.ctx, pair.B
+    DIRECT = 8
+    seen = {(op["cfg"], op["family"], op["wnf"])}
+    claim = lambda o: (o["arith"], o["BN"] if op["stat"] else 0)
+    bases = {} if op["cfg"] == DIRECT else {claim(op): (bits_plan, op)}
+    for cfg in ctx.op_cfgs(B, j):
+        for lin_mode in (0, 1, 3):
+            pair.prepare(R.CANARY_A, reads, values)
+            ch = ctx.run_op_as(B, j, cfg, lin_mode)
+            if ch is None:
+                variants["refused"].add((cfg, op["pro"], op["epi"]))
+                continue
+            key = (ch["cfg"], ch["family"], ch["wnf"])
+            launched.append((ch["cfg"], ch["family"], ch["label"]))
+            if key in seen:
+                continue
+            seen.add(key)
+            vop = dict(op, **ch)
+            got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
+            before = R.expected_arena(pair.ctx_floats, R.CANARY_A, pair.consts_u32, reads, values)
+            try:
+                R.check_op(vop, pair.mode, got, before, snap)
+            except R.OpMismatch as e:
+                raise R.OpMismatch(f"as cfg {ch['cfg']} family {ch['family']} wnf {ch['wnf']} ({ch['label']}): {e}")
+            bits = written_bits(lambda lo, hi: got[lo:hi], op, snap)
+            base_bits, base = bases.setdefault(claim(vop), (bits.copy(), vop))
+            if not np.array_equal(bits, base_bits):
+                raise R.OpMismatch(f"{op['name']}: cfg {ch['cfg']} family {ch['family']} ({ch['label']}) differs in bits from "
+                                   f"cfg {base['cfg']} family {base['family']} ({base['label']}) in the same arithmetic")
+            variants["checked"] += 1
+
+
+def record(pair, rows, failures, tag=""):
+    d = os.environ.get("DMX_OP_PARITY_RECORD")
+    if not d:
+        return
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, f"op_parity_{pair.case}_{pair.mode}{tag}.txt"), "w") as f:
+        f.write("# op\tkernel\tK\tc\tworst |g - r| / (u s)\tRMS (g - r) / (u s)\tRMS of the fp32 interpreter (ops under the RMS rule)\tmedian s / |r|\n")
+        for name, label, K, c, worst, rg, rf, loose in rows:
+            f.write(f"{name}\t{label}\t{K}\t{c}\t{worst:.3f}\t{rg:.4f}\t{'-' if rf is None else format(rf, '.4f')}\t{loose:.3g}\n")
+        for msg in failures:
+            f.write(f"# MISMATCH {msg}\n")
+
+
+@pytest.mark.parametrize("case,mode", [(c, m) for c, v in R.CASES.items() for m in v[3]])
+def test_every_op_against_fp64(case, mode, dmxb, L, tmp_models):
+    pair = Pair(dmxb, L, tmp_models, case, mode)
+    try:
+        pair.assert_same_plan()
+        rows, _, failures = sweep(pair)
+        record(pair, rows, failures)
+        assert not failures, failures[:12]
+        assert len(rows) > 100
+    finally:
+        pair.close()
+
+
+def test_every_op_against_fp64_with_a_silent_segment(dmxb, L, tmp_models):
+    """one of the two segments all zeros: standard deviation 0, exact zeros wherever the magnitude is 0"""
+    pair = Pair(dmxb, L, tmp_models, "4s_8000", "bf16x3", zero_segment=True)
+    try:
+        pair.assert_same_plan()
+        rows, _, failures = sweep(pair)
+        record(pair, rows, failures, "_silent")
+        assert not failures, failures[:12]
+    finally:
+        pair.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# every tile and every kernel family
+UNUSED_CFGS = {1, 17, 18}  # plan.h kTileCfgs: 1 is never chosen, 17 / 18 have no kernel (the slots keep the numbering)
+FAMILIES = {1: "GF_DIRECT", 2: "GF_TILE", 3: "GF_LIN256", 4: "GF_SPLIT_STAGED", 5: "GF_SPLIT_STAGED_LIN", 6: "GF_SPLIT_LIN", 7: "GF_SPLIT_LINH",
+            8: "GF_SPLIT_LINW", 9: "GF_SPLIT_WIDE_CONV", 10: "GF_SPLIT_NARROW"}
+# not reachable in f32 / bf16x3 contexts: the fp16-term linear kernel exists in fp16x3 contexts only (test_every_op_against_fp64
+# [4s_8000-fp16x3] launches it as the plan's own choice)
+EXEMPT_FAMILIES = {7}
+
+
+@pytest.fixture(scope="module")
+def variant_sweeps(dmxb, L, tmp_models):
+    out = {}
+    for case in ("4s_8000", "6s_7000"):
+        for mode in ("f32", "bf16x3"):
+            pair = Pair(dmxb, L, tmp_models, case, mode)
+            try:
+                pair.assert_same_plan()
+                variants = {"checked": 0, "refused": set()}
+                rows, launched, failures = sweep(pair, variants)
+                record(pair, rows, failures, "_variants")
+                out[(case, mode)] = (variants, launched, failures)
+            finally:
+                pair.close()
+    return out
+
+
+def test_every_tile_and_family_meets_the_bound_and_the_sibling_claims(variant_sweeps):
+    for key, (variants, _, failures) in variant_sweeps.items():
+        assert not failures, (key, failures[:12])
+        assert variants["checked"] > 50, (key, variants["checked"])
+
+
+def test_every_tile_and_family_is_launched(variant_sweeps):
+    cfgs, fams = set(), set()
+    for _, launched, _ in variant_sweeps.values():
+        cfgs |= {c for c, _, _ in launched if c >= 0}
+        fams |= {f for _, f, _ in launched if f > 0}
+    want_cfgs = (set(range(17)) | {19, 20}) - UNUSED_CFGS
+    assert not want_cfgs - cfgs, f"tile cfgs never launched: {sorted(want_cfgs - cfgs)}"
+    want_fams = set(FAMILIES) - EXEMPT_FAMILIES
+    assert not want_fams - fams, f"kernel families never launched: {[FAMILIES[f] for f in sorted(want_fams - fams)]}"
