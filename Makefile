@@ -16,12 +16,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
 OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o attention.o attention_split.o resample.o pcm.o flac.o v3.o api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp op_step plan_harness harness micro
+all: $(LIB) cli oracle interp op_step plan_harness att_harness harness micro
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@ $(QUIET)
-build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
+build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@ $(QUIET)
 
@@ -50,6 +50,11 @@ plan_harness: tests/_build/tracks_plan_harness
 tests/_build/tracks_plan_harness: tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p tests/_build
 	g++ -O2 -std=c++17 -Wall -o $@ tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp
+# the attention form rule (csrc/attention_select.h: host arithmetic, no HIP) over the plans a context builds, as a stand-alone CPU program
+att_harness: tests/_build/attention_select_harness
+tests/_build/attention_select_harness: tests/attention_select_harness.cpp $(CSRC)/attention_select.h $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp $(CSRC)/gemm_select.h
+	@mkdir -p tests/_build
+	g++ -O2 -std=c++17 -Wall -o $@ tests/attention_select_harness.cpp
 
 # GPU test harnesses of the C++ shim (re-entrancy; Eigen-typed overloads against tests/eigen_stub, which is NOT Eigen)
 harness: tests/_build/shim_harness tests/_build/shim_harness_eigen tests/_build/wav_harness tests/_build/pcm_wav_harness tests/_build/remix_parse_harness
@@ -89,7 +94,7 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp op_step plan_harness harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness att_harness harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:

@@ -199,7 +199,7 @@ def parse_op_info(text: str) -> dict:
         k, _, v = word.partition("=")
         if k in ("reads", "writes", "scratch", "rowstat"):
             d[k] = [tuple(int(x) for x in r.split(":")) for r in v.split(",") if r]
-        elif k in ("name", "label"):
+        elif k in ("name", "label", "form"):
             d[k] = v
         else:
             d[k] = int(v)

@@ -351,12 +351,18 @@ static Plan *get_plan(dmx_ctx *c, int batch)
     kv.hs = c->m->pm.dim / 8;
     const bool kvPlanes = c->gemm != DMX_GEMM_F32 && !planesOff && c->m->pm.arch != 3 && launch_attention_split(kv, nullptr, true) == 0;
     build_chosen_plan(c->m->pm, c->seg, batch, c->gemm, kvPlanes, model_facts(c->m), split_lin_mode(), *p);
+    // DMX_ATT_PAIR (read per plan, like DMX_KV_PLANES): 0 never the paired kernel, 2 wherever it exists, unset: attention_select.h's rule
+    const char *pairEnv = getenv("DMX_ATT_PAIR");
+    const int pairMode = !pairEnv ? 1 : atoi(pairEnv) == 0 ? 0 : atoi(pairEnv) == 2 ? 2 : 1;
     for (Op &op : p->ops)
         if (op.kind == OP_ATTENTION)
         {
-            AttnArgs t{};
-            t.hs = op.at.hs;
-            op.at.split = c->gemm != DMX_GEMM_F32 && launch_attention_split(t, nullptr, true) == 0 ? 1 : 0;
+            Attention &t = op.at;
+            AttnArgs k{};
+            k.hs = t.hs;
+            t.split = c->gemm != DMX_GEMM_F32 && launch_attention_split(k, nullptr, true) == 0 ? 1 : 0;
+            if (t.split)
+                t.form = att_select_form(t.Tq, t.Tk, t.H, t.B, t.hs, t.kpl >= 0 && t.vt >= 0, pairMode);
         }
     Plan *raw = p.get();
     c->plans[batch] = std::move(p);
@@ -910,6 +916,7 @@ static int launch_op(const dmx_ctx *c, const Op &op, hipStream_t s, i64 zeroOff)
         k.kpl = t.kpl >= 0 ? reinterpret_cast<const unsigned short *>(A + t.kpl) : nullptr;
         k.vt = t.vt >= 0 ? reinterpret_cast<const unsigned short *>(A + t.vt) : nullptr;
         k.kvPlane = (i64)t.B * t.Tk * t.H * t.hs;
+        k.form = t.form;
         if (!(t.split && launch_attention_split(k, s) == 0))
         {
             if (t.kpl >= 0)

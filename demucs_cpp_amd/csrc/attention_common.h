@@ -4,6 +4,7 @@
 // pre-multiplied by scale * log2 e), lane (l15, h4) of a wave holds, for the query 16 f + l15 of a fragment, the scores of
 // keys 16 kf + 4 h4 + r (kf < 4, r < 4) of the current 64-key tile.
 #pragma once
+#include "attention_select.h"
 #include "kernels.h"
 
 namespace dmx
@@ -133,18 +134,7 @@ __device__ __forceinline__ bool att_tile_of_block(const AttnArgs &p, unsigned &q
     return true;
 }
 
-// 32 queries per wave (128 per workgroup) when that still leaves >= 2 rounds of workgroups per CU; the key-tile order,
-// hence every rounding, is the same for both shapes. (rounds of the 512 resident workgroups) x (relative duration of
-// one workgroup): the 64-query shape does ~0.6x the work of the 128-query one per workgroup (K/V LDS reads amortised
-// over half the queries); e.g. Tq = 1344 at batch 12 is 1056 big workgroups = 2.06 rounds -> 3, or 2016 small = 3.94 ->
-// 4 x 0.6. Below two full rounds of 128-query workgroups the launch is latency-bound, not matrix-bound, and the 64-query
-// shape (twice the waves for the same work) wins whatever the round count says: measured at 1 / 2 / 4 segments
-// 1.12 / 1.78 / 3.17 ms (64) vs 1.39 / 2.05 / 3.32 ms (128) for the ten attention launches of a plan run.
-inline bool att_use_big_shape(const AttnArgs &a)
-{
-    const long wg128 = (long)((a.Tq + 127) / 128) * a.H * a.B, wg64 = (long)((a.Tq + 63) / 64) * a.H * a.B;
-    const double costBig = (double)((wg128 + 511) / 512), costSmall = 0.6 * (double)((wg64 + 511) / 512);
-    return wg128 >= 1024 && costBig <= costSmall;
-}
+// 128- or 64-query workgroups: the shape rule of attention_select.h on a launch's arguments
+inline bool att_use_big_shape(const AttnArgs &a) { return att_big_shape(a.Tq, a.H, a.B); }
 
 } // namespace dmx

@@ -33,6 +33,10 @@
 // 1 KB per wave instruction, the XOR swizzle applied to the SOURCE slot): no staging registers, no split and no ds_write in
 // the tile loop - the K / V splits were 1.6 of the 16.7 ms this kernel took per 42-segment step (ablation, profiles/r05_*),
 // redone by every query tile. Whole 64-key tiles only (plan.cpp planes_ok), so no masked tile exists in this form.
+//
+// Three launch forms, chosen per op when its plan is built (attention_select.h; plan.h Attention::form): 64- and 128-query
+// workgroups of 256 threads (attention_split_kernel, QF = 1 | 2) and, for the planes form, PAIRS of 128-query units in one
+// 512-thread workgroup (attention_split_pair_kernel). All three run attention_split_body: one text, the same bits.
 #include "attention_common.h"
 #include "igemm_common.h"
 #include <cstdlib>
@@ -44,9 +48,14 @@ namespace dmx
 __device__ __forceinline__ int swzK(int key) { return (key >> 1) & 7; }
 __device__ __forceinline__ int swzV(int dim) { return ((dim >> 1) & 1) | (((dim >> 3) & 1) << 1) | (((dim >> 2) & 1) << 2); }
 
-template <int HS, int QF, bool PL>
-__global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs p)
+// One 256-thread, four-wave unit on one 64 QF-query tile: the whole of attention_split_kernel, and one HALF of a workgroup of
+// attention_split_pair_kernel (PAIR; planes form only). tid is the thread's number within the unit, the images are the unit's own,
+// live = false (PAIR only): a half without a tile, which runs a duplicate for its barriers and stores nothing.
+template <int HS, int QF, bool PL, bool PAIR>
+__device__ __forceinline__ void attention_split_body(const AttnArgs &p, u32x4 (*Kp0)[64][8], u32x4 (*Kp1)[64][8], u32x4 (*Vp)[HS][8], const int tid,
+                                                     const unsigned qt, const unsigned bh, const int half, const bool live)
 {
+    static_assert(!PAIR || (PL && QF == 2), "the paired form exists for the 128-query planes kernel only");
     constexpr int DF = HS / 16;  // dim fragments of O
     constexpr int KT = 64;       // keys per tile
     constexpr int NS = 8;        // 16-byte slots per image row
@@ -55,14 +64,8 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs 
     constexpr int DQ = HS / 4;   // dim quads
     static_assert(HS == 64 || HS == 48, "head dims of htdemucs (512 / 8, 384 / 8)");
 
-    __shared__ u32x4 Kp0[3][KT][NS], Kp1[3][KT][NS]; // [plane][key][slot]
-    __shared__ u32x4 Vp[3][HS][NS];                  // [plane][dim][slot]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, h4 = lane >> 4;
-    unsigned qt, bh;
-    if (!att_tile_of_block(p, qt, bh))
-        return;
     const int b = (int)(bh / (unsigned)p.H), head = (int)(bh - (unsigned)b * (unsigned)p.H);
     const int q0 = (int)qt * (64 * QF) + wave * (16 * QF);
     const float *Q = p.q + (i64)b * p.qB + head * HS;
@@ -179,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs 
     // at (row 8 c + l / 8, slot position l % 8) and therefore FETCHES source slot (l % 8) ^ swizzle(row).
     const int drow = lane >> 3, dpos = lane & 7;
     const int D = p.H * HS;
-    const int wv = __builtin_amdgcn_readfirstlane(wave); // (uniform: the chunk tests below are scalar branches)
+    const int wv = __builtin_amdgcn_readfirstlane(wave) & 3; // (uniform: the chunk tests below are scalar; a unit has four waves)
     auto dma_k = [&](int t0, int buf) {
         u32x4(*Kp)[KT][NS] = buf ? Kp1 : Kp0;
 #pragma unroll
@@ -259,51 +262,130 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs 
                                                                                       sT[f][kf0 + u], 0, 0, 0);
             }
     };
-    // O^T += V^T P^T: per 32-key step s the P planes of both query fragments, then the dim fragments two at a time
+    // O^T += V^T P^T: per 32-key step s the P planes of both query fragments (psplit: the exact three-term split of the softmax's
+    // fp32 P), then the dim fragments two at a time (pvmul)
+    auto psplit = [&](int s, f32x4 (*sT)[4], bf16x8 (*pp)[3]) {
+#pragma unroll
+        for (int f = 0; f < QF; ++f)
+        {
+            unsigned h1[4], h2[4], h3[4];
+            split3_pk(sT[f][2 * s][0], sT[f][2 * s][1], h1[0], h2[0], h3[0]);
+            split3_pk(sT[f][2 * s][2], sT[f][2 * s][3], h1[1], h2[1], h3[1]);
+            split3_pk(sT[f][2 * s + 1][0], sT[f][2 * s + 1][1], h1[2], h2[2], h3[2]);
+            split3_pk(sT[f][2 * s + 1][2], sT[f][2 * s + 1][3], h1[3], h2[3], h3[3]);
+            pp[f][0] = __builtin_bit_cast(bf16x8, u32x4{h1[0], h1[1], h1[2], h1[3]});
+            pp[f][1] = __builtin_bit_cast(bf16x8, u32x4{h2[0], h2[1], h2[2], h2[3]});
+            pp[f][2] = __builtin_bit_cast(bf16x8, u32x4{h3[0], h3[1], h3[2], h3[3]});
+        }
+    };
+    auto pvmul = [&](int s, bf16x8 (*pp)[3]) {
+#pragma unroll
+        for (int d0 = 0; d0 < DF; d0 += 2)
+        {
+            constexpr int ND = 2;
+            bf16x8 va[ND][3];
+#pragma unroll
+            for (int u = 0; u < ND; ++u)
+                if (d0 + u < DF)
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl)
+                        va[u][pl] = __builtin_bit_cast(bf16x8, Vp[pl][16 * (d0 + u) + l15][(4 * s + h4) ^ vsw]);
+            constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0}; // v3 p1, v1 p3, v2 p2, v2 p1, v1 p2, v1 p1
+#pragma unroll
+            for (int tm = 0; tm < 6; ++tm)
+#pragma unroll
+                for (int u = 0; u < ND; ++u)
+                    if (d0 + u < DF)
+#pragma unroll
+                        for (int f = 0; f < QF; ++f)
+                            o[f][d0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[u][TA[tm]], pp[f][TB[tm]], o[f][d0 + u], 0, 0, 0);
+        }
+    };
     auto pvprod = [&](f32x4 (*sT)[4]) {
 #pragma unroll
         for (int s = 0; s < 2; ++s)
         {
             bf16x8 pp[QF][3];
-#pragma unroll
-            for (int f = 0; f < QF; ++f)
-            {
-                unsigned h1[4], h2[4], h3[4];
-                split3_pk(sT[f][2 * s][0], sT[f][2 * s][1], h1[0], h2[0], h3[0]);
-                split3_pk(sT[f][2 * s][2], sT[f][2 * s][3], h1[1], h2[1], h3[1]);
-                split3_pk(sT[f][2 * s + 1][0], sT[f][2 * s + 1][1], h1[2], h2[2], h3[2]);
-                split3_pk(sT[f][2 * s + 1][2], sT[f][2 * s + 1][3], h1[3], h2[3], h3[3]);
-                pp[f][0] = __builtin_bit_cast(bf16x8, u32x4{h1[0], h1[1], h1[2], h1[3]});
-                pp[f][1] = __builtin_bit_cast(bf16x8, u32x4{h2[0], h2[1], h2[2], h2[3]});
-                pp[f][2] = __builtin_bit_cast(bf16x8, u32x4{h3[0], h3[1], h3[2], h3[3]});
-            }
-#pragma unroll
-            for (int d0 = 0; d0 < DF; d0 += 2)
-            {
-                constexpr int ND = 2;
-                bf16x8 va[ND][3];
-#pragma unroll
-                for (int u = 0; u < ND; ++u)
-                    if (d0 + u < DF)
-#pragma unroll
-                        for (int pl = 0; pl < 3; ++pl)
-                            va[u][pl] = __builtin_bit_cast(bf16x8, Vp[pl][16 * (d0 + u) + l15][(4 * s + h4) ^ vsw]);
-                constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0}; // v3 p1, v1 p3, v2 p2, v2 p1, v1 p2, v1 p1
-#pragma unroll
-                for (int tm = 0; tm < 6; ++tm)
-#pragma unroll
-                    for (int u = 0; u < ND; ++u)
-                        if (d0 + u < DF)
-#pragma unroll
-                            for (int f = 0; f < QF; ++f)
-                                o[f][d0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[u][TA[tm]], pp[f][TB[tm]], o[f][d0 + u], 0, 0, 0);
-            }
+            psplit(s, sT, pp);
+            pvmul(s, pp);
         }
     };
 
     const int nt = (p.Tk + KT - 1) / KT;
     const bool partial = (p.Tk % KT) != 0;
-    if constexpr (PL)
+    if constexpr (PAIR)
+    {
+        // Two phases per tile, each closed by a workgroup barrier (attention_select.h att_pair_barriers counts them):
+        //   alpha(t): request V(t) -> V^T image (t >= 1; free: every wave of the half is past P V of tile t-1) and K(t+1) -> K buffer
+        //             (t+1) & 1 (last read by S(t-1)); softmax of S(t) in place and the three-term split of P; wait for the
+        //             pieces                                                                                      VALU + DMA
+        //   beta(t):  O += V(t)^T P^T from the P planes; S(t+1) from K buffer (t+1) & 1 into the S registers     matrix pipe + LDS reads
+        // (With the P split left in beta, where pvprod has it, the pairing LOSES 3 - 7 %: a lone wave's MFMA phase is then half VALU,
+        // and two unrelated workgroups fill each other's gaps better than that - profiles/attention_pair_ab.txt.)
+        // Half B passes one barrier more before its loop and half A one more behind it, so that from then on the alpha of one half
+        // lies beside the beta of the other on every SIMD. The barriers are the workgroup's: both halves pass 3 + 2 nt of them.
+        f32x4 sT[QF][4];
+        bf16x8 pp[2][QF][3]; // the P planes of the tile's two 32-key steps
+        const std::integral_constant<int, 0> even{};
+        const std::integral_constant<int, 1> odd{};
+        auto sync = [&]() {
+            __builtin_amdgcn_sched_barrier(0); // (the compiler moves MFMAs across a bare barrier)
+            __syncthreads();
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto alpha = [&](int t, auto parTag) {
+            constexpr int PAR = decltype(parTag)::value;
+            if (t >= 1)
+                dma_v(t);
+            __builtin_amdgcn_sched_barrier(0);
+            dma_k((t + 1) * KT, PAR ^ 1); // beyond the end: a clamped re-read, never used
+#pragma unroll
+            for (int f = 0; f < QF; ++f)
+            {
+                att_softmax_pre<DF, false, false>(sT[f], o[f], mrun[f], lrun[f], mcur[f], t, h4, p.Tk, 0, 0.f);
+                att_softmax_post(sT[f], lrun[f], mcur[f]);
+            }
+            psplit(0, sT, pp[0]);
+            psplit(1, sT, pp[1]);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            sync();
+        };
+        auto beta = [&](auto parTag, auto lastTag) {
+            constexpr int PAR = decltype(parTag)::value;
+            pvmul(0, pp[0]);
+            pvmul(1, pp[1]);
+            if constexpr (!decltype(lastTag)::value)
+                scores(PAR ^ 1, sT);
+            sync();
+        };
+        dma_k(0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        dma_v(0);
+        if (half)
+            sync();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        sync();
+        scores(0, sT);
+        sync();
+        int t = 0;
+        for (; t + 2 < nt; t += 2)
+        {
+            alpha(t, even);
+            beta(even, std::false_type{});
+            alpha(t + 1, odd);
+            beta(odd, std::false_type{});
+        }
+        alpha(t, even);
+        if (t + 1 < nt)
+        {
+            beta(even, std::false_type{});
+            alpha(t + 1, odd);
+            beta(odd, std::true_type{});
+        }
+        else
+            beta(even, std::true_type{});
+    }
+    else if constexpr (PL)
     {
         // prologue: K(0) -> Kp0; then per tile t (PAR = t & 1):
         //   request V(t) -> V^T image (every wave is past P V of tile t-1: barrier X) and K(t+1) -> K buffer PAR ^ 1 (last read by
@@ -405,7 +487,7 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs 
         const float l = quad_lanes_sum(lrun[f]);
         const float inv = 1.0f / l;
         const int qr = q0 + 16 * f + l15;
-        if (qr < p.Tq)
+        if (live && qr < p.Tq)
         {
             float *O = p.o + (i64)b * p.oB + (i64)qr * p.ldo + head * HS;
 #pragma unroll
@@ -414,6 +496,49 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs 
                     make_float4(o[f][d][0] * inv, o[f][d][1] * inv, o[f][d][2] * inv, o[f][d][3] * inv);
         }
     }
+    if constexpr (PAIR)
+        if (!half) // half B's last beta
+        {
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+        }
+}
+
+template <int HS, int QF, bool PL>
+__global__ __launch_bounds__(256, 2) void attention_split_kernel(const AttnArgs p)
+{
+    __shared__ u32x4 Kp0[3][64][8], Kp1[3][64][8]; // [plane][key][slot]
+    __shared__ u32x4 Vp[3][HS][8];                 // [plane][dim][slot]
+    unsigned qt, bh;
+    if (!att_tile_of_block(p, qt, bh))
+        return;
+    attention_split_body<HS, QF, PL, false>(p, Kp0, Kp1, Vp, (int)threadIdx.x, qt, bh, 0, true);
+}
+
+// Two 128-query units in one 512-thread workgroup, one wave of each per SIMD: waves 0-3 are half A, waves 4-7 half B, each with
+// its own query tile, Q planes and LDS images (2 x 72 KB), run one phase apart (attention_split_body PAIR) so that the softmax and
+// P split of one half issue beside the MFMAs of the other. Workgroup w of XCD w % 8 takes tiles 2 (w / 8) and 2 (w / 8) + 1 of that
+// XCD's tile list, which is the list of att_tile_of_block: all tiles of a (batch, head) stay on one XCD. The tiles of an XCD are
+// a prefix of its list, so only its last workgroup can have a half without a tile; one without any returns as a whole.
+template <int HS>
+__global__ __launch_bounds__(512, 1) void attention_split_pair_kernel(const AttnArgs p)
+{
+    __shared__ u32x4 Kp[2][2][3][64][8]; // [half][buffer][plane][key][slot]
+    __shared__ u32x4 Vp[2][3][HS][8];    // [half][plane][dim][slot]
+    const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8); // by wave number, not parity: SIMD = wave % 4
+    const unsigned xcd = blockIdx.x & 7u, j0 = 2u * (blockIdx.x >> 3);
+    const unsigned nbh = (unsigned)(p.B * p.H);
+    if ((j0 / p.nQt) * 8u + xcd >= nbh)
+        return; // (both halves: no barrier is left waiting)
+    unsigned j = j0 + (unsigned)half;
+    const bool live = (j / p.nQt) * 8u + xcd < nbh;
+    if (!live)
+        j = j0;
+    const unsigned g = j / p.nQt;
+    // the second-dispatched half loses the VALU arbitration of every phase to the older one: one static priority, no flips
+    if (half)
+        __builtin_amdgcn_s_setprio(1);
+    attention_split_body<HS, 2, true, true>(p, Kp[half][0], Kp[half][1], Vp[half], (int)threadIdx.x & 255, j - g * p.nQt, g * 8u + xcd, half, live);
 }
 
 // -1: no split kernel for this head dim (the caller falls back to the fp32 MFMA kernel)
@@ -426,11 +551,23 @@ int launch_attention_split(const AttnArgs &a0, hipStream_t s, bool dry)
     constexpr int xcdMap = 1; // all query tiles of one (batch, head) on one XCD
     AttnArgs a = a0;
     a.xcdMap = xcdMap;
-    const bool big = att_use_big_shape(a); // 128- or 64-query workgroups (attention_common.h): same arithmetic either way
+    // the form was chosen when the plan was built (attention_select.h): same arithmetic in every one
+    const bool big = a.form != ATT_FORM_WG64;
     a.nQt = (unsigned)(big ? (a.Tq + 127) / 128 : (a.Tq + 63) / 64);
     const unsigned nbh = (unsigned)(a.B * a.H);
     const dim3 grid(xcdMap ? 8u * ((nbh + 7u) / 8u) * a.nQt : nbh * a.nQt);
     const bool planes = a.kpl && a.vt && a.Tk % 64 == 0;
+    if (a.form == ATT_FORM_PAIR)
+    {
+        if (!att_pair_exists(a.Tk, a.hs, planes))
+            return -1;
+        const dim3 pairs(8u * (((nbh + 7u) / 8u * a.nQt + 1u) / 2u)); // per XCD: the tiles of its list two by two
+        if (a.hs == 64)
+            hipLaunchKernelGGL((attention_split_pair_kernel<64>), pairs, dim3(512), 0, s, a);
+        else
+            hipLaunchKernelGGL((attention_split_pair_kernel<48>), pairs, dim3(512), 0, s, a);
+        return 0;
+    }
 #define DMX_ATT_LAUNCH(HS_, QF_)                                                                            \
     do                                                                                                      \
     {                                                                                                       \

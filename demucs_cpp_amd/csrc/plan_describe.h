@@ -1,6 +1,7 @@
 // plan_describe.h — one op of a plan as a line of key=value words: what dmx_debug_op_info (api.cpp) reports and what
 // tests/cpu_interp.cpp reports for its own plan, so that the two plans can be compared word by word. Plain C++, no HIP.
 #pragma once
+#include "attention_select.h"
 #include "plan.h"
 #include <algorithm>
 #include <cstdio>
@@ -58,6 +59,8 @@ inline std::string describe_op(const Op &op)
     case OP_ATTENTION:
         all += std::string(" label=") + (op.at.split ? "attention_split" : "attention");
         word("K", op.at.hs), word("T", op.at.Tk), word("split", op.at.split), word("planes", op.at.kpl >= 0);
+        word("Tq", op.at.Tq), word("H", op.at.H), word("B", op.at.B);
+        all += std::string(" form=") + (op.at.split ? att_form_name(op.at.form) : "-");
         if (op.at.kpl >= 0)
             word("kpl", op.at.kpl), word("vt", op.at.vt), word("kvPlane", (i64)op.at.B * op.at.Tk * op.at.H * op.at.hs);
         break;
