@@ -14,9 +14,9 @@ NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
 QUIET := 2> >(grep -v "packed-fp32-ops' is not a recognized feature" >&2)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(NOPK)
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
-OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o attention.o attention_split.o resample.o pcm.o flac.o v3.o api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
+OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o attention.o attention_split.o resample.o pcm.o flac.o flac_in.o v3.o api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp op_step plan_harness att_harness harness micro
+all: $(LIB) cli oracle interp op_step plan_harness att_harness flac_in_host harness micro
 
 build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
@@ -56,6 +56,16 @@ tests/_build/attention_select_harness: tests/attention_select_harness.cpp $(CSRC
 	@mkdir -p tests/_build
 	g++ -O2 -std=c++17 -Wall -o $@ tests/attention_select_harness.cpp
 
+# the FLAC input stage's kernel text (csrc/flac_in.hip) as host code in a stand-alone CPU program (tests/test_flac_in_cpu.py;
+# CXXFLAGS_FLAC_IN=-fsanitize=address,undefined FLAC_IN_OUT=... builds the sanitizer form, as flac_in_host_asan does)
+FLAC_IN_OUT ?= tests/_build/flac_in_host_main
+flac_in_host: $(FLAC_IN_OUT)
+$(FLAC_IN_OUT): tests/flac_in_host_main.cpp $(CSRC)/flac_in.hip include/demucs_hip.h
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -Wall -DDMX_FLAC_IN_HOST $(CXXFLAGS_FLAC_IN) -o $@ tests/flac_in_host_main.cpp
+flac_in_host_asan:
+	$(MAKE) flac_in_host FLAC_IN_OUT=tests/_build/flac_in_host_main_asan CXXFLAGS_FLAC_IN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
+
 # GPU test harnesses of the C++ shim (re-entrancy; Eigen-typed overloads against tests/eigen_stub, which is NOT Eigen)
 harness: tests/_build/shim_harness tests/_build/shim_harness_eigen tests/_build/wav_harness tests/_build/pcm_wav_harness tests/_build/remix_parse_harness
 tests/_build/remix_parse_harness: tests/remix_parse_harness.cpp $(LIB) demucs_cpp_amd/host/demucscpp_hip.hpp
@@ -94,12 +104,12 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp op_step plan_harness att_harness harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness att_harness flac_in_host flac_in_host_asan harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:
 	@mkdir -p build/$(NAME)
-	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc attention attention_split resample pcm flac v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
+	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc attention attention_split resample pcm flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
 	for f in api engine plan model_pack tracks_plan gemm_select; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -x hip -c $(CSRC)/$$f.cpp -o build/$(NAME)/$$f.o & done; wait
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o demucs_cpp_amd/lib/libdemucs_hip_$(NAME).so build/$(NAME)/*.o
 # one file rebuilt with other flags, the rest of the product's objects unchanged:

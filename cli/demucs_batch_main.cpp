@@ -2,7 +2,11 @@
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--bag-weights w00,w01,...]
-//                         <model> <out dir> <wav file>...
+//                         <model> <out dir> <wav or flac file>...
+// An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a 44.1 kHz FLAC
+// file the files go to the GPU as they are and are decoded there (dmx_tracks_infer_from_flac; csrc/flac_in.hip) - the outputs
+// are those of the equivalent WAV inputs; otherwise a FLAC file is decoded on the GPU (dmx_flac_decode) and treated as a
+// WAV file of its rate (DMX_RESAMPLE).
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
 // byte-identical to what demucs.cpp.main / demucs_v3.cpp.main writes for that input alone. The model's architecture
 // (HTDemucs v4 4s / 6s, or Demucs v3) is read from the file; the segments of all tracks share batches
@@ -235,13 +239,14 @@ int main(int argc, const char **argv)
     // minus, none, --remix and --flac leave through the remix entry points; everything else as before
     const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE || flac;
     remix_options remix;
+    bool flac_in = false; // every input is a 44.1 kHz .flac file (decided once the inputs have been looked at)
     auto make_remix = [&](int nb_sources) { // once the model's stems are known
         if (with_out_opts && out_opts.two_stems >= nb_sources)
         {
             std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
             exit(1);
         }
-        if (!with_remix)
+        if (!with_remix && !flac_in)
             return;
         try
         {
@@ -263,6 +268,8 @@ int main(int argc, const char **argv)
             exit(1);
         }
         remix.encoding = out_opts.encoding, remix.clip = out_opts.clip, remix.flac = flac;
+        if (!with_out_opts) // FLAC inputs without an output option: the float32 stems, through unit gains
+            remix.encoding = DMX_PCM_F32, remix.clip = DMX_CLIP_NONE;
     };
     if (!opts.shift_offsets.empty() && (int)opts.shift_offsets.size() != opts.shifts)
     {
@@ -338,8 +345,44 @@ int main(int argc, const char **argv)
     std::vector<StereoMatrix> tracks((size_t)n_files);
     std::vector<int> native_rate((size_t)n_files, SUPPORTED_SAMPLE_RATE); // != 44100 only with DMX_RESAMPLE=1 (wav.hpp)
     std::vector<int64_t> native_frames((size_t)n_files, -1);
+    // FLAC inputs (the content decides, not the name). When EVERY input is a 44.1 kHz .flac file the bytes go to the GPU as
+    // they are (dmx_tracks_infer_from_flac); otherwise a .flac file is decoded on the GPU (dmx_flac_decode) and then takes
+    // the way of a WAV file of its rate.
+    std::vector<FlacFile> flac_files((size_t)n_files);
+    std::vector<int64_t> flac_frames;
+    int n_flac = 0, n_flac_441 = 0;
     for (int i = 0; i < n_files; ++i)
-        if (!wavio::load_audio_file(argv[3 + i], tracks[(size_t)i], &native_rate[(size_t)i], &native_frames[(size_t)i]))
+    {
+        std::vector<uint8_t> head(16);
+        FILE *fh = fopen(argv[3 + i], "rb");
+        const size_t got = fh ? fread(head.data(), 1, head.size(), fh) : 0;
+        if (fh)
+            fclose(fh);
+        head.resize(got);
+        if (!(got >= 4 && (memcmp(head.data(), "fLaC", 4) == 0 || memcmp(head.data(), "ID3", 3) == 0)))
+            continue;
+        if (!wavio::read_file_bytes(argv[3 + i], flac_files[(size_t)i]))
+            exit(1);
+        if (!wavio::is_flac_image(flac_files[(size_t)i]))
+        {
+            flac_files[(size_t)i].clear();
+            continue;
+        }
+        ++n_flac;
+        dmx_flac_info info;
+        if (dmx_flac_probe(flac_files[(size_t)i].data(), (int64_t)flac_files[(size_t)i].size(), &info) != DMX_OK)
+        {
+            std::cerr << "[ERROR] " << argv[3 + i] << ": " << dmx_last_error() << std::endl;
+            exit(1);
+        }
+        n_flac_441 += info.sample_rate == SUPPORTED_SAMPLE_RATE;
+    }
+    flac_in = n_flac == n_files && n_flac_441 == n_files;
+    for (int i = 0; i < n_files && !flac_in; ++i)
+        if (!(flac_files[(size_t)i].empty()
+                  ? wavio::load_audio_file(argv[3 + i], tracks[(size_t)i], &native_rate[(size_t)i], &native_frames[(size_t)i])
+                  : wavio::load_flac_image(argv[3 + i], flac_files[(size_t)i], tracks[(size_t)i], &native_rate[(size_t)i],
+                                           &native_frames[(size_t)i])))
             exit(1);
     if (with_out_opts)
         for (int i = 0; i < n_files; ++i)
@@ -356,6 +399,7 @@ int main(int argc, const char **argv)
     };
     std::vector<StemTensor> outs;
     PcmOutputs pcm_outs;
+    auto remix_or = [&](int encoding) { return flac_in ? remix.encoding : encoding; };
     int nb_sources = 4;
     if (bag_mode)
     {
@@ -387,7 +431,9 @@ int main(int argc, const char **argv)
         std::cout << "Starting Demucs bag (" << bag_files.size() << " models, " << nb_sources << "-source) inference of " << n_files
                   << " tracks" << std::endl;
         make_remix(nb_sources);
-        if (with_remix)
+        if (flac_in)
+            pcm_outs = demucs_inference_batch_remix(bag, flac_files, cb, weights, opts, remix, nullptr, &flac_frames);
+        else if (with_remix)
             pcm_outs = demucs_inference_batch_remix(bag, tracks, cb, weights, opts, remix);
         else if (with_out_opts)
             pcm_outs = demucs_inference_batch_pcm(bag, tracks, cb, weights, opts, out_opts);
@@ -404,7 +450,9 @@ int main(int argc, const char **argv)
         }
         std::cout << "Starting Demucs v3 MMI inference of " << n_files << " tracks" << std::endl;
         make_remix(nb_sources);
-        if (with_remix)
+        if (flac_in)
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames);
+        else if (with_remix)
             pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, cb, opts, remix);
         else if (with_out_opts)
             pcm_outs = demucscpp_v3::demucs_v3_inference_batch_pcm(model, tracks, cb, opts, out_opts);
@@ -423,7 +471,9 @@ int main(int argc, const char **argv)
         nb_sources = model.is_4sources ? 4 : 6;
         std::cout << "Starting Demucs (" << nb_sources << "-source) inference of " << n_files << " tracks" << std::endl;
         make_remix(nb_sources);
-        if (with_remix)
+        if (flac_in)
+            pcm_outs = demucs_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames);
+        else if (with_remix)
             pcm_outs = demucs_inference_batch_remix(model, tracks, cb, opts, remix);
         else if (with_out_opts)
             pcm_outs = demucs_inference_batch_pcm(model, tracks, cb, opts, out_opts);
@@ -436,12 +486,13 @@ int main(int argc, const char **argv)
         const StereoMatrix &audio = tracks[(size_t)f];
         std::filesystem::path p = std::filesystem::path(out_dir) / std::filesystem::path(argv[3 + f]).stem();
         std::filesystem::create_directories(p);
-        if (with_out_opts) // the bytes are WAV data already
+        if (with_out_opts || flac_in) // the bytes are WAV data already
         {
+            const int64_t frames = flac_in ? flac_frames[(size_t)f] : audio.cols();
             const auto &po = pcm_outs[(size_t)f];
             for (size_t target = 0; target < po.size(); ++target)
             {
-                const std::string name = with_remix               ? remix.names[target]
+                const std::string name = with_remix || flac_in    ? remix.names[target]
                                          : out_opts.two_stems < 0 ? names[target]
                                                                   : (target == 0 ? two_stems : "no_" + two_stems);
                 auto p_target = p / ("target_" + std::to_string(target) + "_" + name + (flac ? ".flac" : ".wav"));
@@ -454,7 +505,7 @@ int main(int argc, const char **argv)
                     ok = (bool)f;
                 }
                 else
-                    ok = wavio::write_pcm_file(po[target].data(), audio.cols(), out_opts.encoding, p_target.string());
+                    ok = wavio::write_pcm_file(po[target].data(), frames, remix_or(out_opts.encoding), p_target.string());
                 if (!ok)
                 {
                     std::cerr << "Error writing " << p_target << std::endl;

@@ -194,6 +194,88 @@ inline bool load_audio_file(const std::string &filename, demucscpp::StereoMatrix
     return true;
 }
 
+// the whole file as bytes
+inline bool read_file_bytes(const std::string &filename, std::vector<uint8_t> &b)
+{
+    FILE *f = fopen(filename.c_str(), "rb");
+    if (!f)
+    {
+        std::cerr << "[ERROR] cannot open " << filename << std::endl;
+        return false;
+    }
+    fseek(f, 0, SEEK_END);
+    const long sz = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    b.resize((size_t)std::max(sz, 0L));
+    const bool ok = fread(b.data(), 1, b.size(), f) == b.size();
+    fclose(f);
+    return ok;
+}
+// does the content begin with "fLaC", or with an ID3v2 tag and then "fLaC" ?
+inline bool is_flac_image(const std::vector<uint8_t> &b)
+{
+    size_t p = 0;
+    if (b.size() >= 10 && memcmp(b.data(), "ID3", 3) == 0)
+        p = 10 + (((size_t)(b[6] & 127) << 21) | ((size_t)(b[7] & 127) << 14) | ((size_t)(b[8] & 127) << 7) | (size_t)(b[9] & 127)) +
+            ((b[5] & 0x10) ? 10 : 0);
+    return b.size() >= p + 4 && memcmp(b.data() + p, "fLaC", 4) == 0;
+}
+// a .flac file's image -> the track, decoded on the GPU (dmx_flac_decode); a rate other than 44.1 kHz as load_audio_file
+// treats a WAV file of that rate (DMX_RESAMPLE=1: converted on the GPU, native_rate / native_frames report the file's)
+inline bool load_flac_image(const std::string &filename, const std::vector<uint8_t> &b, demucscpp::StereoMatrix &out, int *native_rate = nullptr,
+                            int64_t *native_frames = nullptr)
+{
+    dmx_flac_info info;
+    if (dmx_flac_probe(b.data(), (int64_t)b.size(), &info) != DMX_OK)
+    {
+        std::cerr << "[ERROR] " << filename << ": " << dmx_last_error() << std::endl;
+        return false;
+    }
+    const int rate = info.sample_rate;
+    const char *rs = getenv("DMX_RESAMPLE");
+    const bool convert = rate != demucscpp::SUPPORTED_SAMPLE_RATE && native_rate && rs && atoi(rs) == 1;
+    if (rate != demucscpp::SUPPORTED_SAMPLE_RATE && !convert)
+    {
+        std::cerr << "[ERROR] demucs.cpp only supports the following sample rate (Hz): " << demucscpp::SUPPORTED_SAMPLE_RATE << std::endl;
+        return false;
+    }
+    if (native_rate)
+        *native_rate = rate;
+    if (native_frames)
+        *native_frames = -1;
+    const int64_t N = info.total_samples;
+    out = demucscpp::StereoMatrix(N);
+    int64_t status[2] = {0, 0};
+    if (dmx_flac_decode(resample_device(), b.data(), (int64_t)b.size(), &info, DMX_PCM_F32, out.data.data(), status) != DMX_OK)
+    {
+        std::cerr << "[ERROR] " << filename << ": " << dmx_last_error() << std::endl;
+        return false;
+    }
+    if (status[0] != DMX_FLAC_OK)
+    {
+        std::cerr << "[ERROR] " << filename << ": the FLAC stream is damaged at sample " << status[1] << " of " << N << std::endl;
+        return false;
+    }
+    std::cout << "Input samples: " << N << std::endl;
+    std::cout << "Length in seconds: " << (double)N / rate << std::endl;
+    std::cout << "Number of channels: " << info.channels << std::endl;
+    if (convert)
+    {
+        const int64_t n441 = dmx_resample_length(N, rate, demucscpp::SUPPORTED_SAMPLE_RATE);
+        demucscpp::StereoMatrix conv(n441);
+        if (dmx_resample(resample_device(), out.data.data(), N, 2, 1, rate, demucscpp::SUPPORTED_SAMPLE_RATE, conv.data.data()) != DMX_OK)
+        {
+            std::cerr << "[ERROR] sample-rate conversion failed: " << dmx_last_error() << std::endl;
+            return false;
+        }
+        std::cout << "Converted " << rate << " Hz -> " << demucscpp::SUPPORTED_SAMPLE_RATE << " Hz on the GPU: " << n441 << " samples" << std::endl;
+        out = std::move(conv);
+        if (native_frames)
+            *native_frames = N;
+    }
+    return true;
+}
+
 // stereo float32 WAV; `interleaved` = 2*N floats at 44.1 kHz. out_rate != 44100 (a track that was converted on the way
 // in): the stem is converted to that rate on the GPU first and cut to native_frames (>= 0: what load_audio_file reported).
 inline bool write_audio_file(const float *interleaved, int64_t N, const std::string &filename, int out_rate = 44100,

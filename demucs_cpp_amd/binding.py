@@ -41,6 +41,7 @@ EXPORTS = [
     "dmx_bag_weights", "dmx_tracks_infer_bag",
     "dmx_remix_two_stems", "dmx_remix_check", "dmx_tracks_infer_remix", "dmx_remix_encode_device", "dmx_remix_encode",
     "dmx_flac_bound", "dmx_flac_workspace_bytes", "dmx_flac_encode_device", "dmx_flac_encode", "dmx_tracks_infer_flac",
+    "dmx_flac_probe", "dmx_flac_decode_workspace_bytes", "dmx_flac_decode_device", "dmx_flac_decode", "dmx_tracks_infer_from_flac", "dmx_flac_decode_profile",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -156,6 +157,13 @@ def lib():
         L.dmx_flac_workspace_bytes.restype = i64
         L.dmx_flac_encode_device.argtypes = [ci, vp, ci, i64, ci, vp, vp, vp, vp]
         L.dmx_flac_encode.argtypes = [ci, vp, ci, i64, ci, vp, vp]
+        L.dmx_flac_probe.argtypes = [vp, i64, vp]
+        L.dmx_flac_decode_workspace_bytes.argtypes = [vp, i64]
+        L.dmx_flac_decode_workspace_bytes.restype = i64
+        L.dmx_flac_decode_device.argtypes = [ci, vp, i64, vp, ci, vp, vp, vp, vp]
+        L.dmx_flac_decode.argtypes = [ci, vp, i64, vp, ci, vp, vp]
+        L.dmx_flac_decode_profile.argtypes = [ci, vp, i64, vp, ci, vp, vp, vp, vp, vp]
+        L.dmx_tracks_infer_from_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, vp, vp, vp]
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -529,6 +537,71 @@ class Context:
         ospec = spec.output_spec()
         return [pcm_views(b, ospec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
 
+    def tracks_from_flac(self, files, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
+                         shift_offsets=None, flac_out: bool = False, progress=None, track_status=None, out=None):
+        """tracks_remix() (flac_out False) or tracks_flac() at 44100 Hz (flac_out True) on tracks given as the bytes of .flac
+        files (dmx_tracks_infer_from_flac). Returns (outs, peaks, track_status): track_status np.int64 (T, 2) = {status, good}
+        per track. A damaged track raises DmxError after all work has drained; pass `track_status` (np.int64, T * 2, flat) to
+        keep what the call learned, and `.partial` of the error holds (outs, peaks) of that call. `out`: buffers to reuse, as
+        tracks_remix() / tracks_flac() take them."""
+        T = len(files)
+        Q = 0 if models is None else len(models)
+        imgs = [np.frombuffer(f, np.uint8) for f in files]
+        ns = []
+        for t, f in enumerate(imgs):  # the sizes of the outputs come from the probe, before any GPU work
+            try:
+                ns.append(int(flac_probe(f).total_samples))
+            except DmxError as e:
+                raise DmxError(e.code, f"track {t}: {e}") from None
+        n_out = max(spec.n_out, 0)
+        fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
+        bits = 24 if spec.encoding == PCM_S24 else 16
+        if flac_out:
+            bounds = [max(lib().dmx_flac_bound(bits, n), 0) for n in ns]
+            want = [max(n_out * b, 1) for b in bounds]
+        else:
+            want = [max(n_out * n * fb, 1) for n in ns]
+        bufs = out if out is not None else [np.zeros(w, np.uint8) for w in want]
+        assert len(bufs) == T
+        for b, w in zip(bufs, want):
+            assert b.dtype == np.uint8 and b.ndim == 1 and b.size >= w and b.flags.c_contiguous
+        sizes = np.zeros(max(T * n_out, 1), np.int64)
+        peaks = np.zeros(max(T * n_out, 1), np.float32)
+        if track_status is None:
+            track_status = np.zeros(2 * max(T, 1), np.int64)
+        assert track_status.dtype == np.int64 and track_status.ndim == 1 and track_status.size >= 2 * T
+        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
+        wp = None
+        if weights is not None:
+            warr = np.ascontiguousarray(weights, np.float32)
+            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
+            wp = warr.ctypes.data
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
+            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        fp = (ctypes.c_void_p * max(T, 1))(*[f.ctypes.data for f in imgs])
+        fn = (ctypes.c_int64 * max(T, 1))(*[f.size for f in imgs])
+        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
+        rc = lib().dmx_tracks_infer_from_flac(self.h, mp, Q, wp, T, fp, fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c),
+                                              1 if flac_out else 0, op, sizes.ctypes.data, peaks.ctypes.data, track_status.ctypes.data,
+                                              cbp, None)
+        if flac_out:
+            outs = [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))]
+        else:
+            ospec = spec.output_spec()
+            outs = [pcm_views(b[:n_out * n * fb], ospec, n, n_out) for b, n in zip(bufs, ns)]
+        pk = [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+        if rc != 0:
+            e = DmxError(rc, lib().dmx_last_error().decode(errors="replace"))
+            e.partial = (outs, pk)
+            raise e
+        return outs, pk, track_status[:2 * T].reshape(T, 2)
+
     def tracks_flac(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                     shift_offsets=None, sample_rate: int = 44100, progress=None, layout: int = LAYOUT_PLANAR, out=None, sizes=None,
                     peaks=None):
@@ -780,6 +853,38 @@ def flac_encode(pcm: np.ndarray, bits: int, sample_rate: int = 44100, device: in
     size = ctypes.c_int64(0)
     _chk(lib().dmx_flac_encode(device, pcm.ctypes.data, int(bits), n, int(sample_rate), out.ctypes.data, ctypes.byref(size)))
     return bytes(out[:size.value])
+
+
+class FlacInfo(ctypes.Structure):
+    """dmx_flac_info: what dmx_flac_probe reads from a file's header"""
+    _fields_ = [("sample_rate", ctypes.c_int), ("channels", ctypes.c_int), ("bits", ctypes.c_int), ("total_samples", ctypes.c_int64),
+                ("min_block", ctypes.c_int), ("max_block", ctypes.c_int), ("min_frame", ctypes.c_int), ("max_frame", ctypes.c_int),
+                ("variable_blocking", ctypes.c_int), ("first_frame", ctypes.c_int64)]
+
+
+FLAC_OK, FLAC_BROKEN, FLAC_TOO_MANY_CANDIDATES = 0, 1, 2
+
+
+def flac_probe(data) -> FlacInfo:
+    """the header of a .flac file's bytes (dmx_flac_probe; no GPU); raises DmxError with the probe's message"""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    info = FlacInfo()
+    _chk(lib().dmx_flac_probe(buf.ctypes.data if buf.size else None, int(buf.size), ctypes.byref(info)))
+    return info
+
+
+def flac_decode(data, encoding: int = PCM_F32, device: int = 0):
+    """The FLAC input stage alone (dmx_flac_decode): the bytes of a .flac file -> (samples, status, good, info). samples:
+    np.float32 (n, 2) for PCM_F32, np.int16 (n, 2) for PCM_S16, np.uint8 (n, 2, 3) for PCM_S24; [good, n) is zero."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    info = flac_probe(buf)
+    n = int(info.total_samples)
+    out = np.zeros((n, 2), np.float32) if encoding == PCM_F32 else np.zeros((n, 2), np.int16) if encoding == PCM_S16 \
+        else np.zeros((n, 2, 3), np.uint8)
+    status = np.zeros(2, np.int64)
+    _chk(lib().dmx_flac_decode(device, buf.ctypes.data, int(buf.size), ctypes.byref(info), int(encoding), out.ctypes.data,
+                               status.ctypes.data))
+    return out, int(status[0]), int(status[1]), info
 
 
 def resample_length(n_in: int, rate_in: int, rate_out: int) -> int:

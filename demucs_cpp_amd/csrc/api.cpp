@@ -692,7 +692,7 @@ dmx_ctx::~dmx_ctx()
     {
         if (sl.copied)
             (void)hipEventDestroy(sl.copied);
-        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes})
+        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes, &sl.flacIn, &sl.flacInWork, &sl.flacInStatus})
             if (b->p)
                 (void)hipFree(b->p);
     }
@@ -1332,6 +1332,11 @@ struct TracksRun
     void *user = nullptr;
     const PcmOut *pcm = nullptr;
     const BagRun *bag = nullptr;
+    // dmx_tracks_infer_from_flac: audio[t] is the image of a .flac file of fileBytes[t] bytes that the probe has described
+    // (n[t] = its total samples); the slot's interleaved track is decoded on the upload stream; trackStatus: 2 per track
+    const dmx_flac_info *flacIn = nullptr;
+    const int64_t *fileBytes = nullptr;
+    int64_t *trackStatus = nullptr;
     // set by tracks_run_impl
     TracksPlan plan;
     int S = 0, eigen = 0, olaEigen = 0;
@@ -1382,6 +1387,18 @@ static int tracks_prepare(TracksRun &r)
                 DMXCHK(dmx_ensure_buf(sl.flacSizes, 2 * DMX_MAX_OUTPUTS));
             }
         }
+        if (r.flacIn)
+        {
+            i64 fileMax = 0, workMax = 0;
+            for (int t = 0; t < r.T; ++t)
+            {
+                fileMax = std::max<i64>(fileMax, r.fileBytes[t]);
+                workMax = std::max<i64>(workMax, flac_in_workspace_bytes(&r.flacIn[t], r.fileBytes[t]));
+            }
+            DMXCHK(dmx_ensure_buf(sl.flacIn, (fileMax + 15) / 16 * 4));
+            DMXCHK(dmx_ensure_buf(sl.flacInWork, workMax / 4));
+            DMXCHK(dmx_ensure_buf(sl.flacInStatus, 4));
+        }
         if (!sl.copied)
             HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
     }
@@ -1412,7 +1429,14 @@ static int tracks_upload(TracksRun &r, int k, int tLo, int tHi)
             HIPCHK(hipEventSynchronize(sl.copied));
         if (r.pcm)
             HIPCHK(hipMemsetAsync(sl.peaks.p, 0, sizeof(float) * (size_t)r.pcm->nOut, c->stream));
-        if (r.eigen)
+        if (r.flacIn) // the file's bytes go up; the five launches of flac_in.hip leave the interleaved track in the slot
+        {
+            HIPCHK(hipMemcpyAsync(sl.flacIn.p, r.audio[t], (size_t)r.fileBytes[t], hipMemcpyHostToDevice, c->uploadStream));
+            if (launch_flac_decode((const unsigned char *)sl.flacIn.p, r.fileBytes[t], &r.flacIn[t], DMX_PCM_F32, sl.audio.p,
+                                   (long long *)sl.flacInStatus.p, sl.flacInWork.p, c->uploadStream) != 0)
+                return fail(DMX_ERR_ARG, "%s: track %d: internal error (the probe's description was refused)", r.fn, t);
+        }
+        else if (r.eigen)
             HIPCHK(hipMemcpyAsync(sl.audio.p, r.audio[t], sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
         else
         {
@@ -1625,6 +1649,8 @@ static int tracks_copy_out(TracksRun &r, int k)
                     HIPCHK(hipMemcpyAsync(out + (size_t)pl * j.n + i0, dOut + (size_t)pl * j.n + i0, sizeof(float) * (size_t)(i1 - i0),
                                           hipMemcpyDeviceToHost, c->copyStream));
         }
+        if (j.kLast == k && r.flacIn) // behind batch k, so behind the decode; before the slot's next holder may start
+            HIPCHK(hipMemcpyAsync(r.trackStatus + 2 * (size_t)pc.t, sl.flacInStatus.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->copyStream));
         if (j.kLast == k)
             HIPCHK(hipEventRecord(sl.copied, c->copyStream));
     }
@@ -1816,6 +1842,9 @@ struct TracksCall
     const dmx_remix_spec *remix;
     int flacRate;
     int64_t *flacSizes;
+    const dmx_flac_info *flacIn; // dmx_tracks_infer_from_flac: audio[t] is a file image, described here; else NULL
+    const int64_t *fileBytes;
+    int64_t *trackStatus;
     void *const *out;
     float *peaks;
     int layout;
@@ -2160,6 +2189,7 @@ static int tracks_call(const TracksCall &a)
     TracksRun r;
     r.c = a.c, r.fn = fn, r.T = a.n_tracks, r.audio = a.audio, r.n = a.n, r.N = a.n_shifts, r.stride = stride, r.shifts = shifts.data();
     r.layout = a.layout, r.progress = a.progress, r.user = a.user;
+    r.flacIn = a.flacIn, r.fileBytes = a.fileBytes, r.trackStatus = a.trackStatus;
     if (a.kind == TRACKS_OUT_F32)
         r.out = reinterpret_cast<float *const *>(a.out);
     else
@@ -2406,6 +2436,156 @@ extern "C" int dmx_tracks_infer_flac(dmx_ctx *c, const dmx_model *const *models,
     a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
     return tracks_call(a);
+}
+
+// --------------------------------------------------------------------------- FLAC input (flac_in.hip)
+extern "C" int dmx_flac_probe(const void *file, int64_t bytes, dmx_flac_info *info)
+{
+    if (!file || !info)
+        return fail(DMX_ERR_ARG, "dmx_flac_probe: null %s pointer", !file ? "file" : "info");
+    char msg[160];
+    if (flac_in_probe(file, bytes, info, msg, sizeof msg) != 0)
+        return fail(DMX_ERR_FORMAT, "dmx_flac_probe: %s", msg);
+    return DMX_OK;
+}
+extern "C" int64_t dmx_flac_decode_workspace_bytes(const dmx_flac_info *info, int64_t bytes) { return flac_in_workspace_bytes(info, bytes); }
+
+static int flac_in_check(const char *fn, int64_t bytes, const dmx_flac_info *info, int encoding)
+{
+    if (!info)
+        return fail(DMX_ERR_ARG, "%s: null info pointer", fn);
+    if (flac_in_workspace_bytes(info, bytes) < 0)
+        return fail(DMX_ERR_ARG, "%s: info is not what dmx_flac_probe returns for a file of %lld bytes", fn, (long long)bytes);
+    if (info->bits != 8 && info->bits != 12 && info->bits != 16 && info->bits != 20 && info->bits != 24)
+        return fail(DMX_ERR_ARG, "%s: %d bits per sample (8, 12, 16, 20 or 24)", fn, info->bits);
+    if (encoding != DMX_PCM_F32 && encoding != DMX_PCM_S16 && encoding != DMX_PCM_S24)
+        return fail(DMX_ERR_ARG, "%s: encoding %d (DMX_PCM_F32 0, DMX_PCM_S16 1, DMX_PCM_S24 2)", fn, encoding);
+    if (encoding != DMX_PCM_F32 && (info->channels != 2 || info->bits != (encoding == DMX_PCM_S16 ? 16 : 24)))
+        return fail(DMX_ERR_ARG, "%s: encoding %s needs a stereo stream of exactly that depth (this one: %d channel(s), %d bits)", fn,
+                    encoding == DMX_PCM_S16 ? "DMX_PCM_S16" : "DMX_PCM_S24", info->channels, info->bits);
+    return DMX_OK;
+}
+
+extern "C" int dmx_flac_decode_device(int device, const void *d_file, int64_t bytes, const dmx_flac_info *info, int encoding, void *d_out,
+                                      int64_t *d_status, void *d_work, void *stream)
+{
+    const char *fn = "dmx_flac_decode_device";
+    DMXCHK(flac_in_check(fn, bytes, info, encoding));
+    if (!d_file || !d_out || !d_status || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_file ? "d_file" : !d_out ? "d_out" : !d_status ? "d_status" : "d_work");
+    if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_status & 7) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_out and d_work must be 16-byte aligned, d_status 8-byte aligned", fn);
+    HIPCHK(hipSetDevice(device));
+    if (launch_flac_decode((const unsigned char *)d_file, bytes, info, encoding, d_out, (long long *)d_status, d_work, (hipStream_t)stream) != 0)
+        return fail(DMX_ERR_ARG, "%s: info rejected", fn);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_flac_decode(int device, const void *file, int64_t bytes, const dmx_flac_info *info, int encoding, void *out, int64_t *status)
+{
+    const char *fn = "dmx_flac_decode";
+    DMXCHK(flac_in_check(fn, bytes, info, encoding));
+    if (!file || !out || !status)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !file ? "file" : !out ? "out" : "status");
+    HIPCHK(hipSetDevice(device));
+    const size_t outBytes = (size_t)info->total_samples * (encoding == DMX_PCM_F32 ? 8 : encoding == DMX_PCM_S16 ? 4 : 6);
+    const i64 workBytes = flac_in_workspace_bytes(info, bytes);
+    unsigned char *dIn = nullptr, *dOut = nullptr, *dWork = nullptr;
+    int64_t *dStatus = nullptr;
+    int rc = DMX_OK;
+    if (hipMalloc((void **)&dIn, (size_t)bytes) != hipSuccess || hipMalloc((void **)&dOut, DMX_OUTPUT_STRIDE(outBytes)) != hipSuccess ||
+        hipMalloc((void **)&dWork, (size_t)workBytes) != hipSuccess || hipMalloc((void **)&dStatus, 2 * sizeof(int64_t)) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK && hipMemcpy(dIn, file, (size_t)bytes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    if (rc == DMX_OK)
+        rc = dmx_flac_decode_device(device, dIn, bytes, info, encoding, dOut, dStatus, dWork, nullptr);
+    if (rc == DMX_OK && hipDeviceSynchronize() != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (rc == DMX_OK && (hipMemcpy(status, dStatus, 2 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = fail(DMX_ERR_HIP, "%s: download failed", fn);
+    for (void *p : {(void *)dIn, (void *)dOut, (void *)dWork, (void *)dStatus})
+        if (p)
+            (void)hipFree(p);
+    return rc;
+}
+
+// measurement aid (tools/flac_in_bench.py): dmx_flac_decode_device with HIP events around each of the five launches;
+// ms[0..5): candidates, scan, chain, decode, finish. Synchronises the stream.
+extern "C" int dmx_flac_decode_profile(int device, const void *d_file, int64_t bytes, const dmx_flac_info *info, int encoding, void *d_out,
+                                       int64_t *d_status, void *d_work, void *stream, float *ms)
+{
+    const char *fn = "dmx_flac_decode_profile";
+    DMXCHK(flac_in_check(fn, bytes, info, encoding));
+    if (!d_file || !d_out || !d_status || !d_work || !ms)
+        return fail(DMX_ERR_ARG, "%s: null pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    hipEvent_t ev[6] = {};
+    int rc = DMX_OK;
+    for (hipEvent_t &e : ev)
+        if (hipEventCreate(&e) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+    if (rc == DMX_OK && launch_flac_decode((const unsigned char *)d_file, bytes, info, encoding, d_out, (long long *)d_status, d_work,
+                                           (hipStream_t)stream, ev) != 0)
+        rc = fail(DMX_ERR_ARG, "%s: info rejected", fn);
+    if (rc == DMX_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    for (int k = 0; rc == DMX_OK && k < 5; ++k)
+        if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    for (hipEvent_t e : ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    return rc;
+}
+
+// tracks given as .flac files: every file is probed before any GPU work, then the request is dmx_tracks_infer_remix's or
+// dmx_tracks_infer_flac's with the tracks decoded in their slots (tracks_upload)
+extern "C" int dmx_tracks_infer_from_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                          const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                          const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                          float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user)
+{
+    const char *fn = "dmx_tracks_infer_from_flac";
+    if (n_tracks < 1)
+        return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
+    if (!files || !file_bytes || !track_status)
+        return fail(DMX_ERR_ARG, "%s: null %s array", fn, !files ? "files" : !file_bytes ? "file_bytes" : "track_status");
+    std::vector<dmx_flac_info> infos((size_t)n_tracks);
+    std::vector<int64_t> ns((size_t)n_tracks);
+    for (int t = 0; t < n_tracks; ++t)
+    {
+        if (!files[t])
+            return fail(DMX_ERR_ARG, "%s: track %d: null file pointer", fn, t);
+        char msg[160];
+        if (flac_in_probe(files[t], file_bytes[t], &infos[(size_t)t], msg, sizeof msg) != 0)
+            return fail(DMX_ERR_FORMAT, "%s: track %d: %s", fn, t, msg);
+        if (infos[(size_t)t].sample_rate != 44100)
+            return fail(DMX_ERR_ARG, "%s: track %d: sample rate %d (the track path takes 44100; decode with dmx_flac_decode and resample)", fn,
+                        t, infos[(size_t)t].sample_rate);
+        if (flac_in_workspace_bytes(&infos[(size_t)t], file_bytes[t]) < 0)
+            return fail(DMX_ERR_FORMAT, "%s: track %d: block size range %d..%d is not supported", fn, t, infos[(size_t)t].min_block,
+                        infos[(size_t)t].max_block);
+        ns[(size_t)t] = infos[(size_t)t].total_samples;
+    }
+    TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
+    if (flac_out)
+        a.kind = TRACKS_OUT_FLAC, a.flacRate = 44100, a.flacSizes = sizes;
+    a.n_tracks = n_tracks, a.audio = reinterpret_cast<const float *const *>(files), a.n = ns.data();
+    a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.flacIn = infos.data(), a.fileBytes = file_bytes, a.trackStatus = track_status;
+    a.out = out, a.peaks = peaks, a.layout = DMX_LAYOUT_EIGEN, a.progress = progress, a.user = user;
+    for (int t = 0; t < 2 * n_tracks; ++t)
+        track_status[t] = -1;
+    DMXCHK(tracks_call(a));
+    for (int t = 0; t < n_tracks; ++t)
+        if (track_status[2 * t] != DMX_FLAC_OK)
+            return fail(DMX_ERR_FORMAT, "%s: track %d: %s at sample %lld of %lld (the samples from there on were taken as silence)", fn, t,
+                        track_status[2 * t] == DMX_FLAC_BROKEN ? "the stream breaks" : "too many frame header look-alikes, nothing decoded",
+                        (long long)track_status[2 * t + 1], (long long)ns[(size_t)t]);
+    return DMX_OK;
 }
 
 // --------------------------------------------------------------------------- debug

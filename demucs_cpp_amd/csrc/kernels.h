@@ -409,6 +409,20 @@ struct RemixTable
 };
 void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s);
 void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// ---- the FLAC input stage (flac_in.hip; specification: DESIGN.md section 2.12, restated in tests/flac_in_spec.py) ----
+} // namespace dmx
+struct dmx_flac_info;
+namespace dmx
+{
+// 0 and *info, or -1 and a message (pure host)
+int flac_in_probe(const void *file, int64_t bytes, dmx_flac_info *info, char *msg, size_t msgLen);
+// -1: an info the kernels do not take
+int64_t flac_in_workspace_bytes(const dmx_flac_info *info, int64_t bytes);
+// five launches on s; out 16-byte aligned and padded to 16 bytes, status {DMX_FLAC_*, good}, work 16-byte aligned; -1 as above
+// (marks: NULL, or six events recorded around the five launches)
+int launch_flac_decode(const unsigned char *file, long long bytes, const dmx_flac_info *info, int encoding, void *out, long long *status,
+                       void *work, hipStream_t s, hipEvent_t *marks = nullptr);
+
 // ---- the FLAC output stage (flac.hip; specification: DESIGN.md section 2.11, restated in tests/flac_spec.py) ----
 // an upper bound of the encoded stream of n frames of `bits` (16 | 24) bit stereo, a multiple of 16; -1: bad argument
 i64 flac_bound(int bits, i64 n);

@@ -399,6 +399,8 @@ struct remix_options
     bool flac = false;
     int sample_rate = 44100;
 };
+// the image of a .flac file, for the overloads that take tracks as files (dmx_tracks_infer_from_flac)
+using FlacFile = std::vector<unsigned char>;
 // demucs's --two-stems NAME with --other-method add | minus | none (DMX_OTHER_*): outputs "NAME" and, except for none,
 // "no_NAME" (add: the other stems added; minus: mixture - stem). Throws std::invalid_argument with the library's message.
 inline remix_options remix_two_stems(int nb_sources, int stem, int method)
@@ -588,6 +590,101 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
     }
     return out;
 }
+// the same on tracks given as the images of .flac files (dmx_tracks_infer_from_flac): ro.flac chooses the output form.
+// frames (optional) receives each track's sample count. A file the probe refuses, a rate other than 44100 Hz or a stream
+// that breaks inside ends the process with the library's message, which names the track.
+inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const *models, int Q, const float *w, int S,
+                                  const std::vector<FlacFile> &files, const std::vector<int> &shifts, const ProgressCallback &cb,
+                                  const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks,
+                                  std::vector<int64_t> *frames)
+{
+    const size_t T = files.size();
+    PcmOutputs out(T);
+    const int n_out = (int)ro.names.size();
+    if (ro.gains.size() != (size_t)n_out * (size_t)(S + 1))
+    {
+        std::cerr << who << ": " << ro.gains.size() << " gains for " << n_out << " outputs x (" << S << " stems + the mixture)" << std::endl;
+        std::exit(1);
+    }
+    const dmx_remix_spec spec{ro.encoding, ro.clip, n_out, ro.gains.data()};
+    if (dmx_remix_check(S, &spec) != DMX_OK)
+        die(who);
+    if (ro.flac && (ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24 || ro.sample_rate != 44100))
+    {
+        std::cerr << who << ": remix_options.flac needs encoding DMX_PCM_S16 or DMX_PCM_S24 and sample_rate 44100" << std::endl;
+        std::exit(1);
+    }
+    const dmx_output_spec ospec{ro.encoding, ro.clip, -1};
+    std::vector<const void *> in(T);
+    std::vector<int64_t> bytes(T), n(T), per(T);
+    std::vector<std::vector<unsigned char>> flat(T);
+    std::vector<void *> dst(T);
+    for (size_t t = 0; t < T; ++t)
+    {
+        dmx_flac_info info;
+        in[t] = files[t].data(), bytes[t] = (int64_t)files[t].size();
+        if (dmx_flac_probe(in[t], bytes[t], &info) != DMX_OK)
+        {
+            std::cerr << who << ": track " << t << ": " << dmx_last_error() << std::endl;
+            std::exit(1);
+        }
+        n[t] = info.total_samples;
+        per[t] = ro.flac ? dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]) : dmx_output_bytes(&ospec, n[t]);
+        if (per[t] < 0)
+            die(who);
+        flat[t].resize((size_t)(std::max<int64_t>(per[t], 1) * n_out));
+        dst[t] = flat[t].data();
+    }
+    std::vector<float> pk(T * (size_t)n_out, 0.0f);
+    std::vector<int64_t> sizes(T * (size_t)n_out, 0), status(2 * T, 0);
+    CbThunk th{&cb};
+    if (!c || dmx_tracks_infer_from_flac(c, models, Q, w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                         ro.flac ? 1 : 0, dst.data(), sizes.data(), pk.data(), status.data(), progress_thunk, &th) != DMX_OK)
+        die(who);
+    for (size_t t = 0; t < T; ++t)
+    {
+        for (int o = 0; o < n_out; ++o)
+            out[t].emplace_back(flat[t].begin() + (size_t)o * (size_t)per[t],
+                                flat[t].begin() + (size_t)o * (size_t)per[t] + (size_t)(ro.flac ? sizes[t * (size_t)n_out + o] : per[t]));
+        flat[t] = std::vector<unsigned char>();
+    }
+    if (peaks)
+    {
+        peaks->assign(T, std::vector<float>());
+        for (size_t t = 0; t < T; ++t)
+            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
+    }
+    if (frames)
+        *frames = n;
+    return out;
+}
+inline std::vector<int> engine_shifts(const char *who, const engine_model &model, size_t T, const inference_options &opts)
+{
+    const size_t N = (size_t)std::max(opts.shifts, 0);
+    std::vector<int> shifts(T * N, model.shift_offset);
+    if (opts.shift_offsets.size() == N)
+        for (size_t i = 0; i < shifts.size(); ++i)
+            shifts[i] = opts.shift_offsets[i % N];
+    else if (opts.shift_offsets.size() == T * N)
+        shifts = opts.shift_offsets;
+    else if (!opts.shift_offsets.empty())
+    {
+        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
+        std::exit(1);
+    }
+    return shifts;
+}
+inline PcmOutputs batch_call_from_flac(const char *who, const engine_model &model, const std::vector<FlacFile> &files,
+                                       const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
+                                       std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames)
+{
+    if (files.empty())
+        return PcmOutputs();
+    const std::vector<int> shifts = engine_shifts(who, model, files.size(), opts);
+    std::lock_guard<std::mutex> guard(model.lock);
+    return flac_files_call(who, dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, dmx_engine_n_sources(model.engine), files, shifts, cb,
+                           opts, ro, peaks, frames);
+}
 inline PcmOutputs batch_call_remix(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks,
                                    const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
                                    std::vector<std::vector<float>> *peaks)
@@ -616,6 +713,14 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const 
                                                std::vector<std::vector<float>> *peaks = nullptr)
 {
     return detail::batch_call_remix("demucs_inference_batch_remix", model, tracks, cb, opts, remix, peaks);
+}
+
+// tracks given as .flac files (44100 Hz; decoded on the GPU): frames (optional) receives each track's sample count
+inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<FlacFile> &files, ProgressCallback cb,
+                                               const inference_options &opts, const remix_options &remix,
+                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
+{
+    return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames);
 }
 
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
@@ -850,6 +955,19 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std:
     return detail::remix_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, tracks, shifts, cb, opts, remix,
                               peaks);
 }
+inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<FlacFile> &files, ProgressCallback cb,
+                                               const std::vector<float> &weights, const inference_options &opts, const remix_options &remix,
+                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
+{
+    const char *who = "demucs_inference_batch_remix (bag, flac files)";
+    if (files.empty())
+        return PcmOutputs();
+    const std::vector<int> shifts = detail::bag_shifts(who, bag, files.size(), opts);
+    const float *w = detail::bag_weights(who, bag, weights);
+    std::lock_guard<std::mutex> guard(bag.lock);
+    return detail::flac_files_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, files, shifts, cb, opts, remix,
+                                   peaks, frames);
+}
 
 // segment-level surface; src/model.hpp:569-647 (only the boundary members are kept:
 // `mix` in, `targets_out` out - every intermediate lives in the HBM arena)
@@ -1003,6 +1121,14 @@ inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_mod
                                                              std::vector<std::vector<float>> *peaks = nullptr)
 {
     return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix", model, tracks, cb, opts, remix, peaks);
+}
+inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<demucscpp::FlacFile> &files,
+                                                             ProgressCallback cb, const demucscpp::inference_options &opts,
+                                                             const demucscpp::remix_options &remix,
+                                                             std::vector<std::vector<float>> *peaks = nullptr,
+                                                             std::vector<int64_t> *frames = nullptr)
+{
+    return demucscpp::detail::batch_call_from_flac("demucs_v3_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

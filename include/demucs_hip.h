@@ -358,6 +358,58 @@ extern "C"
                               const dmx_remix_spec *spec, int sample_rate, void *const *out, int64_t *sizes, float *peaks, int layout,
                               dmx_progress_fn progress, void *user);
 
+    /* ---- tracks as FLAC (csrc/flac_in.hip; DESIGN.md section 2.12, restated in tests/flac_in_spec.py): native FLAC streams
+     * (RFC 9639) of 1 or 2 channels and 8, 12, 16, 20 or 24 bits, every subframe type (CONSTANT, VERBATIM, FIXED 0-4, LPC
+     * 1-32), both Rice methods with escapes, wasted bits, the four channel assignments, fixed and variable blocking. CRC-8
+     * and CRC-16 are verified on every frame; STREAMINFO's MD5 is NOT (it is serial over the whole stream). Out of scope,
+     * each refused by the probe with its own message: Ogg FLAC, more than 2 channels, 32-bit samples, unknown length. */
+    typedef struct dmx_flac_info
+    {
+        int sample_rate, channels, bits;
+        int64_t total_samples;              /* per channel, >= 1 */
+        int min_block, max_block;           /* STREAMINFO's block size range */
+        int min_frame, max_frame;           /* STREAMINFO's frame byte range (0: unknown) */
+        int variable_blocking;              /* the blocking strategy bit of the first frame */
+        int64_t first_frame;                /* byte offset of the first frame */
+    } dmx_flac_info;
+#define DMX_FLAC_OK 0                   /* every sample was delivered                                         */
+#define DMX_FLAC_BROKEN 1               /* the stream breaks at sample `good`: [good, n) is zero               */
+#define DMX_FLAC_TOO_MANY_CANDIDATES 2  /* more header look-alikes than 2 * ceil(n / min_block) + 1024: good = 0 */
+    /* pure host function, no GPU: skips an ID3v2 tag, checks "fLaC" and the metadata chain, reads STREAMINFO and locates the
+     * first frame. Every failure returns DMX_ERR_FORMAT (DMX_ERR_ARG for a NULL pointer) with its own dmx_last_error text. */
+    int dmx_flac_probe(const void *file, int64_t bytes, dmx_flac_info *info);
+    /* bytes of device workspace one dmx_flac_decode_device call needs (candidate masks and tables, two int32 planes of
+     * total_samples); -1 on an info the decoder does not take. Pure host function. */
+    int64_t dmx_flac_decode_workspace_bytes(const dmx_flac_info *info, int64_t bytes);
+    /* the file in device memory (d_file, `bytes` long, info from the probe) -> total_samples frames at d_out (16-byte
+     * aligned, DMX_OUTPUT_STRIDE(total_samples * frame bytes) large): DMX_PCM_F32 interleaved stereo (float)v / 2^(bits-1)
+     * with mono duplicated - the floats cli/wav.hpp gives for the same integers; DMX_PCM_S16 / DMX_PCM_S24 the bytes
+     * csrc/pcm.hip writes, only for a stereo stream of exactly that depth. d_status: two int64 ON THE DEVICE, {DMX_FLAC_*,
+     * good}: samples [0, good) are the stream's, [good, n) are zero. Asynchronous on `stream`, five launches, d_work
+     * (dmx_flac_decode_workspace_bytes, 16-byte aligned) needs no initialisation. */
+    int dmx_flac_decode_device(int device, const void *d_file, int64_t bytes, const dmx_flac_info *info, int encoding, void *d_out,
+                               int64_t *d_status, void *d_work, void *stream);
+    /* measurement aid: the same with HIP events around the five launches; synchronises `stream`; ms[0..5) receive the
+     * milliseconds of candidates, scan, chain, decode, finish */
+    int dmx_flac_decode_profile(int device, const void *d_file, int64_t bytes, const dmx_flac_info *info, int encoding, void *d_out,
+                                int64_t *d_status, void *d_work, void *stream, float *ms);
+    /* the same on host buffers: out holds total_samples * frame bytes, status two int64 */
+    int dmx_flac_decode(int device, const void *file, int64_t bytes, const dmx_flac_info *info, int encoding, void *out, int64_t *status);
+    /* dmx_tracks_infer_remix (flac_out == 0; sizes may be NULL) or dmx_tracks_infer_flac at 44100 Hz (flac_out != 0) on tracks
+     * given as the images of .flac files: files[t] of file_bytes[t] bytes. Every file is probed before any GPU work; a probe
+     * that fails, or a sample rate other than 44100, fails the call with a message that names the track, and nothing is
+     * written. n[t] is the file's total_samples (>= 2), which sizes out[t] as there. The file's bytes go up on the upload
+     * stream and are decoded in the track's slot (mono duplicated); the remix mixture is the decoded track. Damage inside
+     * the frames is only known on the device: track_status[2 t], [2 t + 1] receive {DMX_FLAC_*, good} of track t, its samples
+     * from `good` on are silence, every track runs to its end, and after all work has drained the call returns
+     * DMX_ERR_FORMAT naming the first damaged track; the other tracks' outputs are complete and what a call without the
+     * damaged track gives. Device memory: per track slot, on top of the output form's, the largest file and the largest
+     * dmx_flac_decode_workspace_bytes. */
+    int dmx_tracks_infer_from_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                   const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                   const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                   float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
