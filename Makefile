@@ -16,7 +16,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
 OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o attention.o attention_split.o resample.o pcm.o flac.o flac_in.o v3.o api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp op_step plan_harness att_harness flac_in_host harness micro
+all: $(LIB) cli oracle interp op_step plan_harness att_harness flac_in_host flac_host harness micro
 
 build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
@@ -66,6 +66,17 @@ $(FLAC_IN_OUT): tests/flac_in_host_main.cpp $(CSRC)/flac_in.hip include/demucs_h
 flac_in_host_asan:
 	$(MAKE) flac_in_host FLAC_IN_OUT=tests/_build/flac_in_host_main_asan CXXFLAGS_FLAC_IN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 
+# the FLAC output stage's kernel text (csrc/flac.hip) as host code in a stand-alone CPU program (tests/test_flac_lpc_cpu.py;
+# CXXFLAGS_FLAC=-fsanitize=address,undefined FLAC_OUT=... builds the sanitizer form, as flac_host_asan does). Contraction is
+# off, as it is in the kernel's Levinson-Durbin and quantisation: every binary64 operation is rounded once
+FLAC_OUT ?= tests/_build/flac_host_main
+flac_host: $(FLAC_OUT)
+$(FLAC_OUT): tests/flac_host_main.cpp $(CSRC)/flac.hip
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off -DDMX_FLAC_HOST $(CXXFLAGS_FLAC) -o $@ tests/flac_host_main.cpp
+flac_host_asan:
+	$(MAKE) flac_host FLAC_OUT=tests/_build/flac_host_main_asan CXXFLAGS_FLAC="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
+
 # GPU test harnesses of the C++ shim (re-entrancy; Eigen-typed overloads against tests/eigen_stub, which is NOT Eigen)
 harness: tests/_build/shim_harness tests/_build/shim_harness_eigen tests/_build/wav_harness tests/_build/pcm_wav_harness tests/_build/remix_parse_harness
 tests/_build/remix_parse_harness: tests/remix_parse_harness.cpp $(LIB) demucs_cpp_amd/host/demucscpp_hip.hpp
@@ -104,7 +115,7 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp op_step plan_harness att_harness flac_in_host flac_in_host_asan harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:

@@ -1,7 +1,7 @@
 // demucs_batch.cpp.main — many tracks in one call (no reference counterpart: the reference's CLIs take one file):
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
-//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--bag-weights w00,w01,...]
+//                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a 44.1 kHz FLAC
 // file the files go to the GPU as they are and are decoded there (dmx_tracks_infer_from_flac; csrc/flac_in.hip) - the outputs
@@ -36,6 +36,8 @@
 //   --flac                   write target_*.flac instead of target_*.wav (demucs's option; it takes no value): the same samples,
 //                            losslessly coded on the GPU (dmx_tracks_infer_flac; csrc/flac.hip), 16 bit by default, 24 bit
 //                            with --int24; --float32 --flac is an error. It combines with every option above and with bags.
+//   --flac-level N           with --flac: 0 (default) FIXED predictors alone, 1 adds an LPC predictor of order 8, 2 orders 8
+//                            and 12 (smaller files, the same samples); without --flac it changes nothing
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
 // They are refused for a track that DMX_RESAMPLE=1 converted: converting the stems back needs them in fp32.
 // <model> may also be a bag of models (dmx_tracks_infer_bag through the demucscpp::demucs_bag overloads; every option
@@ -62,7 +64,7 @@ using namespace demucscpp;
 {
     std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
-              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--bag-weights w00,w01,...]"
+              << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
@@ -105,6 +107,7 @@ int main(int argc, const char **argv)
     bool with_opts = false, with_out_opts = false, flac = false, float32_given = false;
     std::string two_stems, remix_text;
     int other_method = -1; // DMX_OTHER_*, -1: not given
+    int flac_level = 0;
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -131,6 +134,12 @@ int main(int argc, const char **argv)
             if (stem_index(val) < 0)
                 usage(argv[0]);
             two_stems = val, out_opts.two_stems = stem_index(val), with_out_opts = true;
+            continue;
+        }
+        if (opt == "--flac-level") // the level alone asks for nothing: without --flac it is not used
+        {
+            if (!parse_int(val, 0, 2, flac_level))
+                usage(argv[0]);
             continue;
         }
         if (opt == "--other-method")
@@ -267,7 +276,7 @@ int main(int argc, const char **argv)
             std::cerr << (remix_text.empty() ? "--other-method: " : "--remix: ") << e.what() << std::endl;
             exit(1);
         }
-        remix.encoding = out_opts.encoding, remix.clip = out_opts.clip, remix.flac = flac;
+        remix.encoding = out_opts.encoding, remix.clip = out_opts.clip, remix.flac = flac, remix.flac_level = flac_level;
         if (!with_out_opts) // FLAC inputs without an output option: the float32 stems, through unit gains
             remix.encoding = DMX_PCM_F32, remix.clip = DMX_CLIP_NONE;
     };

@@ -41,6 +41,7 @@ EXPORTS = [
     "dmx_bag_weights", "dmx_tracks_infer_bag",
     "dmx_remix_two_stems", "dmx_remix_check", "dmx_tracks_infer_remix", "dmx_remix_encode_device", "dmx_remix_encode",
     "dmx_flac_bound", "dmx_flac_workspace_bytes", "dmx_flac_encode_device", "dmx_flac_encode", "dmx_tracks_infer_flac",
+    "dmx_flac_encode_device_level", "dmx_flac_encode_level", "dmx_flac_encode_device_timed", "dmx_ctx_set_flac_level", "dmx_ctx_flac_level",
     "dmx_flac_probe", "dmx_flac_decode_workspace_bytes", "dmx_flac_decode_device", "dmx_flac_decode", "dmx_tracks_infer_from_flac", "dmx_flac_decode_profile",
 ]
 
@@ -157,6 +158,11 @@ def lib():
         L.dmx_flac_workspace_bytes.restype = i64
         L.dmx_flac_encode_device.argtypes = [ci, vp, ci, i64, ci, vp, vp, vp, vp]
         L.dmx_flac_encode.argtypes = [ci, vp, ci, i64, ci, vp, vp]
+        L.dmx_flac_encode_device_level.argtypes = [ci, vp, ci, i64, ci, ci, vp, vp, vp, vp]
+        L.dmx_flac_encode_level.argtypes = [ci, vp, ci, i64, ci, ci, vp, vp]
+        L.dmx_flac_encode_device_timed.argtypes = [ci, vp, ci, i64, ci, ci, vp, vp, vp, vp, vp]
+        L.dmx_ctx_set_flac_level.argtypes = [vp, ci]
+        L.dmx_ctx_flac_level.argtypes = [vp]
         L.dmx_flac_probe.argtypes = [vp, i64, vp]
         L.dmx_flac_decode_workspace_bytes.argtypes = [vp, i64]
         L.dmx_flac_decode_workspace_bytes.restype = i64
@@ -302,6 +308,16 @@ class Context:
     @property
     def arena_bytes(self) -> int:
         return lib().dmx_ctx_arena_bytes(self.h)
+
+    @property
+    def flac_level(self) -> int:
+        """the compression level of tracks_flac() and tracks_from_flac(flac_out=True): 0 (default) FIXED predictors alone,
+        1 + LPC order 8, 2 + LPC orders 8 and 12 (dmx_ctx_set_flac_level)"""
+        return lib().dmx_ctx_flac_level(self.h)
+
+    @flac_level.setter
+    def flac_level(self, level: int):
+        _chk(lib().dmx_ctx_set_flac_level(self.h, int(level)))
 
     def synchronize(self):
         _chk(lib().dmx_ctx_synchronize(self.h))
@@ -840,9 +856,10 @@ def flac_bound(bits: int, n: int) -> int:
     return b
 
 
-def flac_encode(pcm: np.ndarray, bits: int, sample_rate: int = 44100, device: int = 0) -> bytes:
-    """The FLAC stage alone (dmx_flac_encode): pcm as the PCM stage returns it - np.int16 (n, 2) for bits 16, np.uint8
-    (n, 2, 3) for bits 24 - -> the bytes of the .flac file."""
+def flac_encode(pcm: np.ndarray, bits: int, sample_rate: int = 44100, device: int = 0, level: int = 0) -> bytes:
+    """The FLAC stage alone (dmx_flac_encode / dmx_flac_encode_level): pcm as the PCM stage returns it - np.int16 (n, 2) for
+    bits 16, np.uint8 (n, 2, 3) for bits 24 - -> the bytes of the .flac file. level 0 | 1 | 2: FIXED predictors alone, + LPC
+    order 8, + LPC orders 8 and 12."""
     pcm = np.ascontiguousarray(pcm)
     if bits == 16:
         assert pcm.dtype == np.int16 and pcm.ndim == 2 and pcm.shape[1] == 2
@@ -851,7 +868,11 @@ def flac_encode(pcm: np.ndarray, bits: int, sample_rate: int = 44100, device: in
     n = pcm.shape[0]
     out = np.zeros(max(lib().dmx_flac_bound(int(bits), n), 1), np.uint8)
     size = ctypes.c_int64(0)
-    _chk(lib().dmx_flac_encode(device, pcm.ctypes.data, int(bits), n, int(sample_rate), out.ctypes.data, ctypes.byref(size)))
+    if level == 0:
+        _chk(lib().dmx_flac_encode(device, pcm.ctypes.data, int(bits), n, int(sample_rate), out.ctypes.data, ctypes.byref(size)))
+    else:
+        _chk(lib().dmx_flac_encode_level(device, pcm.ctypes.data, int(bits), n, int(sample_rate), int(level), out.ctypes.data,
+                                         ctypes.byref(size)))
     return bytes(out[:size.value])
 
 

@@ -1572,7 +1572,7 @@ static int tracks_output_stage(TracksRun &r, int k)
             const dmx_ctx::TrackSlot &sl = r.slot(g.t);
             launch_flac_encode((const unsigned char *)sl.pcm.p, DMX_OUTPUT_STRIDE(n * pcm->frameBytes), pcm->flacBits, n, pcm->flacRate,
                                pcm->nOut, (unsigned char *)sl.flac.p, flac_bound(pcm->flacBits, n), (long long *)sl.flacSizes.p,
-                               (unsigned char *)sl.flacWork.p, s);
+                               (unsigned char *)sl.flacWork.p, s, r.c->flacLevel);
         }
     HIPCHK(hipGetLastError());
     return DMX_OK;
@@ -2374,26 +2374,72 @@ static int flac_check(const char *fn, int bits, int64_t n, int sample_rate)
     return DMX_OK;
 }
 
-extern "C" int dmx_flac_encode_device(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, void *d_out, int64_t *d_size,
-                                      void *d_work, void *stream)
+static int flac_level_check(const char *fn, int level)
 {
-    const char *fn = "dmx_flac_encode_device";
+    if (level < 0 || level > 2)
+        return fail(DMX_ERR_ARG, "%s: level %d (0, 1 or 2)", fn, level);
+    return DMX_OK;
+}
+
+// marks: null, or four events recorded around the three launches (dmx_flac_encode_device_timed)
+static int flac_encode_device(const char *fn, int device, const void *d_pcm, int bits, int64_t n, int sample_rate, int level, void *d_out,
+                              int64_t *d_size, void *d_work, void *stream, hipEvent_t *marks)
+{
     DMXCHK(flac_check(fn, bits, n, sample_rate));
+    DMXCHK(flac_level_check(fn, level));
     if (!d_pcm || !d_out || !d_size || !d_work)
         return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_pcm ? "d_pcm" : !d_out ? "d_out" : !d_size ? "d_size" : "d_work");
     if (((uintptr_t)d_pcm & 15) != 0 || ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_size & 7) != 0)
         return fail(DMX_ERR_ARG, "%s: d_pcm and d_work must be 16-byte aligned, d_size 8-byte aligned", fn);
     HIPCHK(hipSetDevice(device));
     launch_flac_encode((const unsigned char *)d_pcm, 0, bits, n, sample_rate, 1, (unsigned char *)d_out, 0, (long long *)d_size,
-                       (unsigned char *)d_work, (hipStream_t)stream);
+                       (unsigned char *)d_work, (hipStream_t)stream, level, marks);
     HIPCHK(hipGetLastError());
     return DMX_OK;
 }
 
-extern "C" int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n, int sample_rate, void *out, int64_t *size)
+extern "C" int dmx_flac_encode_device(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, void *d_out, int64_t *d_size,
+                                      void *d_work, void *stream)
 {
-    const char *fn = "dmx_flac_encode";
+    return flac_encode_device("dmx_flac_encode_device", device, d_pcm, bits, n, sample_rate, 0, d_out, d_size, d_work, stream, nullptr);
+}
+extern "C" int dmx_flac_encode_device_level(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, int level, void *d_out,
+                                            int64_t *d_size, void *d_work, void *stream)
+{
+    return flac_encode_device("dmx_flac_encode_device_level", device, d_pcm, bits, n, sample_rate, level, d_out, d_size, d_work, stream,
+                              nullptr);
+}
+// measurement (tools/flac_bench.py): the call above, synchronised, with the three kernels' times between HIP events in ms[0..3)
+extern "C" int dmx_flac_encode_device_timed(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, int level, void *d_out,
+                                            int64_t *d_size, void *d_work, void *stream, float *ms)
+{
+    const char *fn = "dmx_flac_encode_device_timed";
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = DMX_OK;
+    for (int i = 0; i < 4 && rc == DMX_OK; ++i)
+        if (hipEventCreate(&ev[i]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+    if (rc == DMX_OK)
+        rc = flac_encode_device(fn, device, d_pcm, bits, n, sample_rate, level, d_out, d_size, d_work, stream, ev);
+    if (rc == DMX_OK && hipEventSynchronize(ev[3]) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    for (int i = 0; i < 3 && rc == DMX_OK; ++i)
+        if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    for (hipEvent_t e : ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    return rc;
+}
+
+static int flac_encode_host(const char *fn, int device, const void *pcm, int bits, int64_t n, int sample_rate, int level, void *out,
+                            int64_t *size)
+{
     DMXCHK(flac_check(fn, bits, n, sample_rate));
+    DMXCHK(flac_level_check(fn, level));
     if (!pcm || !out || !size)
         return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !pcm ? "pcm" : !out ? "out" : "size");
     HIPCHK(hipSetDevice(device));
@@ -2409,7 +2455,7 @@ extern "C" int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n,
     if (rc == DMX_OK && hipMemcpy(dIn, pcm, inBytes, hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(DMX_ERR_HIP, "%s: upload failed", fn);
     if (rc == DMX_OK)
-        rc = dmx_flac_encode_device(device, dIn, bits, n, sample_rate, dOut, dSize, dWork, nullptr);
+        rc = flac_encode_device(fn, device, dIn, bits, n, sample_rate, level, dOut, dSize, dWork, nullptr, nullptr);
     if (rc == DMX_OK && hipDeviceSynchronize() != hipSuccess)
         rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
     if (rc == DMX_OK && hipMemcpy(&got, dSize, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
@@ -2425,6 +2471,24 @@ extern "C" int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n,
         *size = got;
     return rc;
 }
+extern "C" int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n, int sample_rate, void *out, int64_t *size)
+{
+    return flac_encode_host("dmx_flac_encode", device, pcm, bits, n, sample_rate, 0, out, size);
+}
+extern "C" int dmx_flac_encode_level(int device, const void *pcm, int bits, int64_t n, int sample_rate, int level, void *out, int64_t *size)
+{
+    return flac_encode_host("dmx_flac_encode_level", device, pcm, bits, n, sample_rate, level, out, size);
+}
+
+extern "C" int dmx_ctx_set_flac_level(dmx_ctx *c, int level)
+{
+    if (!c)
+        return fail(DMX_ERR_ARG, "dmx_ctx_set_flac_level: null context");
+    DMXCHK(flac_level_check("dmx_ctx_set_flac_level", level));
+    c->flacLevel = level;
+    return DMX_OK;
+}
+extern "C" int dmx_ctx_flac_level(const dmx_ctx *c) { return c ? c->flacLevel : -1; }
 
 extern "C" int dmx_tracks_infer_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
                                      const float *const *audio, const int64_t *n, int n_shifts, float overlap, const int *shift_offsets,

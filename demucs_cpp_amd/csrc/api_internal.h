@@ -97,6 +97,7 @@ struct dmx_ctx
         hipEvent_t copied = nullptr; // on copyStream behind the last copy-out of the track that holds the slot (TracksPlan)
     };
     std::vector<TrackSlot> slots;
+    int flacLevel = 0; // dmx_ctx_set_flac_level: 0 FIXED predictors alone, 1 + LPC order 8, 2 + LPC orders 8 and 12
     hipStream_t uploadStream = nullptr;
     hipEvent_t evUpload = nullptr;
     float *dStats = nullptr;            // 4 floats

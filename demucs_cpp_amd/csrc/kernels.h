@@ -430,9 +430,10 @@ i64 flac_bound(int bits, i64 n);
 i64 flac_workspace_bytes(int bits, i64 n);
 // nOut outputs of interleaved PCM as pcm.hip writes it (output o at pcm + o*pcmStride, 16-byte aligned) -> nOut .flac files
 // (output o at out + o*outStride, any alignment), their byte counts in sizes[o]; work: nOut * flac_workspace_bytes, 16-byte
-// aligned. Three launches on s, no host synchronisation.
+// aligned. Three launches on s, no host synchronisation. level 0 | 1 | 2: FIXED predictors alone, + LPC order 8, + LPC orders 8
+// and 12 (tests/flac_lpc_spec.py). marks: null, or four events recorded around the three launches (tools/flac_bench.py).
 void launch_flac_encode(const unsigned char *pcm, i64 pcmStride, int bits, i64 n, int rate, int nOut, unsigned char *out, i64 outStride,
-                        long long *sizes, unsigned char *work, hipStream_t s);
+                        long long *sizes, unsigned char *work, hipStream_t s, int level = 0, hipEvent_t *marks = nullptr);
 // dst[r*dpitch + i] = src[r*spitch + i], r < rows, i < width (floats)
 void launch_copy_rows(float *dst, i64 dpitch, const float *src, i64 spitch, i64 width, int rows, hipStream_t s);
 // dst[i] = fp16 bit pattern of src[i], round to nearest even (the opt-in fp16 weight plane, api.cpp dmx_model_fp16_plane)

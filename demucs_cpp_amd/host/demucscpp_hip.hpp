@@ -147,6 +147,21 @@ struct CbThunk
 {
     const ProgressCallback *cb;
 };
+// remix_options::flac_level around one track call: the context's level is put back when the call has returned
+struct FlacLevelGuard
+{
+    dmx_ctx *c;
+    int before;
+    bool ok;
+    FlacLevelGuard(dmx_ctx *ctx, int level) : c(ctx), before(ctx ? dmx_ctx_flac_level(ctx) : 0), ok(ctx && dmx_ctx_set_flac_level(ctx, level) == DMX_OK) {}
+    ~FlacLevelGuard()
+    {
+        if (c)
+            (void)dmx_ctx_set_flac_level(c, before);
+    }
+    FlacLevelGuard(const FlacLevelGuard &) = delete;
+    FlacLevelGuard &operator=(const FlacLevelGuard &) = delete;
+};
 inline void progress_thunk(float p, const char *msg, void *user)
 {
     const ProgressCallback *cb = static_cast<CbThunk *>(user)->cb;
@@ -398,6 +413,9 @@ struct remix_options
     // DMX_PCM_S16 and 24 bit for DMX_PCM_S24 (DMX_PCM_F32 is refused); sample_rate is written into their headers
     bool flac = false;
     int sample_rate = 44100;
+    // the compression level of those files (dmx_ctx_set_flac_level, applied around the call and put back behind it):
+    // 0 FIXED predictors alone, 1 + LPC order 8, 2 + LPC orders 8 and 12; it means nothing without flac
+    int flac_level = 0;
 };
 // the image of a .flac file, for the overloads that take tracks as files (dmx_tracks_infer_from_flac)
 using FlacFile = std::vector<unsigned char>;
@@ -561,7 +579,8 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
     if (ro.flac)
     {
         std::vector<int64_t> sizes(T * (size_t)n_out, 0);
-        if (!c || dmx_tracks_infer_flac(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+        FlacLevelGuard level(c, ro.flac_level);
+        if (!c || !level.ok || dmx_tracks_infer_flac(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
                                         ro.sample_rate, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
             die(who);
         for (size_t t = 0; t < T; ++t)
@@ -638,7 +657,8 @@ inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const 
     std::vector<float> pk(T * (size_t)n_out, 0.0f);
     std::vector<int64_t> sizes(T * (size_t)n_out, 0), status(2 * T, 0);
     CbThunk th{&cb};
-    if (!c || dmx_tracks_infer_from_flac(c, models, Q, w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+    FlacLevelGuard level(c, ro.flac ? ro.flac_level : 0);
+    if (!c || !level.ok || dmx_tracks_infer_from_flac(c, models, Q, w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
                                          ro.flac ? 1 : 0, dst.data(), sizes.data(), pk.data(), status.data(), progress_thunk, &th) != DMX_OK)
         die(who);
     for (size_t t = 0; t < T; ++t)

@@ -329,7 +329,12 @@ extern "C"
      * Rice coding (partition order <= 4, no escape code) and the four stereo decorrelations - every choice by exact bit
      * counts with stated tie-breaks, so the bytes are reproducible anywhere. sample_rate (1 .. 655350) is carried in the
      * headers only; rates other than 44100 / 48000 are written as "from STREAMINFO", which is legal but outside the
-     * streamable subset. Out of scope: LPC predictors, wasted-bits detection, MD5, seek tables, tags, mono / multichannel. */
+     * streamable subset. A compression LEVEL (tests/flac_lpc_spec.py) adds LPC candidates behind the FIXED orders: level 0
+     * (the default everywhere) none, level 1 order 8, level 2 orders 8 and 12 - an integer Welch window, exact int64
+     * autocorrelation, Levinson-Durbin in binary64 with a fixed operation order and no contraction, 12 / 15 bit coefficients
+     * with error feedback, chosen by the same exact bit counts, so a frame never grows with the level and the bound and the
+     * workspace stand unchanged. Out of scope: wasted-bits detection, MD5, orders above 12, escape-coded partitions, variable
+     * block sizes, seek tables, tags, mono / multichannel. */
     /* an upper bound of the file for n frames of `bits` (16 | 24): 42 + 18 * ceil(n / 4096) + n * 2 * bits / 8, rounded up to
      * 16. Pure host function; -1 on a bad argument (bits, n < 1, n >= 2^36). */
     int64_t dmx_flac_bound(int bits, int64_t n);
@@ -343,6 +348,19 @@ extern "C"
                                void *d_work, void *stream);
     /* the same on host buffers: out holds dmx_flac_bound(bits, n) bytes, *size receives the file's byte count */
     int dmx_flac_encode(int device, const void *pcm, int bits, int64_t n, int sample_rate, void *out, int64_t *size);
+    /* the two calls above at a compression level (0: their bytes; 1: + LPC order 8; 2: + LPC orders 8 and 12). A level
+     * outside [0, 2] is DMX_ERR_ARG before any GPU work. */
+    int dmx_flac_encode_device_level(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, int level, void *d_out,
+                                     int64_t *d_size, void *d_work, void *stream);
+    int dmx_flac_encode_level(int device, const void *pcm, int bits, int64_t n, int sample_rate, int level, void *out, int64_t *size);
+    /* measurement: dmx_flac_encode_device_level, synchronised, with the times of its three kernels (frames, scan, compact)
+     * between HIP events in ms[0..3) */
+    int dmx_flac_encode_device_timed(int device, const void *d_pcm, int bits, int64_t n, int sample_rate, int level, void *d_out,
+                                     int64_t *d_size, void *d_work, void *stream, float *ms);
+    /* the level that dmx_tracks_infer_flac and dmx_tracks_infer_from_flac with flac_out use on this context (default 0);
+     * the getter returns -1 for a NULL context */
+    int dmx_ctx_set_flac_level(dmx_ctx *c, int level);
+    int dmx_ctx_flac_level(const dmx_ctx *c);
     /* dmx_tracks_infer_remix whose outputs leave as .flac files: the same arguments plus sample_rate and sizes. out[t]: n_out
      * chunks at a stride of dmx_flac_bound(bits, n[t]); sizes[t * n_out + o]: the byte count of track t's output o; the PCM
      * behind a file is the bytes dmx_tracks_infer_remix returns for the same arguments (bits 16 for DMX_PCM_S16, 24 for
