@@ -14,7 +14,7 @@ NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
 QUIET := 2> >(grep -v "packed-fp32-ops' is not a recognized feature" >&2)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(NOPK)
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
-OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o attention.o attention_split.o resample.o pcm.o flac.o flac_in.o v3.o api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
+OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
 all: $(LIB) cli oracle interp op_step plan_harness att_harness flac_in_host flac_host harness micro
 
@@ -63,7 +63,8 @@ flac_in_host: $(FLAC_IN_OUT)
 $(FLAC_IN_OUT): tests/flac_in_host_main.cpp $(CSRC)/flac_in.hip include/demucs_hip.h
 	@mkdir -p $(dir $@)
 	g++ -O1 -g -std=c++17 -Wall -DDMX_FLAC_IN_HOST $(CXXFLAGS_FLAC_IN) -o $@ tests/flac_in_host_main.cpp
-flac_in_host_asan:
+# (the plain form comes with it: the tests that run either of them build through this target)
+flac_in_host_asan: flac_in_host
 	$(MAKE) flac_in_host FLAC_IN_OUT=tests/_build/flac_in_host_main_asan CXXFLAGS_FLAC_IN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 
 # the FLAC output stage's kernel text (csrc/flac.hip) as host code in a stand-alone CPU program (tests/test_flac_lpc_cpu.py;
@@ -120,8 +121,8 @@ clean:
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:
 	@mkdir -p build/$(NAME)
-	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc attention attention_split resample pcm flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
-	for f in api engine plan model_pack tracks_plan gemm_select; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -x hip -c $(CSRC)/$$f.cpp -o build/$(NAME)/$$f.o & done; wait
+	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc tracks attention attention_split resample pcm flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
+	for f in api exec tracks_exec codec_api debug_api engine plan model_pack tracks_plan gemm_select; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -x hip -c $(CSRC)/$$f.cpp -o build/$(NAME)/$$f.o & done; wait
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o demucs_cpp_amd/lib/libdemucs_hip_$(NAME).so build/$(NAME)/*.o
 # one file rebuilt with other flags, the rest of the product's objects unchanged:
 #   make variant1 NAME=fftnoslp FILE=fft FLAGS=-fno-slp-vectorize   ->  demucs_cpp_amd/lib/libdemucs_hip_fftnoslp.so

@@ -1,4 +1,5 @@
-// api_internal.h — host-side state shared by api.cpp (single-context C ABI) and engine.cpp
+// api_internal.h — host-side state shared by the units of the single-context C ABI (api.cpp: models and contexts; exec.cpp:
+// the plan executor; tracks_exec.cpp: the track path; codec_api.cpp: the codecs; debug_api.cpp) and engine.cpp
 // (multi-device / multi-model scheduler). Nothing here crosses the C ABI.
 #pragma once
 #include "../../include/demucs_hip.h"
@@ -14,6 +15,7 @@
 int dmx_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 const std::string &dmx_err_string();         // last error of the calling thread
 void dmx_set_err_string(const std::string &); // adopt an error produced on another thread
+#define fail dmx_fail
 
 #define HIPCHK(expr)                                                                                              \
     do                                                                                                            \
@@ -132,6 +134,25 @@ struct dmx_ctx
     ~dmx_ctx();
 };
 
+// the device scratch of a host convenience wrapper: freed when the wrapper returns, whichever way it does
+struct DevScratch
+{
+    void *held[4];
+    int n = 0;
+    bool ok = true; // no hipMalloc has failed; after a failure nothing more is attempted
+    void *get(size_t bytes)
+    {
+        void *p = nullptr;
+        ok = ok && n < 4 && hipMalloc(&p, bytes) == hipSuccess;
+        return ok ? held[n++] = p : nullptr;
+    }
+    ~DevScratch()
+    {
+        while (n > 0)
+            (void)hipFree(held[--n]);
+    }
+};
+
 // bf16 <-> fp32 on the host (round to nearest even; the weight planes of the exact-split GEMM path)
 static inline unsigned short dmx_bf16_rn(float f)
 {
@@ -161,6 +182,18 @@ static inline bool dmx_split_weight(float w, unsigned short &w1, unsigned short 
 // every host-side wait on a context's results goes through this (a cooperative kernel whose bounded spin timed
 // out must never produce silently corrupt stems)
 int dmx_ctx_sync_checked(dmx_ctx *c);
+
+// ---- exec.cpp, used by api.cpp and debug_api.cpp
+dmx::GemmModelFacts dmx_model_facts(const dmx_model *m);       // what the kernel selection reads of a model (gemm_select.h)
+bool dmx_validate_gemm(const dmx::Op &op, std::string &why);  // one OP_IGEMM: staging alignment + kernel availability
+bool dmx_validate_plan(const dmx::Plan &p, std::string &why); // every OP_IGEMM of a plan
+dmx::Plan *dmx_get_plan(dmx_ctx *c, int batch);               // the context's plan for `batch`, built and chosen on first use
+int dmx_launch_op(const dmx_ctx *c, const dmx::Op &op, hipStream_t s, dmx::i64 zeroOff); // one op of a plan on stream s
+namespace dmx { extern std::mutex g_graphMutex; }             // every HIP graph API call of the process holds it
+// ---- tracks_exec.cpp, used by codec_api.cpp
+int dmx_pcm_check_spec(const char *fn, const dmx_output_spec *spec, int S); // S < 0: the model is not known yet
+int dmx_pcm_frame_bytes(int encoding);                                      // bytes of one stereo frame
+int dmx_remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, dmx::PcmGains *G, bool noModel);
 
 // ---- internal entry points used by engine.cpp
 int dmx_ensure_buf(DevBuf &b, dmx::i64 floats);

@@ -1,4 +1,4 @@
-// gemm_select.h — which kernel runs an OP_IGEMM: decided once, on the host, when the op's plan is built (api.cpp get_plan), from plan
+// gemm_select.h — which kernel runs an OP_IGEMM: decided once, on the host, when the op's plan is built (exec.cpp dmx_get_plan), from plan
 // fields and a few facts about the model. The launchers (igemm.hip, dgemm.hip, igemm_lin256.hip, igemm_split.hip) launch what was
 // chosen; the per-op profile labels (dmx_debug_profile, bench.py's roofline classes) are the choice's. No HIP here: plain C++.
 #pragma once

@@ -121,7 +121,7 @@ int refine_cfg(int cfg, i64 M, int N, bool stat)
 }
 
 // The shapes of the two tiles finish() reaches from another tile by the ROW COUNT of a launch: everything but that count (the
-// debug entry points of api.cpp run an op on them at small sizes).
+// debug entry points of debug_api.cpp run an op on them at small sizes).
 // cfg 19 (igemm_lin256.hip, same conditions as its lin256_ok): plain linear layers; N a multiple of 512 only: with three column
 // tiles (N = 384: the channel up / down samplers) half as many, twice as large workgroups quantise worse on the 64 slots of an XCD
 // than they gain (measured 126 -> 115, 121 -> 111 TFLOP/s)

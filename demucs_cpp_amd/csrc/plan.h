@@ -81,7 +81,7 @@ enum StatsMode
     MODE_ZNORM = 1,
 };
 
-// Which kernel runs an OP_IGEMM (gemm_select.h select_gemm decides, api.cpp get_plan stores it in the op)
+// Which kernel runs an OP_IGEMM (gemm_select.h select_gemm decides, exec.cpp dmx_get_plan stores it in the op)
 enum GemmFamily
 {
     GF_NONE = 0,         // not chosen: plans outside a context (tests/cpu_interp.cpp)
@@ -142,7 +142,7 @@ struct IGemm
     int trS, trOff;           // EPI_TRCONV: n = (r, co), r < trS; output position j = trS*p0 + r - trOff
                               // (k8/s4 with the 2-sample crop: 4, 2; v3's uncropped k8/s4: 4, 0; k4/s2: 2, 0)
     int cfg;                  // tile configuration index (engine)
-    GemmChoice choice;        // the kernel that runs the op in its context (api.cpp get_plan)
+    GemmChoice choice;        // the kernel that runs the op in its context (exec.cpp dmx_get_plan)
     // EPI_KPL / EPI_VT: A (float offset) of three bf16 planes of B*kvT*(kvH*kvHs) elements each; rows are tokens (P1 = kvT,
     // P0 = 1), kvT a multiple of 64; -1 otherwise
     i64 kv;
@@ -201,10 +201,10 @@ struct Attention
     i64 qBatch, kBatch, vBatch, oBatch; // batch strides (elements)
     int B, Tq, Tk, H, hs;
     float scale; // 1/sqrt(hs)
-    int split;   // GEMM_BF16X3 contexts (api.cpp): run on the exact-split bf16 kernel (attention_split.hip)
+    int split;   // GEMM_BF16X3 contexts (exec.cpp dmx_get_plan): run on the exact-split bf16 kernel (attention_split.hip)
     i64 kpl = -1, vt = -1; // A: bf16 operand planes of K ([3][B][Tk][H*hs]) and V^T ([3][B][H][Tk/64][hs][64]) written by the
                            // projections (EPI_KPL / EPI_VT), or -1: the kernel splits fp32 k / v itself
-    int form = 0; // split ops: the AttentionForm (attention_select.h: wg64 / wg128 / pair) chosen when the plan is built (api.cpp get_plan)
+    int form = 0; // split ops: the AttentionForm (attention_select.h: wg64 / wg128 / pair) chosen when the plan is built (exec.cpp dmx_get_plan)
 };
 
 struct Istft

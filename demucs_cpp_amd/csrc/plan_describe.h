@@ -1,4 +1,4 @@
-// plan_describe.h — one op of a plan as a line of key=value words: what dmx_debug_op_info (api.cpp) reports and what
+// plan_describe.h — one op of a plan as a line of key=value words: what dmx_debug_op_info (debug_api.cpp) reports and what
 // tests/cpu_interp.cpp reports for its own plan, so that the two plans can be compared word by word. Plain C++, no HIP.
 #pragma once
 #include "attention_select.h"

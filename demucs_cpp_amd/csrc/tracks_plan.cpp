@@ -1,8 +1,8 @@
-// The plan of a multi-track call: host arithmetic only (tracks_plan.h). The executor is csrc/api.cpp.
+// The plan of a multi-track call: host arithmetic only (tracks_plan.h). The executor is csrc/tracks_exec.cpp.
 //
 // Several tracks: their segments are laid end to end in track order (global item index) and dealt in batches of
 // max_batch, so a batch may hold the tail of one track and the head of the next. Every kernel serves each of its tracks
-// exactly as it serves a track of its own (misc.hip), so every result is the bits of a call per track.
+// exactly as it serves a track of its own (tracks.hip), so every result is the bits of a call per track.
 // The shifts ensemble (N copies of each track, dmx_tracks_infer_opts): the items of a track are its copies' segments in
 // (row g, copy k) order, a copy absent from the rows past its last segment (the copies' segment counts differ when their
 // shifted lengths straddle a multiple of the stride), so the copies of one stretch of the track are adjacent.
@@ -50,7 +50,7 @@ int plan_fail(std::string &err, const char *fmt, long long a = 0, long long b = 
     return DMX_ERR_ARG;
 }
 
-// item index of (row g, copy k) within a track (misc.hip ens_item)
+// item index of (row g, copy k) within a track (tracks.hip ens_item)
 i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
 {
     if (g < nMin)

@@ -1,7 +1,7 @@
 // The host-only plan of a multi-track call (dmx_track_infer, dmx_tracks_infer*): everything the scheduler decides before
 // any GPU work, from plain numbers. No HIP: this header and tracks_plan.cpp use the standard library and
 // include/demucs_hip.h only, so the arithmetic can be built and checked without a GPU (tests/tracks_plan_harness.cpp).
-// The executor that enqueues a plan is csrc/api.cpp (tracks_run_impl).
+// The executor that enqueues a plan is csrc/tracks_exec.cpp (tracks_run_impl).
 #pragma once
 #include "../../include/demucs_hip.h"
 

@@ -3,7 +3,7 @@
 //   attention_select_harness barriers NTMAX
 //       one line per nt = 1 .. NTMAX: nt, barriers of half A, barriers of half B (att_pair_barriers)
 //   attention_select_harness plans MODEL SEG:BATCH:GEMM ...
-//       the plan a context of that GEMM mode builds (gemm_select.h build_chosen_plan, as api.cpp get_plan calls it; every weight
+//       the plan a context of that GEMM mode builds (gemm_select.h build_chosen_plan, as exec.cpp dmx_get_plan calls it; every weight
 //       exact), one line per OP_ATTENTION: seg batch gemm name Tq Tk H hs planes, then att_select_form under DMX_ATT_PAIR = 0, unset, 2
 //   attention_select_harness form TQ TK H B HS PLANES MODE
 //       att_select_form of a hand-made shape

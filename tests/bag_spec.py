@@ -1,5 +1,5 @@
 """NumPy restatement of the bag of models on the track path (include/demucs_hip.h dmx_tracks_infer_bag / dmx_bag_weights,
-csrc/misc.hip track_ola_bag_kernel).
+csrc/tracks.hip track_ola_bag_kernel).
 
 Notation: Q models of S stems, N shifted copies per model and track, weights w[q][s] >= 0. The shift of track t, model q,
 copy k is shift_offsets[(t*Q + q)*N + k]; NULL or -1 entries are rand() % 22050 drawn in that row-major order.

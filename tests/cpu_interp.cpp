@@ -1115,7 +1115,7 @@ static bool is_fp16_number(float x)
 }
 
 // The plan a context of GEMM mode `gemm` builds for the handle's model at segment length seg and batch B (gemm_select.h build_chosen_plan, as
-// api.cpp get_plan calls it), one line per OP_IGEMM: name, tile cfg, epilogue, hterms, family, arithmetic, wnf, label.
+// exec.cpp dmx_get_plan calls it), one line per OP_IGEMM: name, tile cfg, epilogue, hterms, family, arithmetic, wnf, label.
 // Model facts: both kinds of weight planes exist; BOTH inexact lists hold the blob elements that are not fp16 numbers (the fp16 list
 // of dmx_model_upload; every fp16 number is two-bf16-term exact, so it contains the bf16 list) plus all weights of the op named
 // `inexact` ("" = none).
@@ -1190,7 +1190,7 @@ extern "C" int interp_select_one(void *h, const char *name, int gemm, int linMod
 // the frames of the OP_ISTFT stepped just before it unrounded, as the fused GPU kernel does). tests/test_gpu_op_parity.py puts
 // each HIP kernel next to it; tests/test_op_reference_cpu.py checks the harness itself.
 
-// The plan a context of GEMM mode `gemm` builds (gemm_select.h build_chosen_plan, as api.cpp get_plan calls it: every weight of
+// The plan a context of GEMM mode `gemm` builds (gemm_select.h build_chosen_plan, as exec.cpp dmx_get_plan calls it: every weight of
 // the synthetic test models is an fp16 number, derived ones are listed as inexact), with an arena.
 extern "C" void *interp_create_chosen(const char *model_path, int64_t seg, int B, int gemm, int kvPlanes)
 {

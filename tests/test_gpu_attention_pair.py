@@ -3,7 +3,7 @@
 same order, so nothing may differ in a single bit: the plans' whole arenas after one run from the same canary (which also catches a
 store outside an op's rows), the stems, and repeated runs beside another context's work on the same GPU.
 
-DMX_ATT_PAIR is read when a plan is built (api.cpp get_plan): 2 = the paired kernel wherever it exists, 0 = never."""
+DMX_ATT_PAIR is read when a plan is built (exec.cpp dmx_get_plan): 2 = the paired kernel wherever it exists, 0 = never."""
 import threading
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""Bags of models on the multi-track path (include/demucs_hip.h dmx_tracks_infer_bag, csrc/misc.hip track_ola_bag_kernel,
+"""Bags of models on the multi-track path (include/demucs_hip.h dmx_tracks_infer_bag, csrc/tracks.hip track_ola_bag_kernel,
 binding Context.tracks_bag, the C++ shim's demucs_bag through cli/demucs_batch.cpp.main): the fine-tuned bag (stem i from
 model i) and weighted ensembles, with shifts, overlap and PCM output (run with -m gpu on an MI355X). The specification is
 restated in tests/bag_spec.py."""

@@ -62,7 +62,7 @@ class Pair:
         self.n_ops, self.ctx_floats, self.floats, self.consts = self.ctx.plan_info(B)
         self.gops = [self.ctx.op_info(B, i) for i in range(self.n_ops)]
         # a split context of a v4 model asks for K / V operand planes and falls back to the fp32-K/V form where a projection cannot
-        # take its exact-split kernel (api.cpp get_plan): the reference is built the same way
+        # take its exact-split kernel (exec.cpp dmx_get_plan): the reference is built the same way
         self.ref = R.Ref(L, tmp_models[key], seg, B, mode, mode != "f32" and key != 3)
         if self.ref.floats != self.floats and not any(o["kind"] == R.OP_ATTENTION and o.get("planes") for o in self.gops):
             self.ref.close()

@@ -313,7 +313,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu(model, port):
     root checks that the double-buffered gather + pipelined overlap-add of all ranks' segments is
     bit-identical to a local recomputation. Covers everything of the N > 1 bench path except the RCCL
     transport itself (the sharded track path has its own gloo test on CPU). v3: two PROCESSES issue the
-    cooperative LSTM kernel on one GPU - the launches take turns through the process-shared lane (api.cpp), a raised
+    cooperative LSTM kernel on one GPU - the launches take turns through the process-shared lane (exec.cpp), a raised
     status word would fail the run. ft: the bag's four models per rank and step, one gather per model - and the strong-scaling
     leg of configs[4]: ONE 4-minute track's 168 (model, segment) items dealt 84 per rank (cli-apps/demucs_ft.cpp:221-241),
     checked by the root against one rank alone; the line must carry track_strong_xRT / strong_ceiling for the bag."""
@@ -1011,7 +1011,7 @@ def test_shim_is_reentrant_and_eigen_overloads_match(dmx, tmp_models):
 
 def test_single_segment_graph_replay_is_bit_identical(dmx, tmp_models, monkeypatch):
     """Repeated small-batch calls with the same I/O buffers are replayed from a captured HIP graph
-    (csrc/api.cpp run_plan): same bits as eager launches (DMX_GRAPH=0), call after call."""
+    (csrc/exec.cpp run_plan): same bits as eager launches (DMX_GRAPH=0), call after call."""
     import torch
     rng = np.random.default_rng(77)
     mixes = (0.1 * rng.standard_normal((2, 2, 12000))).astype(np.float32)

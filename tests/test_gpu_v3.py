@@ -202,7 +202,7 @@ def test_v3_concurrent_contexts_at_full_batches_share_the_lstm_lane(dmx, tmp_mod
     """Four contexts on ONE GPU, each running a 42-segment batch at the same time (engine with logical devices
     [0, 0, 0, 0]): every launch of the cooperative LSTM kernel keeps 144 workgroups spinning on their partners and the
     device holds 512, so four unordered launches could starve each other's partners of slots (the bounded spin would
-    report an error). csrc/api.cpp orders the LSTM launches of a device in a lane; the result must be the single-context
+    report an error). csrc/exec.cpp orders the LSTM launches of a device in a lane; the result must be the single-context
     track, bit for bit, twice in a row."""
     stride = 257985
     nseg = 4 * 42

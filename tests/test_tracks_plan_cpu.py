@@ -1,5 +1,5 @@
 """The host-only plan of the multi-track path (demucs_cpp_amd/csrc/tracks_plan.cpp) without a GPU: the stand-alone
-tests/tracks_plan_harness.cpp prints the plan of a case as JSON, and every property the executor in csrc/api.cpp relies on
+tests/tracks_plan_harness.cpp prints the plan of a case as JSON, and every property the executor in csrc/tracks_exec.cpp relies on
 is recomputed here by brute force from the geometry alone (shift, stride, segment): which segments cover which samples,
 what has been dealt by which batch, which tracks are live. Nothing here restates the plan's own index arithmetic: the
 position of a (track, copy, row) in a model's sequence is looked up in the sequence the plan prints.
