@@ -16,7 +16,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
 OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp op_step plan_harness att_harness flac_in_host flac_host harness micro
+all: $(LIB) cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_host harness micro
 
 build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
@@ -50,6 +50,13 @@ plan_harness: tests/_build/tracks_plan_harness
 tests/_build/tracks_plan_harness: tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p tests/_build
 	g++ -O2 -std=c++17 -Wall -o $@ tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp
+# the same plan for tracks at other sample rates (native-rate ranges), printed by a program of its own (tests/test_track_rates_cpu.py;
+# CXXFLAGS_RATES=-fsanitize=address,undefined RATES_OUT=... builds the sanitizer form)
+RATES_OUT ?= tests/_build/track_rates_harness
+rates_harness: $(RATES_OUT)
+$(RATES_OUT): tests/track_rates_harness.cpp $(CSRC)/tracks_plan.cpp $(CSRC)/tracks_plan.h include/demucs_hip.h
+	@mkdir -p $(dir $@)
+	g++ -O2 -g -std=c++17 -Wall $(CXXFLAGS_RATES) -o $@ tests/track_rates_harness.cpp $(CSRC)/tracks_plan.cpp
 # the attention form rule (csrc/attention_select.h: host arithmetic, no HIP) over the plans a context builds, as a stand-alone CPU program
 att_harness: tests/_build/attention_select_harness
 tests/_build/attention_select_harness: tests/attention_select_harness.cpp $(CSRC)/attention_select.h $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp $(CSRC)/gemm_select.h
@@ -116,7 +123,7 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp op_step plan_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:

@@ -3,10 +3,10 @@
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
 //                         <model> <out dir> <wav or flac file>...
-// An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a 44.1 kHz FLAC
-// file the files go to the GPU as they are and are decoded there (dmx_tracks_infer_from_flac; csrc/flac_in.hip) - the outputs
-// are those of the equivalent WAV inputs; otherwise a FLAC file is decoded on the GPU (dmx_flac_decode) and treated as a
-// WAV file of its rate (DMX_RESAMPLE).
+// An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
+// (at 44.1 kHz, or with DMX_RESAMPLE=1 at any rate) the files go to the GPU as they are and are decoded there
+// (dmx_tracks_infer_from_flac, dmx_tracks_infer_from_flac_rates; csrc/flac_in.hip) - the outputs are those of the equivalent
+// WAV inputs; otherwise a FLAC file is decoded on the GPU (dmx_flac_decode) and treated as a WAV file of its rate (DMX_RESAMPLE).
 // -> <out dir>/<wav file stem>/target_{i}_{drums|bass|other|vocals|guitar|piano}.wav (stereo float32), every file
 // byte-identical to what demucs.cpp.main / demucs_v3.cpp.main writes for that input alone. The model's architecture
 // (HTDemucs v4 4s / 6s, or Demucs v3) is read from the file; the segments of all tracks share batches
@@ -39,7 +39,8 @@
 //   --flac-level N           with --flac: 0 (default) FIXED predictors alone, 1 adds an LPC predictor of order 8, 2 orders 8
 //                            and 12 (smaller files, the same samples); without --flac it changes nothing
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
-// They are refused for a track that DMX_RESAMPLE=1 converted: converting the stems back needs them in fp32.
+// A track at another rate (DMX_RESAMPLE=1) takes them at its own rate: the library converts inside the track path
+// (dmx_tracks_infer_rates, dmx_tracks_infer_from_flac_rates) and the outputs are the stems at the file's rate.
 // <model> may also be a bag of models (dmx_tracks_infer_bag through the demucscpp::demucs_bag overloads; every option
 // above still applies, and every model gets the same offsets, from --shift-offsets or DMX_SHIFT_OFFSET):
 //   a directory              scanned as demucs_ft.cpp.main scans it (file names containing htdemucs_ft_{drums,bass,other,
@@ -248,14 +249,16 @@ int main(int argc, const char **argv)
     // minus, none, --remix and --flac leave through the remix entry points; everything else as before
     const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE || flac;
     remix_options remix;
-    bool flac_in = false; // every input is a 44.1 kHz .flac file (decided once the inputs have been looked at)
+    bool flac_in = false; // every input is a .flac file the GPU takes as it is (decided once the inputs have been looked at):
+                          // at 44.1 kHz, or with DMX_RESAMPLE=1 at any rate
+    bool any_rate = false; // DMX_RESAMPLE=1 and an input at another rate: the tracks go to the library with their rates
     auto make_remix = [&](int nb_sources) { // once the model's stems are known
         if (with_out_opts && out_opts.two_stems >= nb_sources)
         {
             std::cerr << "--two-stems " << two_stems << ": the loaded model has no such stem (" << nb_sources << " sources)" << std::endl;
             exit(1);
         }
-        if (!with_remix && !flac_in)
+        if (!with_remix && !flac_in && !any_rate)
             return;
         try
         {
@@ -277,7 +280,7 @@ int main(int argc, const char **argv)
             exit(1);
         }
         remix.encoding = out_opts.encoding, remix.clip = out_opts.clip, remix.flac = flac, remix.flac_level = flac_level;
-        if (!with_out_opts) // FLAC inputs without an output option: the float32 stems, through unit gains
+        if (!with_out_opts) // FLAC inputs or other rates without an output option: the float32 stems, through unit gains
             remix.encoding = DMX_PCM_F32, remix.clip = DMX_CLIP_NONE;
     };
     if (!opts.shift_offsets.empty() && (int)opts.shift_offsets.size() != opts.shifts)
@@ -353,10 +356,11 @@ int main(int argc, const char **argv)
     }
     std::vector<StereoMatrix> tracks((size_t)n_files);
     std::vector<int> native_rate((size_t)n_files, SUPPORTED_SAMPLE_RATE); // != 44100 only with DMX_RESAMPLE=1 (wav.hpp)
-    std::vector<int64_t> native_frames((size_t)n_files, -1);
-    // FLAC inputs (the content decides, not the name). When EVERY input is a 44.1 kHz .flac file the bytes go to the GPU as
-    // they are (dmx_tracks_infer_from_flac); otherwise a .flac file is decoded on the GPU (dmx_flac_decode) and then takes
-    // the way of a WAV file of its rate.
+    // FLAC inputs (the content decides, not the name). When EVERY input is a .flac file - at 44.1 kHz, or with DMX_RESAMPLE=1
+    // at any rate - the bytes go to the GPU as they are (dmx_tracks_infer_from_flac, dmx_tracks_infer_from_flac_rates);
+    // otherwise a .flac file is decoded on the GPU (dmx_flac_decode) and then takes the way of a WAV file of its rate.
+    // With DMX_RESAMPLE=1 a track at another rate goes to the library as it is, with its rate (dmx_tracks_infer_rates): both
+    // conversions run inside the track path, and every output option applies to the stems at the file's rate.
     std::vector<FlacFile> flac_files((size_t)n_files);
     std::vector<int64_t> flac_frames;
     int n_flac = 0, n_flac_441 = 0;
@@ -386,29 +390,26 @@ int main(int argc, const char **argv)
         }
         n_flac_441 += info.sample_rate == SUPPORTED_SAMPLE_RATE;
     }
-    flac_in = n_flac == n_files && n_flac_441 == n_files;
+    const char *rs_env = std::getenv("DMX_RESAMPLE");
+    const bool resample = rs_env && std::atoi(rs_env) == 1;
+    flac_in = n_flac == n_files && (n_flac_441 == n_files || resample);
+    any_rate = flac_in && n_flac_441 != n_files;
+    // without DMX_RESAMPLE=1 another rate is refused here with the reference's message; with it the track stays at its rate
     for (int i = 0; i < n_files && !flac_in; ++i)
+    {
         if (!(flac_files[(size_t)i].empty()
-                  ? wavio::load_audio_file(argv[3 + i], tracks[(size_t)i], &native_rate[(size_t)i], &native_frames[(size_t)i])
-                  : wavio::load_flac_image(argv[3 + i], flac_files[(size_t)i], tracks[(size_t)i], &native_rate[(size_t)i],
-                                           &native_frames[(size_t)i])))
+                  ? wavio::load_audio_file(argv[3 + i], tracks[(size_t)i], &native_rate[(size_t)i], nullptr, true)
+                  : wavio::load_flac_image(argv[3 + i], flac_files[(size_t)i], tracks[(size_t)i], &native_rate[(size_t)i], nullptr, true)))
             exit(1);
-    if (with_out_opts)
-        for (int i = 0; i < n_files; ++i)
-            if (native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE)
-            {
-                std::cerr << "--two-stems / --other-method / --remix / --clip-mode / --int16 / --int24 / --float32 / --flac are not available for a track converted by "
-                          << "DMX_RESAMPLE=1 (" << argv[3 + i] << ", " << native_rate[(size_t)i]
-                          << " Hz): converting the stems back needs them in fp32" << std::endl;
-                exit(1);
-            }
+        any_rate = any_rate || native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE;
+    }
     std::cout << std::fixed << std::setprecision(3);
     ProgressCallback cb = [](float progress, const std::string &msg) {
         std::cout << "(" << std::setw(3) << std::setfill(' ') << progress * 100.0f << "%) " << msg << std::endl;
     };
     std::vector<StemTensor> outs;
     PcmOutputs pcm_outs;
-    auto remix_or = [&](int encoding) { return flac_in ? remix.encoding : encoding; };
+    auto remix_or = [&](int encoding) { return flac_in || any_rate ? remix.encoding : encoding; };
     int nb_sources = 4;
     if (bag_mode)
     {
@@ -440,8 +441,12 @@ int main(int argc, const char **argv)
         std::cout << "Starting Demucs bag (" << bag_files.size() << " models, " << nb_sources << "-source) inference of " << n_files
                   << " tracks" << std::endl;
         make_remix(nb_sources);
-        if (flac_in)
+        if (flac_in && any_rate)
+            pcm_outs = demucs_inference_batch_remix(bag, flac_files, native_rate, cb, weights, opts, remix, nullptr, &flac_frames);
+        else if (flac_in)
             pcm_outs = demucs_inference_batch_remix(bag, flac_files, cb, weights, opts, remix, nullptr, &flac_frames);
+        else if (any_rate)
+            pcm_outs = demucs_inference_batch_remix(bag, tracks, native_rate, cb, weights, opts, remix);
         else if (with_remix)
             pcm_outs = demucs_inference_batch_remix(bag, tracks, cb, weights, opts, remix);
         else if (with_out_opts)
@@ -459,8 +464,12 @@ int main(int argc, const char **argv)
         }
         std::cout << "Starting Demucs v3 MMI inference of " << n_files << " tracks" << std::endl;
         make_remix(nb_sources);
-        if (flac_in)
+        if (flac_in && any_rate)
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, native_rate, cb, opts, remix, nullptr, &flac_frames);
+        else if (flac_in)
             pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames);
+        else if (any_rate)
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, native_rate, cb, opts, remix);
         else if (with_remix)
             pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, cb, opts, remix);
         else if (with_out_opts)
@@ -480,8 +489,12 @@ int main(int argc, const char **argv)
         nb_sources = model.is_4sources ? 4 : 6;
         std::cout << "Starting Demucs (" << nb_sources << "-source) inference of " << n_files << " tracks" << std::endl;
         make_remix(nb_sources);
-        if (flac_in)
+        if (flac_in && any_rate)
+            pcm_outs = demucs_inference_batch_remix(model, flac_files, native_rate, cb, opts, remix, nullptr, &flac_frames);
+        else if (flac_in)
             pcm_outs = demucs_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames);
+        else if (any_rate)
+            pcm_outs = demucs_inference_batch_remix(model, tracks, native_rate, cb, opts, remix);
         else if (with_remix)
             pcm_outs = demucs_inference_batch_remix(model, tracks, cb, opts, remix);
         else if (with_out_opts)
@@ -495,13 +508,13 @@ int main(int argc, const char **argv)
         const StereoMatrix &audio = tracks[(size_t)f];
         std::filesystem::path p = std::filesystem::path(out_dir) / std::filesystem::path(argv[3 + f]).stem();
         std::filesystem::create_directories(p);
-        if (with_out_opts || flac_in) // the bytes are WAV data already
+        if (with_out_opts || flac_in || any_rate) // the bytes are WAV data already
         {
             const int64_t frames = flac_in ? flac_frames[(size_t)f] : audio.cols();
             const auto &po = pcm_outs[(size_t)f];
             for (size_t target = 0; target < po.size(); ++target)
             {
-                const std::string name = with_remix || flac_in    ? remix.names[target]
+                const std::string name = with_remix || flac_in || any_rate ? remix.names[target]
                                          : out_opts.two_stems < 0 ? names[target]
                                                                   : (target == 0 ? two_stems : "no_" + two_stems);
                 auto p_target = p / ("target_" + std::to_string(target) + "_" + name + (flac ? ".flac" : ".wav"));
@@ -514,7 +527,7 @@ int main(int argc, const char **argv)
                     ok = (bool)f;
                 }
                 else
-                    ok = wavio::write_pcm_file(po[target].data(), frames, remix_or(out_opts.encoding), p_target.string());
+                    ok = wavio::write_pcm_file(po[target].data(), frames, remix_or(out_opts.encoding), p_target.string(), native_rate[(size_t)f]);
                 if (!ok)
                 {
                     std::cerr << "Error writing " << p_target << std::endl;
@@ -534,7 +547,7 @@ int main(int argc, const char **argv)
                 wave[(size_t)(2 * i)] = out(target, 0, i);
                 wave[(size_t)(2 * i + 1)] = out(target, 1, i);
             }
-            if (!wavio::write_audio_file(wave.data(), audio.cols(), p_target.string(), native_rate[(size_t)f], native_frames[(size_t)f]))
+            if (!wavio::write_audio_file(wave.data(), audio.cols(), p_target.string())) // (every track is at 44.1 kHz here)
             {
                 std::cerr << "Error writing " << p_target << std::endl;
                 exit(1);

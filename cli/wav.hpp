@@ -33,8 +33,10 @@ inline int resample_device()
 // file when the track was converted (-1 otherwise): write_audio_file cuts the stems back to it (the round trip
 // ceil(ceil(N L/M) M/L) is up to a few samples longer than N, and a stem must line up with ITS source file - the count
 // travels with the caller, not in a process-wide variable, so several files may be in flight).
+// keep_native: such a track is NOT converted here; it comes back at the file's rate (native_frames = its frames), for a caller
+// that hands the rates to the library (the batch calls that take rates: both conversions run on the device, in the track path).
 inline bool load_audio_file(const std::string &filename, demucscpp::StereoMatrix &out, int *native_rate = nullptr,
-                            int64_t *native_frames = nullptr)
+                            int64_t *native_frames = nullptr, bool keep_native = false)
 {
     FILE *f = fopen(filename.c_str(), "rb");
     if (!f)
@@ -177,7 +179,12 @@ inline bool load_audio_file(const std::string &filename, demucscpp::StereoMatrix
         out(0, (int64_t)i) = l;
         out(1, (int64_t)i) = r;
     }
-    if (convert)
+    if (convert && keep_native)
+    {
+        if (native_frames)
+            *native_frames = (int64_t)N;
+    }
+    else if (convert)
     {
         const int64_t n441 = dmx_resample_length((int64_t)N, (int)rate, demucscpp::SUPPORTED_SAMPLE_RATE);
         demucscpp::StereoMatrix conv(n441);
@@ -223,7 +230,7 @@ inline bool is_flac_image(const std::vector<uint8_t> &b)
 // a .flac file's image -> the track, decoded on the GPU (dmx_flac_decode); a rate other than 44.1 kHz as load_audio_file
 // treats a WAV file of that rate (DMX_RESAMPLE=1: converted on the GPU, native_rate / native_frames report the file's)
 inline bool load_flac_image(const std::string &filename, const std::vector<uint8_t> &b, demucscpp::StereoMatrix &out, int *native_rate = nullptr,
-                            int64_t *native_frames = nullptr)
+                            int64_t *native_frames = nullptr, bool keep_native = false)
 {
     dmx_flac_info info;
     if (dmx_flac_probe(b.data(), (int64_t)b.size(), &info) != DMX_OK)
@@ -259,7 +266,12 @@ inline bool load_flac_image(const std::string &filename, const std::vector<uint8
     std::cout << "Input samples: " << N << std::endl;
     std::cout << "Length in seconds: " << (double)N / rate << std::endl;
     std::cout << "Number of channels: " << info.channels << std::endl;
-    if (convert)
+    if (convert && keep_native)
+    {
+        if (native_frames)
+            *native_frames = N;
+    }
+    else if (convert)
     {
         const int64_t n441 = dmx_resample_length(N, rate, demucscpp::SUPPORTED_SAMPLE_RATE);
         demucscpp::StereoMatrix conv(n441);

@@ -43,6 +43,7 @@ EXPORTS = [
     "dmx_flac_bound", "dmx_flac_workspace_bytes", "dmx_flac_encode_device", "dmx_flac_encode", "dmx_tracks_infer_flac",
     "dmx_flac_encode_device_level", "dmx_flac_encode_level", "dmx_flac_encode_device_timed", "dmx_ctx_set_flac_level", "dmx_ctx_flac_level",
     "dmx_flac_probe", "dmx_flac_decode_workspace_bytes", "dmx_flac_decode_device", "dmx_flac_decode", "dmx_tracks_infer_from_flac", "dmx_flac_decode_profile",
+    "dmx_tracks_infer_rates", "dmx_tracks_infer_from_flac_rates", "dmx_resample_ready",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -170,6 +171,10 @@ def lib():
         L.dmx_flac_decode.argtypes = [ci, vp, i64, vp, ci, vp, vp]
         L.dmx_flac_decode_profile.argtypes = [ci, vp, i64, vp, ci, vp, vp, vp, vp, vp]
         L.dmx_tracks_infer_from_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        L.dmx_tracks_infer_from_flac_rates.argtypes = L.dmx_tracks_infer_from_flac.argtypes
+        L.dmx_tracks_infer_rates.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
+        L.dmx_resample_ready.argtypes = [i64, i64, ci, ci, i64]
+        L.dmx_resample_ready.restype = i64
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -554,9 +559,10 @@ class Context:
         return [pcm_views(b, ospec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
 
     def tracks_from_flac(self, files, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
-                         shift_offsets=None, flac_out: bool = False, progress=None, track_status=None, out=None):
+                         shift_offsets=None, flac_out: bool = False, progress=None, track_status=None, out=None, any_rate: bool = False):
         """tracks_remix() (flac_out False) or tracks_flac() at 44100 Hz (flac_out True) on tracks given as the bytes of .flac
-        files (dmx_tracks_infer_from_flac). Returns (outs, peaks, track_status): track_status np.int64 (T, 2) = {status, good}
+        files (dmx_tracks_infer_from_flac). any_rate: every track runs at the rate of its file, as tracks_rates() runs it
+        (dmx_tracks_infer_from_flac_rates); the outputs have the file's frames and rate. Returns (outs, peaks, track_status): track_status np.int64 (T, 2) = {status, good}
         per track. A damaged track raises DmxError after all work has drained; pass `track_status` (np.int64, T * 2, flat) to
         keep what the call learned, and `.partial` of the error holds (outs, peaks) of that call. `out`: buffers to reuse, as
         tracks_remix() / tracks_flac() take them."""
@@ -603,9 +609,9 @@ class Context:
         fp = (ctypes.c_void_p * max(T, 1))(*[f.ctypes.data for f in imgs])
         fn = (ctypes.c_int64 * max(T, 1))(*[f.size for f in imgs])
         op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
-        rc = lib().dmx_tracks_infer_from_flac(self.h, mp, Q, wp, T, fp, fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c),
-                                              1 if flac_out else 0, op, sizes.ctypes.data, peaks.ctypes.data, track_status.ctypes.data,
-                                              cbp, None)
+        call = lib().dmx_tracks_infer_from_flac_rates if any_rate else lib().dmx_tracks_infer_from_flac
+        rc = call(self.h, mp, Q, wp, T, fp, fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), 1 if flac_out else 0, op,
+                  sizes.ctypes.data, peaks.ctypes.data, track_status.ctypes.data, cbp, None)
         if flac_out:
             outs = [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))]
         else:
@@ -617,6 +623,62 @@ class Context:
             e.partial = (outs, pk)
             raise e
         return outs, pk, track_status[:2 * T].reshape(T, 2)
+
+    def tracks_rates(self, audios, rates, spec: Optional[RemixSpec] = None, flac: bool = False, models=None, weights=None,
+                     n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR):
+        """Tracks at their own sample rates (dmx_tracks_infer_rates): audios[t] is (2, n_t) at rates[t] Hz; a track that is not
+        at 44100 Hz is converted on the device in front of the model and its stems behind it. spec None: a list of (S, 2, n_t)
+        float32 arrays as tracks_opts() / tracks_bag(); a RemixSpec: (outs, peaks) as tracks_remix(), or with flac=True
+        (files, peaks) as tracks_flac(), every file at its track's rate. models / weights / shift_offsets as tracks_remix()."""
+        T = len(audios)
+        Q = 0 if models is None else len(models)
+        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+        ns = [a.shape[1] for a in audios]
+        assert len(rates) == T
+        ra = (ctypes.c_int * max(T, 1))(*[int(r) for r in rates])
+        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
+        wp = None
+        if weights is not None:
+            warr = np.ascontiguousarray(weights, np.float32)
+            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
+            wp = warr.ctypes.data
+        so = None
+        if shift_offsets is not None:
+            arr = np.asarray(shift_offsets, np.int64)
+            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
+            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
+            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
+        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
+        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
+        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        if spec is None:
+            assert not flac, "FLAC files need a RemixSpec"
+            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
+            dst = [np.zeros((n, 2, self.S), np.float32) for n in ns] if layout == LAYOUT_EIGEN else out
+            op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
+            _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, None, 0, op, None, None,
+                                              layout, cbp, None))
+            if layout == LAYOUT_EIGEN:
+                for o, img in zip(out, dst):
+                    o[...] = img.transpose(2, 1, 0)
+            return out
+        n_out = max(spec.n_out, 0)
+        fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
+        bits = 24 if spec.encoding == PCM_S24 else 16
+        bounds = [max(lib().dmx_flac_bound(bits, n), 0) for n in ns] if flac else [n * fb for n in ns]
+        bufs = [np.zeros(max(n_out * b, 1), np.uint8) for b in bounds]
+        sizes = np.zeros(max(T * n_out, 1), np.int64)
+        peaks = np.zeros(max(T * n_out, 1), np.float32)
+        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
+        _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, ctypes.byref(spec.c),
+                                          1 if flac else 0, op, sizes.ctypes.data, peaks.ctypes.data, layout, cbp, None))
+        pk = [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+        if flac:
+            return [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))], pk
+        ospec = spec.output_spec()
+        return [pcm_views(b[:n_out * n * fb], ospec, n, n_out) for b, n in zip(bufs, ns)], pk
 
     def tracks_flac(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                     shift_offsets=None, sample_rate: int = 44100, progress=None, layout: int = LAYOUT_PLANAR, out=None, sizes=None,
@@ -913,6 +975,11 @@ def resample_length(n_in: int, rate_in: int, rate_out: int) -> int:
     L.dmx_resample_length.restype = ctypes.c_int64
     L.dmx_resample_length.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
     return L.dmx_resample_length(n_in, rate_in, rate_out)
+
+
+def resample_ready(n_in_final: int, n_in: int, rate_in: int, rate_out: int, n_out: int) -> int:
+    """dmx_resample_ready (pure host): the outputs that are final once the inputs [0, n_in_final) are; -1: invalid argument"""
+    return lib().dmx_resample_ready(n_in_final, n_in, rate_in, rate_out, n_out)
 
 
 def resample_filter(rate_in: int, rate_out: int):

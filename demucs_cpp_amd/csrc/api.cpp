@@ -321,7 +321,7 @@ dmx_ctx::~dmx_ctx()
     {
         if (sl.copied)
             (void)hipEventDestroy(sl.copied);
-        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes, &sl.flacIn, &sl.flacInWork, &sl.flacInStatus})
+        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes, &sl.flacIn, &sl.flacInWork, &sl.flacInStatus, &sl.native, &sl.nativeOut})
             if (b->p)
                 (void)hipFree(b->p);
     }

@@ -96,6 +96,7 @@ struct dmx_ctx
         DevBuf pcm, peaks; // dmx_tracks_infer_pcm: the encoded outputs (each at a 16-byte-rounded stride) and their peaks
         DevBuf flac, flacWork, flacSizes; // dmx_tracks_infer_flac: the files (stride dmx_flac_bound), the workspace, n_out int64 counts
         DevBuf flacIn, flacInWork, flacInStatus; // dmx_tracks_infer_from_flac: the file's bytes, the decoder's workspace, {status, good}
+        DevBuf native, nativeOut; // dmx_tracks_infer_rates, a call with a converted track: the track [m][2] and its stems at its own rate
         hipEvent_t copied = nullptr; // on copyStream behind the last copy-out of the track that holds the slot (TracksPlan)
     };
     std::vector<TrackSlot> slots;

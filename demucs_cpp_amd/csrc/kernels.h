@@ -409,6 +409,28 @@ struct RemixTable
 };
 void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s);
 void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// ---- the track path's converter (resample.hip) ----
+// outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
+// output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the
+// Eigen image s + S*(c + 2*k): 1, S, 2 S). The value of an output is dmx_resample_device's, whatever the cut into pieces.
+struct ResamplePiece
+{
+    const float *src;
+    float *dst;
+    i64 n, dstStem, dstChan, dstStep, k0, k1;
+};
+struct ResampleTable
+{
+    static const int kMax = 32;
+    ResamplePiece p[kMax];
+    int blk0[kMax + 1]; // piece z owns the workgroups [blk0[z], blk0[z + 1]) of the grid's x
+};
+// pure host: DMX_OK when the filter of the ratio exists and a launch over `planes` planes fits the LDS, else the error
+int resample_check(int rateIn, int rateOut, int planes);
+// the device's copy of the filter, made on first use (a blocking upload): call it before the work that must not stall
+int resample_prepare(int device, int rateIn, int rateOut);
+// one launch per ResampleTable::kMax non-empty pieces, all of one ratio; DMX_OK or an error
+int launch_resample_pieces(int device, const ResamplePiece *pieces, int P, int planes, int rateIn, int rateOut, hipStream_t s);
 // ---- the FLAC input stage (flac_in.hip; specification: DESIGN.md section 2.12, restated in tests/flac_in_spec.py) ----
 } // namespace dmx
 struct dmx_flac_info;

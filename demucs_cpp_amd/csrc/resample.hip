@@ -14,8 +14,12 @@
 // is bit-reproducible and independent of the launch geometry. Algorithmic traffic: every input sample read once,
 // every output written once (the table of L*T coefficients, 20 KB for 48 kHz <-> 44.1 kHz, is re-staged per
 // workgroup from L2); the inner loop is LDS-bound (2 T reads per output and plane pair).
+// Two kernels share one workgroup body (resample_block): the whole-signal form (dmx_resample_device) and the piece-table form
+// of the track path (launch_resample_pieces: the outputs [k0, k1) of several tracks in one launch, each with its own source
+// length and destination strides). An output's value is the same in both, wherever the pieces are cut.
 #include "api_internal.h"
 
+#include <climits>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -99,19 +103,17 @@ int design(int rate_in, int rate_out, Filter &f)
 // phases fall into different banks) and T fmaf per plane, in ascending tap order - the arithmetic and its order
 // are those of the one-line definition in the header. Two planes per thread share the coefficient reads
 // (interleaved stereo: NP = 2 with plane stride 1; a (S, 2, n) stem tensor: plane pairs).
+// One workgroup's work, shared by the two kernels below: outputs [k0, k1) of planes plane0 .. plane0 + NP - 1; output k of
+// plane p (stem p / 2, channel p % 2) goes to y + (p / 2) outStem + (p % 2) outChan + k outStep.
 template <int NP, bool TAB_LDS>
-__global__ __launch_bounds__(256) void resample_kernel(const float *x, i64 n, i64 inPlane, i64 inStep, float *y, i64 nOut, i64 outPlane,
-                                                       i64 outStep, const float *hp, int L, int M, int T, i64 c, int KB, int win,
-                                                       int planes)
+__device__ __forceinline__ void resample_block(const float *x, i64 n, i64 inPlane, i64 inStep, float *y, i64 outStem, i64 outChan,
+                                               i64 outStep, const float *hp, int L, int M, int T, i64 c, i64 k0, i64 k1, int plane0, int win, int planes)
 {
     extern __shared__ float smem[];
     float *xs = smem;            // [win][NP]: the planes of a thread side by side (NP = 2: one ds_read_b64 per tap)
     float *hs = smem + NP * win; // [L][Tp], Tp = T | 1
     const int Tp = T | 1;
     const int tid = threadIdx.x;
-    const int plane0 = blockIdx.y * NP;
-    const i64 k0 = (i64)blockIdx.x * KB;
-    const i64 k1 = k0 + KB < nOut ? k0 + KB : nOut;
     const i64 jlo = (c + k0 * M) / L - (T - 1);
     const int count = (int)((c + (k1 - 1) * M) / L - jlo + 1);
     for (int idx = tid; idx < count; idx += 256)
@@ -153,8 +155,38 @@ __global__ __launch_bounds__(256) void resample_kernel(const float *x, i64 n, i6
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
             if (plane0 + pl < planes)
-                y[(i64)(plane0 + pl) * outPlane + k * outStep] = acc[pl];
+                y[(i64)((plane0 + pl) >> 1) * outStem + (i64)((plane0 + pl) & 1) * outChan + k * outStep] = acc[pl];
     }
+}
+
+template <int NP, bool TAB_LDS>
+__global__ __launch_bounds__(256) void resample_kernel(const float *x, i64 n, i64 inPlane, i64 inStep, float *y, i64 nOut, i64 outPlane,
+                                                       i64 outStep, const float *hp, int L, int M, int T, i64 c, int KB, int win,
+                                                       int planes)
+{
+    const i64 k0 = (i64)blockIdx.x * KB;
+    const i64 k1 = k0 + KB < nOut ? k0 + KB : nOut;
+    resample_block<NP, TAB_LDS>(x, n, inPlane, inStep, y, 2 * outPlane, outPlane, outStep, hp, L, M, T, c, k0, k1, blockIdx.y * NP, win, planes);
+}
+
+// The piece-table form (the track path's converter behind the overlap-add, tracks_exec.cpp): one launch produces the
+// outputs [k0, k1) of every piece of the table, each from planar planes of its own length n and to its own destination
+// strides. Workgroup blockIdx.x belongs to the piece z with blk0[z] <= blockIdx.x < blk0[z + 1] and produces KB outputs
+// of it exactly as a workgroup of resample_kernel does: the value of an output does not depend on the cut.
+static_assert(sizeof(ResampleTable) <= 3584, "ResampleTable must leave room in HIP's 4 KB kernel-argument limit");
+template <int NP, bool TAB_LDS>
+__global__ __launch_bounds__(256) void resample_pieces_kernel(ResampleTable t, int P, const float *hp, int L, int M, int T, i64 c, int KB,
+                                                              int win, int planes)
+{
+    int z = 0;
+    while (z + 1 < P && (int)blockIdx.x >= t.blk0[z + 1])
+        ++z;
+    const ResamplePiece &e = t.p[z];
+    const i64 k0 = e.k0 + (i64)((int)blockIdx.x - t.blk0[z]) * KB;
+    const i64 k1 = k0 + KB < e.k1 ? k0 + KB : e.k1;
+    if (k0 >= k1) // (never: the launch counts the workgroups from the same numbers)
+        return;
+    resample_block<NP, TAB_LDS>(e.src, e.n, e.n, 1, e.dst, e.dstStem, e.dstChan, e.dstStep, hp, L, M, T, c, k0, k1, blockIdx.y * NP, win, planes);
 }
 
 struct DeviceFilter
@@ -181,6 +213,33 @@ int device_filter(int device, int rate_in, int rate_out, const DeviceFilter **ou
         it = g_filters.emplace(key, std::move(df)).first;
     }
     *out = &it->second;
+    return DMX_OK;
+}
+// how a launch cuts the outputs: KB per workgroup, NP planes per thread, the LDS it takes
+struct Geometry
+{
+    int KB, NP, win;
+    bool tabLds;
+    size_t lds;
+};
+int geometry(const Filter &f, int planes, Geometry &g, const char *fn)
+{
+    // outputs per workgroup: 1024 (4096 would amortise the table staging further but leaves one workgroup per CU:
+    // measured slower), fewer when the input window of a decimation would not fit 32 KB of LDS
+    int KB = 1024, NP = planes >= 2 ? 2 : 1;
+    auto window = [&](int kb) { return (int)(((i64)kb * f.M) / f.L + f.T + 2); };
+    while (KB > 64 && sizeof(float) * (size_t)NP * window(KB) > 32 * 1024)
+        KB /= 2;
+    if (sizeof(float) * (size_t)NP * window(KB) > 64 * 1024)
+        NP = 1;
+    const int win = window(KB);
+    const int Tp = f.T | 1;
+    const size_t ldsSig = sizeof(float) * (size_t)NP * win, ldsTab = sizeof(float) * (size_t)f.L * Tp;
+    const bool tabLds = ldsSig + ldsTab <= 64 * 1024; // (48 <-> 44.1 kHz: 20 KB; 96 -> 44.1 kHz: 42 KB; else from L1/L2)
+    const size_t lds = ldsSig + (tabLds ? ldsTab : 0);
+    if (lds > 64 * 1024)
+        return dmx_fail(DMX_ERR_ARG, "%s: the ratio %d/%d needs a %zu-byte input window per workgroup", fn, f.L, f.M, ldsSig);
+    g = Geometry{KB, NP, win, tabLds, lds};
     return DMX_OK;
 }
 } // namespace
@@ -227,21 +286,11 @@ extern "C" int dmx_resample_device(int device, const float *d_in, int64_t n_in, 
         return DMX_OK;
     HIPCHK(hipSetDevice(device));
     const Filter &f = df->f;
-    // outputs per workgroup: 1024 (4096 would amortise the table staging further but leaves one workgroup per CU:
-    // measured slower), fewer when the input window of a decimation would not fit 32 KB of LDS
-    int KB = 1024, NP = planes >= 2 ? 2 : 1;
-    auto window = [&](int kb) { return (int)(((i64)kb * f.M) / f.L + f.T + 2); };
-    while (KB > 64 && sizeof(float) * (size_t)NP * window(KB) > 32 * 1024)
-        KB /= 2;
-    if (sizeof(float) * (size_t)NP * window(KB) > 64 * 1024)
-        NP = 1;
-    const int win = window(KB);
-    const int Tp = f.T | 1;
-    const size_t ldsSig = sizeof(float) * (size_t)NP * win, ldsTab = sizeof(float) * (size_t)f.L * Tp;
-    const bool tabLds = ldsSig + ldsTab <= 64 * 1024; // (48 <-> 44.1 kHz: 20 KB; 96 -> 44.1 kHz: 42 KB; else from L1/L2)
-    const size_t lds = ldsSig + (tabLds ? ldsTab : 0);
-    if (lds > 64 * 1024)
-        return dmx_fail(DMX_ERR_ARG, "dmx_resample_device: the ratio %d/%d needs a %zu-byte input window per workgroup", f.L, f.M, ldsSig);
+    Geometry gm;
+    DMXCHK(geometry(f, planes, gm, "dmx_resample_device"));
+    const int KB = gm.KB, NP = gm.NP, win = gm.win;
+    const bool tabLds = gm.tabLds;
+    const size_t lds = gm.lds;
     const dim3 grid((unsigned)((nOut + KB - 1) / KB), (unsigned)((planes + NP - 1) / NP));
     hipStream_t st = (hipStream_t)stream;
 #define DMX_RS_LAUNCH(NP_, TAB_)                                                                                                       \
@@ -294,5 +343,64 @@ extern "C" int dmx_resample(int device, const float *in, int64_t n_in, int plane
         return rc;
     if (e != hipSuccess)
         return dmx_fail(DMX_ERR_HIP, "dmx_resample: copy failed: %s", hipGetErrorString(e));
+    return DMX_OK;
+}
+
+// ---- the track path's converter (kernels.h)
+int dmx::resample_check(int rate_in, int rate_out, int planes)
+{
+    Filter f;
+    DMXCHK(design(rate_in, rate_out, f));
+    Geometry gm;
+    return geometry(f, planes, gm, "resample");
+}
+
+int dmx::resample_prepare(int device, int rate_in, int rate_out)
+{
+    const DeviceFilter *df = nullptr;
+    return device_filter(device, rate_in, rate_out, &df);
+}
+
+int dmx::launch_resample_pieces(int device, const ResamplePiece *pieces, int P, int planes, int rate_in, int rate_out, hipStream_t s)
+{
+    const DeviceFilter *df = nullptr;
+    DMXCHK(device_filter(device, rate_in, rate_out, &df));
+    const Filter &f = df->f;
+    Geometry gm;
+    DMXCHK(geometry(f, planes, gm, "resample"));
+    for (int z0 = 0; z0 < P;)
+    {
+        ResampleTable t{};
+        int nt = 0;
+        i64 blocks = 0;
+        for (; z0 < P && nt < ResampleTable::kMax; ++z0)
+        {
+            const ResamplePiece &e = pieces[z0];
+            if (e.k1 <= e.k0)
+                continue;
+            const i64 nb = (e.k1 - e.k0 + gm.KB - 1) / gm.KB;
+            if (blocks + nb > INT_MAX / 2)
+                return dmx_fail(DMX_ERR_ARG, "resample: a piece of %lld outputs is too long for one launch", (long long)(e.k1 - e.k0));
+            t.p[nt] = e, t.blk0[nt] = (int)blocks;
+            blocks += nb, ++nt;
+        }
+        if (nt == 0)
+            continue;
+        t.blk0[nt] = (int)blocks;
+        const dim3 grid((unsigned)blocks, (unsigned)((planes + gm.NP - 1) / gm.NP));
+#define DMX_RS_LAUNCH(NP_, TAB_)                                                                                                  \
+    hipLaunchKernelGGL((resample_pieces_kernel<NP_, TAB_>), grid, dim3(256), gm.lds, s, t, nt, df->dPoly, f.L, f.M, f.T, f.c, gm.KB, \
+                       gm.win, planes)
+        if (gm.NP == 2 && gm.tabLds)
+            DMX_RS_LAUNCH(2, true);
+        else if (gm.NP == 2)
+            DMX_RS_LAUNCH(2, false);
+        else if (gm.tabLds)
+            DMX_RS_LAUNCH(1, true);
+        else
+            DMX_RS_LAUNCH(1, false);
+#undef DMX_RS_LAUNCH
+    }
+    HIPCHK(hipGetLastError());
     return DMX_OK;
 }

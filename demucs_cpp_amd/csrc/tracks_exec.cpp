@@ -104,6 +104,13 @@ extern "C" int dmx_track_overlap_add_device(dmx_ctx *c, const float *d_seg_out, 
 // A bag of Q models (dmx_tracks_infer_bag): a batch holds items of one model, and the context is
 // rebound (dmx_ctx_set_model) between batches; one launch of track_ola_bag_kernel combines the rings, and the peak / encode
 // stage and the copy-out follow unchanged. One model through the old entry points (no bag) is the sequence of launches it was.
+// Tracks at another rate (dmx_tracks_infer_rates): the caller's track goes up into sl.native and the
+// whole-signal resampler leaves it at 44.1 kHz in sl.audio, on the upload stream ahead of the statistics; the overlap-add of
+// such a track always writes planes; behind it the piece-table resampler (resample.hip) converts the native-rate frames the
+// batch's pieces make final (plan.native) into sl.nativeOut, in the caller's layout or, for the PCM stage, as planes; and the
+// PCM stage, the FLAC stage and the copy-out work on those frames, with the caller's track (sl.native) as the remix mixture.
+// A slot then also holds 2 m_max + S x 2 x m_max floats (m_max: the most frames of a converted track), allocated only in a call
+// that converts a track. A call whose rates are all 44100 enqueues exactly what the other entry points enqueue.
 namespace
 {
 struct BagRun // the models of a call and their effective weights [Q][S] (dmx_bag_weights)
@@ -122,6 +129,8 @@ struct PcmOut // the output spec of a call, checked (dmx_pcm_check_spec)
     // dmx_tracks_infer_flac (flacBits 16 | 24, else 0): out[t] takes n_out files at a stride of dmx_flac_bound, sizes their byte counts
     int flacBits, flacRate;
     int64_t *sizes;
+    const int *rates; // dmx_tracks_infer_rates: the tracks' own rates, which their files carry; NULL: flacRate
+    int flac_rate(int t) const { return rates ? rates[t] : flacRate; }
 };
 // One call of the track path. shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches
 // track_ola_kernel and N >= 2 track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
@@ -133,6 +142,9 @@ struct TracksRun
     int T = 0;
     const float *const *audio = nullptr;
     const int64_t *n = nullptr;
+    // dmx_tracks_infer_rates: track t has n[t] frames at rates[t]; a track whose rate is not 44100 is converted in its slot
+    // (sl.native -> sl.audio in front of the model, sl.out -> sl.nativeOut behind the overlap-add); NULL: all 44100
+    const int *rates = nullptr;
     int N = 1;
     i64 stride = 0;
     const int *shifts = nullptr;
@@ -162,6 +174,7 @@ struct TracksRun
     std::vector<TrackBagModel> bagModels;
     std::vector<RemixPiece> pieces, whole; // the PCM stage's; under a remix spec the mixture is the slot's upload
     std::vector<PcmPiece> pcmPeak, pcmEnc;  // the same without the mixture, for the kernels of an output spec
+    std::vector<ResamplePiece> conv;        // the converter's, of one ratio
 
     const dmx_ctx::TrackSlot &slot(int t) const { return c->slots[(size_t)plan.jobs[(size_t)t].slot]; }
 };
@@ -173,7 +186,10 @@ static int tracks_prepare(TracksRun &r)
     dmx_ctx *c = r.c;
     const TracksPlan &p = r.plan;
     const PcmOut *pcm = r.pcm;
-    const i64 nmax = p.nmax;
+    const i64 nmax = p.nmax, mmax = p.mmax;
+    i64 omax = 0; // the most frames of a track's outputs
+    for (const TrackJob &j : p.jobs)
+        omax = std::max<i64>(omax, j.outFrames());
     DMXCHK(dmx_ensure_buf(c->bMix, 2 * p.seg * p.B));
     DMXCHK(dmx_ensure_buf(c->bSegOut, p.ringBlocks * r.blk));
     if ((int)c->slots.size() < p.nSlots)
@@ -183,17 +199,22 @@ static int tracks_prepare(TracksRun &r)
         dmx_ctx::TrackSlot &sl = c->slots[(size_t)i];
         DMXCHK(dmx_ensure_buf(sl.audio, 2 * nmax));
         if (r.layout == DMX_LAYOUT_PLANAR)
-            DMXCHK(dmx_ensure_buf(sl.tmp, 2 * nmax));
+            DMXCHK(dmx_ensure_buf(sl.tmp, 2 * std::max(nmax, mmax)));
+        if (mmax > 0)
+        {
+            DMXCHK(dmx_ensure_buf(sl.native, 2 * mmax));
+            DMXCHK(dmx_ensure_buf(sl.nativeOut, (i64)r.S * 2 * mmax));
+        }
         DMXCHK(dmx_ensure_buf(sl.out, (i64)r.S * 2 * nmax));
         DMXCHK(dmx_ensure_buf(sl.stats, 4));
         if (pcm)
         {
-            DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(nmax * pcm->frameBytes) / 4)));
+            DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(omax * pcm->frameBytes) / 4)));
             DMXCHK(dmx_ensure_buf(sl.peaks, 8));
             if (pcm->flacBits)
             {
-                DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, nmax) / 4)));
-                DMXCHK(dmx_ensure_buf(sl.flacWork, (i64)pcm->nOut * (flac_workspace_bytes(pcm->flacBits, nmax) / 4)));
+                DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, omax) / 4)));
+                DMXCHK(dmx_ensure_buf(sl.flacWork, (i64)pcm->nOut * (flac_workspace_bytes(pcm->flacBits, omax) / 4)));
                 DMXCHK(dmx_ensure_buf(sl.flacSizes, 2 * DMX_MAX_OUTPUTS));
             }
         }
@@ -212,6 +233,12 @@ static int tracks_prepare(TracksRun &r)
         if (!sl.copied)
             HIPCHK(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
     }
+    for (const TrackJob &j : p.jobs) // the filters go up now (once per process and ratio), not between the batches
+        if (j.converted())
+        {
+            DMXCHK(resample_prepare(c->m->device, j.rate, 44100));
+            DMXCHK(resample_prepare(c->m->device, 44100, j.rate));
+        }
     if (!c->uploadStream)
         HIPCHK(hipStreamCreateWithFlags(&c->uploadStream, hipStreamNonBlocking));
     if (!c->evUpload)
@@ -239,20 +266,23 @@ static int tracks_upload(TracksRun &r, int k, int tLo, int tHi)
             HIPCHK(hipEventSynchronize(sl.copied));
         if (r.pcm)
             HIPCHK(hipMemsetAsync(sl.peaks.p, 0, sizeof(float) * (size_t)r.pcm->nOut, c->stream));
+        float *up = j.converted() ? sl.native.p : sl.audio.p; // the caller's track, interleaved, j.m frames
         if (r.flacIn) // the file's bytes go up; the five launches of flac_in.hip leave the interleaved track in the slot
         {
             HIPCHK(hipMemcpyAsync(sl.flacIn.p, r.audio[t], (size_t)r.fileBytes[t], hipMemcpyHostToDevice, c->uploadStream));
-            if (launch_flac_decode((const unsigned char *)sl.flacIn.p, r.fileBytes[t], &r.flacIn[t], DMX_PCM_F32, sl.audio.p,
+            if (launch_flac_decode((const unsigned char *)sl.flacIn.p, r.fileBytes[t], &r.flacIn[t], DMX_PCM_F32, up,
                                    (long long *)sl.flacInStatus.p, sl.flacInWork.p, c->uploadStream) != 0)
                 return fail(DMX_ERR_ARG, "%s: track %d: internal error (the probe's description was refused)", r.fn, t);
         }
         else if (r.eigen)
-            HIPCHK(hipMemcpyAsync(sl.audio.p, r.audio[t], sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
+            HIPCHK(hipMemcpyAsync(up, r.audio[t], sizeof(float) * 2 * (size_t)j.m, hipMemcpyHostToDevice, c->uploadStream));
         else
         {
-            HIPCHK(hipMemcpyAsync(sl.tmp.p, r.audio[t], sizeof(float) * 2 * (size_t)j.n, hipMemcpyHostToDevice, c->uploadStream));
-            launch_planar_to_interleaved(sl.tmp.p, sl.audio.p, j.n, c->uploadStream);
+            HIPCHK(hipMemcpyAsync(sl.tmp.p, r.audio[t], sizeof(float) * 2 * (size_t)j.m, hipMemcpyHostToDevice, c->uploadStream));
+            launch_planar_to_interleaved(sl.tmp.p, up, j.m, c->uploadStream);
         }
+        if (j.converted()) // the whole track to 44.1 kHz, ahead of its statistics
+            DMXCHK(dmx_resample_device(c->m->device, sl.native.p, j.m, 2, 1, 2, j.rate, 44100, sl.audio.p, 1, 2, c->uploadStream));
         st.audio[nSt] = sl.audio.p, st.n[nSt] = j.n, st.stats[nSt] = sl.stats.p;
         if (++nSt == TrackStatsTable::kMax || t == tHi - 1)
         {
@@ -283,17 +313,20 @@ static int tracks_infer(TracksRun &r, int k)
     return dmx_segment_infer_device(c, c->bMix.p, const_cast<float *>(r.rings[(size_t)bt.q]) + (bt.g0 % p.R[(size_t)bt.q]) * r.blk, bt.nb);
 }
 
-// the overlap-add of what batch k makes final: one of three kernels (N == 1, the shifts ensemble, a bag)
-static int tracks_ola(TracksRun &r, int k)
+// the overlap-add of what batch k makes final: one of three kernels (N == 1, the shifts ensemble, a bag).
+// which < 0: every piece, in the call's layout. A call that converts a track launches twice instead: which 0, the pieces of
+// the tracks at 44.1 kHz in the call's layout; which 1, those of the converted tracks as planes, which the converter reads
+static int tracks_ola(TracksRun &r, int k, int which = -1)
 {
     const TracksPlan &p = r.plan;
     const int Q = p.Q, N = p.N, S = r.S;
     const i64 Rq = p.R[(size_t)p.batches[(size_t)k].q];
+    const int olaEigen = which == 1 ? 0 : r.olaEigen;
     hipStream_t s = r.c->stream;
     r.ola.clear(), r.ens.clear(), r.ensCopies.clear(), r.bagPieces.clear(), r.bagModels.clear();
     for (const TrackPiece &pc : p.pieces[(size_t)k])
     {
-        if (pc.hi <= pc.lo)
+        if (pc.hi <= pc.lo || (which >= 0 && (int)p.jobs[(size_t)pc.t].converted() != which))
             continue;
         const i64 n = p.jobs[(size_t)pc.t].n;
         const dmx_ctx::TrackSlot &sl = r.slot(pc.t);
@@ -324,18 +357,51 @@ static int tracks_ola(TracksRun &r, int k)
                 r.ensCopies.push_back(TrackEnsCopy{p.copy(pc.t, 0, k2).shift, p.copy(pc.t, 0, k2).nseg});
         }
     }
+    if (which >= 0 && r.ola.empty() && r.ens.empty() && r.bagPieces.empty())
+        return DMX_OK;
     if (r.bag)
     {
         if (!launch_track_ola_bag(r.bagPieces.data(), r.bagModels.data(), r.ensCopies.data(), (int)r.bagPieces.size(), Q, N, r.bag->w,
-                                  r.rings.data(), p.R.data(), S, p.seg, p.stride, r.olaEigen, 0, 2 * S, s))
+                                  r.rings.data(), p.R.data(), S, p.seg, p.stride, olaEigen, 0, 2 * S, s))
             return fail(DMX_ERR_ARG, "%s: internal error (the bag's overlap-add was refused in batch %d)", r.fn, k);
     }
     else if (N == 1)
-        launch_track_ola(r.ola.data(), (int)r.ola.size(), S, p.seg, p.stride, Rq, r.olaEigen, 0, 2 * S, s);
+        launch_track_ola(r.ola.data(), (int)r.ola.size(), S, p.seg, p.stride, Rq, olaEigen, 0, 2 * S, s);
     else
-        launch_track_ola_ens(r.ens.data(), r.ensCopies.data(), (int)r.ens.size(), N, r.rings[0], S, p.seg, p.stride, Rq, r.olaEigen, 0,
+        launch_track_ola_ens(r.ens.data(), r.ensCopies.data(), (int)r.ens.size(), N, r.rings[0], S, p.seg, p.stride, Rq, olaEigen, 0,
                              2 * S, s);
     HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+// the converter behind batch k's overlap-add: the native-rate frames that the batch's pieces make final (plan.native), one
+// launch per ratio, from the planes of sl.out to sl.nativeOut - planes for the PCM stage, else the caller's layout
+static int tracks_convert(TracksRun &r, int k)
+{
+    const TracksPlan &p = r.plan;
+    const std::vector<PcmRange> &ranges = p.native[(size_t)k];
+    const i64 S = r.S;
+    const bool eigen = !r.pcm && r.eigen;
+    for (size_t a = 0; a < ranges.size(); ++a)
+    {
+        const int rate = p.jobs[(size_t)ranges[a].t].rate;
+        bool seen = false; // a ratio is launched where it first occurs
+        for (size_t b = 0; b < a; ++b)
+            seen = seen || p.jobs[(size_t)ranges[b].t].rate == rate;
+        if (seen)
+            continue;
+        r.conv.clear();
+        for (size_t b = a; b < ranges.size(); ++b)
+        {
+            const TrackJob &j = p.jobs[(size_t)ranges[b].t];
+            if (j.rate != rate)
+                continue;
+            const dmx_ctx::TrackSlot &sl = r.slot(ranges[b].t);
+            r.conv.push_back(ResamplePiece{sl.out.p, sl.nativeOut.p, j.n, eigen ? 1 : 2 * j.m, eigen ? S : j.m, eigen ? 2 * S : 1,
+                                           ranges[b].lo, ranges[b].hi});
+        }
+        DMXCHK(launch_resample_pieces(r.c->m->device, r.conv.data(), (int)r.conv.size(), 2 * r.S, 44100, rate, r.c->stream));
+    }
     return DMX_OK;
 }
 
@@ -349,10 +415,13 @@ static int tracks_output_stage(TracksRun &r, int k)
     r.pieces.clear(), r.whole.clear();
     for (const PcmRange &g : p.pcm[(size_t)k])
     {
-        const i64 n = p.jobs[(size_t)g.t].n;
+        const TrackJob &j = p.jobs[(size_t)g.t];
+        const i64 n = j.outFrames();
         const dmx_ctx::TrackSlot &sl = r.slot(g.t);
-        RemixPiece pp{PcmPiece{sl.out.p, (unsigned char *)sl.pcm.p, (unsigned *)sl.peaks.p, n, n, DMX_OUTPUT_STRIDE(n * pcm->frameBytes), g.lo, g.hi},
-                      pcm->remix ? sl.audio.p : nullptr};
+        // a converted track: its stems and the caller's track at its own rate
+        RemixPiece pp{PcmPiece{j.converted() ? sl.nativeOut.p : sl.out.p, (unsigned char *)sl.pcm.p, (unsigned *)sl.peaks.p, n, n,
+                               DMX_OUTPUT_STRIDE(n * pcm->frameBytes), g.lo, g.hi},
+                      !pcm->remix ? nullptr : j.converted() ? sl.native.p : sl.audio.p};
         r.pieces.push_back(pp);
         if (g.hi == n)
         {
@@ -376,11 +445,11 @@ static int tracks_output_stage(TracksRun &r, int k)
     if (pcm->flacBits)
         for (const PcmRange &g : p.pcm[(size_t)k])
         {
-            const i64 n = p.jobs[(size_t)g.t].n;
+            const i64 n = p.jobs[(size_t)g.t].outFrames();
             if (g.hi != n)
                 continue;
             const dmx_ctx::TrackSlot &sl = r.slot(g.t);
-            launch_flac_encode((const unsigned char *)sl.pcm.p, DMX_OUTPUT_STRIDE(n * pcm->frameBytes), pcm->flacBits, n, pcm->flacRate,
+            launch_flac_encode((const unsigned char *)sl.pcm.p, DMX_OUTPUT_STRIDE(n * pcm->frameBytes), pcm->flacBits, n, pcm->flac_rate(g.t),
                                pcm->nOut, (unsigned char *)sl.flac.p, flac_bound(pcm->flacBits, n), (long long *)sl.flacSizes.p,
                                (unsigned char *)sl.flacWork.p, s, r.c->flacLevel);
         }
@@ -394,7 +463,7 @@ static int tracks_copy_pcm(TracksRun &r, int k, const PcmRange &g)
 {
     dmx_ctx *c = r.c;
     const PcmOut *pcm = r.pcm;
-    const i64 n = r.plan.jobs[(size_t)g.t].n;
+    const i64 n = r.plan.jobs[(size_t)g.t].outFrames();
     const dmx_ctx::TrackSlot &sl = r.slot(g.t);
     const bool last = g.hi == n;
     const i64 lo = r.wholeTrack ? 0 : g.lo, fb = pcm->frameBytes;
@@ -442,6 +511,20 @@ static int tracks_copy_out(TracksRun &r, int k)
     if (r.pcm)
         for (const PcmRange &g : p.pcm[(size_t)k])
             DMXCHK(tracks_copy_pcm(r, k, g));
+    for (size_t x = 0; !r.pcm && p.mmax > 0 && x < p.native[(size_t)k].size(); ++x) // fp32 stems of the converted tracks
+    {
+        const PcmRange &g = p.native[(size_t)k][x];
+        const i64 m = p.jobs[(size_t)g.t].m;
+        const float *dOut = r.slot(g.t).nativeOut.p;
+        float *out = r.out[g.t];
+        if (r.eigen)
+            HIPCHK(hipMemcpyAsync(out + (size_t)g.lo * 2 * S, dOut + (size_t)g.lo * 2 * S, sizeof(float) * (size_t)(g.hi - g.lo) * 2 * S,
+                                  hipMemcpyDeviceToHost, c->copyStream));
+        else
+            for (int pl = 0; pl < 2 * S; ++pl)
+                HIPCHK(hipMemcpyAsync(out + (size_t)pl * m + g.lo, dOut + (size_t)pl * m + g.lo, sizeof(float) * (size_t)(g.hi - g.lo),
+                                      hipMemcpyDeviceToHost, c->copyStream));
+    }
     for (const TrackPiece &pc : p.pieces[(size_t)k])
     {
         const TrackJob &j = p.jobs[(size_t)pc.t];
@@ -449,7 +532,7 @@ static int tracks_copy_out(TracksRun &r, int k)
         const float *dOut = sl.out.p;
         float *out = r.out ? r.out[pc.t] : nullptr;
         const i64 i0 = pc.lo, i1 = pc.hi;
-        if (i1 > i0 && !r.pcm)
+        if (i1 > i0 && !r.pcm && !j.converted())
         {
             if (r.eigen)
                 HIPCHK(hipMemcpyAsync(out + (size_t)i0 * 2 * S, dOut + (size_t)i0 * 2 * S, sizeof(float) * (size_t)(i1 - i0) * 2 * S,
@@ -501,8 +584,16 @@ static int tracks_run_impl(TracksRun &r)
     r.olaEigen = r.pcm ? 0 : r.eigen; // the PCM stage reads planes
     r.wholeTrack = r.pcm && r.pcm->spec.clip == DMX_CLIP_RESCALE;
     std::string why;
-    const int rcPlan = tracks_plan_build(r.plan, r.T, r.n, r.bag ? r.bag->Q : 1, r.N, r.shifts, c->seg, r.stride, c->maxBatch, r.pcm != nullptr,
-                                         r.bag ? -1 : TrackEnsTable::kMaxTail, why);
+    std::vector<int64_t> n44; // the plan is made on the tracks' lengths at 44.1 kHz
+    if (r.rates)
+    {
+        n44.assign(r.n, r.n + r.T);
+        for (int t = 0; t < r.T; ++t)
+            if (r.rates[t] != 44100)
+                n44[(size_t)t] = dmx_resample_length(r.n[t], r.rates[t], 44100);
+    }
+    const int rcPlan = tracks_plan_build(r.plan, r.T, r.rates ? n44.data() : r.n, r.bag ? r.bag->Q : 1, r.N, r.shifts, c->seg, r.stride, c->maxBatch,
+                                         r.pcm != nullptr, r.bag ? -1 : TrackEnsTable::kMaxTail, why, r.rates, r.n);
     if (rcPlan != DMX_OK)
         return fail(rcPlan, "%s: %s", r.fn, why.c_str());
     if (r.bag)
@@ -523,7 +614,14 @@ static int tracks_run_impl(TracksRun &r)
             ++tHi;
         DMXCHK(tracks_upload(r, k, tLo, tHi));
         DMXCHK(tracks_infer(r, k));
-        DMXCHK(tracks_ola(r, k));
+        if (p.mmax == 0)
+            DMXCHK(tracks_ola(r, k));
+        else
+        {
+            DMXCHK(tracks_ola(r, k, 0));
+            DMXCHK(tracks_ola(r, k, 1));
+            DMXCHK(tracks_convert(r, k));
+        }
         if (r.pcm)
             DMXCHK(tracks_output_stage(r, k));
         hipEvent_t ev = dmx_batch_event(c, (size_t)k);
@@ -652,6 +750,7 @@ struct TracksCall
     const dmx_remix_spec *remix;
     int flacRate;
     int64_t *flacSizes;
+    const int *rates;            // dmx_tracks_infer_rates: n[t] frames at rates[t] (checked: check_tracks_rates); else NULL, all 44100
     const dmx_flac_info *flacIn; // dmx_tracks_infer_from_flac: audio[t] is a file image, described here; else NULL
     const int64_t *fileBytes;
     int64_t *trackStatus;
@@ -986,19 +1085,21 @@ static int tracks_call(const TracksCall &a)
     else if (a.kind == TRACKS_OUT_PCM)
         pcm = PcmOut{*a.spec, a.out, a.peaks, a.spec->stem < 0 ? S : 2, dmx_pcm_frame_bytes(a.spec->encoding), nullptr, 0, 0, nullptr};
     if (a.kind == TRACKS_OUT_FLAC)
-        pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = a.flacRate, pcm.sizes = a.flacSizes;
+        pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = a.flacRate, pcm.sizes = a.flacSizes, pcm.rates = a.rates;
     // (track, copy) order; with models (track, model, copy) order
     const std::vector<int> shifts = draw_shifts(a.bag ? a.n_tracks * a.n_models : a.n_tracks, a.n_shifts, a.shift_offsets);
     TracksRun r;
     r.c = a.c, r.fn = fn, r.T = a.n_tracks, r.audio = a.audio, r.n = a.n, r.N = a.n_shifts, r.stride = stride, r.shifts = shifts.data();
     r.layout = a.layout, r.progress = a.progress, r.user = a.user;
-    r.flacIn = a.flacIn, r.fileBytes = a.fileBytes, r.trackStatus = a.trackStatus;
+    r.flacIn = a.flacIn, r.fileBytes = a.fileBytes, r.trackStatus = a.trackStatus, r.rates = a.rates;
     if (a.kind == TRACKS_OUT_F32)
         r.out = reinterpret_cast<float *const *>(a.out);
     else
         r.pcm = &pcm;
     if (a.bag)
         r.bag = &bag;
+    for (int t = 0; a.trackStatus && t < 2 * a.n_tracks; ++t) // every argument has passed
+        a.trackStatus[t] = -1;
     return tracks_run(r);
 }
 
@@ -1049,20 +1150,43 @@ extern "C" int dmx_tracks_infer_flac(dmx_ctx *c, const dmx_model *const *models,
     return tracks_call(a);
 }
 
+// what a call with rates asks of them, from numbers alone (no context, no device): n may be NULL (reported later)
+static int check_tracks_rates(const char *fn, int n_tracks, const int64_t *n, const int *rates, bool flac)
+{
+    for (int t = 0; t < n_tracks; ++t)
+    {
+        const int rate = rates[t];
+        if (rate == 44100)
+            continue;
+        if (rate >= 1 && n && n[t] >= 0 && dmx_resample_length(n[t], rate, 44100) < 2)
+            return fail(DMX_ERR_ARG, "%s: track %d: %lld frames at %d Hz leave %lld at 44100 Hz", fn, t, (long long)n[t], rate,
+                        (long long)dmx_resample_length(n[t], rate, 44100));
+        if (resample_check(rate, 44100, 2) != DMX_OK || resample_check(44100, rate, 2) != DMX_OK)
+        {
+            const std::string why = dmx_err_string();
+            return fail(DMX_ERR_ARG, "%s: track %d: sample rate %d: %s", fn, t, rate, why.c_str());
+        }
+        if (flac && rate > 655350)
+            return fail(DMX_ERR_ARG, "%s: track %d: sample rate %d has no FLAC form (at most 655350)", fn, t, rate);
+    }
+    return DMX_OK;
+}
+
 // tracks given as .flac files: every file is probed before any GPU work, then the request is dmx_tracks_infer_remix's or
 // dmx_tracks_infer_flac's with the tracks decoded in their slots (tracks_upload)
-extern "C" int dmx_tracks_infer_from_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
-                                          const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
-                                          const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
-                                          float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user)
+// anyRate (dmx_tracks_infer_from_flac_rates): every track runs at its file's rate, as dmx_tracks_infer_rates runs it
+static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights,
+                            int n_tracks, const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                            const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes, float *peaks,
+                            int64_t *track_status, dmx_progress_fn progress, void *user)
 {
-    const char *fn = "dmx_tracks_infer_from_flac";
     if (n_tracks < 1)
         return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
     if (!files || !file_bytes || !track_status)
         return fail(DMX_ERR_ARG, "%s: null %s array", fn, !files ? "files" : !file_bytes ? "file_bytes" : "track_status");
     std::vector<dmx_flac_info> infos((size_t)n_tracks);
     std::vector<int64_t> ns((size_t)n_tracks);
+    std::vector<int> rates((size_t)n_tracks);
     for (int t = 0; t < n_tracks; ++t)
     {
         if (!files[t])
@@ -1070,28 +1194,69 @@ extern "C" int dmx_tracks_infer_from_flac(dmx_ctx *c, const dmx_model *const *mo
         char msg[160];
         if (flac_in_probe(files[t], file_bytes[t], &infos[(size_t)t], msg, sizeof msg) != 0)
             return fail(DMX_ERR_FORMAT, "%s: track %d: %s", fn, t, msg);
-        if (infos[(size_t)t].sample_rate != 44100)
+        if (!anyRate && infos[(size_t)t].sample_rate != 44100)
             return fail(DMX_ERR_ARG, "%s: track %d: sample rate %d (the track path takes 44100; decode with dmx_flac_decode and resample)", fn,
                         t, infos[(size_t)t].sample_rate);
         if (flac_in_workspace_bytes(&infos[(size_t)t], file_bytes[t]) < 0)
             return fail(DMX_ERR_FORMAT, "%s: track %d: block size range %d..%d is not supported", fn, t, infos[(size_t)t].min_block,
                         infos[(size_t)t].max_block);
         ns[(size_t)t] = infos[(size_t)t].total_samples;
+        rates[(size_t)t] = infos[(size_t)t].sample_rate;
     }
+    if (anyRate)
+        DMXCHK(check_tracks_rates(fn, n_tracks, ns.data(), rates.data(), flac_out != 0));
     TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
+    a.rates = anyRate ? rates.data() : nullptr;
     if (flac_out)
         a.kind = TRACKS_OUT_FLAC, a.flacRate = 44100, a.flacSizes = sizes;
     a.n_tracks = n_tracks, a.audio = reinterpret_cast<const float *const *>(files), a.n = ns.data();
     a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.flacIn = infos.data(), a.fileBytes = file_bytes, a.trackStatus = track_status;
     a.out = out, a.peaks = peaks, a.layout = DMX_LAYOUT_EIGEN, a.progress = progress, a.user = user;
-    for (int t = 0; t < 2 * n_tracks; ++t)
-        track_status[t] = -1;
-    DMXCHK(tracks_call(a));
+    DMXCHK(tracks_call(a)); // (track_status: -1 until the track's own arrives)
     for (int t = 0; t < n_tracks; ++t)
         if (track_status[2 * t] != DMX_FLAC_OK)
             return fail(DMX_ERR_FORMAT, "%s: track %d: %s at sample %lld of %lld (the samples from there on were taken as silence)", fn, t,
                         track_status[2 * t] == DMX_FLAC_BROKEN ? "the stream breaks" : "too many frame header look-alikes, nothing decoded",
                         (long long)track_status[2 * t + 1], (long long)ns[(size_t)t]);
     return DMX_OK;
+}
+
+extern "C" int dmx_tracks_infer_from_flac(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                          const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                          const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                          float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user)
+{
+    return tracks_from_flac("dmx_tracks_infer_from_flac", false, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts, overlap,
+                            shift_offsets, spec, flac_out, out, sizes, peaks, track_status, progress, user);
+}
+
+extern "C" int dmx_tracks_infer_from_flac_rates(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                                const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                                const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                                int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user)
+{
+    return tracks_from_flac("dmx_tracks_infer_from_flac_rates", true, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts,
+                            overlap, shift_offsets, spec, flac_out, out, sizes, peaks, track_status, progress, user);
+}
+
+extern "C" int dmx_tracks_infer_rates(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                      const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                                      const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                      float *peaks, int layout, dmx_progress_fn progress, void *user)
+{
+    const char *fn = "dmx_tracks_infer_rates";
+    if (n_tracks < 1)
+        return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
+    if (!rates)
+        return fail(DMX_ERR_ARG, "%s: null rates array", fn);
+    if (!spec && flac_out)
+        return fail(DMX_ERR_ARG, "%s: FLAC files need a remix spec", fn);
+    DMXCHK(check_tracks_rates(fn, n_tracks, n, rates, flac_out != 0));
+    TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
+    a.kind = !spec ? TRACKS_OUT_F32 : flac_out ? TRACKS_OUT_FLAC : TRACKS_OUT_REMIX;
+    a.flacRate = 44100, a.flacSizes = sizes, a.rates = rates; // (flacRate: not used, every track's file carries its own)
+    a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
+    return tracks_call(a);
 }

@@ -30,13 +30,32 @@
 // q on a tie - so the models advance through the tracks abreast (round-robin when their shifts agree) and no ring has to
 // span more than the other models' batch in flight: the memory bound stays independent of the number and length of tracks.
 // A piece is final when every copy of every model has covered it.
+// Tracks at another rate (dmx_tracks_infer_rates): everything above is planned on the track's length
+// at 44.1 kHz. Behind a piece that ends at `hi` the converter (resample.hip) can finish the native-rate outputs below
+// K(hi) = dmx_resample_ready(hi, ...): output k's newest tap is input (c + k M) div L, so K is the first k with
+// c + k M >= hi L. The plan lists these native ranges per batch, and the PCM ranges of such a track are cut from them.
 #include "tracks_plan.h"
 
 #include <algorithm>
 #include <climits>
 #include <cstdio>
+#include <numeric>
 
 typedef int64_t i64;
+
+extern "C" int64_t dmx_resample_ready(int64_t n_in_final, int64_t n_in, int rate_in, int rate_out, int64_t n_out)
+{
+    if (n_in_final < 0 || n_in_final > n_in || rate_in < 1 || rate_out < 1 || n_out < 0)
+        return -1;
+    if (n_in_final == n_in)
+        return n_out;
+    const int g = std::gcd(rate_in, rate_out);
+    const i64 L = rate_out / g, M = rate_in / g, c = 16 * std::max(L, M);
+    if (n_in_final > (INT64_MAX - M) / L)
+        return -1;
+    const i64 num = n_in_final * L - c; // the first k with c + k M >= n_in_final L
+    return std::min<i64>(n_out, num <= 0 ? 0 : (num + M - 1) / M);
+}
 
 i64 overlap_stride(i64 seg, float overlap) { return (i64)((1.0f - overlap) * (float)seg); }
 
@@ -67,7 +86,7 @@ i64 track_item(const TrackCopy *cp, int N, int nMin, i64 g, int k)
 }
 
 // copy geometry, and each model's item sequence
-int plan_items(TracksPlan &p, const int64_t *n, const int *shifts, int ensTailCap, std::string &err)
+int plan_items(TracksPlan &p, const int64_t *n, const int *shifts, int ensTailCap, const int *rates, const int64_t *native, std::string &err)
 {
     const int T = p.T, Q = p.Q, N = p.N;
     p.jobs.resize((size_t)T);
@@ -77,6 +96,16 @@ int plan_items(TracksPlan &p, const int64_t *n, const int *shifts, int ensTailCa
     for (int t = 0; t < T; ++t)
     {
         p.jobs[(size_t)t] = TrackJob{n[t], INT_MAX, -1, -1, false};
+        p.jobs[(size_t)t].m = n[t];
+        if (rates && rates[t] != 44100)
+        {
+            TrackJob &j = p.jobs[(size_t)t];
+            j.rate = rates[t], j.m = native[t];
+            const i64 g = j.rate < 1 ? 1 : std::gcd(j.rate, 44100), up = 44100 / g, down = j.rate / g; // to 44.1 kHz
+            if (j.rate < 1 || j.m < 1 || n[t] != (j.m * up + down - 1) / down)
+                return plan_fail(err, "internal error (track %lld: %lld frames at %lld Hz are not %lld at 44100 Hz)", t, j.m, j.rate, n[t]);
+            p.mmax = std::max<i64>(p.mmax, j.m);
+        }
         for (int q = 0; q < Q; ++q)
         {
             TrackModel &x = p.tm[(size_t)t * Q + q];
@@ -247,6 +276,31 @@ int plan_slots(TracksPlan &p, std::string &err)
     return DMX_OK;
 }
 
+// the output frames that are final behind a piece: its end, or for a track at another rate the native frames ready then
+i64 piece_out_hi(const TracksPlan &p, const TrackPiece &pc)
+{
+    const TrackJob &j = p.jobs[(size_t)pc.t];
+    return j.converted() ? dmx_resample_ready(pc.hi, j.n, 44100, j.rate, j.m) : pc.hi;
+}
+
+// the native-rate frames each batch's converter finishes, for the tracks at another rate
+void plan_native(TracksPlan &p)
+{
+    p.native.resize(p.batches.size());
+    std::vector<i64> done((size_t)p.T, 0);
+    for (int k = 0; k < p.nBatches(); ++k)
+        for (const TrackPiece &pc : p.pieces[(size_t)k])
+        {
+            if (!p.jobs[(size_t)pc.t].converted())
+                continue;
+            const i64 hi = piece_out_hi(p, pc);
+            if (hi <= done[(size_t)pc.t])
+                continue;
+            p.native[(size_t)k].push_back(PcmRange{pc.t, done[(size_t)pc.t], hi});
+            done[(size_t)pc.t] = hi;
+        }
+}
+
 // the frames each batch's PCM stage encodes: whole groups of 4, except at the end of the track
 void plan_pcm(TracksPlan &p)
 {
@@ -255,8 +309,8 @@ void plan_pcm(TracksPlan &p)
     for (int k = 0; k < p.nBatches(); ++k)
         for (const TrackPiece &pc : p.pieces[(size_t)k])
         {
-            const i64 n = p.jobs[(size_t)pc.t].n;
-            const i64 hi = pc.hi == n ? n : pc.hi & ~(i64)3;
+            const i64 n = p.jobs[(size_t)pc.t].outFrames(), end = piece_out_hi(p, pc);
+            const i64 hi = end == n ? n : end & ~(i64)3;
             if (hi <= done[(size_t)pc.t])
                 continue;
             p.pcm[(size_t)k].push_back(PcmRange{pc.t, done[(size_t)pc.t], hi});
@@ -266,11 +320,11 @@ void plan_pcm(TracksPlan &p)
 } // namespace
 
 int tracks_plan_build(TracksPlan &p, int T, const int64_t *n, int Q, int N, const int *shifts, i64 seg, i64 stride, int B, bool pcm,
-                      int ensTailCap, std::string &err)
+                      int ensTailCap, std::string &err, const int *rates, const int64_t *native)
 {
     p = TracksPlan();
     p.T = T, p.Q = Q, p.N = N, p.B = B, p.seg = seg, p.stride = stride;
-    if (int rc = plan_items(p, n, shifts, ensTailCap, err))
+    if (int rc = plan_items(p, n, shifts, ensTailCap, rates, native, err))
         return rc;
     plan_batches(p);
     std::vector<i64> reach((size_t)Q, 0);
@@ -285,6 +339,8 @@ int tracks_plan_build(TracksPlan &p, int T, const int64_t *n, int Q, int N, cons
     }
     if (int rc = plan_slots(p, err))
         return rc;
+    if (p.mmax > 0)
+        plan_native(p);
     if (pcm)
         plan_pcm(p);
     return DMX_OK;

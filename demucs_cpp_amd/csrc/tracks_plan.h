@@ -22,6 +22,12 @@ struct TrackJob
     int kFirst, kLast; // the first / last batch (of any model) holding an item of the track
     int slot;          // the track slot it holds during batches [kFirst, kLast + 1]
     bool takeover;     // the slot had a holder (finished in batch kFirst - 2 or earlier): wait on that track's copy-out first
+    // a track at another rate (dmx_tracks_infer_rates): n is its length at 44.1 kHz, m the caller's frames at `rate`;
+    // rate 44100 (every track of the other entry points): m == n and nothing is converted
+    int64_t m = 0;
+    int rate = 44100;
+    bool converted() const { return rate != 44100; }
+    int64_t outFrames() const { return converted() ? m : n; } // the frames of its outputs
 };
 struct TrackModel // one model's items of one track
 {
@@ -49,7 +55,7 @@ struct TrackBatch
     int64_t g0; // its first item, in the model's sequence
     int nb;
 };
-struct PcmRange // frames [lo, hi) of track t encoded behind one batch
+struct PcmRange // frames [lo, hi) of track t encoded (or, in TracksPlan::native, converted) behind one batch
 {
     int t;
     int64_t lo, hi;
@@ -70,7 +76,11 @@ struct TracksPlan
     std::vector<int64_t> M, R, ringOff; // [Q]: items, ring blocks and first ring block of model q
     int64_t ringBlocks = 0, nmax = 0, Mtot = 0;
     int nSlots = 0;
-    std::vector<std::vector<PcmRange>> pcm; // [batch] with a PCM stage, else empty
+    std::vector<std::vector<PcmRange>> pcm; // [batch] with a PCM stage, else empty; a converted track's are in native frames
+    // [batch], tracks at another rate only: the frames [lo, hi) at the track's own rate that are final once the batch's
+    // pieces are (dmx_resample_ready of the piece's end), in piece order; empty ranges are not listed
+    std::vector<std::vector<PcmRange>> native;
+    int64_t mmax = 0; // the most native frames of a converted track; 0: the call converts nothing
 
     int nBatches() const { return (int)batches.size(); }
     const TrackCopy &copy(int t, int q, int k) const { return copies[(size_t)(tm[(size_t)t * Q + q].c0 + k)]; }
@@ -78,6 +88,8 @@ struct TracksPlan
 
 // shifts: T x Q x N, row-major. ensTailCap: the most tail rows x copies of a track the ensemble overlap-add takes
 // (TrackEnsTable::kMaxTail), < 0: no such cap (a bag checks its own, on the plan's nMin / nMax).
+// rates (NULL: all 44100) and native (the caller's frames per track, read where rates[t] != 44100): n[t] is then the length
+// at 44.1 kHz, ceil(native[t] * 44100 / rates[t]), on which everything but `native` and `pcm` is planned.
 // DMX_OK, else an error code and its message in `err` (without the entry point's name)
 int tracks_plan_build(TracksPlan &p, int T, const int64_t *n, int Q, int N, const int *shifts, int64_t seg, int64_t stride, int B, bool pcm,
-                      int ensTailCap, std::string &err);
+                      int ensTailCap, std::string &err, const int *rates = nullptr, const int64_t *native = nullptr);

@@ -538,11 +538,17 @@ namespace detail
 // one call of dmx_tracks_infer_remix: models NULL / Q 0 (the context's model) or a bag; shifts as the caller's path lays them out
 inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *models, int Q, const float *w, int S,
                              const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts, const ProgressCallback &cb,
-                             const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks)
+                             const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks,
+                             const std::vector<int> *rates = nullptr) // rates: track t is at (*rates)[t] Hz (dmx_tracks_infer_rates)
 {
     const size_t T = tracks.size();
     PcmOutputs out(T);
     const int n_out = (int)ro.names.size();
+    if (rates && rates->size() != T)
+    {
+        std::cerr << who << ": " << rates->size() << " rates for " << T << " tracks" << std::endl;
+        std::exit(1);
+    }
     if (ro.gains.size() != (size_t)n_out * (size_t)(S + 1))
     {
         std::cerr << who << ": " << ro.gains.size() << " gains for " << n_out << " outputs x (" << S << " stems + the mixture)" << std::endl;
@@ -580,8 +586,11 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
     {
         std::vector<int64_t> sizes(T * (size_t)n_out, 0);
         FlacLevelGuard level(c, ro.flac_level);
-        if (!c || !level.ok || dmx_tracks_infer_flac(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
-                                        ro.sample_rate, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
+        if (!c || !level.ok ||
+            (rates ? dmx_tracks_infer_rates(c, models, Q, w, (int)T, in.data(), n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                            1, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)
+                   : dmx_tracks_infer_flac(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                           ro.sample_rate, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)) != DMX_OK)
             die(who);
         for (size_t t = 0; t < T; ++t)
         {
@@ -591,8 +600,11 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
             flat[t] = std::vector<unsigned char>();
         }
     }
-    else if (!c || dmx_tracks_infer_remix(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(),
-                                     pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
+    else if (!c ||
+             (rates ? dmx_tracks_infer_rates(c, models, Q, w, (int)T, in.data(), n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                             0, dst.data(), nullptr, pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)
+                    : dmx_tracks_infer_remix(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(),
+                                             pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)) != DMX_OK)
         die(who);
     for (size_t t = 0; !ro.flac && t < T; ++t)
     {
@@ -611,11 +623,12 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
 }
 // the same on tracks given as the images of .flac files (dmx_tracks_infer_from_flac): ro.flac chooses the output form.
 // frames (optional) receives each track's sample count. A file the probe refuses, a rate other than 44100 Hz or a stream
-// that breaks inside ends the process with the library's message, which names the track.
+// that breaks inside ends the process with the library's message, which names the track. rates (optional) receives the
+// files' sample rates and lets every track run at its own (dmx_tracks_infer_from_flac_rates; .flac outputs carry it).
 inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const *models, int Q, const float *w, int S,
                                   const std::vector<FlacFile> &files, const std::vector<int> &shifts, const ProgressCallback &cb,
                                   const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks,
-                                  std::vector<int64_t> *frames)
+                                  std::vector<int64_t> *frames, std::vector<int> *rates = nullptr)
 {
     const size_t T = files.size();
     PcmOutputs out(T);
@@ -628,7 +641,7 @@ inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const 
     const dmx_remix_spec spec{ro.encoding, ro.clip, n_out, ro.gains.data()};
     if (dmx_remix_check(S, &spec) != DMX_OK)
         die(who);
-    if (ro.flac && (ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24 || ro.sample_rate != 44100))
+    if (ro.flac && (ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24 || (!rates && ro.sample_rate != 44100)))
     {
         std::cerr << who << ": remix_options.flac needs encoding DMX_PCM_S16 or DMX_PCM_S24 and sample_rate 44100" << std::endl;
         std::exit(1);
@@ -648,6 +661,8 @@ inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const 
             std::exit(1);
         }
         n[t] = info.total_samples;
+        if (rates)
+            rates->resize(T), (*rates)[t] = info.sample_rate;
         per[t] = ro.flac ? dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]) : dmx_output_bytes(&ospec, n[t]);
         if (per[t] < 0)
             die(who);
@@ -658,8 +673,10 @@ inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const 
     std::vector<int64_t> sizes(T * (size_t)n_out, 0), status(2 * T, 0);
     CbThunk th{&cb};
     FlacLevelGuard level(c, ro.flac ? ro.flac_level : 0);
-    if (!c || !level.ok || dmx_tracks_infer_from_flac(c, models, Q, w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
-                                         ro.flac ? 1 : 0, dst.data(), sizes.data(), pk.data(), status.data(), progress_thunk, &th) != DMX_OK)
+    if (!c || !level.ok ||
+        (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(c, models, Q, w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap,
+                                                                                shifts.data(), &spec, ro.flac ? 1 : 0, dst.data(), sizes.data(), pk.data(),
+                                                                                status.data(), progress_thunk, &th) != DMX_OK)
         die(who);
     for (size_t t = 0; t < T; ++t)
     {
@@ -696,18 +713,18 @@ inline std::vector<int> engine_shifts(const char *who, const engine_model &model
 }
 inline PcmOutputs batch_call_from_flac(const char *who, const engine_model &model, const std::vector<FlacFile> &files,
                                        const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
-                                       std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames)
+                                       std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames, std::vector<int> *rates = nullptr)
 {
     if (files.empty())
         return PcmOutputs();
     const std::vector<int> shifts = engine_shifts(who, model, files.size(), opts);
     std::lock_guard<std::mutex> guard(model.lock);
     return flac_files_call(who, dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, dmx_engine_n_sources(model.engine), files, shifts, cb,
-                           opts, ro, peaks, frames);
+                           opts, ro, peaks, frames, rates);
 }
 inline PcmOutputs batch_call_remix(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks,
                                    const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
-                                   std::vector<std::vector<float>> *peaks)
+                                   std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr)
 {
     const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
     if (T == 0)
@@ -725,7 +742,7 @@ inline PcmOutputs batch_call_remix(const char *who, const engine_model &model, c
     }
     std::lock_guard<std::mutex> guard(model.lock);
     return remix_call(who, dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, dmx_engine_n_sources(model.engine), tracks, shifts, cb,
-                      opts, ro, peaks);
+                      opts, ro, peaks, rates);
 }
 } // namespace detail
 inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
@@ -741,6 +758,22 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const 
                                                std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
 {
     return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames);
+}
+
+// Tracks at their own sample rates (dmx_tracks_infer_rates): tracks[t] holds the caller's frames at rates[t] Hz, the outputs
+// have those frames and that rate, and both conversions run on the device inside the track path. For .flac files `rates`
+// RECEIVES the files' rates, and remix.sample_rate is not read: every .flac output carries its track's rate.
+inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<StereoMatrix> &tracks, const std::vector<int> &rates,
+                                               ProgressCallback cb, const inference_options &opts, const remix_options &remix,
+                                               std::vector<std::vector<float>> *peaks = nullptr)
+{
+    return detail::batch_call_remix("demucs_inference_batch_remix (rates)", model, tracks, cb, opts, remix, peaks, &rates);
+}
+inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<FlacFile> &files, std::vector<int> &rates,
+                                               ProgressCallback cb, const inference_options &opts, const remix_options &remix,
+                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
+{
+    return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files, rates)", model, files, cb, opts, remix, peaks, frames, &rates);
 }
 
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
@@ -988,6 +1021,34 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std:
     return detail::flac_files_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, files, shifts, cb, opts, remix,
                                    peaks, frames);
 }
+// the same with tracks at their own rates (see the demucs_model overloads)
+inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, const std::vector<int> &rates,
+                                               ProgressCallback cb, const std::vector<float> &weights, const inference_options &opts,
+                                               const remix_options &remix, std::vector<std::vector<float>> *peaks = nullptr)
+{
+    const char *who = "demucs_inference_batch_remix (bag, rates)";
+    if (tracks.empty())
+        return PcmOutputs();
+    const std::vector<int> shifts = detail::bag_shifts(who, bag, tracks.size(), opts);
+    const float *w = detail::bag_weights(who, bag, weights);
+    std::lock_guard<std::mutex> guard(bag.lock);
+    return detail::remix_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, tracks, shifts, cb, opts, remix,
+                              peaks, &rates);
+}
+inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<FlacFile> &files, std::vector<int> &rates,
+                                               ProgressCallback cb, const std::vector<float> &weights, const inference_options &opts,
+                                               const remix_options &remix, std::vector<std::vector<float>> *peaks = nullptr,
+                                               std::vector<int64_t> *frames = nullptr)
+{
+    const char *who = "demucs_inference_batch_remix (bag, flac files, rates)";
+    if (files.empty())
+        return PcmOutputs();
+    const std::vector<int> shifts = detail::bag_shifts(who, bag, files.size(), opts);
+    const float *w = detail::bag_weights(who, bag, weights);
+    std::lock_guard<std::mutex> guard(bag.lock);
+    return detail::flac_files_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, files, shifts, cb, opts, remix,
+                                   peaks, frames, &rates);
+}
 
 // segment-level surface; src/model.hpp:569-647 (only the boundary members are kept:
 // `mix` in, `targets_out` out - every intermediate lives in the HBM arena)
@@ -1149,6 +1210,23 @@ inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_mod
                                                              std::vector<int64_t> *frames = nullptr)
 {
     return demucscpp::detail::batch_call_from_flac("demucs_v3_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames);
+}
+// the same with tracks at their own rates (see demucscpp::demucs_inference_batch_remix)
+inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
+                                                             const std::vector<int> &rates, ProgressCallback cb,
+                                                             const demucscpp::inference_options &opts, const demucscpp::remix_options &remix,
+                                                             std::vector<std::vector<float>> *peaks = nullptr)
+{
+    return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix (rates)", model, tracks, cb, opts, remix, peaks, &rates);
+}
+inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<demucscpp::FlacFile> &files,
+                                                             std::vector<int> &rates, ProgressCallback cb,
+                                                             const demucscpp::inference_options &opts, const demucscpp::remix_options &remix,
+                                                             std::vector<std::vector<float>> *peaks = nullptr,
+                                                             std::vector<int64_t> *frames = nullptr)
+{
+    return demucscpp::detail::batch_call_from_flac("demucs_v3_inference_batch_remix (flac files, rates)", model, files, cb, opts, remix, peaks,
+                                                   frames, &rates);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

@@ -428,6 +428,37 @@ extern "C"
                                    const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
                                    float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user);
 
+    /* ---- tracks at any sample rate. Track t has n[t] frames at rates[t] Hz. A track at 44100 Hz is
+     * what the entry points above make of it, bit for bit. Any other track is the composition of the public calls:
+     *   x44 = dmx_resample(x, rates[t] -> 44100), dmx_resample_length(n[t], rates[t], 44100) frames;
+     *   the stems of x44 as dmx_tracks_infer_opts (models given: dmx_tracks_infer_bag) makes them: same shifts, overlap, rand() order;
+     *   every stem plane v = dmx_resample(v44, 44100 -> rates[t]), cut to its first n[t] frames;
+     *   spec NULL: fp32 stems S x 2 x n[t] in `layout` (sizes, peaks not used, flac_out must be 0); else the outputs of
+     *   dmx_remix_encode on v with the CALLER's track (not the round trip) as the mixture and the peak over the n[t] native
+     *   frames, as PCM (flac_out == 0) or as .flac files whose headers carry rates[t] (dmx_tracks_infer_flac's out / sizes).
+     * Both conversions run in the track's slot: no stem crosses to the host at 44.1 kHz, and the pieces of a track leave as they
+     * become final (a native-rate frame k is final once the 44.1 kHz frames below dmx_resample_ready's argument are). out[t],
+     * dmx_output_bytes and dmx_flac_bound are sized by n[t]. Refused before any GPU work, naming the track, nothing written:
+     * fewer than 2 frames at 44.1 kHz, a rate dmx_resample_filter refuses (or whose filter does not fit the kernel), FLAC
+     * output above 655350 Hz. Device memory: as the entry point of the same output form on the lengths at 44.1 kHz, the encoded
+     * outputs on n[t]; and, only in a call with a track that is not at 44100 Hz, per track slot 2 m_max floats (the track at
+     * its rate) and n_sources x 2 x m_max floats (its stems at its rate), m_max the most frames of such a track. */
+    int dmx_tracks_infer_rates(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                               const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                               const int *shift_offsets, const dmx_remix_spec *spec /* NULL: fp32 S x 2 x n[t] in layout */, int flac_out,
+                               void *const *out, int64_t *sizes, float *peaks, int layout, dmx_progress_fn progress, void *user);
+    /* dmx_tracks_infer_from_flac with every track at the rate of its file, as dmx_tracks_infer_rates runs it: the file is decoded
+     * in the slot at its own rate (a damaged stream is silence from `good` on BEFORE the conversion; track_status is in the
+     * file's frames). Device memory: both of the above. */
+    int dmx_tracks_infer_from_flac_rates(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                         const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                         const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                         float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user);
+    /* pure host function: the outputs of a conversion of n_in -> n_out = dmx_resample_length frames that no longer change once
+     * the inputs [0, n_in_final) are final: n_out when n_in_final == n_in, else min(n_out, max(0, ceil((n_in_final L - c) / M))),
+     * the first output whose newest tap (c + k M) div L reaches n_in_final. -1: invalid argument */
+    int64_t dmx_resample_ready(int64_t n_in_final, int64_t n_in, int rate_in, int rate_out, int64_t n_out);
+
     /* ---- building blocks of dmx_track_infer on device memory (segment sharding over
      * several GPUs: one process per GPU runs steps 2-3 on its share, results are gathered
      * (RCCL) to the root which runs step 4). All asynchronous on the context's stream.   */
