@@ -286,6 +286,114 @@ def split_activations_fp16(x: np.ndarray, scale_exp: int = 0, device: int = 0) -
     return planes
 
 
+# ---- marshalling of the track calls (Context.track, Context.tracks_*, Engine.track): one helper per duty. What a helper
+# returns beside the ctypes pointers is what the caller keeps alive until the library call has returned.
+def _progress_thunk(progress):
+    """(the PROGRESS_FN object, the pointer to pass) of a progress(fraction, message) callable; (None, None) without one"""
+    if not progress:
+        return None, None
+    cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode()))
+    return cb, ctypes.cast(cb, ctypes.c_void_p)
+
+
+def _pointers(arrays):
+    return (ctypes.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+
+
+def _shift_array(shift_offsets, T: int, Q: Optional[int], n_shifts: int):
+    """the c_int array of shift offsets of shape (T, n_shifts), or (T, Q, n_shifts) with models; None stays None"""
+    if shift_offsets is None:
+        return None
+    arr = np.asarray(shift_offsets, np.int64)
+    want = (T, n_shifts) if Q is None else (T, Q, n_shifts)
+    assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
+    return (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
+
+
+def _models_weights(models, weights, S: int):
+    """(model pointers or None, Q, weights pointer or None, the weights array): models None is the context's own model
+    (Q 0); a None entry becomes a NULL model, which the library refuses"""
+    Q = 0 if models is None else len(models)
+    mp = None if models is None else (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models])
+    if weights is None:
+        return mp, Q, None, None
+    warr = np.ascontiguousarray(weights, np.float32)
+    assert warr.shape == (Q, S), f"weights: expected shape {(Q, S)}, got {warr.shape}"
+    return mp, Q, warr.ctypes.data, warr
+
+
+def _track_inputs(audios, layout: int):
+    """(T, lengths, the arrays passed, their pointers, the c_int64 lengths) of (2, n_t) tracks: float32 and contiguous as
+    they are, or for LAYOUT_EIGEN their transposed copies, [n][2] == column-major 2 x n"""
+    audios = [np.ascontiguousarray(a, np.float32) for a in audios]
+    ns = [a.shape[1] for a in audios]
+    src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
+    return len(ns), ns, src, _pointers(src), (ctypes.c_int64 * max(len(ns), 1))(*ns)
+
+
+def _fp32_results(out, ns, S: int, layout: int):
+    """(pointers to write through, finish): `out` is the caller's list of (S, 2, n_t) float32 arrays or None (allocated);
+    finish() returns it, for LAYOUT_EIGEN after copying back the images the library wrote (flat index s + S*(c + 2*i))"""
+    if out is None:
+        out = [np.zeros((S, 2, n), np.float32) for n in ns]
+    assert len(out) == len(ns)
+    for o, n in zip(out, ns):
+        assert o.shape == (S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
+    if layout != LAYOUT_EIGEN:
+        return _pointers(out), lambda: out
+    dst = [np.zeros((n, 2, S), np.float32) for n in ns]
+
+    def finish():
+        for o, img in zip(out, dst):
+            o[...] = img.transpose(2, 1, 0)
+        return out
+    return _pointers(dst), finish
+
+
+def _byte_results(want, out, exact: bool):
+    """(buffers, their pointers): one np.uint8 buffer of want[t] bytes per track, allocated, or the caller's `out`, which
+    must have exactly that size (the PCM forms) or at least that size (the FLAC forms, whose sizes are bounds)"""
+    bufs = out if out is not None else [np.zeros(w if exact else max(w, 1), np.uint8) for w in want]
+    assert len(bufs) == len(want)
+    for b, w in zip(bufs, want):
+        assert b.dtype == np.uint8 and b.ndim == 1 and (b.size == w if exact else b.size >= w) and b.flags.c_contiguous
+    return bufs, _pointers(bufs)
+
+
+def _flat_result(arr, count: int, dtype):
+    """a flat array of at least `count` entries (peaks, sizes): the caller's, checked, or a new one"""
+    if arr is None:
+        arr = np.zeros(max(count, 1), dtype)
+    assert arr.dtype == dtype and arr.ndim == 1 and arr.size >= count and arr.flags.c_contiguous
+    return arr
+
+
+def _frame_bytes(encoding: int) -> int:
+    """bytes of one stereo frame of PCM_*"""
+    return {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(encoding, 8)
+
+
+def _remix_bytes(spec: "RemixSpec", ns, flac: bool):
+    """bytes of one output of every track under a RemixSpec: its PCM, or the bound of its .flac file (0 where the library
+    refuses the arguments, which the call itself then reports)"""
+    if not flac:
+        return [n * _frame_bytes(spec.encoding) for n in ns]
+    return [max(lib().dmx_flac_bound(24 if spec.encoding == PCM_S24 else 16, n), 0) for n in ns]
+
+
+def _pcm_results(bufs, spec: "OutputSpec", ns, n_out: int):
+    return [pcm_views(b, spec, n, n_out) for b, n in zip(bufs, ns)]
+
+
+def _flac_files(bufs, bounds, sizes, n_out: int):
+    """files[t][o]: output o of track t starts at o * bounds[t] and has sizes[t * n_out + o] bytes"""
+    return [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))]
+
+
+def _cut_peaks(peaks, T: int, n_out: int):
+    return [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+
+
 class Context:
     def __init__(self, model: Model, segment_samples: int = 0, max_batch: int = 1, gemm: Optional[int] = None):
         self.model = model
@@ -360,40 +468,28 @@ class Context:
         if out is None:
             out = np.zeros((self.S, 2, n), np.float32)
         assert out.shape == (self.S, 2, n) and out.dtype == np.float32 and out.flags.c_contiguous
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        cb, cbp = _progress_thunk(progress)
         _chk(lib().dmx_track_infer(self.h, audio.ctypes.data, n, shift_offset, out.ctypes.data, LAYOUT_PLANAR, cbp, None))
         return out
+
+    # ---- many tracks in one call: every method assembles the pieces of the helpers above, makes one call and shapes the result
+    def _output_count(self, spec: "OutputSpec") -> int:
+        n_out = lib().dmx_output_count(self.model.h, ctypes.byref(spec))
+        if n_out < 0:
+            raise DmxError(5, lib().dmx_last_error().decode(errors="replace"))
+        return n_out
 
     def tracks(self, audios, shift_offsets=None, progress=None, out=None, layout: int = LAYOUT_PLANAR) -> List[np.ndarray]:
         """Several (2, n_t) planar tracks -> list of (S, 2, n_t) in ONE call (dmx_tracks_infer: their segments share batches);
         each result is bit-identical to track() of that track. shift_offsets: None or one per track (-1: rand() % 22050,
         drawn in track order). `out`: a list of result buffers to reuse. layout=LAYOUT_EIGEN passes the tracks and receives
         the results through the C ABI as Eigen column-major images; the arrays seen by the caller are the same."""
-        T = len(audios)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
-        if out is None:
-            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
-        assert len(out) == T
-        for o, n in zip(out, ns):
-            assert o.shape == (self.S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
-        if layout == LAYOUT_EIGEN:
-            src = [np.ascontiguousarray(a.T) for a in audios]  # [n][2] == column-major 2 x n
-            dst = [np.zeros((n, 2, self.S), np.float32) for n in ns]  # flat index s + S*(c + 2*i)
-        else:
-            src, dst = audios, out
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        T, ns, src, ap, na = _track_inputs(audios, layout)
+        op, finish = _fp32_results(out, ns, self.S, layout)
         so = (ctypes.c_int * max(T, 1))(*shift_offsets) if shift_offsets is not None else None
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        cb, cbp = _progress_thunk(progress)
         _chk(lib().dmx_tracks_infer(self.h, T, ap, na, so, op, layout, cbp, None))
-        if layout == LAYOUT_EIGEN:
-            for o, img in zip(out, dst):
-                o[...] = img.transpose(2, 1, 0)
-        return out
+        return finish()
 
     def tracks_opts(self, audios, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None, progress=None, out=None,
                     layout: int = LAYOUT_PLANAR) -> List[np.ndarray]:
@@ -401,34 +497,12 @@ class Context:
         copies, copy k shifted by shift_offsets[t, k], and the copies' normalised results are averaged before
         de-normalisation. shift_offsets: None or an int array of shape (T, n_shifts), -1 entries drawn as rand() % 22050 in
         (track, copy) order. n_shifts=1, overlap=0.25 gives the bits of tracks()."""
-        T = len(audios)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
-        if out is None:
-            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
-        assert len(out) == T
-        for o, n in zip(out, ns):
-            assert o.shape == (self.S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
-        if layout == LAYOUT_EIGEN:
-            src = [np.ascontiguousarray(a.T) for a in audios]
-            dst = [np.zeros((n, 2, self.S), np.float32) for n in ns]
-        else:
-            src, dst = audios, out
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            assert arr.shape == (T, n_shifts), f"shift_offsets: expected shape {(T, n_shifts)}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        T, ns, src, ap, na = _track_inputs(audios, layout)
+        op, finish = _fp32_results(out, ns, self.S, layout)
+        so = _shift_array(shift_offsets, T, None, n_shifts)
+        cb, cbp = _progress_thunk(progress)
         _chk(lib().dmx_tracks_infer_opts(self.h, T, ap, na, int(n_shifts), float(overlap), so, op, layout, cbp, None))
-        if layout == LAYOUT_EIGEN:
-            for o, img in zip(out, dst):
-                o[...] = img.transpose(2, 1, 0)
-        return out
+        return finish()
 
     def tracks_pcm(self, audios, spec: Optional[OutputSpec] = None, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None,
                    progress=None, layout: int = LAYOUT_PLANAR, out=None):
@@ -437,31 +511,15 @@ class Context:
         np.uint8 (n, 2, 3) (packed little-endian 24 bit) or np.float32 (n, 2); peaks[t] is an np.float32 (n_out,) array.
         `out`: a list of np.uint8 buffers of n_out * output_bytes(spec, n_t) bytes to reuse (the results are views of them)."""
         spec = spec if spec is not None else OutputSpec()
-        T = len(audios)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
-        n_out = lib().dmx_output_count(self.model.h, ctypes.byref(spec))
-        if n_out < 0:
-            raise DmxError(5, lib().dmx_last_error().decode(errors="replace"))
-        bufs = out if out is not None else [np.zeros(n_out * output_bytes(spec, n), np.uint8) for n in ns]
-        assert len(bufs) == T
-        for b, n in zip(bufs, ns):
-            assert b.dtype == np.uint8 and b.ndim == 1 and b.size == n_out * output_bytes(spec, n) and b.flags.c_contiguous
-        peaks = np.zeros((max(T, 1), n_out), np.float32)
-        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            assert arr.shape == (T, n_shifts), f"shift_offsets: expected shape {(T, n_shifts)}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        T, ns, src, ap, na = _track_inputs(audios, layout)
+        n_out = self._output_count(spec)
+        bufs, op = _byte_results([n_out * output_bytes(spec, n) for n in ns], out, exact=True)
+        peaks = _flat_result(None, T * n_out, np.float32)
+        so = _shift_array(shift_offsets, T, None, n_shifts)
+        cb, cbp = _progress_thunk(progress)
         _chk(lib().dmx_tracks_infer_pcm(self.h, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec), op,
                                         peaks.ctypes.data, layout, cbp, None))
-        return [pcm_views(b, spec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t] for t in range(T)]
+        return _pcm_results(bufs, spec, ns, n_out), _cut_peaks(peaks, T, n_out)
 
     def tracks_bag(self, models, audios, weights=None, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None,
                    spec: Optional[OutputSpec] = None, progress=None, layout: int = LAYOUT_PLANAR, out=None):
@@ -470,51 +528,20 @@ class Context:
         weights >= 0 (equal weights: an ensemble). shift_offsets: None or an int array of shape (T, Q, n_shifts), -1
         entries drawn as rand() % 22050 in that row-major order. spec None: a list of (S, 2, n_t) float32 arrays as
         tracks_opts(); else (outs, peaks) as tracks_pcm(). The context stays bound to its own model."""
-        T, Q = len(audios), len(models)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
-        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models])
-        wp = None
-        if weights is not None:
-            warr = np.ascontiguousarray(weights, np.float32)
-            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
-            wp = warr.ctypes.data
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            assert arr.shape == (T, Q, n_shifts), f"shift_offsets: expected shape {(T, Q, n_shifts)}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
-        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        if spec is not None:
-            n_out = lib().dmx_output_count(self.model.h, ctypes.byref(spec))
-            if n_out < 0:
-                raise DmxError(5, lib().dmx_last_error().decode(errors="replace"))
-            bufs = out if out is not None else [np.zeros(n_out * output_bytes(spec, n), np.uint8) for n in ns]
-            assert len(bufs) == T
-            for b, n in zip(bufs, ns):
-                assert b.dtype == np.uint8 and b.ndim == 1 and b.size == n_out * output_bytes(spec, n) and b.flags.c_contiguous
-            peaks = np.zeros((max(T, 1), n_out), np.float32)
-            op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
-            _chk(lib().dmx_tracks_infer_bag(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec), op,
-                                            peaks.ctypes.data, layout, cbp, None))
-            return [pcm_views(b, spec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t] for t in range(T)]
-        if out is None:
-            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
-        assert len(out) == T
-        for o, n in zip(out, ns):
-            assert o.shape == (self.S, 2, n) and o.dtype == np.float32 and o.flags.c_contiguous
-        dst = [np.zeros((n, 2, self.S), np.float32) for n in ns] if layout == LAYOUT_EIGEN else out
-        op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
-        _chk(lib().dmx_tracks_infer_bag(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, None, op, None, layout,
-                                        cbp, None))
-        if layout == LAYOUT_EIGEN:
-            for o, img in zip(out, dst):
-                o[...] = img.transpose(2, 1, 0)
-        return out
+        T, ns, src, ap, na = _track_inputs(audios, layout)
+        mp, Q, wp, keep = _models_weights(list(models), weights, self.S)
+        so = _shift_array(shift_offsets, T, Q, n_shifts)
+        cb, cbp = _progress_thunk(progress)
+        if spec is None:
+            op, finish = _fp32_results(out, ns, self.S, layout)
+            sp = pk = None
+        else:
+            n_out = self._output_count(spec)
+            bufs, op = _byte_results([n_out * output_bytes(spec, n) for n in ns], out, exact=True)
+            peaks = _flat_result(None, T * n_out, np.float32)
+            sp, pk = ctypes.byref(spec), peaks.ctypes.data
+        _chk(lib().dmx_tracks_infer_bag(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, sp, op, pk, layout, cbp, None))
+        return finish() if spec is None else (_pcm_results(bufs, spec, ns, n_out), _cut_peaks(peaks, T, n_out))
 
     def tracks_remix(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                      shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, out=None, peaks=None):
@@ -522,41 +549,16 @@ class Context:
         models None: this context's model, shift_offsets (T, n_shifts); else a bag as tracks_bag(), shift_offsets
         (T, Q, n_shifts). Returns (outs, peaks) in the shapes of tracks_pcm(), n_out = spec.n_out. `out` / `peaks`: buffers
         to reuse (np.uint8 of n_out * output_bytes bytes per track; a flat np.float32 array of at least T * n_out entries)."""
-        T = len(audios)
-        Q = 0 if models is None else len(models)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
+        T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = max(spec.n_out, 0)
-        fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
-        bufs = out if out is not None else [np.zeros(n_out * n * fb, np.uint8) for n in ns]
-        assert len(bufs) == T
-        for b, n in zip(bufs, ns):
-            assert b.dtype == np.uint8 and b.ndim == 1 and b.size == n_out * n * fb and b.flags.c_contiguous
-        if peaks is None:
-            peaks = np.zeros(max(T * n_out, 1), np.float32)
-        assert peaks.dtype == np.float32 and peaks.ndim == 1 and peaks.size >= T * n_out and peaks.flags.c_contiguous
-        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
-        wp = None
-        if weights is not None:
-            warr = np.ascontiguousarray(weights, np.float32)
-            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
-            wp = warr.ctypes.data
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
-            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
-        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        bufs, op = _byte_results([n_out * b for b in _remix_bytes(spec, ns, False)], out, exact=True)
+        peaks = _flat_result(peaks, T * n_out, np.float32)
+        mp, Q, wp, keep = _models_weights(models, weights, self.S)
+        so = _shift_array(shift_offsets, T, None if models is None else Q, n_shifts)
+        cb, cbp = _progress_thunk(progress)
         _chk(lib().dmx_tracks_infer_remix(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), op,
                                           peaks.ctypes.data, layout, cbp, None))
-        ospec = spec.output_spec()
-        return [pcm_views(b, ospec, n, n_out) for b, n in zip(bufs, ns)], [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+        return _pcm_results(bufs, spec.output_spec(), ns, n_out), _cut_peaks(peaks, T, n_out)
 
     def tracks_from_flac(self, files, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                          shift_offsets=None, flac_out: bool = False, progress=None, track_status=None, out=None, any_rate: bool = False):
@@ -566,8 +568,7 @@ class Context:
         per track. A damaged track raises DmxError after all work has drained; pass `track_status` (np.int64, T * 2, flat) to
         keep what the call learned, and `.partial` of the error holds (outs, peaks) of that call. `out`: buffers to reuse, as
         tracks_remix() / tracks_flac() take them."""
-        T = len(files)
-        Q = 0 if models is None else len(models)
+        T, n_out = len(files), max(spec.n_out, 0)
         imgs = [np.frombuffer(f, np.uint8) for f in files]
         ns = []
         for t, f in enumerate(imgs):  # the sizes of the outputs come from the probe, before any GPU work
@@ -575,49 +576,22 @@ class Context:
                 ns.append(int(flac_probe(f).total_samples))
             except DmxError as e:
                 raise DmxError(e.code, f"track {t}: {e}") from None
-        n_out = max(spec.n_out, 0)
-        fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
-        bits = 24 if spec.encoding == PCM_S24 else 16
-        if flac_out:
-            bounds = [max(lib().dmx_flac_bound(bits, n), 0) for n in ns]
-            want = [max(n_out * b, 1) for b in bounds]
-        else:
-            want = [max(n_out * n * fb, 1) for n in ns]
-        bufs = out if out is not None else [np.zeros(w, np.uint8) for w in want]
-        assert len(bufs) == T
-        for b, w in zip(bufs, want):
-            assert b.dtype == np.uint8 and b.ndim == 1 and b.size >= w and b.flags.c_contiguous
-        sizes = np.zeros(max(T * n_out, 1), np.int64)
-        peaks = np.zeros(max(T * n_out, 1), np.float32)
+        per = _remix_bytes(spec, ns, flac_out)
+        bufs, op = _byte_results([max(n_out * b, 1) for b in per], out, exact=False)
+        sizes = _flat_result(None, T * n_out, np.int64)
+        peaks = _flat_result(None, T * n_out, np.float32)
         if track_status is None:
             track_status = np.zeros(2 * max(T, 1), np.int64)
         assert track_status.dtype == np.int64 and track_status.ndim == 1 and track_status.size >= 2 * T
-        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
-        wp = None
-        if weights is not None:
-            warr = np.ascontiguousarray(weights, np.float32)
-            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
-            wp = warr.ctypes.data
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
-            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
-        fp = (ctypes.c_void_p * max(T, 1))(*[f.ctypes.data for f in imgs])
+        mp, Q, wp, keep = _models_weights(models, weights, self.S)
+        so = _shift_array(shift_offsets, T, None if models is None else Q, n_shifts)
+        cb, cbp = _progress_thunk(progress)
         fn = (ctypes.c_int64 * max(T, 1))(*[f.size for f in imgs])
-        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
         call = lib().dmx_tracks_infer_from_flac_rates if any_rate else lib().dmx_tracks_infer_from_flac
-        rc = call(self.h, mp, Q, wp, T, fp, fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), 1 if flac_out else 0, op,
+        rc = call(self.h, mp, Q, wp, T, _pointers(imgs), fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), 1 if flac_out else 0, op,
                   sizes.ctypes.data, peaks.ctypes.data, track_status.ctypes.data, cbp, None)
-        if flac_out:
-            outs = [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))]
-        else:
-            ospec = spec.output_spec()
-            outs = [pcm_views(b[:n_out * n * fb], ospec, n, n_out) for b, n in zip(bufs, ns)]
-        pk = [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+        outs = _flac_files(bufs, per, sizes, n_out) if flac_out else _pcm_results(bufs, spec.output_spec(), ns, n_out)
+        pk = _cut_peaks(peaks, T, n_out)
         if rc != 0:
             e = DmxError(rc, lib().dmx_last_error().decode(errors="replace"))
             e.partial = (outs, pk)
@@ -630,55 +604,29 @@ class Context:
         at 44100 Hz is converted on the device in front of the model and its stems behind it. spec None: a list of (S, 2, n_t)
         float32 arrays as tracks_opts() / tracks_bag(); a RemixSpec: (outs, peaks) as tracks_remix(), or with flac=True
         (files, peaks) as tracks_flac(), every file at its track's rate. models / weights / shift_offsets as tracks_remix()."""
-        T = len(audios)
-        Q = 0 if models is None else len(models)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
+        T, ns, src, ap, na = _track_inputs(audios, layout)
         assert len(rates) == T
         ra = (ctypes.c_int * max(T, 1))(*[int(r) for r in rates])
-        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
-        wp = None
-        if weights is not None:
-            warr = np.ascontiguousarray(weights, np.float32)
-            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
-            wp = warr.ctypes.data
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
-            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
-        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        mp, Q, wp, keep = _models_weights(models, weights, self.S)
+        so = _shift_array(shift_offsets, T, None if models is None else Q, n_shifts)
+        cb, cbp = _progress_thunk(progress)
         if spec is None:
             assert not flac, "FLAC files need a RemixSpec"
-            out = [np.zeros((self.S, 2, n), np.float32) for n in ns]
-            dst = [np.zeros((n, 2, self.S), np.float32) for n in ns] if layout == LAYOUT_EIGEN else out
-            op = (ctypes.c_void_p * max(T, 1))(*[o.ctypes.data for o in dst])
-            _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, None, 0, op, None, None,
-                                              layout, cbp, None))
-            if layout == LAYOUT_EIGEN:
-                for o, img in zip(out, dst):
-                    o[...] = img.transpose(2, 1, 0)
-            return out
-        n_out = max(spec.n_out, 0)
-        fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
-        bits = 24 if spec.encoding == PCM_S24 else 16
-        bounds = [max(lib().dmx_flac_bound(bits, n), 0) for n in ns] if flac else [n * fb for n in ns]
-        bufs = [np.zeros(max(n_out * b, 1), np.uint8) for b in bounds]
-        sizes = np.zeros(max(T * n_out, 1), np.int64)
-        peaks = np.zeros(max(T * n_out, 1), np.float32)
-        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
-        _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, ctypes.byref(spec.c),
-                                          1 if flac else 0, op, sizes.ctypes.data, peaks.ctypes.data, layout, cbp, None))
-        pk = [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
-        if flac:
-            return [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))], pk
-        ospec = spec.output_spec()
-        return [pcm_views(b[:n_out * n * fb], ospec, n, n_out) for b, n in zip(bufs, ns)], pk
+            op, finish = _fp32_results(None, ns, self.S, layout)
+            sp = sz = pk = None
+        else:
+            n_out = max(spec.n_out, 0)
+            per = _remix_bytes(spec, ns, flac)
+            bufs, op = _byte_results([n_out * b for b in per], None, exact=False)
+            sizes = _flat_result(None, T * n_out, np.int64)
+            peaks = _flat_result(None, T * n_out, np.float32)
+            sp, sz, pk = ctypes.byref(spec.c), sizes.ctypes.data, peaks.ctypes.data
+        _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op, sz, pk,
+                                          layout, cbp, None))
+        if spec is None:
+            return finish()
+        outs = _flac_files(bufs, per, sizes, n_out) if flac else _pcm_results(bufs, spec.output_spec(), ns, n_out)
+        return outs, _cut_peaks(peaks, T, n_out)
 
     def tracks_flac(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                     shift_offsets=None, sample_rate: int = 44100, progress=None, layout: int = LAYOUT_PLANAR, out=None, sizes=None,
@@ -686,45 +634,19 @@ class Context:
         """tracks_remix() whose outputs leave as .flac files (dmx_tracks_infer_flac): spec.encoding PCM_S16 or PCM_S24.
         Returns (files, peaks): files[t][o] the bytes of track t's output o, peaks as tracks_remix(). `out`: buffers to reuse
         (np.uint8 of n_out * flac_bound(bits, n) bytes per track); `sizes`: a flat np.int64 array of at least T * n_out."""
-        T = len(audios)
-        Q = 0 if models is None else len(models)
-        audios = [np.ascontiguousarray(a, np.float32) for a in audios]
-        ns = [a.shape[1] for a in audios]
+        T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = max(spec.n_out, 0)
         bits = 24 if spec.encoding == PCM_S24 else 16
-        bounds = [max(flac_bound(bits, n), 0) if n >= 1 else 0 for n in ns]
-        bufs = out if out is not None else [np.zeros(max(n_out * b, 1), np.uint8) for b in bounds]
-        assert len(bufs) == T
-        for b, bd in zip(bufs, bounds):
-            assert b.dtype == np.uint8 and b.ndim == 1 and b.size >= n_out * bd and b.flags.c_contiguous
-        if sizes is None:
-            sizes = np.zeros(max(T * n_out, 1), np.int64)
-        assert sizes.dtype == np.int64 and sizes.ndim == 1 and sizes.size >= T * n_out and sizes.flags.c_contiguous
-        if peaks is None:
-            peaks = np.zeros(max(T * n_out, 1), np.float32)
-        assert peaks.dtype == np.float32 and peaks.ndim == 1 and peaks.size >= T * n_out and peaks.flags.c_contiguous
-        mp = (ctypes.c_void_p * max(Q, 1))(*[m.h.value if m is not None else None for m in models]) if models is not None else None
-        wp = None
-        if weights is not None:
-            warr = np.ascontiguousarray(weights, np.float32)
-            assert warr.shape == (Q, self.S), f"weights: expected shape {(Q, self.S)}, got {warr.shape}"
-            wp = warr.ctypes.data
-        so = None
-        if shift_offsets is not None:
-            arr = np.asarray(shift_offsets, np.int64)
-            want = (T, n_shifts) if models is None else (T, Q, n_shifts)
-            assert arr.shape == want, f"shift_offsets: expected shape {want}, got {arr.shape}"
-            so = (ctypes.c_int * max(arr.size, 1))(*[int(v) for v in arr.ravel()])
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
-        src = [np.ascontiguousarray(a.T) for a in audios] if layout == LAYOUT_EIGEN else audios
-        ap = (ctypes.c_void_p * max(T, 1))(*[a.ctypes.data for a in src])
-        op = (ctypes.c_void_p * max(T, 1))(*[b.ctypes.data for b in bufs])
-        na = (ctypes.c_int64 * max(T, 1))(*ns)
+        bounds = [max(flac_bound(bits, n), 0) if n >= 1 else 0 for n in ns]  # raises on a bad argument, unlike _remix_bytes
+        bufs, op = _byte_results([n_out * b for b in bounds], out, exact=False)
+        sizes = _flat_result(sizes, T * n_out, np.int64)
+        peaks = _flat_result(peaks, T * n_out, np.float32)
+        mp, Q, wp, keep = _models_weights(models, weights, self.S)
+        so = _shift_array(shift_offsets, T, None if models is None else Q, n_shifts)
+        cb, cbp = _progress_thunk(progress)
         _chk(lib().dmx_tracks_infer_flac(self.h, mp, Q, wp, T, ap, na, int(n_shifts), float(overlap), so, ctypes.byref(spec.c),
                                          int(sample_rate), op, sizes.ctypes.data, peaks.ctypes.data, layout, cbp, None))
-        files = [[bytes(b[o * bd:o * bd + int(sizes[t * n_out + o])]) for o in range(n_out)] for t, (b, bd) in enumerate(zip(bufs, bounds))]
-        return files, [peaks[t * n_out:(t + 1) * n_out] for t in range(T)]
+        return _flac_files(bufs, bounds, sizes, n_out), _cut_peaks(peaks, T, n_out)
 
     def track_geometry(self, n: int, shift_offset: int) -> Tuple[int, int, int]:
         ln, st, ns = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
@@ -902,7 +824,7 @@ def remix_encode(planes: np.ndarray, mix: Optional[np.ndarray], spec: RemixSpec,
         assert mix.shape == (2, n)
         mi = np.ascontiguousarray(np.asarray(mix, np.float32).T)
     n_out = max(spec.n_out, 0)
-    fb = {PCM_F32: 8, PCM_S16: 4, PCM_S24: 6}.get(spec.encoding, 8)
+    fb = _frame_bytes(spec.encoding)
     buf = np.zeros(max(n_out * n * fb, 1), np.uint8)
     peaks = np.zeros(max(n_out, 1), np.float32)
     _chk(lib().dmx_remix_encode(device, planes.ctypes.data, S, n, None if mi is None else mi.ctypes.data, ctypes.byref(spec.c),
@@ -1069,8 +991,7 @@ class Engine:
         audio = np.ascontiguousarray(audio, np.float32)
         n = audio.shape[1]
         so = (ctypes.c_int * self.n_models)(*shift_offsets)
-        cb = PROGRESS_FN(lambda p, m, u: progress(p, m.decode())) if progress else None
-        cbp = ctypes.cast(cb, ctypes.c_void_p) if cb else None
+        cb, cbp = _progress_thunk(progress)
         if layout == LAYOUT_EIGEN:
             a = np.ascontiguousarray(audio.T)  # [n][2] == column-major 2 x n
             img = np.zeros((n, 2, self.S), np.float32)  # flat index s + S*(c + 2*i)

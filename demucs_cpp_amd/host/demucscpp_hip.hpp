@@ -227,41 +227,6 @@ inline StemTensor demucs_inference(const demucs_model &model, const StereoMatrix
     return out;
 }
 
-namespace detail
-{
-// many tracks through dmx_tracks_infer on the model's first device (the root context of its engine); each result is
-// bit-identical to demucs_inference of that track alone. model.shift_offset applies to every track (-1: rand() % 22050
-// drawn per track, in order).
-inline std::vector<StemTensor> batch_call(const char *who, const engine_model &model, int S, const std::vector<StereoMatrix> &tracks,
-                                          const ProgressCallback &cb)
-{
-    const size_t T = tracks.size();
-    std::vector<StemTensor> out;
-    out.reserve(T);
-    if (T == 0)
-        return out;
-    std::vector<const float *> in(T);
-    std::vector<float *> dst(T);
-    std::vector<int64_t> n(T);
-    std::vector<int> shifts(T, model.shift_offset);
-    for (size_t t = 0; t < T; ++t)
-    {
-        out.emplace_back(S, tracks[t].cols());
-        in[t] = tracks[t].data.data(), dst[t] = out[t].data.data(), n[t] = tracks[t].cols();
-    }
-    CbThunk th{&cb};
-    std::lock_guard<std::mutex> guard(model.lock);
-    dmx_ctx *c = dmx_engine_root_ctx(model.engine, 0);
-    if (!c || dmx_tracks_infer(c, (int)T, in.data(), n.data(), shifts.data(), dst.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
-        die(who);
-    return out;
-}
-} // namespace detail
-inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb)
-{
-    return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb);
-}
-
 // demucs's inference-time quality options (PyTorch demucs apply_model(shifts=, overlap=); the reference fixes 1 and 0.25) for
 // the batch calls (dmx_tracks_infer_opts). shift_offsets: empty (model.shift_offset for every copy; -1: rand() % 22050 drawn
 // per (track, copy)), `shifts` values applied to every track, or tracks x shifts values, row-major.
@@ -273,46 +238,100 @@ struct inference_options
 };
 namespace detail
 {
-inline std::vector<StemTensor> batch_call(const char *who, const engine_model &model, int S, const std::vector<StereoMatrix> &tracks,
-                                          const ProgressCallback &cb, const inference_options &opts)
+// what a batch call runs on: the root context of a model's engine (models NULL, Q 0), or a bag's context, models and weights
+struct Target
 {
-    const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
-    std::vector<StemTensor> out;
-    out.reserve(T);
-    if (T == 0)
-        return out;
-    std::vector<int> shifts(T * N, model.shift_offset);
+    dmx_ctx *c;
+    dmx_model *const *models;
+    int Q;
+    const float *w;
+    int S;
+};
+inline Target root_target(const engine_model &model, int S) // under model.lock
+{
+    return Target{dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, S};
+}
+// tracks x shifts offsets from the options, or with a bag (Q >= 0) tracks x models x shifts: empty (`fill` everywhere),
+// `shifts` values (for every track and model) or all of them, row-major
+inline std::vector<int> expand_shifts(const char *who, int fill, size_t T, int Q, const inference_options &opts)
+{
+    const size_t N = (size_t)std::max(opts.shifts, 0), all = T * (Q < 0 ? 1 : (size_t)Q) * N;
+    std::vector<int> shifts(all, fill);
     if (opts.shift_offsets.size() == N)
         for (size_t i = 0; i < shifts.size(); ++i)
             shifts[i] = opts.shift_offsets[i % N];
-    else if (opts.shift_offsets.size() == T * N)
+    else if (opts.shift_offsets.size() == all)
         shifts = opts.shift_offsets;
     else if (!opts.shift_offsets.empty())
     {
-        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
+        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x ";
+        if (Q >= 0)
+            std::cerr << Q << " models x ";
+        std::cerr << N << " shifts" << std::endl;
         std::exit(1);
     }
-    std::vector<const float *> in(T);
-    std::vector<float *> dst(T);
-    std::vector<int64_t> n(T);
-    for (size_t t = 0; t < T; ++t)
+    return shifts;
+}
+struct TrackInputs // the tracks as the ABI takes them
+{
+    std::vector<const float *> in;
+    std::vector<int64_t> n;
+    explicit TrackInputs(const std::vector<StereoMatrix> &tracks)
     {
-        out.emplace_back(S, tracks[t].cols());
-        in[t] = tracks[t].data.data(), dst[t] = out[t].data.data(), n[t] = tracks[t].cols();
+        for (const StereoMatrix &t : tracks)
+            in.push_back(t.data.data()), n.push_back(t.cols());
     }
+};
+// fp32 stems of many tracks in one call; each result is bit-identical to demucs_inference of that track alone. opts NULL:
+// dmx_tracks_infer, one offset per track; else dmx_tracks_infer_opts, or with a bag dmx_tracks_infer_bag
+inline std::vector<StemTensor> fp32_call(const char *who, const Target &g, const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts,
+                                         const ProgressCallback &cb, const inference_options *opts)
+{
+    const int T = (int)tracks.size();
+    const TrackInputs x(tracks);
+    std::vector<StemTensor> out;
+    out.reserve(tracks.size());
+    std::vector<float *> dst;
+    for (const StereoMatrix &t : tracks)
+    {
+        out.emplace_back(g.S, t.cols());
+        dst.push_back(out.back().data.data());
+    }
+    const std::vector<void *> vdst(dst.begin(), dst.end());
     CbThunk th{&cb};
-    std::lock_guard<std::mutex> guard(model.lock);
-    dmx_ctx *c = dmx_engine_root_ctx(model.engine, 0);
-    if (!c || dmx_tracks_infer_opts(c, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), dst.data(), DMX_LAYOUT_EIGEN,
-                                    progress_thunk, &th) != DMX_OK)
+    auto run = [&]() -> int {
+        if (g.models)
+            return dmx_tracks_infer_bag(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), opts->shifts, opts->overlap, shifts.data(), nullptr,
+                                        vdst.data(), nullptr, DMX_LAYOUT_EIGEN, progress_thunk, &th);
+        if (opts)
+            return dmx_tracks_infer_opts(g.c, T, x.in.data(), x.n.data(), opts->shifts, opts->overlap, shifts.data(), dst.data(), DMX_LAYOUT_EIGEN,
+                                         progress_thunk, &th);
+        return dmx_tracks_infer(g.c, T, x.in.data(), x.n.data(), shifts.data(), dst.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th);
+    };
+    if (!g.c || run() != DMX_OK)
         die(who);
     return out;
 }
+// on the model's first device (the root context of its engine). model.shift_offset applies to every track and copy
+// (-1: rand() % 22050 drawn per (track, copy), in order)
+inline std::vector<StemTensor> batch_call(const char *who, const engine_model &model, int S, const std::vector<StereoMatrix> &tracks,
+                                          const ProgressCallback &cb, const inference_options *opts = nullptr)
+{
+    if (tracks.empty())
+        return std::vector<StemTensor>();
+    const std::vector<int> shifts = expand_shifts(who, model.shift_offset, tracks.size(), -1, opts ? *opts : inference_options());
+    std::lock_guard<std::mutex> guard(model.lock);
+    return fp32_call(who, root_target(model, S), tracks, shifts, cb, opts);
+}
 } // namespace detail
+inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb)
+{
+    return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb);
+}
 inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
                                                       const inference_options &opts)
 {
-    return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb, opts);
+    return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb, &opts);
 }
 
 // Stems as WAV-ready PCM, encoded on the GPU (dmx_tracks_infer_pcm): demucs's --two-stems, --clip-mode and --int24 /
@@ -337,60 +356,74 @@ inline int stem_index(const std::string &name)
 using PcmOutputs = std::vector<std::vector<std::vector<unsigned char>>>;
 namespace detail
 {
+// what a PCM / remix / FLAC call writes: one flat buffer per track (a track's n_out outputs are consecutive across the ABI,
+// `per` bytes apart), the peaks and, for .flac files, the sizes
+struct TrackOutputs
+{
+    int n_out;
+    std::vector<std::vector<unsigned char>> flat;
+    std::vector<void *> dst;
+    std::vector<int64_t> per, sizes;
+    std::vector<float> pk;
+    TrackOutputs(size_t T, int n) : n_out(n), sizes(T * (size_t)n, 0), pk(T * (size_t)n, 0.0f) { flat.reserve(T); }
+    void add(const char *who, int64_t bytes) // the next track: `bytes` per output, as the library sized it
+    {
+        if (bytes < 0)
+            die(who);
+        per.push_back(bytes);
+        flat.emplace_back((size_t)(std::max<int64_t>(bytes, 1) * n_out));
+        dst.push_back(flat.back().data());
+    }
+    // result[t][o]: the `per` bytes of the output, or for .flac files the first sizes[t * n_out + o] of them; then the peaks
+    PcmOutputs cut(std::vector<std::vector<float>> *peaks, bool flac = false)
+    {
+        const size_t T = flat.size();
+        PcmOutputs out(T);
+        for (size_t t = 0; t < T; ++t)
+        {
+            for (int o = 0; o < n_out; ++o)
+            {
+                const auto first = flat[t].begin() + (size_t)o * (size_t)per[t];
+                out[t].emplace_back(first, first + (size_t)(flac ? sizes[t * (size_t)n_out + o] : per[t]));
+            }
+            flat[t] = std::vector<unsigned char>();
+        }
+        if (peaks)
+        {
+            peaks->assign(T, std::vector<float>());
+            for (size_t t = 0; t < T; ++t)
+                (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
+        }
+        return out;
+    }
+};
+// dmx_tracks_infer_pcm, or with a bag dmx_tracks_infer_bag
+inline PcmOutputs pcm_call(const char *who, const Target &g, const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts,
+                           const ProgressCallback &cb, const inference_options &opts, const output_options &oo,
+                           std::vector<std::vector<float>> *peaks)
+{
+    const int T = (int)tracks.size();
+    const dmx_output_spec spec{oo.encoding, oo.clip, oo.two_stems};
+    const TrackInputs x(tracks);
+    TrackOutputs y(tracks.size(), oo.two_stems < 0 ? g.S : 2);
+    for (int64_t n : x.n)
+        y.add(who, dmx_output_bytes(&spec, n));
+    CbThunk th{&cb};
+    if (!g.c || (g.models ? dmx_tracks_infer_bag(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                                 y.dst.data(), y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)
+                          : dmx_tracks_infer_pcm(g.c, T, x.in.data(), x.n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, y.dst.data(),
+                                                 y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)) != DMX_OK)
+        die(who);
+    return y.cut(peaks);
+}
 inline PcmOutputs batch_call_pcm(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks, const ProgressCallback &cb,
                                  const inference_options &opts, const output_options &oo, std::vector<std::vector<float>> *peaks)
 {
-    const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
-    PcmOutputs out(T);
-    if (T == 0)
-        return out;
-    std::vector<int> shifts(T * N, model.shift_offset);
-    if (opts.shift_offsets.size() == N)
-        for (size_t i = 0; i < shifts.size(); ++i)
-            shifts[i] = opts.shift_offsets[i % N];
-    else if (opts.shift_offsets.size() == T * N)
-        shifts = opts.shift_offsets;
-    else if (!opts.shift_offsets.empty())
-    {
-        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
-        std::exit(1);
-    }
-    const dmx_output_spec spec{oo.encoding, oo.clip, oo.two_stems};
-    CbThunk th{&cb};
+    if (tracks.empty())
+        return PcmOutputs();
+    const std::vector<int> shifts = expand_shifts(who, model.shift_offset, tracks.size(), -1, opts);
     std::lock_guard<std::mutex> guard(model.lock);
-    dmx_ctx *c = dmx_engine_root_ctx(model.engine, 0);
-    const int n_out = oo.two_stems < 0 ? dmx_engine_n_sources(model.engine) : 2;
-    std::vector<const float *> in(T);
-    std::vector<std::vector<unsigned char>> flat(T); // a track's outputs are consecutive across the ABI
-    std::vector<void *> dst(T);
-    std::vector<int64_t> n(T);
-    for (size_t t = 0; t < T; ++t)
-    {
-        in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
-        const int64_t per = dmx_output_bytes(&spec, n[t]);
-        if (per < 0)
-            die(who);
-        flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
-        dst[t] = flat[t].data();
-    }
-    std::vector<float> pk(T * (size_t)n_out, 0.0f);
-    if (!c || dmx_tracks_infer_pcm(c, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(), pk.data(),
-                                   DMX_LAYOUT_EIGEN, progress_thunk, &th) != DMX_OK)
-        die(who);
-    for (size_t t = 0; t < T; ++t)
-    {
-        const size_t per = (size_t)dmx_output_bytes(&spec, n[t]);
-        for (int o = 0; o < n_out; ++o)
-            out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)(o + 1) * per);
-        flat[t] = std::vector<unsigned char>();
-    }
-    if (peaks)
-    {
-        peaks->assign(T, std::vector<float>());
-        for (size_t t = 0; t < T; ++t)
-            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
-    }
-    return out;
+    return pcm_call(who, root_target(model, dmx_engine_n_sources(model.engine)), tracks, shifts, cb, opts, oo, peaks);
 }
 } // namespace detail
 inline PcmOutputs demucs_inference_batch_pcm(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
@@ -535,20 +568,10 @@ inline remix_options parse_remix(const std::string &text, int nb_sources)
 }
 namespace detail
 {
-// one call of dmx_tracks_infer_remix: models NULL / Q 0 (the context's model) or a bag; shifts as the caller's path lays them out
-inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *models, int Q, const float *w, int S,
-                             const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts, const ProgressCallback &cb,
-                             const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks,
-                             const std::vector<int> *rates = nullptr) // rates: track t is at (*rates)[t] Hz (dmx_tracks_infer_rates)
+// the dmx_remix_spec of the options (it points into them), checked against a model of S stems
+inline dmx_remix_spec remix_spec(const char *who, int S, const remix_options &ro)
 {
-    const size_t T = tracks.size();
-    PcmOutputs out(T);
     const int n_out = (int)ro.names.size();
-    if (rates && rates->size() != T)
-    {
-        std::cerr << who << ": " << rates->size() << " rates for " << T << " tracks" << std::endl;
-        std::exit(1);
-    }
     if (ro.gains.size() != (size_t)n_out * (size_t)(S + 1))
     {
         std::cerr << who << ": " << ro.gains.size() << " gains for " << n_out << " outputs x (" << S << " stems + the mixture)" << std::endl;
@@ -557,100 +580,71 @@ inline PcmOutputs remix_call(const char *who, dmx_ctx *c, dmx_model *const *mode
     const dmx_remix_spec spec{ro.encoding, ro.clip, n_out, ro.gains.data()};
     if (dmx_remix_check(S, &spec) != DMX_OK)
         die(who);
+    return spec;
+}
+// bytes of one output of n frames: its WAV data, or the bound of its .flac file
+inline int64_t remix_bytes(const remix_options &ro, int64_t n)
+{
     const dmx_output_spec ospec{ro.encoding, ro.clip, -1};
-    std::vector<const float *> in(T);
-    std::vector<std::vector<unsigned char>> flat(T); // a track's outputs are consecutive across the ABI
-    std::vector<void *> dst(T);
-    std::vector<int64_t> n(T);
-    for (size_t t = 0; t < T; ++t)
+    return ro.flac ? dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n) : dmx_output_bytes(&ospec, n);
+}
+// one call of dmx_tracks_infer_remix, or for ro.flac dmx_tracks_infer_flac; shifts as the caller's path lays them out.
+// rates: track t is at (*rates)[t] Hz (dmx_tracks_infer_rates)
+inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts,
+                             const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
+                             std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr)
+{
+    const int T = (int)tracks.size();
+    if (rates && rates->size() != tracks.size())
     {
-        in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
-        int64_t per = dmx_output_bytes(&ospec, n[t]);
-        if (ro.flac)
-        {
-            if (ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24)
-            {
-                std::cerr << who << ": remix_options.flac needs encoding DMX_PCM_S16 or DMX_PCM_S24" << std::endl;
-                std::exit(1);
-            }
-            per = dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]);
-        }
-        if (per < 0)
-            die(who);
-        flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
-        dst[t] = flat[t].data();
+        std::cerr << who << ": " << rates->size() << " rates for " << T << " tracks" << std::endl;
+        std::exit(1);
     }
-    std::vector<float> pk(T * (size_t)n_out, 0.0f);
+    const dmx_remix_spec spec = remix_spec(who, g.S, ro);
+    if (ro.flac && ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24)
+    {
+        std::cerr << who << ": remix_options.flac needs encoding DMX_PCM_S16 or DMX_PCM_S24" << std::endl;
+        std::exit(1);
+    }
+    const TrackInputs x(tracks);
+    TrackOutputs y(tracks.size(), spec.n_out);
+    for (int64_t n : x.n)
+        y.add(who, remix_bytes(ro, n));
     CbThunk th{&cb};
-    if (ro.flac)
-    {
-        std::vector<int64_t> sizes(T * (size_t)n_out, 0);
-        FlacLevelGuard level(c, ro.flac_level);
-        if (!c || !level.ok ||
-            (rates ? dmx_tracks_infer_rates(c, models, Q, w, (int)T, in.data(), n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(), &spec,
-                                            1, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)
-                   : dmx_tracks_infer_flac(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
-                                           ro.sample_rate, dst.data(), sizes.data(), pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)) != DMX_OK)
-            die(who);
-        for (size_t t = 0; t < T; ++t)
-        {
-            const size_t per = (size_t)dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]);
-            for (int o = 0; o < n_out; ++o)
-                out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)o * per + (size_t)sizes[t * (size_t)n_out + o]);
-            flat[t] = std::vector<unsigned char>();
-        }
-    }
-    else if (!c ||
-             (rates ? dmx_tracks_infer_rates(c, models, Q, w, (int)T, in.data(), n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(), &spec,
-                                             0, dst.data(), nullptr, pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)
-                    : dmx_tracks_infer_remix(c, models, Q, w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap, shifts.data(), &spec, dst.data(),
-                                             pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th)) != DMX_OK)
+    FlacLevelGuard level(g.c, ro.flac ? ro.flac_level : 0);
+    auto run = [&]() -> int {
+        if (rates)
+            return dmx_tracks_infer_rates(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(),
+                                          &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr, y.pk.data(), DMX_LAYOUT_EIGEN,
+                                          progress_thunk, &th);
+        if (ro.flac)
+            return dmx_tracks_infer_flac(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                         ro.sample_rate, y.dst.data(), y.sizes.data(), y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th);
+        return dmx_tracks_infer_remix(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), opts.shifts, opts.overlap, shifts.data(), &spec,
+                                      y.dst.data(), y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th);
+    };
+    if (!g.c || !level.ok || run() != DMX_OK)
         die(who);
-    for (size_t t = 0; !ro.flac && t < T; ++t)
-    {
-        const size_t per = (size_t)dmx_output_bytes(&ospec, n[t]);
-        for (int o = 0; o < n_out; ++o)
-            out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)(o + 1) * per);
-        flat[t] = std::vector<unsigned char>();
-    }
-    if (peaks)
-    {
-        peaks->assign(T, std::vector<float>());
-        for (size_t t = 0; t < T; ++t)
-            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
-    }
-    return out;
+    return y.cut(peaks, ro.flac);
 }
 // the same on tracks given as the images of .flac files (dmx_tracks_infer_from_flac): ro.flac chooses the output form.
 // frames (optional) receives each track's sample count. A file the probe refuses, a rate other than 44100 Hz or a stream
 // that breaks inside ends the process with the library's message, which names the track. rates (optional) receives the
 // files' sample rates and lets every track run at its own (dmx_tracks_infer_from_flac_rates; .flac outputs carry it).
-inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const *models, int Q, const float *w, int S,
-                                  const std::vector<FlacFile> &files, const std::vector<int> &shifts, const ProgressCallback &cb,
-                                  const inference_options &opts, const remix_options &ro, std::vector<std::vector<float>> *peaks,
-                                  std::vector<int64_t> *frames, std::vector<int> *rates = nullptr)
+inline PcmOutputs flac_files_call(const char *who, const Target &g, const std::vector<FlacFile> &files, const std::vector<int> &shifts,
+                                  const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
+                                  std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames, std::vector<int> *rates = nullptr)
 {
     const size_t T = files.size();
-    PcmOutputs out(T);
-    const int n_out = (int)ro.names.size();
-    if (ro.gains.size() != (size_t)n_out * (size_t)(S + 1))
-    {
-        std::cerr << who << ": " << ro.gains.size() << " gains for " << n_out << " outputs x (" << S << " stems + the mixture)" << std::endl;
-        std::exit(1);
-    }
-    const dmx_remix_spec spec{ro.encoding, ro.clip, n_out, ro.gains.data()};
-    if (dmx_remix_check(S, &spec) != DMX_OK)
-        die(who);
+    const dmx_remix_spec spec = remix_spec(who, g.S, ro);
     if (ro.flac && (ro.encoding != DMX_PCM_S16 && ro.encoding != DMX_PCM_S24 || (!rates && ro.sample_rate != 44100)))
     {
         std::cerr << who << ": remix_options.flac needs encoding DMX_PCM_S16 or DMX_PCM_S24 and sample_rate 44100" << std::endl;
         std::exit(1);
     }
-    const dmx_output_spec ospec{ro.encoding, ro.clip, -1};
     std::vector<const void *> in(T);
-    std::vector<int64_t> bytes(T), n(T), per(T);
-    std::vector<std::vector<unsigned char>> flat(T);
-    std::vector<void *> dst(T);
+    std::vector<int64_t> bytes(T), n(T);
+    TrackOutputs y(T, spec.n_out);
     for (size_t t = 0; t < T; ++t)
     {
         dmx_flac_info info;
@@ -663,53 +657,19 @@ inline PcmOutputs flac_files_call(const char *who, dmx_ctx *c, dmx_model *const 
         n[t] = info.total_samples;
         if (rates)
             rates->resize(T), (*rates)[t] = info.sample_rate;
-        per[t] = ro.flac ? dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n[t]) : dmx_output_bytes(&ospec, n[t]);
-        if (per[t] < 0)
-            die(who);
-        flat[t].resize((size_t)(std::max<int64_t>(per[t], 1) * n_out));
-        dst[t] = flat[t].data();
+        y.add(who, remix_bytes(ro, n[t]));
     }
-    std::vector<float> pk(T * (size_t)n_out, 0.0f);
-    std::vector<int64_t> sizes(T * (size_t)n_out, 0), status(2 * T, 0);
+    std::vector<int64_t> status(2 * T, 0);
     CbThunk th{&cb};
-    FlacLevelGuard level(c, ro.flac ? ro.flac_level : 0);
-    if (!c || !level.ok ||
-        (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(c, models, Q, w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap,
-                                                                                shifts.data(), &spec, ro.flac ? 1 : 0, dst.data(), sizes.data(), pk.data(),
-                                                                                status.data(), progress_thunk, &th) != DMX_OK)
+    FlacLevelGuard level(g.c, ro.flac ? ro.flac_level : 0);
+    if (!g.c || !level.ok ||
+        (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts,
+                                                                                opts.overlap, shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(),
+                                                                                y.sizes.data(), y.pk.data(), status.data(), progress_thunk, &th) != DMX_OK)
         die(who);
-    for (size_t t = 0; t < T; ++t)
-    {
-        for (int o = 0; o < n_out; ++o)
-            out[t].emplace_back(flat[t].begin() + (size_t)o * (size_t)per[t],
-                                flat[t].begin() + (size_t)o * (size_t)per[t] + (size_t)(ro.flac ? sizes[t * (size_t)n_out + o] : per[t]));
-        flat[t] = std::vector<unsigned char>();
-    }
-    if (peaks)
-    {
-        peaks->assign(T, std::vector<float>());
-        for (size_t t = 0; t < T; ++t)
-            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
-    }
     if (frames)
         *frames = n;
-    return out;
-}
-inline std::vector<int> engine_shifts(const char *who, const engine_model &model, size_t T, const inference_options &opts)
-{
-    const size_t N = (size_t)std::max(opts.shifts, 0);
-    std::vector<int> shifts(T * N, model.shift_offset);
-    if (opts.shift_offsets.size() == N)
-        for (size_t i = 0; i < shifts.size(); ++i)
-            shifts[i] = opts.shift_offsets[i % N];
-    else if (opts.shift_offsets.size() == T * N)
-        shifts = opts.shift_offsets;
-    else if (!opts.shift_offsets.empty())
-    {
-        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
-        std::exit(1);
-    }
-    return shifts;
+    return y.cut(peaks, ro.flac);
 }
 inline PcmOutputs batch_call_from_flac(const char *who, const engine_model &model, const std::vector<FlacFile> &files,
                                        const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
@@ -717,32 +677,19 @@ inline PcmOutputs batch_call_from_flac(const char *who, const engine_model &mode
 {
     if (files.empty())
         return PcmOutputs();
-    const std::vector<int> shifts = engine_shifts(who, model, files.size(), opts);
+    const std::vector<int> shifts = expand_shifts(who, model.shift_offset, files.size(), -1, opts);
     std::lock_guard<std::mutex> guard(model.lock);
-    return flac_files_call(who, dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, dmx_engine_n_sources(model.engine), files, shifts, cb,
-                           opts, ro, peaks, frames, rates);
+    return flac_files_call(who, root_target(model, dmx_engine_n_sources(model.engine)), files, shifts, cb, opts, ro, peaks, frames, rates);
 }
 inline PcmOutputs batch_call_remix(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks,
                                    const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
                                    std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr)
 {
-    const size_t T = tracks.size(), N = (size_t)std::max(opts.shifts, 0);
-    if (T == 0)
+    if (tracks.empty())
         return PcmOutputs();
-    std::vector<int> shifts(T * N, model.shift_offset);
-    if (opts.shift_offsets.size() == N)
-        for (size_t i = 0; i < shifts.size(); ++i)
-            shifts[i] = opts.shift_offsets[i % N];
-    else if (opts.shift_offsets.size() == T * N)
-        shifts = opts.shift_offsets;
-    else if (!opts.shift_offsets.empty())
-    {
-        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << N << " shifts" << std::endl;
-        std::exit(1);
-    }
+    const std::vector<int> shifts = expand_shifts(who, model.shift_offset, tracks.size(), -1, opts);
     std::lock_guard<std::mutex> guard(model.lock);
-    return remix_call(who, dmx_engine_root_ctx(model.engine, 0), nullptr, 0, nullptr, dmx_engine_n_sources(model.engine), tracks, shifts, cb,
-                      opts, ro, peaks, rates);
+    return remix_call(who, root_target(model, dmx_engine_n_sources(model.engine)), tracks, shifts, cb, opts, ro, peaks, rates);
 }
 } // namespace detail
 inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
@@ -888,25 +835,7 @@ inline bool load_demucs_bag(const std::vector<std::string> &model_files, demucs_
 }
 namespace detail
 {
-// tracks x models x shifts offsets from the options: empty (the bag's shift_offset everywhere), `shifts` values (for every
-// track and model) or all of them, row-major
-inline std::vector<int> bag_shifts(const char *who, const demucs_bag &bag, size_t T, const inference_options &opts)
-{
-    const size_t Q = bag.models.size(), N = (size_t)std::max(opts.shifts, 0);
-    std::vector<int> shifts(T * Q * N, bag.shift_offset);
-    if (opts.shift_offsets.size() == N)
-        for (size_t i = 0; i < shifts.size(); ++i)
-            shifts[i] = opts.shift_offsets[i % N];
-    else if (opts.shift_offsets.size() == T * Q * N)
-        shifts = opts.shift_offsets;
-    else if (!opts.shift_offsets.empty())
-    {
-        std::cerr << who << ": " << opts.shift_offsets.size() << " shift offsets for " << T << " tracks x " << Q << " models x " << N
-                  << " shifts" << std::endl;
-        std::exit(1);
-    }
-    return shifts;
-}
+// weights: empty (the diagonal) or models x stems
 inline const float *bag_weights(const char *who, const demucs_bag &bag, const std::vector<float> &weights)
 {
     if (weights.empty())
@@ -919,6 +848,19 @@ inline const float *bag_weights(const char *who, const demucs_bag &bag, const st
     }
     return weights.data();
 }
+// the prologue of every call on a bag: the shift offsets (tracks x models x shifts; the bag's shift_offset where the options
+// give none), then the weights are checked, then the bag's lock is taken and held
+struct BagCall
+{
+    std::vector<int> shifts;
+    Target g;
+    std::lock_guard<std::mutex> guard;
+    BagCall(const char *who, const demucs_bag &bag, size_t T, const std::vector<float> &weights, const inference_options &opts)
+        : shifts(expand_shifts(who, bag.shift_offset, T, (int)bag.models.size(), opts)),
+          g{bag.ctx, bag.models.data(), (int)bag.models.size(), bag_weights(who, bag, weights), bag.nb_sources}, guard(bag.lock)
+    {
+    }
+};
 } // namespace detail
 // weights: empty (the diagonal: needs as many models as stems) or models x stems, row-major
 inline std::vector<StemTensor> demucs_inference_batch(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
@@ -926,74 +868,20 @@ inline std::vector<StemTensor> demucs_inference_batch(const demucs_bag &bag, con
                                                       const inference_options &opts = inference_options())
 {
     const char *who = "demucs_inference_batch (bag)";
-    const size_t T = tracks.size();
-    std::vector<StemTensor> out;
-    out.reserve(T);
-    if (T == 0)
-        return out;
-    const std::vector<int> shifts = detail::bag_shifts(who, bag, T, opts);
-    const float *w = detail::bag_weights(who, bag, weights);
-    std::vector<const float *> in(T);
-    std::vector<void *> dst(T);
-    std::vector<int64_t> n(T);
-    for (size_t t = 0; t < T; ++t)
-    {
-        out.emplace_back(bag.nb_sources, tracks[t].cols());
-        in[t] = tracks[t].data.data(), dst[t] = out[t].data.data(), n[t] = tracks[t].cols();
-    }
-    detail::CbThunk th{&cb};
-    std::lock_guard<std::mutex> guard(bag.lock);
-    if (dmx_tracks_infer_bag(bag.ctx, bag.models.data(), (int)bag.models.size(), w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap,
-                             shifts.data(), nullptr, dst.data(), nullptr, DMX_LAYOUT_EIGEN, detail::progress_thunk, &th) != DMX_OK)
-        detail::die(who);
-    return out;
+    if (tracks.empty())
+        return std::vector<StemTensor>();
+    const detail::BagCall b(who, bag, tracks.size(), weights, opts);
+    return detail::fp32_call(who, b.g, tracks, b.shifts, cb, &opts);
 }
 inline PcmOutputs demucs_inference_batch_pcm(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
                                              const std::vector<float> &weights, const inference_options &opts, const output_options &oo,
                                              std::vector<std::vector<float>> *peaks = nullptr)
 {
     const char *who = "demucs_inference_batch_pcm (bag)";
-    const size_t T = tracks.size();
-    PcmOutputs out(T);
-    if (T == 0)
-        return out;
-    const std::vector<int> shifts = detail::bag_shifts(who, bag, T, opts);
-    const float *w = detail::bag_weights(who, bag, weights);
-    const dmx_output_spec spec{oo.encoding, oo.clip, oo.two_stems};
-    const int n_out = oo.two_stems < 0 ? bag.nb_sources : 2;
-    std::vector<const float *> in(T);
-    std::vector<std::vector<unsigned char>> flat(T); // a track's outputs are consecutive across the ABI
-    std::vector<void *> dst(T);
-    std::vector<int64_t> n(T);
-    for (size_t t = 0; t < T; ++t)
-    {
-        in[t] = tracks[t].data.data(), n[t] = tracks[t].cols();
-        const int64_t per = dmx_output_bytes(&spec, n[t]);
-        if (per < 0)
-            detail::die(who);
-        flat[t].resize((size_t)(std::max<int64_t>(per, 1) * n_out));
-        dst[t] = flat[t].data();
-    }
-    std::vector<float> pk(T * (size_t)n_out, 0.0f);
-    detail::CbThunk th{&cb};
-    std::lock_guard<std::mutex> guard(bag.lock);
-    if (dmx_tracks_infer_bag(bag.ctx, bag.models.data(), (int)bag.models.size(), w, (int)T, in.data(), n.data(), opts.shifts, opts.overlap,
-                             shifts.data(), &spec, dst.data(), pk.data(), DMX_LAYOUT_EIGEN, detail::progress_thunk, &th) != DMX_OK)
-        detail::die(who);
-    for (size_t t = 0; t < T; ++t)
-    {
-        const size_t per = (size_t)dmx_output_bytes(&spec, n[t]);
-        for (int o = 0; o < n_out; ++o)
-            out[t].emplace_back(flat[t].begin() + (size_t)o * per, flat[t].begin() + (size_t)(o + 1) * per);
-        flat[t] = std::vector<unsigned char>();
-    }
-    if (peaks)
-    {
-        peaks->assign(T, std::vector<float>());
-        for (size_t t = 0; t < T; ++t)
-            (*peaks)[t].assign(pk.begin() + t * (size_t)n_out, pk.begin() + (t + 1) * (size_t)n_out);
-    }
-    return out;
+    if (tracks.empty())
+        return PcmOutputs();
+    const detail::BagCall b(who, bag, tracks.size(), weights, opts);
+    return detail::pcm_call(who, b.g, tracks, b.shifts, cb, opts, oo, peaks);
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
                                                const std::vector<float> &weights, const inference_options &opts, const remix_options &remix,
@@ -1002,11 +890,8 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std:
     const char *who = "demucs_inference_batch_remix (bag)";
     if (tracks.empty())
         return PcmOutputs();
-    const std::vector<int> shifts = detail::bag_shifts(who, bag, tracks.size(), opts);
-    const float *w = detail::bag_weights(who, bag, weights);
-    std::lock_guard<std::mutex> guard(bag.lock);
-    return detail::remix_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, tracks, shifts, cb, opts, remix,
-                              peaks);
+    const detail::BagCall b(who, bag, tracks.size(), weights, opts);
+    return detail::remix_call(who, b.g, tracks, b.shifts, cb, opts, remix, peaks);
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<FlacFile> &files, ProgressCallback cb,
                                                const std::vector<float> &weights, const inference_options &opts, const remix_options &remix,
@@ -1015,11 +900,8 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std:
     const char *who = "demucs_inference_batch_remix (bag, flac files)";
     if (files.empty())
         return PcmOutputs();
-    const std::vector<int> shifts = detail::bag_shifts(who, bag, files.size(), opts);
-    const float *w = detail::bag_weights(who, bag, weights);
-    std::lock_guard<std::mutex> guard(bag.lock);
-    return detail::flac_files_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, files, shifts, cb, opts, remix,
-                                   peaks, frames);
+    const detail::BagCall b(who, bag, files.size(), weights, opts);
+    return detail::flac_files_call(who, b.g, files, b.shifts, cb, opts, remix, peaks, frames);
 }
 // the same with tracks at their own rates (see the demucs_model overloads)
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, const std::vector<int> &rates,
@@ -1029,11 +911,8 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std:
     const char *who = "demucs_inference_batch_remix (bag, rates)";
     if (tracks.empty())
         return PcmOutputs();
-    const std::vector<int> shifts = detail::bag_shifts(who, bag, tracks.size(), opts);
-    const float *w = detail::bag_weights(who, bag, weights);
-    std::lock_guard<std::mutex> guard(bag.lock);
-    return detail::remix_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, tracks, shifts, cb, opts, remix,
-                              peaks, &rates);
+    const detail::BagCall b(who, bag, tracks.size(), weights, opts);
+    return detail::remix_call(who, b.g, tracks, b.shifts, cb, opts, remix, peaks, &rates);
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<FlacFile> &files, std::vector<int> &rates,
                                                ProgressCallback cb, const std::vector<float> &weights, const inference_options &opts,
@@ -1043,11 +922,8 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std:
     const char *who = "demucs_inference_batch_remix (bag, flac files, rates)";
     if (files.empty())
         return PcmOutputs();
-    const std::vector<int> shifts = detail::bag_shifts(who, bag, files.size(), opts);
-    const float *w = detail::bag_weights(who, bag, weights);
-    std::lock_guard<std::mutex> guard(bag.lock);
-    return detail::flac_files_call(who, bag.ctx, bag.models.data(), (int)bag.models.size(), w, bag.nb_sources, files, shifts, cb, opts, remix,
-                                   peaks, frames, &rates);
+    const detail::BagCall b(who, bag, files.size(), weights, opts);
+    return detail::flac_files_call(who, b.g, files, b.shifts, cb, opts, remix, peaks, frames, &rates);
 }
 
 // segment-level surface; src/model.hpp:569-647 (only the boundary members are kept:
@@ -1186,7 +1062,7 @@ inline std::vector<StemTensor> demucs_v3_inference_batch(const demucs_v3_model &
 inline std::vector<StemTensor> demucs_v3_inference_batch(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
                                                          ProgressCallback cb, const demucscpp::inference_options &opts)
 {
-    return demucscpp::detail::batch_call("demucs_v3_inference_batch", model, 4, tracks, cb, opts);
+    return demucscpp::detail::batch_call("demucs_v3_inference_batch", model, 4, tracks, cb, &opts);
 }
 
 inline demucscpp::PcmOutputs demucs_v3_inference_batch_pcm(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
