@@ -2,6 +2,7 @@
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
+//                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
 // (at 44.1 kHz, or with DMX_RESAMPLE=1 at any rate) the files go to the GPU as they are and are decoded there
@@ -36,6 +37,11 @@
 //   --flac                   write target_*.flac instead of target_*.wav (demucs's option; it takes no value): the same samples,
 //                            losslessly coded on the GPU (dmx_tracks_infer_flac; csrc/flac.hip), 16 bit by default, 24 bit
 //                            with --int24; --float32 --flac is an error. It combines with every option above and with bags.
+//   --loudnorm LUFS          bring every track's MIXTURE to LUFS (integrated loudness, ITU-R BS.1770; -70 .. 0) with one gain for all
+//                            of its outputs, so that the stems keep their balance (DMX_LOUD_MIXTURE); --loudnorm-each LUFS gives
+//                            every output its own gain (DMX_LOUD_EACH); --loudness only measures. --max-peak DB (default -1) is the
+//                            ceiling of the sample peak: the gain is reduced where it would be exceeded. A line per output is
+//                            printed: "vocals: -14.23 LUFS, gain +3.10 dB". They combine with every option above.
 //   --flac-level N           with --flac: 0 (default) FIXED predictors alone, 1 adds an LPC predictor of order 8, 2 orders 8
 //                            and 12 (smaller files, the same samples); without --flac it changes nothing
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
@@ -66,6 +72,7 @@ using namespace demucscpp;
     std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
+              << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB]"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
@@ -109,6 +116,9 @@ int main(int argc, const char **argv)
     std::string two_stems, remix_text;
     int other_method = -1; // DMX_OTHER_*, -1: not given
     int flac_level = 0;
+    int loud_mode = -1; // DMX_LOUD_*, -1: not given
+    float loud_target = -14.0f, max_peak_db = -1.0f;
+    LoudnessReport loud_report; // filled by the remix calls when a loudness flag is given
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -127,9 +137,30 @@ int main(int argc, const char **argv)
             --a;
             continue;
         }
+        if (opt == "--loudness") // no value: measure and report, the bytes stay
+        {
+            loud_mode = DMX_LOUD_MEASURE, with_out_opts = true;
+            --a;
+            continue;
+        }
         if (a + 1 >= argc)
             usage(argv[0]);
         const std::string val = argv[a + 1];
+        if (opt == "--loudnorm" || opt == "--loudnorm-each" || opt == "--max-peak")
+        {
+            char *end = nullptr;
+            errno = 0;
+            const float v = std::strtof(val.c_str(), &end);
+            if (val.empty() || errno || *end || !std::isfinite(v))
+                usage(argv[0]);
+            if (opt == "--max-peak")
+                max_peak_db = v;
+            else if (v < -70.0f || v > 0.0f) // the library's range for a target in LUFS
+                usage(argv[0]);
+            else
+                loud_target = v, loud_mode = opt == "--loudnorm" ? DMX_LOUD_MIXTURE : DMX_LOUD_EACH, with_out_opts = true;
+            continue;
+        }
         if (opt == "--two-stems")
         {
             if (stem_index(val) < 0)
@@ -247,7 +278,7 @@ int main(int argc, const char **argv)
         usage(argv[0]);
     }
     // minus, none, --remix and --flac leave through the remix entry points; everything else as before
-    const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE || flac;
+    const bool with_remix = !remix_text.empty() || other_method == DMX_OTHER_MINUS || other_method == DMX_OTHER_NONE || flac || loud_mode >= 0;
     remix_options remix;
     bool flac_in = false; // every input is a .flac file the GPU takes as it is (decided once the inputs have been looked at):
                           // at 44.1 kHz, or with DMX_RESAMPLE=1 at any rate
@@ -280,6 +311,11 @@ int main(int argc, const char **argv)
             exit(1);
         }
         remix.encoding = out_opts.encoding, remix.clip = out_opts.clip, remix.flac = flac, remix.flac_level = flac_level;
+        if (loud_mode >= 0)
+        {
+            remix.loudness.on = true, remix.loudness.mode = loud_mode, remix.loudness.target_lufs = loud_target;
+            remix.loudness.max_peak = (float)std::pow(10.0, (double)max_peak_db / 20.0);
+        }
         if (!with_out_opts) // FLAC inputs or other rates without an output option: the float32 stems, through unit gains
             remix.encoding = DMX_PCM_F32, remix.clip = DMX_CLIP_NONE;
     };
@@ -442,13 +478,13 @@ int main(int argc, const char **argv)
                   << " tracks" << std::endl;
         make_remix(nb_sources);
         if (flac_in && any_rate)
-            pcm_outs = demucs_inference_batch_remix(bag, flac_files, native_rate, cb, weights, opts, remix, nullptr, &flac_frames);
+            pcm_outs = demucs_inference_batch_remix(bag, flac_files, native_rate, cb, weights, opts, remix, nullptr, &flac_frames, &loud_report);
         else if (flac_in)
-            pcm_outs = demucs_inference_batch_remix(bag, flac_files, cb, weights, opts, remix, nullptr, &flac_frames);
+            pcm_outs = demucs_inference_batch_remix(bag, flac_files, cb, weights, opts, remix, nullptr, &flac_frames, &loud_report);
         else if (any_rate)
-            pcm_outs = demucs_inference_batch_remix(bag, tracks, native_rate, cb, weights, opts, remix);
+            pcm_outs = demucs_inference_batch_remix(bag, tracks, native_rate, cb, weights, opts, remix, nullptr, &loud_report);
         else if (with_remix)
-            pcm_outs = demucs_inference_batch_remix(bag, tracks, cb, weights, opts, remix);
+            pcm_outs = demucs_inference_batch_remix(bag, tracks, cb, weights, opts, remix, nullptr, &loud_report);
         else if (with_out_opts)
             pcm_outs = demucs_inference_batch_pcm(bag, tracks, cb, weights, opts, out_opts);
         else
@@ -465,13 +501,13 @@ int main(int argc, const char **argv)
         std::cout << "Starting Demucs v3 MMI inference of " << n_files << " tracks" << std::endl;
         make_remix(nb_sources);
         if (flac_in && any_rate)
-            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, native_rate, cb, opts, remix, nullptr, &flac_frames);
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, native_rate, cb, opts, remix, nullptr, &flac_frames, &loud_report);
         else if (flac_in)
-            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames);
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames, &loud_report);
         else if (any_rate)
-            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, native_rate, cb, opts, remix);
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, native_rate, cb, opts, remix, nullptr, &loud_report);
         else if (with_remix)
-            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, cb, opts, remix);
+            pcm_outs = demucscpp_v3::demucs_v3_inference_batch_remix(model, tracks, cb, opts, remix, nullptr, &loud_report);
         else if (with_out_opts)
             pcm_outs = demucscpp_v3::demucs_v3_inference_batch_pcm(model, tracks, cb, opts, out_opts);
         else
@@ -490,13 +526,13 @@ int main(int argc, const char **argv)
         std::cout << "Starting Demucs (" << nb_sources << "-source) inference of " << n_files << " tracks" << std::endl;
         make_remix(nb_sources);
         if (flac_in && any_rate)
-            pcm_outs = demucs_inference_batch_remix(model, flac_files, native_rate, cb, opts, remix, nullptr, &flac_frames);
+            pcm_outs = demucs_inference_batch_remix(model, flac_files, native_rate, cb, opts, remix, nullptr, &flac_frames, &loud_report);
         else if (flac_in)
-            pcm_outs = demucs_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames);
+            pcm_outs = demucs_inference_batch_remix(model, flac_files, cb, opts, remix, nullptr, &flac_frames, &loud_report);
         else if (any_rate)
-            pcm_outs = demucs_inference_batch_remix(model, tracks, native_rate, cb, opts, remix);
+            pcm_outs = demucs_inference_batch_remix(model, tracks, native_rate, cb, opts, remix, nullptr, &loud_report);
         else if (with_remix)
-            pcm_outs = demucs_inference_batch_remix(model, tracks, cb, opts, remix);
+            pcm_outs = demucs_inference_batch_remix(model, tracks, cb, opts, remix, nullptr, &loud_report);
         else if (with_out_opts)
             pcm_outs = demucs_inference_batch_pcm(model, tracks, cb, opts, out_opts);
         else
@@ -512,6 +548,23 @@ int main(int argc, const char **argv)
         {
             const int64_t frames = flac_in ? flac_frames[(size_t)f] : audio.cols();
             const auto &po = pcm_outs[(size_t)f];
+            for (size_t o = 0; loud_mode >= 0 && o <= po.size(); ++o) // the report: the outputs, then the mixture
+            {
+                const dmx_loudness_result &lr = loud_report[(size_t)f][o];
+                char line[160];
+                const std::string who = o < po.size() ? remix.names[o] : std::string("mixture");
+                if (lr.lufs_c == DMX_LUFS_UNMEASURABLE)
+                    snprintf(line, sizeof line, "%s: unmeasurable", who.c_str());
+                else
+                    snprintf(line, sizeof line, "%s: %.2f LUFS", who.c_str(), lr.lufs_c / 100.0);
+                std::cout << line;
+                if (o < po.size())
+                {
+                    snprintf(line, sizeof line, ", gain %+.2f dB", 20.0 * std::log10((double)lr.gain));
+                    std::cout << line;
+                }
+                std::cout << std::endl;
+            }
             for (size_t target = 0; target < po.size(); ++target)
             {
                 const std::string name = with_remix || flac_in || any_rate ? remix.names[target]

@@ -321,11 +321,11 @@ dmx_ctx::~dmx_ctx()
     {
         if (sl.copied)
             (void)hipEventDestroy(sl.copied);
-        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes, &sl.flacIn, &sl.flacInWork, &sl.flacInStatus, &sl.native, &sl.nativeOut})
+        for (DevBuf *b : {&sl.audio, &sl.tmp, &sl.out, &sl.stats, &sl.pcm, &sl.peaks, &sl.flac, &sl.flacWork, &sl.flacSizes, &sl.flacIn, &sl.flacInWork, &sl.flacInStatus, &sl.native, &sl.nativeOut, &sl.loud})
             if (b->p)
                 (void)hipFree(b->p);
     }
-    for (void *p : {(void *)dA, (void *)dPartials, (void *)dStats, (void *)dStatus, (void *)dRowScale[0], (void *)dRowScale[1], (void *)bAudio.p, (void *)bTmp.p, (void *)bMix.p,
+    for (void *p : {(void *)dA, (void *)dPartials, (void *)dStats, (void *)dStatus, (void *)dRowScale[0], (void *)dRowScale[1], (void *)dLoudTable, (void *)bAudio.p, (void *)bTmp.p, (void *)bMix.p,
                     (void *)bSegOut.p, (void *)bOut.p})
         if (p)
             (void)hipFree(p);

@@ -96,10 +96,12 @@ struct dmx_ctx
         DevBuf pcm, peaks; // dmx_tracks_infer_pcm: the encoded outputs (each at a 16-byte-rounded stride) and their peaks
         DevBuf flac, flacWork, flacSizes; // dmx_tracks_infer_flac: the files (stride dmx_flac_bound), the workspace, n_out int64 counts
         DevBuf flacIn, flacInWork, flacInStatus; // dmx_tracks_infer_from_flac: the file's bytes, the decoder's workspace, {status, good}
+        DevBuf loud; // dmx_tracks_infer_loud: n_out + 1 measurement workspaces, then 64 bytes of gains, then the n_out + 1 report entries
         DevBuf native, nativeOut; // dmx_tracks_infer_rates, a call with a converted track: the track [m][2] and its stems at its own rate
         hipEvent_t copied = nullptr; // on copyStream behind the last copy-out of the track that holds the slot (TracksPlan)
     };
     std::vector<TrackSlot> slots;
+    float *dLoudTable = nullptr; // dmx_tracks_infer_loud: the gain table (loud_gain_table), built and uploaded on the context's first such call
     int flacLevel = 0; // dmx_ctx_set_flac_level: 0 FIXED predictors alone, 1 + LPC order 8, 2 + LPC orders 8 and 12
     hipStream_t uploadStream = nullptr;
     hipEvent_t evUpload = nullptr;
@@ -195,6 +197,8 @@ namespace dmx { extern std::mutex g_graphMutex; }             // every HIP graph
 int dmx_pcm_check_spec(const char *fn, const dmx_output_spec *spec, int S); // S < 0: the model is not known yet
 int dmx_pcm_frame_bytes(int encoding);                                      // bytes of one stereo frame
 int dmx_remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, dmx::PcmGains *G, bool noModel);
+// ---- codec_api.cpp, used by tracks_exec.cpp (the loudness stage)
+int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate, int track); // track < 0: no track to name
 
 // ---- internal entry points used by engine.cpp
 int dmx_ensure_buf(DevBuf &b, dmx::i64 floats);

@@ -3,6 +3,7 @@
 #include "api_internal.h"
 
 #include <climits>
+#include <cmath>
 
 using namespace dmx;
 
@@ -130,6 +131,264 @@ extern "C" int dmx_remix_encode(int device, const float *planes, int n_sources, 
         return fail(DMX_ERR_HIP, "%s: upload failed", fn);
     DMXCHK(dmx_remix_encode_device(device, dIn, n_sources, n, n, dMix, spec, dOut, dPeaks, nullptr));
     return pcm_download(fn, out, peaks, dOut, dPeaks, nOut, bytes, devStride);
+}
+
+// --------------------------------------------------------------------------- loudness (loudness.hip)
+extern "C" int dmx_loudness_coefficients(int rate, double *coef)
+{
+    if (!coef)
+        return fail(DMX_ERR_ARG, "dmx_loudness_coefficients: null coef pointer");
+    if (rate < DMX_LOUD_MIN_RATE)
+        return fail(DMX_ERR_ARG, "dmx_loudness_coefficients: rate %d is below %d Hz", rate, DMX_LOUD_MIN_RATE);
+    loud_coefficients(rate, coef);
+    return DMX_OK;
+}
+extern "C" int dmx_loudness_gain_table(float *table)
+{
+    if (!table)
+        return fail(DMX_ERR_ARG, "dmx_loudness_gain_table: null table pointer");
+    loud_gain_table(table);
+    return DMX_OK;
+}
+extern "C" int64_t dmx_loudness_workspace_bytes(int64_t n) { return loud_workspace_bytes(n); }
+
+int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate, int track)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: null loudness spec", fn);
+    if (spec->mode != DMX_LOUD_MEASURE && spec->mode != DMX_LOUD_MIXTURE && spec->mode != DMX_LOUD_EACH)
+        return fail(DMX_ERR_ARG, "%s: loudness spec: mode %d (DMX_LOUD_MEASURE 0, DMX_LOUD_MIXTURE 1, DMX_LOUD_EACH 2)", fn, spec->mode);
+    if (!std::isfinite(spec->target_lufs) || spec->target_lufs < -70.0f || spec->target_lufs > 0.0f)
+        return fail(DMX_ERR_ARG, "%s: loudness spec: target_lufs %g is not in [-70, 0]", fn, (double)spec->target_lufs);
+    if (!(spec->max_peak > 0.0f))
+        return fail(DMX_ERR_ARG, "%s: loudness spec: max_peak %g is not above 0", fn, (double)spec->max_peak);
+    if (rate < DMX_LOUD_MIN_RATE && track >= 0)
+        return fail(DMX_ERR_ARG, "%s: track %d: loudness: rate %d is below %d Hz", fn, track, rate, DMX_LOUD_MIN_RATE);
+    if (rate < DMX_LOUD_MIN_RATE)
+        return fail(DMX_ERR_ARG, "%s: loudness: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
+    return DMX_OK;
+}
+static int loud_check(const char *fn, const dmx_loudness_spec *spec, int rate) { return dmx_loud_check_spec(fn, spec, rate, -1); }
+extern "C" int dmx_loudness_check(const dmx_loudness_spec *spec, int rate) { return loud_check("dmx_loudness_check", spec, rate); }
+
+// the stage alone has no context to own the gain table: one copy per device, made on first use (a blocking upload) and kept
+// for the life of the process (48 KB; the track path keeps its own in the context, dmx_ctx::dLoudTable)
+static int loud_table(int device, const float **T)
+{
+    static std::mutex mu;
+    static std::map<int, float *> tables;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = tables.find(device);
+    if (it == tables.end())
+    {
+        std::vector<float> h(kLoudGainSteps);
+        loud_gain_table(h.data());
+        float *d = nullptr;
+        HIPCHK(hipMalloc(&d, sizeof(float) * h.size()));
+        if (hipMemcpy(d, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+        {
+            (void)hipFree(d);
+            return fail(DMX_ERR_HIP, "loudness: the gain table's upload failed");
+        }
+        it = tables.emplace(device, d).first;
+    }
+    *T = it->second;
+    return DMX_OK;
+}
+
+// one stereo signal as a one-row gain table: planar through source 0 of one "stem", interleaved through the mixture column
+static void loud_signal(const float *d_x, int64_t n, int64_t plane_stride, RemixPiece *pc, PcmGains *G)
+{
+    *G = PcmGains{};
+    G->nOut = 1, G->S = plane_stride ? 1 : 0;
+    G->g[0][0] = 1.0f;
+    *pc = RemixPiece{PcmPiece{plane_stride ? d_x : nullptr, nullptr, nullptr, n, plane_stride, 0, 0, n}, plane_stride ? nullptr : d_x};
+}
+
+// marks: null, or five events around the four launches
+static int loudness_device(const char *fn, int device, const float *d_x, int64_t n, int64_t plane_stride, int rate,
+                           dmx_loudness_result *d_result, double *d_e, void *d_work, void *stream, hipEvent_t *marks)
+{
+    if (rate < DMX_LOUD_MIN_RATE)
+        return fail(DMX_ERR_ARG, "%s: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
+    if (n < 1 || n >= (int64_t)1 << 36 || (plane_stride != 0 && plane_stride < n))
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n < 2^36; plane_stride 0 or >= n)", fn, (long long)n,
+                    (long long)plane_stride);
+    if (!d_x || !d_result || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_x ? "d_x" : !d_result ? "d_result" : "d_work");
+    if (((uintptr_t)d_x & 3) != 0 || ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_result & 7) != 0 || ((uintptr_t)d_e & 7) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_x must be 4-byte aligned, d_work 16-byte aligned, d_result and d_e 8-byte aligned", fn);
+    LoudPlan lp;
+    if (loud_plan(rate, n, &lp) != 0)
+        return fail(DMX_ERR_ARG, "%s: no plan for rate %d, n %lld", fn, rate, (long long)n);
+    HIPCHK(hipSetDevice(device));
+    RemixPiece pc;
+    PcmGains G;
+    loud_signal(d_x, n, plane_stride, &pc, &G);
+    launch_loud_measure(pc, G, lp, (unsigned char *)d_work, 0, d_e, d_result, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_loudness_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                                   double *d_e, void *d_work, void *stream)
+{
+    return loudness_device("dmx_loudness_device", device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, nullptr);
+}
+
+extern "C" int dmx_loudness_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate,
+                                         dmx_loudness_result *d_result, double *d_e, void *d_work, void *stream, float *ms)
+{
+    const char *fn = "dmx_loudness_device_timed";
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    hipEvent_t ev[7] = {};
+    unsigned *dPeak = nullptr;
+    int rc = DMX_OK;
+    for (hipEvent_t &e : ev)
+        if (rc == DMX_OK && hipEventCreate(&e) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+    if (rc == DMX_OK && hipMalloc(&dPeak, sizeof(unsigned)) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK)
+        rc = loudness_device(fn, device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, ev);
+    if (rc == DMX_OK)
+    {
+        RemixPiece pc;
+        PcmGains G;
+        loud_signal(d_x, n, plane_stride, &pc, &G);
+        pc.peaks = dPeak;
+        (void)hipMemsetAsync(dPeak, 0, sizeof(unsigned), s);
+        (void)hipEventRecord(ev[5], s);
+        launch_remix_peak(&pc, 1, G, s);
+        (void)hipEventRecord(ev[6], s);
+        if (hipEventSynchronize(ev[6]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    }
+    for (int i = 0; i < 4 && rc == DMX_OK; ++i)
+        if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    if (rc == DMX_OK && hipEventElapsedTime(&ms[4], ev[5], ev[6]) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    for (hipEvent_t e : ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    if (dPeak)
+        (void)hipFree(dPeak);
+    return rc;
+}
+
+extern "C" int dmx_loudness(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e)
+{
+    const char *fn = "dmx_loudness";
+    if (rate < DMX_LOUD_MIN_RATE)
+        return fail(DMX_ERR_ARG, "%s: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
+    if (!x || !result || n < 1 || n >= (int64_t)1 << 36)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer, n < 1 or n >= 2^36)", fn);
+    HIPCHK(hipSetDevice(device));
+    const size_t inBytes = sizeof(float) * 2 * (size_t)n, eBytes = sizeof(double) * 2 * (size_t)(n / ((rate + 5) / 10));
+    DevScratch d;
+    float *dX = (float *)d.get(inBytes);
+    void *dWork = d.get((size_t)loud_workspace_bytes(n));
+    dmx_loudness_result *dRes = (dmx_loudness_result *)d.get(sizeof(dmx_loudness_result));
+    double *dE = e && eBytes ? (double *)d.get(eBytes) : nullptr;
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (hipMemcpy(dX, x, inBytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(loudness_device(fn, device, dX, n, interleaved ? 0 : n, rate, dRes, dE, dWork, nullptr, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(result, dRes, sizeof(dmx_loudness_result), hipMemcpyDeviceToHost) != hipSuccess ||
+        (dE && hipMemcpy(e, dE, eBytes, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
+}
+
+extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride, const float *d_mix,
+                                      const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out, float *d_peaks,
+                                      dmx_loudness_result *d_report, void *d_work, void *stream)
+{
+    const char *fn = "dmx_loud_encode_device";
+    PcmGains G;
+    DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
+    DMXCHK(loud_check(fn, loud, rate));
+    if (!d_planes || !d_out || !d_peaks || !d_mix || !d_report || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn,
+                    !d_planes ? "d_planes" : !d_out ? "d_out" : !d_peaks ? "d_peaks" : !d_mix ? "d_mix" : !d_report ? "d_report" : "d_work");
+    if (n < 1 || n >= (int64_t)1 << 36 || plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n <= plane_stride, n < 2^36)", fn, (long long)n,
+                    (long long)plane_stride);
+    if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_planes & 3) != 0 || ((uintptr_t)d_peaks & 3) != 0 || ((uintptr_t)d_mix & 3) != 0 ||
+        ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_report & 7) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_out and d_work must be 16-byte aligned, d_report 8-byte aligned, d_planes, d_mix and d_peaks 4-byte aligned",
+                    fn);
+    LoudPlan lp;
+    if (loud_plan(rate, n, &lp) != 0)
+        return fail(DMX_ERR_ARG, "%s: no plan for rate %d, n %lld", fn, rate, (long long)n);
+    HIPCHK(hipSetDevice(device));
+    const float *T = nullptr;
+    DMXCHK(loud_table(device, &T));
+    hipStream_t s = (hipStream_t)stream;
+    const i64 slotBytes = loud_workspace_bytes(n);
+    unsigned char *work = (unsigned char *)d_work;
+    float *gains = (float *)(work + (i64)(G.nOut + 1) * slotBytes);
+    HIPCHK(hipMemsetAsync(d_peaks, 0, sizeof(float) * (size_t)G.nOut, s));
+    LoudPiece pp;
+    static_cast<PcmPiece &>(pp) = PcmPiece{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
+                                           DMX_OUTPUT_STRIDE(n * dmx_pcm_frame_bytes(spec->encoding)), 0, n};
+    pp.mix = d_mix;
+    pp.gains = gains;
+    PcmGains M{}; // the mixture as a one-row table of its own: its slot is the last
+    M.nOut = 1, M.S = G.S;
+    M.g[0][G.S] = 1.0f;
+    launch_loud_measure(pp, G, lp, work, 0, nullptr, nullptr, s);
+    launch_loud_measure(pp, M, lp, work, G.nOut, nullptr, nullptr, s);
+    launch_remix_peak(&pp, 1, G, s);
+    launch_loud_gain(work, slotBytes, G.nOut, (unsigned *)d_peaks, loud->mode, (int)rintf(100.0f * loud->target_lufs), loud->max_peak, T, gains,
+                     d_report, s);
+    if (loud->mode == DMX_LOUD_MEASURE)
+        launch_remix_encode(&pp, 1, G, spec->encoding, spec->clip, s);
+    else
+        launch_loud_encode(&pp, 1, G, spec->encoding, spec->clip, s);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_loud_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                               const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report)
+{
+    const char *fn = "dmx_loud_encode";
+    PcmGains G;
+    DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
+    DMXCHK(loud_check(fn, loud, rate));
+    if (!planes || !out || !mix || n < 1 || n >= (int64_t)1 << 36)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null planes, mix or out pointer, n < 1 or n >= 2^36)", fn);
+    HIPCHK(hipSetDevice(device));
+    const int nOut = G.nOut;
+    const i64 bytes = n * dmx_pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
+    const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n, mixBytes = sizeof(float) * 2 * (size_t)n;
+    const size_t workBytes = (size_t)((nOut + 1) * loud_workspace_bytes(n) + 64);
+    const size_t smallBytes = 256 + sizeof(dmx_loudness_result) * (size_t)(nOut + 1); // the peaks, then the report
+    DevScratch d;
+    float *dIn = (float *)d.get(inBytes + DMX_OUTPUT_STRIDE(mixBytes)); // the planes, then the mixture
+    unsigned char *dOut = (unsigned char *)d.get((size_t)(nOut * devStride));
+    unsigned char *dSmall = (unsigned char *)d.get(smallBytes);
+    void *dWork = d.get(workBytes);
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    float *dMix = dIn + (size_t)n_sources * 2 * (size_t)n;
+    float *dPeaks = (float *)dSmall;
+    dmx_loudness_result *dReport = (dmx_loudness_result *)(dSmall + 256);
+    if (hipMemcpy(dIn, planes, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dMix, mix, mixBytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(dmx_loud_encode_device(device, dIn, n_sources, n, n, dMix, spec, loud, rate, dOut, dPeaks, dReport, dWork, nullptr));
+    DMXCHK(pcm_download(fn, out, peaks, dOut, dPeaks, nOut, bytes, devStride));
+    if (report && hipMemcpy(report, dReport, sizeof(dmx_loudness_result) * (size_t)(nOut + 1), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
 }
 
 // --------------------------------------------------------------------------- FLAC output (flac.hip)

@@ -2,6 +2,7 @@
 // Semantics of every op are specified by plan.h and, executable, by tests/cpu_interp.cpp.
 #pragma once
 #include "gemm_select.h"
+#include "loudness_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -409,6 +410,28 @@ struct RemixTable
 };
 void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s);
 void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// ---- the loudness stage (loudness.hip; specification: DESIGN.md section 2.14, restated in tests/loudness_spec.py) ----
+struct LoudPiece : RemixPiece
+{
+    const float *gains; // G.nOut gains on the device (launch_loud_gain)
+};
+struct LoudTable
+{
+    static const int kMax = 32;
+    LoudPiece p[kMax];
+};
+// launch_remix_encode with every gathered sample multiplied by its output's gain before clip (pcm.hip)
+void launch_loud_encode(const LoudPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// (LoudPlan and the pure host functions: loudness_plan.h)
+// measures the G.nOut outputs of the piece's frames [0, lp.n): signal o uses the workspace slot work + (slot0 + o) *
+// loud_workspace_bytes(n) (16-byte aligned). Four launches on s. eOut: NULL, or G.nOut x 2 x H hop energies on the device;
+// resOut: NULL, or G.nOut entries {int32 lufs_c, float 0, double L}. marks: NULL, or five events around the four launches.
+void launch_loud_measure(const RemixPiece &pc, const PcmGains &G, const LoudPlan &lp, unsigned char *work, int slot0, double *eOut,
+                         void *resOut, hipStream_t s, hipEvent_t *marks = nullptr);
+// behind the measurement of nOut outputs (slots 0 .. nOut - 1) and the mixture (slot nOut) and behind the peak kernel: the gains
+// (DMX_LOUD_*), peaks[o] *= gain, and the report of nOut + 1 entries; all on the device, one launch
+void launch_loud_gain(const unsigned char *work, i64 slotBytes, int nOut, unsigned *peaks, int mode, int targetC, float maxPeak,
+                      const float *table, float *gains, void *report, hipStream_t s);
 // ---- the track path's converter (resample.hip) ----
 // outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
 // output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the

@@ -22,9 +22,10 @@
 // Sources are visited in increasing index, a source with gain 0 is NOT read (a uniform branch: the table sits in the kernel
 // arguments), the first visited source gives a = g * x and each later one p = g * x, a = a + p - every product and every sum
 // its own correctly rounded fp32 operation. hipcc contracts device code by default, so the gather is compiled with
-// contraction off (remix_acc below); no fused multiply-add may appear in it. The mixture's 4 frames are 32 contiguous
+// contraction off (remix_acc, pcm_gather.h); no fused multiply-add may appear in it. The mixture's 4 frames are 32 contiguous
 // bytes: two 16-byte loads when aligned, dword loads otherwise and in the edge group.
 #include "kernels.h"
+#include "pcm_gather.h"
 
 #include "../../include/demucs_hip.h"
 
@@ -35,124 +36,6 @@ namespace dmx
 {
 namespace
 {
-// 4 frames (cnt of them valid) of plane p starting at frame i
-__device__ __forceinline__ void pcm_load4(const float *plane, i64 i, int cnt, float v[4])
-{
-    const float *q = plane + i;
-    if (cnt == 4 && ((uintptr_t)q & 15) == 0)
-    {
-        const float4 t = *reinterpret_cast<const float4 *>(q);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    }
-    else
-    {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            v[k] = k < cnt ? q[k] : 0.0f;
-    }
-}
-// the two channels of output o for frames [i, i + cnt)
-__device__ __forceinline__ void pcm_gather(const PcmPiece &pc, int S, int stem, int o, i64 i, int cnt, float L[4], float R[4])
-{
-    if (stem < 0 || o == 0)
-    {
-        const int s = stem < 0 ? o : stem;
-        pcm_load4(pc.planes + (i64)(2 * s) * pc.planeStride, i, cnt, L);
-        pcm_load4(pc.planes + (i64)(2 * s + 1) * pc.planeStride, i, cnt, R);
-        return;
-    }
-    bool first = true;
-    for (int s = 0; s < S; ++s)
-    {
-        if (s == stem)
-            continue;
-        float a[4], b[4];
-        pcm_load4(pc.planes + (i64)(2 * s) * pc.planeStride, i, cnt, a);
-        pcm_load4(pc.planes + (i64)(2 * s + 1) * pc.planeStride, i, cnt, b);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-        {
-            L[k] = first ? a[k] : L[k] + a[k];
-            R[k] = first ? b[k] : R[k] + b[k];
-        }
-        first = false;
-    }
-}
-// frames [i, i + cnt) of the interleaved mixture: L0 R0 L1 R1 ...
-__device__ __forceinline__ void pcm_load_mix4(const float *mix, i64 i, int cnt, float L[4], float R[4])
-{
-    const float *q = mix + 2 * i;
-    if (cnt == 4 && ((uintptr_t)q & 15) == 0)
-    {
-        const float4 t = reinterpret_cast<const float4 *>(q)[0], u = reinterpret_cast<const float4 *>(q)[1];
-        L[0] = t.x, R[0] = t.y, L[1] = t.z, R[1] = t.w;
-        L[2] = u.x, R[2] = u.y, L[3] = u.z, R[3] = u.w;
-    }
-    else
-    {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-        {
-            L[k] = k < cnt ? q[2 * k] : 0.0f;
-            R[k] = k < cnt ? q[2 * k + 1] : 0.0f;
-        }
-    }
-}
-// a = g x for the first visited source, then p = g x, a = a + p: two roundings, never one
-__device__ __forceinline__ void remix_acc(float g, const float x[4], bool first, float a[4])
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-    {
-        const float p = g * x[k];
-        a[k] = first ? p : a[k] + p;
-    }
-}
-// the two channels of output o for frames [i, i + cnt) under a gain table
-__device__ __forceinline__ void remix_gather(const RemixPiece &pc, const PcmGains &G, int o, i64 i, int cnt, float L[4], float R[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        L[k] = R[k] = 0.0f; // a checked spec has a non-zero gain in every row: never what is used
-    bool first = true;
-    for (int s = 0; s < G.S; ++s)
-    {
-        const float g = G.g[o][s];
-        if (g == 0.0f) // uniform: the plane is not loaded
-            continue;
-        float a[4], b[4];
-        pcm_load4(pc.planes + (i64)(2 * s) * pc.planeStride, i, cnt, a);
-        pcm_load4(pc.planes + (i64)(2 * s + 1) * pc.planeStride, i, cnt, b);
-        remix_acc(g, a, first, L);
-        remix_acc(g, b, first, R);
-        first = false;
-    }
-    const float gm = G.g[o][G.S];
-    if (gm != 0.0f)
-    {
-        float a[4], b[4];
-        pcm_load_mix4(pc.mix, i, cnt, a, b);
-        remix_acc(gm, a, first, L);
-        remix_acc(gm, b, first, R);
-    }
-}
-struct GatherStems // dmx_output_spec: a stem, or the sum of the others
-{
-    int S, stem;
-    __device__ __forceinline__ void operator()(const PcmPiece &pc, int o, i64 i, int cnt, float L[4], float R[4]) const
-    {
-        pcm_gather(pc, S, stem, o, i, cnt, L, R);
-    }
-};
-struct GatherRemix // dmx_remix_spec: a row of gains
-{
-    const PcmGains &G;
-    __device__ __forceinline__ void operator()(const RemixPiece &pc, int o, i64 i, int cnt, float L[4], float R[4]) const
-    {
-        remix_gather(pc, G, o, i, cnt, L, R);
-    }
-};
 __device__ __forceinline__ int pcm_quant(float y, float scale, float lo, float hi)
 {
     float t = rintf(y * scale); // v_rndne_f32: ties to even
@@ -204,7 +87,9 @@ __device__ __forceinline__ void pcm_peak_body(const Table &t, const Gather &gath
     }
 }
 
-template <int ENC, class Table, class Gather>
+// GAIN (the loudness stage): the gathered value is multiplied by the output's gain pc.gains[o], one
+// fp32 product per sample, before clip; pc.peaks[o] then holds the peak of the gained samples (loud_gain_kernel)
+template <int ENC, bool GAIN = false, class Table, class Gather>
 __device__ __forceinline__ void pcm_encode_body(const Table &t, int clip, const Gather &gather)
 {
     const auto &pc = t.p[blockIdx.z];
@@ -228,6 +113,13 @@ __device__ __forceinline__ void pcm_encode_body(const Table &t, int clip, const 
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             y[2 * k] = L[k], y[2 * k + 1] = R[k];
+        if constexpr (GAIN)
+        {
+            const float gn = pc.gains[o];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                y[k] = gn * y[k];
+        }
         if (clip == DMX_CLIP_CLAMP)
         {
 #pragma unroll
@@ -317,6 +209,12 @@ __global__ __launch_bounds__(256) void remix_encode_kernel(RemixTable t, PcmGain
 {
     pcm_encode_body<ENC>(t, clip, GatherRemix{G});
 }
+// the remix encode behind a per-output gain read from device memory: grid (blocks, G.nOut, pieces)
+template <int ENC>
+__global__ __launch_bounds__(256) void loud_encode_kernel(LoudTable t, PcmGains G, int clip)
+{
+    pcm_encode_body<ENC, true>(t, clip, GatherRemix{G});
+}
 
 namespace
 {
@@ -378,6 +276,17 @@ void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int
             hipLaunchKernelGGL(remix_encode_kernel<DMX_PCM_S16>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
         else
             hipLaunchKernelGGL(remix_encode_kernel<DMX_PCM_S24>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+    });
+}
+void launch_loud_encode(const LoudPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s)
+{
+    pcm_for_tables<LoudTable>(pieces, P, [&](const LoudTable &t, int nt, int gx) {
+        if (encoding == DMX_PCM_F32)
+            hipLaunchKernelGGL(loud_encode_kernel<DMX_PCM_F32>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+        else if (encoding == DMX_PCM_S16)
+            hipLaunchKernelGGL(loud_encode_kernel<DMX_PCM_S16>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+        else
+            hipLaunchKernelGGL(loud_encode_kernel<DMX_PCM_S24>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
     });
 }
 

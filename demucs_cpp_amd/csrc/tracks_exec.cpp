@@ -131,6 +131,12 @@ struct PcmOut // the output spec of a call, checked (dmx_pcm_check_spec)
     int64_t *sizes;
     const int *rates; // dmx_tracks_infer_rates: the tracks' own rates, which their files carry; NULL: flacRate
     int flac_rate(int t) const { return rates ? rates[t] : flacRate; }
+    // dmx_tracks_infer_loud (remix specs only): the checked spec, the report (n_out + 1 entries per track) and
+    // the device's gain table; else NULL
+    const dmx_loudness_spec *loud;
+    dmx_loudness_result *report;
+    const float *loudTable;
+    bool gained() const { return loud && loud->mode != DMX_LOUD_MEASURE; }
 };
 // One call of the track path. shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches
 // track_ola_kernel and N >= 2 track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
@@ -175,6 +181,8 @@ struct TracksRun
     std::vector<RemixPiece> pieces, whole; // the PCM stage's; under a remix spec the mixture is the slot's upload
     std::vector<PcmPiece> pcmPeak, pcmEnc;  // the same without the mixture, for the kernels of an output spec
     std::vector<ResamplePiece> conv;        // the converter's, of one ratio
+    std::vector<LoudPlan> loudPlans;        // per track, made before the first batch (host arithmetic)
+    std::vector<LoudPiece> loudEnc;         // the whole tracks of a batch, each with its gains
 
     const dmx_ctx::TrackSlot &slot(int t) const { return c->slots[(size_t)plan.jobs[(size_t)t].slot]; }
 };
@@ -211,6 +219,8 @@ static int tracks_prepare(TracksRun &r)
         {
             DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(omax * pcm->frameBytes) / 4)));
             DMXCHK(dmx_ensure_buf(sl.peaks, 8));
+            if (pcm->loud)
+                DMXCHK(dmx_ensure_buf(sl.loud, ((pcm->nOut + 1) * (loud_workspace_bytes(omax) + (i64)sizeof(dmx_loudness_result)) + 64) / 4));
             if (pcm->flacBits)
             {
                 DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, omax) / 4)));
@@ -430,7 +440,40 @@ static int tracks_output_stage(TracksRun &r, int k)
         }
     }
     const std::vector<RemixPiece> &enc = r.wholeTrack ? r.whole : r.pieces;
-    if (pcm->remix)
+    if (pcm->loud)
+    {
+        // behind a track's last piece: its outputs and its mixture are measured, and one launch turns lufs_c and the peaks into
+        // the gains, the gained peaks and the report; the gained tracks are whole-track ones, encoded here with their gains
+        launch_remix_peak(r.pieces.data(), (int)r.pieces.size(), *pcm->remix, s);
+        r.loudEnc.clear();
+        PcmGains M{}; // the mixture as a one-row table: its slot is the last
+        M.nOut = 1, M.S = pcm->remix->S;
+        M.g[0][M.S] = 1.0f;
+        for (size_t x = 0, w = 0; x < p.pcm[(size_t)k].size(); ++x)
+        {
+            const PcmRange &g = p.pcm[(size_t)k][x];
+            if (g.hi != p.jobs[(size_t)g.t].outFrames())
+                continue;
+            const RemixPiece &pp = r.whole[w++];
+            const LoudPlan &lp = r.loudPlans[(size_t)g.t];
+            const i64 slotBytes = loud_workspace_bytes(lp.n);
+            unsigned char *work = (unsigned char *)r.slot(g.t).loud.p;
+            float *gains = (float *)(work + (i64)(pcm->nOut + 1) * slotBytes);
+            launch_loud_measure(pp, *pcm->remix, lp, work, 0, nullptr, nullptr, s);
+            launch_loud_measure(pp, M, lp, work, pcm->nOut, nullptr, nullptr, s);
+            launch_loud_gain(work, slotBytes, pcm->nOut, pp.peaks, pcm->loud->mode, (int)rintf(100.0f * pcm->loud->target_lufs),
+                             pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
+            LoudPiece lq;
+            static_cast<RemixPiece &>(lq) = pp;
+            lq.gains = gains;
+            r.loudEnc.push_back(lq);
+        }
+        if (pcm->gained())
+            launch_loud_encode(r.loudEnc.data(), (int)r.loudEnc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
+        else
+            launch_remix_encode(enc.data(), (int)enc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
+    }
+    else if (pcm->remix)
     {
         launch_remix_peak(r.pieces.data(), (int)r.pieces.size(), *pcm->remix, s);
         launch_remix_encode(enc.data(), (int)enc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
@@ -496,6 +539,10 @@ static int tracks_copy_pcm(TracksRun &r, int k, const PcmRange &g)
     if (last && pcm->peaks)
         HIPCHK(hipMemcpyAsync(pcm->peaks + (size_t)g.t * pcm->nOut, sl.peaks.p, sizeof(float) * (size_t)pcm->nOut, hipMemcpyDeviceToHost,
                               c->copyStream));
+    if (last && pcm->report) // the report leaves with the peaks
+        HIPCHK(hipMemcpyAsync(pcm->report + (size_t)g.t * (pcm->nOut + 1),
+                              (const unsigned char *)sl.loud.p + (size_t)((pcm->nOut + 1) * loud_workspace_bytes(n) + 64),
+                              sizeof(dmx_loudness_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
     return DMX_OK;
 }
 
@@ -582,7 +629,7 @@ static int tracks_run_impl(TracksRun &r)
     r.blk = (i64)r.S * 2 * c->seg;
     r.eigen = r.layout == DMX_LAYOUT_EIGEN ? 1 : 0;
     r.olaEigen = r.pcm ? 0 : r.eigen; // the PCM stage reads planes
-    r.wholeTrack = r.pcm && r.pcm->spec.clip == DMX_CLIP_RESCALE;
+    r.wholeTrack = r.pcm && (r.pcm->spec.clip == DMX_CLIP_RESCALE || r.pcm->gained());
     std::string why;
     std::vector<int64_t> n44; // the plan is made on the tracks' lengths at 44.1 kHz
     if (r.rates)
@@ -600,6 +647,13 @@ static int tracks_run_impl(TracksRun &r)
         DMXCHK(tracks_check_bag_caps(r));
     DMXCHK(tracks_prepare(r));
     const TracksPlan &p = r.plan;
+    if (r.pcm && r.pcm->loud)
+    {
+        r.loudPlans.resize((size_t)p.T);
+        for (int t = 0; t < p.T; ++t)
+            if (loud_plan(r.rates ? r.rates[t] : 44100, p.jobs[(size_t)t].outFrames(), &r.loudPlans[(size_t)t]) != 0)
+                return fail(DMX_ERR_ARG, "%s: track %d: no loudness plan for %lld frames", r.fn, t, (long long)p.jobs[(size_t)t].outFrames());
+    }
     if (r.progress)
         r.progress(0.0f, "1., apply model w/ shift", r.user);
     int tLo = 0; // first track of the current batch
@@ -751,6 +805,8 @@ struct TracksCall
     int flacRate;
     int64_t *flacSizes;
     const int *rates;            // dmx_tracks_infer_rates: n[t] frames at rates[t] (checked: check_tracks_rates); else NULL, all 44100
+    const dmx_loudness_spec *loud; // dmx_tracks_infer_loud: the loudness stage behind a remix spec, and its report; else NULL
+    dmx_loudness_result *report;
     const dmx_flac_info *flacIn; // dmx_tracks_infer_from_flac: audio[t] is a file image, described here; else NULL
     const int64_t *fileBytes;
     int64_t *trackStatus;
@@ -1086,6 +1142,19 @@ static int tracks_call(const TracksCall &a)
         pcm = PcmOut{*a.spec, a.out, a.peaks, a.spec->stem < 0 ? S : 2, dmx_pcm_frame_bytes(a.spec->encoding), nullptr, 0, 0, nullptr};
     if (a.kind == TRACKS_OUT_FLAC)
         pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = a.flacRate, pcm.sizes = a.flacSizes, pcm.rates = a.rates;
+    if (remix && a.loud)
+    {
+        pcm.loud = a.loud, pcm.report = a.report;
+        if (!a.c->dLoudTable) // once per context: built on the host, uploaded, freed with the context
+        {
+            std::vector<float> h((size_t)kLoudGainSteps);
+            loud_gain_table(h.data());
+            HIPCHK(hipSetDevice(a.c->m->device));
+            HIPCHK(hipMalloc(&a.c->dLoudTable, sizeof(float) * h.size()));
+            HIPCHK(hipMemcpy(a.c->dLoudTable, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+        }
+        pcm.loudTable = a.c->dLoudTable;
+    }
     // (track, copy) order; with models (track, model, copy) order
     const std::vector<int> shifts = draw_shifts(a.bag ? a.n_tracks * a.n_models : a.n_tracks, a.n_shifts, a.shift_offsets);
     TracksRun r;
@@ -1178,7 +1247,8 @@ static int check_tracks_rates(const char *fn, int n_tracks, const int64_t *n, co
 static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights,
                             int n_tracks, const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
                             const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes, float *peaks,
-                            int64_t *track_status, dmx_progress_fn progress, void *user)
+                            int64_t *track_status, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud = nullptr,
+                            dmx_loudness_result *report = nullptr)
 {
     if (n_tracks < 1)
         return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
@@ -1203,6 +1273,8 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
         ns[(size_t)t] = infos[(size_t)t].total_samples;
         rates[(size_t)t] = infos[(size_t)t].sample_rate;
     }
+    for (int t = 0; loud && t < n_tracks; ++t) // the loudness stage's own floor on a rate, with the track's number
+        DMXCHK(dmx_loud_check_spec(fn, loud, rates[(size_t)t], t));
     if (anyRate)
         DMXCHK(check_tracks_rates(fn, n_tracks, ns.data(), rates.data(), flac_out != 0));
     TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
@@ -1212,6 +1284,7 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
     a.n_tracks = n_tracks, a.audio = reinterpret_cast<const float *const *>(files), a.n = ns.data();
     a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.flacIn = infos.data(), a.fileBytes = file_bytes, a.trackStatus = track_status;
+    a.loud = loud, a.report = report;
     a.out = out, a.peaks = peaks, a.layout = DMX_LAYOUT_EIGEN, a.progress = progress, a.user = user;
     DMXCHK(tracks_call(a)); // (track_status: -1 until the track's own arrives)
     for (int t = 0; t < n_tracks; ++t)
@@ -1259,4 +1332,42 @@ extern "C" int dmx_tracks_infer_rates(dmx_ctx *c, const dmx_model *const *models
     a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
     return tracks_call(a);
+}
+
+// dmx_tracks_infer_rates / dmx_tracks_infer_from_flac_rates behind the loudness stage
+extern "C" int dmx_tracks_infer_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                     const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                                     const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                     float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                                     dmx_loudness_result *report)
+{
+    const char *fn = "dmx_tracks_infer_loud";
+    if (n_tracks < 1)
+        return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: the loudness stage needs a remix spec", fn);
+    DMXCHK(dmx_loud_check_spec(fn, loud, 44100, -1));
+    for (int t = 0; rates && t < n_tracks; ++t) // the loudness stage's own floor on a rate, with the track's number
+        DMXCHK(dmx_loud_check_spec(fn, loud, rates[t], t));
+    if (rates)
+        DMXCHK(check_tracks_rates(fn, n_tracks, n, rates, flac_out != 0));
+    TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
+    a.kind = flac_out ? TRACKS_OUT_FLAC : TRACKS_OUT_REMIX;
+    a.flacRate = 44100, a.flacSizes = sizes, a.rates = rates;
+    a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
+    a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
+    a.loud = loud, a.report = report;
+    return tracks_call(a);
+}
+
+extern "C" int dmx_tracks_infer_from_flac_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                               const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                               const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                               int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
+                                               const dmx_loudness_spec *loud, dmx_loudness_result *report)
+{
+    const char *fn = "dmx_tracks_infer_from_flac_loud";
+    DMXCHK(dmx_loud_check_spec(fn, loud, 44100, -1));
+    return tracks_from_flac(fn, true, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts, overlap, shift_offsets, spec,
+                            flac_out, out, sizes, peaks, track_status, progress, user, loud, report);
 }

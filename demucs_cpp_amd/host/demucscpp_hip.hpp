@@ -449,7 +449,20 @@ struct remix_options
     // the compression level of those files (dmx_ctx_set_flac_level, applied around the call and put back behind it):
     // 0 FIXED predictors alone, 1 + LPC order 8, 2 + LPC orders 8 and 12; it means nothing without flac
     int flac_level = 0;
+    // the loudness stage (dmx_tracks_infer_loud / dmx_tracks_infer_from_flac_loud), off by default: mode
+    // DMX_LOUD_MEASURE | DMX_LOUD_MIXTURE | DMX_LOUD_EACH, the target in LUFS, the ceiling of the sample peak as a linear value
+    // (-1 dBFS; infinity: none). The overloads that take these options have a last argument, LoudnessReport *loudness_report,
+    // that receives the report. With flac and without rates the files are taken to be at 44100 Hz (sample_rate must say so).
+    struct loudness_options
+    {
+        bool on = false;
+        int mode = DMX_LOUD_MIXTURE;
+        float target_lufs = -14.0f, max_peak = 0.8912509f;
+    };
+    loudness_options loudness;
 };
+// what a call with remix_options::loudness on reports: per track the library's n_out + 1 entries, the outputs and then the mixture
+using LoudnessReport = std::vector<std::vector<dmx_loudness_result>>;
 // the image of a .flac file, for the overloads that take tracks as files (dmx_tracks_infer_from_flac)
 using FlacFile = std::vector<unsigned char>;
 // demucs's --two-stems NAME with --other-method add | minus | none (DMX_OTHER_*): outputs "NAME" and, except for none,
@@ -588,11 +601,21 @@ inline int64_t remix_bytes(const remix_options &ro, int64_t n)
     const dmx_output_spec ospec{ro.encoding, ro.clip, -1};
     return ro.flac ? dmx_flac_bound(ro.encoding == DMX_PCM_S16 ? 16 : 24, n) : dmx_output_bytes(&ospec, n);
 }
+// the flat report of a call with ro.loudness.on, cut per track into *report
+inline void loudness_report_cut(const remix_options &ro, const std::vector<dmx_loudness_result> &rep, size_t T, int n_out, LoudnessReport *report)
+{
+    if (!ro.loudness.on || !report)
+        return;
+    report->assign(T, std::vector<dmx_loudness_result>());
+    for (size_t t = 0; t < T; ++t)
+        (*report)[t].assign(rep.begin() + (std::ptrdiff_t)(t * (size_t)(n_out + 1)),
+                                        rep.begin() + (std::ptrdiff_t)((t + 1) * (size_t)(n_out + 1)));
+}
 // one call of dmx_tracks_infer_remix, or for ro.flac dmx_tracks_infer_flac; shifts as the caller's path lays them out.
 // rates: track t is at (*rates)[t] Hz (dmx_tracks_infer_rates)
 inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts,
                              const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
-                             std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr)
+                             std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr, LoudnessReport *report = nullptr)
 {
     const int T = (int)tracks.size();
     if (rates && rates->size() != tracks.size())
@@ -610,9 +633,20 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
     TrackOutputs y(tracks.size(), spec.n_out);
     for (int64_t n : x.n)
         y.add(who, remix_bytes(ro, n));
+    if (ro.loudness.on && ro.flac && !rates && ro.sample_rate != 44100)
+    {
+        std::cerr << who << ": remix_options.loudness with flac takes the tracks to be at 44100 Hz (pass their rates instead)" << std::endl;
+        std::exit(1);
+    }
     CbThunk th{&cb};
     FlacLevelGuard level(g.c, ro.flac ? ro.flac_level : 0);
+    const dmx_loudness_spec lspec{ro.loudness.mode, ro.loudness.target_lufs, ro.loudness.max_peak};
+    std::vector<dmx_loudness_result> rep(ro.loudness.on ? (size_t)T * (size_t)(spec.n_out + 1) : 0);
     auto run = [&]() -> int {
+        if (ro.loudness.on)
+            return dmx_tracks_infer_loud(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates ? rates->data() : nullptr, opts.shifts,
+                                         opts.overlap, shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr,
+                                         y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th, &lspec, rep.data());
         if (rates)
             return dmx_tracks_infer_rates(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(),
                                           &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr, y.pk.data(), DMX_LAYOUT_EIGEN,
@@ -625,6 +659,7 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
     };
     if (!g.c || !level.ok || run() != DMX_OK)
         die(who);
+    loudness_report_cut(ro, rep, tracks.size(), spec.n_out, report);
     return y.cut(peaks, ro.flac);
 }
 // the same on tracks given as the images of .flac files (dmx_tracks_infer_from_flac): ro.flac chooses the output form.
@@ -633,7 +668,7 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
 // files' sample rates and lets every track run at its own (dmx_tracks_infer_from_flac_rates; .flac outputs carry it).
 inline PcmOutputs flac_files_call(const char *who, const Target &g, const std::vector<FlacFile> &files, const std::vector<int> &shifts,
                                   const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
-                                  std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames, std::vector<int> *rates = nullptr)
+                                  std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames, std::vector<int> *rates = nullptr, LoudnessReport *report = nullptr)
 {
     const size_t T = files.size();
     const dmx_remix_spec spec = remix_spec(who, g.S, ro);
@@ -662,49 +697,57 @@ inline PcmOutputs flac_files_call(const char *who, const Target &g, const std::v
     std::vector<int64_t> status(2 * T, 0);
     CbThunk th{&cb};
     FlacLevelGuard level(g.c, ro.flac ? ro.flac_level : 0);
+    const dmx_loudness_spec lspec{ro.loudness.mode, ro.loudness.target_lufs, ro.loudness.max_peak};
+    std::vector<dmx_loudness_result> rep(ro.loudness.on ? T * (size_t)(spec.n_out + 1) : 0);
     if (!g.c || !level.ok ||
-        (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts,
-                                                                                opts.overlap, shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(),
-                                                                                y.sizes.data(), y.pk.data(), status.data(), progress_thunk, &th) != DMX_OK)
+        (ro.loudness.on
+             ? dmx_tracks_infer_from_flac_loud(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap, shifts.data(),
+                                               &spec, ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(), status.data(), progress_thunk,
+                                               &th, &lspec, rep.data())
+             : (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(),
+                                                                                       opts.shifts, opts.overlap, shifts.data(), &spec,
+                                                                                       ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(),
+                                                                                       status.data(), progress_thunk, &th)) != DMX_OK)
         die(who);
+    loudness_report_cut(ro, rep, T, spec.n_out, report);
     if (frames)
         *frames = n;
     return y.cut(peaks, ro.flac);
 }
 inline PcmOutputs batch_call_from_flac(const char *who, const engine_model &model, const std::vector<FlacFile> &files,
                                        const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
-                                       std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames, std::vector<int> *rates = nullptr)
+                                       std::vector<std::vector<float>> *peaks, std::vector<int64_t> *frames, std::vector<int> *rates = nullptr, LoudnessReport *report = nullptr)
 {
     if (files.empty())
         return PcmOutputs();
     const std::vector<int> shifts = expand_shifts(who, model.shift_offset, files.size(), -1, opts);
     std::lock_guard<std::mutex> guard(model.lock);
-    return flac_files_call(who, root_target(model, dmx_engine_n_sources(model.engine)), files, shifts, cb, opts, ro, peaks, frames, rates);
+    return flac_files_call(who, root_target(model, dmx_engine_n_sources(model.engine)), files, shifts, cb, opts, ro, peaks, frames, rates, report);
 }
 inline PcmOutputs batch_call_remix(const char *who, const engine_model &model, const std::vector<StereoMatrix> &tracks,
                                    const ProgressCallback &cb, const inference_options &opts, const remix_options &ro,
-                                   std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr)
+                                   std::vector<std::vector<float>> *peaks, const std::vector<int> *rates = nullptr, LoudnessReport *report = nullptr)
 {
     if (tracks.empty())
         return PcmOutputs();
     const std::vector<int> shifts = expand_shifts(who, model.shift_offset, tracks.size(), -1, opts);
     std::lock_guard<std::mutex> guard(model.lock);
-    return remix_call(who, root_target(model, dmx_engine_n_sources(model.engine)), tracks, shifts, cb, opts, ro, peaks, rates);
+    return remix_call(who, root_target(model, dmx_engine_n_sources(model.engine)), tracks, shifts, cb, opts, ro, peaks, rates, report);
 }
 } // namespace detail
 inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
                                                const inference_options &opts, const remix_options &remix,
-                                               std::vector<std::vector<float>> *peaks = nullptr)
+                                               std::vector<std::vector<float>> *peaks = nullptr, LoudnessReport *loudness_report = nullptr)
 {
-    return detail::batch_call_remix("demucs_inference_batch_remix", model, tracks, cb, opts, remix, peaks);
+    return detail::batch_call_remix("demucs_inference_batch_remix", model, tracks, cb, opts, remix, peaks, nullptr, loudness_report);
 }
 
 // tracks given as .flac files (44100 Hz; decoded on the GPU): frames (optional) receives each track's sample count
 inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<FlacFile> &files, ProgressCallback cb,
                                                const inference_options &opts, const remix_options &remix,
-                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
+                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr, LoudnessReport *loudness_report = nullptr)
 {
-    return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames);
+    return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames, nullptr, loudness_report);
 }
 
 // Tracks at their own sample rates (dmx_tracks_infer_rates): tracks[t] holds the caller's frames at rates[t] Hz, the outputs
@@ -712,15 +755,15 @@ inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const 
 // RECEIVES the files' rates, and remix.sample_rate is not read: every .flac output carries its track's rate.
 inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<StereoMatrix> &tracks, const std::vector<int> &rates,
                                                ProgressCallback cb, const inference_options &opts, const remix_options &remix,
-                                               std::vector<std::vector<float>> *peaks = nullptr)
+                                               std::vector<std::vector<float>> *peaks = nullptr, LoudnessReport *loudness_report = nullptr)
 {
-    return detail::batch_call_remix("demucs_inference_batch_remix (rates)", model, tracks, cb, opts, remix, peaks, &rates);
+    return detail::batch_call_remix("demucs_inference_batch_remix (rates)", model, tracks, cb, opts, remix, peaks, &rates, loudness_report);
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_model &model, const std::vector<FlacFile> &files, std::vector<int> &rates,
                                                ProgressCallback cb, const inference_options &opts, const remix_options &remix,
-                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
+                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr, LoudnessReport *loudness_report = nullptr)
 {
-    return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files, rates)", model, files, cb, opts, remix, peaks, frames, &rates);
+    return detail::batch_call_from_flac("demucs_inference_batch_remix (flac files, rates)", model, files, cb, opts, remix, peaks, frames, &rates, loudness_report);
 }
 
 // The fine-tuned bag (cli-apps/demucs_ft.cpp:136-241): four 4-source models, stem i from model i. The
@@ -885,45 +928,45 @@ inline PcmOutputs demucs_inference_batch_pcm(const demucs_bag &bag, const std::v
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
                                                const std::vector<float> &weights, const inference_options &opts, const remix_options &remix,
-                                               std::vector<std::vector<float>> *peaks = nullptr)
+                                               std::vector<std::vector<float>> *peaks = nullptr, LoudnessReport *loudness_report = nullptr)
 {
     const char *who = "demucs_inference_batch_remix (bag)";
     if (tracks.empty())
         return PcmOutputs();
     const detail::BagCall b(who, bag, tracks.size(), weights, opts);
-    return detail::remix_call(who, b.g, tracks, b.shifts, cb, opts, remix, peaks);
+    return detail::remix_call(who, b.g, tracks, b.shifts, cb, opts, remix, peaks, nullptr, loudness_report);
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<FlacFile> &files, ProgressCallback cb,
                                                const std::vector<float> &weights, const inference_options &opts, const remix_options &remix,
-                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr)
+                                               std::vector<std::vector<float>> *peaks = nullptr, std::vector<int64_t> *frames = nullptr, LoudnessReport *loudness_report = nullptr)
 {
     const char *who = "demucs_inference_batch_remix (bag, flac files)";
     if (files.empty())
         return PcmOutputs();
     const detail::BagCall b(who, bag, files.size(), weights, opts);
-    return detail::flac_files_call(who, b.g, files, b.shifts, cb, opts, remix, peaks, frames);
+    return detail::flac_files_call(who, b.g, files, b.shifts, cb, opts, remix, peaks, frames, nullptr, loudness_report);
 }
 // the same with tracks at their own rates (see the demucs_model overloads)
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<StereoMatrix> &tracks, const std::vector<int> &rates,
                                                ProgressCallback cb, const std::vector<float> &weights, const inference_options &opts,
-                                               const remix_options &remix, std::vector<std::vector<float>> *peaks = nullptr)
+                                               const remix_options &remix, std::vector<std::vector<float>> *peaks = nullptr, LoudnessReport *loudness_report = nullptr)
 {
     const char *who = "demucs_inference_batch_remix (bag, rates)";
     if (tracks.empty())
         return PcmOutputs();
     const detail::BagCall b(who, bag, tracks.size(), weights, opts);
-    return detail::remix_call(who, b.g, tracks, b.shifts, cb, opts, remix, peaks, &rates);
+    return detail::remix_call(who, b.g, tracks, b.shifts, cb, opts, remix, peaks, &rates, loudness_report);
 }
 inline PcmOutputs demucs_inference_batch_remix(const demucs_bag &bag, const std::vector<FlacFile> &files, std::vector<int> &rates,
                                                ProgressCallback cb, const std::vector<float> &weights, const inference_options &opts,
                                                const remix_options &remix, std::vector<std::vector<float>> *peaks = nullptr,
-                                               std::vector<int64_t> *frames = nullptr)
+                                               std::vector<int64_t> *frames = nullptr, LoudnessReport *loudness_report = nullptr)
 {
     const char *who = "demucs_inference_batch_remix (bag, flac files, rates)";
     if (files.empty())
         return PcmOutputs();
     const detail::BagCall b(who, bag, files.size(), weights, opts);
-    return detail::flac_files_call(who, b.g, files, b.shifts, cb, opts, remix, peaks, frames, &rates);
+    return detail::flac_files_call(who, b.g, files, b.shifts, cb, opts, remix, peaks, frames, &rates, loudness_report);
 }
 
 // segment-level surface; src/model.hpp:569-647 (only the boundary members are kept:
@@ -1075,34 +1118,34 @@ inline demucscpp::PcmOutputs demucs_v3_inference_batch_pcm(const demucs_v3_model
 inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
                                                              ProgressCallback cb, const demucscpp::inference_options &opts,
                                                              const demucscpp::remix_options &remix,
-                                                             std::vector<std::vector<float>> *peaks = nullptr)
+                                                             std::vector<std::vector<float>> *peaks = nullptr, demucscpp::LoudnessReport *loudness_report = nullptr)
 {
-    return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix", model, tracks, cb, opts, remix, peaks);
+    return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix", model, tracks, cb, opts, remix, peaks, nullptr, loudness_report);
 }
 inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<demucscpp::FlacFile> &files,
                                                              ProgressCallback cb, const demucscpp::inference_options &opts,
                                                              const demucscpp::remix_options &remix,
                                                              std::vector<std::vector<float>> *peaks = nullptr,
-                                                             std::vector<int64_t> *frames = nullptr)
+                                                             std::vector<int64_t> *frames = nullptr, demucscpp::LoudnessReport *loudness_report = nullptr)
 {
-    return demucscpp::detail::batch_call_from_flac("demucs_v3_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames);
+    return demucscpp::detail::batch_call_from_flac("demucs_v3_inference_batch_remix (flac files)", model, files, cb, opts, remix, peaks, frames, nullptr, loudness_report);
 }
 // the same with tracks at their own rates (see demucscpp::demucs_inference_batch_remix)
 inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<StereoMatrix> &tracks,
                                                              const std::vector<int> &rates, ProgressCallback cb,
                                                              const demucscpp::inference_options &opts, const demucscpp::remix_options &remix,
-                                                             std::vector<std::vector<float>> *peaks = nullptr)
+                                                             std::vector<std::vector<float>> *peaks = nullptr, demucscpp::LoudnessReport *loudness_report = nullptr)
 {
-    return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix (rates)", model, tracks, cb, opts, remix, peaks, &rates);
+    return demucscpp::detail::batch_call_remix("demucs_v3_inference_batch_remix (rates)", model, tracks, cb, opts, remix, peaks, &rates, loudness_report);
 }
 inline demucscpp::PcmOutputs demucs_v3_inference_batch_remix(const demucs_v3_model &model, const std::vector<demucscpp::FlacFile> &files,
                                                              std::vector<int> &rates, ProgressCallback cb,
                                                              const demucscpp::inference_options &opts, const demucscpp::remix_options &remix,
                                                              std::vector<std::vector<float>> *peaks = nullptr,
-                                                             std::vector<int64_t> *frames = nullptr)
+                                                             std::vector<int64_t> *frames = nullptr, demucscpp::LoudnessReport *loudness_report = nullptr)
 {
     return demucscpp::detail::batch_call_from_flac("demucs_v3_inference_batch_remix (flac files, rates)", model, files, cb, opts, remix, peaks,
-                                                   frames, &rates);
+                                                   frames, &rates, loudness_report);
 }
 
 // src/model.hpp:1238-1394: the boundary members (`mix` in, `targets_out` out); LSTM state, decay tables and every

@@ -321,6 +321,94 @@ extern "C"
     int dmx_remix_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
                          void *out, float *peaks);
 
+    /* ---- loudness (csrc/loudness.hip; DESIGN.md section 2.14, restated in tests/loudness_spec.py; no reference counterpart).
+     * Integrated loudness after ITU-R BS.1770-4 / EBU R 128 of a stereo signal x[2][n] of fp32 samples at `rate` Hz, measured
+     * on the GPU in binary64, and the gain that brings a track's outputs to a target.
+     * Coefficients (host, libm, binary64): shelf f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196,
+     * K = tan(pi f0 / rate), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2, b = [(Vh + Vb K/Q + K^2)/a0,
+     * 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0], a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0]; high-pass f0 = 38.13547087602444,
+     * Q = 0.5003270373238773, b = [1, -2, 1] (not normalised), a as above. At 48 kHz these are the BS.1770 table values.
+     * Measurement: y = highpass(shelf(x)) per channel from zero state; hop h = (rate + 5) / 10 frames, H = n / h whole hops
+     * (the tail is ignored); e[c][j] the sum of y^2 over hop j; block b in [0, H - 3): z[b] = (sum over both channels and hops
+     * b .. b + 3 of e) / (4 h); l[b] = -0.691 + 10 log10 z[b]; a block with l[b] <= -70 is dropped (absolute gate), then one
+     * with l[b] <= -0.691 + 10 log10(mean z of the remaining blocks) - 10 (relative gate); L = -0.691 + 10 log10(mean z of the
+     * blocks past both gates). A NaN block passes the gates, so one NaN in the signal makes L NaN. UNMEASURABLE: H < 4, no
+     * block left, or L not finite. The quantum lufs_c = rint(100 L), ties to even, an int32 in hundredths of a LU
+     * (DMX_LUFS_UNMEASURABLE = INT32_MIN); everything downstream uses lufs_c, never L, so the gain and every output byte are
+     * reproducible although the device sums in another order than a host would. The device's sums have a fixed order and
+     * use no atomics: L is the same bits from run to run, whatever else a call holds.
+     * Gain (fp32): target_c = rint(100 target_lufs); k = clamp(target_c - lufs_c, -6000, 6000); g = T[k + 6000] with the
+     * host-made table T[i] = (float)pow(10.0, (i - 6000) / 2000.0); ceiling: with P the sample peak of the specification
+     * above, if P > 0 and the fp32 product g * P exceeds max_peak then g = max_peak / P, correctly rounded (+inf: no
+     * ceiling); unmeasurable: g = 1, no ceiling. Apply: y = g * x, one fp32 product per sample on the gathered output value
+     * (behind the remix sum, in front of clip); clip and encode follow with the peak g * P, which is exactly the peak of
+     * the gained samples (a positive factor and its rounding are monotone) and is the peak reported. g == 1 gives the bytes
+     * of the entry point without loudness.
+     * Modes: DMX_LOUD_MEASURE no gain, only the report; DMX_LOUD_MIXTURE one g for all outputs of a track, from the lufs_c
+     * of the MIXTURE (the caller's track at its own rate) and the largest of the outputs' peaks - the outputs keep their
+     * balance and none exceeds the ceiling; DMX_LOUD_EACH every output its own lufs_c, P and g.
+     * The report of a track holds n_out + 1 entries, the outputs and then the mixture (whose gain is 0); lufs is the
+     * unquantised L, NaN when unmeasurable. A mono file is measured as the dual-mono stereo it becomes.
+     * Out of scope: true peak (4x oversampled), loudness range, momentary and short-term meters (the hop energies are
+     * returned: a caller can derive them), ReplayGain tags (FLAC tags stay out of scope), the engine. */
+#define DMX_LOUD_MEASURE 0
+#define DMX_LOUD_MIXTURE 1
+#define DMX_LOUD_EACH 2
+#define DMX_LUFS_UNMEASURABLE (-2147483647 - 1)
+#define DMX_LOUD_MIN_RATE 4000 /* tan(pi f0 / rate) of the shelf needs rate > 2 * 1682 */
+    typedef struct dmx_loudness_spec
+    {
+        int mode;          /* DMX_LOUD_* */
+        float target_lufs; /* finite, in [-70, 0] */
+        float max_peak;    /* > 0; +inf: no ceiling */
+    } dmx_loudness_spec;
+    typedef struct dmx_loudness_result
+    {
+        int32_t lufs_c; /* rint(100 L), or DMX_LUFS_UNMEASURABLE */
+        float gain;     /* the gain applied (1 under DMX_LOUD_MEASURE; 0 in the mixture's entry and from the measuring calls) */
+        double lufs;    /* L, NaN when unmeasurable */
+    } dmx_loudness_result;
+    /* the two stages' b0 b1 b2 a1 a2, ten doubles. Pure host function; DMX_ERR_ARG for rate < DMX_LOUD_MIN_RATE. */
+    int dmx_loudness_coefficients(int rate, double *coef);
+    /* the table T above, 12001 floats. Pure host function. */
+    int dmx_loudness_gain_table(float *table);
+    /* validates a spec for a signal at `rate`. Pure host function. Rejected, each with a message that names the field
+     * ("loudness spec: target_lufs 3 is not in [-70, 0]"): a bad mode, a target_lufs that is not finite or outside [-70, 0],
+     * a max_peak that is not above 0, a rate below DMX_LOUD_MIN_RATE. */
+    int dmx_loudness_check(const dmx_loudness_spec *spec, int rate);
+    /* bytes of device workspace for ONE measured signal of n frames, whatever the rate: 64 + 256 per tile of 4096 frames (64
+     * bytes of states, 192 of hop partials sized for the smallest hop) + 16 per 400 frames (the hop energies, sized likewise) -
+     * about n / 10. The design condition of at most one byte per frame holds from 320 frames on; below that the first tile's
+     * 320 bytes are a constant that a shorter signal cannot be spared. Pure host function; -1 for n < 1. */
+    int64_t dmx_loudness_workspace_bytes(int64_t n);
+    /* measures one signal on device memory, asynchronous on `stream`, four launches: d_x is planar (channel c at d_x + c *
+     * plane_stride, plane_stride >= n) or, with plane_stride == 0, interleaved [n][2]; any 4-byte alignment. d_result: one
+     * entry ON THE DEVICE (gain 0); d_e: NULL or 2 x (n / h) doubles on the device, e[c][j]; d_work: 16-byte aligned,
+     * the bytes above. 1 <= n < 2^36. */
+    int dmx_loudness_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                            double *d_e, void *d_work, void *stream);
+    /* measurement (tools/loudness_bench.py): the call above, synchronised, with the times of its four launches (states, scan,
+     * energies, final) between HIP events in ms[0..4) and, in ms[4], the peak kernel's time on the same signal */
+    int dmx_loudness_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate,
+                                  dmx_loudness_result *d_result, double *d_e, void *d_work, void *stream, float *ms);
+    /* the same on host buffers: x planar [2][n] or (interleaved != 0) [n][2]; e NULL or 2 x (n / h) doubles */
+    int dmx_loudness(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e);
+    /* dmx_remix_encode_device behind the loudness stage: measure the n_out outputs and the mixture, form the peaks and the
+     * gains, encode - all enqueued on `stream`, no host round trip. d_mix is required (it is the signal DMX_LOUD_MIXTURE
+     * measures, and the report's last entry). d_report: n_out + 1 entries on the device. d_work: 16-byte aligned,
+     * (n_out + 1) x dmx_loudness_workspace_bytes(n) + 64 bytes. Under DMX_LOUD_MEASURE the bytes and peaks are
+     * dmx_remix_encode_device's, from the kernels it launches. This call has no context to own the gain table: the first
+     * call on a device uploads one copy (48 KB, a blocking copy) that stays for the life of the process.
+     * An output spec (a stem, or the sum of the others) reaches the stage as its 0/1 gain matrix (dmx_remix_two_stems or
+     * unit rows), whose bytes are the output spec's: the measuring kernels are instantiated for gain tables only. */
+    int dmx_loud_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride, const float *d_mix,
+                               const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out, float *d_peaks,
+                               dmx_loudness_result *d_report, void *d_work, void *stream);
+    /* host buffers: planes [n_sources][2][n], mix [n][2]; out: n_out consecutive chunks; peaks NULL or n_out; report NULL or
+     * n_out + 1 entries */
+    int dmx_loud_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                        const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report);
+
     /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
      * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
      * PCM as the stages above write it (16-bit pairs or packed 24 bit) -> a complete .flac file: "fLaC", one STREAMINFO block
@@ -454,6 +542,27 @@ extern "C"
                                          const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
                                          const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
                                          float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user);
+    /* the two calls above behind the loudness stage (the section on loudness, above): the arguments of dmx_tracks_infer_rates
+     * (rates == NULL: 44100 for all tracks) resp. dmx_tracks_infer_from_flac_rates, plus the loudness spec (required, as is
+     * the remix spec) and the report, NULL or n_tracks x (n_out + 1) entries, per track its outputs and then its mixture.
+     * DMX_LOUD_MIXTURE and DMX_LOUD_EACH make a track a whole-track one, as DMX_CLIP_RESCALE does: its outputs are measured,
+     * gained, encoded and copied out behind its last piece. DMX_LOUD_MEASURE lets the pieces leave as without loudness, from
+     * the kernels that run without it, and measures behind the last piece. The mixture is the caller's track at its own
+     * rate (the slot's one upload); a damaged FLAC track is measured as it stands, silence from `good` on. The report leaves
+     * with the peaks, which are those of the gained samples. Refused before any GPU work, naming the field and, for a rate
+     * below DMX_LOUD_MIN_RATE, the track. Device memory: per track slot, on top of the call without loudness, (n_out + 1) x
+     * dmx_loudness_workspace_bytes(n_max) + 64 + 16 (n_out + 1) bytes, and once per context the gain table (48 KB, built on
+     * the host and uploaded by the context's first such call, freed with the context). */
+    int dmx_tracks_infer_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                              const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                              const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                              float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                              dmx_loudness_result *report);
+    int dmx_tracks_infer_from_flac_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                        const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                        const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                        int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
+                                        const dmx_loudness_spec *loud, dmx_loudness_result *report);
     /* pure host function: the outputs of a conversion of n_in -> n_out = dmx_resample_length frames that no longer change once
      * the inputs [0, n_in_final) are final: n_out when n_in_final == n_in, else min(n_out, max(0, ceil((n_in_final L - c) / M))),
      * the first output whose newest tap (c + k M) div L reaches n_in_final. -1: invalid argument */
