@@ -31,7 +31,7 @@ EXPORTS = [
     "dmx_track_gather_device", "dmx_track_overlap_add_device", "dmx_debug_tap", "dmx_debug_n_ops",
     "dmx_debug_profile", "dmx_ctx_set_model", "dmx_model_clone",
     "dmx_debug_plan_info", "dmx_debug_op_info", "dmx_debug_arena_fill", "dmx_debug_arena_io", "dmx_debug_run_op", "dmx_debug_op_cfgs",
-    "dmx_debug_run_op_as",
+    "dmx_debug_run_op_as", "dmx_debug_run_attention_as",
     "dmx_engine_create", "dmx_engine_free", "dmx_engine_n_devices", "dmx_engine_n_models", "dmx_engine_n_sources",
     "dmx_resample_length", "dmx_resample_filter", "dmx_resample_device", "dmx_resample",
     "dmx_ctx_create_gemm", "dmx_ctx_gemm", "dmx_default_gemm", "dmx_set_default_gemm", "dmx_debug_split_weights", "dmx_debug_split_activations", "dmx_debug_split_activations_fp16",
@@ -205,6 +205,7 @@ def lib():
         L.dmx_debug_run_op.argtypes = [vp, ci, ci]
         L.dmx_debug_op_cfgs.argtypes = [vp, ci, ci, vp, ci]
         L.dmx_debug_run_op_as.argtypes = [vp, ci, ci, ci, ci, ctypes.c_char_p, ci]
+        L.dmx_debug_run_attention_as.argtypes = [vp, ci, ci, ci]
         L.dmx_ctx_set_model.argtypes = [vp, vp]
         L.dmx_engine_create.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, ctypes.POINTER(ci), ci, ci, ci, ctypes.POINTER(vp)]
         L.dmx_engine_free.argtypes = [vp]
@@ -223,7 +224,8 @@ def _chk(rc):
         raise DmxError(rc, lib().dmx_last_error().decode(errors="replace"))
 
 
-DEBUG_NO_KERNEL = 6  # dmx_debug_run_op_as: no such kernel, nothing launched
+DEBUG_NO_KERNEL = 6  # dmx_debug_run_op_as / dmx_debug_run_attention_as: no such kernel, nothing launched
+ATTENTION_FORMS = ("wg64", "wg128", "pair")  # csrc/attention_select.h AttentionForm, by value
 
 
 def parse_op_info(text: str) -> dict:
@@ -235,6 +237,8 @@ def parse_op_info(text: str) -> dict:
             d[k] = [tuple(int(x) for x in r.split(":")) for r in v.split(",") if r]
         elif k in ("name", "label", "form"):
             d[k] = v
+        elif k == "scale":
+            d[k] = float(v)
         else:
             d[k] = int(v)
     return d
@@ -775,6 +779,14 @@ class Context:
             return None
         _chk(rc)
         return parse_op_info(buf.value.decode())
+
+    def run_attention_as(self, batch: int, i: int, form: str) -> Optional[str]:
+        """runs attention op i in form "wg64" / "wg128" / "pair"; None where that form does not exist (nothing launched), else the form"""
+        rc = lib().dmx_debug_run_attention_as(self.h, batch, i, ATTENTION_FORMS.index(form))
+        if rc == DEBUG_NO_KERNEL:
+            return None
+        _chk(rc)
+        return form
 
     def profile(self, batch: int = 1, reps: int = 3):
         """[(op name, kernel, ms per launch, algorithmic flops, algorithmic bytes)]"""

@@ -369,7 +369,7 @@ void launch_attention(const AttnArgs &a0, hipStream_t s)
     constexpr int xcdMap = 1; // all query tiles of one (batch, head) on one XCD
     AttnArgs a = a0;
     a.xcdMap = xcdMap;
-    const bool big = att_use_big_shape(a); // 128- or 64-query workgroups (attention_common.h)
+    const bool big = a.form != ATT_FORM_WG64; // 128- or 64-query workgroups: chosen when the plan was built (attention_select.h)
     if (a.hs != 64 && a.hs != 48)
         abort();
     a.nQt = (unsigned)(big ? (a.Tq + 127) / 128 : (a.Tq + 63) / 64);

@@ -134,7 +134,4 @@ __device__ __forceinline__ bool att_tile_of_block(const AttnArgs &p, unsigned &q
     return true;
 }
 
-// 128- or 64-query workgroups: the shape rule of attention_select.h on a launch's arguments
-inline bool att_use_big_shape(const AttnArgs &a) { return att_big_shape(a.Tq, a.H, a.B); }
-
 } // namespace dmx

@@ -1,7 +1,8 @@
 // attention_select.h — which form of the exact-split attention kernel (attention_split.hip) runs an OP_ATTENTION: decided once, on
 // the host, when the op's plan is built (exec.cpp dmx_get_plan -> plan.h Attention::form), as gemm_select.h decides the GEMM ops'.
 // Plain C++, no HIP: a pure function of the op's shape. Every form computes the same bits (same key-tile order, same term order
-// per query), so the choice is one of speed only.
+// per query), so the choice is one of speed only. The fp32 kernel (attention.hip) has the two unpaired shapes and takes them by
+// the same att_big_shape, decided at the same place.
 #pragma once
 
 namespace dmx

@@ -399,3 +399,32 @@ extern "C" int dmx_debug_run_op_as(dmx_ctx *c, int batch, int i, int cfg, int li
     DMXCHK(dmx_launch_op(c, op, c->stream, p->zeroOff));
     return dmx_ctx_sync_checked(c);
 }
+
+// Runs a COPY of OP_ATTENTION / OP_LOCAL_ATTN i in AttentionForm `form` (attention_select.h: every form computes the same bits).
+// DMX_DEBUG_NO_KERNEL, nothing launched, where the form does not exist: the paired form without operand planes, with keys that
+// are no whole 64-key tiles or in an fp32 context; LocalState in anything but 64-query workgroups.
+extern "C" int dmx_debug_run_attention_as(dmx_ctx *c, int batch, int i, int form)
+{
+    Plan *p = nullptr;
+    const Op *src = debug_op(c, batch, i, &p);
+    if (!src || (src->kind != OP_ATTENTION && src->kind != OP_LOCAL_ATTN))
+        return fail(DMX_ERR_ARG, "dmx_debug_run_attention_as: op %d is no attention op of the plan", i);
+    if (form != ATT_FORM_WG64 && form != ATT_FORM_WG128 && form != ATT_FORM_PAIR)
+        return fail(DMX_ERR_ARG, "dmx_debug_run_attention_as: no such form %d", form);
+    Op op = *src;
+    if (op.kind == OP_LOCAL_ATTN)
+    {
+        if (form != ATT_FORM_WG64)
+            return fail(DMX_DEBUG_NO_KERNEL, "op %s: LocalState runs on 64-query workgroups only", op.name.c_str());
+    }
+    else
+    {
+        const Attention &t = op.at;
+        if (form == ATT_FORM_PAIR && !(t.split && att_pair_exists(t.Tk, t.hs, t.kpl >= 0 && t.vt >= 0)))
+            return fail(DMX_DEBUG_NO_KERNEL, "op %s: no paired kernel (needs the exact-split kernel, operand planes and whole key tiles)",
+                        op.name.c_str());
+        op.at.form = form;
+    }
+    DMXCHK(dmx_launch_op(c, op, c->stream, p->zeroOff));
+    return dmx_ctx_sync_checked(c);
+}

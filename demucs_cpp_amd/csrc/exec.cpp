@@ -102,8 +102,10 @@ Plan *dmx_get_plan(dmx_ctx *c, int batch)
             AttnArgs k{};
             k.hs = t.hs;
             t.split = c->gemm != DMX_GEMM_F32 && launch_attention_split(k, nullptr, true) == 0 ? 1 : 0;
-            if (t.split)
-                t.form = att_select_form(t.Tq, t.Tk, t.H, t.B, t.hs, t.kpl >= 0 && t.vt >= 0, pairMode);
+            // the fp32 kernel (attention.hip) has the two unpaired shapes only, by the same rule
+            t.form = t.split                           ? att_select_form(t.Tq, t.Tk, t.H, t.B, t.hs, t.kpl >= 0 && t.vt >= 0, pairMode)
+                     : att_big_shape(t.Tq, t.H, t.B) ? ATT_FORM_WG128
+                                                     : ATT_FORM_WG64;
         }
     Plan *raw = p.get();
     c->plans[batch] = std::move(p);

@@ -165,7 +165,7 @@ struct AttnArgs
     // bf16 operand planes written by the K / V projections (plan.h Attention::kpl / vt), or null
     const unsigned short *kpl, *vt;
     i64 kvPlane; // elements per plane = B * Tk * H * hs
-    int form;    // launch_attention_split: the AttentionForm (attention_select.h) the plan chose for this op
+    int form;    // launch_attention / launch_attention_split: the AttentionForm (attention_select.h) the plan chose for this op
 };
 
 void launch_attention(const AttnArgs &a, hipStream_t s);

@@ -204,7 +204,7 @@ struct Attention
     int split;   // GEMM_BF16X3 contexts (exec.cpp dmx_get_plan): run on the exact-split bf16 kernel (attention_split.hip)
     i64 kpl = -1, vt = -1; // A: bf16 operand planes of K ([3][B][Tk][H*hs]) and V^T ([3][B][H][Tk/64][hs][64]) written by the
                            // projections (EPI_KPL / EPI_VT), or -1: the kernel splits fp32 k / v itself
-    int form = 0; // split ops: the AttentionForm (attention_select.h: wg64 / wg128 / pair) chosen when the plan is built (exec.cpp dmx_get_plan)
+    int form = 0; // the AttentionForm (attention_select.h: wg64 / wg128, split ops: or pair) chosen when the plan is built (exec.cpp dmx_get_plan)
 };
 
 struct Istft

@@ -60,7 +60,12 @@ inline std::string describe_op(const Op &op)
         all += std::string(" label=") + (op.at.split ? "attention_split" : "attention");
         word("K", op.at.hs), word("T", op.at.Tk), word("split", op.at.split), word("planes", op.at.kpl >= 0);
         word("Tq", op.at.Tq), word("H", op.at.H), word("B", op.at.B);
-        all += std::string(" form=") + (op.at.split ? att_form_name(op.at.form) : "-");
+        all += std::string(" form=") + att_form_name(op.at.form);
+        {
+            char sc[32];
+            snprintf(sc, sizeof(sc), " scale=%.9g", (double)op.at.scale);
+            all += sc;
+        }
         if (op.at.kpl >= 0)
             word("kpl", op.at.kpl), word("vt", op.at.vt), word("kvPlane", (i64)op.at.B * op.at.Tk * op.at.H * op.at.hs);
         break;

@@ -681,7 +681,11 @@ extern "C"
      * dmx_debug_run_op: launches op i alone.
      * dmx_debug_op_cfgs / dmx_debug_run_op_as: the tile configurations GEMM i may be asked to run on, and a run of a copy of it
      *   on one of them with the kernel the selection gives under lin_mode (DMX_SPLIT_LIN); DMX_DEBUG_NO_KERNEL, nothing
-     *   launched, where that kernel does not exist; `choice` receives "cfg= family= arith= wnf= label= BM= BN= NB=".        */
+     *   launched, where that kernel does not exist; `choice` receives "cfg= family= arith= wnf= label= BM= BN= NB=".
+     * dmx_debug_run_attention_as: a run of a copy of attention op i (the transformer's or v3's LocalState) in form 0 = 64-query
+     *   workgroups, 1 = 128-query workgroups, 2 = paired (the form= word of dmx_debug_op_info names the plan's own);
+     *   DMX_DEBUG_NO_KERNEL, nothing launched, where the form does not exist: paired without K / V operand planes, with keys that
+     *   are no whole 64-key tiles or in a DMX_GEMM_F32 context; LocalState in anything but form 0.                          */
     int dmx_debug_plan_info(dmx_ctx *c, int batch, int *n_ops, int64_t *arena_floats, int64_t *plan_floats, int64_t *const_floats);
     int dmx_debug_op_info(dmx_ctx *c, int batch, int i, char *buf, int cap);
     int dmx_debug_arena_fill(dmx_ctx *c, int batch, unsigned pattern);
@@ -689,6 +693,7 @@ extern "C"
     int dmx_debug_run_op(dmx_ctx *c, int batch, int i);
     int dmx_debug_op_cfgs(dmx_ctx *c, int batch, int i, int *cfgs, int cap);
     int dmx_debug_run_op_as(dmx_ctx *c, int batch, int i, int cfg, int lin_mode, char *choice, int cap);
+    int dmx_debug_run_attention_as(dmx_ctx *c, int batch, int i, int form);
     /* the operand splits of DMX_GEMM_BF16X3, exposed for their unit tests. Weights (pure host function): w[i] -> bf16 bit
      * patterns w1[i], w2[i]; returns the number of elements with w1 + w2 != w. Activations (runs the kernels' own device
      * function on `device`): x[i] -> planes[0..n), [n..2n), [2n..3n) = a1, a2, a3; host pointers. */

@@ -548,6 +548,61 @@ struct Interp
         return ld_bf16(a.vt, e) + ld_bf16(a.vt, plane + e) + ld_bf16(a.vt, 2 * plane + e);
     }
 
+    // interp_set_attention: operands given as dense [B][T][H * hs] fp32 arrays written where run_attention reads them - Q rows, fp32
+    // K / V rows or, where the op reads operand planes, their exact three-term split in the layouts of run_igemm's EPI_KPL / EPI_VT
+    // (the inverse of attn_k / attn_v). Keeps no record in mask: it is no step.
+    void set_attention(const Attention &a, const float *q, const float *k, const float *v)
+    {
+        const int C = a.H * a.hs;
+        const i64 plane = (i64)a.B * a.Tk * C;
+        unsigned short *kp = a.kpl >= 0 ? reinterpret_cast<unsigned short *>(&A[(size_t)a.kpl]) : nullptr;
+        unsigned short *vp = a.vt >= 0 ? reinterpret_cast<unsigned short *>(&A[(size_t)a.vt]) : nullptr;
+        for (int b = 0; b < a.B; ++b)
+        {
+            for (int t = 0; t < a.Tq; ++t)
+                for (int c = 0; c < C; ++c)
+                    A[(size_t)(a.q + b * a.qBatch + (i64)t * a.ldq + c)] = q[((i64)b * a.Tq + t) * C + c];
+            for (int s = 0; s < a.Tk; ++s)
+                for (int c = 0; c < C; ++c)
+                {
+                    const i64 src = ((i64)b * a.Tk + s) * C + c;
+                    unsigned short h[3];
+                    if (!kp)
+                        A[(size_t)(a.k + b * a.kBatch + (i64)s * a.ldk + c)] = k[src];
+                    else
+                    {
+                        split3(k[src], h);
+                        for (int p = 0; p < 3; ++p)
+                            kp[p * plane + src] = h[p];
+                    }
+                    if (!vp)
+                        A[(size_t)(a.v + b * a.vBatch + (i64)s * a.ldv + c)] = v[src];
+                    else
+                    {
+                        const int head = c / a.hs, dim = c % a.hs, tt = s & 63, nt = a.Tk / 64;
+                        const int slot = 4 * (tt >> 5) + ((tt >> 2) & 3), half = (tt >> 4) & 1;
+                        const i64 e = ((((i64)b * a.H + head) * nt + (s >> 6)) * a.hs + dim) * 64 + slot * 8 + half * 4 + (tt & 3);
+                        split3(v[src], h);
+                        for (int p = 0; p < 3; ++p)
+                            vp[p * plane + e] = h[p];
+                    }
+                }
+        }
+    }
+    // LocalState: the [q | k | v | decay] row of qkvd as run_local_attn reads it; q / k / v dense [B][T][H], decay [B][T][16]
+    // (4 heads x 4 terms: the logits before the sigmoid)
+    void set_local_attn(const LocalAttn &a, const float *q, const float *k, const float *v, const float *decay)
+    {
+        for (i64 r = 0; r < (i64)a.B * a.T; ++r)
+        {
+            float *row = &A[(size_t)(a.qkvd + r * a.ld)];
+            for (int c = 0; c < a.H; ++c)
+                row[c] = q[r * a.H + c], row[a.H + c] = k[r * a.H + c], row[2 * a.H + c] = v[r * a.H + c];
+            for (int c = 0; c < 16; ++c)
+                row[3 * a.H + c] = decay[r * 16 + c];
+        }
+    }
+
     template <class T>
     void run_attention(const Attention &a)
     {
@@ -1245,6 +1300,24 @@ extern "C" int interp_op_info(void *h, int i, char *buf, int cap)
     const Op &op = it->pl.ops[(size_t)i];
     const std::string all = describe_op(op);
     return copy_out(all, buf, cap);
+}
+
+// Operands of attention op i (OP_ATTENTION, or OP_LOCAL_ATTN with its decay logits) written straight into the ranges the op reads:
+// q [B][Tq][H hs], k / v [B][Tk][H hs] dense fp32; decay [B][T][16] for LocalState, null otherwise. -1: no such op or a decay
+// array that does not go with the op's kind.
+extern "C" int interp_set_attention(void *h, int i, const float *q, const float *k, const float *v, const float *decay)
+{
+    Interp *it = (Interp *)h;
+    if (i < 0 || i >= (int)it->pl.ops.size() || !q || !k || !v)
+        return -1;
+    const Op &op = it->pl.ops[(size_t)i];
+    if (op.kind == OP_ATTENTION && !decay)
+        it->set_attention(op.at, q, k, v);
+    else if (op.kind == OP_LOCAL_ATTN && decay)
+        it->set_local_attn(op.la, q, k, v, decay);
+    else
+        return -1;
+    return 0;
 }
 
 extern "C" int interp_step(void *h, int i, int mode)

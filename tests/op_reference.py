@@ -55,6 +55,7 @@ def lib():
     L.interp_planes.argtypes = [vp, vp, vp]
     L.interp_op_info.argtypes = [vp, ci, ctypes.c_char_p, ci]
     L.interp_step.argtypes = [vp, ci, ci]
+    L.interp_set_attention.argtypes = [vp, ci, vp, vp, vp, vp]
     L.interp_run.argtypes = [vp, vp, vp]
     L.interp_weights.restype = vp
     L.interp_weights.argtypes = [vp]
@@ -102,6 +103,12 @@ class Ref:
         if precise and self.R is None:
             self.R = _view(self.L.interp_precise(self.h), self.floats, np.float64)
             self.S = _view(self.L.interp_magnitude(self.h), self.floats, np.float32)
+
+    def set_attention(self, i, q, k, v, decay=None):
+        """operands of attention op i written where the op reads them (cpu_interp.cpp interp_set_attention): q [B][Tq][H hs], k / v
+        [B][Tk][H hs]; decay [B][T][16] for a LocalState op"""
+        arr = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (q, k, v, decay)]
+        assert self.L.interp_set_attention(self.h, i, *[None if a is None else a.ctypes.data for a in arr]) == 0
 
     def planes(self):
         """(r, s) of the last precise step's K / V operand planes, indexed like the elements of plane 0; None if it wrote none"""
@@ -322,3 +329,128 @@ def canary_arena(ref, op_reads, canary):
     before = expected_arena(ref.floats, canary, saved.view(np.uint32)[:ref.consts], op_reads, [saved[lo:hi] for lo, hi in op_reads])
     ref.A.view(np.uint32)[:] = before
     return saved, before
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The GPU side of the op-level tests (tests/test_gpu_op_parity.py, tests/test_gpu_attention_crafted.py): a context beside the
+# interpreter handle of the same plan, and the check of one launch.
+DEVICE_ERROR = []  # the first error the library reported from the device: after it no op-level test launches anything
+
+
+class Pair:
+    """a context and the interpreter handle of the same plan; `cases`: the table `case` is a key of (default CASES)"""
+
+    def __init__(self, dmxb, L, tmp_models, case, mode, zero_segment=False, cases=None):
+        assert not DEVICE_ERROR, f"an earlier launch failed on the device, nothing more is launched: {DEVICE_ERROR[0]}"
+        self.dmxb = dmxb
+        key, seg, B, _ = (cases or CASES)[case]
+        self.B, self.mode, self.case = B, mode, case
+        self.model = dmxb.Model(tmp_models[key], 0)
+        self.ctx = dmxb.Context(self.model, seg, B, gemm=GEMM[mode])
+        self.n_ops, self.ctx_floats, self.floats, self.consts = self.ctx.plan_info(B)
+        self.gops = [self.ctx.op_info(B, i) for i in range(self.n_ops)]
+        # a split context of a v4 model asks for K / V operand planes and falls back to the fp32-K/V form where a projection cannot
+        # take its exact-split kernel (exec.cpp dmx_get_plan): the reference is built the same way
+        self.ref = Ref(L, tmp_models[key], seg, B, mode, mode != "f32" and key != 3)
+        if self.ref.floats != self.floats and not any(o["kind"] == OP_ATTENTION and o.get("planes") for o in self.gops):
+            self.ref.close()
+            self.ref = Ref(L, tmp_models[key], seg, B, mode, False)
+        rng = np.random.default_rng(seg + B)
+        mix = (0.1 * rng.standard_normal((B, 2, seg))).astype(np.float32)
+        if zero_segment:
+            mix[B - 1] = 0.0
+        self.ref.set_mix(mix)
+        # the constants as the LIBRARY computed them (the interpreter's come from another compiler: window sums differ in the last bit)
+        self.ctx.arena_fill(B, CANARY_A)
+        self.consts_u32 = self.ctx.arena_read(0, self.consts).view(np.uint32).copy()
+        self.buf = np.empty(self.ctx_floats, np.float32)
+
+    def assert_same_plan(self):
+        ref = self.ref
+        assert ref.n_ops == self.n_ops and ref.floats == self.floats and ref.consts == self.consts
+        for a, b in zip(ref.ops, self.gops):
+            assert (a["name"], a["kind"], a["reads"], a["writes"], a["scratch"]) == (b["name"], b["kind"], b["reads"], b["writes"], b["scratch"])
+
+    def prepare(self, canary, reads, values):
+        self.ctx.arena_fill(self.B, canary)
+        for (lo, hi), v in zip(reads, values):
+            self.ctx.arena_write(lo, v)
+
+    def close(self):
+        self.ref.close()
+        self.ctx.close()
+        self.model.close()
+
+
+def float_rms(ref, i, j, snap, op):
+    """RMS ratio of the interpreter's fp32 arithmetic for ops i .. j on the current inputs; leaves the arena as it was"""
+    hull = [rg for k in range(i, j + 1) for rg in ref.ops[k]["writes"]]
+    saved = [ref.A[lo:hi].copy() for lo, hi in hull]
+    for k in range(i, j + 1):
+        ref.step(k, False)
+    q = [ratios(ref.A[snap["idx"]], snap["r"], snap["s"])]
+    pr = plane_range(op)
+    if pr:
+        total, _ = bf16_planes_sum(ref.A[pr[0]:pr[1]].view(np.uint16), op["kvPlane"])
+        q.append(ratios(total, *snap["planes"]))
+    for (lo, hi), v in zip(hull, saved):
+        ref.A[lo:hi] = v
+    return rms(np.concatenate(q))
+
+
+def written_bits(fetch, op, snap):
+    """the bits of everything the op wrote; fetch(lo, hi) -> the arena's uint32 words [lo, hi) (write ranges only are asked for)"""
+    pr, idx, out = plane_range(op), snap["idx"], []
+    for lo, hi in op["writes"]:
+        words = fetch(lo, hi)
+        out.append(words[idx[(idx >= lo) & (idx < hi)] - lo])
+        if pr and lo <= pr[0] and pr[1] <= hi:
+            out.append(words[pr[0] - lo:pr[1] - lo])
+    return np.concatenate(out)
+
+
+def check_launch(pair, i, j, op, reads, values, snap):
+    """Op j of the context's plan (the reference stepped ops i .. j: a fused pair, else i == j) launched alone on `values` in its
+    read ranges: from canary A (value bound and containment: check_op), again with canary B in everything it does not declare to
+    read (the same bits), and the RMS rule against the interpreter's fp32 arithmetic on the same inputs. Raises OpMismatch;
+    returns (worst ratio, RMS of the kernel, RMS of the fp32 interpreter or None, the bits the kernel wrote)"""
+    ref, ctx, B, mode = pair.ref, pair.ctx, pair.B, pair.mode
+    # ---- the kernel on canary A
+    pair.prepare(CANARY_A, reads, values)
+    ctx.run_op(B, j)
+    got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
+    before = expected_arena(pair.ctx_floats, CANARY_A, pair.consts_u32, reads, values)
+    worst, q = check_op(op, mode, got, before, snap)
+    bits_a = written_bits(lambda lo, hi: got[lo:hi], op, snap)
+    # ---- the same launch with canary B in everything it does not declare to read
+    pair.prepare(CANARY_B, reads, values)
+    ctx.run_op(B, j)
+    bits_b = written_bits(lambda lo, hi: ctx.arena_read(lo, hi - lo).view(np.uint32), op, snap)
+    if not np.array_equal(bits_b, bits_a):
+        k = int(np.flatnonzero(bits_b != bits_a)[0])
+        raise OpMismatch(f"{op['name']}: the result depends on arena contents outside its declared read ranges (first at written element {k})")
+    rms_g = rms(q)
+    rms_f = None
+    if rms_rule_applies(op, mode):
+        # the interpreter's fp32 arithmetic on the same inputs (restored: the precise step may have worked in place)
+        after = [ref.A[lo:hi].copy() for lo, hi in reads]
+        for (lo, hi), v in zip(reads, values):
+            ref.A[lo:hi] = v
+        rms_f = float_rms(ref, i, j, snap, op)
+        for (lo, hi), v in zip(reads, after):
+            ref.A[lo:hi] = v
+        # the precise results are the chain: put them back over what the fp32 step restored
+        ref.A[snap["idx"]] = snap["r"].astype(np.float32)
+        if not rms_rule_ok(rms_g, rms_f):
+            raise OpMismatch(f"{op['name']}: RMS of (g - r) / (u s) = {rms_g:.4f}, the fp32 interpreter's is {rms_f:.4f} (cap {RMS_CAP} x)")
+    return worst, rms_g, rms_f, bits_a
+
+
+def rejects(op, mode, got, before, snap, rms_fp32):
+    """the GPU tests' verdict on what an implementation left in the arena (value bound and containment: check_op; the RMS rule against
+    rms_fp32, the interpreter's fp32 figure): True = rejected. The teeth tests apply it to seeded mistakes"""
+    try:
+        _, q = check_op(op, mode, got, before, snap)
+    except OpMismatch:
+        return True
+    return rms_rule_applies(op, mode) and not rms_rule_ok(rms(q), rms_fp32)

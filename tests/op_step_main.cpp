@@ -1,7 +1,8 @@
 // op_step_main.cpp — the step interface of tests/cpu_interp.cpp as a stand-alone program, for a run under AddressSanitizer / UBSan
 // (tests/test_op_reference_cpu.py builds it with -fsanitize=address,undefined and starts it as a child process).
 //   op_step_main MODEL SEG BATCH GEMM KVPLANES
-// steps every op of the plan in fp32 and in double (a fused inverse STFT + overlap-add chained) and reads every accessor.
+// steps every op of the plan in fp32 and in double (a fused inverse STFT + overlap-add chained), writes the operands of every
+// attention op through interp_set_attention first, and reads every accessor.
 #include "cpu_interp.cpp"
 
 #include <random>
@@ -29,6 +30,24 @@ int main(int argc, char **argv)
             return 4;
         if (op.kind == OP_TAP)
             continue;
+        if (op.kind == OP_ATTENTION || op.kind == OP_LOCAL_ATTN)
+        {
+            // interp_set_attention: dense operands written over what the chain left in the op's read ranges
+            const bool loc = op.kind == OP_LOCAL_ATTN;
+            const i64 nq = loc ? (i64)op.la.B * op.la.T * op.la.H : (i64)op.at.B * op.at.Tq * op.at.H * op.at.hs;
+            const i64 nk = loc ? nq : (i64)op.at.B * op.at.Tk * op.at.H * op.at.hs;
+            std::normal_distribution<float> unit(0.f, 1.f);
+            std::vector<float> q((size_t)nq), k((size_t)nk), v((size_t)nk), d(loc ? (size_t)op.la.B * op.la.T * 16 : 0);
+            for (std::vector<float> *a : {&q, &k, &v, &d})
+                for (float &x : *a)
+                    x = unit(rng);
+            if (interp_set_attention(h, i, q.data(), k.data(), v.data(), loc ? d.data() : nullptr) != 0)
+                return 9;
+            if (interp_set_attention(h, i, q.data(), k.data(), v.data(), loc ? nullptr : q.data()) != -1) // decay of the other kind
+                return 10;
+        }
+        else if (interp_set_attention(h, i, nullptr, nullptr, nullptr, nullptr) != -1)
+            return 11;
         if (interp_step(h, i, 0) != 0)
             return 6;
         const bool chained = op.kind == OP_OLA && op.ola.x >= 0 && i > 0 && it->pl.ops[(size_t)i - 1].kind == OP_ISTFT;

@@ -22,6 +22,11 @@ raises and the test ends there: nothing more is launched.
 The variant sweep runs every GEMM of two cases on every tile of its shape's chain (dmx_debug_run_op_as), see
 test_every_tile_and_family_*.
 
+What the sweep does NOT reach: its inputs are what a 0.1 randn mixture produces through synthetic weights, and on those the
+attention kernels raise their deferred running maximum on the first key tile only, run in 64-query workgroups only, and see
+LocalState with a handful of tokens in one masked tile. tests/test_gpu_attention_crafted.py covers those paths on operands
+written straight into the attention ops' read ranges (Pair, check_launch and written_bits are shared: op_reference.py).
+
 DMX_OP_PARITY_RECORD=<dir> writes the per-op figures (profiles/op_parity_*.txt are such records)."""
 import os
 
@@ -46,115 +51,15 @@ def dmxb():
     return binding
 
 
-DEVICE_ERROR = []  # the first error the library reported from the device: after it no test of this module launches anything
-
-
-class Pair:
-    """a context and the interpreter handle of the same plan"""
-
-    def __init__(self, dmxb, L, tmp_models, case, mode, zero_segment=False):
-        assert not DEVICE_ERROR, f"an earlier launch failed on the device, nothing more is launched: {DEVICE_ERROR[0]}"
-        self.dmxb = dmxb
-        key, seg, B, _ = R.CASES[case]
-        self.B, self.mode, self.case = B, mode, case
-        self.model = dmxb.Model(tmp_models[key], 0)
-        self.ctx = dmxb.Context(self.model, seg, B, gemm=R.GEMM[mode])
-        self.n_ops, self.ctx_floats, self.floats, self.consts = self.ctx.plan_info(B)
-        self.gops = [self.ctx.op_info(B, i) for i in range(self.n_ops)]
-        # a split context of a v4 model asks for K / V operand planes and falls back to the fp32-K/V form where a projection cannot
-        # take its exact-split kernel (exec.cpp dmx_get_plan): the reference is built the same way
-        self.ref = R.Ref(L, tmp_models[key], seg, B, mode, mode != "f32" and key != 3)
-        if self.ref.floats != self.floats and not any(o["kind"] == R.OP_ATTENTION and o.get("planes") for o in self.gops):
-            self.ref.close()
-            self.ref = R.Ref(L, tmp_models[key], seg, B, mode, False)
-        rng = np.random.default_rng(seg + B)
-        mix = (0.1 * rng.standard_normal((B, 2, seg))).astype(np.float32)
-        if zero_segment:
-            mix[B - 1] = 0.0
-        self.ref.set_mix(mix)
-        # the constants as the LIBRARY computed them (the interpreter's come from another compiler: window sums differ in the last bit)
-        self.ctx.arena_fill(B, R.CANARY_A)
-        self.consts_u32 = self.ctx.arena_read(0, self.consts).view(np.uint32).copy()
-        self.buf = np.empty(self.ctx_floats, np.float32)
-
-    def assert_same_plan(self):
-        ref = self.ref
-        assert ref.n_ops == self.n_ops and ref.floats == self.floats and ref.consts == self.consts
-        for a, b in zip(ref.ops, self.gops):
-            assert (a["name"], a["kind"], a["reads"], a["writes"], a["scratch"]) == (b["name"], b["kind"], b["reads"], b["writes"], b["scratch"])
-
-    def prepare(self, canary, reads, values):
-        self.ctx.arena_fill(self.B, canary)
-        for (lo, hi), v in zip(reads, values):
-            self.ctx.arena_write(lo, v)
-
-    def close(self):
-        self.ref.close()
-        self.ctx.close()
-        self.model.close()
-
-
-def float_rms(ref, i, j, snap, op):
-    """RMS ratio of the interpreter's fp32 arithmetic for ops i .. j on the current inputs; leaves the arena as it was"""
-    hull = [rg for k in range(i, j + 1) for rg in ref.ops[k]["writes"]]
-    saved = [ref.A[lo:hi].copy() for lo, hi in hull]
-    for k in range(i, j + 1):
-        ref.step(k, False)
-    q = [R.ratios(ref.A[snap["idx"]], snap["r"], snap["s"])]
-    pr = R.plane_range(op)
-    if pr:
-        total, _ = R.bf16_planes_sum(ref.A[pr[0]:pr[1]].view(np.uint16), op["kvPlane"])
-        q.append(R.ratios(total, *snap["planes"]))
-    for (lo, hi), v in zip(hull, saved):
-        ref.A[lo:hi] = v
-    return R.rms(np.concatenate(q))
-
-
-def written_bits(fetch, op, snap):
-    """the bits of everything the op wrote; fetch(lo, hi) -> the arena's uint32 words [lo, hi) (write ranges only are asked for)"""
-    pr, idx, out = R.plane_range(op), snap["idx"], []
-    for lo, hi in op["writes"]:
-        words = fetch(lo, hi)
-        out.append(words[idx[(idx >= lo) & (idx < hi)] - lo])
-        if pr and lo <= pr[0] and pr[1] <= hi:
-            out.append(words[pr[0] - lo:pr[1] - lo])
-    return np.concatenate(out)
+Pair, DEVICE_ERROR, written_bits = R.Pair, R.DEVICE_ERROR, R.written_bits  # (shared with tests/test_gpu_attention_crafted.py)
 
 
 def check_launch(pair, i, j, op, reads, values, snap, rows, launched, variants):
-    ref, ctx, B, mode = pair.ref, pair.ctx, pair.B, pair.mode
-    # ---- the kernel on canary A
-    pair.prepare(R.CANARY_A, reads, values)
-    ctx.run_op(B, j)
-    got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
-    before = R.expected_arena(pair.ctx_floats, R.CANARY_A, pair.consts_u32, reads, values)
-    worst, q = R.check_op(op, mode, got, before, snap)
-    bits_a = written_bits(lambda lo, hi: got[lo:hi], op, snap)
     launched.append((op.get("cfg", -1), op.get("family", -1), op.get("label")))
-    # ---- the same launch with canary B in everything it does not declare to read
-    pair.prepare(R.CANARY_B, reads, values)
-    ctx.run_op(B, j)
-    bits_b = written_bits(lambda lo, hi: ctx.arena_read(lo, hi - lo).view(np.uint32), op, snap)
-    if not np.array_equal(bits_b, bits_a):
-        k = int(np.flatnonzero(bits_b != bits_a)[0])
-        raise R.OpMismatch(f"{op['name']}: the result depends on arena contents outside its declared read ranges (first at written element {k})")
-    rms_g = R.rms(q)
-    rms_f = None
-    if R.rms_rule_applies(op, mode):
-        # the interpreter's fp32 arithmetic on the same inputs (restored: the precise step may have worked in place)
-        after = [ref.A[lo:hi].copy() for lo, hi in reads]
-        for (lo, hi), v in zip(reads, values):
-            ref.A[lo:hi] = v
-        rms_f = float_rms(ref, i, j, snap, op)
-        for (lo, hi), v in zip(reads, after):
-            ref.A[lo:hi] = v
-        # the precise results are the chain: put them back over what the fp32 step restored
-        ref.A[snap["idx"]] = snap["r"].astype(np.float32)
-        if not R.rms_rule_ok(rms_g, rms_f):
-            raise R.OpMismatch(f"{op['name']}: RMS of (g - r) / (u s) = {rms_g:.4f}, the fp32 interpreter's is {rms_f:.4f} (cap {R.RMS_CAP} x)")
+    worst, rms_g, rms_f, bits_a = R.check_launch(pair, i, j, op, reads, values, snap)
     with np.errstate(divide="ignore", invalid="ignore"):
         loose = float(np.nanmedian(snap["s"] / np.abs(snap["r"]))) if snap["idx"].size else 0.0  # how far s is above |r|: the bound's slack
-    rows.append((op["name"], op.get("label"), op.get("K", 0), R.bound_c(op, mode), worst, rms_g, rms_f, loose))
+    rows.append((op["name"], op.get("label"), op.get("K", 0), R.bound_c(op, pair.mode), worst, rms_g, rms_f, loose))
     if variants is not None and op["kind"] == R.OP_IGEMM:
         run_variants(pair, j, op, reads, values, snap, bits_a, variants, launched)
 
