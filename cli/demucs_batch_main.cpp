@@ -2,7 +2,7 @@
 //   demucs_batch.cpp.main [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
-//                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB]
+//                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
 // (at 44.1 kHz, or with DMX_RESAMPLE=1 at any rate) the files go to the GPU as they are and are decoded there
@@ -42,6 +42,11 @@
 //                            every output its own gain (DMX_LOUD_EACH); --loudness only measures. --max-peak DB (default -1) is the
 //                            ceiling of the sample peak: the gain is reduced where it would be exceeded. A line per output is
 //                            printed: "vocals: -14.23 LUFS, gain +3.10 dB". They combine with every option above.
+//   --true-peak              with --loudnorm or --loudnorm-each: --max-peak is a ceiling of the TRUE peak (4x oversampled below
+//                            96 kHz; DMX_LOUD_TRUE_PEAK), -1 dBTP by default. --meters (with any of the three flags above) extends
+//                            the line: "vocals: -14.23 LUFS, gain +3.10 dB, TP -1.00 dBTP, LRA 6.20 LU, max M -9.80, max S -11.42",
+//                            TP the true peak of what leaves, LRA the loudness range, M and S the largest momentary and short-term
+//                            loudness in LUFS of the output as measured. These two take no value.
 //   --flac-level N           with --flac: 0 (default) FIXED predictors alone, 1 adds an LPC predictor of order 8, 2 orders 8
 //                            and 12 (smaller files, the same samples); without --flac it changes nothing
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
@@ -72,7 +77,7 @@ using namespace demucscpp;
     std::cerr << "Usage: " << argv0 << " [--shifts N] [--overlap F] [--shift-offsets a,b,...] [--two-stems NAME]"
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
-              << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB]"
+              << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
@@ -119,6 +124,8 @@ int main(int argc, const char **argv)
     int loud_mode = -1; // DMX_LOUD_*, -1: not given
     float loud_target = -14.0f, max_peak_db = -1.0f;
     LoudnessReport loud_report; // filled by the remix calls when a loudness flag is given
+    bool true_peak = false, with_meters = false;
+    MetersReport meters_report; // filled as well with --meters
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -134,6 +141,12 @@ int main(int argc, const char **argv)
         if (opt == "--flac") // no value either
         {
             flac = with_out_opts = true;
+            --a;
+            continue;
+        }
+        if (opt == "--true-peak" || opt == "--meters") // no value; what they need is checked behind the loop
+        {
+            (opt == "--meters" ? with_meters : true_peak) = true;
             --a;
             continue;
         }
@@ -272,6 +285,16 @@ int main(int argc, const char **argv)
         std::cerr << "--remix and --two-stems exclude each other" << std::endl;
         usage(argv[0]);
     }
+    if (true_peak && loud_mode != DMX_LOUD_MIXTURE && loud_mode != DMX_LOUD_EACH)
+    {
+        std::cerr << "--true-peak needs --loudnorm or --loudnorm-each: it is the ceiling of their gain" << std::endl;
+        usage(argv[0]);
+    }
+    if (with_meters && loud_mode < 0)
+    {
+        std::cerr << "--meters needs --loudnorm, --loudnorm-each or --loudness: it extends their report" << std::endl;
+        usage(argv[0]);
+    }
     if (flac && (float32_given || out_opts.encoding == DMX_PCM_F32))
     {
         std::cerr << "--float32 and --flac exclude each other: FLAC holds integer samples (--int16, the default, or --int24)" << std::endl;
@@ -315,6 +338,8 @@ int main(int argc, const char **argv)
         {
             remix.loudness.on = true, remix.loudness.mode = loud_mode, remix.loudness.target_lufs = loud_target;
             remix.loudness.max_peak = (float)std::pow(10.0, (double)max_peak_db / 20.0);
+            remix.loudness.true_peak = true_peak;
+            remix.loudness.meters = with_meters ? &meters_report : nullptr;
         }
         if (!with_out_opts) // FLAC inputs or other rates without an output option: the float32 stems, through unit gains
             remix.encoding = DMX_PCM_F32, remix.clip = DMX_CLIP_NONE;
@@ -562,6 +587,25 @@ int main(int argc, const char **argv)
                 {
                     snprintf(line, sizeof line, ", gain %+.2f dB", 20.0 * std::log10((double)lr.gain));
                     std::cout << line;
+                }
+                if (with_meters) // the true peak of what leaves (the mixture: as measured), then the meters of the signal as measured
+                {
+                    const dmx_meters_result &mr = meters_report[(size_t)f][o];
+                    const float tp = o < po.size() ? lr.gain * mr.true_peak : mr.true_peak;
+                    auto lu = [](int32_t c, const char *unit) {
+                        char b[48];
+                        if (c == DMX_LUFS_UNMEASURABLE)
+                            snprintf(b, sizeof b, "n/a");
+                        else
+                            snprintf(b, sizeof b, "%.2f%s", c / 100.0, unit);
+                        return std::string(b);
+                    };
+                    if (tp > 0.0f)
+                        snprintf(line, sizeof line, ", TP %.2f dBTP", 20.0 * std::log10((double)tp));
+                    else
+                        snprintf(line, sizeof line, ", TP -inf dBTP");
+                    std::cout << line << ", LRA " << lu(mr.lra_c, " LU") << ", max M " << lu(mr.max_momentary_c, "") << ", max S "
+                              << lu(mr.max_short_c, "");
                 }
                 std::cout << std::endl;
             }

@@ -47,6 +47,8 @@ EXPORTS = [
     "dmx_loudness_coefficients", "dmx_loudness_gain_table", "dmx_loudness_check", "dmx_loudness_workspace_bytes", "dmx_loudness_device",
     "dmx_loudness_device_timed", "dmx_loudness", "dmx_loud_encode_device", "dmx_loud_encode",
     "dmx_tracks_infer_loud", "dmx_tracks_infer_from_flac_loud",
+    "dmx_true_peak_filter", "dmx_meters_workspace_bytes", "dmx_meters_device", "dmx_meters_device_timed", "dmx_meters",
+    "dmx_loud_encode_meters_device", "dmx_loud_encode_meters", "dmx_tracks_infer_meters", "dmx_tracks_infer_from_flac_meters",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -190,6 +192,16 @@ def lib():
         L.dmx_loud_encode.argtypes = [ci, vp, ci, i64, vp, vp, vp, ci, vp, vp, vp]
         L.dmx_tracks_infer_loud.argtypes = L.dmx_tracks_infer_rates.argtypes + [vp, vp]
         L.dmx_tracks_infer_from_flac_loud.argtypes = L.dmx_tracks_infer_from_flac.argtypes + [vp, vp]
+        L.dmx_true_peak_filter.argtypes = [ci, vp, vp]
+        L.dmx_meters_workspace_bytes.argtypes = [i64]
+        L.dmx_meters_workspace_bytes.restype = i64
+        L.dmx_meters_device.argtypes = L.dmx_loudness_device.argtypes + [vp]
+        L.dmx_meters_device_timed.argtypes = [ci, vp, i64, i64, ci, vp, vp, vp]
+        L.dmx_meters.argtypes = L.dmx_loudness.argtypes + [vp]
+        L.dmx_loud_encode_meters_device.argtypes = L.dmx_loud_encode_device.argtypes + [vp]
+        L.dmx_loud_encode_meters.argtypes = L.dmx_loud_encode.argtypes + [vp]
+        L.dmx_tracks_infer_meters.argtypes = L.dmx_tracks_infer_loud.argtypes + [vp]
+        L.dmx_tracks_infer_from_flac_meters.argtypes = L.dmx_tracks_infer_from_flac_loud.argtypes + [vp]
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -524,9 +536,9 @@ class Context:
         return finish()
 
     def tracks_pcm(self, audios, spec: Optional[OutputSpec] = None, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None,
-                   progress=None, layout: int = LAYOUT_PLANAR, out=None, loudness=None):
+                   progress=None, layout: int = LAYOUT_PLANAR, out=None, loudness=None, meters: bool = False):
         """loudness: None, or a LoudnessSpec - the spec's outputs as 0/1 gains (the same bits) through dmx_tracks_infer_loud;
-        returns (outs, peaks, report) as tracks_remix() does.
+        returns (outs, peaks, report) as tracks_remix() does, with meters=True (outs, peaks, report, meters).
         tracks_opts() whose stems leave the GPU as WAV data (dmx_tracks_infer_pcm): two-stems, clip mode and sample
         format are applied on the device. Returns (outs, peaks): outs[t] is a list of n_out arrays, np.int16 (n, 2),
         np.uint8 (n, 2, 3) (packed little-endian 24 bit) or np.float32 (n, 2); peaks[t] is an np.float32 (n_out,) array.
@@ -536,7 +548,8 @@ class Context:
             assert out is None, "loudness=: buffers to reuse are not taken"
             g = np.eye(self.S, self.S + 1, dtype=np.float32) if spec.stem < 0 else remix_two_stems(self.S, spec.stem, OTHER_ADD)
             return self.tracks_rates(audios, None, RemixSpec(g, spec.encoding, spec.clip), False, None, None, n_shifts, overlap, shift_offsets,
-                                     progress, layout, loudness)
+                                     progress, layout, loudness, meters)
+        assert not meters, "meters=True needs loudness="
         T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = self._output_count(spec)
         bufs, op = _byte_results([n_out * output_bytes(spec, n) for n in ns], out, exact=True)
@@ -570,16 +583,20 @@ class Context:
         return finish() if spec is None else (_pcm_results(bufs, spec, ns, n_out), _cut_peaks(peaks, T, n_out))
 
     def tracks_remix(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
-                     shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, out=None, peaks=None, loudness=None):
+                     shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, out=None, peaks=None, loudness=None,
+                     meters: bool = False):
         """tracks_pcm() whose outputs are rows of gains over the stems and the original mixture (dmx_tracks_infer_remix).
         loudness: None, or a LoudnessSpec - the call goes through dmx_tracks_infer_loud and returns (outs, peaks, report), report
-        a (T, n_out + 1) array of LOUDNESS_DTYPE, per track its outputs and then its mixture.
+        a (T, n_out + 1) array of LOUDNESS_DTYPE, per track its outputs and then its mixture. meters=True (with loudness=): the call
+        goes through dmx_tracks_infer_meters and returns (outs, peaks, report, meters), meters a (T, n_out + 1) array of METERS_DTYPE.
         models None: this context's model, shift_offsets (T, n_shifts); else a bag as tracks_bag(), shift_offsets
         (T, Q, n_shifts). Returns (outs, peaks) in the shapes of tracks_pcm(), n_out = spec.n_out. `out` / `peaks`: buffers
         to reuse (np.uint8 of n_out * output_bytes bytes per track; a flat np.float32 array of at least T * n_out entries)."""
         if loudness is not None:
             assert out is None and peaks is None, "loudness=: buffers to reuse are not taken"
-            return self.tracks_rates(audios, None, spec, False, models, weights, n_shifts, overlap, shift_offsets, progress, layout, loudness)
+            return self.tracks_rates(audios, None, spec, False, models, weights, n_shifts, overlap, shift_offsets, progress, layout, loudness,
+                                     meters)
+        assert not meters, "meters=True needs loudness="
         T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = max(spec.n_out, 0)
         bufs, op = _byte_results([n_out * b for b in _remix_bytes(spec, ns, False)], out, exact=True)
@@ -593,8 +610,9 @@ class Context:
 
     def tracks_from_flac(self, files, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                          shift_offsets=None, flac_out: bool = False, progress=None, track_status=None, out=None, any_rate: bool = False,
-                         loudness=None):
-        """tracks_remix() (flac_out False) or tracks_flac() at 44100 Hz (flac_out True) on tracks given as the bytes of .flac
+                         loudness=None, meters: bool = False):
+        """meters=True (with loudness=): through dmx_tracks_infer_from_flac_meters, and the meters report is returned last.
+        tracks_remix() (flac_out False) or tracks_flac() at 44100 Hz (flac_out True) on tracks given as the bytes of .flac
         files (dmx_tracks_infer_from_flac). any_rate: every track runs at the rate of its file, as tracks_rates() runs it
         (dmx_tracks_infer_from_flac_rates); the outputs have the file's frames and rate. Returns (outs, peaks, track_status): track_status np.int64 (T, 2) = {status, good}
         per track. A damaged track raises DmxError after all work has drained; pass `track_status` (np.int64, T * 2, flat) to
@@ -628,6 +646,11 @@ class Context:
                     raise DmxError(5, f"tracks_from_flac: track {t}: sample rate {flac_probe(f).sample_rate} (any_rate=True takes other rates)")
             report = np.zeros((max(T, 1), n_out + 1), LOUDNESS_DTYPE)
             call, extra = lib().dmx_tracks_infer_from_flac_loud, (ctypes.byref(loudness), report.ctypes.data)
+            if meters:
+                mrep = np.zeros((max(T, 1), n_out + 1), METERS_DTYPE)
+                call, extra = lib().dmx_tracks_infer_from_flac_meters, extra + (mrep.ctypes.data,)
+        else:
+            assert not meters, "meters=True needs loudness="
         rc = call(self.h, mp, Q, wp, T, _pointers(imgs), fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), 1 if flac_out else 0, op,
                   sizes.ctypes.data, peaks.ctypes.data, track_status.ctypes.data, cbp, None, *extra)
         outs = _flac_files(bufs, per, sizes, n_out) if flac_out else _pcm_results(bufs, spec.output_spec(), ns, n_out)
@@ -637,19 +660,22 @@ class Context:
             e.partial = (outs, pk)
             raise e
         if loudness is not None:
-            return outs, pk, track_status[:2 * T].reshape(T, 2), report[:T]
+            return (outs, pk, track_status[:2 * T].reshape(T, 2), report[:T]) + ((mrep[:T],) if meters else ())
         return outs, pk, track_status[:2 * T].reshape(T, 2)
 
     def tracks_rates(self, audios, rates, spec: Optional[RemixSpec] = None, flac: bool = False, models=None, weights=None,
-                     n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, loudness=None):
+                     n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, loudness=None,
+                     meters: bool = False):
         """loudness: None, or a LoudnessSpec (a RemixSpec is then required; rates may be None: all 44100) - the call goes through
-        dmx_tracks_infer_loud and returns (outs, peaks, report), report a (T, n_out + 1) array of LOUDNESS_DTYPE.
+        dmx_tracks_infer_loud and returns (outs, peaks, report), report a (T, n_out + 1) array of LOUDNESS_DTYPE; with meters=True
+        through dmx_tracks_infer_meters, and (outs, peaks, report, meters) with meters a (T, n_out + 1) array of METERS_DTYPE.
         Tracks at their own sample rates (dmx_tracks_infer_rates): audios[t] is (2, n_t) at rates[t] Hz; a track that is not
         at 44100 Hz is converted on the device in front of the model and its stems behind it. spec None: a list of (S, 2, n_t)
         float32 arrays as tracks_opts() / tracks_bag(); a RemixSpec: (outs, peaks) as tracks_remix(), or with flac=True
         (files, peaks) as tracks_flac(), every file at its track's rate. models / weights / shift_offsets as tracks_remix()."""
         T, ns, src, ap, na = _track_inputs(audios, layout)
         assert rates is not None or loudness is not None
+        assert loudness is not None or not meters, "meters=True needs loudness="
         assert rates is None or len(rates) == T
         ra = None if rates is None else (ctypes.c_int * max(T, 1))(*[int(r) for r in rates])
         mp, Q, wp, keep = _models_weights(models, weights, self.S)
@@ -668,8 +694,12 @@ class Context:
             sp, sz, pk = ctypes.byref(spec.c), sizes.ctypes.data, peaks.ctypes.data
         if loudness is not None:
             report = np.zeros((max(T, 1), (0 if spec is None else n_out) + 1), LOUDNESS_DTYPE)
-            _chk(lib().dmx_tracks_infer_loud(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op, sz,
-                                             pk, layout, cbp, None, ctypes.byref(loudness), report.ctypes.data))
+            call, extra = lib().dmx_tracks_infer_loud, ()
+            if meters:
+                mrep = np.zeros(report.shape, METERS_DTYPE)
+                call, extra = lib().dmx_tracks_infer_meters, (mrep.ctypes.data,)
+            _chk(call(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op, sz, pk, layout, cbp, None,
+                      ctypes.byref(loudness), report.ctypes.data, *extra))
         else:
             _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op, sz,
                                               pk, layout, cbp, None))
@@ -677,19 +707,21 @@ class Context:
             return finish()
         outs = _flac_files(bufs, per, sizes, n_out) if flac else _pcm_results(bufs, spec.output_spec(), ns, n_out)
         if loudness is not None:
-            return outs, _cut_peaks(peaks, T, n_out), report[:T]
+            return (outs, _cut_peaks(peaks, T, n_out), report[:T]) + ((mrep[:T],) if meters else ())
         return outs, _cut_peaks(peaks, T, n_out)
 
     def tracks_flac(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                     shift_offsets=None, sample_rate: int = 44100, progress=None, layout: int = LAYOUT_PLANAR, out=None, sizes=None,
-                    peaks=None, loudness=None):
+                    peaks=None, loudness=None, meters: bool = False):
         """tracks_remix() whose outputs leave as .flac files (dmx_tracks_infer_flac): spec.encoding PCM_S16 or PCM_S24.
         Returns (files, peaks): files[t][o] the bytes of track t's output o, peaks as tracks_remix(). `out`: buffers to reuse
         (np.uint8 of n_out * flac_bound(bits, n) bytes per track); `sizes`: a flat np.int64 array of at least T * n_out."""
         if loudness is not None:  # (files, peaks, report)
             assert out is None and sizes is None and peaks is None, "loudness=: buffers to reuse are not taken"
             assert int(sample_rate) == 44100, "loudness=: the tracks are at 44100 Hz; tracks_rates() takes tracks at other rates"
-            return self.tracks_rates(audios, None, spec, True, models, weights, n_shifts, overlap, shift_offsets, progress, layout, loudness)
+            return self.tracks_rates(audios, None, spec, True, models, weights, n_shifts, overlap, shift_offsets, progress, layout, loudness,
+                                     meters)
+        assert not meters, "meters=True needs loudness="
         T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = max(spec.n_out, 0)
         bits = 24 if spec.encoding == PCM_S24 else 16
@@ -899,15 +931,17 @@ def remix_encode(planes: np.ndarray, mix: Optional[np.ndarray], spec: RemixSpec,
 LOUD_MEASURE, LOUD_MIXTURE, LOUD_EACH = 0, 1, 2  # DMX_LOUD_*
 LUFS_UNMEASURABLE = -(2 ** 31)  # DMX_LUFS_UNMEASURABLE
 LOUD_MIN_RATE = 4000  # DMX_LOUD_MIN_RATE
+LOUD_TRUE_PEAK = 0x100  # DMX_LOUD_TRUE_PEAK, OR-ed into the mode: max_peak is a true-peak ceiling
 
 
 class LoudnessSpec(ctypes.Structure):
     """dmx_loudness_spec: mode LOUD_*, the target in LUFS (finite, in [-70, 0]) and the ceiling of the sample peak as a linear
-    value (> 0; inf: none). The default ceiling is -1 dBFS."""
+    value (> 0; inf: none). The default ceiling is -1 dBFS. true_peak: the ceiling is one of the true peak (-1 dBTP), the flag
+    LOUD_TRUE_PEAK in the mode."""
     _fields_ = [("mode", ctypes.c_int), ("target_lufs", ctypes.c_float), ("max_peak", ctypes.c_float)]
 
-    def __init__(self, mode=LOUD_MIXTURE, target_lufs=-14.0, max_peak=10.0 ** (-1.0 / 20.0)):
-        super().__init__(int(mode), float(target_lufs), float(max_peak))
+    def __init__(self, mode=LOUD_MIXTURE, target_lufs=-14.0, max_peak=10.0 ** (-1.0 / 20.0), true_peak: bool = False):
+        super().__init__(int(mode) | (LOUD_TRUE_PEAK if true_peak else 0), float(target_lufs), float(max_peak))
 
 
 class LoudnessResult(ctypes.Structure):
@@ -916,6 +950,38 @@ class LoudnessResult(ctypes.Structure):
 
 
 LOUDNESS_DTYPE = np.dtype([("lufs_c", "<i4"), ("gain", "<f4"), ("lufs", "<f8")])  # an array of dmx_loudness_result
+
+
+class MetersResult(ctypes.Structure):
+    """dmx_meters_result: the true peak (linear, of the signal as measured), and in hundredths of a LU or LUFS_UNMEASURABLE the
+    loudness range and the largest momentary and short-term loudness"""
+    _fields_ = [("true_peak", ctypes.c_float), ("lra_c", ctypes.c_int32), ("max_momentary_c", ctypes.c_int32), ("max_short_c", ctypes.c_int32)]
+
+
+METERS_DTYPE = np.dtype([("true_peak", "<f4"), ("lra_c", "<i4"), ("max_momentary_c", "<i4"), ("max_short_c", "<i4")])  # dmx_meters_result
+
+
+def true_peak_filter(rate: int):
+    """(F, taps): the oversampling factor at `rate` and the 12 F + 1 float32 taps of the true-peak filter (dmx_true_peak_filter; no GPU)"""
+    F = ctypes.c_int(0)
+    t = np.zeros(49, np.float32)
+    _chk(lib().dmx_true_peak_filter(int(rate), ctypes.byref(F), t.ctypes.data))
+    return F.value, t[:12 * F.value + 1].copy()
+
+
+def meters_workspace_bytes(n: int) -> int:
+    return lib().dmx_meters_workspace_bytes(int(n))
+
+
+def meters(x: np.ndarray, rate: int, interleaved: bool = False, device: int = 0):
+    """loudness() plus the meters of one stereo signal (dmx_meters): -> (LoudnessResult, e, MetersResult)"""
+    x = np.ascontiguousarray(x, np.float32)
+    n = x.shape[0] if interleaved else x.shape[1]
+    assert x.shape == ((n, 2) if interleaved else (2, n))
+    res, m = LoudnessResult(), MetersResult()
+    e = np.zeros((2, n // ((int(rate) + 5) // 10) if rate > 0 else 0), np.float64)
+    _chk(lib().dmx_meters(device, x.ctypes.data, n, int(bool(interleaved)), int(rate), ctypes.byref(res), e.ctypes.data, ctypes.byref(m)))
+    return res, e, m
 
 
 def loudness_coefficients(rate: int) -> np.ndarray:
@@ -953,9 +1019,10 @@ def loudness(x: np.ndarray, rate: int, interleaved: bool = False, device: int = 
     return res, e
 
 
-def loud_encode(planes: np.ndarray, mix: np.ndarray, spec: RemixSpec, loud: LoudnessSpec, rate: int, device: int = 0):
+def loud_encode(planes: np.ndarray, mix: np.ndarray, spec: RemixSpec, loud: LoudnessSpec, rate: int, device: int = 0, meters: bool = False):
     """The remix output stage behind the loudness stage (dmx_loud_encode): planes (S, 2, n) float32, mix (2, n) float32 ->
-    (list of n_out arrays as tracks_pcm, peaks, report) with report a (n_out + 1,) array of LOUDNESS_DTYPE, the mixture last."""
+    (list of n_out arrays as tracks_pcm, peaks, report) with report a (n_out + 1,) array of LOUDNESS_DTYPE, the mixture last.
+    meters=True (dmx_loud_encode_meters): (outs, peaks, report, meters), meters a (n_out + 1,) array of METERS_DTYPE."""
     planes = np.ascontiguousarray(planes, np.float32)
     S, two, n = planes.shape
     assert two == 2 and mix is not None and mix.shape == (2, n)
@@ -964,6 +1031,11 @@ def loud_encode(planes: np.ndarray, mix: np.ndarray, spec: RemixSpec, loud: Loud
     buf = np.zeros(max(n_out * n * _frame_bytes(spec.encoding), 1), np.uint8)
     peaks = np.zeros(max(n_out, 1), np.float32)
     report = np.zeros(n_out + 1, LOUDNESS_DTYPE)
+    if meters:
+        mrep = np.zeros(n_out + 1, METERS_DTYPE)
+        _chk(lib().dmx_loud_encode_meters(device, planes.ctypes.data, S, n, mi.ctypes.data, ctypes.byref(spec.c), ctypes.byref(loud), int(rate),
+                                          buf.ctypes.data, peaks.ctypes.data, report.ctypes.data, mrep.ctypes.data))
+        return pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out], report, mrep
     _chk(lib().dmx_loud_encode(device, planes.ctypes.data, S, n, mi.ctypes.data, ctypes.byref(spec.c), ctypes.byref(loud), int(rate),
                                buf.ctypes.data, peaks.ctypes.data, report.ctypes.data))
     return pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out], report

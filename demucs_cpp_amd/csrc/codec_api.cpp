@@ -156,8 +156,10 @@ int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate,
 {
     if (!spec)
         return fail(DMX_ERR_ARG, "%s: null loudness spec", fn);
-    if (spec->mode != DMX_LOUD_MEASURE && spec->mode != DMX_LOUD_MIXTURE && spec->mode != DMX_LOUD_EACH)
-        return fail(DMX_ERR_ARG, "%s: loudness spec: mode %d (DMX_LOUD_MEASURE 0, DMX_LOUD_MIXTURE 1, DMX_LOUD_EACH 2)", fn, spec->mode);
+    const int base = spec->mode & ~DMX_LOUD_TRUE_PEAK;
+    if (spec->mode < 0 || (base != DMX_LOUD_MEASURE && base != DMX_LOUD_MIXTURE && base != DMX_LOUD_EACH))
+        return fail(DMX_ERR_ARG, "%s: loudness spec: mode %d (DMX_LOUD_MEASURE 0, DMX_LOUD_MIXTURE 1, DMX_LOUD_EACH 2, each alone or with DMX_LOUD_TRUE_PEAK 0x100)",
+                    fn, spec->mode);
     if (!std::isfinite(spec->target_lufs) || spec->target_lufs < -70.0f || spec->target_lufs > 0.0f)
         return fail(DMX_ERR_ARG, "%s: loudness spec: target_lufs %g is not in [-70, 0]", fn, (double)spec->target_lufs);
     if (!(spec->max_peak > 0.0f))
@@ -307,11 +309,11 @@ extern "C" int dmx_loudness(int device, const float *x, int64_t n, int interleav
     return DMX_OK;
 }
 
-extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride, const float *d_mix,
-                                      const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out, float *d_peaks,
-                                      dmx_loudness_result *d_report, void *d_work, void *stream)
+// d_meters: null (dmx_loud_encode_device: the workspace is the one without meters), or n_out + 1 entries on the device
+static int loud_encode_device(const char *fn, int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                              const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                              float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream, dmx_meters_result *d_meters)
 {
-    const char *fn = "dmx_loud_encode_device";
     PcmGains G;
     DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
     DMXCHK(loud_check(fn, loud, rate));
@@ -322,8 +324,8 @@ extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_s
         return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n <= plane_stride, n < 2^36)", fn, (long long)n,
                     (long long)plane_stride);
     if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_planes & 3) != 0 || ((uintptr_t)d_peaks & 3) != 0 || ((uintptr_t)d_mix & 3) != 0 ||
-        ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_report & 7) != 0)
-        return fail(DMX_ERR_ARG, "%s: d_out and d_work must be 16-byte aligned, d_report 8-byte aligned, d_planes, d_mix and d_peaks 4-byte aligned",
+        ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_report & 7) != 0 || ((uintptr_t)d_meters & 3) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_out and d_work must be 16-byte aligned, d_report 8-byte aligned, d_planes, d_mix, d_peaks and d_meters 4-byte aligned",
                     fn);
     LoudPlan lp;
     if (loud_plan(rate, n, &lp) != 0)
@@ -347,9 +349,32 @@ extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_s
     launch_loud_measure(pp, G, lp, work, 0, nullptr, nullptr, s);
     launch_loud_measure(pp, M, lp, work, G.nOut, nullptr, nullptr, s);
     launch_remix_peak(&pp, 1, G, s);
-    launch_loud_gain(work, slotBytes, G.nOut, (unsigned *)d_peaks, loud->mode, (int)rintf(100.0f * loud->target_lufs), loud->max_peak, T, gains,
-                     d_report, s);
-    if (loud->mode == DMX_LOUD_MEASURE)
+    const int mode = loud->mode & ~DMX_LOUD_TRUE_PEAK;
+    const bool byTp = (loud->mode & DMX_LOUD_TRUE_PEAK) != 0;
+    // the true peaks: behind the gains in their 64 bytes (n_out <= 8 of each), or, with meters, n_out + 1 of them in the meters' part
+    unsigned *tp = d_meters ? (unsigned *)(work + (i64)(G.nOut + 1) * slotBytes + 64) : (unsigned *)(gains + PcmGains::kMaxOut);
+    if (byTp || d_meters)
+    {
+        TpFilter f;
+        tp_filter(rate, &f);
+        HIPCHK(hipMemsetAsync(tp, 0, sizeof(unsigned) * (size_t)(G.nOut + (d_meters ? 1 : 0)), s));
+        LoudPiece tq = pp;
+        tq.peaks = tp;
+        launch_true_peak(&tq, 1, G, f, s);
+        if (d_meters)
+        {
+            tq.peaks = tp + G.nOut;
+            launch_true_peak(&tq, 1, M, f, s);
+            launch_meters(work, 0, G.nOut + 1, lp, tp, d_meters, s);
+        }
+    }
+    if (byTp)
+        launch_loud_gain_tp(work, slotBytes, G.nOut, (unsigned *)d_peaks, tp, mode, (int)rintf(100.0f * loud->target_lufs), loud->max_peak, T,
+                            gains, d_report, s);
+    else
+        launch_loud_gain(work, slotBytes, G.nOut, (unsigned *)d_peaks, mode, (int)rintf(100.0f * loud->target_lufs), loud->max_peak, T, gains,
+                         d_report, s);
+    if (mode == DMX_LOUD_MEASURE)
         launch_remix_encode(&pp, 1, G, spec->encoding, spec->clip, s);
     else
         launch_loud_encode(&pp, 1, G, spec->encoding, spec->clip, s);
@@ -357,10 +382,31 @@ extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_s
     return DMX_OK;
 }
 
-extern "C" int dmx_loud_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
-                               const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report)
+extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride, const float *d_mix,
+                                      const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out, float *d_peaks,
+                                      dmx_loudness_result *d_report, void *d_work, void *stream)
 {
-    const char *fn = "dmx_loud_encode";
+    return loud_encode_device("dmx_loud_encode_device", device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks,
+                              d_report, d_work, stream, nullptr);
+}
+
+extern "C" int dmx_loud_encode_meters_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                             const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                                             float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream,
+                                             dmx_meters_result *d_meters)
+{
+    const char *fn = "dmx_loud_encode_meters_device";
+    if (!d_meters)
+        return fail(DMX_ERR_ARG, "%s: null d_meters pointer", fn);
+    return loud_encode_device(fn, device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks, d_report, d_work, stream,
+                              d_meters);
+}
+
+// meters: null, or n_out + 1 entries; withMeters: the entry point is dmx_loud_encode_meters
+static int loud_encode_host(const char *fn, int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                            const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
+                            dmx_meters_result *meters)
+{
     PcmGains G;
     DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
     DMXCHK(loud_check(fn, loud, rate));
@@ -370,8 +416,9 @@ extern "C" int dmx_loud_encode(int device, const float *planes, int n_sources, i
     const int nOut = G.nOut;
     const i64 bytes = n * dmx_pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
     const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n, mixBytes = sizeof(float) * 2 * (size_t)n;
-    const size_t workBytes = (size_t)((nOut + 1) * loud_workspace_bytes(n) + 64);
-    const size_t smallBytes = 256 + sizeof(dmx_loudness_result) * (size_t)(nOut + 1); // the peaks, then the report
+    const size_t workBytes = (size_t)((nOut + 1) * (loud_workspace_bytes(n) + (meters ? meters_workspace_bytes(n) : 0)) + 64);
+    const size_t reportBytes = sizeof(dmx_loudness_result) * (size_t)(nOut + 1), metersBytes = sizeof(dmx_meters_result) * (size_t)(nOut + 1);
+    const size_t smallBytes = 256 + reportBytes + (meters ? metersBytes : 0); // the peaks, then the report, then the meters
     DevScratch d;
     float *dIn = (float *)d.get(inBytes + DMX_OUTPUT_STRIDE(mixBytes)); // the planes, then the mixture
     unsigned char *dOut = (unsigned char *)d.get((size_t)(nOut * devStride));
@@ -384,9 +431,150 @@ extern "C" int dmx_loud_encode(int device, const float *planes, int n_sources, i
     dmx_loudness_result *dReport = (dmx_loudness_result *)(dSmall + 256);
     if (hipMemcpy(dIn, planes, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dMix, mix, mixBytes, hipMemcpyHostToDevice) != hipSuccess)
         return fail(DMX_ERR_HIP, "%s: upload failed", fn);
-    DMXCHK(dmx_loud_encode_device(device, dIn, n_sources, n, n, dMix, spec, loud, rate, dOut, dPeaks, dReport, dWork, nullptr));
+    dmx_meters_result *dMeters = meters ? (dmx_meters_result *)(dSmall + 256 + reportBytes) : nullptr;
+    DMXCHK(loud_encode_device(fn, device, dIn, n_sources, n, n, dMix, spec, loud, rate, dOut, dPeaks, dReport, dWork, nullptr, dMeters));
     DMXCHK(pcm_download(fn, out, peaks, dOut, dPeaks, nOut, bytes, devStride));
-    if (report && hipMemcpy(report, dReport, sizeof(dmx_loudness_result) * (size_t)(nOut + 1), hipMemcpyDeviceToHost) != hipSuccess)
+    if (report && hipMemcpy(report, dReport, reportBytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    if (meters && hipMemcpy(meters, dMeters, metersBytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
+}
+
+extern "C" int dmx_loud_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                               const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report)
+{
+    return loud_encode_host("dmx_loud_encode", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, nullptr);
+}
+
+extern "C" int dmx_loud_encode_meters(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                                      const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
+                                      dmx_meters_result *meters)
+{
+    return loud_encode_host("dmx_loud_encode_meters", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, meters);
+}
+
+// --------------------------------------------------------------------------- meters (meters.hip)
+extern "C" int dmx_true_peak_filter(int rate, int *factor, float *taps)
+{
+    if (rate < 1)
+        return fail(DMX_ERR_ARG, "dmx_true_peak_filter: rate %d", rate);
+    if (!factor)
+        return fail(DMX_ERR_ARG, "dmx_true_peak_filter: null factor pointer");
+    TpFilter f;
+    tp_filter(rate, &f);
+    *factor = f.F;
+    if (taps)
+        std::memcpy(taps, f.h, sizeof(float) * (size_t)(kTpTaps * f.F + 1));
+    return DMX_OK;
+}
+extern "C" int64_t dmx_meters_workspace_bytes(int64_t n) { return meters_workspace_bytes(n); }
+
+extern "C" int dmx_meters_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                                 double *d_e, void *d_work, void *stream, dmx_meters_result *d_meters)
+{
+    const char *fn = "dmx_meters_device";
+    if (!d_meters || ((uintptr_t)d_meters & 3) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_meters is null or not 4-byte aligned", fn);
+    DMXCHK(loudness_device(fn, device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, nullptr));
+    LoudPlan lp;
+    (void)loud_plan(rate, n, &lp); // checked by the measurement
+    hipStream_t s = (hipStream_t)stream;
+    unsigned *tp = (unsigned *)((unsigned char *)d_work + loud_workspace_bytes(n));
+    RemixPiece pc;
+    PcmGains G;
+    loud_signal(d_x, n, plane_stride, &pc, &G);
+    pc.peaks = tp;
+    TpFilter f;
+    tp_filter(rate, &f);
+    HIPCHK(hipMemsetAsync(tp, 0, sizeof(unsigned), s));
+    launch_true_peak(&pc, 1, G, f, s);
+    launch_meters((const unsigned char *)d_work, 0, 1, lp, tp, d_meters, s);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_meters_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, void *d_work, void *stream,
+                                       float *ms)
+{
+    const char *fn = "dmx_meters_device_timed";
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    hipEvent_t ev[6] = {};
+    unsigned char *dSmall = nullptr; // a loudness result, a meters result, a sample peak
+    int rc = DMX_OK;
+    for (hipEvent_t &e : ev)
+        if (rc == DMX_OK && hipEventCreate(&e) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+    if (rc == DMX_OK && hipMalloc(&dSmall, 64) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK)
+        rc = loudness_device(fn, device, d_x, n, plane_stride, rate, (dmx_loudness_result *)dSmall, nullptr, d_work, stream, nullptr);
+    if (rc == DMX_OK)
+    {
+        LoudPlan lp;
+        (void)loud_plan(rate, n, &lp);
+        unsigned *tp = (unsigned *)((unsigned char *)d_work + loud_workspace_bytes(n));
+        RemixPiece pc;
+        PcmGains G;
+        loud_signal(d_x, n, plane_stride, &pc, &G);
+        TpFilter f;
+        tp_filter(rate, &f);
+        (void)hipMemsetAsync(tp, 0, sizeof(unsigned), s);
+        (void)hipMemsetAsync(dSmall + 48, 0, sizeof(unsigned), s);
+        pc.peaks = tp;
+        (void)hipEventRecord(ev[0], s);
+        launch_true_peak(&pc, 1, G, f, s);
+        (void)hipEventRecord(ev[1], s);
+        pc.peaks = (unsigned *)(dSmall + 48);
+        (void)hipEventRecord(ev[2], s);
+        launch_remix_peak(&pc, 1, G, s);
+        (void)hipEventRecord(ev[3], s);
+        (void)hipEventRecord(ev[4], s);
+        launch_meters((const unsigned char *)d_work, 0, 1, lp, tp, dSmall + 16, s);
+        (void)hipEventRecord(ev[5], s);
+        if (hipEventSynchronize(ev[5]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    }
+    for (int i = 0; i < 3 && rc == DMX_OK; ++i)
+        if (hipEventElapsedTime(&ms[i], ev[2 * i], ev[2 * i + 1]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    for (hipEvent_t e : ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    if (dSmall)
+        (void)hipFree(dSmall);
+    return rc;
+}
+
+extern "C" int dmx_meters(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e,
+                          dmx_meters_result *meters)
+{
+    const char *fn = "dmx_meters";
+    if (rate < DMX_LOUD_MIN_RATE)
+        return fail(DMX_ERR_ARG, "%s: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
+    if (!x || !result || !meters || n < 1 || n >= (int64_t)1 << 36)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer, n < 1 or n >= 2^36)", fn);
+    HIPCHK(hipSetDevice(device));
+    const size_t inBytes = sizeof(float) * 2 * (size_t)n, eBytes = sizeof(double) * 2 * (size_t)(n / ((rate + 5) / 10));
+    DevScratch d;
+    float *dX = (float *)d.get(inBytes);
+    void *dWork = d.get((size_t)(loud_workspace_bytes(n) + meters_workspace_bytes(n)));
+    unsigned char *dRes = (unsigned char *)d.get(64); // the loudness result, then the meters
+    double *dE = e && eBytes ? (double *)d.get(eBytes) : nullptr;
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (hipMemcpy(dX, x, inBytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(dmx_meters_device(device, dX, n, interleaved ? 0 : n, rate, (dmx_loudness_result *)dRes, dE, dWork, nullptr,
+                             (dmx_meters_result *)(dRes + 16)));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(result, dRes, sizeof(dmx_loudness_result), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(meters, dRes + 16, sizeof(dmx_meters_result), hipMemcpyDeviceToHost) != hipSuccess ||
+        (dE && hipMemcpy(e, dE, eBytes, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(DMX_ERR_HIP, "%s: download failed", fn);
     return DMX_OK;
 }

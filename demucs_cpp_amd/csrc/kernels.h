@@ -3,6 +3,7 @@
 #pragma once
 #include "gemm_select.h"
 #include "loudness_plan.h"
+#include "meters_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -432,6 +433,18 @@ void launch_loud_measure(const RemixPiece &pc, const PcmGains &G, const LoudPlan
 // (DMX_LOUD_*), peaks[o] *= gain, and the report of nOut + 1 entries; all on the device, one launch
 void launch_loud_gain(const unsigned char *work, i64 slotBytes, int nOut, unsigned *peaks, int mode, int targetC, float maxPeak,
                       const float *table, float *gains, void *report, hipStream_t s);
+// launch_loud_gain with the ceiling read from the true peaks tp[o] (launch_true_peak) in place of the sample peaks; peaks[o] still
+// becomes the gained SAMPLE peak
+void launch_loud_gain_tp(const unsigned char *work, i64 slotBytes, int nOut, unsigned *peaks, const unsigned *tp, int mode, int targetC,
+                         float maxPeak, const float *table, float *gains, void *report, hipStream_t s);
+// ---- the meters (meters.hip; specification: DESIGN.md section 2.15, restated in tests/meters_spec.py) ----
+// (TpFilter and the pure host functions: meters_plan.h)
+// peaks[o] of each piece = max(peaks[o], the true peak of output o over the frames the piece evaluates): the pieces' `peaks`
+// point at the bit patterns of the TRUE peaks, zeroed before the track's first piece. All pieces are at the filter's rate.
+void launch_true_peak(const RemixPiece *pieces, int P, const PcmGains &G, const TpFilter &f, hipStream_t s);
+// behind launch_loud_measure of nSignals signals in the slots slot0 ..: out[o] = {tp[o], lra_c, max_momentary_c, max_short_c},
+// nSignals entries of dmx_meters_result on the device. One launch.
+void launch_meters(const unsigned char *work, int slot0, int nSignals, const LoudPlan &lp, const unsigned *tp, void *out, hipStream_t s);
 // ---- the track path's converter (resample.hip) ----
 // outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
 // output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the

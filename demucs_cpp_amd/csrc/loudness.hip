@@ -27,8 +27,8 @@
 // The bodies are templates over the gather functor (the host driver brings its own); the kernels are instantiated for GatherRemix
 // alone. An output spec (GatherStems) is measured as its 0/1 gain matrix, which gathers the same bits (1 * x is exact).
 //
-// Out of scope: true peak (4x oversampled), loudness range, momentary and short-term meters (the hop energies are returned, a
-// caller can derive them), ReplayGain tags, the engine.
+// True peak, loudness range and the momentary and short-term maxima are meters.hip's (they read the hop energies left here);
+// loud_gain_tp_kernel is the ceiling by true peak. Out of scope: ReplayGain tags, the engine.
 //
 // With DMX_LOUDNESS_HOST defined the same bodies compile as plain C++ (tests/loudness_host_main.cpp): each kernel is a
 // sequence of phases, each a function of (tile, lane); the device kernels call them with barriers between, the host driver at
@@ -246,7 +246,7 @@ struct LoudRes
 LD_DEV LoudRes *loud_ws_res(unsigned char *slot) { return reinterpret_cast<LoudRes *>(slot); }
 LD_DEV double *loud_ws_states(unsigned char *slot) { return reinterpret_cast<double *>(slot + 64); } // [2][nTiles][4]
 LD_DEV double *loud_ws_part(unsigned char *slot, const LoudPlan &lp) { return loud_ws_states(slot) + (i64)8 * lp.nTiles; } // [2][nTiles][kHops]
-LD_DEV double *loud_ws_e(unsigned char *slot, const LoudPlan &lp) { return loud_ws_part(slot, lp) + (i64)2 * lp.nTiles * lp.kHops; } // [2][H]
+LD_DEV double *loud_ws_e(unsigned char *slot, const LoudPlan &lp) { return reinterpret_cast<double *>(slot + loud_ws_e_offset(lp)); } // [2][H]
 
 constexpr int kLoudRow = kLoudChunk + 1; // words of a staged row: lane l's row starts at bank (l * 65) % 32 = l % 32
 struct LoudLds
@@ -585,6 +585,42 @@ __global__ __launch_bounds__(64) void loud_gain_kernel(const unsigned char *work
     report[o].lufs_c = own.lufsC, report[o].gain = g, report[o].lufs = own.L;
 }
 
+// the same with the ceiling by true peak (DMX_LOUD_TRUE_PEAK): the gain rule reads tp[o], the true peaks
+// the true-peak kernel formed, where it read the sample peaks; peaks[o] still becomes the gained SAMPLE peak g * P
+__global__ __launch_bounds__(64) void loud_gain_tp_kernel(const unsigned char *work, i64 slotBytes, int nOut, unsigned *peaks, const unsigned *tp,
+                                                          int mode, int targetC, float maxPeak, const float *T, float *gains,
+                                                          dmx_loudness_result *report)
+{
+    __shared__ float sP[PcmGains::kMaxOut], sTP[PcmGains::kMaxOut];
+    const int o = threadIdx.x;
+    if (o < nOut)
+        sP[o] = __uint_as_float(peaks[o]), sTP[o] = __uint_as_float(tp[o]);
+    __syncthreads();
+    if (o > nOut)
+        return;
+    const LoudRes own = *reinterpret_cast<const LoudRes *>(work + (i64)o * slotBytes);
+    if (o == nOut)
+    {
+        report[o].lufs_c = own.lufsC, report[o].gain = 0.0f, report[o].lufs = own.L;
+        return;
+    }
+    float g = 1.0f;
+    if (mode == DMX_LOUD_MIXTURE)
+    {
+        float P = 0.0f;
+        for (int q = 0; q < nOut; ++q)
+            P = sTP[q] > P ? sTP[q] : P;
+        const LoudRes mix = *reinterpret_cast<const LoudRes *>(work + (i64)nOut * slotBytes);
+        g = loud_gain_of(mix.lufsC, targetC, P, maxPeak, T);
+    }
+    else if (mode == DMX_LOUD_EACH)
+        g = loud_gain_of(own.lufsC, targetC, sTP[o], maxPeak, T);
+    gains[o] = g;
+    if (mode != DMX_LOUD_MEASURE)
+        peaks[o] = __float_as_uint(g * sP[o]);
+    report[o].lufs_c = own.lufsC, report[o].gain = g, report[o].lufs = own.L;
+}
+
 void launch_loud_measure(const RemixPiece &pc, const PcmGains &G, const LoudPlan &lp, unsigned char *work, int slot0, double *eOut,
                          void *resOut, hipStream_t s, hipEvent_t *marks)
 {
@@ -610,6 +646,12 @@ void launch_loud_gain(const unsigned char *work, i64 slotBytes, int nOut, unsign
                       const float *table, float *gains, void *report, hipStream_t s)
 {
     hipLaunchKernelGGL(loud_gain_kernel, dim3(1), dim3(64), 0, s, work, slotBytes, nOut, peaks, mode, targetC, maxPeak, table, gains,
+                       (dmx_loudness_result *)report);
+}
+void launch_loud_gain_tp(const unsigned char *work, i64 slotBytes, int nOut, unsigned *peaks, const unsigned *tp, int mode, int targetC,
+                         float maxPeak, const float *table, float *gains, void *report, hipStream_t s)
+{
+    hipLaunchKernelGGL(loud_gain_tp_kernel, dim3(1), dim3(64), 0, s, work, slotBytes, nOut, peaks, tp, mode, targetC, maxPeak, table, gains,
                        (dmx_loudness_result *)report);
 }
 #else

@@ -27,6 +27,13 @@ void loud_coefficients(int rate, double coef[10]);
 int loud_plan(int rate, int64_t n, LoudPlan *p);
 // bytes of workspace per measured signal of n frames, whatever the rate: a multiple of 16: 64 + 256 per tile + 16 per 400 frames, about n / 10
 int64_t loud_workspace_bytes(int64_t n);
+// where a signal's hop energies e[2][H] start in its workspace slot, in bytes: behind the result (64), the tiles' states
+// [2][nTiles][4] and the tiles' hop partials [2][nTiles][kHops], all binary64 (the meters launch reads them: meters.hip)
+#ifdef __HIP__
+__host__ __device__
+#endif
+    inline int64_t
+    loud_ws_e_offset(const LoudPlan &p) { return 64 + 8 * ((int64_t)8 * p.nTiles + (int64_t)2 * p.nTiles * p.kHops); }
 // T[i] = (float)pow(10, (i - 6000) / 2000.0), kLoudGainSteps entries
 void loud_gain_table(float *T);
 } // namespace dmx

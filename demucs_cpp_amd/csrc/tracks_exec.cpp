@@ -136,7 +136,16 @@ struct PcmOut // the output spec of a call, checked (dmx_pcm_check_spec)
     const dmx_loudness_spec *loud;
     dmx_loudness_result *report;
     const float *loudTable;
-    bool gained() const { return loud && loud->mode != DMX_LOUD_MEASURE; }
+    // dmx_tracks_infer_meters: the meters report, n_out + 1 entries per track; else NULL
+    dmx_meters_result *meters;
+    int loudMode() const { return loud->mode & ~DMX_LOUD_TRUE_PEAK; }
+    bool byTruePeak() const { return loud && (loud->mode & DMX_LOUD_TRUE_PEAK) != 0; }
+    bool truePeaks() const { return byTruePeak() || meters; } // the slot holds true peaks and a meters report behind the loudness report
+    bool gained() const { return loud && loudMode() != DMX_LOUD_MEASURE; }
+    // in a slot's loudness buffer behind the n_out + 1 workspaces of a track of n frames: 64 bytes of gains, the loudness report,
+    // and with truePeaks() 64 bytes of true peaks and the meters report
+    i64 loudTail(i64 n) const { return (i64)(nOut + 1) * loud_workspace_bytes(n); }
+    i64 tpOffset(i64 n) const { return loudTail(n) + 64 + (i64)sizeof(dmx_loudness_result) * (nOut + 1); }
 };
 // One call of the track path. shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches
 // track_ola_kernel and N >= 2 track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
@@ -220,7 +229,9 @@ static int tracks_prepare(TracksRun &r)
             DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(omax * pcm->frameBytes) / 4)));
             DMXCHK(dmx_ensure_buf(sl.peaks, 8));
             if (pcm->loud)
-                DMXCHK(dmx_ensure_buf(sl.loud, ((pcm->nOut + 1) * (loud_workspace_bytes(omax) + (i64)sizeof(dmx_loudness_result)) + 64) / 4));
+                DMXCHK(dmx_ensure_buf(sl.loud, ((pcm->nOut + 1) * (loud_workspace_bytes(omax) + (i64)sizeof(dmx_loudness_result)) + 64 +
+                                                (pcm->truePeaks() ? 64 + (i64)sizeof(dmx_meters_result) * (pcm->nOut + 1) : 0)) /
+                                                   4));
             if (pcm->flacBits)
             {
                 DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, omax) / 4)));
@@ -461,8 +472,29 @@ static int tracks_output_stage(TracksRun &r, int k)
             float *gains = (float *)(work + (i64)(pcm->nOut + 1) * slotBytes);
             launch_loud_measure(pp, *pcm->remix, lp, work, 0, nullptr, nullptr, s);
             launch_loud_measure(pp, M, lp, work, pcm->nOut, nullptr, nullptr, s);
-            launch_loud_gain(work, slotBytes, pcm->nOut, pp.peaks, pcm->loud->mode, (int)rintf(100.0f * pcm->loud->target_lufs),
-                             pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
+            unsigned *tp = (unsigned *)(work + pcm->tpOffset(lp.n));
+            if (pcm->truePeaks())
+            {
+                // the true peaks of the whole track's outputs, and for a meters report the mixture's and the hop meters
+                TpFilter f;
+                tp_filter(r.rates ? r.rates[g.t] : 44100, &f);
+                HIPCHK(hipMemsetAsync(tp, 0, 64, s));
+                RemixPiece tq = pp;
+                tq.peaks = tp;
+                launch_true_peak(&tq, 1, *pcm->remix, f, s);
+                if (pcm->meters)
+                {
+                    tq.peaks = tp + pcm->nOut;
+                    launch_true_peak(&tq, 1, M, f, s);
+                    launch_meters(work, 0, pcm->nOut + 1, lp, tp, tp + 16, s);
+                }
+            }
+            if (pcm->byTruePeak())
+                launch_loud_gain_tp(work, slotBytes, pcm->nOut, pp.peaks, tp, pcm->loudMode(), (int)rintf(100.0f * pcm->loud->target_lufs),
+                                    pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
+            else
+                launch_loud_gain(work, slotBytes, pcm->nOut, pp.peaks, pcm->loudMode(), (int)rintf(100.0f * pcm->loud->target_lufs),
+                                 pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
             LoudPiece lq;
             static_cast<RemixPiece &>(lq) = pp;
             lq.gains = gains;
@@ -543,6 +575,9 @@ static int tracks_copy_pcm(TracksRun &r, int k, const PcmRange &g)
         HIPCHK(hipMemcpyAsync(pcm->report + (size_t)g.t * (pcm->nOut + 1),
                               (const unsigned char *)sl.loud.p + (size_t)((pcm->nOut + 1) * loud_workspace_bytes(n) + 64),
                               sizeof(dmx_loudness_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
+    if (last && pcm->meters) // and the meters report
+        HIPCHK(hipMemcpyAsync(pcm->meters + (size_t)g.t * (pcm->nOut + 1), (const unsigned char *)sl.loud.p + (size_t)(pcm->tpOffset(n) + 64),
+                              sizeof(dmx_meters_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
     return DMX_OK;
 }
 
@@ -807,6 +842,7 @@ struct TracksCall
     const int *rates;            // dmx_tracks_infer_rates: n[t] frames at rates[t] (checked: check_tracks_rates); else NULL, all 44100
     const dmx_loudness_spec *loud; // dmx_tracks_infer_loud: the loudness stage behind a remix spec, and its report; else NULL
     dmx_loudness_result *report;
+    dmx_meters_result *meters;   // dmx_tracks_infer_meters: the meters report, or NULL
     const dmx_flac_info *flacIn; // dmx_tracks_infer_from_flac: audio[t] is a file image, described here; else NULL
     const int64_t *fileBytes;
     int64_t *trackStatus;
@@ -1144,7 +1180,7 @@ static int tracks_call(const TracksCall &a)
         pcm.flacBits = pcm.spec.encoding == DMX_PCM_S16 ? 16 : 24, pcm.flacRate = a.flacRate, pcm.sizes = a.flacSizes, pcm.rates = a.rates;
     if (remix && a.loud)
     {
-        pcm.loud = a.loud, pcm.report = a.report;
+        pcm.loud = a.loud, pcm.report = a.report, pcm.meters = a.meters;
         if (!a.c->dLoudTable) // once per context: built on the host, uploaded, freed with the context
         {
             std::vector<float> h((size_t)kLoudGainSteps);
@@ -1248,7 +1284,7 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
                             int n_tracks, const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
                             const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes, float *peaks,
                             int64_t *track_status, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud = nullptr,
-                            dmx_loudness_result *report = nullptr)
+                            dmx_loudness_result *report = nullptr, dmx_meters_result *meters = nullptr)
 {
     if (n_tracks < 1)
         return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
@@ -1284,7 +1320,7 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
     a.n_tracks = n_tracks, a.audio = reinterpret_cast<const float *const *>(files), a.n = ns.data();
     a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.flacIn = infos.data(), a.fileBytes = file_bytes, a.trackStatus = track_status;
-    a.loud = loud, a.report = report;
+    a.loud = loud, a.report = report, a.meters = meters;
     a.out = out, a.peaks = peaks, a.layout = DMX_LAYOUT_EIGEN, a.progress = progress, a.user = user;
     DMXCHK(tracks_call(a)); // (track_status: -1 until the track's own arrives)
     for (int t = 0; t < n_tracks; ++t)
@@ -1335,13 +1371,12 @@ extern "C" int dmx_tracks_infer_rates(dmx_ctx *c, const dmx_model *const *models
 }
 
 // dmx_tracks_infer_rates / dmx_tracks_infer_from_flac_rates behind the loudness stage
-extern "C" int dmx_tracks_infer_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
-                                     const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
-                                     const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
-                                     float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
-                                     dmx_loudness_result *report)
+static int tracks_infer_loud(const char *fn, dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                             const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                             const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes, float *peaks,
+                             int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud, dmx_loudness_result *report,
+                             dmx_meters_result *meters)
 {
-    const char *fn = "dmx_tracks_infer_loud";
     if (n_tracks < 1)
         return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
     if (!spec)
@@ -1356,8 +1391,41 @@ extern "C" int dmx_tracks_infer_loud(dmx_ctx *c, const dmx_model *const *models,
     a.flacRate = 44100, a.flacSizes = sizes, a.rates = rates;
     a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
-    a.loud = loud, a.report = report;
+    a.loud = loud, a.report = report, a.meters = meters;
     return tracks_call(a);
+}
+
+extern "C" int dmx_tracks_infer_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                     const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                                     const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                     float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                                     dmx_loudness_result *report)
+{
+    return tracks_infer_loud("dmx_tracks_infer_loud", c, models, n_models, weights, n_tracks, audio, n, rates, n_shifts, overlap, shift_offsets,
+                             spec, flac_out, out, sizes, peaks, layout, progress, user, loud, report, nullptr);
+}
+
+// the two calls behind the loudness stage with a meters report
+extern "C" int dmx_tracks_infer_meters(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                       const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                                       const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                       float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                                       dmx_loudness_result *report, dmx_meters_result *meters)
+{
+    return tracks_infer_loud("dmx_tracks_infer_meters", c, models, n_models, weights, n_tracks, audio, n, rates, n_shifts, overlap,
+                             shift_offsets, spec, flac_out, out, sizes, peaks, layout, progress, user, loud, report, meters);
+}
+
+extern "C" int dmx_tracks_infer_from_flac_meters(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                                 const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                                 const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                                 int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
+                                                 const dmx_loudness_spec *loud, dmx_loudness_result *report, dmx_meters_result *meters)
+{
+    const char *fn = "dmx_tracks_infer_from_flac_meters";
+    DMXCHK(dmx_loud_check_spec(fn, loud, 44100, -1));
+    return tracks_from_flac(fn, true, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts, overlap, shift_offsets, spec,
+                            flac_out, out, sizes, peaks, track_status, progress, user, loud, report, meters);
 }
 
 extern "C" int dmx_tracks_infer_from_flac_loud(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,

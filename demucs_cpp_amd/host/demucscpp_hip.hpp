@@ -433,6 +433,9 @@ inline PcmOutputs demucs_inference_batch_pcm(const demucs_model &model, const st
     return detail::batch_call_pcm("demucs_inference_batch_pcm", model, tracks, cb, opts, out_opts, peaks);
 }
 
+// what remix_options::loudness.meters receives (dmx_tracks_infer_meters): per track the library's n_out + 1 entries, the outputs
+// and then the mixture
+using MetersReport = std::vector<std::vector<dmx_meters_result>>;
 // Outputs mixed on the GPU from the stems and the original mixture (dmx_tracks_infer_remix; include/demucs_hip.h
 // dmx_remix_spec): output o is names[o], its row of gains is gains[o * (nb_sources + 1) ...], the last entry of a row the
 // gain of the mixture. The defaults are demucs's: 16 bit, rescale.
@@ -453,11 +456,16 @@ struct remix_options
     // DMX_LOUD_MEASURE | DMX_LOUD_MIXTURE | DMX_LOUD_EACH, the target in LUFS, the ceiling of the sample peak as a linear value
     // (-1 dBFS; infinity: none). The overloads that take these options have a last argument, LoudnessReport *loudness_report,
     // that receives the report. With flac and without rates the files are taken to be at 44100 Hz (sample_rate must say so).
+    // true_peak: max_peak is a ceiling of the TRUE peak (DMX_LOUD_TRUE_PEAK), -1 dBTP. meters: null, or
+    // where the call leaves its meters report (dmx_tracks_infer_meters / dmx_tracks_infer_from_flac_meters): per track n_out + 1
+    // entries, the outputs and then the mixture, each with its true peak, loudness range and momentary and short-term maxima.
     struct loudness_options
     {
         bool on = false;
         int mode = DMX_LOUD_MIXTURE;
         float target_lufs = -14.0f, max_peak = 0.8912509f;
+        bool true_peak = false;
+        MetersReport *meters = nullptr;
     };
     loudness_options loudness;
 };
@@ -611,6 +619,20 @@ inline void loudness_report_cut(const remix_options &ro, const std::vector<dmx_l
         (*report)[t].assign(rep.begin() + (std::ptrdiff_t)(t * (size_t)(n_out + 1)),
                                         rep.begin() + (std::ptrdiff_t)((t + 1) * (size_t)(n_out + 1)));
 }
+// the loudness spec of a call, and the flat meters report it fills (empty: none asked for), cut per track behind the call
+inline dmx_loudness_spec loudness_spec_of(const remix_options &ro)
+{
+    return dmx_loudness_spec{ro.loudness.mode | (ro.loudness.true_peak ? DMX_LOUD_TRUE_PEAK : 0), ro.loudness.target_lufs, ro.loudness.max_peak};
+}
+inline void meters_report_cut(const remix_options &ro, const std::vector<dmx_meters_result> &rep, size_t T, int n_out)
+{
+    if (!ro.loudness.on || !ro.loudness.meters)
+        return;
+    ro.loudness.meters->assign(T, std::vector<dmx_meters_result>());
+    for (size_t t = 0; t < T; ++t)
+        (*ro.loudness.meters)[t].assign(rep.begin() + (std::ptrdiff_t)(t * (size_t)(n_out + 1)),
+                                        rep.begin() + (std::ptrdiff_t)((t + 1) * (size_t)(n_out + 1)));
+}
 // one call of dmx_tracks_infer_remix, or for ro.flac dmx_tracks_infer_flac; shifts as the caller's path lays them out.
 // rates: track t is at (*rates)[t] Hz (dmx_tracks_infer_rates)
 inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector<StereoMatrix> &tracks, const std::vector<int> &shifts,
@@ -640,13 +662,15 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
     }
     CbThunk th{&cb};
     FlacLevelGuard level(g.c, ro.flac ? ro.flac_level : 0);
-    const dmx_loudness_spec lspec{ro.loudness.mode, ro.loudness.target_lufs, ro.loudness.max_peak};
+    const dmx_loudness_spec lspec = loudness_spec_of(ro);
     std::vector<dmx_loudness_result> rep(ro.loudness.on ? (size_t)T * (size_t)(spec.n_out + 1) : 0);
+    std::vector<dmx_meters_result> mrep(ro.loudness.on && ro.loudness.meters ? rep.size() : 0);
     auto run = [&]() -> int {
-        if (ro.loudness.on)
-            return dmx_tracks_infer_loud(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates ? rates->data() : nullptr, opts.shifts,
-                                         opts.overlap, shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr,
-                                         y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th, &lspec, rep.data());
+        if (ro.loudness.on) // (a null meters report: dmx_tracks_infer_loud)
+            return dmx_tracks_infer_meters(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates ? rates->data() : nullptr, opts.shifts,
+                                           opts.overlap, shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr,
+                                           y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th, &lspec, rep.data(),
+                                           mrep.empty() ? nullptr : mrep.data());
         if (rates)
             return dmx_tracks_infer_rates(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(),
                                           &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr, y.pk.data(), DMX_LAYOUT_EIGEN,
@@ -660,6 +684,7 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
     if (!g.c || !level.ok || run() != DMX_OK)
         die(who);
     loudness_report_cut(ro, rep, tracks.size(), spec.n_out, report);
+    meters_report_cut(ro, mrep, tracks.size(), spec.n_out);
     return y.cut(peaks, ro.flac);
 }
 // the same on tracks given as the images of .flac files (dmx_tracks_infer_from_flac): ro.flac chooses the output form.
@@ -697,19 +722,21 @@ inline PcmOutputs flac_files_call(const char *who, const Target &g, const std::v
     std::vector<int64_t> status(2 * T, 0);
     CbThunk th{&cb};
     FlacLevelGuard level(g.c, ro.flac ? ro.flac_level : 0);
-    const dmx_loudness_spec lspec{ro.loudness.mode, ro.loudness.target_lufs, ro.loudness.max_peak};
+    const dmx_loudness_spec lspec = loudness_spec_of(ro);
     std::vector<dmx_loudness_result> rep(ro.loudness.on ? T * (size_t)(spec.n_out + 1) : 0);
+    std::vector<dmx_meters_result> mrep(ro.loudness.on && ro.loudness.meters ? rep.size() : 0);
     if (!g.c || !level.ok ||
         (ro.loudness.on
-             ? dmx_tracks_infer_from_flac_loud(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap, shifts.data(),
-                                               &spec, ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(), status.data(), progress_thunk,
-                                               &th, &lspec, rep.data())
+             ? dmx_tracks_infer_from_flac_meters(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap,
+                                                 shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(), status.data(),
+                                                 progress_thunk, &th, &lspec, rep.data(), mrep.empty() ? nullptr : mrep.data())
              : (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(),
                                                                                        opts.shifts, opts.overlap, shifts.data(), &spec,
                                                                                        ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(),
                                                                                        status.data(), progress_thunk, &th)) != DMX_OK)
         die(who);
     loudness_report_cut(ro, rep, T, spec.n_out, report);
+    meters_report_cut(ro, mrep, T, spec.n_out);
     if (frames)
         *frames = n;
     return y.cut(peaks, ro.flac);

@@ -349,8 +349,9 @@ extern "C"
      * balance and none exceeds the ceiling; DMX_LOUD_EACH every output its own lufs_c, P and g.
      * The report of a track holds n_out + 1 entries, the outputs and then the mixture (whose gain is 0); lufs is the
      * unquantised L, NaN when unmeasurable. A mono file is measured as the dual-mono stereo it becomes.
-     * Out of scope: true peak (4x oversampled), loudness range, momentary and short-term meters (the hop energies are
-     * returned: a caller can derive them), ReplayGain tags (FLAC tags stay out of scope), the engine. */
+     * True peak (4x oversampled), loudness range and the momentary and short-term maxima are the meters below, and
+     * DMX_LOUD_TRUE_PEAK turns the ceiling into a true-peak one. Out of scope: ReplayGain tags (FLAC tags stay out of
+     * scope), the engine. */
 #define DMX_LOUD_MEASURE 0
 #define DMX_LOUD_MIXTURE 1
 #define DMX_LOUD_EACH 2
@@ -408,6 +409,66 @@ extern "C"
      * n_out + 1 entries */
     int dmx_loud_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
                         const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report);
+
+    /* ---- meters (csrc/meters.hip; DESIGN.md section 2.15, restated in tests/meters_spec.py; no reference counterpart): what
+     * EBU R 128 asks for beside integrated loudness, of the same signals, on the GPU.
+     * True peak TP: the oversampling factor F is 4 for rate < 96000, 2 for rate < 192000, else 1 (TP is then the sample
+     * peak). Taps h[k] = (float)(sinc((k - 6 F) / F) * 0.5 * (1 - cos(2 pi k / (12 F)))), k = 0 .. 12 F, sinc(t) =
+     * sin(pi t) / (pi t), sinc(0) = 1, made on the host in binary64 and rounded once. Phase 0 is the sample itself; phase p
+     * (0 < p < F) at frame i is y_p[i] = sum over j = 0 .. 11 of h[p + F j] * x[i + 6 - j], x = 0 outside [0, n), in fp32,
+     * every product rounded and then added with a rounding of its own, j ascending. TP is the largest |y_p[i]| over the
+     * channels, 0 <= i < n and the phases; NaN is ignored, nothing left gives 0. TP >= the sample peak, and TP is exact:
+     * the same bits as the specification, whatever the cut into tiles and pieces.
+     * Hop meters, from the hop energies e[c][j] and the hop h of the section on loudness, H = n / h: momentary blocks are
+     * that section's l[b]; short-term blocks S[b] = -0.691 + 10 log10((sum over hops b .. b + 29, channel 0 then channel 1
+     * of a hop, of e) / (30 h)), b in [0, H - 29). max_momentary_c = max rint(100 l[b]), max_short_c = max rint(100 S[b]),
+     * int32 in hundredths of a LU; DMX_LUFS_UNMEASURABLE without a block or with a block that is not finite; a block of
+     * zero energy is -inf and never wins (all zero: unmeasurable).
+     * Loudness range after EBU Tech 3342 over an integer histogram: s_c[b] = min(rint(100 S[b]), 2000); the values above
+     * -7000 are counted in bins k = s_c + 7000; mean = sum cnt[k] 10^((k - 7000) / 1000) / sum cnt[k] in binary64, k
+     * ascending; r_c = floor(100 * 10 log10(mean)) - 2000; the bins with k - 7000 > r_c remain, m values; lra_c =
+     * v[((m - 1) 95 + 50) / 100] - v[((m - 1) 10 + 50) / 100] in their ascending order. Unmeasurable: H < 30, a block that
+     * is not finite, no bin past a gate.
+     * DMX_LOUD_TRUE_PEAK, OR-ed into dmx_loudness_spec.mode, makes max_peak a true-peak ceiling: the gain rule above reads
+     * TP where it reads P (under DMX_LOUD_MIXTURE the largest TP of the outputs). The peaks a call returns stay the gained
+     * SAMPLE peaks g * P (what DMX_CLIP_RESCALE divides by). Without the flag every byte and every launch is unchanged. */
+#define DMX_LOUD_TRUE_PEAK 0x100
+    typedef struct dmx_meters_result
+    {
+        float true_peak;         /* TP of the signal as measured, linear; the TP that leaves is the fp32 product gain * true_peak */
+        int32_t lra_c;           /* hundredths of a LU, or DMX_LUFS_UNMEASURABLE */
+        int32_t max_momentary_c; /* idem */
+        int32_t max_short_c;     /* idem */
+    } dmx_meters_result;
+    /* the factor F for `rate` and the 12 F + 1 taps (taps may be NULL). Pure host function; DMX_ERR_ARG for rate < 1. */
+    int dmx_true_peak_filter(int rate, int *factor, float *taps);
+    /* bytes of device workspace for ONE metered signal on top of dmx_loudness_workspace_bytes(n): 64 (the histogram lives in
+     * LDS). Pure host function; -1 for n < 1. */
+    int64_t dmx_meters_workspace_bytes(int64_t n);
+    /* dmx_loudness_device plus the two new stages, asynchronous on `stream`: d_meters is one entry ON THE DEVICE; d_work:
+     * 16-byte aligned, dmx_loudness_workspace_bytes(n) + dmx_meters_workspace_bytes(n) bytes. d_result receives what
+     * dmx_loudness_device writes, from the same launches. */
+    int dmx_meters_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                          double *d_e, void *d_work, void *stream, dmx_meters_result *d_meters);
+    /* measurement (tools/meters_bench.py): the true-peak launch and the peak kernel on the same signal, synchronised, their
+     * times between HIP events in ms[0] and ms[1], and the meters launch behind a measurement in ms[2]; d_work as above */
+    int dmx_meters_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, void *d_work, void *stream,
+                                float *ms);
+    /* the same on host buffers */
+    int dmx_meters(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e,
+                   dmx_meters_result *meters);
+    /* dmx_loud_encode_device plus a meters report of n_out + 1 entries on the device, the outputs and then the mixture, each
+     * signal as measured (in front of the gain). Honours DMX_LOUD_TRUE_PEAK, as dmx_loud_encode_device does (which then
+     * enqueues the true-peak launch over the outputs and the gain launch's true-peak form, and nothing else new). d_work:
+     * (n_out + 1) x (dmx_loudness_workspace_bytes(n) + dmx_meters_workspace_bytes(n)) + 64 bytes. */
+    int dmx_loud_encode_meters_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                      const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                                      float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream,
+                                      dmx_meters_result *d_meters);
+    /* host buffers, as dmx_loud_encode; meters NULL or n_out + 1 entries */
+    int dmx_loud_encode_meters(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                               const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
+                               dmx_meters_result *meters);
 
     /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
      * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
@@ -563,6 +624,21 @@ extern "C"
                                         const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
                                         int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
                                         const dmx_loudness_spec *loud, dmx_loudness_result *report);
+    /* the two calls above with a meters report (the section on meters, above): meters is NULL (the calls above) or n_tracks x
+     * (n_out + 1) entries, per track the outputs and then the mixture, each signal as measured (in front of the gain). They
+     * honour DMX_LOUD_TRUE_PEAK, as the calls above do: those then enqueue per track the true-peak launch over its outputs and
+     * the gain launch's true-peak form, and nothing else new. Device memory: with the flag or a meters report, per track slot
+     * another 64 + 16 (n_out + 1) bytes. */
+    int dmx_tracks_infer_meters(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                                const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                                dmx_loudness_result *report, dmx_meters_result *meters);
+    int dmx_tracks_infer_from_flac_meters(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                          const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                          const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                          int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
+                                          const dmx_loudness_spec *loud, dmx_loudness_result *report, dmx_meters_result *meters);
     /* pure host function: the outputs of a conversion of n_in -> n_out = dmx_resample_length frames that no longer change once
      * the inputs [0, n_in_final) are final: n_out when n_in_final == n_in, else min(n_out, max(0, ceil((n_in_final L - c) / M))),
      * the first output whose newest tap (c + k M) div L reaches n_in_final. -1: invalid argument */
