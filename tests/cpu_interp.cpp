@@ -18,6 +18,7 @@
 #include "../demucs_cpp_amd/csrc/gemm_select.cpp"
 #include "../demucs_cpp_amd/csrc/plan_describe.h"
 
+#include <atomic>
 #include <complex>
 #include <type_traits>
 
@@ -48,6 +49,95 @@ inline P &operator*=(P &a, P b) { return a = a * b; }
 inline P &operator/=(P &a, P b) { return a = a / b; }
 inline bool operator<(P a, P b) { return a.v < b.v; }
 
+// ---- the census (interp_census): how many evaluations of the LAST precise step fell into each value class. Filled by the P
+// overloads of gelu / sigmoidf / tanh_ and by the statistics code in its precise form only; the fp32 arithmetic never looks at it.
+// Classes (tests/op_reference.py CENSUS names them in this order):
+//   GELU by z = v / sqrt 2, the argument of the device's dmx_erff (kernels.h): sign x {|z| < 0.92, 0.92 <= |z| < 4, |z| >= 4}, and
+//     |z| within 2^-10 relative of 0.92, below and above;
+//   sigmoid by its argument v: sign x {|v| < 2^-10, < 1, < 9, < 17, < 89, >= 89};  tanh: sign x {|v| < 2^-10, < 1, < 9, >= 9};
+//   statistics, per row / group / record formed: all, zero (every element 0), constant (variance 0, mean != 0), |mean| / sigma
+//     {< 1, < 64, >= 64}, sigma {< 2^-10, < 2^6, >= 2^6}, "clamped" (the one-pass form q - n mean^2 the device evaluates in double
+//     is negative), spike (one element carries more than half of the squared deviations);
+//   LSTM cell states with |c| >= 8; the largest number of non-zero operand elements in one GEMM row (a maximum, not a count).
+enum
+{
+    CEN_GELU = 0,
+    CEN_SIG = 8,
+    CEN_TANH = 20,
+    CEN_STAT = 28,
+    CEN_C8 = 39,
+    CEN_KNZ = 40,
+    CEN_N = 41
+};
+enum
+{
+    ST_ALL,
+    ST_ZERO,
+    ST_CONST,
+    ST_R0,
+    ST_R8,
+    ST_R512,
+    ST_SIG_SMALL,
+    ST_SIG_MID,
+    ST_SIG_BIG,
+    ST_CLAMPED,
+    ST_SPIKE
+};
+std::atomic<long long> g_census[CEN_N];
+inline void census(int k) { g_census[k].fetch_add(1, std::memory_order_relaxed); }
+inline void census_gelu(double v)
+{
+    const double z = std::fabs(v) * std::sqrt(0.5), e = 0.92 * std::ldexp(1.0, -10);
+    census(CEN_GELU + (v < 0 ? 0 : 3) + (z < 0.92 ? 0 : z < 4.0 ? 1 : 2));
+    if (z >= 0.92 - e && z < 0.92)
+        census(CEN_GELU + 6);
+    if (z >= 0.92 && z <= 0.92 + e)
+        census(CEN_GELU + 7);
+}
+inline void census_sig(double v)
+{
+    const double a = std::fabs(v);
+    census(CEN_SIG + (v < 0 ? 0 : 6) + (a < std::ldexp(1.0, -10) ? 0 : a < 1 ? 1 : a < 9 ? 2 : a < 17 ? 3 : a < 89 ? 4 : 5));
+}
+inline void census_tanh(double v)
+{
+    const double a = std::fabs(v);
+    census(CEN_TANH + (v < 0 ? 0 : 4) + (a < std::ldexp(1.0, -10) ? 0 : a < 1 ? 1 : a < 9 ? 2 : 3));
+}
+// one set of statistics: n values of sum s and sum of squares q (plain doubles, as the device's one-pass form has them), the
+// variance the reference formed, the largest squared deviation (< 0: not known, the elements were not seen)
+inline void census_stat(double n, double s, double q, double var, double maxdev2)
+{
+    const double mean = s / n, sd = std::sqrt(var);
+    census(CEN_STAT + ST_ALL);
+    if (q == 0)
+        census(CEN_STAT + ST_ZERO);
+    else if (var == 0)
+        census(CEN_STAT + ST_CONST);
+    else
+    {
+        const double ratio = std::fabs(mean) / sd;
+        census(CEN_STAT + (ratio < 1 ? ST_R0 : ratio < 64 ? ST_R8 : ST_R512));
+        census(CEN_STAT + (sd < std::ldexp(1.0, -10) ? ST_SIG_SMALL : sd < 64 ? ST_SIG_MID : ST_SIG_BIG));
+        if (maxdev2 > 0.5 * var * (n - 1.0))
+            census(CEN_STAT + ST_SPIKE);
+    }
+    if (q - n * mean * mean < 0)
+        census(CEN_STAT + ST_CLAMPED);
+}
+// ... of rows x cols fp32 elements (leading dimension ld) whose variance the reference formed as var
+inline void census_elements(const float *x, int cols, int rows, i64 ld, double n, double var)
+{
+    double s = 0, q = 0, far = 0;
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c)
+            s += (double)x[r * ld + c], q += (double)x[r * ld + c] * (double)x[r * ld + c];
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c)
+            far = std::max(far, ((double)x[r * ld + c] - s / n) * ((double)x[r * ld + c] - s / n));
+    census_stat(n, s, q, var, far);
+}
+
 inline float gelu(float v) { return 0.5f * v * (1.0f + std::erf(v / std::sqrt(2.0f))); }
 inline float sigmoidf(float v) { return 1.0f / (1.0f + std::exp(-v)); }
 inline float exp_(float v) { return std::exp(v); }
@@ -59,11 +149,13 @@ inline double max_(double a, double b) { return std::max(a, b); }
 // |gelu'| <= 1.13, |sigmoid'| <= 1 / 4, |tanh'| <= 1, exp' = exp, sqrt' = 1 / (2 sqrt)
 inline P gelu(P x)
 {
+    census_gelu(x.v);
     const double f = 0.5 * x.v * (1.0 + std::erf(x.v / std::sqrt(2.0)));
     return P(f, std::fabs(f) + 1.13 * x.m);
 }
 inline P sigmoidf(P x)
 {
+    census_sig(x.v);
     const double f = 1.0 / (1.0 + std::exp(-x.v));
     return P(f, f + 0.25 * x.m);
 }
@@ -76,6 +168,7 @@ inline P exp_(P x)
 // |v| - the "< 2e-7 absolute" its header states. The magnitude therefore carries 1, not |tanh v|)
 inline P tanh_(P x)
 {
+    census_tanh(x.v);
     const double f = std::tanh(x.v);
     return P(f, 1.0 + x.m);
 }
@@ -84,6 +177,8 @@ inline P sqrt_(P x)
     const double f = std::sqrt(x.v);
     return P(f, f + (f > 0 ? 0.5 * x.m / f : 0.0));
 }
+inline double num(double x) { return x; }
+inline double num(P x) { return x.v; }
 inline P fma_(P a, P b, P c) { return a * b + c; }
 inline P max_(P a, P b) { return a.v < b.v ? b : a; }
 
@@ -129,6 +224,7 @@ inline void inner_stats(double s, double q, double cnt, float eps, float &mean, 
 inline void inner_stats(P s, P q, double cnt, float eps, P &mean, P &rstd)
 {
     const double m = s.v / cnt, var = std::max((q.v - cnt * m * m) / (cnt - 1.0), 0.0);
+    census_stat(cnt, s.v, q.v, var, -1.0);
     mean = P(m), rstd = P(1.0 / std::sqrt(var + (double)eps));
 }
 
@@ -251,6 +347,7 @@ struct Interp
             int grp = bb * g.G0 + (g.G0 > 1 ? p0 : 0);
             std::vector<T> arow((size_t)g.K);
             double rowmax = 0;
+            long long knz = 0;
             for (int k = 0; k < g.K; ++k)
             {
                 int s1 = k / g.seg0, off = k % g.seg0;
@@ -273,6 +370,13 @@ struct Interp
                 }
                 arow[(size_t)k] = a;
                 rowmax = std::max(rowmax, std::fabs(Tr<T>::val(a)));
+                knz += Tr<T>::val(a) != 0;
+            }
+            if (precise)
+            {
+                long long seen = g_census[CEN_KNZ].load(std::memory_order_relaxed);
+                while (seen < knz && !g_census[CEN_KNZ].compare_exchange_weak(seen, knz, std::memory_order_relaxed))
+                    ;
             }
             std::vector<T> v((size_t)g.N);
             for (int n = 0; n < g.N; ++n)
@@ -422,6 +526,8 @@ struct Interp
                 Wd var = (sq - s.count * mean * mean) / (s.count - 1.0);
                 if (var < Wd(0))
                     var = 0;
+                if (!std::is_same<T, float>::value)
+                    census_stat(s.count, num(sum), num(sq), num(var), -1.0);
                 const i64 o = s.out + ((i64)b * G + gi) * 4;
                 st(o, Tr<T>::rf(mean));
                 st(o + 2, Tr<T>::rf(sqrt_(var)));
@@ -495,6 +601,8 @@ struct Interp
             for (int c = 0; c < l.D; ++c)
                 ss += (Tr<T>::wd(x[c]) - mean) * (Tr<T>::wd(x[c]) - mean);
             T rstd = Tr<T>::rf(1.0 / sqrt_(ss / (l.D - 1) + (double)l.eps));
+            if (!std::is_same<T, float>::value)
+                census_elements(x, l.D, 1, l.D, l.D, num(ss) / (l.D - 1));
             std::vector<T> tmp((size_t)l.D);
             for (int c = 0; c < l.D; ++c)
             {
@@ -782,6 +890,8 @@ struct Interp
                         ss += d * d;
                     }
                 const Wd var = ss / (cnt - 1.0);
+                if (!std::is_same<T, float>::value)
+                    census_elements(&A[(size_t)(g.x + (i64)b * g.rows * g.C + gi * gs)], gs, g.rows, g.C, cnt, num(var));
                 const i64 o = g.out + ((i64)b * g.G + gi) * 4;
                 st(o, mean);
                 st(o + 1, Tr<T>::rf(1.0 / sqrt_(var + (double)g.eps)));
@@ -847,6 +957,8 @@ struct Interp
                         const T ig = sigmoidf(gt[0]), fg = sigmoidf(gt[1]), gg = tanh_(gt[2]), og = sigmoidf(gt[3]);
                         const T cn = fg * c[(size_t)j] + ig * gg;
                         c[(size_t)j] = Tr<T>::rebase(cn);
+                        if (!std::is_same<T, float>::value && std::fabs(num(Tr<T>::wd(cn))) >= 8.0)
+                            census(CEN_C8);
                         hn[(size_t)j] = og * tanh_(cn);
                     }
                     // The magnitude of an output is that of ITS step from the state before it, the state taken as numbers of their
@@ -1320,6 +1432,92 @@ extern "C" int interp_set_attention(void *h, int i, const float *q, const float 
     return 0;
 }
 
+// the census of the last precise step (one per process: handles are stepped one at a time): CEN_N counters, see the enum
+extern "C" int interp_census(long long *out, int cap)
+{
+    for (int k = 0; k < CEN_N && k < cap; ++k)
+        out[k] = g_census[k].load();
+    return CEN_N;
+}
+
+// Where op i reads each of its operands, by role, for tests that write crafted values there (tests/value_cases.py): words
+// role=off:rows:cols:ld:batchStride:batches (floats; element (b, r, c) at off + b batchStride + r ld + c). Roles: act (the
+// activation operand), prostats / epistats (the records {mean, scale, std, 0} a prologue / epilogue reads), res (the residual),
+// rowstat (the partials of an OP_STATS_REDUCE), xproj (OP_LSTM), rowtensor (the in-place tensor of an OP_DCONV_ROW). Words W.name
+// give a range of the packed weights in the same form; conv= a GEMM's gather geometry, rows= {rowOff, rowsOut, G} of an OP_GN_ACT,
+// reduce= {G, count, mode, eps bits} of an OP_STATS_REDUCE
+extern "C" int interp_operands(void *h, int i, char *buf, int cap)
+{
+    Interp *it = (Interp *)h;
+    if (i < 0 || i >= (int)it->pl.ops.size())
+        return -1;
+    const Op &op = it->pl.ops[(size_t)i];
+    std::string all;
+    auto word = [&](const char *role, i64 off, i64 rows, i64 cols, i64 ld, i64 batch, i64 nb) {
+        char t[192];
+        snprintf(t, sizeof(t), "%s=%lld:%lld:%lld:%lld:%lld:%lld ", role, (long long)off, (long long)rows, (long long)cols, (long long)ld, (long long)batch, (long long)nb);
+        all += t;
+    };
+    switch (op.kind)
+    {
+    case OP_IGEMM:
+    {
+        const IGemm &g = op.g;
+        const int G = g.G0 > 1 ? g.G0 : 1;
+        const int Nout = g.epi == EPI_GLU || g.epi == EPI_GN_GLU_SCALE_RES ? g.N / 2 : g.N;
+        word("act", g.x, (i64)g.L1 * g.L0, g.Cin, g.Cin, g.xBatchStride, g.B);
+        {
+            // how output row (b, p1, p0) gathers its K = S1 seg0 operand elements: k = s1 seg0 + o is element o of the run starting
+            // at (p0 stride0 - pad0) Cin of input row in1 = p1 stride1 + s1 dil1 - pad1 (plan.h IGemm)
+            char t[256];
+            snprintf(t, sizeof(t), "conv=%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d:%d ", g.L1, g.L0, g.Cin, g.K / g.seg0, g.stride1, g.dil1, g.pad1, g.seg0, g.stride0, g.pad0,
+                     g.P1, g.P0, G);
+            all += t;
+        }
+        if (g.pro == PRO_AFFINE)
+            word("prostats", g.proStats, g.B, 4, 4, 0, 1);
+        if (g.pro == PRO_GN_GELU)
+            word("prostats", g.proStats, (i64)g.B * G, 4, 4, 0, 1);
+        if (g.epi == EPI_GN_GLU_SCALE_RES)
+            word("epistats", g.epiStats, (i64)g.B * G, 4, 4, 0, 1);
+        if (g.res >= 0 && g.epi != EPI_TRCONV)
+            word("res", g.res, (i64)g.P1 * g.P0, Nout, g.ldy, g.yBatchStride, g.B);
+        break;
+    }
+    case OP_STATS_REDUCE:
+    {
+        unsigned eb;
+        std::memcpy(&eb, &op.sr.eps, 4);
+        word("rowstat", op.sr.rowstat, op.sr.R, (i64)op.sr.NB * 2, (i64)op.sr.NB * 2, (i64)op.sr.R * op.sr.NB * 2, op.sr.B);
+        word("reduce", op.sr.G0 > 1 ? op.sr.G0 : 1, (i64)op.sr.count, op.sr.mode, eb, 0, 1);
+        break;
+    }
+    case OP_LAYERNORM: word("act", op.ln.x, op.ln.rows, op.ln.D, op.ln.D, 0, 1); break;
+    case OP_GROUP_STATS: word("act", op.gs.x, op.gs.rows, op.gs.C, op.gs.C, (i64)op.gs.rows * op.gs.C, op.gs.B); break;
+    case OP_GN_ACT:
+        word("act", op.ga.x, op.ga.rowsIn, op.ga.C, op.ga.C, (i64)op.ga.rowsIn * op.ga.C, op.ga.B);
+        word("epistats", op.ga.stats, (i64)op.ga.B * op.ga.G, 4, 4, 0, 1);
+        word("W.w", op.ga.w_w, 1, op.ga.C, op.ga.C, 0, 1), word("W.b", op.ga.b_w, 1, op.ga.C, op.ga.C, 0, 1);
+        if (op.ga.scale_w >= 0)
+            word("W.scale", op.ga.scale_w, 1, op.ga.mode == 2 ? op.ga.C / 2 : op.ga.C, op.ga.C, 0, 1);
+        word("rows", op.ga.rowOff, op.ga.rowsOut, op.ga.G, 0, 0, 1);
+        if (op.ga.res >= 0)
+        {
+            const int Co = op.ga.mode == 2 ? op.ga.C / 2 : op.ga.C;
+            word("res", op.ga.res, op.ga.rowsOut, Co, Co, (i64)op.ga.rowsOut * Co, op.ga.B);
+        }
+        break;
+    case OP_LSTM:
+        word("W.whh", op.lstm.whh_w, 2, 4 * (i64)op.lstm.H * op.lstm.H, 4 * (i64)op.lstm.H * op.lstm.H, 0, 1);
+        word("xproj", op.lstm.xproj, op.lstm.T, 8 * (i64)op.lstm.H, 8 * (i64)op.lstm.H, (i64)op.lstm.T * 8 * op.lstm.H, op.lstm.B); break;
+    case OP_DCONV_ROW:
+        word("rowtensor", op.dr.x, (i64)op.dr.T * op.dr.F, op.dr.C, op.dr.C, (i64)op.dr.T * op.dr.F * op.dr.C, op.dr.B);
+        break;
+    default: break;
+    }
+    return copy_out(all, buf, cap);
+}
+
 extern "C" int interp_step(void *h, int i, int mode)
 {
     Interp *it = (Interp *)h;
@@ -1331,6 +1529,8 @@ extern "C" int interp_step(void *h, int i, int mode)
     it->hterms = (mode & 2) != 0, it->chained = (mode & 4) != 0;
     if (mode & 1)
     {
+        for (auto &c : g_census)
+            c.store(0);
         if (it->R.size() != n)
             it->R.assign(n, 0.0), it->S.assign(n, 0.f);
         it->run_op<P>(it->pl.ops[(size_t)i]);

@@ -32,6 +32,14 @@ CASES = {
 }
 
 
+# the value classes of cpu_interp.cpp's census, in its order
+CENSUS = (["gelu-lo", "gelu-mid", "gelu-hi", "gelu+lo", "gelu+mid", "gelu+hi", "gelu_edge_below", "gelu_edge_above"]
+          + [f"sig{s}{c}" for s in "-+" for c in ("<2^-10", "<1", "<9", "<17", "<89", ">=89")]
+          + [f"tanh{s}{c}" for s in "-+" for c in ("<2^-10", "<1", "<9", ">=9")]
+          + ["stat_all", "stat_zero", "stat_const", "stat_ratio<1", "stat_ratio<64", "stat_ratio>=64", "stat_sigma<2^-10", "stat_sigma<2^6",
+             "stat_sigma>=2^6", "stat_clamped", "stat_spike", "lstm_c>=8", "gemm_row_nonzeros_max"])
+
+
 def lib():
     srcs = [os.path.join(ROOT, "tests", "cpu_interp.cpp")] + [os.path.join(ROOT, "demucs_cpp_amd", "csrc", f)
                                                               for f in ("plan.cpp", "plan.h", "model_pack.cpp", "gemm_select.cpp", "plan_describe.h")]
@@ -61,6 +69,8 @@ def lib():
     L.interp_weights.argtypes = [vp]
     L.interp_weight_floats.restype = i64
     L.interp_weight_floats.argtypes = [vp]
+    L.interp_operands.argtypes = [vp, ci, ctypes.c_char_p, ci]
+    L.interp_census.argtypes = [vp, ci]
     return L
 
 
@@ -109,6 +119,30 @@ class Ref:
         [B][Tk][H hs]; decay [B][T][16] for a LocalState op"""
         arr = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (q, k, v, decay)]
         assert self.L.interp_set_attention(self.h, i, *[None if a is None else a.ctypes.data for a in arr]) == 0
+
+    def operands(self, i):
+        """where op i reads its operands, by role (cpu_interp.cpp interp_operands): role -> dict(off, rows, cols, ld, batch, nb); the
+        words conv, rows and reduce -> their tuple of integers"""
+        buf = ctypes.create_string_buffer(1024)
+        assert self.L.interp_operands(self.h, i, buf, 1024) >= 0
+        out = {}
+        for word in buf.value.decode().split():
+            role, v = word.split("=")
+            v = tuple(int(t) for t in v.split(":"))
+            out[role] = v if role in ("conv", "rows", "reduce") else dict(zip(("off", "rows", "cols", "ld", "batch", "nb"), v))
+        return out
+
+    def view(self, geo):
+        """the arena elements of one operand (operands()) as an array [nb][rows][cols] that writes through"""
+        return np.lib.stride_tricks.as_strided(self.A[geo["off"]:], (geo["nb"], geo["rows"], geo["cols"]), (4 * geo["batch"], 4 * geo["ld"], 4))
+
+    def census(self):
+        """evaluations per value class of the last precise step (cpu_interp.cpp interp_census): name -> count"""
+        n = self.L.interp_census(None, 0)
+        arr = (ctypes.c_longlong * n)()
+        self.L.interp_census(arr, n)
+        assert n == len(CENSUS)
+        return dict(zip(CENSUS, (int(v) for v in arr)))
 
     def planes(self):
         """(r, s) of the last precise step's K / V operand planes, indexed like the elements of plane 0; None if it wrote none"""
@@ -282,10 +316,16 @@ def expected_arena(n_floats, canary, consts_u32, reads, read_values):
     return e
 
 
-def check_op(op, mode, arena_u32, before_u32, snap):
+def effective(op, K_eff):
+    """the op with the number of non-zero terms its operands really put into each sum in place of K (None: the op as it is): the
+    same line of bound_c's table, for operands crafted so that a sum has K_eff terms"""
+    return op if K_eff is None else dict(op, K=K_eff)
+
+
+def check_op(op, mode, arena_u32, before_u32, snap, K_eff=None):
     """arena_u32: what the implementation left of before_u32 (expected_arena). Raises OpMismatch; returns (worst ratio, the ratios
     of every compared element)"""
-    name, c = op["name"], bound_c(op, mode)
+    name, c = op["name"], bound_c(effective(op, K_eff), mode)
     g = arena_u32.view(np.float32)
     # ---- values
     q = ratios(g[snap["idx"]], snap["r"], snap["s"])
@@ -332,7 +372,7 @@ def canary_arena(ref, op_reads, canary):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# The GPU side of the op-level tests (tests/test_gpu_op_parity.py, tests/test_gpu_attention_crafted.py): a context beside the
+# The GPU side of the op-level tests (tests/test_gpu_op_parity.py, tests/test_gpu_attention_crafted.py, tests/test_gpu_value_cases.py): a context beside the
 # interpreter handle of the same plan, and the check of one launch.
 DEVICE_ERROR = []  # the first error the library reported from the device: after it no op-level test launches anything
 
@@ -409,7 +449,7 @@ def written_bits(fetch, op, snap):
     return np.concatenate(out)
 
 
-def check_launch(pair, i, j, op, reads, values, snap):
+def check_launch(pair, i, j, op, reads, values, snap, K_eff=None):
     """Op j of the context's plan (the reference stepped ops i .. j: a fused pair, else i == j) launched alone on `values` in its
     read ranges: from canary A (value bound and containment: check_op), again with canary B in everything it does not declare to
     read (the same bits), and the RMS rule against the interpreter's fp32 arithmetic on the same inputs. Raises OpMismatch;
@@ -420,7 +460,7 @@ def check_launch(pair, i, j, op, reads, values, snap):
     ctx.run_op(B, j)
     got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
     before = expected_arena(pair.ctx_floats, CANARY_A, pair.consts_u32, reads, values)
-    worst, q = check_op(op, mode, got, before, snap)
+    worst, q = check_op(op, mode, got, before, snap, K_eff)
     bits_a = written_bits(lambda lo, hi: got[lo:hi], op, snap)
     # ---- the same launch with canary B in everything it does not declare to read
     pair.prepare(CANARY_B, reads, values)
@@ -431,7 +471,7 @@ def check_launch(pair, i, j, op, reads, values, snap):
         raise OpMismatch(f"{op['name']}: the result depends on arena contents outside its declared read ranges (first at written element {k})")
     rms_g = rms(q)
     rms_f = None
-    if rms_rule_applies(op, mode):
+    if rms_rule_applies(effective(op, K_eff), mode):
         # the interpreter's fp32 arithmetic on the same inputs (restored: the precise step may have worked in place)
         after = [ref.A[lo:hi].copy() for lo, hi in reads]
         for (lo, hi), v in zip(reads, values):
@@ -446,11 +486,50 @@ def check_launch(pair, i, j, op, reads, values, snap):
     return worst, rms_g, rms_f, bits_a
 
 
-def rejects(op, mode, got, before, snap, rms_fp32):
+def run_variants(pair, j, op, reads, values, snap, bits_plan, variants, launched, K_eff=None):
+    """GEMM j on every tile cfg of its shape (dmx_debug_op_cfgs) under lin_mode 0 / 1 / 3: each distinct (cfg, family, wnf) meets the
+    op's bound; results of one arithmetic are bit-identical whatever the tile or family (plan.h kTileCfgs: siblings keep the column
+    decomposition; gemm_select.h: all families of one arithmetic give the same bits) - row-statistics partials included, among
+    tiles of one column block width. The direct kernels (cfg 8, chosen by shape alone, with a k order of their own: dgemm.hip) are
+    outside that claim: where the plan's kernel is one, the tile variants are compared with each other. K_eff: as check_op takes it
+    (crafted operands: a sibling of another arithmetic than the plan's is held to ITS line of the table at that K)."""
+    ctx, B = pair.ctx, pair.B
+    DIRECT = 8
+    seen = {(op["cfg"], op["family"], op["wnf"])}
+    claim = lambda o: (o["arith"], o["BN"] if op["stat"] else 0)
+    bases = {} if op["cfg"] == DIRECT else {claim(op): (bits_plan, op)}
+    for cfg in ctx.op_cfgs(B, j):
+        for lin_mode in (0, 1, 3):
+            pair.prepare(CANARY_A, reads, values)
+            ch = ctx.run_op_as(B, j, cfg, lin_mode)
+            if ch is None:
+                variants["refused"].add((cfg, op["pro"], op["epi"]))
+                continue
+            key = (ch["cfg"], ch["family"], ch["wnf"])
+            launched.append((ch["cfg"], ch["family"], ch["label"]))
+            if key in seen:
+                continue
+            seen.add(key)
+            vop = dict(op, **ch)
+            got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
+            before = expected_arena(pair.ctx_floats, CANARY_A, pair.consts_u32, reads, values)
+            try:
+                check_op(vop, pair.mode, got, before, snap, K_eff)
+            except OpMismatch as e:
+                raise OpMismatch(f"as cfg {ch['cfg']} family {ch['family']} wnf {ch['wnf']} ({ch['label']}): {e}")
+            bits = written_bits(lambda lo, hi: got[lo:hi], op, snap)
+            base_bits, base = bases.setdefault(claim(vop), (bits.copy(), vop))
+            if not np.array_equal(bits, base_bits):
+                raise OpMismatch(f"{op['name']}: cfg {ch['cfg']} family {ch['family']} ({ch['label']}) differs in bits from "
+                                   f"cfg {base['cfg']} family {base['family']} ({base['label']}) in the same arithmetic")
+            variants["checked"] += 1
+
+
+def rejects(op, mode, got, before, snap, rms_fp32, K_eff=None):
     """the GPU tests' verdict on what an implementation left in the arena (value bound and containment: check_op; the RMS rule against
     rms_fp32, the interpreter's fp32 figure): True = rejected. The teeth tests apply it to seeded mistakes"""
     try:
-        _, q = check_op(op, mode, got, before, snap)
+        _, q = check_op(op, mode, got, before, snap, K_eff)
     except OpMismatch:
         return True
-    return rms_rule_applies(op, mode) and not rms_rule_ok(rms(q), rms_fp32)
+    return rms_rule_applies(effective(op, K_eff), mode) and not rms_rule_ok(rms(q), rms_fp32)

@@ -59,6 +59,30 @@ int main(int argc, char **argv)
         for (i64 k = 0; k < interp_arena_floats(h); ++k)
             if (mask[k])
                 sum += r[k] + s[k], ++writes;
+        // interp_census: the counters of the precise step; interp_operands: every role's range lies inside the arena (W. words:
+        // inside the packed weights) - the crafted-operand tests write through them
+        long long cen[64];
+        const int nc = interp_census(cen, 64);
+        if (nc <= 0 || nc > 64)
+            return 12;
+        for (int k = 0; k < nc; ++k)
+            sum += (double)cen[k] * 1e-9;
+        char roles[1024];
+        if (interp_operands(h, i, roles, sizeof(roles)) < 0)
+            return 13;
+        for (char *w = strtok(roles, " "); w; w = strtok(nullptr, " "))
+        {
+            long long f[6];
+            char role[32];
+            if (sscanf(w, "%31[^=]=%lld:%lld:%lld:%lld:%lld:%lld", role, f, f + 1, f + 2, f + 3, f + 4, f + 5) != 7)
+                continue; // (conv= has more fields and names no range)
+            if (!strcmp(role, "rows") || !strcmp(role, "reduce"))
+                continue;
+            const i64 last = f[0] + (f[5] - 1) * f[4] + (f[1] - 1) * f[3] + f[2];
+            const i64 cap = strncmp(role, "W.", 2) ? interp_arena_floats(h) : interp_weight_floats(h);
+            if (f[0] < 0 || last > cap)
+                return 14;
+        }
         double *pr;
         float *ps;
         const i64 np = interp_planes(h, &pr, &ps);

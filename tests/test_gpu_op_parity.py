@@ -22,10 +22,19 @@ raises and the test ends there: nothing more is launched.
 The variant sweep runs every GEMM of two cases on every tile of its shape's chain (dmx_debug_run_op_as), see
 test_every_tile_and_family_*.
 
-What the sweep does NOT reach: its inputs are what a 0.1 randn mixture produces through synthetic weights, and on those the
-attention kernels raise their deferred running maximum on the first key tile only, run in 64-query workgroups only, and see
-LocalState with a handful of tokens in one masked tile. tests/test_gpu_attention_crafted.py covers those paths on operands
-written straight into the attention ops' read ranges (Pair, check_launch and written_bits are shared: op_reference.py).
+What the sweep does NOT reach, and what does: its inputs are what a 0.1 randn mixture produces through synthetic weights. On those
+the attention kernels raise their deferred running maximum on the first key tile only, run in 64-query workgroups only, and see
+LocalState with a handful of tokens in one masked tile: tests/test_gpu_attention_crafted.py covers those paths on operands
+written straight into the attention ops' read ranges. And on those no GELU argument passes the clamp of dmx_erff (8 % are in its
+upper range at all), no sigmoid or LSTM gate saturates, no normalised row has a mean beyond half its deviation or is constant,
+zero or spiked, no variance is clamped, no fp16-term row is zero, denormal or huge, and the LSTM runs 7 and 4 steps:
+tests/test_gpu_value_cases.py covers those classes, one op per kernel instance, on operands written by role into the ops' read
+ranges (tests/value_cases.py; the census of the reference says which classes a launch evaluated). Pair, check_launch,
+written_bits and run_variants are shared by the three tests: op_reference.py. Still unreached by any of them
+(value_cases.UNREACHABLE): the variance clamp of group_stats as a DECIDED class (a constant group of elements is launched, but
+whether its one-pass variance rounds below zero is up to the order of a double summation; only fp32 partials, the statistics
+reduction's input, can be made to decide it), and the row-resident DConv's activations beyond their middle ranges (a GroupNorm
+in front of each bounds them).
 
 DMX_OP_PARITY_RECORD=<dir> writes the per-op figures (profiles/op_parity_*.txt are such records)."""
 import os
@@ -61,7 +70,7 @@ def check_launch(pair, i, j, op, reads, values, snap, rows, launched, variants):
         loose = float(np.nanmedian(snap["s"] / np.abs(snap["r"]))) if snap["idx"].size else 0.0  # how far s is above |r|: the bound's slack
     rows.append((op["name"], op.get("label"), op.get("K", 0), R.bound_c(op, pair.mode), worst, rms_g, rms_f, loose))
     if variants is not None and op["kind"] == R.OP_IGEMM:
-        run_variants(pair, j, op, reads, values, snap, bits_a, variants, launched)
+        R.run_variants(pair, j, op, reads, values, snap, bits_a, variants, launched)
 
 
 def sweep(pair, variants=None):
@@ -106,44 +115,6 @@ def sweep_ops(pair, variants):
             failures.append(str(e))
         i = j + 1
     return rows, launched, failures
-
-
-def run_variants(pair, j, op, reads, values, snap, bits_plan, variants, launched):
-    """GEMM j on every tile cfg of its shape (dmx_debug_op_cfgs) under lin_mode 0 / 1 / 3: each distinct (cfg, family, wnf) meets the
-    op's bound; results of one arithmetic are bit-identical whatever the tile or family (plan.h kTileCfgs: siblings keep the column
-    decomposition; gemm_select.h: all families of one arithmetic give the same bits) - row-statistics partials included, among
-    tiles of one column block width. The direct kernels (cfg 8, chosen by shape alone, with a k order of their own: dgemm.hip) are
-    outside that claim: where the plan's kernel is one, the tile variants are compared with each other."""
-    ctx, B = pair.ctx, pair.B
-    DIRECT = 8
-    seen = {(op["cfg"], op["family"], op["wnf"])}
-    claim = lambda o: (o["arith"], o["BN"] if op["stat"] else 0)
-    bases = {} if op["cfg"] == DIRECT else {claim(op): (bits_plan, op)}
-    for cfg in ctx.op_cfgs(B, j):
-        for lin_mode in (0, 1, 3):
-            pair.prepare(R.CANARY_A, reads, values)
-            ch = ctx.run_op_as(B, j, cfg, lin_mode)
-            if ch is None:
-                variants["refused"].add((cfg, op["pro"], op["epi"]))
-                continue
-            key = (ch["cfg"], ch["family"], ch["wnf"])
-            launched.append((ch["cfg"], ch["family"], ch["label"]))
-            if key in seen:
-                continue
-            seen.add(key)
-            vop = dict(op, **ch)
-            got = ctx.arena_read(0, pair.ctx_floats, pair.buf).view(np.uint32)
-            before = R.expected_arena(pair.ctx_floats, R.CANARY_A, pair.consts_u32, reads, values)
-            try:
-                R.check_op(vop, pair.mode, got, before, snap)
-            except R.OpMismatch as e:
-                raise R.OpMismatch(f"as cfg {ch['cfg']} family {ch['family']} wnf {ch['wnf']} ({ch['label']}): {e}")
-            bits = written_bits(lambda lo, hi: got[lo:hi], op, snap)
-            base_bits, base = bases.setdefault(claim(vop), (bits.copy(), vop))
-            if not np.array_equal(bits, base_bits):
-                raise R.OpMismatch(f"{op['name']}: cfg {ch['cfg']} family {ch['family']} ({ch['label']}) differs in bits from "
-                                   f"cfg {base['cfg']} family {base['family']} ({base['label']}) in the same arithmetic")
-            variants["checked"] += 1
 
 
 def record(pair, rows, failures, tag=""):
