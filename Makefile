@@ -14,14 +14,16 @@ NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
 QUIET := 2> >(grep -v "packed-fp32-ops' is not a recognized feature" >&2)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(NOPK)
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
-OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o loudness.o meters.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
+OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o loudness.o meters.o limiter.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_host loudness_host meters_host harness micro
+all: $(LIB) cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_host loudness_host meters_host limiter_host harness micro
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@ $(QUIET)
-build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
+# the limiter's products are separate roundings: contraction off for the whole file
+build/limiter.o: HIPFLAGS += -ffp-contract=off
+build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@ $(QUIET)
 
@@ -100,11 +102,22 @@ loudness_host_asan:
 # way. Contraction is off, as it is in the kernel: every product and every sum is rounded once
 METERS_OUT ?= tests/_build/meters_host_main
 meters_host: $(METERS_OUT)
-$(METERS_OUT): tests/meters_host_main.cpp $(CSRC)/meters.hip $(CSRC)/meters_plan.h $(CSRC)/loudness.hip $(CSRC)/loudness_plan.h
+$(METERS_OUT): tests/meters_host_main.cpp $(CSRC)/meters.hip $(CSRC)/meters_plan.h $(CSRC)/tp_phases.h $(CSRC)/loudness.hip $(CSRC)/loudness_plan.h
 	@mkdir -p $(dir $@)
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(CXXFLAGS_METERS) -o $@ tests/meters_host_main.cpp
 meters_host_asan:
 	$(MAKE) meters_host METERS_OUT=tests/_build/meters_host_main_asan CXXFLAGS_METERS="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
+
+# the limiter's kernel text (csrc/limiter.hip) as host code in a stand-alone CPU program (tests/test_limiter_cpu.py): the level,
+# the required reduction, the tiles' aggregates, the carry sweeps and the two scans, thread by thread; the true-peak phases
+# through meters.hip compiled the same way. Contraction is off, as it is in the kernel
+LIMITER_OUT ?= tests/_build/limiter_host_main
+limiter_host: $(LIMITER_OUT)
+$(LIMITER_OUT): tests/limiter_host_main.cpp $(CSRC)/limiter.hip $(CSRC)/limiter_plan.h $(CSRC)/meters.hip $(CSRC)/meters_plan.h $(CSRC)/tp_phases.h
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -Wno-unused-function -ffp-contract=off $(CXXFLAGS_LIMITER) -o $@ tests/limiter_host_main.cpp
+limiter_host_asan:
+	$(MAKE) limiter_host LIMITER_OUT=tests/_build/limiter_host_main_asan CXXFLAGS_LIMITER="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 
 # GPU test harnesses of the C++ shim (re-entrancy; Eigen-typed overloads against tests/eigen_stub, which is NOT Eigen)
 harness: tests/_build/shim_harness tests/_build/shim_harness_eigen tests/_build/wav_harness tests/_build/pcm_wav_harness tests/_build/remix_parse_harness
@@ -144,19 +157,19 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan loudness_host loudness_host_asan meters_host meters_host_asan harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan loudness_host loudness_host_asan meters_host meters_host_asan limiter_host limiter_host_asan harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:
 	@mkdir -p build/$(NAME)
-	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc tracks attention attention_split resample pcm loudness meters flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
+	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc tracks attention attention_split resample pcm loudness meters limiter flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) $$([ $$f = limiter ] && echo -ffp-contract=off) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
 	for f in api exec tracks_exec codec_api debug_api engine plan model_pack tracks_plan gemm_select; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -x hip -c $(CSRC)/$$f.cpp -o build/$(NAME)/$$f.o & done; wait
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o demucs_cpp_amd/lib/libdemucs_hip_$(NAME).so build/$(NAME)/*.o
 # one file rebuilt with other flags, the rest of the product's objects unchanged:
 #   make variant1 NAME=fftnoslp FILE=fft FLAGS=-fno-slp-vectorize   ->  demucs_cpp_amd/lib/libdemucs_hip_fftnoslp.so
 variant1: $(LIB)
 	@mkdir -p build/$(NAME)
-	$(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(CSRC)/$(FILE).hip -o build/$(NAME)/$(FILE).o $(QUIET)
+	$(HIPCC) $(HIPFLAGS) $(if $(filter limiter,$(FILE)),-ffp-contract=off) $(FLAGS) -c $(CSRC)/$(FILE).hip -o build/$(NAME)/$(FILE).o $(QUIET)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o demucs_cpp_amd/lib/libdemucs_hip_$(NAME).so $(filter-out build/$(FILE).o,$(OBJS)) build/$(NAME)/$(FILE).o -ldl -lpthread
 # the same with the one file taken from another path (generated, instrumented copies: tools/micro/dconv_row_timing.py)
 variant1src: $(LIB)

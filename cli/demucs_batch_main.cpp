@@ -3,6 +3,7 @@
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
 //                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]
+//                         [--limit] [--limit-attack MS] [--limit-release MS]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
 // (at 44.1 kHz, or with DMX_RESAMPLE=1 at any rate) the files go to the GPU as they are and are decoded there
@@ -42,6 +43,11 @@
 //                            every output its own gain (DMX_LOUD_EACH); --loudness only measures. --max-peak DB (default -1) is the
 //                            ceiling of the sample peak: the gain is reduced where it would be exceeded. A line per output is
 //                            printed: "vocals: -14.23 LUFS, gain +3.10 dB". They combine with every option above.
+//   --limit                  the look-ahead peak limiter holds --max-peak (DMX_LOUD_LIMIT): with --loudnorm or
+//                            --loudnorm-each the ceiling no longer lowers the gain, so the target is reached; on its own (or as
+//                            --clip-mode limit) it limits the stems as they are (DMX_LOUD_UNITY). --limit-attack MS (default 5) and
+//                            --limit-release MS (default 100) are the times in which the reduction moves by 10 dB, 0.1 .. 10000. The
+//                            report gains a part such as "limited 1234 frames, max -5.21 dB, peak -1.00 dBFS".
 //   --true-peak              with --loudnorm or --loudnorm-each: --max-peak is a ceiling of the TRUE peak (4x oversampled below
 //                            96 kHz; DMX_LOUD_TRUE_PEAK), -1 dBTP by default. --meters (with any of the three flags above) extends
 //                            the line: "vocals: -14.23 LUFS, gain +3.10 dB, TP -1.00 dBTP, LRA 6.20 LU, max M -9.80, max S -11.42",
@@ -78,6 +84,7 @@ using namespace demucscpp;
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
               << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]"
+              << " [--limit] [--limit-attack MS] [--limit-release MS] (--clip-mode limit: --limit without loudnorm)"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
 }
@@ -126,6 +133,9 @@ int main(int argc, const char **argv)
     LoudnessReport loud_report; // filled by the remix calls when a loudness flag is given
     bool true_peak = false, with_meters = false;
     MetersReport meters_report; // filled as well with --meters
+    bool limit = false, clip_limit = false, limit_times = false;
+    float limit_attack = DMX_LIMIT_ATTACK_MS, limit_release = DMX_LIMIT_RELEASE_MS;
+    LimitReport limit_report; // filled as well with --limit
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -147,6 +157,12 @@ int main(int argc, const char **argv)
         if (opt == "--true-peak" || opt == "--meters") // no value; what they need is checked behind the loop
         {
             (opt == "--meters" ? with_meters : true_peak) = true;
+            --a;
+            continue;
+        }
+        if (opt == "--limit") // no value; what it goes with is checked behind the loop
+        {
+            limit = true;
             --a;
             continue;
         }
@@ -172,6 +188,16 @@ int main(int argc, const char **argv)
                 usage(argv[0]);
             else
                 loud_target = v, loud_mode = opt == "--loudnorm" ? DMX_LOUD_MIXTURE : DMX_LOUD_EACH, with_out_opts = true;
+            continue;
+        }
+        if (opt == "--limit-attack" || opt == "--limit-release")
+        {
+            char *end = nullptr;
+            errno = 0;
+            const float v = std::strtof(val.c_str(), &end);
+            if (val.empty() || errno || *end || !std::isfinite(v) || v < 0.1f || v > 10000.0f) // the library's range
+                usage(argv[0]);
+            (opt == "--limit-attack" ? limit_attack : limit_release) = v, limit_times = true;
             continue;
         }
         if (opt == "--two-stems")
@@ -217,6 +243,8 @@ int main(int argc, const char **argv)
                 out_opts.clip = DMX_CLIP_CLAMP;
             else if (val == "none")
                 out_opts.clip = DMX_CLIP_NONE;
+            else if (val == "limit") // --limit without loudnorm: nothing is left to clip under the ceiling
+                out_opts.clip = DMX_CLIP_NONE, limit = clip_limit = true;
             else
                 usage(argv[0]);
             with_out_opts = true;
@@ -285,9 +313,23 @@ int main(int argc, const char **argv)
         std::cerr << "--remix and --two-stems exclude each other" << std::endl;
         usage(argv[0]);
     }
-    if (true_peak && loud_mode != DMX_LOUD_MIXTURE && loud_mode != DMX_LOUD_EACH)
+    if (limit_times && !limit)
     {
-        std::cerr << "--true-peak needs --loudnorm or --loudnorm-each: it is the ceiling of their gain" << std::endl;
+        std::cerr << "--limit-attack and --limit-release need --limit" << std::endl;
+        usage(argv[0]);
+    }
+    if (limit && (loud_mode == DMX_LOUD_MEASURE || (clip_limit && loud_mode >= 0)))
+    {
+        std::cerr << (clip_limit ? "--clip-mode limit is --limit without loudnorm: give --limit beside --loudnorm or --loudnorm-each"
+                                 : "--limit changes the samples and --loudness only measures: they exclude each other")
+                  << std::endl;
+        usage(argv[0]);
+    }
+    if (limit && loud_mode < 0) // the limiter alone under --max-peak
+        loud_mode = DMX_LOUD_UNITY, with_out_opts = true;
+    if (true_peak && !limit && loud_mode != DMX_LOUD_MIXTURE && loud_mode != DMX_LOUD_EACH)
+    {
+        std::cerr << "--true-peak needs --loudnorm, --loudnorm-each or --limit: it is the ceiling of their gain" << std::endl;
         usage(argv[0]);
     }
     if (with_meters && loud_mode < 0)
@@ -340,6 +382,8 @@ int main(int argc, const char **argv)
             remix.loudness.max_peak = (float)std::pow(10.0, (double)max_peak_db / 20.0);
             remix.loudness.true_peak = true_peak;
             remix.loudness.meters = with_meters ? &meters_report : nullptr;
+            remix.loudness.limit = limit, remix.loudness.attack_ms = limit_attack, remix.loudness.release_ms = limit_release;
+            remix.loudness.limit_report = limit ? &limit_report : nullptr;
         }
         if (!with_out_opts) // FLAC inputs or other rates without an output option: the float32 stems, through unit gains
             remix.encoding = DMX_PCM_F32, remix.clip = DMX_CLIP_NONE;
@@ -588,10 +632,24 @@ int main(int argc, const char **argv)
                     snprintf(line, sizeof line, ", gain %+.2f dB", 20.0 * std::log10((double)lr.gain));
                     std::cout << line;
                 }
+                if (limit && o < po.size()) // what the limiter did to the output (1 unit = 1 / 65536 octave)
+                {
+                    const dmx_limit_result &li = limit_report[(size_t)f][o];
+                    char peak[48];
+                    if (li.peak_out > 0.0f)
+                        snprintf(peak, sizeof peak, "%.2f dBFS", 20.0 * std::log10((double)li.peak_out));
+                    else
+                        snprintf(peak, sizeof peak, "-inf dBFS");
+                    snprintf(line, sizeof line, ", limited %lld frames, max %.2f dB, peak %s", (long long)li.limited_frames,
+                             -(double)li.max_reduction / 65536.0 * 20.0 * std::log10(2.0), peak);
+                    std::cout << line;
+                }
                 if (with_meters) // the true peak of what leaves (the mixture: as measured), then the meters of the signal as measured
                 {
                     const dmx_meters_result &mr = meters_report[(size_t)f][o];
-                    const float tp = o < po.size() ? lr.gain * mr.true_peak : mr.true_peak;
+                    // (behind the limiter with --true-peak: the true peak of the limited output)
+                    const float tp = o < po.size() ? (limit && true_peak ? limit_report[(size_t)f][o].true_peak_out : lr.gain * mr.true_peak)
+                                                   : mr.true_peak;
                     auto lu = [](int32_t c, const char *unit) {
                         char b[48];
                         if (c == DMX_LUFS_UNMEASURABLE)

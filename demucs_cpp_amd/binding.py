@@ -49,6 +49,8 @@ EXPORTS = [
     "dmx_tracks_infer_loud", "dmx_tracks_infer_from_flac_loud",
     "dmx_true_peak_filter", "dmx_meters_workspace_bytes", "dmx_meters_device", "dmx_meters_device_timed", "dmx_meters",
     "dmx_loud_encode_meters_device", "dmx_loud_encode_meters", "dmx_tracks_infer_meters", "dmx_tracks_infer_from_flac_meters",
+    "dmx_limiter_tables", "dmx_limiter_slopes", "dmx_limiter_workspace_bytes", "dmx_limit_device", "dmx_limit_device_timed", "dmx_limit",
+    "dmx_limiter_check", "dmx_loud_encode_limit_device", "dmx_loud_encode_limit", "dmx_tracks_infer_limit", "dmx_tracks_infer_from_flac_limit",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -202,6 +204,18 @@ def lib():
         L.dmx_loud_encode_meters.argtypes = L.dmx_loud_encode.argtypes + [vp]
         L.dmx_tracks_infer_meters.argtypes = L.dmx_tracks_infer_loud.argtypes + [vp]
         L.dmx_tracks_infer_from_flac_meters.argtypes = L.dmx_tracks_infer_from_flac_loud.argtypes + [vp]
+        L.dmx_limiter_tables.argtypes = [vp, vp, vp]
+        L.dmx_limiter_slopes.argtypes = [ci, ctypes.c_double, ctypes.c_double, vp, vp]
+        L.dmx_limiter_workspace_bytes.argtypes = [i64]
+        L.dmx_limiter_workspace_bytes.restype = i64
+        L.dmx_limit_device.argtypes = [ci, vp, i64, i64, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
+        L.dmx_limit_device_timed.argtypes = L.dmx_limit_device.argtypes + [vp]
+        L.dmx_limit.argtypes = [ci, vp, i64, ci, ci, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
+        L.dmx_limiter_check.argtypes = [vp, vp, ci]
+        L.dmx_loud_encode_limit_device.argtypes = L.dmx_loud_encode_meters_device.argtypes + [vp, vp]
+        L.dmx_loud_encode_limit.argtypes = L.dmx_loud_encode_meters.argtypes + [vp, vp]
+        L.dmx_tracks_infer_limit.argtypes = L.dmx_tracks_infer_meters.argtypes + [vp, vp]
+        L.dmx_tracks_infer_from_flac_limit.argtypes = L.dmx_tracks_infer_from_flac_meters.argtypes + [vp, vp]
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -536,7 +550,7 @@ class Context:
         return finish()
 
     def tracks_pcm(self, audios, spec: Optional[OutputSpec] = None, n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None,
-                   progress=None, layout: int = LAYOUT_PLANAR, out=None, loudness=None, meters: bool = False):
+                   progress=None, layout: int = LAYOUT_PLANAR, out=None, loudness=None, meters: bool = False, limit_report: bool = False):
         """loudness: None, or a LoudnessSpec - the spec's outputs as 0/1 gains (the same bits) through dmx_tracks_infer_loud;
         returns (outs, peaks, report) as tracks_remix() does, with meters=True (outs, peaks, report, meters).
         tracks_opts() whose stems leave the GPU as WAV data (dmx_tracks_infer_pcm): two-stems, clip mode and sample
@@ -548,8 +562,8 @@ class Context:
             assert out is None, "loudness=: buffers to reuse are not taken"
             g = np.eye(self.S, self.S + 1, dtype=np.float32) if spec.stem < 0 else remix_two_stems(self.S, spec.stem, OTHER_ADD)
             return self.tracks_rates(audios, None, RemixSpec(g, spec.encoding, spec.clip), False, None, None, n_shifts, overlap, shift_offsets,
-                                     progress, layout, loudness, meters)
-        assert not meters, "meters=True needs loudness="
+                                     progress, layout, loudness, meters, limit_report)
+        assert not meters and not limit_report, "meters=True and limit_report=True need loudness="
         T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = self._output_count(spec)
         bufs, op = _byte_results([n_out * output_bytes(spec, n) for n in ns], out, exact=True)
@@ -584,7 +598,7 @@ class Context:
 
     def tracks_remix(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                      shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, out=None, peaks=None, loudness=None,
-                     meters: bool = False):
+                     meters: bool = False, limit_report: bool = False):
         """tracks_pcm() whose outputs are rows of gains over the stems and the original mixture (dmx_tracks_infer_remix).
         loudness: None, or a LoudnessSpec - the call goes through dmx_tracks_infer_loud and returns (outs, peaks, report), report
         a (T, n_out + 1) array of LOUDNESS_DTYPE, per track its outputs and then its mixture. meters=True (with loudness=): the call
@@ -595,8 +609,8 @@ class Context:
         if loudness is not None:
             assert out is None and peaks is None, "loudness=: buffers to reuse are not taken"
             return self.tracks_rates(audios, None, spec, False, models, weights, n_shifts, overlap, shift_offsets, progress, layout, loudness,
-                                     meters)
-        assert not meters, "meters=True needs loudness="
+                                     meters, limit_report)
+        assert not meters and not limit_report, "meters=True and limit_report=True need loudness="
         T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = max(spec.n_out, 0)
         bufs, op = _byte_results([n_out * b for b in _remix_bytes(spec, ns, False)], out, exact=True)
@@ -610,8 +624,9 @@ class Context:
 
     def tracks_from_flac(self, files, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                          shift_offsets=None, flac_out: bool = False, progress=None, track_status=None, out=None, any_rate: bool = False,
-                         loudness=None, meters: bool = False):
+                         loudness=None, meters: bool = False, limit_report: bool = False):
         """meters=True (with loudness=): through dmx_tracks_infer_from_flac_meters, and the meters report is returned last.
+        A loudness spec with LOUD_LIMIT, or limit_report=True: through dmx_tracks_infer_from_flac_limit; the limiter's report last.
         tracks_remix() (flac_out False) or tracks_flac() at 44100 Hz (flac_out True) on tracks given as the bytes of .flac
         files (dmx_tracks_infer_from_flac). any_rate: every track runs at the rate of its file, as tracks_rates() runs it
         (dmx_tracks_infer_from_flac_rates); the outputs have the file's frames and rate. Returns (outs, peaks, track_status): track_status np.int64 (T, 2) = {status, good}
@@ -644,13 +659,10 @@ class Context:
             for t, f in enumerate(imgs):
                 if not any_rate and flac_probe(f).sample_rate != 44100:  # what dmx_tracks_infer_from_flac says of such a file
                     raise DmxError(5, f"tracks_from_flac: track {t}: sample rate {flac_probe(f).sample_rate} (any_rate=True takes other rates)")
-            report = np.zeros((max(T, 1), n_out + 1), LOUDNESS_DTYPE)
-            call, extra = lib().dmx_tracks_infer_from_flac_loud, (ctypes.byref(loudness), report.ctypes.data)
-            if meters:
-                mrep = np.zeros((max(T, 1), n_out + 1), METERS_DTYPE)
-                call, extra = lib().dmx_tracks_infer_from_flac_meters, extra + (mrep.ctypes.data,)
+            tail = _LoudTail(loudness, meters, limit_report, (max(T, 1),), n_out)
+            call, extra = tail.pick(lib(), "dmx_tracks_infer_from_flac"), tail.args
         else:
-            assert not meters, "meters=True needs loudness="
+            assert not meters and not limit_report, "meters=True and limit_report=True need loudness="
         rc = call(self.h, mp, Q, wp, T, _pointers(imgs), fn, int(n_shifts), float(overlap), so, ctypes.byref(spec.c), 1 if flac_out else 0, op,
                   sizes.ctypes.data, peaks.ctypes.data, track_status.ctypes.data, cbp, None, *extra)
         outs = _flac_files(bufs, per, sizes, n_out) if flac_out else _pcm_results(bufs, spec.output_spec(), ns, n_out)
@@ -660,22 +672,24 @@ class Context:
             e.partial = (outs, pk)
             raise e
         if loudness is not None:
-            return (outs, pk, track_status[:2 * T].reshape(T, 2), report[:T]) + ((mrep[:T],) if meters else ())
+            return (outs, pk, track_status[:2 * T].reshape(T, 2)) + tail.results(T)
         return outs, pk, track_status[:2 * T].reshape(T, 2)
 
     def tracks_rates(self, audios, rates, spec: Optional[RemixSpec] = None, flac: bool = False, models=None, weights=None,
                      n_shifts: int = 1, overlap: float = 0.25, shift_offsets=None, progress=None, layout: int = LAYOUT_PLANAR, loudness=None,
-                     meters: bool = False):
+                     meters: bool = False, limit_report: bool = False):
         """loudness: None, or a LoudnessSpec (a RemixSpec is then required; rates may be None: all 44100) - the call goes through
         dmx_tracks_infer_loud and returns (outs, peaks, report), report a (T, n_out + 1) array of LOUDNESS_DTYPE; with meters=True
         through dmx_tracks_infer_meters, and (outs, peaks, report, meters) with meters a (T, n_out + 1) array of METERS_DTYPE.
+        A loudness spec with LOUD_LIMIT, or limit_report=True: through dmx_tracks_infer_limit; limit_report=True returns a (T, n_out)
+        array of LIMIT_DTYPE last.
         Tracks at their own sample rates (dmx_tracks_infer_rates): audios[t] is (2, n_t) at rates[t] Hz; a track that is not
         at 44100 Hz is converted on the device in front of the model and its stems behind it. spec None: a list of (S, 2, n_t)
         float32 arrays as tracks_opts() / tracks_bag(); a RemixSpec: (outs, peaks) as tracks_remix(), or with flac=True
         (files, peaks) as tracks_flac(), every file at its track's rate. models / weights / shift_offsets as tracks_remix()."""
         T, ns, src, ap, na = _track_inputs(audios, layout)
         assert rates is not None or loudness is not None
-        assert loudness is not None or not meters, "meters=True needs loudness="
+        assert loudness is not None or not (meters or limit_report), "meters=True and limit_report=True need loudness="
         assert rates is None or len(rates) == T
         ra = None if rates is None else (ctypes.c_int * max(T, 1))(*[int(r) for r in rates])
         mp, Q, wp, keep = _models_weights(models, weights, self.S)
@@ -693,13 +707,9 @@ class Context:
             peaks = _flat_result(None, T * n_out, np.float32)
             sp, sz, pk = ctypes.byref(spec.c), sizes.ctypes.data, peaks.ctypes.data
         if loudness is not None:
-            report = np.zeros((max(T, 1), (0 if spec is None else n_out) + 1), LOUDNESS_DTYPE)
-            call, extra = lib().dmx_tracks_infer_loud, ()
-            if meters:
-                mrep = np.zeros(report.shape, METERS_DTYPE)
-                call, extra = lib().dmx_tracks_infer_meters, (mrep.ctypes.data,)
-            _chk(call(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op, sz, pk, layout, cbp, None,
-                      ctypes.byref(loudness), report.ctypes.data, *extra))
+            tail = _LoudTail(loudness, meters, limit_report, (max(T, 1),), 0 if spec is None else n_out)
+            _chk(tail.pick(lib(), "dmx_tracks_infer")(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op,
+                                                      sz, pk, layout, cbp, None, *tail.args))
         else:
             _chk(lib().dmx_tracks_infer_rates(self.h, mp, Q, wp, T, ap, na, ra, int(n_shifts), float(overlap), so, sp, 1 if flac else 0, op, sz,
                                               pk, layout, cbp, None))
@@ -707,12 +717,12 @@ class Context:
             return finish()
         outs = _flac_files(bufs, per, sizes, n_out) if flac else _pcm_results(bufs, spec.output_spec(), ns, n_out)
         if loudness is not None:
-            return (outs, _cut_peaks(peaks, T, n_out), report[:T]) + ((mrep[:T],) if meters else ())
+            return (outs, _cut_peaks(peaks, T, n_out)) + tail.results(T)
         return outs, _cut_peaks(peaks, T, n_out)
 
     def tracks_flac(self, audios, spec: RemixSpec, models=None, weights=None, n_shifts: int = 1, overlap: float = 0.25,
                     shift_offsets=None, sample_rate: int = 44100, progress=None, layout: int = LAYOUT_PLANAR, out=None, sizes=None,
-                    peaks=None, loudness=None, meters: bool = False):
+                    peaks=None, loudness=None, meters: bool = False, limit_report: bool = False):
         """tracks_remix() whose outputs leave as .flac files (dmx_tracks_infer_flac): spec.encoding PCM_S16 or PCM_S24.
         Returns (files, peaks): files[t][o] the bytes of track t's output o, peaks as tracks_remix(). `out`: buffers to reuse
         (np.uint8 of n_out * flac_bound(bits, n) bytes per track); `sizes`: a flat np.int64 array of at least T * n_out."""
@@ -720,8 +730,8 @@ class Context:
             assert out is None and sizes is None and peaks is None, "loudness=: buffers to reuse are not taken"
             assert int(sample_rate) == 44100, "loudness=: the tracks are at 44100 Hz; tracks_rates() takes tracks at other rates"
             return self.tracks_rates(audios, None, spec, True, models, weights, n_shifts, overlap, shift_offsets, progress, layout, loudness,
-                                     meters)
-        assert not meters, "meters=True needs loudness="
+                                     meters, limit_report)
+        assert not meters and not limit_report, "meters=True and limit_report=True need loudness="
         T, ns, src, ap, na = _track_inputs(audios, layout)
         n_out = max(spec.n_out, 0)
         bits = 24 if spec.encoding == PCM_S24 else 16
@@ -932,16 +942,26 @@ LOUD_MEASURE, LOUD_MIXTURE, LOUD_EACH = 0, 1, 2  # DMX_LOUD_*
 LUFS_UNMEASURABLE = -(2 ** 31)  # DMX_LUFS_UNMEASURABLE
 LOUD_MIN_RATE = 4000  # DMX_LOUD_MIN_RATE
 LOUD_TRUE_PEAK = 0x100  # DMX_LOUD_TRUE_PEAK, OR-ed into the mode: max_peak is a true-peak ceiling
+LOUD_UNITY = 3  # DMX_LOUD_UNITY: the limiter without loudnorm (needs LOUD_LIMIT)
+LOUD_LIMIT = 0x200  # DMX_LOUD_LIMIT, OR-ed into the mode: the look-ahead limiter holds max_peak, the gain is not lowered
+LIMIT_ATTACK_MS, LIMIT_RELEASE_MS = 5.0, 100.0  # DMX_LIMIT_*: the times in which the reduction moves by 10 dB
 
 
 class LoudnessSpec(ctypes.Structure):
     """dmx_loudness_spec: mode LOUD_*, the target in LUFS (finite, in [-70, 0]) and the ceiling of the sample peak as a linear
     value (> 0; inf: none). The default ceiling is -1 dBFS. true_peak: the ceiling is one of the true peak (-1 dBTP), the flag
-    LOUD_TRUE_PEAK in the mode."""
+    LOUD_TRUE_PEAK in the mode. limit: the flag LOUD_LIMIT (loud_encode then goes through dmx_loud_encode_limit); attack_ms and
+    release_ms are the limiter's times, kept beside the struct (dmx_limiter_spec)."""
     _fields_ = [("mode", ctypes.c_int), ("target_lufs", ctypes.c_float), ("max_peak", ctypes.c_float)]
+    attack_ms, release_ms = LIMIT_ATTACK_MS, LIMIT_RELEASE_MS  # of a spec that was not made by __init__ (a copy of the bytes): the defaults
 
-    def __init__(self, mode=LOUD_MIXTURE, target_lufs=-14.0, max_peak=10.0 ** (-1.0 / 20.0), true_peak: bool = False):
-        super().__init__(int(mode) | (LOUD_TRUE_PEAK if true_peak else 0), float(target_lufs), float(max_peak))
+    def __init__(self, mode=LOUD_MIXTURE, target_lufs=-14.0, max_peak=10.0 ** (-1.0 / 20.0), true_peak: bool = False, limit: bool = False,
+                 attack_ms: float = LIMIT_ATTACK_MS, release_ms: float = LIMIT_RELEASE_MS):
+        super().__init__(int(mode) | (LOUD_TRUE_PEAK if true_peak else 0) | (LOUD_LIMIT if limit else 0), float(target_lufs), float(max_peak))
+        self.attack_ms, self.release_ms = float(attack_ms), float(release_ms)
+
+    def limiter(self):
+        return LimiterSpec(self.attack_ms, self.release_ms)
 
 
 class LoudnessResult(ctypes.Structure):
@@ -1019,10 +1039,47 @@ def loudness(x: np.ndarray, rate: int, interleaved: bool = False, device: int = 
     return res, e
 
 
-def loud_encode(planes: np.ndarray, mix: np.ndarray, spec: RemixSpec, loud: LoudnessSpec, rate: int, device: int = 0, meters: bool = False):
+def limiter_check(spec: Optional[LoudnessSpec], rate: int):
+    """validates a LoudnessSpec that may carry LOUD_LIMIT or be LOUD_UNITY, with its limiter times (dmx_limiter_check; no GPU)"""
+    lim = None if spec is None else spec.limiter()
+    _chk(lib().dmx_limiter_check(None if spec is None else ctypes.byref(spec), None if lim is None else ctypes.byref(lim), int(rate)))
+
+
+class _LoudTail:
+    """what a call behind the loudness stage appends to its arguments and to its results - the one marshalling path of the
+    `_loud` / `_meters` / `_limit` entry points: the spec and the loudness report; with meters=True the meters report; with
+    LOUD_LIMIT in the spec's mode or limit_report=True the limiter's times and its report. shape: () or (T,)."""
+
+    def __init__(self, loud, meters: bool, limit_report: bool, shape, n_out: int):
+        self.meters, self.limit_report = bool(meters), bool(limit_report)
+        self.limited = self.limit_report or bool(loud.mode & LOUD_LIMIT)
+        self.report = np.zeros(shape + (n_out + 1,), LOUDNESS_DTYPE)
+        self.mrep = np.zeros(shape + (n_out + 1,), METERS_DTYPE) if meters else None
+        self.lrep = np.zeros(shape + (max(n_out, 1),), LIMIT_DTYPE) if self.limited else None
+        self.n_out = n_out
+        self._keep = (loud, loud.limiter())
+        self.args = (ctypes.byref(loud), self.report.ctypes.data)
+        if self.limited:
+            self.args += (None if self.mrep is None else self.mrep.ctypes.data, ctypes.byref(self._keep[1]), self.lrep.ctypes.data)
+        elif meters:
+            self.args += (self.mrep.ctypes.data,)
+
+    def pick(self, L, stem: str):
+        plain = "" if stem == "dmx_loud_encode" else "_loud"
+        return getattr(L, stem + ("_limit" if self.limited else "_meters" if self.meters else plain))
+
+    def results(self, T=None):
+        cut = (lambda a: a) if T is None else (lambda a: a[:T])
+        return (cut(self.report),) + ((cut(self.mrep),) if self.meters else ()) + ((cut(self.lrep)[..., :self.n_out],) if self.limit_report else ())
+
+
+def loud_encode(planes: np.ndarray, mix: np.ndarray, spec: RemixSpec, loud: LoudnessSpec, rate: int, device: int = 0, meters: bool = False,
+                limit_report: bool = False):
     """The remix output stage behind the loudness stage (dmx_loud_encode): planes (S, 2, n) float32, mix (2, n) float32 ->
     (list of n_out arrays as tracks_pcm, peaks, report) with report a (n_out + 1,) array of LOUDNESS_DTYPE, the mixture last.
-    meters=True (dmx_loud_encode_meters): (outs, peaks, report, meters), meters a (n_out + 1,) array of METERS_DTYPE."""
+    meters=True (dmx_loud_encode_meters): (outs, peaks, report, meters), meters a (n_out + 1,) array of METERS_DTYPE.
+    A spec with LOUD_LIMIT, or limit_report=True, goes through dmx_loud_encode_limit; limit_report=True returns a (n_out,) array of
+    LIMIT_DTYPE last."""
     planes = np.ascontiguousarray(planes, np.float32)
     S, two, n = planes.shape
     assert two == 2 and mix is not None and mix.shape == (2, n)
@@ -1030,15 +1087,62 @@ def loud_encode(planes: np.ndarray, mix: np.ndarray, spec: RemixSpec, loud: Loud
     n_out = max(spec.n_out, 0)
     buf = np.zeros(max(n_out * n * _frame_bytes(spec.encoding), 1), np.uint8)
     peaks = np.zeros(max(n_out, 1), np.float32)
-    report = np.zeros(n_out + 1, LOUDNESS_DTYPE)
-    if meters:
-        mrep = np.zeros(n_out + 1, METERS_DTYPE)
-        _chk(lib().dmx_loud_encode_meters(device, planes.ctypes.data, S, n, mi.ctypes.data, ctypes.byref(spec.c), ctypes.byref(loud), int(rate),
-                                          buf.ctypes.data, peaks.ctypes.data, report.ctypes.data, mrep.ctypes.data))
-        return pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out], report, mrep
-    _chk(lib().dmx_loud_encode(device, planes.ctypes.data, S, n, mi.ctypes.data, ctypes.byref(spec.c), ctypes.byref(loud), int(rate),
-                               buf.ctypes.data, peaks.ctypes.data, report.ctypes.data))
-    return pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out], report
+    tail = _LoudTail(loud, meters, limit_report, (), n_out)
+    a = tail.args
+    _chk(tail.pick(lib(), "dmx_loud_encode")(device, planes.ctypes.data, S, n, mi.ctypes.data, ctypes.byref(spec.c), a[0], int(rate), buf.ctypes.data,
+                                             peaks.ctypes.data, *a[1:]))
+    return (pcm_views(buf, spec.output_spec(), n, n_out), peaks[:n_out]) + tail.results()
+
+
+class LimiterSpec(ctypes.Structure):
+    """dmx_limiter_spec: the attack and release times in ms, finite and in [0.1, 10000]"""
+    _fields_ = [("attack_ms", ctypes.c_float), ("release_ms", ctypes.c_float)]
+
+    def __init__(self, attack_ms=LIMIT_ATTACK_MS, release_ms=LIMIT_RELEASE_MS):
+        super().__init__(float(attack_ms), float(release_ms))
+
+
+class LimitResult(ctypes.Structure):
+    """dmx_limit_result: the sample peak and (with true_peak, else 0) the true peak of the limited signal, the largest reduction
+    in units of 1 / 65536 octave, and the frames whose reduction is not 0"""
+    _fields_ = [("peak_out", ctypes.c_float), ("true_peak_out", ctypes.c_float), ("max_reduction", ctypes.c_int32),
+                ("limited_frames", ctypes.c_int64)]
+
+
+LIMIT_DTYPE = np.dtype([("peak_out", "<f4"), ("true_peak_out", "<f4"), ("max_reduction", "<i4"), ("limited_frames", "<i8")],
+                       align=True)  # an array of dmx_limit_result
+
+
+def limiter_tables():
+    """(LUT int32 [4096], THI float32 [385], TLO float32 [4096]) of the limiter (dmx_limiter_tables; no GPU)"""
+    lut, thi, tlo = np.zeros(4096, np.int32), np.zeros(385, np.float32), np.zeros(4096, np.float32)
+    _chk(lib().dmx_limiter_tables(lut.ctypes.data, thi.ctypes.data, tlo.ctypes.data))
+    return lut, thi, tlo
+
+
+def limiter_slopes(rate: int, attack_ms: float = LIMIT_ATTACK_MS, release_ms: float = LIMIT_RELEASE_MS):
+    """(qa, qr) in units per frame (dmx_limiter_slopes; no GPU); raises DmxError naming the field"""
+    qa, qr = ctypes.c_int32(0), ctypes.c_int32(0)
+    _chk(lib().dmx_limiter_slopes(int(rate), float(attack_ms), float(release_ms), ctypes.byref(qa), ctypes.byref(qr)))
+    return qa.value, qr.value
+
+
+def limiter_workspace_bytes(n: int) -> int:
+    return lib().dmx_limiter_workspace_bytes(int(n))
+
+
+def limit(x: np.ndarray, rate: int, max_peak: float, gain: float = 1.0, true_peak: bool = False, attack_ms: float = LIMIT_ATTACK_MS,
+          release_ms: float = LIMIT_RELEASE_MS, interleaved: bool = False, device: int = 0):
+    """The look-ahead peak limiter alone on one stereo signal (dmx_limit): x (2, n) float32 or, interleaved, (n, 2) ->
+    (M int32 (n,) the required reduction, G float32 (n,) the gain plane, LimitResult). The limited signal is (gain * x) * G."""
+    x = np.ascontiguousarray(x, np.float32)
+    n = x.shape[0] if interleaved else x.shape[1]
+    assert x.shape == ((n, 2) if interleaved else (2, n))
+    M, G, res = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32), LimitResult()
+    spec = LimiterSpec(attack_ms, release_ms)
+    _chk(lib().dmx_limit(device, x.ctypes.data, n, int(bool(interleaved)), int(rate), float(gain), float(max_peak), int(bool(true_peak)),
+                         ctypes.byref(spec), M.ctypes.data, G.ctypes.data, ctypes.byref(res)))
+    return M[:n], G[:n], res
 
 
 def flac_bound(bits: int, n: int) -> int:

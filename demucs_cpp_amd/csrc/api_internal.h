@@ -199,6 +199,10 @@ int dmx_pcm_frame_bytes(int encoding);                                      // b
 int dmx_remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, dmx::PcmGains *G, bool noModel);
 // ---- codec_api.cpp, used by tracks_exec.cpp (the loudness stage)
 int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate, int track); // track < 0: no track to name
+// the same validator for the entry points that take the limiter: DMX_LOUD_LIMIT, DMX_LOUD_UNITY and the times
+int dmx_limit_check_spec(const char *fn, const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate, int track);
+// the limiter's tables on `device` (kLimTableWords words): one copy per device, uploaded on first use, kept for the process
+int dmx_limiter_device_tables(int device, const int32_t **T);
 
 // ---- internal entry points used by engine.cpp
 int dmx_ensure_buf(DevBuf &b, dmx::i64 floats);

@@ -152,23 +152,44 @@ extern "C" int dmx_loudness_gain_table(float *table)
 }
 extern "C" int64_t dmx_loudness_workspace_bytes(int64_t n) { return loud_workspace_bytes(n); }
 
-int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate, int track)
+// the one validator of a loudness spec. limiter: the spec may carry DMX_LOUD_LIMIT or be DMX_LOUD_UNITY (sections 2.16), and
+// the limiter's times are checked (lim NULL: the defaults); else the modes of section 2.15 alone, as dmx_loudness_check's
+// contract has it
+static int loud_check_impl(const char *fn, const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate, int track, bool limiter)
 {
     if (!spec)
         return fail(DMX_ERR_ARG, "%s: null loudness spec", fn);
-    const int base = spec->mode & ~DMX_LOUD_TRUE_PEAK;
-    if (spec->mode < 0 || (base != DMX_LOUD_MEASURE && base != DMX_LOUD_MIXTURE && base != DMX_LOUD_EACH))
-        return fail(DMX_ERR_ARG, "%s: loudness spec: mode %d (DMX_LOUD_MEASURE 0, DMX_LOUD_MIXTURE 1, DMX_LOUD_EACH 2, each alone or with DMX_LOUD_TRUE_PEAK 0x100)",
-                    fn, spec->mode);
+    const int flags = DMX_LOUD_TRUE_PEAK | (limiter ? DMX_LOUD_LIMIT : 0), base = spec->mode & ~flags;
+    const bool limit = limiter && spec->mode >= 0 && (spec->mode & DMX_LOUD_LIMIT) != 0;
+    const bool okBase = base == DMX_LOUD_MEASURE || base == DMX_LOUD_MIXTURE || base == DMX_LOUD_EACH || (limiter && base == DMX_LOUD_UNITY);
+    if (spec->mode < 0 || !okBase || (limit && base == DMX_LOUD_MEASURE) || (!limit && base == DMX_LOUD_UNITY))
+        return fail(DMX_ERR_ARG, "%s: loudness spec: mode %d (DMX_LOUD_MEASURE 0, DMX_LOUD_MIXTURE 1, DMX_LOUD_EACH 2, each alone or with DMX_LOUD_TRUE_PEAK 0x100%s)",
+                    fn, spec->mode, limiter ? "; DMX_LOUD_LIMIT 0x200 with DMX_LOUD_MIXTURE, DMX_LOUD_EACH or DMX_LOUD_UNITY 3, which needs it" : "");
     if (!std::isfinite(spec->target_lufs) || spec->target_lufs < -70.0f || spec->target_lufs > 0.0f)
         return fail(DMX_ERR_ARG, "%s: loudness spec: target_lufs %g is not in [-70, 0]", fn, (double)spec->target_lufs);
     if (!(spec->max_peak > 0.0f))
         return fail(DMX_ERR_ARG, "%s: loudness spec: max_peak %g is not above 0", fn, (double)spec->max_peak);
+    if (limit && !std::isfinite(spec->max_peak))
+        return fail(DMX_ERR_ARG, "%s: loudness spec: max_peak %g with DMX_LOUD_LIMIT: the limiter needs a finite ceiling", fn, (double)spec->max_peak);
     if (rate < DMX_LOUD_MIN_RATE && track >= 0)
         return fail(DMX_ERR_ARG, "%s: track %d: loudness: rate %d is below %d Hz", fn, track, rate, DMX_LOUD_MIN_RATE);
     if (rate < DMX_LOUD_MIN_RATE)
         return fail(DMX_ERR_ARG, "%s: loudness: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
+    if (!limiter)
+        return DMX_OK;
+    const double ms[2] = {lim ? (double)lim->attack_ms : kLimAttackMs, lim ? (double)lim->release_ms : kLimReleaseMs};
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(ms[k]) || ms[k] < kLimMinMs || ms[k] > kLimMaxMs)
+            return fail(DMX_ERR_ARG, "%s: limiter spec: %s %g is not in [0.1, 10000]", fn, k ? "release_ms" : "attack_ms", ms[k]);
     return DMX_OK;
+}
+int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate, int track)
+{
+    return loud_check_impl(fn, spec, nullptr, rate, track, false);
+}
+int dmx_limit_check_spec(const char *fn, const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate, int track)
+{
+    return loud_check_impl(fn, spec, lim, rate, track, true);
 }
 static int loud_check(const char *fn, const dmx_loudness_spec *spec, int rate) { return dmx_loud_check_spec(fn, spec, rate, -1); }
 extern "C" int dmx_loudness_check(const dmx_loudness_spec *spec, int rate) { return loud_check("dmx_loudness_check", spec, rate); }
@@ -382,12 +403,22 @@ static int loud_encode_device(const char *fn, int device, const float *d_planes,
     return DMX_OK;
 }
 
+// the entry points of this section and of the meters' are the limiter's without its two arguments: a mode
+// without DMX_LOUD_LIMIT enqueues loud_encode_device, above
+static int loud_encode_limit_device(const char *fn, int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                    const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                                    float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream, dmx_meters_result *d_meters,
+                                    const dmx_limiter_spec *lim, dmx_limit_result *d_limit);
+static int loud_encode_limit_host(const char *fn, int device, const float *planes, int n_sources, int64_t n, const float *mix,
+                                  const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *out, float *peaks,
+                                  dmx_loudness_result *report, dmx_meters_result *meters, const dmx_limiter_spec *lim, dmx_limit_result *limit);
+
 extern "C" int dmx_loud_encode_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride, const float *d_mix,
                                       const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out, float *d_peaks,
                                       dmx_loudness_result *d_report, void *d_work, void *stream)
 {
-    return loud_encode_device("dmx_loud_encode_device", device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks,
-                              d_report, d_work, stream, nullptr);
+    return loud_encode_limit_device("dmx_loud_encode_device", device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out,
+                                    d_peaks, d_report, d_work, stream, nullptr, nullptr, nullptr);
 }
 
 extern "C" int dmx_loud_encode_meters_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
@@ -398,60 +429,22 @@ extern "C" int dmx_loud_encode_meters_device(int device, const float *d_planes, 
     const char *fn = "dmx_loud_encode_meters_device";
     if (!d_meters)
         return fail(DMX_ERR_ARG, "%s: null d_meters pointer", fn);
-    return loud_encode_device(fn, device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks, d_report, d_work, stream,
-                              d_meters);
-}
-
-// meters: null, or n_out + 1 entries; withMeters: the entry point is dmx_loud_encode_meters
-static int loud_encode_host(const char *fn, int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
-                            const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
-                            dmx_meters_result *meters)
-{
-    PcmGains G;
-    DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
-    DMXCHK(loud_check(fn, loud, rate));
-    if (!planes || !out || !mix || n < 1 || n >= (int64_t)1 << 36)
-        return fail(DMX_ERR_ARG, "%s: invalid argument (null planes, mix or out pointer, n < 1 or n >= 2^36)", fn);
-    HIPCHK(hipSetDevice(device));
-    const int nOut = G.nOut;
-    const i64 bytes = n * dmx_pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
-    const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n, mixBytes = sizeof(float) * 2 * (size_t)n;
-    const size_t workBytes = (size_t)((nOut + 1) * (loud_workspace_bytes(n) + (meters ? meters_workspace_bytes(n) : 0)) + 64);
-    const size_t reportBytes = sizeof(dmx_loudness_result) * (size_t)(nOut + 1), metersBytes = sizeof(dmx_meters_result) * (size_t)(nOut + 1);
-    const size_t smallBytes = 256 + reportBytes + (meters ? metersBytes : 0); // the peaks, then the report, then the meters
-    DevScratch d;
-    float *dIn = (float *)d.get(inBytes + DMX_OUTPUT_STRIDE(mixBytes)); // the planes, then the mixture
-    unsigned char *dOut = (unsigned char *)d.get((size_t)(nOut * devStride));
-    unsigned char *dSmall = (unsigned char *)d.get(smallBytes);
-    void *dWork = d.get(workBytes);
-    if (!d.ok)
-        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
-    float *dMix = dIn + (size_t)n_sources * 2 * (size_t)n;
-    float *dPeaks = (float *)dSmall;
-    dmx_loudness_result *dReport = (dmx_loudness_result *)(dSmall + 256);
-    if (hipMemcpy(dIn, planes, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dMix, mix, mixBytes, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
-    dmx_meters_result *dMeters = meters ? (dmx_meters_result *)(dSmall + 256 + reportBytes) : nullptr;
-    DMXCHK(loud_encode_device(fn, device, dIn, n_sources, n, n, dMix, spec, loud, rate, dOut, dPeaks, dReport, dWork, nullptr, dMeters));
-    DMXCHK(pcm_download(fn, out, peaks, dOut, dPeaks, nOut, bytes, devStride));
-    if (report && hipMemcpy(report, dReport, reportBytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(DMX_ERR_HIP, "%s: download failed", fn);
-    if (meters && hipMemcpy(meters, dMeters, metersBytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(DMX_ERR_HIP, "%s: download failed", fn);
-    return DMX_OK;
+    return loud_encode_limit_device(fn, device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks, d_report, d_work,
+                                    stream, d_meters, nullptr, nullptr);
 }
 
 extern "C" int dmx_loud_encode(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
                                const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report)
 {
-    return loud_encode_host("dmx_loud_encode", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, nullptr);
+    return loud_encode_limit_host("dmx_loud_encode", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, nullptr, nullptr, nullptr);
 }
 
 extern "C" int dmx_loud_encode_meters(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
                                       const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
                                       dmx_meters_result *meters)
 {
-    return loud_encode_host("dmx_loud_encode_meters", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, meters);
+    return loud_encode_limit_host("dmx_loud_encode_meters", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, meters, nullptr,
+                                  nullptr);
 }
 
 // --------------------------------------------------------------------------- meters (meters.hip)
@@ -575,6 +568,331 @@ extern "C" int dmx_meters(int device, const float *x, int64_t n, int interleaved
     if (hipMemcpy(result, dRes, sizeof(dmx_loudness_result), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(meters, dRes + 16, sizeof(dmx_meters_result), hipMemcpyDeviceToHost) != hipSuccess ||
         (dE && hipMemcpy(e, dE, eBytes, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
+}
+
+// --------------------------------------------------------------------------- limiter (limiter.hip)
+extern "C" int dmx_limiter_tables(int32_t *lut, float *thi, float *tlo)
+{
+    if (!lut || !thi || !tlo)
+        return fail(DMX_ERR_ARG, "dmx_limiter_tables: null %s pointer", !lut ? "lut" : !thi ? "thi" : "tlo");
+    lim_tables(lut, thi, tlo);
+    return DMX_OK;
+}
+static int limiter_slopes(const char *fn, int rate, double attack_ms, double release_ms, int *qa, int *qr)
+{
+    if (rate < 1)
+        return fail(DMX_ERR_ARG, "%s: limiter spec: rate %d", fn, rate);
+    if (!std::isfinite(attack_ms) || attack_ms < kLimMinMs || attack_ms > kLimMaxMs)
+        return fail(DMX_ERR_ARG, "%s: limiter spec: attack_ms %g is not in [0.1, 10000]", fn, attack_ms);
+    if (!std::isfinite(release_ms) || release_ms < kLimMinMs || release_ms > kLimMaxMs)
+        return fail(DMX_ERR_ARG, "%s: limiter spec: release_ms %g is not in [0.1, 10000]", fn, release_ms);
+    (void)lim_slopes(rate, attack_ms, release_ms, qa, qr);
+    return DMX_OK;
+}
+extern "C" int dmx_limiter_slopes(int rate, double attack_ms, double release_ms, int32_t *qa, int32_t *qr)
+{
+    if (!qa || !qr)
+        return fail(DMX_ERR_ARG, "dmx_limiter_slopes: null %s pointer", !qa ? "qa" : "qr");
+    return limiter_slopes("dmx_limiter_slopes", rate, attack_ms, release_ms, qa, qr);
+}
+extern "C" int64_t dmx_limiter_workspace_bytes(int64_t n) { return lim_workspace_bytes(n); }
+
+// the stage alone has no context to own the tables: one copy per device, made on first use (a blocking upload) and kept for
+// the life of the process (34 KB), as loud_table keeps the gain table
+int dmx_limiter_device_tables(int device, const int32_t **T)
+{
+    static std::mutex mu;
+    static std::map<int, int32_t *> tables;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = tables.find(device);
+    if (it == tables.end())
+    {
+        std::vector<int32_t> h(kLimTableWords, 0);
+        lim_tables(h.data(), reinterpret_cast<float *>(h.data() + kLimLut), reinterpret_cast<float *>(h.data() + kLimLut + kLimHiPad));
+        int32_t *d = nullptr;
+        HIPCHK(hipMalloc(&d, sizeof(int32_t) * h.size()));
+        if (hipMemcpy(d, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+        {
+            (void)hipFree(d);
+            return fail(DMX_ERR_HIP, "limiter: the tables' upload failed");
+        }
+        it = tables.emplace(device, d).first;
+    }
+    *T = it->second;
+    return DMX_OK;
+}
+
+// what the stage refuses before any GPU work, and the slopes
+static int limit_check(const char *fn, int rate, float max_peak, const dmx_limiter_spec *lim, int *qa, int *qr)
+{
+    DMXCHK(limiter_slopes(fn, rate, lim ? (double)lim->attack_ms : kLimAttackMs, lim ? (double)lim->release_ms : kLimReleaseMs, qa, qr));
+    if (!(max_peak > 0.0f) || !std::isfinite(max_peak))
+        return fail(DMX_ERR_ARG, "%s: max_peak %g is not finite and above 0", fn, (double)max_peak);
+    return DMX_OK;
+}
+
+// marks: null, or five events around the launches
+static int limit_device(const char *fn, int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, float gain, float max_peak,
+                        int true_peak, const dmx_limiter_spec *lim, dmx_limit_result *d_result, void *d_work, void *stream, hipEvent_t *marks)
+{
+    LimJob job{};
+    DMXCHK(limit_check(fn, rate, max_peak, lim, &job.qa, &job.qr));
+    if (n < 1 || n >= (int64_t)1 << 36 || (plane_stride != 0 && plane_stride < n))
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n < 2^36; plane_stride 0 or >= n)", fn, (long long)n,
+                    (long long)plane_stride);
+    if (!d_x || !d_result || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_x ? "d_x" : !d_result ? "d_result" : "d_work");
+    if (((uintptr_t)d_x & 3) != 0 || ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_result & 7) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_x must be 4-byte aligned, d_work 16-byte aligned, d_result 8-byte aligned", fn);
+    HIPCHK(hipSetDevice(device));
+    DMXCHK(dmx_limiter_device_tables(device, &job.tables));
+    loud_signal(d_x, n, plane_stride, &job.pc, &job.G);
+    job.gains = nullptr, job.gainImm = gain, job.ceiling = max_peak, job.link = 0;
+    job.work = (unsigned char *)d_work, job.res = d_result;
+    TpFilter f;
+    tp_filter(rate, &f);
+    launch_limit(job, f, true_peak != 0, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_limit_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, float gain, float max_peak,
+                                int true_peak, const dmx_limiter_spec *lim, dmx_limit_result *d_result, void *d_work, void *stream)
+{
+    return limit_device("dmx_limit_device", device, d_x, n, plane_stride, rate, gain, max_peak, true_peak, lim, d_result, d_work, stream, nullptr);
+}
+
+extern "C" int dmx_limit_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, float gain, float max_peak,
+                                      int true_peak, const dmx_limiter_spec *lim, dmx_limit_result *d_result, void *d_work, void *stream,
+                                      float *ms)
+{
+    const char *fn = "dmx_limit_device_timed";
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    hipEvent_t ev[7] = {};
+    unsigned *dPeak = nullptr;
+    int rc = DMX_OK;
+    for (hipEvent_t &e : ev)
+        if (rc == DMX_OK && hipEventCreate(&e) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+    if (rc == DMX_OK && hipMalloc(&dPeak, sizeof(unsigned)) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (rc == DMX_OK)
+        rc = limit_device(fn, device, d_x, n, plane_stride, rate, gain, max_peak, true_peak, lim, d_result, d_work, stream, ev);
+    if (rc == DMX_OK)
+    {
+        RemixPiece pc;
+        PcmGains G;
+        loud_signal(d_x, n, plane_stride, &pc, &G);
+        pc.peaks = dPeak;
+        (void)hipMemsetAsync(dPeak, 0, sizeof(unsigned), s);
+        (void)hipEventRecord(ev[5], s);
+        launch_remix_peak(&pc, 1, G, s);
+        (void)hipEventRecord(ev[6], s);
+        if (hipEventSynchronize(ev[6]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    }
+    for (int i = 0; i < 4 && rc == DMX_OK; ++i)
+        if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
+            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    if (rc == DMX_OK && hipEventElapsedTime(&ms[4], ev[5], ev[6]) != hipSuccess)
+        rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+    for (hipEvent_t e : ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    if (dPeak)
+        (void)hipFree(dPeak);
+    return rc;
+}
+
+extern "C" int dmx_limit(int device, const float *x, int64_t n, int interleaved, int rate, float gain, float max_peak, int true_peak,
+                         const dmx_limiter_spec *lim, int32_t *m, float *gain_plane, dmx_limit_result *result)
+{
+    const char *fn = "dmx_limit";
+    if (!x || !result || n < 1 || n >= (int64_t)1 << 36)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer, n < 1 or n >= 2^36)", fn);
+    int qa, qr;
+    DMXCHK(limit_check(fn, rate, max_peak, lim, &qa, &qr));
+    HIPCHK(hipSetDevice(device));
+    const size_t inBytes = sizeof(float) * 2 * (size_t)n;
+    DevScratch d;
+    float *dX = (float *)d.get(inBytes);
+    unsigned char *dWork = (unsigned char *)d.get((size_t)lim_workspace_bytes(n));
+    dmx_limit_result *dRes = (dmx_limit_result *)d.get(sizeof(dmx_limit_result));
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    if (hipMemcpy(dX, x, inBytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(limit_device(fn, device, dX, n, interleaved ? 0 : n, rate, gain, max_peak, true_peak, lim, dRes, dWork, nullptr, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(result, dRes, sizeof(dmx_limit_result), hipMemcpyDeviceToHost) != hipSuccess ||
+        (m && hipMemcpy(m, dWork, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (gain_plane && hipMemcpy(gain_plane, dWork + lim_ws_gain_offset(n), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
+}
+
+static int limiter_check(const char *fn, const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate)
+{
+    return dmx_limit_check_spec(fn, spec, lim, rate, -1);
+}
+extern "C" int dmx_limiter_check(const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate)
+{
+    return limiter_check("dmx_limiter_check", spec, lim, rate);
+}
+
+static size_t loud_encode_work_bytes(int nOut, int64_t n, bool meters)
+{
+    return (size_t)((nOut + 1) * (loud_workspace_bytes(n) + (meters ? meters_workspace_bytes(n) : 0)) + 64);
+}
+
+static int loud_encode_limit_device(const char *fn, int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                    const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                                    float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream, dmx_meters_result *d_meters,
+                                    const dmx_limiter_spec *lim, dmx_limit_result *d_limit)
+{
+    PcmGains G;
+    DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
+    DMXCHK(limiter_check(fn, loud, lim, rate));
+    if (((uintptr_t)d_limit & 7) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_limit must be 8-byte aligned", fn);
+    hipStream_t s = (hipStream_t)stream;
+    if (!(loud->mode & DMX_LOUD_LIMIT)) // the call as it was
+    {
+        DMXCHK(loud_encode_device(fn, device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks, d_report, d_work, stream,
+                                  d_meters));
+        if (d_limit)
+            HIPCHK(hipMemsetAsync(d_limit, 0, sizeof(dmx_limit_result) * (size_t)G.nOut, s));
+        return DMX_OK;
+    }
+    if (!d_planes || !d_out || !d_peaks || !d_mix || !d_report || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn,
+                    !d_planes ? "d_planes" : !d_out ? "d_out" : !d_peaks ? "d_peaks" : !d_mix ? "d_mix" : !d_report ? "d_report" : "d_work");
+    if (n < 1 || n >= (int64_t)1 << 36 || plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n <= plane_stride, n < 2^36)", fn, (long long)n,
+                    (long long)plane_stride);
+    if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_planes & 3) != 0 || ((uintptr_t)d_peaks & 3) != 0 || ((uintptr_t)d_mix & 3) != 0 ||
+        ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_report & 7) != 0 || ((uintptr_t)d_meters & 3) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_out and d_work must be 16-byte aligned, d_report 8-byte aligned, d_planes, d_mix, d_peaks and d_meters 4-byte aligned",
+                    fn);
+    LoudPlan lp;
+    if (loud_plan(rate, n, &lp) != 0)
+        return fail(DMX_ERR_ARG, "%s: no plan for rate %d, n %lld", fn, rate, (long long)n);
+    HIPCHK(hipSetDevice(device));
+    const float *T = nullptr;
+    DMXCHK(loud_table(device, &T));
+    LimJob job{};
+    DMXCHK(dmx_limiter_device_tables(device, &job.tables));
+    (void)lim_slopes(rate, lim ? (double)lim->attack_ms : kLimAttackMs, lim ? (double)lim->release_ms : kLimReleaseMs, &job.qa, &job.qr);
+    const int base = loud->mode & ~(DMX_LOUD_TRUE_PEAK | DMX_LOUD_LIMIT);
+    const bool byTp = (loud->mode & DMX_LOUD_TRUE_PEAK) != 0;
+    const i64 slotBytes = loud_workspace_bytes(n), envBytes = lim_workspace_bytes(n);
+    unsigned char *work = (unsigned char *)d_work;
+    float *gains = (float *)(work + (i64)(G.nOut + 1) * slotBytes);
+    unsigned char *limWork = work + (((i64)loud_encode_work_bytes(G.nOut, n, d_meters != nullptr) + 63) & ~(i64)63);
+    dmx_limit_result *limRes = (dmx_limit_result *)(limWork + (i64)G.nOut * envBytes);
+    HIPCHK(hipMemsetAsync(d_peaks, 0, sizeof(float) * (size_t)G.nOut, s));
+    LimitPiece pp;
+    static_cast<PcmPiece &>(pp) = PcmPiece{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
+                                           DMX_OUTPUT_STRIDE(n * dmx_pcm_frame_bytes(spec->encoding)), 0, n};
+    pp.mix = d_mix;
+    pp.gains = gains;
+    pp.gplane = (const float *)(limWork + lim_ws_gain_offset(n));
+    pp.gplaneStride = base == DMX_LOUD_MIXTURE ? 0 : envBytes / 4;
+    PcmGains M{}; // the mixture as a one-row table of its own: its slot is the last
+    M.nOut = 1, M.S = G.S;
+    M.g[0][G.S] = 1.0f;
+    launch_loud_measure(pp, G, lp, work, 0, nullptr, nullptr, s);
+    launch_loud_measure(pp, M, lp, work, G.nOut, nullptr, nullptr, s);
+    TpFilter f;
+    tp_filter(rate, &f);
+    if (d_meters)
+    {
+        unsigned *tp = (unsigned *)(work + (i64)(G.nOut + 1) * slotBytes + 64);
+        HIPCHK(hipMemsetAsync(tp, 0, sizeof(unsigned) * (size_t)(G.nOut + 1), s));
+        LoudPiece tq = pp;
+        tq.peaks = tp;
+        launch_true_peak(&tq, 1, G, f, s);
+        tq.peaks = tp + G.nOut;
+        launch_true_peak(&tq, 1, M, f, s);
+        launch_meters(work, 0, G.nOut + 1, lp, tp, d_meters, s);
+    }
+    // the gain without a ceiling (the peaks are zero: nothing to cap, nothing to scale); DMX_LOUD_UNITY: g = 1, as under MEASURE
+    launch_loud_gain(work, slotBytes, G.nOut, (unsigned *)d_peaks, base == DMX_LOUD_UNITY ? DMX_LOUD_MEASURE : base,
+                     (int)rintf(100.0f * loud->target_lufs), INFINITY, T, gains, d_report, s);
+    job.pc = pp, job.G = G;
+    job.gains = gains, job.gainImm = 1.0f, job.ceiling = loud->max_peak, job.link = base == DMX_LOUD_MIXTURE;
+    job.work = limWork, job.res = limRes;
+    launch_limit(job, f, byTp, s);
+    HIPCHK(hipMemcpy2DAsync(d_peaks, sizeof(float), &limRes->peak_out, sizeof(dmx_limit_result), sizeof(float), (size_t)G.nOut,
+                            hipMemcpyDeviceToDevice, s));
+    launch_limit_encode(&pp, 1, G, spec->encoding, spec->clip, s);
+    if (d_limit)
+        HIPCHK(hipMemcpyAsync(d_limit, limRes, sizeof(dmx_limit_result) * (size_t)G.nOut, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_loud_encode_limit_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                            const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                                            float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream,
+                                            dmx_meters_result *d_meters, const dmx_limiter_spec *lim, dmx_limit_result *d_limit)
+{
+    return loud_encode_limit_device("dmx_loud_encode_limit_device", device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out,
+                                    d_peaks, d_report, d_work, stream, d_meters, lim, d_limit);
+}
+
+extern "C" int dmx_loud_encode_limit(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                                     const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
+                                     dmx_meters_result *meters, const dmx_limiter_spec *lim, dmx_limit_result *limit)
+{
+    return loud_encode_limit_host("dmx_loud_encode_limit", device, planes, n_sources, n, mix, spec, loud, rate, out, peaks, report, meters, lim,
+                                  limit);
+}
+
+// host buffers: meters NULL or n_out + 1 entries, limit NULL or n_out entries
+static int loud_encode_limit_host(const char *fn, int device, const float *planes, int n_sources, int64_t n, const float *mix,
+                                  const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *out, float *peaks,
+                                  dmx_loudness_result *report, dmx_meters_result *meters, const dmx_limiter_spec *lim, dmx_limit_result *limit)
+{
+    PcmGains G;
+    DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
+    DMXCHK(limiter_check(fn, loud, lim, rate));
+    if (!planes || !out || !mix || n < 1 || n >= (int64_t)1 << 36)
+        return fail(DMX_ERR_ARG, "%s: invalid argument (null planes, mix or out pointer, n < 1 or n >= 2^36)", fn);
+    HIPCHK(hipSetDevice(device));
+    const int nOut = G.nOut;
+    const i64 bytes = n * dmx_pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
+    const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n, mixBytes = sizeof(float) * 2 * (size_t)n;
+    const size_t workBytes = ((loud_encode_work_bytes(nOut, n, meters != nullptr) + 63) & ~(size_t)63) +
+                             ((loud->mode & DMX_LOUD_LIMIT) ? (size_t)nOut * (size_t)(lim_workspace_bytes(n) + 64) : 0);
+    const size_t reportBytes = sizeof(dmx_loudness_result) * (size_t)(nOut + 1), metersBytes = sizeof(dmx_meters_result) * (size_t)(nOut + 1),
+                 limitBytes = sizeof(dmx_limit_result) * (size_t)nOut;
+    DevScratch d;
+    float *dIn = (float *)d.get(inBytes + DMX_OUTPUT_STRIDE(mixBytes)); // the planes, then the mixture
+    unsigned char *dOut = (unsigned char *)d.get((size_t)(nOut * devStride));
+    unsigned char *dSmall = (unsigned char *)d.get(256 + reportBytes + metersBytes + 16 + limitBytes); // the peaks, the reports
+    void *dWork = d.get(workBytes);
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    float *dMix = dIn + (size_t)n_sources * 2 * (size_t)n;
+    float *dPeaks = (float *)dSmall;
+    dmx_loudness_result *dReport = (dmx_loudness_result *)(dSmall + 256);
+    dmx_meters_result *dMeters = meters ? (dmx_meters_result *)(dSmall + 256 + reportBytes) : nullptr;
+    dmx_limit_result *dLimit = (dmx_limit_result *)(dSmall + ((256 + reportBytes + metersBytes + 15) & ~(size_t)15));
+    if (hipMemcpy(dIn, planes, inBytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dMix, mix, mixBytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(loud_encode_limit_device(fn, device, dIn, n_sources, n, n, dMix, spec, loud, rate, dOut, dPeaks, dReport, dWork, nullptr, dMeters, lim,
+                                    limit ? dLimit : nullptr));
+    DMXCHK(pcm_download(fn, out, peaks, dOut, dPeaks, nOut, bytes, devStride));
+    if ((report && hipMemcpy(report, dReport, reportBytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (meters && hipMemcpy(meters, dMeters, metersBytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (limit && hipMemcpy(limit, dLimit, limitBytes, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(DMX_ERR_HIP, "%s: download failed", fn);
     return DMX_OK;
 }

@@ -4,6 +4,7 @@
 #include "gemm_select.h"
 #include "loudness_plan.h"
 #include "meters_plan.h"
+#include "limiter_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -445,6 +446,38 @@ void launch_true_peak(const RemixPiece *pieces, int P, const PcmGains &G, const 
 // behind launch_loud_measure of nSignals signals in the slots slot0 ..: out[o] = {tp[o], lra_c, max_momentary_c, max_short_c},
 // nSignals entries of dmx_meters_result on the device. One launch.
 void launch_meters(const unsigned char *work, int slot0, int nSignals, const LoudPlan &lp, const unsigned *tp, void *out, hipStream_t s);
+// ---- the look-ahead peak limiter (limiter.hip; specification: DESIGN.md section 2.16, restated in tests/limiter_spec.py) ----
+// (the tables, the slopes and the workspace: limiter_plan.h)
+// one job: the envelopes over the G.nOut outputs of the piece's frames [0, pc.n), each output o under its gain (gains[o] on the
+// device, or gainImm where gains is null). link: one envelope over all outputs (DMX_LOUD_MIXTURE), else one per output; envelope
+// e uses the workspace work + e * lim_workspace_bytes(n). tables: the kLimTableWords words of lim_tables on the device. res:
+// G.nOut entries of dmx_limit_result on the device, zeroed here. f.F > 1: the level takes the interpolated phases
+// (DMX_LOUD_TRUE_PEAK) and res[o].true_peak_out is measured. Three launches, or four; marks: NULL, or five events around them.
+struct LimJob
+{
+    RemixPiece pc;
+    PcmGains G;
+    const float *gains;
+    float gainImm, ceiling;
+    int qa, qr, link;
+    unsigned char *work;
+    const int32_t *tables;
+    void *res;
+};
+void launch_limit(const LimJob &job, const TpFilter &f, bool truePeak, hipStream_t s, hipEvent_t *marks = nullptr);
+// launch_loud_encode with every gained sample multiplied by its frame's limiter gain before clip (pcm.hip): output o reads the
+// plane gplane + o * gplaneStride (fp32 per frame, 16-byte aligned; stride 0: the outputs share one plane)
+struct LimitPiece : LoudPiece
+{
+    const float *gplane;
+    i64 gplaneStride;
+};
+struct LimitTable
+{
+    static const int kMax = 32;
+    LimitPiece p[kMax];
+};
+void launch_limit_encode(const LimitPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
 // ---- the track path's converter (resample.hip) ----
 // outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
 // output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the

@@ -88,8 +88,10 @@ __device__ __forceinline__ void pcm_peak_body(const Table &t, const Gather &gath
 }
 
 // GAIN (the loudness stage): the gathered value is multiplied by the output's gain pc.gains[o], one
-// fp32 product per sample, before clip; pc.peaks[o] then holds the peak of the gained samples (loud_gain_kernel)
-template <int ENC, bool GAIN = false, class Table, class Gather>
+// fp32 product per sample, before clip; pc.peaks[o] then holds the peak of the gained samples (loud_gain_kernel). GAIN == 2 (the
+// limiter): that product is multiplied by the frame's gain from the plane pc.gplane, a second fp32
+// product; pc.peaks[o] then holds the peak of the limited samples
+template <int ENC, int GAIN = 0, class Table, class Gather>
 __device__ __forceinline__ void pcm_encode_body(const Table &t, int clip, const Gather &gather)
 {
     const auto &pc = t.p[blockIdx.z];
@@ -113,12 +115,20 @@ __device__ __forceinline__ void pcm_encode_body(const Table &t, int clip, const 
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             y[2 * k] = L[k], y[2 * k + 1] = R[k];
-        if constexpr (GAIN)
+        if constexpr (GAIN != 0)
         {
             const float gn = pc.gains[o];
 #pragma unroll
             for (int k = 0; k < 8; ++k)
                 y[k] = gn * y[k];
+        }
+        if constexpr (GAIN == 2)
+        {
+            float gl[4];
+            pcm_load4(pc.gplane + (i64)o * pc.gplaneStride, i, cnt, gl);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                y[k] = y[k] * gl[k >> 1];
         }
         if (clip == DMX_CLIP_CLAMP)
         {
@@ -213,7 +223,13 @@ __global__ __launch_bounds__(256) void remix_encode_kernel(RemixTable t, PcmGain
 template <int ENC>
 __global__ __launch_bounds__(256) void loud_encode_kernel(LoudTable t, PcmGains G, int clip)
 {
-    pcm_encode_body<ENC, true>(t, clip, GatherRemix{G});
+    pcm_encode_body<ENC, 1>(t, clip, GatherRemix{G});
+}
+// and behind the limiter's gain plane: grid (blocks, G.nOut, pieces)
+template <int ENC>
+__global__ __launch_bounds__(256) void limit_encode_kernel(LimitTable t, PcmGains G, int clip)
+{
+    pcm_encode_body<ENC, 2>(t, clip, GatherRemix{G});
 }
 
 namespace
@@ -287,6 +303,17 @@ void launch_loud_encode(const LoudPiece *pieces, int P, const PcmGains &G, int e
             hipLaunchKernelGGL(loud_encode_kernel<DMX_PCM_S16>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
         else
             hipLaunchKernelGGL(loud_encode_kernel<DMX_PCM_S24>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+    });
+}
+void launch_limit_encode(const LimitPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s)
+{
+    pcm_for_tables<LimitTable>(pieces, P, [&](const LimitTable &t, int nt, int gx) {
+        if (encoding == DMX_PCM_F32)
+            hipLaunchKernelGGL(limit_encode_kernel<DMX_PCM_F32>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+        else if (encoding == DMX_PCM_S16)
+            hipLaunchKernelGGL(limit_encode_kernel<DMX_PCM_S16>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
+        else
+            hipLaunchKernelGGL(limit_encode_kernel<DMX_PCM_S24>, dim3(gx, G.nOut, nt), dim3(256), 0, s, t, G, clip);
     });
 }
 

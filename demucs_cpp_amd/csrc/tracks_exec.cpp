@@ -138,14 +138,32 @@ struct PcmOut // the output spec of a call, checked (dmx_pcm_check_spec)
     const float *loudTable;
     // dmx_tracks_infer_meters: the meters report, n_out + 1 entries per track; else NULL
     dmx_meters_result *meters;
-    int loudMode() const { return loud->mode & ~DMX_LOUD_TRUE_PEAK; }
+    // dmx_tracks_infer_limit: the limiter's times (NULL: the defaults), its report of n_out entries per
+    // track (or NULL) and the device's tables; read only with DMX_LOUD_LIMIT in the mode
+    const dmx_limiter_spec *lim;
+    dmx_limit_result *limit;
+    const int32_t *limTables;
+    int loudMode() const { return loud->mode & ~(DMX_LOUD_TRUE_PEAK | DMX_LOUD_LIMIT); }
     bool byTruePeak() const { return loud && (loud->mode & DMX_LOUD_TRUE_PEAK) != 0; }
-    bool truePeaks() const { return byTruePeak() || meters; } // the slot holds true peaks and a meters report behind the loudness report
-    bool gained() const { return loud && loudMode() != DMX_LOUD_MEASURE; }
+    bool limited() const { return loud && (loud->mode & DMX_LOUD_LIMIT) != 0; }
+    // the slot holds true peaks and a meters report behind the loudness report; the limiter's level needs no true peak of the track
+    bool truePeaks() const { return (byTruePeak() && !limited()) || meters; }
+    bool gained() const { return loud && loudMode() != DMX_LOUD_MEASURE; } // DMX_LOUD_UNITY too: a whole-track, limited
     // in a slot's loudness buffer behind the n_out + 1 workspaces of a track of n frames: 64 bytes of gains, the loudness report,
     // and with truePeaks() 64 bytes of true peaks and the meters report
     i64 loudTail(i64 n) const { return (i64)(nOut + 1) * loud_workspace_bytes(n); }
     i64 tpOffset(i64 n) const { return loudTail(n) + 64 + (i64)sizeof(dmx_loudness_result) * (nOut + 1); }
+    // with limited(), behind all that at a multiple of 64: the envelopes' workspaces (one under DMX_LOUD_MIXTURE, else n_out) and
+    // then the n_out results
+    int limEnvs() const { return loudMode() == DMX_LOUD_MIXTURE ? 1 : nOut; }
+    i64 limOffset(i64 n) const { return (tpOffset(n) + (meters ? 64 + (i64)sizeof(dmx_meters_result) * (nOut + 1) : 0) + 63) & ~(i64)63; }
+    i64 limResOffset(i64 n) const { return limOffset(n) + (i64)limEnvs() * lim_workspace_bytes(n); }
+    i64 loudBytes(i64 n) const
+    {
+        if (limited())
+            return limResOffset(n) + 64 * (i64)nOut;
+        return tpOffset(n) + (truePeaks() ? 64 + (i64)sizeof(dmx_meters_result) * (nOut + 1) : 0);
+    }
 };
 // One call of the track path. shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches
 // track_ola_kernel and N >= 2 track_ola_ens_kernel; a bag launches track_ola_bag_kernel.
@@ -192,6 +210,7 @@ struct TracksRun
     std::vector<ResamplePiece> conv;        // the converter's, of one ratio
     std::vector<LoudPlan> loudPlans;        // per track, made before the first batch (host arithmetic)
     std::vector<LoudPiece> loudEnc;         // the whole tracks of a batch, each with its gains
+    std::vector<LimitPiece> limitEnc;       // the same behind the limiter, each with its gain planes
 
     const dmx_ctx::TrackSlot &slot(int t) const { return c->slots[(size_t)plan.jobs[(size_t)t].slot]; }
 };
@@ -229,9 +248,7 @@ static int tracks_prepare(TracksRun &r)
             DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(omax * pcm->frameBytes) / 4)));
             DMXCHK(dmx_ensure_buf(sl.peaks, 8));
             if (pcm->loud)
-                DMXCHK(dmx_ensure_buf(sl.loud, ((pcm->nOut + 1) * (loud_workspace_bytes(omax) + (i64)sizeof(dmx_loudness_result)) + 64 +
-                                                (pcm->truePeaks() ? 64 + (i64)sizeof(dmx_meters_result) * (pcm->nOut + 1) : 0)) /
-                                                   4));
+                DMXCHK(dmx_ensure_buf(sl.loud, (pcm->loudBytes(omax) + 3) / 4));
             if (pcm->flacBits)
             {
                 DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, omax) / 4)));
@@ -455,8 +472,9 @@ static int tracks_output_stage(TracksRun &r, int k)
     {
         // behind a track's last piece: its outputs and its mixture are measured, and one launch turns lufs_c and the peaks into
         // the gains, the gained peaks and the report; the gained tracks are whole-track ones, encoded here with their gains
-        launch_remix_peak(r.pieces.data(), (int)r.pieces.size(), *pcm->remix, s);
-        r.loudEnc.clear();
+        if (!pcm->limited()) // (the limiter measures the peaks of what it leaves: the peak kernel is not needed)
+            launch_remix_peak(r.pieces.data(), (int)r.pieces.size(), *pcm->remix, s);
+        r.loudEnc.clear(), r.limitEnc.clear();
         PcmGains M{}; // the mixture as a one-row table: its slot is the last
         M.nOut = 1, M.S = pcm->remix->S;
         M.g[0][M.S] = 1.0f;
@@ -489,6 +507,34 @@ static int tracks_output_stage(TracksRun &r, int k)
                     launch_meters(work, 0, pcm->nOut + 1, lp, tp, tp + 16, s);
                 }
             }
+            if (pcm->limited())
+            {
+                // the gain without a ceiling (DMX_LOUD_UNITY: 1, as under MEASURE), then the limiter under that gain: its
+                // envelopes, the limited peaks in place of the gained ones, and the results
+                const int rate = r.rates ? r.rates[g.t] : 44100, base = pcm->loudMode();
+                launch_loud_gain(work, slotBytes, pcm->nOut, pp.peaks, base == DMX_LOUD_UNITY ? DMX_LOUD_MEASURE : base,
+                                 (int)rintf(100.0f * pcm->loud->target_lufs), INFINITY, pcm->loudTable, gains, gains + 16, s);
+                LimJob job{};
+                (void)lim_slopes(rate, pcm->lim ? (double)pcm->lim->attack_ms : kLimAttackMs, pcm->lim ? (double)pcm->lim->release_ms : kLimReleaseMs,
+                                 &job.qa, &job.qr);
+                const i64 envBytes = lim_workspace_bytes(lp.n);
+                unsigned char *limWork = work + pcm->limOffset(lp.n);
+                dmx_limit_result *limRes = (dmx_limit_result *)(work + pcm->limResOffset(lp.n));
+                job.pc = pp, job.G = *pcm->remix, job.gains = gains, job.gainImm = 1.0f, job.ceiling = pcm->loud->max_peak;
+                job.link = base == DMX_LOUD_MIXTURE, job.work = limWork, job.tables = pcm->limTables, job.res = limRes;
+                TpFilter f;
+                tp_filter(rate, &f);
+                launch_limit(job, f, pcm->byTruePeak(), s);
+                HIPCHK(hipMemcpy2DAsync(pp.peaks, sizeof(float), &limRes->peak_out, sizeof(dmx_limit_result), sizeof(float), (size_t)pcm->nOut,
+                                        hipMemcpyDeviceToDevice, s));
+                LimitPiece mq;
+                static_cast<RemixPiece &>(mq) = pp;
+                mq.gains = gains;
+                mq.gplane = (const float *)(limWork + lim_ws_gain_offset(lp.n));
+                mq.gplaneStride = job.link ? 0 : envBytes / 4;
+                r.limitEnc.push_back(mq);
+                continue;
+            }
             if (pcm->byTruePeak())
                 launch_loud_gain_tp(work, slotBytes, pcm->nOut, pp.peaks, tp, pcm->loudMode(), (int)rintf(100.0f * pcm->loud->target_lufs),
                                     pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
@@ -500,7 +546,9 @@ static int tracks_output_stage(TracksRun &r, int k)
             lq.gains = gains;
             r.loudEnc.push_back(lq);
         }
-        if (pcm->gained())
+        if (pcm->limited())
+            launch_limit_encode(r.limitEnc.data(), (int)r.limitEnc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
+        else if (pcm->gained())
             launch_loud_encode(r.loudEnc.data(), (int)r.loudEnc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
         else
             launch_remix_encode(enc.data(), (int)enc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
@@ -575,6 +623,10 @@ static int tracks_copy_pcm(TracksRun &r, int k, const PcmRange &g)
         HIPCHK(hipMemcpyAsync(pcm->report + (size_t)g.t * (pcm->nOut + 1),
                               (const unsigned char *)sl.loud.p + (size_t)((pcm->nOut + 1) * loud_workspace_bytes(n) + 64),
                               sizeof(dmx_loudness_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
+    if (last && pcm->limit && pcm->limited()) // the limiter's results
+        HIPCHK(hipMemcpyAsync(pcm->limit + (size_t)g.t * pcm->nOut,
+                              (const unsigned char *)sl.loud.p + (size_t)pcm->limResOffset(n),
+                              sizeof(dmx_limit_result) * (size_t)pcm->nOut, hipMemcpyDeviceToHost, c->copyStream));
     if (last && pcm->meters) // and the meters report
         HIPCHK(hipMemcpyAsync(pcm->meters + (size_t)g.t * (pcm->nOut + 1), (const unsigned char *)sl.loud.p + (size_t)(pcm->tpOffset(n) + 64),
                               sizeof(dmx_meters_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
@@ -843,6 +895,8 @@ struct TracksCall
     const dmx_loudness_spec *loud; // dmx_tracks_infer_loud: the loudness stage behind a remix spec, and its report; else NULL
     dmx_loudness_result *report;
     dmx_meters_result *meters;   // dmx_tracks_infer_meters: the meters report, or NULL
+    const dmx_limiter_spec *lim; // dmx_tracks_infer_limit: the limiter's times (NULL: the defaults) and its report, or NULL
+    dmx_limit_result *limit;
     const dmx_flac_info *flacIn; // dmx_tracks_infer_from_flac: audio[t] is a file image, described here; else NULL
     const int64_t *fileBytes;
     int64_t *trackStatus;
@@ -1190,6 +1244,11 @@ static int tracks_call(const TracksCall &a)
             HIPCHK(hipMemcpy(a.c->dLoudTable, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
         }
         pcm.loudTable = a.c->dLoudTable;
+        pcm.lim = a.lim, pcm.limit = a.limit;
+        if (pcm.limited())
+            DMXCHK(dmx_limiter_device_tables(a.c->m->device, &pcm.limTables));
+        else if (a.limit) // nothing is limited: the report says so
+            std::memset(a.limit, 0, sizeof(dmx_limit_result) * (size_t)a.n_tracks * (size_t)pcm.nOut);
     }
     // (track, copy) order; with models (track, model, copy) order
     const std::vector<int> shifts = draw_shifts(a.bag ? a.n_tracks * a.n_models : a.n_tracks, a.n_shifts, a.shift_offsets);
@@ -1284,7 +1343,8 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
                             int n_tracks, const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
                             const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes, float *peaks,
                             int64_t *track_status, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud = nullptr,
-                            dmx_loudness_result *report = nullptr, dmx_meters_result *meters = nullptr)
+                            dmx_loudness_result *report = nullptr, dmx_meters_result *meters = nullptr, const dmx_limiter_spec *lim = nullptr,
+                            dmx_limit_result *limit = nullptr)
 {
     if (n_tracks < 1)
         return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
@@ -1310,7 +1370,7 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
         rates[(size_t)t] = infos[(size_t)t].sample_rate;
     }
     for (int t = 0; loud && t < n_tracks; ++t) // the loudness stage's own floor on a rate, with the track's number
-        DMXCHK(dmx_loud_check_spec(fn, loud, rates[(size_t)t], t));
+        DMXCHK(dmx_limit_check_spec(fn, loud, lim, rates[(size_t)t], t));
     if (anyRate)
         DMXCHK(check_tracks_rates(fn, n_tracks, ns.data(), rates.data(), flac_out != 0));
     TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
@@ -1320,7 +1380,7 @@ static int tracks_from_flac(const char *fn, bool anyRate, dmx_ctx *c, const dmx_
     a.n_tracks = n_tracks, a.audio = reinterpret_cast<const float *const *>(files), a.n = ns.data();
     a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.flacIn = infos.data(), a.fileBytes = file_bytes, a.trackStatus = track_status;
-    a.loud = loud, a.report = report, a.meters = meters;
+    a.loud = loud, a.report = report, a.meters = meters, a.lim = lim, a.limit = limit;
     a.out = out, a.peaks = peaks, a.layout = DMX_LAYOUT_EIGEN, a.progress = progress, a.user = user;
     DMXCHK(tracks_call(a)); // (track_status: -1 until the track's own arrives)
     for (int t = 0; t < n_tracks; ++t)
@@ -1375,15 +1435,15 @@ static int tracks_infer_loud(const char *fn, dmx_ctx *c, const dmx_model *const 
                              const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
                              const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes, float *peaks,
                              int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud, dmx_loudness_result *report,
-                             dmx_meters_result *meters)
+                             dmx_meters_result *meters, const dmx_limiter_spec *lim = nullptr, dmx_limit_result *limit = nullptr)
 {
     if (n_tracks < 1)
         return fail(DMX_ERR_ARG, "%s: n_tracks must be >= 1, got %d", fn, n_tracks);
     if (!spec)
         return fail(DMX_ERR_ARG, "%s: the loudness stage needs a remix spec", fn);
-    DMXCHK(dmx_loud_check_spec(fn, loud, 44100, -1));
+    DMXCHK(dmx_limit_check_spec(fn, loud, lim, 44100, -1));
     for (int t = 0; rates && t < n_tracks; ++t) // the loudness stage's own floor on a rate, with the track's number
-        DMXCHK(dmx_loud_check_spec(fn, loud, rates[t], t));
+        DMXCHK(dmx_limit_check_spec(fn, loud, lim, rates[t], t));
     if (rates)
         DMXCHK(check_tracks_rates(fn, n_tracks, n, rates, flac_out != 0));
     TracksCall a = remix_call(fn, c, models, n_models, weights, spec);
@@ -1391,7 +1451,7 @@ static int tracks_infer_loud(const char *fn, dmx_ctx *c, const dmx_model *const 
     a.flacRate = 44100, a.flacSizes = sizes, a.rates = rates;
     a.n_tracks = n_tracks, a.audio = audio, a.n = n, a.n_shifts = n_shifts, a.overlap = overlap, a.shift_offsets = shift_offsets;
     a.out = out, a.peaks = peaks, a.layout = layout, a.progress = progress, a.user = user;
-    a.loud = loud, a.report = report, a.meters = meters;
+    a.loud = loud, a.report = report, a.meters = meters, a.lim = lim, a.limit = limit;
     return tracks_call(a);
 }
 
@@ -1423,7 +1483,7 @@ extern "C" int dmx_tracks_infer_from_flac_meters(dmx_ctx *c, const dmx_model *co
                                                  const dmx_loudness_spec *loud, dmx_loudness_result *report, dmx_meters_result *meters)
 {
     const char *fn = "dmx_tracks_infer_from_flac_meters";
-    DMXCHK(dmx_loud_check_spec(fn, loud, 44100, -1));
+    DMXCHK(dmx_limit_check_spec(fn, loud, nullptr, 44100, -1));
     return tracks_from_flac(fn, true, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts, overlap, shift_offsets, spec,
                             flac_out, out, sizes, peaks, track_status, progress, user, loud, report, meters);
 }
@@ -1435,7 +1495,32 @@ extern "C" int dmx_tracks_infer_from_flac_loud(dmx_ctx *c, const dmx_model *cons
                                                const dmx_loudness_spec *loud, dmx_loudness_result *report)
 {
     const char *fn = "dmx_tracks_infer_from_flac_loud";
-    DMXCHK(dmx_loud_check_spec(fn, loud, 44100, -1));
+    DMXCHK(dmx_limit_check_spec(fn, loud, nullptr, 44100, -1));
     return tracks_from_flac(fn, true, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts, overlap, shift_offsets, spec,
                             flac_out, out, sizes, peaks, track_status, progress, user, loud, report);
+}
+
+// the two calls above with the limiter: its times and its report
+extern "C" int dmx_tracks_infer_limit(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                      const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                                      const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                                      float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                                      dmx_loudness_result *report, dmx_meters_result *meters, const dmx_limiter_spec *lim,
+                                      dmx_limit_result *limit)
+{
+    return tracks_infer_loud("dmx_tracks_infer_limit", c, models, n_models, weights, n_tracks, audio, n, rates, n_shifts, overlap,
+                             shift_offsets, spec, flac_out, out, sizes, peaks, layout, progress, user, loud, report, meters, lim, limit);
+}
+
+extern "C" int dmx_tracks_infer_from_flac_limit(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                                const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                                const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                                int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
+                                                const dmx_loudness_spec *loud, dmx_loudness_result *report, dmx_meters_result *meters,
+                                                const dmx_limiter_spec *lim, dmx_limit_result *limit)
+{
+    const char *fn = "dmx_tracks_infer_from_flac_limit";
+    DMXCHK(dmx_limit_check_spec(fn, loud, lim, 44100, -1));
+    return tracks_from_flac(fn, true, c, models, n_models, weights, n_tracks, files, file_bytes, n_shifts, overlap, shift_offsets, spec,
+                            flac_out, out, sizes, peaks, track_status, progress, user, loud, report, meters, lim, limit);
 }

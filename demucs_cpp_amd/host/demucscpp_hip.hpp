@@ -436,6 +436,8 @@ inline PcmOutputs demucs_inference_batch_pcm(const demucs_model &model, const st
 // what remix_options::loudness.meters receives (dmx_tracks_infer_meters): per track the library's n_out + 1 entries, the outputs
 // and then the mixture
 using MetersReport = std::vector<std::vector<dmx_meters_result>>;
+// what remix_options::loudness.limit_report receives (dmx_tracks_infer_limit): per track the library's n_out entries
+using LimitReport = std::vector<std::vector<dmx_limit_result>>;
 // Outputs mixed on the GPU from the stems and the original mixture (dmx_tracks_infer_remix; include/demucs_hip.h
 // dmx_remix_spec): output o is names[o], its row of gains is gains[o * (nb_sources + 1) ...], the last entry of a row the
 // gain of the mixture. The defaults are demucs's: 16 bit, rescale.
@@ -466,6 +468,12 @@ struct remix_options
         float target_lufs = -14.0f, max_peak = 0.8912509f;
         bool true_peak = false;
         MetersReport *meters = nullptr;
+        // the look-ahead peak limiter (DMX_LOUD_LIMIT): the ceiling no longer lowers the gain, the limiter
+        // holds max_peak. With mode DMX_LOUD_UNITY it is the limiter without loudnorm. attack_ms / release_ms: the times in which
+        // the reduction moves by 10 dB. limit_report: null, or where the call leaves the limiter's report, per track n_out entries.
+        bool limit = false;
+        float attack_ms = DMX_LIMIT_ATTACK_MS, release_ms = DMX_LIMIT_RELEASE_MS;
+        LimitReport *limit_report = nullptr;
     };
     loudness_options loudness;
 };
@@ -622,7 +630,17 @@ inline void loudness_report_cut(const remix_options &ro, const std::vector<dmx_l
 // the loudness spec of a call, and the flat meters report it fills (empty: none asked for), cut per track behind the call
 inline dmx_loudness_spec loudness_spec_of(const remix_options &ro)
 {
-    return dmx_loudness_spec{ro.loudness.mode | (ro.loudness.true_peak ? DMX_LOUD_TRUE_PEAK : 0), ro.loudness.target_lufs, ro.loudness.max_peak};
+    return dmx_loudness_spec{ro.loudness.mode | (ro.loudness.true_peak ? DMX_LOUD_TRUE_PEAK : 0) | (ro.loudness.limit ? DMX_LOUD_LIMIT : 0),
+                             ro.loudness.target_lufs, ro.loudness.max_peak};
+}
+inline dmx_limiter_spec limiter_spec_of(const remix_options &ro) { return dmx_limiter_spec{ro.loudness.attack_ms, ro.loudness.release_ms}; }
+inline void limit_report_cut(const remix_options &ro, const std::vector<dmx_limit_result> &rep, size_t T, int n_out)
+{
+    if (!ro.loudness.on || !ro.loudness.limit_report)
+        return;
+    ro.loudness.limit_report->assign(T, std::vector<dmx_limit_result>());
+    for (size_t t = 0; t < T; ++t)
+        (*ro.loudness.limit_report)[t].assign(rep.begin() + (std::ptrdiff_t)(t * (size_t)n_out), rep.begin() + (std::ptrdiff_t)((t + 1) * (size_t)n_out));
 }
 inline void meters_report_cut(const remix_options &ro, const std::vector<dmx_meters_result> &rep, size_t T, int n_out)
 {
@@ -665,12 +683,14 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
     const dmx_loudness_spec lspec = loudness_spec_of(ro);
     std::vector<dmx_loudness_result> rep(ro.loudness.on ? (size_t)T * (size_t)(spec.n_out + 1) : 0);
     std::vector<dmx_meters_result> mrep(ro.loudness.on && ro.loudness.meters ? rep.size() : 0);
+    const dmx_limiter_spec lim = limiter_spec_of(ro);
+    std::vector<dmx_limit_result> lrep(ro.loudness.on && ro.loudness.limit_report ? (size_t)T * (size_t)spec.n_out : 0);
     auto run = [&]() -> int {
-        if (ro.loudness.on) // (a null meters report: dmx_tracks_infer_loud)
-            return dmx_tracks_infer_meters(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates ? rates->data() : nullptr, opts.shifts,
+        if (ro.loudness.on) // (null meters and limiter reports: dmx_tracks_infer_loud)
+            return dmx_tracks_infer_limit(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates ? rates->data() : nullptr, opts.shifts,
                                            opts.overlap, shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr,
                                            y.pk.data(), DMX_LAYOUT_EIGEN, progress_thunk, &th, &lspec, rep.data(),
-                                           mrep.empty() ? nullptr : mrep.data());
+                                           mrep.empty() ? nullptr : mrep.data(), &lim, lrep.empty() ? nullptr : lrep.data());
         if (rates)
             return dmx_tracks_infer_rates(g.c, g.models, g.Q, g.w, T, x.in.data(), x.n.data(), rates->data(), opts.shifts, opts.overlap, shifts.data(),
                                           &spec, ro.flac ? 1 : 0, y.dst.data(), ro.flac ? y.sizes.data() : nullptr, y.pk.data(), DMX_LAYOUT_EIGEN,
@@ -685,6 +705,7 @@ inline PcmOutputs remix_call(const char *who, const Target &g, const std::vector
         die(who);
     loudness_report_cut(ro, rep, tracks.size(), spec.n_out, report);
     meters_report_cut(ro, mrep, tracks.size(), spec.n_out);
+    limit_report_cut(ro, lrep, tracks.size(), spec.n_out);
     return y.cut(peaks, ro.flac);
 }
 // the same on tracks given as the images of .flac files (dmx_tracks_infer_from_flac): ro.flac chooses the output form.
@@ -725,11 +746,14 @@ inline PcmOutputs flac_files_call(const char *who, const Target &g, const std::v
     const dmx_loudness_spec lspec = loudness_spec_of(ro);
     std::vector<dmx_loudness_result> rep(ro.loudness.on ? T * (size_t)(spec.n_out + 1) : 0);
     std::vector<dmx_meters_result> mrep(ro.loudness.on && ro.loudness.meters ? rep.size() : 0);
+    const dmx_limiter_spec lim = limiter_spec_of(ro);
+    std::vector<dmx_limit_result> lrep(ro.loudness.on && ro.loudness.limit_report ? T * (size_t)spec.n_out : 0);
     if (!g.c || !level.ok ||
         (ro.loudness.on
-             ? dmx_tracks_infer_from_flac_meters(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap,
+             ? dmx_tracks_infer_from_flac_limit(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(), opts.shifts, opts.overlap,
                                                  shifts.data(), &spec, ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(), status.data(),
-                                                 progress_thunk, &th, &lspec, rep.data(), mrep.empty() ? nullptr : mrep.data())
+                                                 progress_thunk, &th, &lspec, rep.data(), mrep.empty() ? nullptr : mrep.data(), &lim,
+                                                lrep.empty() ? nullptr : lrep.data())
              : (rates ? dmx_tracks_infer_from_flac_rates : dmx_tracks_infer_from_flac)(g.c, g.models, g.Q, g.w, (int)T, in.data(), bytes.data(),
                                                                                        opts.shifts, opts.overlap, shifts.data(), &spec,
                                                                                        ro.flac ? 1 : 0, y.dst.data(), y.sizes.data(), y.pk.data(),
@@ -737,6 +761,7 @@ inline PcmOutputs flac_files_call(const char *who, const Target &g, const std::v
         die(who);
     loudness_report_cut(ro, rep, T, spec.n_out, report);
     meters_report_cut(ro, mrep, T, spec.n_out);
+    limit_report_cut(ro, lrep, T, spec.n_out);
     if (frames)
         *frames = n;
     return y.cut(peaks, ro.flac);

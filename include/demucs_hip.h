@@ -470,6 +470,125 @@ extern "C"
                                const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
                                dmx_meters_result *meters);
 
+    /* ---- look-ahead peak limiter (csrc/limiter.hip; DESIGN.md section 2.16, restated in tests/limiter_spec.py; no reference
+     * counterpart): holds a stereo signal under a ceiling c by shaping its peaks, where the ceiling rule of the section on
+     * loudness lowers the whole signal's gain. The stage is exact: the same bits as the specification, whatever the cut into
+     * tiles. All that depends on time runs in integers in the log domain, one octave being U = 65536 units; only maxima
+     * carry state, and a maximum has no order.
+     * Tables, made on the host in binary64 with libm: LUT[k] = ceil(U log2(1 + (k + 1) / 4096)) + 2, k = 0 .. 4095 (int32: the
+     * logarithm rounded up, with two units of slack for the fp32 roundings below); THI[a] = 2^(-a / 16), a = 0 .. 384, and
+     * TLO[b] = 2^(-b / 65536), b = 0 .. 4095 (float), both rounded TOWARDS ZERO.
+     * Gain of a reduction D (units, 0 <= D <= 24 U): G(D) = THI[D >> 12] * TLO[D & 4095], one fp32 product. G(0) == 1
+     * exactly, and G is non-increasing (checked by exhaustion, tests/test_limiter_cpu.py).
+     * Level: p[j] = max over the two channels of |g x[c][j]|, g x the fp32 product; a NaN sample is ignored by the detector
+     * and stays NaN in the output. With true_peak, p[j] also takes |g y_p[j]| for the F - 1 interpolated phases y_p of the
+     * section on meters at frame j: the same taps, the same order of operations, zeros outside [0, n).
+     * Required reduction: where p[j] > c, M[j] = min(U e + LUT[m >> 11], 24 U), with e the unbiased exponent and m the 23
+     * mantissa bits of the correctly rounded fp32 quotient p[j] / c; else M[j] = 0. p G(M) <= c for p / c < 2^24.
+     * Envelope: D[i] = max(0, max over j <= i of M[j] - qr (i - j), max over j >= i of M[j] - qa (j - i)): a linear-in-dB
+     * attack with unlimited look-ahead and a linear-in-dB release. Slopes: attack_ms and release_ms are the times in which
+     * the reduction moves by 10 dB, q = clamp(rint(U log2(10^0.5) 1000 / (ms rate)), 1, 2^20) in binary64; both times finite
+     * and in [0.1, 10000]; defaults 5 and 100.
+     * Apply: y = (g x[c][j]) G(D[j]), two fp32 products in that order. Where D[j] == 0 the second factor is exactly 1: a
+     * signal that never exceeds c leaves unchanged. For finite samples with p / c < 2^24, peak_out <= c holds exactly.
+     * true_peak_out is the true peak of the limited signal; the gain moves from sample to sample and changes the inter-sample
+     * crests, so true_peak_out is NOT guaranteed to stay under c (DESIGN.md section 2.16 gives the figures on the fixtures).
+     * Behind the loudness stage: DMX_LOUD_LIMIT, OR-ed into dmx_loudness_spec.mode (the struct stays as it is), and the mode
+     * DMX_LOUD_UNITY. With the flag the ceiling rule of the section on loudness no longer lowers g: g = T[k + 6000] always, and
+     * g = 1 when unmeasurable; the limiter holds max_peak instead. DMX_LOUD_UNITY is the limiter without loudnorm: the outputs are
+     * measured and reported as under DMX_LOUD_MEASURE, g = 1. Linking: stereo is always linked (the max over the channels);
+     * DMX_LOUD_MIXTURE has one envelope for the call, from the largest p[j] over its outputs, so that the outputs keep their
+     * balance at every instant; DMX_LOUD_EACH and DMX_LOUD_UNITY have one envelope per output. DMX_LOUD_TRUE_PEAK makes the
+     * level the true-peak one. The peaks a call returns are then peak_out, the exact maximum over the limited samples, which
+     * is what DMX_CLIP_RESCALE divides by. Every entry point that takes a loudness spec accepts the flag and the mode; those
+     * of the sections above (`_loud`, `_meters`) are the `_limit` ones of this section with both new arguments NULL (the default
+     * times, no limiter report), and without the flag they enqueue exactly what they enqueued. dmx_loudness_check alone keeps
+     * the contract of the section on meters - it answers for the modes of that section and refuses 0x200 and 3 - and
+     * dmx_limiter_check is the validator that knows the limiter; both run the same checks. Out of scope: the engine. */
+#define DMX_LOUD_UNITY 3
+#define DMX_LOUD_LIMIT 0x200
+#define DMX_LIMIT_ATTACK_MS 5.0f
+#define DMX_LIMIT_RELEASE_MS 100.0f
+    typedef struct dmx_limiter_spec
+    {
+        float attack_ms;  /* finite, in [0.1, 10000] */
+        float release_ms; /* idem */
+    } dmx_limiter_spec;
+    typedef struct dmx_limit_result
+    {
+        float peak_out;         /* the largest |y| of the limited samples, NaN ignored */
+        float true_peak_out;    /* the true peak of the limited signal; 0 unless true_peak */
+        int32_t max_reduction;  /* the largest D, in units */
+        int64_t limited_frames; /* frames with D > 0 */
+    } dmx_limit_result;
+    /* LUT (4096 int32), THI (385 floats), TLO (4096 floats). Pure host function. */
+    int dmx_limiter_tables(int32_t *lut, float *thi, float *tlo);
+    /* the slopes qa and qr in units per frame. Pure host function; DMX_ERR_ARG, with a message that names the field, for
+     * rate < 1 and for a time that is not finite or outside [0.1, 10000]. */
+    int dmx_limiter_slopes(int rate, double attack_ms, double release_ms, int32_t *qa, int32_t *qr);
+    /* bytes of device workspace for ONE envelope over n frames: 8 n4 + 64 per tile of 2048 frames, n4 = n rounded up to a
+     * multiple of 4. M lies at byte 0 as int32 [n], the gain plane G(D) at byte 4 n4 as float [n], the tiles' aggregates
+     * behind them. A multiple of 16. Pure host function; -1 for n < 1. */
+    int64_t dmx_limiter_workspace_bytes(int64_t n);
+    /* limits one signal on device memory under the gain `gain` and the ceiling max_peak (> 0, finite), asynchronous on
+     * `stream`: three launches (detect, carry, envelope), and a fourth with true_peak != 0 (the limited signal's true peak). d_x
+     * as dmx_loudness_device takes it; lim NULL: the default times. d_result: one entry ON THE DEVICE; d_work: 16-byte aligned,
+     * the bytes above, and holds M and the gain plane afterwards. 1 <= n < 2^36. The first call on a device uploads one copy
+     * of the tables (34 KB, a blocking copy) that stays for the life of the process. */
+    int dmx_limit_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, float gain, float max_peak,
+                         int true_peak, const dmx_limiter_spec *lim, dmx_limit_result *d_result, void *d_work, void *stream);
+    /* measurement (tools/limiter_bench.py): the call above, synchronised, with the times of its launches between HIP events in
+     * ms[0..4) (detect, carry, envelope, the true peak of the limited signal: 0 without true_peak) and, in ms[4], the peak
+     * kernel's time on the same signal */
+    int dmx_limit_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, float gain, float max_peak,
+                               int true_peak, const dmx_limiter_spec *lim, dmx_limit_result *d_result, void *d_work, void *stream,
+                               float *ms);
+    /* the same on host buffers: x planar [2][n] or (interleaved != 0) [n][2]; m NULL or n int32 (M); gain_plane NULL or n
+     * floats (G(D)) */
+    int dmx_limit(int device, const float *x, int64_t n, int interleaved, int rate, float gain, float max_peak, int true_peak,
+                  const dmx_limiter_spec *lim, int32_t *m, float *gain_plane, dmx_limit_result *result);
+
+    /* validates a loudness spec that may carry DMX_LOUD_LIMIT or be DMX_LOUD_UNITY, and the limiter's times (lim NULL: the
+     * defaults), for a signal at `rate`. Pure host function. Rejected, each with a message that names the field: what
+     * dmx_loudness_check rejects (the mode message lists the new values); DMX_LOUD_LIMIT with DMX_LOUD_MEASURE and
+     * DMX_LOUD_UNITY without DMX_LOUD_LIMIT ("mode"); DMX_LOUD_LIMIT with max_peak = +inf ("max_peak"); a bad time
+     * ("attack_ms", "release_ms"). */
+    int dmx_limiter_check(const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate);
+    /* dmx_loud_encode_meters_device plus the limiter: d_meters may be NULL here; lim NULL: the default times; d_limit NULL or
+     * n_out entries on the device. Without DMX_LOUD_LIMIT in the mode the call enqueues exactly what
+     * dmx_loud_encode_device resp. dmx_loud_encode_meters_device enqueues and d_limit is zeroed. With it: the measurements
+     * (and meters) as before, the gain launch without a ceiling, the limiter's three or four launches over one envelope
+     * (DMX_LOUD_MIXTURE) or n_out, and the encode launch that reads the gain plane; the peak kernel is not needed and not
+     * launched. d_work: the bytes of the call without the limiter, rounded up to 64, plus n_out x
+     * dmx_limiter_workspace_bytes(n) + 64 x n_out bytes. The first call on a device uploads the limiter's tables (34 KB). */
+    int dmx_loud_encode_limit_device(int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
+                                     const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
+                                     float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream,
+                                     dmx_meters_result *d_meters, const dmx_limiter_spec *lim, dmx_limit_result *d_limit);
+    /* host buffers, as dmx_loud_encode_meters; limit NULL or n_out entries */
+    int dmx_loud_encode_limit(int device, const float *planes, int n_sources, int64_t n, const float *mix, const dmx_remix_spec *spec,
+                              const dmx_loudness_spec *loud, int rate, void *out, float *peaks, dmx_loudness_result *report,
+                              dmx_meters_result *meters, const dmx_limiter_spec *lim, dmx_limit_result *limit);
+
+    /* dmx_tracks_infer_meters and dmx_tracks_infer_from_flac_meters (below) with the limiter: the `_meters` forms plus the
+     * limiter's times (lim NULL: the defaults) and a report of n_tracks x n_out entries (limit NULL: none; zeroed without
+     * DMX_LOUD_LIMIT). With the flag a track is a whole-track one (DMX_LOUD_UNITY too): behind its last piece its outputs are
+     * measured, gained without a ceiling, limited at the track's own rate, encoded through the gain plane and copied out; the
+     * peaks are peak_out, and the peak kernel is not launched. Device memory per track slot, on top of the call without the
+     * limiter: dmx_limiter_workspace_bytes(n_max) per envelope - one under DMX_LOUD_MIXTURE, n_out under DMX_LOUD_EACH and
+     * DMX_LOUD_UNITY - plus 64 x n_out bytes of results. */
+    int dmx_tracks_infer_limit(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                               const float *const *audio, const int64_t *n, const int *rates, int n_shifts, float overlap,
+                               const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out, int64_t *sizes,
+                               float *peaks, int layout, dmx_progress_fn progress, void *user, const dmx_loudness_spec *loud,
+                               dmx_loudness_result *report, dmx_meters_result *meters, const dmx_limiter_spec *lim, dmx_limit_result *limit);
+    int dmx_tracks_infer_from_flac_limit(dmx_ctx *c, const dmx_model *const *models, int n_models, const float *weights, int n_tracks,
+                                         const void *const *files, const int64_t *file_bytes, int n_shifts, float overlap,
+                                         const int *shift_offsets, const dmx_remix_spec *spec, int flac_out, void *const *out,
+                                         int64_t *sizes, float *peaks, int64_t *track_status, dmx_progress_fn progress, void *user,
+                                         const dmx_loudness_spec *loud, dmx_loudness_result *report, dmx_meters_result *meters,
+                                         const dmx_limiter_spec *lim, dmx_limit_result *limit);
+
     /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
      * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
      * PCM as the stages above write it (16-bit pairs or packed 24 bit) -> a complete .flac file: "fLaC", one STREAMINFO block
