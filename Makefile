@@ -16,14 +16,14 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
 OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o loudness.o meters.o limiter.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
-all: $(LIB) cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_host loudness_host meters_host limiter_host harness micro
+all: $(LIB) cli oracle interp op_step plan_harness chain_harness rates_harness att_harness flac_in_host flac_host loudness_host meters_host limiter_host harness micro
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/loud_chain.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@ $(QUIET)
 # the limiter's products are separate roundings: contraction off for the whole file
 build/limiter.o: HIPFLAGS += -ffp-contract=off
-build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
+build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/loud_chain.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@ $(QUIET)
 
@@ -52,6 +52,15 @@ plan_harness: tests/_build/tracks_plan_harness
 tests/_build/tracks_plan_harness: tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p tests/_build
 	g++ -O2 -std=c++17 -Wall -o $@ tests/tracks_plan_harness.cpp $(CSRC)/tracks_plan.cpp
+# the workspace layout of the loudness / limiter output chain (csrc/loud_chain.h: host arithmetic, no HIP), printed as JSON
+# (tests/test_loud_chain_layout_cpu.py; chain_harness_asan builds the sanitizer form, run as its own program)
+CHAIN_OUT ?= tests/_build/loud_chain_harness
+chain_harness: $(CHAIN_OUT)
+$(CHAIN_OUT): tests/loud_chain_harness.cpp $(CSRC)/loud_chain.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -Wall $(CXXFLAGS_CHAIN) -o $@ tests/loud_chain_harness.cpp
+chain_harness_asan:
+	$(MAKE) chain_harness CHAIN_OUT=tests/_build/loud_chain_harness_asan CXXFLAGS_CHAIN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 # the same plan for tracks at other sample rates (native-rate ranges), printed by a program of its own (tests/test_track_rates_cpu.py;
 # CXXFLAGS_RATES=-fsanitize=address,undefined RATES_OUT=... builds the sanitizer form)
 RATES_OUT ?= tests/_build/track_rates_harness
@@ -157,7 +166,7 @@ tests/_build/lds_dma: tools/micro/lds_dma.hip
 clean:
 	rm -rf build $(LIB) tests/_build cli/*.main
 	$(MAKE) -C oracle clean
-.PHONY: all cli oracle interp op_step plan_harness rates_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan loudness_host loudness_host_asan meters_host meters_host_asan limiter_host limiter_host_asan harness micro clean
+.PHONY: all cli oracle interp op_step plan_harness chain_harness chain_harness_asan rates_harness att_harness flac_in_host flac_in_host_asan flac_host flac_host_asan loudness_host loudness_host_asan meters_host meters_host_asan limiter_host limiter_host_asan harness micro clean
 
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:

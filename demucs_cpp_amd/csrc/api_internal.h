@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/demucs_hip.h"
 #include "kernels.h"
+#include "loud_chain.h"
 
 #include <cstring>
 #include <map>
@@ -96,7 +97,7 @@ struct dmx_ctx
         DevBuf pcm, peaks; // dmx_tracks_infer_pcm: the encoded outputs (each at a 16-byte-rounded stride) and their peaks
         DevBuf flac, flacWork, flacSizes; // dmx_tracks_infer_flac: the files (stride dmx_flac_bound), the workspace, n_out int64 counts
         DevBuf flacIn, flacInWork, flacInStatus; // dmx_tracks_infer_from_flac: the file's bytes, the decoder's workspace, {status, good}
-        DevBuf loud; // dmx_tracks_infer_loud: n_out + 1 measurement workspaces, then 64 bytes of gains, then the n_out + 1 report entries
+        DevBuf loud; // dmx_tracks_infer_loud: the chain's workspace with the reports inside (loud_chain.h)
         DevBuf native, nativeOut; // dmx_tracks_infer_rates, a call with a converted track: the track [m][2] and its stems at its own rate
         hipEvent_t copied = nullptr; // on copyStream behind the last copy-out of the track that holds the slot (TracksPlan)
     };
@@ -203,6 +204,27 @@ int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate,
 int dmx_limit_check_spec(const char *fn, const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate, int track);
 // the limiter's tables on `device` (kLimTableWords words): one copy per device, uploaded on first use, kept for the process
 int dmx_limiter_device_tables(int device, const int32_t **T);
+// The output chain of one whole track behind its remix, enqueued on s: the measurements of the outputs
+// and of the mixture, the true peaks and the meters the layout L has, and the gain launch or, with DMX_LOUD_LIMIT, the gain
+// without a ceiling and the limiter, whose peaks replace pp.peaks. pp: the whole track, peaks the n_out sample peaks (behind
+// the peak kernel unless limited); work: L.total bytes laid out by loud_chain_layout; report and meters (NULL: none) are n_out
+// + 1 entries on the device, in the workspace or the caller's. The caller encodes *piece: launch_limit_encode when limited,
+// else launch_loud_encode or, ungained, launch_remix_encode (gplaneStride 0 when the envelopes are linked).
+struct LoudChainJob
+{
+    dmx::RemixPiece pp;
+    const dmx::PcmGains *G;
+    const dmx::LoudPlan *lp;
+    int rate;
+    const dmx_loudness_spec *loud; // checked
+    const dmx_limiter_spec *lim;   // NULL: the default times
+    const float *loudTable;
+    const int32_t *limTables;      // read only with DMX_LOUD_LIMIT
+    unsigned char *work;
+    dmx::LoudChain L;
+    void *report, *meters;
+};
+int dmx_loud_chain_enqueue(const LoudChainJob &job, hipStream_t s, dmx::LimitPiece *piece);
 
 // ---- internal entry points used by engine.cpp
 int dmx_ensure_buf(DevBuf &b, dmx::i64 floats);

@@ -194,30 +194,81 @@ int dmx_limit_check_spec(const char *fn, const dmx_loudness_spec *spec, const dm
 static int loud_check(const char *fn, const dmx_loudness_spec *spec, int rate) { return dmx_loud_check_spec(fn, spec, rate, -1); }
 extern "C" int dmx_loudness_check(const dmx_loudness_spec *spec, int rate) { return loud_check("dmx_loudness_check", spec, rate); }
 
-// the stage alone has no context to own the gain table: one copy per device, made on first use (a blocking upload) and kept
-// for the life of the process (48 KB; the track path keeps its own in the context, dmx_ctx::dLoudTable)
-static int loud_table(int device, const float **T)
+// the stage alone has no context to own its tables: one copy per device, made on first use (a blocking upload) and kept for the
+// life of the process (the gain table: 48 KB; the limiter's: 34 KB; the track path keeps its own in the context)
+namespace
 {
-    static std::mutex mu;
-    static std::map<int, float *> tables;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = tables.find(device);
-    if (it == tables.end())
+struct DeviceTable
+{
+    size_t words;
+    void (*fill)(int32_t *);
+    const char *uploadFailed;
+    std::mutex mu;
+    std::map<int, int32_t *> copies;
+    int get(int device, const void **T)
     {
-        std::vector<float> h(kLoudGainSteps);
-        loud_gain_table(h.data());
-        float *d = nullptr;
-        HIPCHK(hipMalloc(&d, sizeof(float) * h.size()));
-        if (hipMemcpy(d, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = copies.find(device);
+        if (it == copies.end())
         {
-            (void)hipFree(d);
-            return fail(DMX_ERR_HIP, "loudness: the gain table's upload failed");
+            std::vector<int32_t> h(words, 0);
+            fill(h.data());
+            int32_t *d = nullptr;
+            HIPCHK(hipMalloc(&d, sizeof(int32_t) * words));
+            if (hipMemcpy(d, h.data(), sizeof(int32_t) * words, hipMemcpyHostToDevice) != hipSuccess)
+            {
+                (void)hipFree(d);
+                return fail(DMX_ERR_HIP, "%s", uploadFailed);
+            }
+            it = copies.emplace(device, d).first;
         }
-        it = tables.emplace(device, d).first;
+        *T = it->second;
+        return DMX_OK;
     }
-    *T = it->second;
-    return DMX_OK;
-}
+};
+DeviceTable g_loudTable{kLoudGainSteps, [](int32_t *h) { loud_gain_table(reinterpret_cast<float *>(h)); }, "loudness: the gain table's upload failed"};
+DeviceTable g_limTables{kLimTableWords,
+                        [](int32_t *h) { lim_tables(h, reinterpret_cast<float *>(h + kLimLut), reinterpret_cast<float *>(h + kLimLut + kLimHiPad)); },
+                        "limiter: the tables' upload failed"};
+
+// the events of a timed entry point: made by create(), destroyed with the object
+template <int N>
+struct Events
+{
+    const char *fn;
+    hipEvent_t ev[N] = {};
+    explicit Events(const char *f) : fn(f) {}
+    Events(const Events &) = delete;
+    ~Events()
+    {
+        for (hipEvent_t e : ev)
+            if (e)
+                (void)hipEventDestroy(e);
+    }
+    int create()
+    {
+        for (hipEvent_t &e : ev)
+            if (hipEventCreate(&e) != hipSuccess)
+                return fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
+        return DMX_OK;
+    }
+    int elapsed(int i, int j, float *ms) const
+    {
+        if (hipEventElapsedTime(ms, ev[i], ev[j]) != hipSuccess)
+            return fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
+        return DMX_OK;
+    }
+    // the wait of a timed call on its last event
+    int wait(int i) const
+    {
+        if (hipEventSynchronize(ev[i]) != hipSuccess)
+            return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+        return DMX_OK;
+    }
+};
+} // namespace
+static int loud_table(int device, const float **T) { return g_loudTable.get(device, reinterpret_cast<const void **>(T)); }
+int dmx_limiter_device_tables(int device, const int32_t **T) { return g_limTables.get(device, reinterpret_cast<const void **>(T)); }
 
 // one stereo signal as a one-row gain table: planar through source 0 of one "stem", interleaved through the mixture column
 static void loud_signal(const float *d_x, int64_t n, int64_t plane_stride, RemixPiece *pc, PcmGains *G)
@@ -226,6 +277,36 @@ static void loud_signal(const float *d_x, int64_t n, int64_t plane_stride, Remix
     G->nOut = 1, G->S = plane_stride ? 1 : 0;
     G->g[0][0] = 1.0f;
     *pc = RemixPiece{PcmPiece{plane_stride ? d_x : nullptr, nullptr, nullptr, n, plane_stride, 0, 0, n}, plane_stride ? nullptr : d_x};
+}
+
+// the loudness and the limiter timed calls: `run` enqueues the call with five events around its launches, then one stereo
+// sample-peak launch reads the same signal between two more; synchronised. ms[0..4): the call's launches, ms[4]: the peak kernel
+template <class Run>
+static int timed_beside_peak(const char *fn, int device, const float *d_x, int64_t n, int64_t plane_stride, void *stream, float *ms, Run run)
+{
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    Events<7> ev(fn);
+    DMXCHK(ev.create());
+    DevScratch d;
+    unsigned *dPeak = (unsigned *)d.get(sizeof(unsigned));
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    DMXCHK(run(fn, ev.ev));
+    RemixPiece pc;
+    PcmGains G;
+    loud_signal(d_x, n, plane_stride, &pc, &G);
+    pc.peaks = dPeak;
+    (void)hipMemsetAsync(dPeak, 0, sizeof(unsigned), s);
+    (void)hipEventRecord(ev.ev[5], s);
+    launch_remix_peak(&pc, 1, G, s);
+    (void)hipEventRecord(ev.ev[6], s);
+    DMXCHK(ev.wait(6));
+    for (int i = 0; i < 4; ++i)
+        DMXCHK(ev.elapsed(i, i + 1, &ms[i]));
+    return ev.elapsed(5, 6, &ms[4]);
 }
 
 // marks: null, or five events around the four launches
@@ -262,149 +343,117 @@ extern "C" int dmx_loudness_device(int device, const float *d_x, int64_t n, int6
 extern "C" int dmx_loudness_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate,
                                          dmx_loudness_result *d_result, double *d_e, void *d_work, void *stream, float *ms)
 {
-    const char *fn = "dmx_loudness_device_timed";
-    if (!ms)
-        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t ev[7] = {};
-    unsigned *dPeak = nullptr;
-    int rc = DMX_OK;
-    for (hipEvent_t &e : ev)
-        if (rc == DMX_OK && hipEventCreate(&e) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
-    if (rc == DMX_OK && hipMalloc(&dPeak, sizeof(unsigned)) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
-    if (rc == DMX_OK)
-        rc = loudness_device(fn, device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, ev);
-    if (rc == DMX_OK)
-    {
-        RemixPiece pc;
-        PcmGains G;
-        loud_signal(d_x, n, plane_stride, &pc, &G);
-        pc.peaks = dPeak;
-        (void)hipMemsetAsync(dPeak, 0, sizeof(unsigned), s);
-        (void)hipEventRecord(ev[5], s);
-        launch_remix_peak(&pc, 1, G, s);
-        (void)hipEventRecord(ev[6], s);
-        if (hipEventSynchronize(ev[6]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    }
-    for (int i = 0; i < 4 && rc == DMX_OK; ++i)
-        if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    if (rc == DMX_OK && hipEventElapsedTime(&ms[4], ev[5], ev[6]) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    for (hipEvent_t e : ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    if (dPeak)
-        (void)hipFree(dPeak);
-    return rc;
+    return timed_beside_peak("dmx_loudness_device_timed", device, d_x, n, plane_stride, stream, ms, [&](const char *fn, hipEvent_t *marks) {
+        return loudness_device(fn, device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, marks);
+    });
 }
 
-extern "C" int dmx_loudness(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e)
+static int meters_device(const char *fn, int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                         double *d_e, void *d_work, void *stream, dmx_meters_result *d_meters);
+
+// dmx_loudness and, with its entry `meters` on the host, dmx_meters: the upload, the scratch and the download
+static int loudness_host(const char *fn, int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e,
+                         dmx_meters_result *meters, bool withMeters)
 {
-    const char *fn = "dmx_loudness";
     if (rate < DMX_LOUD_MIN_RATE)
         return fail(DMX_ERR_ARG, "%s: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
-    if (!x || !result || n < 1 || n >= (int64_t)1 << 36)
+    if (!x || !result || (withMeters && !meters) || n < 1 || n >= (int64_t)1 << 36)
         return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer, n < 1 or n >= 2^36)", fn);
     HIPCHK(hipSetDevice(device));
     const size_t inBytes = sizeof(float) * 2 * (size_t)n, eBytes = sizeof(double) * 2 * (size_t)(n / ((rate + 5) / 10));
     DevScratch d;
     float *dX = (float *)d.get(inBytes);
-    void *dWork = d.get((size_t)loud_workspace_bytes(n));
-    dmx_loudness_result *dRes = (dmx_loudness_result *)d.get(sizeof(dmx_loudness_result));
+    void *dWork = d.get((size_t)(loud_workspace_bytes(n) + (withMeters ? meters_workspace_bytes(n) : 0)));
+    unsigned char *dRes = (unsigned char *)d.get(64); // the loudness result, then the meters
+    dmx_meters_result *dMeters = (dmx_meters_result *)(dRes + sizeof(dmx_loudness_result));
     double *dE = e && eBytes ? (double *)d.get(eBytes) : nullptr;
     if (!d.ok)
         return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
     if (hipMemcpy(dX, x, inBytes, hipMemcpyHostToDevice) != hipSuccess)
         return fail(DMX_ERR_HIP, "%s: upload failed", fn);
-    DMXCHK(loudness_device(fn, device, dX, n, interleaved ? 0 : n, rate, dRes, dE, dWork, nullptr, nullptr));
+    DMXCHK(withMeters ? meters_device(fn, device, dX, n, interleaved ? 0 : n, rate, (dmx_loudness_result *)dRes, dE, dWork, nullptr, dMeters)
+                      : loudness_device(fn, device, dX, n, interleaved ? 0 : n, rate, (dmx_loudness_result *)dRes, dE, dWork, nullptr, nullptr));
     if (hipDeviceSynchronize() != hipSuccess)
         return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
     if (hipMemcpy(result, dRes, sizeof(dmx_loudness_result), hipMemcpyDeviceToHost) != hipSuccess ||
+        (withMeters && hipMemcpy(meters, dMeters, sizeof(dmx_meters_result), hipMemcpyDeviceToHost) != hipSuccess) ||
         (dE && hipMemcpy(e, dE, eBytes, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(DMX_ERR_HIP, "%s: download failed", fn);
     return DMX_OK;
 }
-
-// d_meters: null (dmx_loud_encode_device: the workspace is the one without meters), or n_out + 1 entries on the device
-static int loud_encode_device(const char *fn, int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
-                              const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
-                              float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream, dmx_meters_result *d_meters)
+extern "C" int dmx_loudness(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e)
 {
-    PcmGains G;
-    DMXCHK(dmx_remix_check_spec(fn, n_sources, spec, &G, false));
-    DMXCHK(loud_check(fn, loud, rate));
-    if (!d_planes || !d_out || !d_peaks || !d_mix || !d_report || !d_work)
-        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn,
-                    !d_planes ? "d_planes" : !d_out ? "d_out" : !d_peaks ? "d_peaks" : !d_mix ? "d_mix" : !d_report ? "d_report" : "d_work");
-    if (n < 1 || n >= (int64_t)1 << 36 || plane_stride < n)
-        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (1 <= n <= plane_stride, n < 2^36)", fn, (long long)n,
-                    (long long)plane_stride);
-    if (((uintptr_t)d_out & 15) != 0 || ((uintptr_t)d_planes & 3) != 0 || ((uintptr_t)d_peaks & 3) != 0 || ((uintptr_t)d_mix & 3) != 0 ||
-        ((uintptr_t)d_work & 15) != 0 || ((uintptr_t)d_report & 7) != 0 || ((uintptr_t)d_meters & 3) != 0)
-        return fail(DMX_ERR_ARG, "%s: d_out and d_work must be 16-byte aligned, d_report 8-byte aligned, d_planes, d_mix, d_peaks and d_meters 4-byte aligned",
-                    fn);
-    LoudPlan lp;
-    if (loud_plan(rate, n, &lp) != 0)
-        return fail(DMX_ERR_ARG, "%s: no plan for rate %d, n %lld", fn, rate, (long long)n);
-    HIPCHK(hipSetDevice(device));
-    const float *T = nullptr;
-    DMXCHK(loud_table(device, &T));
-    hipStream_t s = (hipStream_t)stream;
-    const i64 slotBytes = loud_workspace_bytes(n);
-    unsigned char *work = (unsigned char *)d_work;
-    float *gains = (float *)(work + (i64)(G.nOut + 1) * slotBytes);
-    HIPCHK(hipMemsetAsync(d_peaks, 0, sizeof(float) * (size_t)G.nOut, s));
-    LoudPiece pp;
-    static_cast<PcmPiece &>(pp) = PcmPiece{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
-                                           DMX_OUTPUT_STRIDE(n * dmx_pcm_frame_bytes(spec->encoding)), 0, n};
-    pp.mix = d_mix;
-    pp.gains = gains;
+    return loudness_host("dmx_loudness", device, x, n, interleaved, rate, result, e, nullptr, false);
+}
+
+static_assert(kChainMaxOut == PcmGains::kMaxOut && kChainReportBytes == sizeof(dmx_loudness_result) &&
+                  kChainReportBytes == sizeof(dmx_meters_result) && kChainLimResBytes >= (int)sizeof(dmx_limit_result),
+              "loud_chain.h restates these sizes");
+
+int dmx_loud_chain_enqueue(const LoudChainJob &job, hipStream_t s, LimitPiece *piece)
+{
+    const RemixPiece &pp = job.pp;
+    const PcmGains &G = *job.G;
+    const LoudPlan &lp = *job.lp;
+    const LoudChain &L = job.L;
+    const dmx_loudness_spec &loud = *job.loud;
+    const int base = loud.mode & ~(DMX_LOUD_TRUE_PEAK | DMX_LOUD_LIMIT), targetC = (int)rintf(100.0f * loud.target_lufs);
+    const bool byTp = (loud.mode & DMX_LOUD_TRUE_PEAK) != 0, limited = (loud.mode & DMX_LOUD_LIMIT) != 0;
+    unsigned char *work = job.work;
+    float *gains = (float *)(work + L.gains);
+    unsigned *tp = (unsigned *)(work + L.truePeaks);
     PcmGains M{}; // the mixture as a one-row table of its own: its slot is the last
     M.nOut = 1, M.S = G.S;
     M.g[0][G.S] = 1.0f;
     launch_loud_measure(pp, G, lp, work, 0, nullptr, nullptr, s);
     launch_loud_measure(pp, M, lp, work, G.nOut, nullptr, nullptr, s);
-    launch_remix_peak(&pp, 1, G, s);
-    const int mode = loud->mode & ~DMX_LOUD_TRUE_PEAK;
-    const bool byTp = (loud->mode & DMX_LOUD_TRUE_PEAK) != 0;
-    // the true peaks: behind the gains in their 64 bytes (n_out <= 8 of each), or, with meters, n_out + 1 of them in the meters' part
-    unsigned *tp = d_meters ? (unsigned *)(work + (i64)(G.nOut + 1) * slotBytes + 64) : (unsigned *)(gains + PcmGains::kMaxOut);
-    if (byTp || d_meters)
+    TpFilter f;
+    if (L.tpWords || limited)
+        tp_filter(job.rate, &f);
+    if (L.tpWords)
     {
-        TpFilter f;
-        tp_filter(rate, &f);
-        HIPCHK(hipMemsetAsync(tp, 0, sizeof(unsigned) * (size_t)(G.nOut + (d_meters ? 1 : 0)), s));
-        LoudPiece tq = pp;
+        // the true peaks of the whole track's outputs, and for a meters report the mixture's and the hop meters
+        HIPCHK(hipMemsetAsync(tp, 0, sizeof(unsigned) * (size_t)L.tpWords, s));
+        RemixPiece tq = pp;
         tq.peaks = tp;
         launch_true_peak(&tq, 1, G, f, s);
-        if (d_meters)
+        if (job.meters)
         {
             tq.peaks = tp + G.nOut;
             launch_true_peak(&tq, 1, M, f, s);
-            launch_meters(work, 0, G.nOut + 1, lp, tp, d_meters, s);
+            launch_meters(work, 0, G.nOut + 1, lp, tp, job.meters, s);
         }
     }
-    if (byTp)
-        launch_loud_gain_tp(work, slotBytes, G.nOut, (unsigned *)d_peaks, tp, mode, (int)rintf(100.0f * loud->target_lufs), loud->max_peak, T,
-                            gains, d_report, s);
-    else
-        launch_loud_gain(work, slotBytes, G.nOut, (unsigned *)d_peaks, mode, (int)rintf(100.0f * loud->target_lufs), loud->max_peak, T, gains,
-                         d_report, s);
-    if (mode == DMX_LOUD_MEASURE)
-        launch_remix_encode(&pp, 1, G, spec->encoding, spec->clip, s);
-    else
-        launch_loud_encode(&pp, 1, G, spec->encoding, spec->clip, s);
-    HIPCHK(hipGetLastError());
+    static_cast<RemixPiece &>(*piece) = pp;
+    piece->gains = gains;
+    piece->gplane = nullptr, piece->gplaneStride = 0;
+    if (!limited)
+    {
+        if (byTp)
+            launch_loud_gain_tp(work, L.slotBytes, G.nOut, pp.peaks, tp, base, targetC, loud.max_peak, job.loudTable, gains, job.report, s);
+        else
+            launch_loud_gain(work, L.slotBytes, G.nOut, pp.peaks, base, targetC, loud.max_peak, job.loudTable, gains, job.report, s);
+        return DMX_OK;
+    }
+    // the gain without a ceiling (the peaks are zero: nothing to cap, nothing to scale; DMX_LOUD_UNITY: g = 1, as under MEASURE),
+    // then the limiter under that gain: its envelopes, the limited peaks in place of the gained ones, and the results
+    launch_loud_gain(work, L.slotBytes, G.nOut, pp.peaks, base == DMX_LOUD_UNITY ? DMX_LOUD_MEASURE : base, targetC, INFINITY, job.loudTable, gains,
+                     job.report, s);
+    LimJob lj{};
+    (void)lim_slopes(job.rate, job.lim ? (double)job.lim->attack_ms : kLimAttackMs, job.lim ? (double)job.lim->release_ms : kLimReleaseMs, &lj.qa,
+                     &lj.qr);
+    dmx_limit_result *limRes = (dmx_limit_result *)(work + L.limRes);
+    lj.pc = pp, lj.G = G, lj.gains = gains, lj.gainImm = 1.0f, lj.ceiling = loud.max_peak;
+    lj.link = base == DMX_LOUD_MIXTURE, lj.work = work + L.lim, lj.tables = job.limTables, lj.res = limRes;
+    launch_limit(lj, f, byTp, s);
+    HIPCHK(hipMemcpy2DAsync(pp.peaks, sizeof(float), &limRes->peak_out, sizeof(dmx_limit_result), sizeof(float), (size_t)G.nOut,
+                            hipMemcpyDeviceToDevice, s));
+    piece->gplane = (const float *)(lj.work + lim_ws_gain_offset(lp.n));
+    piece->gplaneStride = lj.link ? 0 : L.envBytes / 4;
     return DMX_OK;
 }
 
-// the entry points of this section and of the meters' are the limiter's without its two arguments: a mode
-// without DMX_LOUD_LIMIT enqueues loud_encode_device, above
+// the entry points of this section and of the meters' are the limiter's without its two arguments
 static int loud_encode_limit_device(const char *fn, int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
                                     const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
                                     float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream, dmx_meters_result *d_meters,
@@ -463,10 +512,9 @@ extern "C" int dmx_true_peak_filter(int rate, int *factor, float *taps)
 }
 extern "C" int64_t dmx_meters_workspace_bytes(int64_t n) { return meters_workspace_bytes(n); }
 
-extern "C" int dmx_meters_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
-                                 double *d_e, void *d_work, void *stream, dmx_meters_result *d_meters)
+static int meters_device(const char *fn, int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                         double *d_e, void *d_work, void *stream, dmx_meters_result *d_meters)
 {
-    const char *fn = "dmx_meters_device";
     if (!d_meters || ((uintptr_t)d_meters & 3) != 0)
         return fail(DMX_ERR_ARG, "%s: d_meters is null or not 4-byte aligned", fn);
     DMXCHK(loudness_device(fn, device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, nullptr));
@@ -487,6 +535,12 @@ extern "C" int dmx_meters_device(int device, const float *d_x, int64_t n, int64_
     return DMX_OK;
 }
 
+extern "C" int dmx_meters_device(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, dmx_loudness_result *d_result,
+                                 double *d_e, void *d_work, void *stream, dmx_meters_result *d_meters)
+{
+    return meters_device("dmx_meters_device", device, d_x, n, plane_stride, rate, d_result, d_e, d_work, stream, d_meters);
+}
+
 extern "C" int dmx_meters_device_timed(int device, const float *d_x, int64_t n, int64_t plane_stride, int rate, void *d_work, void *stream,
                                        float *ms)
 {
@@ -495,81 +549,44 @@ extern "C" int dmx_meters_device_timed(int device, const float *d_x, int64_t n, 
         return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
     HIPCHK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    hipEvent_t ev[6] = {};
-    unsigned char *dSmall = nullptr; // a loudness result, a meters result, a sample peak
-    int rc = DMX_OK;
-    for (hipEvent_t &e : ev)
-        if (rc == DMX_OK && hipEventCreate(&e) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
-    if (rc == DMX_OK && hipMalloc(&dSmall, 64) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
-    if (rc == DMX_OK)
-        rc = loudness_device(fn, device, d_x, n, plane_stride, rate, (dmx_loudness_result *)dSmall, nullptr, d_work, stream, nullptr);
-    if (rc == DMX_OK)
-    {
-        LoudPlan lp;
-        (void)loud_plan(rate, n, &lp);
-        unsigned *tp = (unsigned *)((unsigned char *)d_work + loud_workspace_bytes(n));
-        RemixPiece pc;
-        PcmGains G;
-        loud_signal(d_x, n, plane_stride, &pc, &G);
-        TpFilter f;
-        tp_filter(rate, &f);
-        (void)hipMemsetAsync(tp, 0, sizeof(unsigned), s);
-        (void)hipMemsetAsync(dSmall + 48, 0, sizeof(unsigned), s);
-        pc.peaks = tp;
-        (void)hipEventRecord(ev[0], s);
-        launch_true_peak(&pc, 1, G, f, s);
-        (void)hipEventRecord(ev[1], s);
-        pc.peaks = (unsigned *)(dSmall + 48);
-        (void)hipEventRecord(ev[2], s);
-        launch_remix_peak(&pc, 1, G, s);
-        (void)hipEventRecord(ev[3], s);
-        (void)hipEventRecord(ev[4], s);
-        launch_meters((const unsigned char *)d_work, 0, 1, lp, tp, dSmall + 16, s);
-        (void)hipEventRecord(ev[5], s);
-        if (hipEventSynchronize(ev[5]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    }
-    for (int i = 0; i < 3 && rc == DMX_OK; ++i)
-        if (hipEventElapsedTime(&ms[i], ev[2 * i], ev[2 * i + 1]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    for (hipEvent_t e : ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    if (dSmall)
-        (void)hipFree(dSmall);
-    return rc;
+    Events<6> ev(fn);
+    DMXCHK(ev.create());
+    DevScratch d;
+    unsigned char *dSmall = (unsigned char *)d.get(64); // a loudness result, a meters result, a sample peak
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    DMXCHK(loudness_device(fn, device, d_x, n, plane_stride, rate, (dmx_loudness_result *)dSmall, nullptr, d_work, stream, nullptr));
+    LoudPlan lp;
+    (void)loud_plan(rate, n, &lp);
+    unsigned *tp = (unsigned *)((unsigned char *)d_work + loud_workspace_bytes(n));
+    RemixPiece pc;
+    PcmGains G;
+    loud_signal(d_x, n, plane_stride, &pc, &G);
+    TpFilter f;
+    tp_filter(rate, &f);
+    (void)hipMemsetAsync(tp, 0, sizeof(unsigned), s);
+    (void)hipMemsetAsync(dSmall + 48, 0, sizeof(unsigned), s);
+    pc.peaks = tp;
+    (void)hipEventRecord(ev.ev[0], s);
+    launch_true_peak(&pc, 1, G, f, s);
+    (void)hipEventRecord(ev.ev[1], s);
+    pc.peaks = (unsigned *)(dSmall + 48);
+    (void)hipEventRecord(ev.ev[2], s);
+    launch_remix_peak(&pc, 1, G, s);
+    (void)hipEventRecord(ev.ev[3], s);
+    (void)hipEventRecord(ev.ev[4], s);
+    launch_meters((const unsigned char *)d_work, 0, 1, lp, tp, dSmall + 16, s);
+    (void)hipEventRecord(ev.ev[5], s);
+    DMXCHK(ev.wait(5));
+    for (int i = 0; i < 3; ++i)
+        DMXCHK(ev.elapsed(2 * i, 2 * i + 1, &ms[i]));
+    return DMX_OK;
 }
 
 extern "C" int dmx_meters(int device, const float *x, int64_t n, int interleaved, int rate, dmx_loudness_result *result, double *e,
                           dmx_meters_result *meters)
 {
-    const char *fn = "dmx_meters";
-    if (rate < DMX_LOUD_MIN_RATE)
-        return fail(DMX_ERR_ARG, "%s: rate %d is below %d Hz", fn, rate, DMX_LOUD_MIN_RATE);
-    if (!x || !result || !meters || n < 1 || n >= (int64_t)1 << 36)
-        return fail(DMX_ERR_ARG, "%s: invalid argument (null pointer, n < 1 or n >= 2^36)", fn);
-    HIPCHK(hipSetDevice(device));
-    const size_t inBytes = sizeof(float) * 2 * (size_t)n, eBytes = sizeof(double) * 2 * (size_t)(n / ((rate + 5) / 10));
-    DevScratch d;
-    float *dX = (float *)d.get(inBytes);
-    void *dWork = d.get((size_t)(loud_workspace_bytes(n) + meters_workspace_bytes(n)));
-    unsigned char *dRes = (unsigned char *)d.get(64); // the loudness result, then the meters
-    double *dE = e && eBytes ? (double *)d.get(eBytes) : nullptr;
-    if (!d.ok)
-        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
-    if (hipMemcpy(dX, x, inBytes, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
-    DMXCHK(dmx_meters_device(device, dX, n, interleaved ? 0 : n, rate, (dmx_loudness_result *)dRes, dE, dWork, nullptr,
-                             (dmx_meters_result *)(dRes + 16)));
-    if (hipDeviceSynchronize() != hipSuccess)
-        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    if (hipMemcpy(result, dRes, sizeof(dmx_loudness_result), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(meters, dRes + 16, sizeof(dmx_meters_result), hipMemcpyDeviceToHost) != hipSuccess ||
-        (dE && hipMemcpy(e, dE, eBytes, hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(DMX_ERR_HIP, "%s: download failed", fn);
-    return DMX_OK;
+    return loudness_host("dmx_meters", device, x, n, interleaved, rate, result, e, meters, true);
 }
 
 // --------------------------------------------------------------------------- limiter (limiter.hip)
@@ -598,31 +615,6 @@ extern "C" int dmx_limiter_slopes(int rate, double attack_ms, double release_ms,
     return limiter_slopes("dmx_limiter_slopes", rate, attack_ms, release_ms, qa, qr);
 }
 extern "C" int64_t dmx_limiter_workspace_bytes(int64_t n) { return lim_workspace_bytes(n); }
-
-// the stage alone has no context to own the tables: one copy per device, made on first use (a blocking upload) and kept for
-// the life of the process (34 KB), as loud_table keeps the gain table
-int dmx_limiter_device_tables(int device, const int32_t **T)
-{
-    static std::mutex mu;
-    static std::map<int, int32_t *> tables;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = tables.find(device);
-    if (it == tables.end())
-    {
-        std::vector<int32_t> h(kLimTableWords, 0);
-        lim_tables(h.data(), reinterpret_cast<float *>(h.data() + kLimLut), reinterpret_cast<float *>(h.data() + kLimLut + kLimHiPad));
-        int32_t *d = nullptr;
-        HIPCHK(hipMalloc(&d, sizeof(int32_t) * h.size()));
-        if (hipMemcpy(d, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
-        {
-            (void)hipFree(d);
-            return fail(DMX_ERR_HIP, "limiter: the tables' upload failed");
-        }
-        it = tables.emplace(device, d).first;
-    }
-    *T = it->second;
-    return DMX_OK;
-}
 
 // what the stage refuses before any GPU work, and the slopes
 static int limit_check(const char *fn, int rate, float max_peak, const dmx_limiter_spec *lim, int *qa, int *qr)
@@ -668,45 +660,9 @@ extern "C" int dmx_limit_device_timed(int device, const float *d_x, int64_t n, i
                                       int true_peak, const dmx_limiter_spec *lim, dmx_limit_result *d_result, void *d_work, void *stream,
                                       float *ms)
 {
-    const char *fn = "dmx_limit_device_timed";
-    if (!ms)
-        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
-    HIPCHK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t ev[7] = {};
-    unsigned *dPeak = nullptr;
-    int rc = DMX_OK;
-    for (hipEvent_t &e : ev)
-        if (rc == DMX_OK && hipEventCreate(&e) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
-    if (rc == DMX_OK && hipMalloc(&dPeak, sizeof(unsigned)) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
-    if (rc == DMX_OK)
-        rc = limit_device(fn, device, d_x, n, plane_stride, rate, gain, max_peak, true_peak, lim, d_result, d_work, stream, ev);
-    if (rc == DMX_OK)
-    {
-        RemixPiece pc;
-        PcmGains G;
-        loud_signal(d_x, n, plane_stride, &pc, &G);
-        pc.peaks = dPeak;
-        (void)hipMemsetAsync(dPeak, 0, sizeof(unsigned), s);
-        (void)hipEventRecord(ev[5], s);
-        launch_remix_peak(&pc, 1, G, s);
-        (void)hipEventRecord(ev[6], s);
-        if (hipEventSynchronize(ev[6]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    }
-    for (int i = 0; i < 4 && rc == DMX_OK; ++i)
-        if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    if (rc == DMX_OK && hipEventElapsedTime(&ms[4], ev[5], ev[6]) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    for (hipEvent_t e : ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    if (dPeak)
-        (void)hipFree(dPeak);
-    return rc;
+    return timed_beside_peak("dmx_limit_device_timed", device, d_x, n, plane_stride, stream, ms, [&](const char *fn, hipEvent_t *marks) {
+        return limit_device(fn, device, d_x, n, plane_stride, rate, gain, max_peak, true_peak, lim, d_result, d_work, stream, marks);
+    });
 }
 
 extern "C" int dmx_limit(int device, const float *x, int64_t n, int interleaved, int rate, float gain, float max_peak, int true_peak,
@@ -746,11 +702,12 @@ extern "C" int dmx_limiter_check(const dmx_loudness_spec *spec, const dmx_limite
     return limiter_check("dmx_limiter_check", spec, lim, rate);
 }
 
-static size_t loud_encode_work_bytes(int nOut, int64_t n, bool meters)
+static LoudChain stage_layout(int nOut, int64_t n, bool meters, int mode)
 {
-    return (size_t)((nOut + 1) * (loud_workspace_bytes(n) + (meters ? meters_workspace_bytes(n) : 0)) + 64);
+    return loud_chain_layout(nOut, n, LoudChainMode{meters, (mode & DMX_LOUD_TRUE_PEAK) != 0, (mode & DMX_LOUD_LIMIT) != 0, nOut, false});
 }
 
+// d_meters: null (the workspace is the one without meters), or n_out + 1 entries on the device; d_limit: null, or n_out entries
 static int loud_encode_limit_device(const char *fn, int device, const float *d_planes, int n_sources, int64_t n, int64_t plane_stride,
                                     const float *d_mix, const dmx_remix_spec *spec, const dmx_loudness_spec *loud, int rate, void *d_out,
                                     float *d_peaks, dmx_loudness_result *d_report, void *d_work, void *stream, dmx_meters_result *d_meters,
@@ -761,15 +718,6 @@ static int loud_encode_limit_device(const char *fn, int device, const float *d_p
     DMXCHK(limiter_check(fn, loud, lim, rate));
     if (((uintptr_t)d_limit & 7) != 0)
         return fail(DMX_ERR_ARG, "%s: d_limit must be 8-byte aligned", fn);
-    hipStream_t s = (hipStream_t)stream;
-    if (!(loud->mode & DMX_LOUD_LIMIT)) // the call as it was
-    {
-        DMXCHK(loud_encode_device(fn, device, d_planes, n_sources, n, plane_stride, d_mix, spec, loud, rate, d_out, d_peaks, d_report, d_work, stream,
-                                  d_meters));
-        if (d_limit)
-            HIPCHK(hipMemsetAsync(d_limit, 0, sizeof(dmx_limit_result) * (size_t)G.nOut, s));
-        return DMX_OK;
-    }
     if (!d_planes || !d_out || !d_peaks || !d_mix || !d_report || !d_work)
         return fail(DMX_ERR_ARG, "%s: null %s pointer", fn,
                     !d_planes ? "d_planes" : !d_out ? "d_out" : !d_peaks ? "d_peaks" : !d_mix ? "d_mix" : !d_report ? "d_report" : "d_work");
@@ -784,56 +732,33 @@ static int loud_encode_limit_device(const char *fn, int device, const float *d_p
     if (loud_plan(rate, n, &lp) != 0)
         return fail(DMX_ERR_ARG, "%s: no plan for rate %d, n %lld", fn, rate, (long long)n);
     HIPCHK(hipSetDevice(device));
-    const float *T = nullptr;
-    DMXCHK(loud_table(device, &T));
-    LimJob job{};
-    DMXCHK(dmx_limiter_device_tables(device, &job.tables));
-    (void)lim_slopes(rate, lim ? (double)lim->attack_ms : kLimAttackMs, lim ? (double)lim->release_ms : kLimReleaseMs, &job.qa, &job.qr);
-    const int base = loud->mode & ~(DMX_LOUD_TRUE_PEAK | DMX_LOUD_LIMIT);
-    const bool byTp = (loud->mode & DMX_LOUD_TRUE_PEAK) != 0;
-    const i64 slotBytes = loud_workspace_bytes(n), envBytes = lim_workspace_bytes(n);
-    unsigned char *work = (unsigned char *)d_work;
-    float *gains = (float *)(work + (i64)(G.nOut + 1) * slotBytes);
-    unsigned char *limWork = work + (((i64)loud_encode_work_bytes(G.nOut, n, d_meters != nullptr) + 63) & ~(i64)63);
-    dmx_limit_result *limRes = (dmx_limit_result *)(limWork + (i64)G.nOut * envBytes);
+    const bool limited = (loud->mode & DMX_LOUD_LIMIT) != 0;
+    LoudChainJob job{};
+    DMXCHK(loud_table(device, &job.loudTable));
+    if (limited)
+        DMXCHK(dmx_limiter_device_tables(device, &job.limTables));
+    hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(d_peaks, 0, sizeof(float) * (size_t)G.nOut, s));
-    LimitPiece pp;
-    static_cast<PcmPiece &>(pp) = PcmPiece{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
-                                           DMX_OUTPUT_STRIDE(n * dmx_pcm_frame_bytes(spec->encoding)), 0, n};
-    pp.mix = d_mix;
-    pp.gains = gains;
-    pp.gplane = (const float *)(limWork + lim_ws_gain_offset(n));
-    pp.gplaneStride = base == DMX_LOUD_MIXTURE ? 0 : envBytes / 4;
-    PcmGains M{}; // the mixture as a one-row table of its own: its slot is the last
-    M.nOut = 1, M.S = G.S;
-    M.g[0][G.S] = 1.0f;
-    launch_loud_measure(pp, G, lp, work, 0, nullptr, nullptr, s);
-    launch_loud_measure(pp, M, lp, work, G.nOut, nullptr, nullptr, s);
-    TpFilter f;
-    tp_filter(rate, &f);
-    if (d_meters)
-    {
-        unsigned *tp = (unsigned *)(work + (i64)(G.nOut + 1) * slotBytes + 64);
-        HIPCHK(hipMemsetAsync(tp, 0, sizeof(unsigned) * (size_t)(G.nOut + 1), s));
-        LoudPiece tq = pp;
-        tq.peaks = tp;
-        launch_true_peak(&tq, 1, G, f, s);
-        tq.peaks = tp + G.nOut;
-        launch_true_peak(&tq, 1, M, f, s);
-        launch_meters(work, 0, G.nOut + 1, lp, tp, d_meters, s);
-    }
-    // the gain without a ceiling (the peaks are zero: nothing to cap, nothing to scale); DMX_LOUD_UNITY: g = 1, as under MEASURE
-    launch_loud_gain(work, slotBytes, G.nOut, (unsigned *)d_peaks, base == DMX_LOUD_UNITY ? DMX_LOUD_MEASURE : base,
-                     (int)rintf(100.0f * loud->target_lufs), INFINITY, T, gains, d_report, s);
-    job.pc = pp, job.G = G;
-    job.gains = gains, job.gainImm = 1.0f, job.ceiling = loud->max_peak, job.link = base == DMX_LOUD_MIXTURE;
-    job.work = limWork, job.res = limRes;
-    launch_limit(job, f, byTp, s);
-    HIPCHK(hipMemcpy2DAsync(d_peaks, sizeof(float), &limRes->peak_out, sizeof(dmx_limit_result), sizeof(float), (size_t)G.nOut,
-                            hipMemcpyDeviceToDevice, s));
-    launch_limit_encode(&pp, 1, G, spec->encoding, spec->clip, s);
-    if (d_limit)
-        HIPCHK(hipMemcpyAsync(d_limit, limRes, sizeof(dmx_limit_result) * (size_t)G.nOut, hipMemcpyDeviceToDevice, s));
+    job.pp = RemixPiece{PcmPiece{d_planes, (unsigned char *)d_out, (unsigned *)d_peaks, n, plane_stride,
+                                 DMX_OUTPUT_STRIDE(n * dmx_pcm_frame_bytes(spec->encoding)), 0, n},
+                        d_mix};
+    job.G = &G, job.lp = &lp, job.rate = rate, job.loud = loud, job.lim = lim;
+    job.work = (unsigned char *)d_work, job.L = stage_layout(G.nOut, n, d_meters != nullptr, loud->mode);
+    job.report = d_report, job.meters = d_meters;
+    if (!limited) // (the limiter measures the peaks of what it leaves: the peak kernel is not needed)
+        launch_remix_peak(&job.pp, 1, G, s);
+    LimitPiece piece;
+    DMXCHK(dmx_loud_chain_enqueue(job, s, &piece));
+    if (limited)
+        launch_limit_encode(&piece, 1, G, spec->encoding, spec->clip, s);
+    else if ((loud->mode & ~DMX_LOUD_TRUE_PEAK) == DMX_LOUD_MEASURE)
+        launch_remix_encode(&piece, 1, G, spec->encoding, spec->clip, s);
+    else
+        launch_loud_encode(&piece, 1, G, spec->encoding, spec->clip, s);
+    if (d_limit && limited)
+        HIPCHK(hipMemcpyAsync(d_limit, job.work + job.L.limRes, sizeof(dmx_limit_result) * (size_t)G.nOut, hipMemcpyDeviceToDevice, s));
+    else if (d_limit) // a mode without DMX_LOUD_LIMIT: the call as it was, and d_limit zeroed
+        HIPCHK(hipMemsetAsync(d_limit, 0, sizeof(dmx_limit_result) * (size_t)G.nOut, s));
     HIPCHK(hipGetLastError());
     return DMX_OK;
 }
@@ -869,8 +794,7 @@ static int loud_encode_limit_host(const char *fn, int device, const float *plane
     const int nOut = G.nOut;
     const i64 bytes = n * dmx_pcm_frame_bytes(spec->encoding), devStride = DMX_OUTPUT_STRIDE(bytes);
     const size_t inBytes = sizeof(float) * (size_t)n_sources * 2 * (size_t)n, mixBytes = sizeof(float) * 2 * (size_t)n;
-    const size_t workBytes = ((loud_encode_work_bytes(nOut, n, meters != nullptr) + 63) & ~(size_t)63) +
-                             ((loud->mode & DMX_LOUD_LIMIT) ? (size_t)nOut * (size_t)(lim_workspace_bytes(n) + 64) : 0);
+    const size_t workBytes = (size_t)stage_layout(nOut, n, meters != nullptr, loud->mode).total;
     const size_t reportBytes = sizeof(dmx_loudness_result) * (size_t)(nOut + 1), metersBytes = sizeof(dmx_meters_result) * (size_t)(nOut + 1),
                  limitBytes = sizeof(dmx_limit_result) * (size_t)nOut;
     DevScratch d;
@@ -955,22 +879,13 @@ extern "C" int dmx_flac_encode_device_timed(int device, const void *d_pcm, int b
     if (!ms)
         return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
     HIPCHK(hipSetDevice(device));
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = DMX_OK;
-    for (int i = 0; i < 4 && rc == DMX_OK; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
-    if (rc == DMX_OK)
-        rc = flac_encode_device(fn, device, d_pcm, bits, n, sample_rate, level, d_out, d_size, d_work, stream, ev);
-    if (rc == DMX_OK && hipEventSynchronize(ev[3]) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    for (int i = 0; i < 3 && rc == DMX_OK; ++i)
-        if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    for (hipEvent_t e : ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    return rc;
+    Events<4> ev(fn);
+    DMXCHK(ev.create());
+    DMXCHK(flac_encode_device(fn, device, d_pcm, bits, n, sample_rate, level, d_out, d_size, d_work, stream, ev.ev));
+    DMXCHK(ev.wait(3));
+    for (int i = 0; i < 3; ++i)
+        DMXCHK(ev.elapsed(i, i + 1, &ms[i]));
+    return DMX_OK;
 }
 
 static int flac_encode_host(const char *fn, int device, const void *pcm, int bits, int64_t n, int sample_rate, int level, void *out,
@@ -1101,21 +1016,13 @@ extern "C" int dmx_flac_decode_profile(int device, const void *d_file, int64_t b
     if (!d_file || !d_out || !d_status || !d_work || !ms)
         return fail(DMX_ERR_ARG, "%s: null pointer", fn);
     HIPCHK(hipSetDevice(device));
-    hipEvent_t ev[6] = {};
-    int rc = DMX_OK;
-    for (hipEvent_t &e : ev)
-        if (hipEventCreate(&e) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventCreate failed", fn);
-    if (rc == DMX_OK && launch_flac_decode((const unsigned char *)d_file, bytes, info, encoding, d_out, (long long *)d_status, d_work,
-                                           (hipStream_t)stream, ev) != 0)
-        rc = fail(DMX_ERR_ARG, "%s: info rejected", fn);
-    if (rc == DMX_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
-        rc = fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    for (int k = 0; rc == DMX_OK && k < 5; ++k)
-        if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
-            rc = fail(DMX_ERR_HIP, "%s: hipEventElapsedTime failed", fn);
-    for (hipEvent_t e : ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    return rc;
+    Events<6> ev(fn);
+    DMXCHK(ev.create());
+    if (launch_flac_decode((const unsigned char *)d_file, bytes, info, encoding, d_out, (long long *)d_status, d_work, (hipStream_t)stream, ev.ev) != 0)
+        return fail(DMX_ERR_ARG, "%s: info rejected", fn);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    for (int k = 0; k < 5; ++k)
+        DMXCHK(ev.elapsed(k, k + 1, &ms[k]));
+    return DMX_OK;
 }

@@ -220,13 +220,7 @@ int loud_plan(int rate, int64_t n, LoudPlan *p)
     return 0;
 }
 
-int64_t loud_workspace_bytes(int64_t n)
-{
-    if (n < 1)
-        return -1;
-    const int64_t tiles = (n + kLoudTile - 1) / kLoudTile;
-    return 64 + tiles * (64 + 16 * kLoudMaxHops) + 16 * (n / ((kLoudMinRate + 5) / 10));
-}
+int64_t loud_workspace_bytes(int64_t n) { return n < 1 ? -1 : loud_ws_bytes(n); }
 
 void loud_gain_table(float *T)
 {

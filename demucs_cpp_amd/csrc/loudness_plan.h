@@ -27,6 +27,10 @@ void loud_coefficients(int rate, double coef[10]);
 int loud_plan(int rate, int64_t n, LoudPlan *p);
 // bytes of workspace per measured signal of n frames, whatever the rate: a multiple of 16: 64 + 256 per tile + 16 per 400 frames, about n / 10
 int64_t loud_workspace_bytes(int64_t n);
+inline int64_t loud_ws_bytes(int64_t n) // n >= 1
+{
+    return 64 + (n + kLoudTile - 1) / kLoudTile * (64 + 16 * kLoudMaxHops) + 16 * (n / ((kLoudMinRate + 5) / 10));
+}
 // where a signal's hop energies e[2][H] start in its workspace slot, in bytes: behind the result (64), the tiles' states
 // [2][nTiles][4] and the tiles' hop partials [2][nTiles][kHops], all binary64 (the meters launch reads them: meters.hip)
 #ifdef __HIP__

@@ -83,7 +83,7 @@ void tp_filter(int rate, TpFilter *f)
     }
 }
 
-int64_t meters_workspace_bytes(int64_t n) { return n < 1 ? -1 : 64; }
+int64_t meters_workspace_bytes(int64_t n) { return n < 1 ? -1 : meters_ws_bytes(n); }
 
 } // namespace dmx
 #include "tp_phases.h"

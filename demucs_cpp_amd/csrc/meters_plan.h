@@ -26,4 +26,5 @@ int tp_factor(int rate);
 void tp_filter(int rate, TpFilter *f);
 // bytes per measured signal on top of loud_workspace_bytes(n): the true peak's bit pattern, padded to 64. -1 for n < 1
 int64_t meters_workspace_bytes(int64_t n);
+inline int64_t meters_ws_bytes(int64_t) { return 64; } // n >= 1
 } // namespace dmx

@@ -146,23 +146,14 @@ struct PcmOut // the output spec of a call, checked (dmx_pcm_check_spec)
     int loudMode() const { return loud->mode & ~(DMX_LOUD_TRUE_PEAK | DMX_LOUD_LIMIT); }
     bool byTruePeak() const { return loud && (loud->mode & DMX_LOUD_TRUE_PEAK) != 0; }
     bool limited() const { return loud && (loud->mode & DMX_LOUD_LIMIT) != 0; }
-    // the slot holds true peaks and a meters report behind the loudness report; the limiter's level needs no true peak of the track
+    // the track's true peaks are measured; the limiter's level needs none of the track
     bool truePeaks() const { return (byTruePeak() && !limited()) || meters; }
     bool gained() const { return loud && loudMode() != DMX_LOUD_MEASURE; } // DMX_LOUD_UNITY too: a whole-track, limited
-    // in a slot's loudness buffer behind the n_out + 1 workspaces of a track of n frames: 64 bytes of gains, the loudness report,
-    // and with truePeaks() 64 bytes of true peaks and the meters report
-    i64 loudTail(i64 n) const { return (i64)(nOut + 1) * loud_workspace_bytes(n); }
-    i64 tpOffset(i64 n) const { return loudTail(n) + 64 + (i64)sizeof(dmx_loudness_result) * (nOut + 1); }
-    // with limited(), behind all that at a multiple of 64: the envelopes' workspaces (one under DMX_LOUD_MIXTURE, else n_out) and
-    // then the n_out results
-    int limEnvs() const { return loudMode() == DMX_LOUD_MIXTURE ? 1 : nOut; }
-    i64 limOffset(i64 n) const { return (tpOffset(n) + (meters ? 64 + (i64)sizeof(dmx_meters_result) * (nOut + 1) : 0) + 63) & ~(i64)63; }
-    i64 limResOffset(i64 n) const { return limOffset(n) + (i64)limEnvs() * lim_workspace_bytes(n); }
-    i64 loudBytes(i64 n) const
+    // a slot's loudness buffer for a track of n frames (loud_chain.h): the reports live in it, and the limiter takes one envelope
+    // under DMX_LOUD_MIXTURE, else n_out
+    LoudChain chain(i64 n) const
     {
-        if (limited())
-            return limResOffset(n) + 64 * (i64)nOut;
-        return tpOffset(n) + (truePeaks() ? 64 + (i64)sizeof(dmx_meters_result) * (nOut + 1) : 0);
+        return loud_chain_layout(nOut, n, LoudChainMode{meters != nullptr, byTruePeak(), limited(), loudMode() == DMX_LOUD_MIXTURE ? 1 : nOut, true});
     }
 };
 // One call of the track path. shifts: T x Q x N, row-major (Q = 1 without a bag). Without a bag, N == 1 launches
@@ -248,7 +239,7 @@ static int tracks_prepare(TracksRun &r)
             DMXCHK(dmx_ensure_buf(sl.pcm, (i64)pcm->nOut * (DMX_OUTPUT_STRIDE(omax * pcm->frameBytes) / 4)));
             DMXCHK(dmx_ensure_buf(sl.peaks, 8));
             if (pcm->loud)
-                DMXCHK(dmx_ensure_buf(sl.loud, (pcm->loudBytes(omax) + 3) / 4));
+                DMXCHK(dmx_ensure_buf(sl.loud, (pcm->chain(omax).total + 3) / 4));
             if (pcm->flacBits)
             {
                 DMXCHK(dmx_ensure_buf(sl.flac, (i64)pcm->nOut * (flac_bound(pcm->flacBits, omax) / 4)));
@@ -475,76 +466,23 @@ static int tracks_output_stage(TracksRun &r, int k)
         if (!pcm->limited()) // (the limiter measures the peaks of what it leaves: the peak kernel is not needed)
             launch_remix_peak(r.pieces.data(), (int)r.pieces.size(), *pcm->remix, s);
         r.loudEnc.clear(), r.limitEnc.clear();
-        PcmGains M{}; // the mixture as a one-row table: its slot is the last
-        M.nOut = 1, M.S = pcm->remix->S;
-        M.g[0][M.S] = 1.0f;
         for (size_t x = 0, w = 0; x < p.pcm[(size_t)k].size(); ++x)
         {
             const PcmRange &g = p.pcm[(size_t)k][x];
             if (g.hi != p.jobs[(size_t)g.t].outFrames())
                 continue;
-            const RemixPiece &pp = r.whole[w++];
-            const LoudPlan &lp = r.loudPlans[(size_t)g.t];
-            const i64 slotBytes = loud_workspace_bytes(lp.n);
-            unsigned char *work = (unsigned char *)r.slot(g.t).loud.p;
-            float *gains = (float *)(work + (i64)(pcm->nOut + 1) * slotBytes);
-            launch_loud_measure(pp, *pcm->remix, lp, work, 0, nullptr, nullptr, s);
-            launch_loud_measure(pp, M, lp, work, pcm->nOut, nullptr, nullptr, s);
-            unsigned *tp = (unsigned *)(work + pcm->tpOffset(lp.n));
-            if (pcm->truePeaks())
-            {
-                // the true peaks of the whole track's outputs, and for a meters report the mixture's and the hop meters
-                TpFilter f;
-                tp_filter(r.rates ? r.rates[g.t] : 44100, &f);
-                HIPCHK(hipMemsetAsync(tp, 0, 64, s));
-                RemixPiece tq = pp;
-                tq.peaks = tp;
-                launch_true_peak(&tq, 1, *pcm->remix, f, s);
-                if (pcm->meters)
-                {
-                    tq.peaks = tp + pcm->nOut;
-                    launch_true_peak(&tq, 1, M, f, s);
-                    launch_meters(work, 0, pcm->nOut + 1, lp, tp, tp + 16, s);
-                }
-            }
+            LoudChainJob job{};
+            job.pp = r.whole[w++];
+            job.G = pcm->remix, job.lp = &r.loudPlans[(size_t)g.t], job.rate = r.rates ? r.rates[g.t] : 44100;
+            job.loud = pcm->loud, job.lim = pcm->lim, job.loudTable = pcm->loudTable, job.limTables = pcm->limTables;
+            job.work = (unsigned char *)r.slot(g.t).loud.p, job.L = pcm->chain(job.lp->n);
+            job.report = job.work + job.L.report, job.meters = pcm->meters ? job.work + job.L.meters : nullptr;
+            LimitPiece piece;
+            DMXCHK(dmx_loud_chain_enqueue(job, s, &piece));
             if (pcm->limited())
-            {
-                // the gain without a ceiling (DMX_LOUD_UNITY: 1, as under MEASURE), then the limiter under that gain: its
-                // envelopes, the limited peaks in place of the gained ones, and the results
-                const int rate = r.rates ? r.rates[g.t] : 44100, base = pcm->loudMode();
-                launch_loud_gain(work, slotBytes, pcm->nOut, pp.peaks, base == DMX_LOUD_UNITY ? DMX_LOUD_MEASURE : base,
-                                 (int)rintf(100.0f * pcm->loud->target_lufs), INFINITY, pcm->loudTable, gains, gains + 16, s);
-                LimJob job{};
-                (void)lim_slopes(rate, pcm->lim ? (double)pcm->lim->attack_ms : kLimAttackMs, pcm->lim ? (double)pcm->lim->release_ms : kLimReleaseMs,
-                                 &job.qa, &job.qr);
-                const i64 envBytes = lim_workspace_bytes(lp.n);
-                unsigned char *limWork = work + pcm->limOffset(lp.n);
-                dmx_limit_result *limRes = (dmx_limit_result *)(work + pcm->limResOffset(lp.n));
-                job.pc = pp, job.G = *pcm->remix, job.gains = gains, job.gainImm = 1.0f, job.ceiling = pcm->loud->max_peak;
-                job.link = base == DMX_LOUD_MIXTURE, job.work = limWork, job.tables = pcm->limTables, job.res = limRes;
-                TpFilter f;
-                tp_filter(rate, &f);
-                launch_limit(job, f, pcm->byTruePeak(), s);
-                HIPCHK(hipMemcpy2DAsync(pp.peaks, sizeof(float), &limRes->peak_out, sizeof(dmx_limit_result), sizeof(float), (size_t)pcm->nOut,
-                                        hipMemcpyDeviceToDevice, s));
-                LimitPiece mq;
-                static_cast<RemixPiece &>(mq) = pp;
-                mq.gains = gains;
-                mq.gplane = (const float *)(limWork + lim_ws_gain_offset(lp.n));
-                mq.gplaneStride = job.link ? 0 : envBytes / 4;
-                r.limitEnc.push_back(mq);
-                continue;
-            }
-            if (pcm->byTruePeak())
-                launch_loud_gain_tp(work, slotBytes, pcm->nOut, pp.peaks, tp, pcm->loudMode(), (int)rintf(100.0f * pcm->loud->target_lufs),
-                                    pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
+                r.limitEnc.push_back(piece);
             else
-                launch_loud_gain(work, slotBytes, pcm->nOut, pp.peaks, pcm->loudMode(), (int)rintf(100.0f * pcm->loud->target_lufs),
-                                 pcm->loud->max_peak, pcm->loudTable, gains, gains + 16, s);
-            LoudPiece lq;
-            static_cast<RemixPiece &>(lq) = pp;
-            lq.gains = gains;
-            r.loudEnc.push_back(lq);
+                r.loudEnc.push_back(piece);
         }
         if (pcm->limited())
             launch_limit_encode(r.limitEnc.data(), (int)r.limitEnc.size(), *pcm->remix, pcm->spec.encoding, pcm->spec.clip, s);
@@ -619,17 +557,19 @@ static int tracks_copy_pcm(TracksRun &r, int k, const PcmRange &g)
     if (last && pcm->peaks)
         HIPCHK(hipMemcpyAsync(pcm->peaks + (size_t)g.t * pcm->nOut, sl.peaks.p, sizeof(float) * (size_t)pcm->nOut, hipMemcpyDeviceToHost,
                               c->copyStream));
-    if (last && pcm->report) // the report leaves with the peaks
-        HIPCHK(hipMemcpyAsync(pcm->report + (size_t)g.t * (pcm->nOut + 1),
-                              (const unsigned char *)sl.loud.p + (size_t)((pcm->nOut + 1) * loud_workspace_bytes(n) + 64),
-                              sizeof(dmx_loudness_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
-    if (last && pcm->limit && pcm->limited()) // the limiter's results
-        HIPCHK(hipMemcpyAsync(pcm->limit + (size_t)g.t * pcm->nOut,
-                              (const unsigned char *)sl.loud.p + (size_t)pcm->limResOffset(n),
-                              sizeof(dmx_limit_result) * (size_t)pcm->nOut, hipMemcpyDeviceToHost, c->copyStream));
-    if (last && pcm->meters) // and the meters report
-        HIPCHK(hipMemcpyAsync(pcm->meters + (size_t)g.t * (pcm->nOut + 1), (const unsigned char *)sl.loud.p + (size_t)(pcm->tpOffset(n) + 64),
-                              sizeof(dmx_meters_result) * (size_t)(pcm->nOut + 1), hipMemcpyDeviceToHost, c->copyStream));
+    if (!last || !pcm->loud)
+        return DMX_OK;
+    const LoudChain L = pcm->chain(n);
+    const unsigned char *work = (const unsigned char *)sl.loud.p;
+    if (pcm->report) // the report leaves with the peaks
+        HIPCHK(hipMemcpyAsync(pcm->report + (size_t)g.t * (pcm->nOut + 1), work + L.report, sizeof(dmx_loudness_result) * (size_t)(pcm->nOut + 1),
+                              hipMemcpyDeviceToHost, c->copyStream));
+    if (pcm->limit && pcm->limited()) // the limiter's results
+        HIPCHK(hipMemcpyAsync(pcm->limit + (size_t)g.t * pcm->nOut, work + L.limRes, sizeof(dmx_limit_result) * (size_t)pcm->nOut,
+                              hipMemcpyDeviceToHost, c->copyStream));
+    if (pcm->meters) // and the meters report
+        HIPCHK(hipMemcpyAsync(pcm->meters + (size_t)g.t * (pcm->nOut + 1), work + L.meters, sizeof(dmx_meters_result) * (size_t)(pcm->nOut + 1),
+                              hipMemcpyDeviceToHost, c->copyStream));
     return DMX_OK;
 }
 

@@ -175,6 +175,61 @@ def test_without_the_flag_the_new_entry_point_gives_the_bytes_of_the_old_ones(dm
     assert _same(new[0], want[0]) and new[1].tobytes() == want[1].tobytes()
 
 
+def _documented_work_bytes(dmx, n_out, n, meters, limited):
+    """d_work of dmx_loud_encode(_meters | _limit)_device as include/demucs_hip.h states it"""
+    per = dmx.loudness_workspace_bytes(n) + (dmx.meters_workspace_bytes(n) if meters else 0)
+    plain = (n_out + 1) * per + 64
+    return (plain + 63) // 64 * 64 + n_out * (dmx.limiter_workspace_bytes(n) + 64) if limited else plain
+
+
+@pytest.mark.parametrize("meters", (False, True), ids=("plain", "meters"))
+@pytest.mark.parametrize("mode", (ls.EACH, ls.MIXTURE | lim.LIMIT, ls.EACH | lim.LIMIT | ms.TRUE_PEAK, ls.EACH | ms.TRUE_PEAK),
+                         ids=("each", "mixture-limit", "each-limit-tp", "each-tp"))
+@pytest.mark.parametrize("n_out", (1, 8))
+@pytest.mark.parametrize("n", (1, 2049))
+def test_the_stage_stays_inside_its_documented_workspace(dmx, n, n_out, mode, meters):
+    """the device entry point on a workspace of exactly the documented bytes between two guards of 4096 bytes: the guards are
+    untouched, and everything it returns is, byte for byte, what the host call (which allocates its own workspace) returns.
+    n_out = 8 fills the 64 bytes that the gains and the true peaks share; n = 2049 is one frame past the limiter's tile"""
+    import ctypes
+    import torch
+    S, rate, guard = 2, 44100, 4096
+    v = np.stack([lcs.signal(n, "noise")] * S)
+    mix = v.sum(axis=0).astype(np.float32)
+    g = np.array([[1.0 + 0.25 * o, 0.5 - 0.125 * o, 0.125 * (o % 3)] for o in range(n_out)], np.float32)
+    spec = dmx.RemixSpec(g, 1, 0)
+    loud = dmx.LoudnessSpec(mode & 0xff, TARGET, STAGE_CEILING, true_peak=bool(mode & ms.TRUE_PEAK), limit=bool(mode & lim.LIMIT))
+    assert loud.mode == mode
+    want = dmx.loud_encode(v, mix, spec, loud, rate, meters=meters, limit_report=True)
+    dev = torch.device("cuda:0")
+    stride = (n * 4 + 15) // 16 * 16
+    bytes_ = _documented_work_bytes(dmx, n_out, n, meters, bool(mode & lim.LIMIT))
+    d_in = torch.from_numpy(v).to(dev)
+    d_mix = torch.from_numpy(np.ascontiguousarray(mix.T)).to(dev)
+    d_out = torch.zeros(n_out * stride, dtype=torch.uint8, device=dev)
+    d_peaks = torch.zeros(n_out, dtype=torch.float32, device=dev)
+    d_report = torch.zeros((n_out + 1) * dmx.LOUDNESS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_meters = torch.zeros((n_out + 1) * dmx.METERS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_limit = torch.full((n_out * dmx.LIMIT_DTYPE.itemsize,), 0x5A, dtype=torch.uint8, device=dev)
+    d_work = torch.full((guard + bytes_ + guard,), 0xA5, dtype=torch.uint8, device=dev)
+    assert (d_work.data_ptr() + guard) % 16 == 0
+    lspec = loud.limiter()
+    dmx._chk(dmx.lib().dmx_loud_encode_limit_device(0, d_in.data_ptr(), S, n, n, d_mix.data_ptr(), ctypes.byref(spec.c), ctypes.byref(loud), rate,
+                                                    d_out.data_ptr(), d_peaks.data_ptr(), d_report.data_ptr(), d_work.data_ptr() + guard, None,
+                                                    d_meters.data_ptr() if meters else None, ctypes.byref(lspec), d_limit.data_ptr()))
+    torch.cuda.synchronize()
+    w = d_work.cpu().numpy()
+    assert (w[:guard] == 0xA5).all(), "the guard in front of d_work was written"
+    assert (w[guard + bytes_:] == 0xA5).all(), f"written past the documented {bytes_} bytes of d_work"
+    out = d_out.cpu().numpy()
+    assert [out[o * stride:o * stride + n * 4].tobytes() for o in range(n_out)] == [np.ascontiguousarray(a).tobytes() for a in want[0]]
+    assert d_peaks.cpu().numpy().tobytes() == want[1].tobytes()
+    assert d_report.cpu().numpy().tobytes() == want[2].tobytes()
+    if meters:
+        assert d_meters.cpu().numpy().tobytes() == want[3].tobytes()
+    assert d_limit.cpu().numpy().tobytes() == want[-1].tobytes()
+
+
 # ------------------------------------------------------------------------------------------------ the track path
 @pytest.fixture(scope="module")
 def run(dmx, tmp_models):
