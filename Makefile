@@ -18,12 +18,12 @@ OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_ro
 
 all: $(LIB) cli oracle interp op_step plan_harness chain_harness rates_harness att_harness flac_in_host flac_host loudness_host meters_host limiter_host harness micro
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/loud_chain.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/loud_chain.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_tiles.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@ $(QUIET)
 # the limiter's products are separate roundings: contraction off for the whole file
 build/limiter.o: HIPFLAGS += -ffp-contract=off
-build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/loud_chain.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
+build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/loud_chain.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_tiles.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@ $(QUIET)
 
@@ -44,7 +44,7 @@ interp:
 # OP_STEP_OUT=... builds the sanitizer form)
 OP_STEP_OUT ?= tests/_build/op_step_main
 op_step: $(OP_STEP_OUT)
-$(OP_STEP_OUT): tests/op_step_main.cpp tests/cpu_interp.cpp $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp
+$(OP_STEP_OUT): tests/op_step_main.cpp tests/cpu_interp.cpp $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp $(CSRC)/gemm_select.h $(CSRC)/gemm_tiles.h
 	@mkdir -p $(dir $@)
 	g++ -O2 -g -std=c++17 -fopenmp $(CXXFLAGS_OP_STEP) -o $@ tests/op_step_main.cpp
 # the multi-track plan (csrc/tracks_plan.cpp: host arithmetic, no HIP) as a stand-alone CPU program that prints it as JSON
@@ -70,7 +70,7 @@ $(RATES_OUT): tests/track_rates_harness.cpp $(CSRC)/tracks_plan.cpp $(CSRC)/trac
 	g++ -O2 -g -std=c++17 -Wall $(CXXFLAGS_RATES) -o $@ tests/track_rates_harness.cpp $(CSRC)/tracks_plan.cpp
 # the attention form rule (csrc/attention_select.h: host arithmetic, no HIP) over the plans a context builds, as a stand-alone CPU program
 att_harness: tests/_build/attention_select_harness
-tests/_build/attention_select_harness: tests/attention_select_harness.cpp $(CSRC)/attention_select.h $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp $(CSRC)/gemm_select.h
+tests/_build/attention_select_harness: tests/attention_select_harness.cpp $(CSRC)/attention_select.h $(CSRC)/plan.cpp $(CSRC)/plan.h $(CSRC)/model_pack.cpp $(CSRC)/gemm_select.cpp $(CSRC)/gemm_select.h $(CSRC)/gemm_tiles.h
 	@mkdir -p tests/_build
 	g++ -O2 -std=c++17 -Wall -o $@ tests/attention_select_harness.cpp
 

@@ -222,9 +222,7 @@ static int ctx_init(dmx_ctx *c, const dmx_model *m, int64_t segment_samples, int
         // dmx_ctx_set_model may bind a model whose K / V projections take the operand-plane form when this one's do not (the
         // decision follows the model's weights, dmx_get_plan): the arena is sized for the larger layout, planes on
         Plan q;
-        PlanOpts o;
-        o.gemm = gemm, o.kvPlanes = 1;
-        build_plan(m->pm, c->seg, max_batch, q, o);
+        build_plan(m->pm, c->seg, max_batch, q, plan_opts_from_env(gemm, true));
         c->arenaFloats = std::max(c->arenaFloats, q.arenaFloats);
     }
     // + 1 KB of slack behind the last activation for the same prefetch

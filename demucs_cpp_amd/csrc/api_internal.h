@@ -189,8 +189,6 @@ int dmx_ctx_sync_checked(dmx_ctx *c);
 
 // ---- exec.cpp, used by api.cpp and debug_api.cpp
 dmx::GemmModelFacts dmx_model_facts(const dmx_model *m);       // what the kernel selection reads of a model (gemm_select.h)
-bool dmx_validate_gemm(const dmx::Op &op, std::string &why);  // one OP_IGEMM: staging alignment + kernel availability
-bool dmx_validate_plan(const dmx::Plan &p, std::string &why); // every OP_IGEMM of a plan
 dmx::Plan *dmx_get_plan(dmx_ctx *c, int batch);               // the context's plan for `batch`, built and chosen on first use
 int dmx_launch_op(const dmx_ctx *c, const dmx::Op &op, hipStream_t s, dmx::i64 zeroOff); // one op of a plan on stream s
 namespace dmx { extern std::mutex g_graphMutex; }             // every HIP graph API call of the process holds it

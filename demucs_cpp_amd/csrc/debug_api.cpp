@@ -344,24 +344,14 @@ extern "C" int dmx_debug_run_op(dmx_ctx *c, int batch, int i)
     return dmx_ctx_sync_checked(c);
 }
 
-// the tile cfgs op i can be asked to run on: the chain choose_cfg -> half_cfg -> ... of its shape, and cfg 19 / 20 where their
-// shape conditions hold (fp32 contexts: plan.cpp finish); returns the count, -1 if op i is no OP_IGEMM of the plan
+// the tile cfgs op i can be asked to run on (gemm_select.h gemm_tile_chain); returns the count, -1 if op i is no OP_IGEMM of the plan
 extern "C" int dmx_debug_op_cfgs(dmx_ctx *c, int batch, int i, int *cfgs, int cap)
 {
     Plan *p = nullptr;
     const Op *op = debug_op(c, batch, i, &p);
     if (!op || op->kind != OP_IGEMM || !cfgs)
         return -1;
-    const IGemm &g = op->g;
-    const bool paired = g.epi == EPI_GLU || g.epi == EPI_GN_GLU_SCALE_RES;
-    int n = 0;
-    for (int cfg = choose_cfg((i64)g.P1 * g.P0, g.N, paired); cfg >= 0 && n < cap; cfg = half_cfg(cfg, g.rowstat >= 0))
-        cfgs[n++] = cfg;
-    if (c->gemm == DMX_GEMM_F32 && lin256_shape(g) && n < cap)
-        cfgs[n++] = 19;
-    if (c->gemm == DMX_GEMM_F32 && shortk_shape(g) && kTileCfgs[g.cfg].BN == 96 && n < cap)
-        cfgs[n++] = 20;
-    return n;
+    return gemm_tile_chain(op->g, c->gemm, cfgs, cap);
 }
 
 // Runs a COPY of OP_IGEMM i on tile cfg `cfg`: NB from the tile, the kernel select_gemm gives for the context's GEMM mode, the

@@ -604,24 +604,21 @@ static void launch_d(const GemmArgs &a, hipStream_t s, int chunks = 1)
                        make_fastdiv((unsigned)a.P1));
 }
 
-// Direct kernel table. key = NF*1000000 + S1*100000 + SEG0*100 + PRO*10 + EPI. Returns 0, or -1 if
-// the combination is not instantiated (the plan then keeps the LDS-tiled igemm).
-int launch_dgemm(const GemmArgs &a, hipStream_t s, bool dry)
+// The direct kernels are DMX_DIRECT_COMBOS and the column-chunk rule direct_chunked (gemm_tiles.h: gemm_select.cpp sends an op here,
+// and answers whether its kernel exists, from the same list). Returns 0, or -1 if the combination is not instantiated.
+int launch_dgemm(const GemmArgs &a, hipStream_t s)
 {
-    const int NF = (a.N + 15) / 16;
     if (a.M >= (1ll << 31) - 16 || (i64)a.L0 * a.Cin >= (1ll << 31))
         return -1;
     if ((a.epi == EPI_LINEAR || a.epi == EPI_TRCONV) && a.res)
         return -1; // residual adds of these epilogues stay with the LDS-tiled kernel
-#define DMX_D(NF_, S1_, SEG_, PRO_, EPI_, PIPE_)                              \
-    case (NF_ * 1000000 + S1_ * 100000 + SEG_ * 100 + PRO_ * 10 + EPI_):      \
-        if (!dry)                                                             \
-            launch_d<NF_, S1_, SEG_, PRO_, EPI_, PIPE_>(a, s);                \
+#define DMX_D(NF_, S1_, SEG_, PRO_, EPI_, PIPE_)           \
+    case direct_key(NF_, S1_, SEG_, PRO_, EPI_):           \
+        launch_d<NF_, S1_, SEG_, PRO_, EPI_, PIPE_>(a, s); \
         return 0;
     if (k1_ring_ok(a) && (a.seg0 == 48 || a.seg0 == 96))
     {
-        if (!dry)
-            a.seg0 == 48 ? launch_k1_ring<48>(a, s) : launch_k1_ring<96>(a, s);
+        a.seg0 == 48 ? launch_k1_ring<48>(a, s) : launch_k1_ring<96>(a, s);
         return 0;
     }
     // DConv k3 of the deep levels (C = 192 / 384: hidden 24 / 48 -> 2C = 384 / 768 packed columns; layers.cpp:204-259): the
@@ -630,50 +627,24 @@ int launch_dgemm(const GemmArgs &a, hipStream_t s, bool dry)
     // channels of the residual in and out) with its 192 x K weights resident, instead of a 128x128 GEMM tile whose single
     // half-empty K-tile made the op all prologue and epilogue (round 3: 1.7-2.3 TB/s). The chunks touch disjoint columns of
     // the in-place tensor; arithmetic per output = the direct kernels' (k ascending, remainder k-slots last).
-    if (a.pro == PRO_GN_GELU && a.epi == EPI_GN_GLU_SCALE_RES && a.S1 == 1 && (a.seg0 == 24 || a.seg0 == 48) && a.N > 192 && a.N % 192 == 0)
+    if (direct_chunked(a.N, a.S1, a.seg0, a.pro, a.epi))
     {
-        if (!dry)
-        {
-            // chunk width: 192 columns keep 12 x K weights in registers (268 / 351 VGPRs: one wave per SIMD) and read the hidden
-            // row N / 192 times; 96 columns (6 fragments, ~130 VGPRs: three to four waves per SIMD) read it N / 96 times.
-            // 96 is the measured winner (profiles/DESIGN_history_r1-r4.md section 7.6)
-            const int cw = 96;
-            GemmArgs c = a; // ONE launch: grid row y = chunk y (the kernel offsets its column-indexed operands by y * N)
-            c.N = c.Np = cw;
-            const int chunks = a.N / cw;
-            if (cw == 192)
-                a.seg0 == 24 ? launch_d<12, 1, 24, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 1>(c, s, chunks) : launch_d<12, 1, 48, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0>(c, s, chunks);
-            else
-                a.seg0 == 24 ? launch_d<6, 1, 24, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0>(c, s, chunks) : launch_d<6, 1, 48, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0>(c, s, chunks);
-        }
+        // chunk width: 192 columns keep 12 x K weights in registers (268 / 351 VGPRs: one wave per SIMD) and read the hidden
+        // row N / 192 times; 96 columns (6 fragments, ~130 VGPRs: three to four waves per SIMD) read it N / 96 times.
+        // 96 is the measured winner (profiles/DESIGN_history_r1-r4.md section 7.6)
+        const int cw = 96;
+        GemmArgs c = a; // ONE launch: grid row y = chunk y (the kernel offsets its column-indexed operands by y * N)
+        c.N = c.Np = cw;
+        const int chunks = a.N / cw;
+        if (cw == 192)
+            a.seg0 == 24 ? launch_d<12, 1, 24, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 1>(c, s, chunks) : launch_d<12, 1, 48, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0>(c, s, chunks);
+        else
+            a.seg0 == 24 ? launch_d<6, 1, 24, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0>(c, s, chunks) : launch_d<6, 1, 48, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0>(c, s, chunks);
         return 0;
     }
-    switch (NF * 1000000 + a.S1 * 100000 + a.seg0 * 100 + a.pro * 10 + a.epi)
+    switch (direct_key((a.N + 15) / 16, a.S1, a.seg0, a.pro, a.epi))
     {
-        // DConv k1: Conv1d(C -> C/8, k3): C = 48, 96 (time branch; the frequency branch takes the ring kernel above)
-        DMX_D(1, 3, 48, PRO_NONE, EPI_LINEAR, 0)
-        DMX_D(1, 3, 96, PRO_NONE, EPI_LINEAR, 1)
-        // DConv k2 / k3: hidden 8 (C=48) / 12 (C=96) -> 2C, statistics / final
-        DMX_D(6, 1, 8, PRO_GN_GELU, EPI_STATS_ONLY, 2)
-        DMX_D(1, 1, 8, PRO_GN_GELU, EPI_STATS_FACT, 0)
-        DMX_D(1, 1, 12, PRO_GN_GELU, EPI_STATS_FACT, 0)
-        DMX_D(6, 1, 8, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0)
-        DMX_D(12, 1, 12, PRO_GN_GELU, EPI_STATS_ONLY, 0)
-        DMX_D(12, 1, 12, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 1)
-        // Demucs v3 DConv (hidden C/4): k3 for hidden 12 (C=48) / 24 (C=96), factorised statistics for hidden 24
-        DMX_D(6, 1, 12, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 0)
-        DMX_D(12, 1, 24, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES, 1)
-        DMX_D(2, 1, 24, PRO_GN_GELU, EPI_STATS_FACT, 0)
-        // first encoder convs (z-norm prologue) k8 s4: Cin = 4 (freq), 2 (time)
-        DMX_D(3, 1, 32, PRO_AFFINE, EPI_LINEAR, 0)
-        DMX_D(3, 1, 16, PRO_AFFINE, EPI_LINEAR, 0)
-        // level-0 rewrites 48 -> 96 + GLU
-        DMX_D(6, 1, 48, PRO_NONE, EPI_GLU, 0)
-        // last transposed convs 48 -> 4*Cout: Cout = 16 / 8 (4 sources), 24 / 12 (6 sources)
-        DMX_D(4, 1, 96, PRO_NONE, EPI_TRCONV, 0)
-        DMX_D(2, 1, 96, PRO_NONE, EPI_TRCONV, 0)
-        DMX_D(6, 1, 96, PRO_NONE, EPI_TRCONV, 0)
-        DMX_D(3, 1, 96, PRO_NONE, EPI_TRCONV, 0)
+        DMX_DIRECT_COMBOS(DMX_D)
     default:
         return -1;
     }

@@ -17,8 +17,7 @@
 
 using namespace dmx;
 
-// the geometry of an op as the kernels see it (no pointers): dmx_launch_op adds the pointers; the launchers' existence queries
-// (dmx_validate_plan) read only this
+// the geometry of an op as the kernels see it (no pointers): dmx_launch_op adds the pointers
 static void fill_gemm_geometry(GemmArgs &k, const IGemm &g)
 {
     k.xBS = g.xBatchStride;
@@ -42,41 +41,6 @@ GemmModelFacts dmx_model_facts(const dmx_model *m)
     f.planeDelta = (i64)m->blobFloats + 512; // (dmx_model_upload)
     f.inexactW = &m->inexactW, f.inexactH = &m->inexactH;
     return f;
-}
-
-// alignment contract of the igemm staging loads (igemm.hip header) + kernel availability, one OP_IGEMM
-bool dmx_validate_gemm(const Op &op, std::string &why)
-{
-    const IGemm &g = op.g;
-    const bool al = ((i64)g.L0 * g.Cin) % 4 == 0 && (g.stride0 * g.Cin) % 4 == 0 && (g.pad0 * g.Cin) % 4 == 0 &&
-                    g.seg0 % 4 == 0 && g.K % 4 == 0 && g.xBatchStride % 4 == 0 && (g.S1 == 1 || g.seg0 % 16 == 0) &&
-                    (g.cfg == kDirectCfg || (g.Cin % 4 == 0 && g.seg0 % g.Cin == 0 && g.S1 * (g.seg0 / g.Cin) <= 31)); // one validity bit per tap (igemm.hip)
-    if (g.epi == EPI_KPL || g.epi == EPI_VT) // exist on the exact-split kernels only; build_chosen_plan keeps them only there
-    {
-        if (g.choice.arith == 0)
-        {
-            why = "op " + op.name + ": K / V plane projection without its exact-split kernel";
-            return false;
-        }
-        return true;
-    }
-    // the fp32 kernel must exist for split ops too: dmx_ctx_set_model may bind a model whose weights turn them to fp32
-    GemmArgs k{};
-    fill_gemm_geometry(k, g);
-    const bool exists = (g.cfg == kDirectCfg ? launch_dgemm(k, nullptr, true) : launch_igemm(g.cfg, k, nullptr, true)) == 0;
-    if (!al || !exists)
-    {
-        why = "op " + op.name + (al ? ": no kernel instantiated for its (tile, prologue, epilogue)" : ": staging alignment contract violated");
-        return false;
-    }
-    return true;
-}
-bool dmx_validate_plan(const Plan &p, std::string &why)
-{
-    for (const Op &op : p.ops)
-        if (op.kind == OP_IGEMM && !dmx_validate_gemm(op, why))
-            return false;
-    return true;
 }
 
 Plan *dmx_get_plan(dmx_ctx *c, int batch)

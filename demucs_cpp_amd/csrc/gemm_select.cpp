@@ -6,39 +6,153 @@
 namespace dmx
 {
 
-// The A/B switch of the exact-split kernels: 1 (default) = every kernel where it applies and pays; 0 = linear layers on the staged
-// 2 x 2-wave kernel and no wide tile (the K / V plane projections, which exist on the linear-layer kernels only, behave as under 1);
-// 2 = never a wide tile; 3 = the wide tiles wherever they exist; 4 = as 1 with the 96-wide layers on the staged tile (bitwise A/B:
-// tools/gpu_lin_ab.py)
-int split_lin_mode()
+// One function reads the switches. DMX_SPLIT_LIN, the A/B switch of the exact-split kernels: 1 (default) = every kernel where it
+// applies and pays; 0 = linear layers on the staged 2 x 2-wave kernel and no wide tile (the K / V plane projections, which exist on
+// the linear-layer kernels only, behave as under 1); 2 = never a wide tile; 3 = the wide tiles wherever they exist; 4 = as 1 with the
+// 96-wide layers on the staged tile (bitwise A/B: tools/gpu_lin_ab.py). The others: 0 switches the tile / the op off (A/B).
+PlanOpts plan_opts_from_env(int gemm, bool kvPlanes)
 {
-    static const int mode = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
-    return mode;
+    static const int splitLin = [] { const char *e = getenv("DMX_SPLIT_LIN"); return e ? atoi(e) : 1; }();
+    auto on = [](const char *e) { return !e || atoi(e) != 0; };
+    PlanOpts o;
+    o.gemm = gemm, o.kvPlanes = kvPlanes ? 1 : 0;
+    o.sw.splitLin = splitLin, o.sw.lin256 = on(getenv("DMX_LIN256")), o.sw.shortK = on(getenv("DMX_SHORTK"));
+    o.dconvRow = on(getenv("DMX_DCONV_ROW"));
+    return o;
 }
+int split_lin_mode() { return plan_opts_from_env(GEMM_F32, false).sw.splitLin; }
 
-static const char *const kCfgNames[] = {"igemm_128x128", "igemm_64x64", "igemm_128x96", "igemm_128x48", "igemm_256x16", "igemm_128x32",
-                                        "igemm_128x64",  "igemm_64x128", "dgemm_direct", "igemm_64x64", "igemm_64x96", "igemm_64x48",
-                                        "igemm_64x32",   "igemm_64x64",  "igemm_128x16", "igemm_32x128", "igemm_32x64", "igemm_256x128", "igemm_256x128w4", "igemm_lin256x128", "igemm_256x96"};
-static_assert(sizeof(kCfgNames) / sizeof(kCfgNames[0]) == kNumTileCfgs, "one label per tile configuration");
-
-// the exact-split kernel of a tile cfg: its own roofline class
-static const char *const kSplitNames[kNumTileCfgs] = {"igemm_split_128x128", nullptr, "igemm_split_128x96", "igemm_split_128x48", nullptr, "igemm_split_128x32d", "igemm_split_128x64d",
-                                                      "igemm_split_64x128", nullptr, "igemm_split_64x64", "igemm_split_64x96", "igemm_split_64x48",
-                                                      "igemm_split_128x32d", "igemm_split_128x64d", nullptr, "igemm_split_32x128", "igemm_split_32x64"};
-
-static bool split_combo_exists(int cfg, int pro, int epi)
+// ---------------------------------------------------------------------------------------------------------------- the tile of an op
+// The tile family of a width: never a function of the batch size, so results are bit-identical for any batching / sharding of
+// segments. The 2 x 4 family comes out as cfg 0: refine_cfg walks down its chain 0 -> 7 -> 15 / 9 -> 16 from the ACTUAL
+// row count (round 3: a nominal-batch choice between 0 and 7 kept the time-branch linears on 64x128 tiles even at 42 segments)
+static int choose_cfg(int N, bool paired)
 {
-#define DMX_CASE(cfgid, WM_, WN_, MF, NF, PRO, EPI) case (cfgid * 100 + PRO * 10 + EPI):
-    switch (cfg * 100 + pro * 10 + epi)
+    if (!paired)
     {
-        DMX_SPLIT_COMBOS(DMX_CASE)
-        return true;
-    default:
-        return false;
+        if (N <= 16)
+            return 4;
+        if (N <= 32)
+            return 5;
+        if (N <= 48)
+            return 3;
     }
-#undef DMX_CASE
+    else if (N <= 32)
+        return 5;
+    if (N <= 64)
+        return 6;
+    if (N <= 96)
+        return 2;
+    if (N % 128 != 0 && N % 96 == 0)
+        return 2;
+    return 0;
 }
 
+// Tile for an op at the ACTUAL number of rows M (all segments in flight): the largest tile of the chain cfg -> half_cfg(cfg) -> ...
+// that keeps the 256 CUs evenly busy. Work per CU is what counts (co-resident workgroups share one matrix pipe per SIMD). A launch
+// of T tiles puts n = ceil(T / 256) workgroups on its busiest CU; two resident workgroups hide each other's ds_read / barrier /
+// staging latencies, ONE does not (measured at one segment per call: 252 tiles of 128x128 take 1.8x as long as
+// 504 of 64x128 for the same op, decoder.1.rewrite 224 -> 126 us; the 3 qkv linears 71 -> 50 us). So the cost of
+// a tile shape is  (n == 1 ? 1.7 : n) x tile area x (1 + small-tile overhead: staging bytes per MFMA grow as the
+// tile shrinks: +3 % per halving, from forced-half runs at batch 24),
+// minimised over the chain of bit-identical half-height siblings. Large batches keep the big tile; one segment
+// (M = 2688 / 1344 rows) gets 64x64 tiles for its transformer linears.
+static int refine_cfg(int cfg, i64 M, int N, bool stat)
+{
+    auto cost = [&](int c, int depth) {
+        // the XCD-aware tile map (igemm.hip) deals ROW tiles round-robin to the 8 XCDs and runs all column tiles of a row
+        // tile on that XCD: the busiest XCD holds ceil(tilesM / 8) x tilesN workgroups for its 32 CUs. (Counting T / 256
+        // instead missed e.g. 84 x 6 tiles = 11 row tiles on four of the XCDs = 66 workgroups for 64 slots: a second
+        // round for two stragglers, decoder.0.rewrite at 4 segments 617 us with 128x128 vs 428 us with 64x128.)
+        const i64 tm = (M + kTileCfgs[c].BM - 1) / kTileCfgs[c].BM, tn = (N + kTileCfgs[c].BN - 1) / kTileCfgs[c].BN;
+        const i64 n = (((tm + 7) / 8) * tn + 31) / 32;
+        return (n == 1 ? 1.7 : (double)n) * (double)(kTileCfgs[c].BM * kTileCfgs[c].BN) * (1.0 + 0.03 * depth);
+    };
+    int best = cfg;
+    double bestCost = cost(cfg, 0);
+    int depth = 1;
+    for (int c = half_cfg(cfg, stat); c >= 0; c = half_cfg(c, stat), ++depth)
+        if (cost(c, depth) < bestCost * 0.95) // the model is good to a few per cent: leave the default tile unless it is clear
+        {
+            best = c;
+            bestCost = cost(c, depth);
+        }
+    return best;
+}
+
+// The shapes of the two tiles choose_tile reaches from another tile by the ROW COUNT of a launch: everything but that count (the
+// debug entry points of debug_api.cpp run an op on them at small sizes: gemm_tile_chain).
+// cfg 19 (igemm_lin256.hip refuses anything else at run time): plain linear layers, residual and scale present where the epilogue
+// reads them; N a multiple of 512 only: with three column tiles (N = 384: the channel up / down samplers) half as many, twice as
+// large workgroups quantise worse on the 64 slots of an XCD than they gain (measured 126 -> 115, 121 -> 111 TFLOP/s)
+static bool lin256_shape(const IGemm &g)
+{
+    return lin256_addressing(g) && (g.epi != EPI_SCALE_RES || (g.res >= 0 && g.scale_w >= 0)) && g.N % 512 == 0;
+}
+// cfg 20: the short-K ops of the 128x96 family, no row statistics
+static bool shortk_shape(const IGemm &g)
+{
+    return g.rowstat < 0 && g.pro == PRO_NONE && (g.epi == EPI_LINEAR || g.epi == EPI_GLU || g.epi == EPI_TRCONV) && g.K <= 160;
+}
+
+// The HBM-bound layers the direct kernels (dgemm.hip) take from the tiles. They carry no residual operand for the LINEAR / TRCONV
+// epilogues.
+static bool direct_residual_ok(const IGemm &g) { return !((g.epi == EPI_LINEAR || g.epi == EPI_TRCONV) && g.res >= 0); }
+static bool takes_direct(const IGemm &g, int gemm)
+{
+    // the level-0 1x1 rewrites (48 -> 96 + GLU) of an exact-split context run on the 128 x 96 direct-fragment split tile
+    // (igemm_split.hip, round 6): 0.900 -> 0.815 / 0.435 -> 0.386 ms at 42 segments against the fp32 direct kernel, which
+    // sits on the fp32 matrix pipe's ridge; an fp32 context keeps the direct kernel (its tiled fp32 form is 20 % slower)
+    const bool rewrite0Split = gemm != GEMM_F32 && g.pro == PRO_NONE && g.epi == EPI_GLU && g.S1 == 1 && g.seg0 == 48 && g.N == 96;
+    // likewise the frequency branch's last transposed conv (48 -> 4 x Cout, K = 96): N = 64 (4 sources; igemm_split.hip
+    // narrow tile, narrow_split_ok: 0.947 -> 0.917 ms) and N = 96 (6 sources: 1.57 -> 1.22 ms). The time branch's (N = 32 / 48) stays on
+    // the direct kernel (N = 32 measured: 0.286 -> 0.293 ms)
+    const bool lastTrSplit = gemm != GEMM_F32 && g.pro == PRO_NONE && g.epi == EPI_TRCONV && g.S1 == 1 && g.seg0 == 96 && (g.N == 64 || g.N == 96);
+    return direct_residual_ok(g) && !rewrite0Split && !lastTrSplit && direct_combo_exists(g.N, g.S1, g.seg0, g.pro, g.epi);
+}
+
+TileChoice choose_tile(const IGemm &g, bool paired, bool pin128Wide, int gemm, const GemmSwitches &sw)
+{
+    const i64 M = (i64)g.B * g.P1 * g.P0;
+    int cfg = refine_cfg(choose_cfg(g.N, paired), M, g.N, g.rowstat >= 0);
+    // (the operand-split path has no 256x128 / 256x96 form: its ops stay on the tiles igemm_split.hip instantiates)
+    if (gemm == GEMM_F32)
+    {
+        // plain linear layers that keep the 128x128 tile (i.e. enough rows to fill the chip a few times over) run on the 256x128 /
+        // four-wave kernel: the shape and at least three rounds of its workgroups on the 64 slots of an XCD (the tile map deals row
+        // tiles to XCDs): at 1.75 rounds (time-branch linears with N = 512 at 42 segments) the 128x128 tile is 10 % faster
+        const i64 perXcd = (((M + 255) / 256 + 7) / 8) * ((g.N + 127) / 128);
+        if (sw.lin256 && lin256_shape(g) && cfg == 0 && perXcd >= 192)
+            cfg = 19;
+        // short-K ops of the 128x96 family (K <= 160: the level-1 1x1 rewrites, K = 96, and the time branch's last k3
+        // rewrite, K = 144) run on the 256x96 tile with 16-deep K-tiles (cfg 20, plain loop): no half-empty last K-tile
+        // (144 = 4.5 x 32) and a shorter pipeline fill - measured 88.8 -> 101.9, 84.6 -> 93.9, 90.4 -> 94.8 TFLOP/s at 42
+        // segments; longer K stays on the interleaved 32-deep loop (decoder.3.rewrite, K = 432: 121 vs 118.7). Same column
+        // decomposition and k order: identical bits.
+        if (sw.shortK && cfg == 2 && shortk_shape(g) && M >= 65536)
+            cfg = 20;
+    }
+    if (takes_direct(g, gemm))
+        cfg = kDirectCfg;
+    if (pin128Wide && cfg != 0 && cfg != 7)
+        cfg = 7;
+    return TileChoice{cfg, (g.N + kTileCfgs[cfg].BN - 1) / kTileCfgs[cfg].BN};
+}
+
+int gemm_tile_chain(const IGemm &g, int gemm, int *cfgs, int cap)
+{
+    const bool paired = g.epi == EPI_GLU || g.epi == EPI_GN_GLU_SCALE_RES;
+    int n = 0;
+    for (int cfg = choose_cfg(g.N, paired); cfg >= 0 && n < cap; cfg = half_cfg(cfg, g.rowstat >= 0))
+        cfgs[n++] = cfg;
+    if (gemm == GEMM_F32 && lin256_shape(g) && n < cap)
+        cfgs[n++] = 19;
+    if (gemm == GEMM_F32 && shortk_shape(g) && kTileCfgs[g.cfg].BN == 96 && n < cap)
+        cfgs[n++] = 20;
+    return n;
+}
+
+// -------------------------------------------------------------------------------------------------------------- the kernel on it
 // no listed (inexact) element inside the op's weights [w_w, w_w + Np * Kp)
 static bool weights_exact(const std::vector<i64> *inexact, const IGemm &g)
 {
@@ -111,7 +225,7 @@ static int wide_conv_width(const IGemm &g, i64 M, int mode)
 //     HBM traffic; here the 88 split operations per 20 MFMAs that kept the staged split tile level with fp32 (round 4) are spread
 //     over four workgroups per CU with nothing else to do (1.10 -> 1.03 ms per 42-segment step: the op is bound by its fragment loads);
 //   cfg 6 / 13, N = 64 (128 x 64, three workgroups per CU): the frequency branch's last transposed conv of a 4-source model
-//     (48 -> 4 x 16, K = 96), which sat on the fp32 matrix pipe at 60 % of its peak in the direct kernel (plan.cpp finish).
+//     (48 -> 4 x 16, K = 96), which sat on the fp32 matrix pipe at 60 % of its peak in the direct kernel (takes_direct).
 // No residual on the linear epilogue; row statistics on the 32-wide linear form only.
 static bool narrow_split_ok(const IGemm &g, int np)
 {
@@ -125,17 +239,18 @@ GemmChoice select_gemm(const IGemm &g, int gemm, const GemmModelFacts &m, int li
     const int cfg = g.cfg;
     if (cfg < 0 || cfg >= kNumTileCfgs) // no such tile: nothing to launch (launch_op reports it)
         return GemmChoice{GF_NONE, 0, 0, "?"};
-    const GemmChoice fp32{cfg == kDirectCfg ? GF_DIRECT : cfg == 19 ? GF_LIN256 : GF_TILE, 0, 0, kCfgNames[cfg]};
+    const TileCfg &t = kTileCfgs[cfg];
+    const GemmChoice fp32{t.kind == TK_DIRECT ? GF_DIRECT : t.kind == TK_LIN256 ? GF_LIN256 : GF_TILE, 0, 0, t.label};
     // exact splits: a split context, the bf16 planes, 32-bit row arithmetic in the kernels' prologues, and every weight the op reads
     // the exact sum of its two planes
-    if (gemm == GEMM_F32 || !m.bf16Planes || M >= (1ll << 31) - 256 || !weights_exact(m.inexactW, g))
+    if (gemm == GEMM_F32 || !m.bf16Planes || !gemm_rows_ok(M) || !weights_exact(m.inexactW, g))
         return fp32;
     if (cfg == 5 || cfg == 12 || cfg == 6 || cfg == 13) // 128x32 / 64x32, 128x64 / 64x64 (4 x 1 waves)
     {
         const int np = (cfg == 5 || cfg == 12) ? 32 : 64;
         if (!narrow_split_ok(g, np))
             return fp32;
-        return GemmChoice{GF_SPLIT_NARROW, 1, np / 16, kSplitNames[cfg]};
+        return GemmChoice{GF_SPLIT_NARROW, 1, np / 16, t.splitLabel};
     }
     if (!split_combo_exists(cfg, g.pro, g.epi))
         return fp32;
@@ -151,7 +266,7 @@ GemmChoice select_gemm(const IGemm &g, int gemm, const GemmModelFacts &m, int li
     if (gemm == GEMM_FP16X3 && m.fp16Plane && g.hterms && linTile && split_lin(g, 0) && weights_exact(m.inexactH, g))
         return GemmChoice{GF_SPLIT_LINH, 2, 0, cfg == 0 ? "igemm_splith_128x128" : "igemm_splith_64x128"};
     const GemmChoice wide256{GF_SPLIT_LINW, 1, 0, "igemm_split_128x256"};
-    const GemmChoice linFrag{GF_SPLIT_LIN, 1, 0, kSplitNames[cfg]};
+    const GemmChoice linFrag{GF_SPLIT_LIN, 1, 0, t.splitLabel};
     if (planes)
         return cfg == 0 && wide_tile_pays(g, M, linMode == 0 ? 1 : linMode) ? wide256 : linFrag;
     // plain linear layers of a width the 128 x 256 linear tile takes go there (below); every other full-height op - strided convs,
@@ -160,7 +275,7 @@ GemmChoice select_gemm(const IGemm &g, int gemm, const GemmModelFacts &m, int li
         if (const int wnf = wide_conv_width(g, M, linMode)) // (96: the tile of cfg 2 with the activation fragments loaded straight into registers)
             return GemmChoice{GF_SPLIT_WIDE_CONV, 1, wnf, wnf == 16 ? "igemm_split_128x256" : wnf == 12 ? "igemm_split_128x192" : "igemm_split_128x96d"};
     if (!lin)
-        return GemmChoice{GF_SPLIT_STAGED, 1, 0, kSplitNames[cfg]};
+        return GemmChoice{GF_SPLIT_STAGED, 1, 0, t.splitLabel};
     if (linTile)
     {
         // activation fragments straight into registers (igemm_split_lin_kernel): same tile size and map, same bits; mode 0 keeps
@@ -172,13 +287,86 @@ GemmChoice select_gemm(const IGemm &g, int gemm, const GemmModelFacts &m, int li
         if (linMode != 0)
             return linFrag;
     }
-    return GemmChoice{GF_SPLIT_STAGED_LIN, 1, 0, kSplitNames[cfg]};
+    return GemmChoice{GF_SPLIT_STAGED_LIN, 1, 0, t.splitLabel};
+}
+
+// ------------------------------------------------------------------------------------------------------------ does it exist
+// (the limits are the launchers': dgemm.hip launch_dgemm, igemm.hip launch_igemm, igemm_lin256.hip lin256_ok)
+bool gemm_fp32_kernel_exists(const IGemm &g)
+{
+    if (g.cfg < 0 || g.cfg >= kNumTileCfgs)
+        return false;
+    const i64 M = (i64)g.B * g.P1 * g.P0;
+    switch (kTileCfgs[g.cfg].kind)
+    {
+    case TK_DIRECT: // 32-bit row and inner-row arithmetic; no residual operand on the LINEAR / TRCONV epilogues
+        return M < (1ll << 31) - 16 && (i64)g.L0 * g.Cin < (1ll << 31) && direct_residual_ok(g) && direct_combo_exists(g.N, g.S1, g.seg0, g.pro, g.epi);
+    case TK_LIN256:
+        return gemm_rows_ok(M) && lin256_addressing(g) && (g.epi != EPI_SCALE_RES || (g.res >= 0 && g.scale_w >= 0));
+    case TK_TILE:
+        return gemm_rows_ok(M) && tile_combo_exists(g.cfg, g.pro, g.epi);
+    default:
+        return false;
+    }
+}
+
+bool gemm_kernel_exists(const IGemm &g)
+{
+    if (g.cfg < 0 || g.cfg >= kNumTileCfgs)
+        return false;
+    const int kind = kTileCfgs[g.cfg].kind;
+    switch (g.choice.family)
+    {
+    case GF_NONE:
+        return false;
+    case GF_DIRECT:
+        return kind == TK_DIRECT && gemm_fp32_kernel_exists(g);
+    case GF_LIN256:
+        return kind == TK_LIN256 && gemm_fp32_kernel_exists(g);
+    case GF_TILE:
+        return kind == TK_TILE && gemm_fp32_kernel_exists(g);
+    case GF_SPLIT_WIDE_CONV:
+    case GF_SPLIT_NARROW:
+        return gemm_rows_ok((i64)g.B * g.P1 * g.P0) && linw_combo_exists(g.choice.wnf, g.epi);
+    default: // the staged and linear-layer families of igemm_split.hip
+        return gemm_rows_ok((i64)g.B * g.P1 * g.P0) && split_combo_exists(g.cfg, g.pro, g.epi) &&
+               split_family_exists(g.choice.family, g.cfg, g.pro, g.epi);
+    }
+}
+
+bool dmx_validate_gemm(const Op &op, std::string &why)
+{
+    const IGemm &g = op.g;
+    const bool al = ((i64)g.L0 * g.Cin) % 4 == 0 && (g.stride0 * g.Cin) % 4 == 0 && (g.pad0 * g.Cin) % 4 == 0 &&
+                    g.seg0 % 4 == 0 && g.K % 4 == 0 && g.xBatchStride % 4 == 0 && (g.S1 == 1 || g.seg0 % 16 == 0) &&
+                    (g.cfg == kDirectCfg || (g.Cin % 4 == 0 && g.seg0 % g.Cin == 0 && g.S1 * (g.seg0 / g.Cin) <= 31)); // one validity bit per tap (igemm.hip)
+    const bool planes = g.epi == EPI_KPL || g.epi == EPI_VT; // exist on the exact-split kernels only; build_chosen_plan keeps them only there
+    if (planes && g.choice.arith == 0)
+    {
+        why = "op " + op.name + ": K / V plane projection without its exact-split kernel";
+        return false;
+    }
+    // the fp32 kernel must exist for split ops too: dmx_ctx_set_model may bind a model whose weights turn them to fp32
+    const bool exists = (planes || gemm_fp32_kernel_exists(g)) && (g.choice.arith == 0 || gemm_kernel_exists(g));
+    if (!al || !exists)
+    {
+        why = "op " + op.name + (al ? ": no kernel instantiated for its (tile, prologue, epilogue)" : ": staging alignment contract violated");
+        return false;
+    }
+    return true;
+}
+bool dmx_validate_plan(const Plan &p, std::string &why)
+{
+    for (const Op &op : p.ops)
+        if (op.kind == OP_IGEMM && !dmx_validate_gemm(op, why))
+            return false;
+    return true;
 }
 
 void build_chosen_plan(const PackedModel &pm, i64 seg, int B, int gemm, bool kvPlanes, const GemmModelFacts &m, int linMode, Plan &plan)
 {
-    PlanOpts opts;
-    opts.gemm = gemm, opts.kvPlanes = kvPlanes ? 1 : 0;
+    PlanOpts opts = plan_opts_from_env(gemm, kvPlanes);
+    opts.sw.splitLin = linMode;
     build_plan(pm, seg, B, plan, opts);
     if (kvPlanes)
         for (const Op &op : plan.ops)

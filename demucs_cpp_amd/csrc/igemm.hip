@@ -35,15 +35,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef DMX_SMALL_KS
-#define DMX_SMALL_KS 2
-#endif
-#ifndef DMX_CFG2_KS
-#define DMX_CFG2_KS 2
-#endif
-#ifndef DMX_BIG_KS
-#define DMX_BIG_KS 2 // experiment: 1 = 16-deep K-tiles for the 128x128 / 64x128 tiles (half the LDS: 3 workgroups per CU)
-#endif
 #ifndef DMX_IGEMM_DIRECT
 #define DMX_IGEMM_DIRECT 0 // 1: kernels without a prologue transform stage global -> LDS directly (global_load_lds_dwordx4).
                            // Measured at batch 24 on the same box: 120.8 (direct) vs 125.2 TFLOP/s (registers) for the
@@ -353,126 +344,45 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, KS == 2 || WMF * WNF >= 24 
     igemm_epilogue<WAVES_N, WMF, WNF, EPI, NT>(p, acc, [&](int r) { return rowinfo[r]; }, rsum, m0, n0, tileN, wm, wn, BM);
 }
 
-template <int WM_, int WN_, int MF, int NF, int KS, int PRO, int EPI>
+// the kernel of (tile cfg, prologue, epilogue): the tile's geometry from the table (gemm_tiles.h); linear-layer addressing where the
+// op has it; the interleaved K loop wherever it is written (KS == 2: every tile but cfg 20)
+template <int CFG, int PRO, int EPI>
 static void launch_one(const GemmArgs &a0, hipStream_t s)
 {
-    constexpr int BM = WM_ * MF * 16, BN = WN_ * NF * 16;
-    constexpr int xcdMap = 1; // XCD-aware tile map (0 = plain row-major tiles: measured slower, round 2)
+    constexpr TileCfg T = kTileCfgs[CFG];
+    constexpr int WM_ = T.WM, WN_ = T.WN, MF = T.MF, NF = T.NF, KS = T.KS;
+    static_assert(T.kind == TK_TILE && (KS == 1 || KS == 2), "a tile of igemm_kernel");
+    constexpr bool IL = KS == 2;
     GemmArgs a = a0;
-    a.tilesM = (unsigned)((a.M + BM - 1) / BM);
-    a.tilesN = (unsigned)((a.N + BN - 1) / BN);
-    a.xcdMap = xcdMap;
+    a.tilesM = (unsigned)((a.M + T.BM - 1) / T.BM);
+    a.tilesN = (unsigned)((a.N + T.BN - 1) / T.BN);
+    a.xcdMap = 1; // XCD-aware tile map (plain row-major tiles: measured slower, round 2)
     a.dP0 = make_fastdiv((unsigned)a.P0), a.dP1 = make_fastdiv((unsigned)a.P1);
-    const unsigned blocks = xcdMap ? 8u * ((a.tilesM + 7u) / 8u) * a.tilesN : a.tilesM * a.tilesN;
-    constexpr int linOn = 1, ilOn = 1; // linear-layer addressing and the interleaved K loop wherever they apply
-    constexpr bool CAN_IL = KS == 2;
+    const unsigned blocks = 8u * ((a.tilesM + 7u) / 8u) * a.tilesN;
     if constexpr (PRO == PRO_NONE && (EPI == EPI_LINEAR || EPI == EPI_SCALE_RES || EPI == EPI_GLU) && KS == 2)
-    {
-        if (linOn && KS == 2 && gemm_is_linear(a, PRO, EPI, 16 * KS))
+        if (gemm_is_linear(a, PRO, EPI, 16 * KS))
         {
-            if (CAN_IL && ilOn)
-                hipLaunchKernelGGL((igemm_kernel<WM_, WN_, MF, NF, KS, PRO, EPI, true, CAN_IL>), dim3(blocks), dim3(WM_ * WN_ * 64), 0, s, a);
-            else
-                hipLaunchKernelGGL((igemm_kernel<WM_, WN_, MF, NF, KS, PRO, EPI, true, false>), dim3(blocks), dim3(WM_ * WN_ * 64), 0, s, a);
+            hipLaunchKernelGGL((igemm_kernel<WM_, WN_, MF, NF, KS, PRO, EPI, true, IL>), dim3(blocks), dim3(WM_ * WN_ * 64), 0, s, a);
             return;
         }
-    }
-    if (CAN_IL && ilOn)
-        hipLaunchKernelGGL((igemm_kernel<WM_, WN_, MF, NF, KS, PRO, EPI, false, CAN_IL>), dim3(blocks), dim3(WM_ * WN_ * 64), 0, s, a);
-    else
-        hipLaunchKernelGGL((igemm_kernel<WM_, WN_, MF, NF, KS, PRO, EPI, false, false>), dim3(blocks), dim3(WM_ * WN_ * 64), 0, s, a);
+    hipLaunchKernelGGL((igemm_kernel<WM_, WN_, MF, NF, KS, PRO, EPI, false, IL>), dim3(blocks), dim3(WM_ * WN_ * 64), 0, s, a);
 }
 
-// Instantiated (tile, prologue, epilogue) combinations = exactly what plan.cpp emits for the
-// 4- and 6-source models at any segment length (enumerated with tests/cpu_interp.cpp
-// interp_combos). key = cfg*100 + pro*10 + epi.
-int launch_igemm(int cfg, const GemmArgs &a, hipStream_t s, bool dry)
+// The instantiated (tile, prologue, epilogue) combinations are DMX_TILE_COMBOS (gemm_tiles.h); gemm_select.h gemm_kernel_exists
+// answers from the same list on the host. -1: not in the list.
+int launch_igemm(int cfg, const GemmArgs &a, hipStream_t s)
 {
-    if (a.M >= (1ll << 31) - 256)
+    if (!gemm_rows_ok(a.M))
         return -1; // 32-bit row arithmetic in the kernel prologue
     if (cfg == 19) // 256x128, four waves of 128x64, linear layers only (igemm_lin256.hip)
-        return launch_igemm_lin256(a, s, dry);
-#define DMX_CASE(cfgid, WM_, WN_, MF, NF, KS, PRO, EPI) \
-    case (cfgid * 100 + PRO * 10 + EPI):                \
-        if (!dry)                                       \
-            launch_one<WM_, WN_, MF, NF, KS, PRO, EPI>(a, s); \
+        return launch_igemm_lin256(a, s);
+#define DMX_CASE(cfgid, PRO, EPI)            \
+    case combo_key(cfgid, PRO, EPI):         \
+        launch_one<cfgid, PRO, EPI>(a, s);   \
         return 0;
-    switch (cfg * 100 + a.pro * 10 + a.epi)
+    switch (combo_key(cfg, a.pro, a.epi))
     {
-        // cfg 0: 128x128, cfg 7: 64x128 (same column decomposition)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_NONE, EPI_GLU)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_STATS_ONLY)
-        DMX_CASE(0, 2, 2, 4, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_STATS_FACT) // Demucs v3 level 3: hidden 96 -> 98 factor columns
-        // cfg 20: 256x96 with four waves of 64x96 and 16-deep K-tiles, plain loop: the short-K ops of the 128x96 family
-        DMX_CASE(20, 4, 1, 4, 6, 1, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(20, 4, 1, 4, 6, 1, PRO_NONE, EPI_GLU)
-        DMX_CASE(20, 4, 1, 4, 6, 1, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_NONE, EPI_GLU)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_STATS_ONLY)
-        DMX_CASE(7, 2, 2, 2, 4, DMX_BIG_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        // cfg 2: 128x96
-        DMX_CASE(2, 4, 1, 2, 6, DMX_CFG2_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(2, 4, 1, 2, 6, DMX_CFG2_KS, PRO_NONE, EPI_GLU)
-        DMX_CASE(2, 4, 1, 2, 6, DMX_CFG2_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(2, 4, 1, 2, 6, DMX_CFG2_KS, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
-        DMX_CASE(2, 4, 1, 2, 6, DMX_CFG2_KS, PRO_GN_GELU, EPI_STATS_ONLY)
-        // cfg 3: 128x48
-        DMX_CASE(3, 4, 1, 2, 3, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(3, 4, 1, 2, 3, DMX_SMALL_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(3, 4, 1, 2, 3, DMX_SMALL_KS, PRO_AFFINE, EPI_LINEAR)
-        // cfg 4: 256x16, cfg 5: 128x32, cfg 6: 128x64
-        DMX_CASE(4, 4, 1, 4, 1, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(4, 4, 1, 4, 1, DMX_SMALL_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        DMX_CASE(5, 4, 1, 2, 2, DMX_SMALL_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        DMX_CASE(6, 4, 1, 2, 4, DMX_SMALL_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        DMX_CASE(5, 4, 1, 2, 2, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(5, 4, 1, 2, 2, DMX_SMALL_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(6, 4, 1, 2, 4, DMX_SMALL_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(6, 4, 1, 2, 4, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        // half-height siblings (plan.cpp refine_cfg): cfg 9: 64x64 of 7; 10: 64x96 of 2; 11: 64x48 of 3; 12: 64x32 of 5;
-        // 13: 64x64 (4 x 1 waves) of 6; 14: 128x16 of 4
-        DMX_CASE(9, 2, 2, 2, 2, 2, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(9, 2, 2, 2, 2, 2, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(9, 2, 2, 2, 2, 2, PRO_NONE, EPI_GLU)
-        DMX_CASE(9, 2, 2, 2, 2, 2, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(9, 2, 2, 2, 2, 2, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
-        DMX_CASE(10, 4, 1, 1, 6, DMX_CFG2_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(10, 4, 1, 1, 6, DMX_CFG2_KS, PRO_NONE, EPI_GLU)
-        DMX_CASE(10, 4, 1, 1, 6, DMX_CFG2_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(10, 4, 1, 1, 6, DMX_CFG2_KS, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
-        DMX_CASE(10, 4, 1, 1, 6, DMX_CFG2_KS, PRO_GN_GELU, EPI_STATS_ONLY)
-        DMX_CASE(11, 4, 1, 1, 3, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(11, 4, 1, 1, 3, DMX_SMALL_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(11, 4, 1, 1, 3, DMX_SMALL_KS, PRO_AFFINE, EPI_LINEAR)
-        DMX_CASE(12, 4, 1, 1, 2, DMX_SMALL_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        DMX_CASE(12, 4, 1, 1, 2, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(12, 4, 1, 1, 2, DMX_SMALL_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(13, 4, 1, 1, 4, DMX_SMALL_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        DMX_CASE(13, 4, 1, 1, 4, DMX_SMALL_KS, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(13, 4, 1, 1, 4, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(14, 4, 1, 2, 1, DMX_SMALL_KS, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(14, 4, 1, 2, 1, DMX_SMALL_KS, PRO_GN_GELU, EPI_STATS_FACT)
-        // quarter-height siblings: cfg 15: 32x128 of 7 (same column decomposition); 16: 32x64 of 9
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_NONE, EPI_GLU)
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_GN_GELU, EPI_STATS_ONLY)
-        DMX_CASE(15, 2, 2, 1, 4, 2, PRO_GN_GELU, EPI_STATS_FACT)
-        DMX_CASE(16, 2, 2, 1, 2, 2, PRO_NONE, EPI_LINEAR)
-        DMX_CASE(16, 2, 2, 1, 2, 2, PRO_NONE, EPI_SCALE_RES)
-        DMX_CASE(16, 2, 2, 1, 2, 2, PRO_NONE, EPI_GLU)
-        DMX_CASE(16, 2, 2, 1, 2, 2, PRO_NONE, EPI_TRCONV)
-        DMX_CASE(16, 2, 2, 1, 2, 2, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES)
+        DMX_TILE_COMBOS(DMX_CASE)
     default:
         return -1;
     }

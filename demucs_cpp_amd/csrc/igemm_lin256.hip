@@ -306,18 +306,15 @@ __global__ __launch_bounds__(256, 2) void igemm_lin256_kernel(const GemmArgs p)
     }
 }
 
-// shapes this kernel covers: "linear layer" addressing (igemm.hip is_linear), no prologue
-bool lin256_ok(const GemmArgs &a)
+// shapes this kernel covers: plain linear layers (gemm_select.h lin256_addressing, the predicate the plan chose the tile by) with the
+// operands of their epilogue present
+static bool lin256_ok(const GemmArgs &a)
 {
-    return a.pro == PRO_NONE && (a.epi == EPI_LINEAR || a.epi == EPI_SCALE_RES) && a.S1 == 1 && a.pad0 == 0 && a.seg0 == a.K &&
-           a.K == a.Kp && a.K % 16 == 0 && a.Np % 4 == 0 && a.N % 4 == 0 && (i64)(a.P0 - 1) * a.stride0 * a.Cin + a.seg0 <= (i64)a.L0 * a.Cin &&
-           a.P1 == a.L1 && a.stride1 == 1 && a.pad1 == 0 && a.M < (1ll << 31) - 256 && (a.epi != EPI_SCALE_RES || (a.res && a.scale));
+    return lin256_addressing(a) && gemm_rows_ok(a.M) && (a.epi != EPI_SCALE_RES || (a.res && a.scale));
 }
 
-int launch_igemm_lin256(const GemmArgs &a0, hipStream_t s, bool dry)
+int launch_igemm_lin256(const GemmArgs &a0, hipStream_t s)
 {
-    if (dry) // availability check at context creation (partial arguments): the plan decided the shape with full information
-        return a0.pro == PRO_NONE && (a0.epi == EPI_LINEAR || a0.epi == EPI_SCALE_RES) ? 0 : -1;
     if (!lin256_ok(a0))
         return -1;
     GemmArgs a = a0;

@@ -991,73 +991,59 @@ static int launch_linw_conv(int wnf, GemmArgs a, hipStream_t s)
 {
     a.tilesM = (unsigned)((a.M + 127) / 128);
     a.tilesN = (unsigned)((a.N + 16 * wnf - 1) / (16 * wnf));
-#define DMX_LINW(WNF, EPI)                                                                                   \
-    case (WNF * 10 + EPI):                                                                                   \
+#define DMX_LINW(WNF, EPI)                                                                              \
+    case (WNF * 10 + EPI):                                                                              \
         hipLaunchKernelGGL((igemm_split_linw_kernel<WNF, EPI, true>), grid_of(a), dim3(256), 0, s, a); \
         return 0;
     switch (wnf * 10 + a.epi)
     {
-        DMX_LINW(16, EPI_LINEAR)
-        DMX_LINW(16, EPI_GLU)
-        DMX_LINW(16, EPI_TRCONV)
-        DMX_LINW(12, EPI_LINEAR)
-        DMX_LINW(12, EPI_GLU)
-        DMX_LINW(12, EPI_TRCONV)
-        DMX_LINW(6, EPI_LINEAR)
-        DMX_LINW(6, EPI_GLU)
-        DMX_LINW(6, EPI_TRCONV)
-        DMX_LINW(4, EPI_LINEAR)
-        DMX_LINW(4, EPI_TRCONV)
-        DMX_LINW(2, EPI_LINEAR)
+        DMX_LINW_COMBOS(DMX_LINW)
     default:
         return -1;
     }
 #undef DMX_LINW
 }
 
-template <int WM_, int WN_, int MF, int NF, int PRO, int EPI>
+// a row of DMX_SPLIT_COMBOS in the family the op's choice names; which families a row has: gemm_tiles.h split_family_exists
+template <int CFG, int PRO, int EPI>
 static int launch_split_one(int family, GemmArgs a, hipStream_t s)
 {
-    constexpr int BM = WM_ * MF * 16, BN = WN_ * NF * 16;
-    // what is instantiated: linear-layer staging for the epilogues linear layers have; igemm_split_lin_kernel for the 128-wide tiles
-    // of at least 64 rows (cfg 0 / 7), the only kernel of the K / V plane projections besides the 128 x 256 tile of cfg 0
-    constexpr bool kPlanes = EPI == EPI_KPL || EPI == EPI_VT;
-    constexpr bool kLinEpi = PRO == PRO_NONE && (EPI == EPI_LINEAR || EPI == EPI_SCALE_RES || EPI == EPI_GLU);
-    constexpr bool kLinTile = PRO == PRO_NONE && (kLinEpi || kPlanes) && WM_ == 2 && WN_ == 2 && NF == 4 && MF >= 2;
-    a.tilesM = (unsigned)((a.M + BM - 1) / BM);
-    a.tilesN = (unsigned)((a.N + BN - 1) / BN);
+    constexpr TileCfg T = kTileCfgs[CFG];
+    constexpr int WM_ = T.WM, WN_ = T.WN, MF = T.MF, NF = T.NF;
+    a.tilesM = (unsigned)((a.M + T.BM - 1) / T.BM);
+    a.tilesN = (unsigned)((a.N + T.BN - 1) / T.BN);
     switch (family)
     {
     case GF_SPLIT_STAGED:
-        if constexpr (!kPlanes)
+        if constexpr (split_family_exists(GF_SPLIT_STAGED, CFG, PRO, EPI))
         {
             hipLaunchKernelGGL((igemm_split_kernel<WM_, WN_, MF, NF, PRO, EPI, false>), grid_of(a), dim3(256), 0, s, a);
             return 0;
         }
         break;
     case GF_SPLIT_STAGED_LIN:
-        if constexpr (kLinEpi)
+        if constexpr (split_family_exists(GF_SPLIT_STAGED_LIN, CFG, PRO, EPI))
         {
             hipLaunchKernelGGL((igemm_split_kernel<WM_, WN_, MF, NF, PRO, EPI, true>), grid_of(a), dim3(256), 0, s, a);
             return 0;
         }
         break;
     case GF_SPLIT_LIN:
-        if constexpr (kLinTile)
+        if constexpr (split_family_exists(GF_SPLIT_LIN, CFG, PRO, EPI))
         {
             hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI>), grid_of(a), dim3(256), 0, s, a);
             return 0;
         }
         break;
     case GF_SPLIT_LINH:
-        if constexpr (kLinTile)
+        if constexpr (split_family_exists(GF_SPLIT_LINH, CFG, PRO, EPI))
         {
             hipLaunchKernelGGL((igemm_split_lin_kernel<MF / 2, 8, EPI, 1>), grid_of(a), dim3(256), 0, s, a);
             return 0;
         }
         break;
     case GF_SPLIT_LINW:
-        if constexpr (kLinTile && MF == 4 && EPI != EPI_GLU)
+        if constexpr (split_family_exists(GF_SPLIT_LINW, CFG, PRO, EPI))
         {
             a.tilesN = (unsigned)(a.N / 256);
             hipLaunchKernelGGL((igemm_split_linw_kernel<16, EPI, false>), grid_of(a), dim3(256), 0, s, a);
@@ -1079,10 +1065,10 @@ int launch_igemm_split(const GemmChoice &ch, int cfg, const GemmArgs &a0, hipStr
     a.dP0 = make_fastdiv((unsigned)a.P0), a.dP1 = make_fastdiv((unsigned)a.P1);
     if (ch.family == GF_SPLIT_WIDE_CONV || ch.family == GF_SPLIT_NARROW)
         return launch_linw_conv(ch.wnf, a, s);
-#define DMX_CASE(cfgid, WM_, WN_, MF, NF, PRO, EPI) \
-    case (cfgid * 100 + PRO * 10 + EPI):           \
-        return launch_split_one<WM_, WN_, MF, NF, PRO, EPI>(ch.family, a, s);
-    switch (cfg * 100 + a.pro * 10 + a.epi)
+#define DMX_CASE(cfgid, PRO, EPI)    \
+    case combo_key(cfgid, PRO, EPI): \
+        return launch_split_one<cfgid, PRO, EPI>(ch.family, a, s);
+    switch (combo_key(cfg, a.pro, a.epi))
     {
         DMX_SPLIT_COMBOS(DMX_CASE)
     default:

@@ -73,7 +73,7 @@ struct GemmArgs
 
 // direct (register-resident weights, no LDS) kernels for the HBM-bound layers; -1 if the shape is
 // not in their table
-int launch_dgemm(const GemmArgs &a, hipStream_t s, bool dry = false);
+int launch_dgemm(const GemmArgs &a, hipStream_t s);
 
 // The frequency branch's whole DConv residual branch with the (C, T) row of one (segment, bin) resident on the CU
 // (dconv_row.hip; plan.h OP_DCONV_ROW). Pointers of the two layers (dilation 1, 2) into the packed model.
@@ -91,11 +91,11 @@ struct DconvRowArgs
 // -1 when no kernel exists for the shape; dry = availability check only (needs B, T, F, C, hid)
 int launch_dconv_row(const DconvRowArgs &a, hipStream_t s, bool dry = false);
 
-// returns 0, or -1 when the (tile, prologue, epilogue) combination is not instantiated;
-// dry = true only checks availability
-int launch_igemm(int cfg, const GemmArgs &a, hipStream_t s, bool dry = false);
+// returns 0, or -1 when the (tile, prologue, epilogue) combination is not instantiated (gemm_select.h gemm_kernel_exists is the
+// host-side answer)
+int launch_igemm(int cfg, const GemmArgs &a, hipStream_t s);
 // linear layers on a 256x128 tile with four waves of 128x64 (igemm_lin256.hip); -1 when the op is not a plain linear layer
-int launch_igemm_lin256(const GemmArgs &a, hipStream_t s, bool dry = false);
+int launch_igemm_lin256(const GemmArgs &a, hipStream_t s);
 // the exact-split kernel family `ch` chose for the op (gemm_select.h; igemm_split.hip): bf16 terms on the two planes Wb1 / Wb2, or
 // (GF_SPLIT_LINH) fp16 terms with Wb1 = the fp16 plane and rowScale set. -1: the family does not exist for the op's (tile,
 // prologue, epilogue) - an internal error, the selection only names kernels that exist

@@ -5,7 +5,7 @@
 // DConv src/layers.cpp:152-375, transformer src/crosstransformer.cpp:205-339 +
 // src/layers.cpp:377-531, STFT/ISTFT src/dsp.cpp:51-185. Fusions relative to the
 // reference are documented per op in DESIGN.md §4.
-#include "plan.h"
+#include "gemm_select.h"
 #include <string>
 
 #include <algorithm>
@@ -35,139 +35,6 @@ Geo make_geo(i64 seg)
         g.Lt[i + 1] = (L - 4 + 3) / 4 + 1; // ceil((L+4-7-1)/4)+1
     }
     return g;
-}
-
-
-int choose_cfg(i64 M1, int N, bool paired)
-{
-    const i64 M = M1 * 4; // nominal batch of 4 segments in flight
-    if (!paired)
-    {
-        if (N <= 16)
-            return 4;
-        if (N <= 32)
-            return 5;
-        if (N <= 48)
-            return 3;
-    }
-    else if (N <= 32)
-        return 5;
-    if (N <= 64)
-        return 6;
-    if (N <= 96)
-        return 2;
-    if (N % 128 != 0 && N % 96 == 0)
-        return 2;
-    // the 2 x 4 family: refine_cfg walks down its chain 0 -> 7 -> 15 / 9 -> 16 from the ACTUAL row count (round 3: the
-    // nominal-batch choice between 0 and 7 kept the time-branch linears on 64x128 tiles even at 42 segments)
-    (void)M;
-    return 0;
-}
-
-int half_cfg(int cfg, bool stat)
-{
-    switch (cfg)
-    {
-    case 0:
-        return 7;
-    case 7:
-        return stat ? 15 : 9;
-    case 9:
-        return 16;
-    case 2:
-        return 10;
-    case 3:
-        return 11;
-    case 5:
-        return 12;
-    case 6:
-        return 13;
-    case 4:
-        return 14;
-    default:
-        return -1;
-    }
-}
-
-// Work per CU is what counts (co-resident workgroups share one matrix pipe per SIMD). A launch of T tiles puts
-// n = ceil(T / 256) workgroups on its busiest CU; two resident workgroups hide each other's ds_read / barrier /
-// staging latencies, ONE does not (measured at one segment per call: 252 tiles of 128x128 take 1.8x as long as
-// 504 of 64x128 for the same op, decoder.1.rewrite 224 -> 126 us; the 3 qkv linears 71 -> 50 us). So the cost of
-// a tile shape is  (n == 1 ? 1.7 : n) x tile area x (1 + small-tile overhead: staging bytes per MFMA grow as the
-// tile shrinks: +3 % per halving, from forced-half runs at batch 24),
-// minimised over the chain of bit-identical half-height siblings. Large batches keep the big tile; one segment
-// (M = 2688 / 1344 rows) gets 64x64 tiles for its transformer linears.
-int refine_cfg(int cfg, i64 M, int N, bool stat)
-{
-    auto cost = [&](int c, int depth) {
-        // the XCD-aware tile map (igemm.hip) deals ROW tiles round-robin to the 8 XCDs and runs all column tiles of a row
-        // tile on that XCD: the busiest XCD holds ceil(tilesM / 8) x tilesN workgroups for its 32 CUs. (Counting T / 256
-        // instead missed e.g. 84 x 6 tiles = 11 row tiles on four of the XCDs = 66 workgroups for 64 slots: a second
-        // round for two stragglers, decoder.0.rewrite at 4 segments 617 us with 128x128 vs 428 us with 64x128.)
-        const i64 tm = (M + kTileCfgs[c].BM - 1) / kTileCfgs[c].BM, tn = (N + kTileCfgs[c].BN - 1) / kTileCfgs[c].BN;
-        const i64 n = (((tm + 7) / 8) * tn + 31) / 32;
-        return (n == 1 ? 1.7 : (double)n) * (double)(kTileCfgs[c].BM * kTileCfgs[c].BN) * (1.0 + 0.03 * depth);
-    };
-    int best = cfg;
-    double bestCost = cost(cfg, 0);
-    int depth = 1;
-    for (int c = half_cfg(cfg, stat); c >= 0; c = half_cfg(c, stat), ++depth)
-        if (cost(c, depth) < bestCost * 0.95) // the model is good to a few per cent: leave the default tile unless it is clear
-        {
-            best = c;
-            bestCost = cost(c, depth);
-        }
-    return best;
-}
-
-// The shapes of the two tiles finish() reaches from another tile by the ROW COUNT of a launch: everything but that count (the
-// debug entry points of debug_api.cpp run an op on them at small sizes).
-// cfg 19 (igemm_lin256.hip, same conditions as its lin256_ok): plain linear layers; N a multiple of 512 only: with three column
-// tiles (N = 384: the channel up / down samplers) half as many, twice as large workgroups quantise worse on the 64 slots of an XCD
-// than they gain (measured 126 -> 115, 121 -> 111 TFLOP/s)
-bool lin256_shape(const IGemm &g)
-{
-    return g.pro == PRO_NONE && (g.epi == EPI_LINEAR || g.epi == EPI_SCALE_RES) && g.S1 == 1 && g.pad0 == 0 && g.seg0 == g.K && g.K == g.Kp &&
-           g.K % 16 == 0 && g.N % 4 == 0 && (i64)(g.P0 - 1) * g.stride0 * g.Cin + g.seg0 <= (i64)g.L0 * g.Cin && g.P1 == g.L1 && g.stride1 == 1 &&
-           g.pad1 == 0 && (g.epi != EPI_SCALE_RES || (g.res >= 0 && g.scale_w >= 0)) && g.N % 512 == 0;
-}
-// cfg 20: the short-K ops of the 128x96 family, no row statistics
-bool shortk_shape(const IGemm &g)
-{
-    return g.rowstat < 0 && g.pro == PRO_NONE && (g.epi == EPI_LINEAR || g.epi == EPI_GLU || g.epi == EPI_TRCONV) && g.K <= 160;
-}
-
-bool direct_available(int N, int S1, int seg0, int pro, int epi)
-{
-    // deep-level DConv k3 in column chunks of 192 (dgemm.hip launch_dgemm)
-    if (pro == PRO_GN_GELU && epi == EPI_GN_GLU_SCALE_RES && S1 == 1 && (seg0 == 24 || seg0 == 48) && N > 192 && N % 192 == 0)
-        return true;
-    const int NF = (N + 15) / 16;
-    const int key = NF * 1000000 + S1 * 100000 + seg0 * 100 + pro * 10 + epi;
-    static const int keys[] = {
-        1 * 1000000 + 3 * 100000 + 48 * 100 + PRO_NONE * 10 + EPI_LINEAR,
-        1 * 1000000 + 3 * 100000 + 96 * 100 + PRO_NONE * 10 + EPI_LINEAR,
-        6 * 1000000 + 1 * 100000 + 8 * 100 + PRO_GN_GELU * 10 + EPI_STATS_ONLY,
-        1 * 1000000 + 1 * 100000 + 8 * 100 + PRO_GN_GELU * 10 + EPI_STATS_FACT,
-        1 * 1000000 + 1 * 100000 + 12 * 100 + PRO_GN_GELU * 10 + EPI_STATS_FACT,
-        6 * 1000000 + 1 * 100000 + 8 * 100 + PRO_GN_GELU * 10 + EPI_GN_GLU_SCALE_RES,
-        12 * 1000000 + 1 * 100000 + 12 * 100 + PRO_GN_GELU * 10 + EPI_STATS_ONLY,
-        12 * 1000000 + 1 * 100000 + 12 * 100 + PRO_GN_GELU * 10 + EPI_GN_GLU_SCALE_RES,
-        6 * 1000000 + 1 * 100000 + 12 * 100 + PRO_GN_GELU * 10 + EPI_GN_GLU_SCALE_RES,  // Demucs v3: hidden C/4
-        12 * 1000000 + 1 * 100000 + 24 * 100 + PRO_GN_GELU * 10 + EPI_GN_GLU_SCALE_RES,
-        2 * 1000000 + 1 * 100000 + 24 * 100 + PRO_GN_GELU * 10 + EPI_STATS_FACT,
-        3 * 1000000 + 1 * 100000 + 32 * 100 + PRO_AFFINE * 10 + EPI_LINEAR,
-        3 * 1000000 + 1 * 100000 + 16 * 100 + PRO_AFFINE * 10 + EPI_LINEAR,
-        6 * 1000000 + 1 * 100000 + 48 * 100 + PRO_NONE * 10 + EPI_GLU,
-        4 * 1000000 + 1 * 100000 + 96 * 100 + PRO_NONE * 10 + EPI_TRCONV,
-        2 * 1000000 + 1 * 100000 + 96 * 100 + PRO_NONE * 10 + EPI_TRCONV,
-        6 * 1000000 + 1 * 100000 + 96 * 100 + PRO_NONE * 10 + EPI_TRCONV,
-        3 * 1000000 + 1 * 100000 + 96 * 100 + PRO_NONE * 10 + EPI_TRCONV,
-    };
-    for (int k : keys)
-        if (k == key)
-            return true;
-    return false;
 }
 
 // dconv_row.hip: C = 48 / 96 with hidden C/8 (v4), C = 48 with hidden C/4 (v3)
@@ -235,52 +102,14 @@ struct Builder
         g.kv = -1;
         return g;
     }
-    void finish(IGemm &g, bool paired)
+    void finish(IGemm &g, bool paired, bool pin128Wide = false)
     {
         g.K = g.S1 * g.seg0;
         g.Kp = rup(g.K, 16);
         g.Np = rup(g.N, 16);
         g.xBatchStride = (i64)g.L1 * g.L0 * g.Cin;
-        g.cfg = refine_cfg(choose_cfg((i64)g.P1 * g.P0, g.N, paired), (i64)g.B * g.P1 * g.P0, g.N, g.rowstat >= 0);
-        // plain linear layers that keep the 128x128 tile (i.e. enough rows to fill the chip a few times over) run on the
-        // 256x128 / four-wave kernel (igemm_lin256.hip; same conditions as its lin256_ok). DMX_LIN256=0 switches it off (A/B).
-        {
-            const char *e = getenv("DMX_LIN256");
-            const bool splitMode = opts.gemm != GEMM_F32;
-            // (the operand-split path has no 256x128 form: its linears stay on the tiles igemm_split.hip instantiates)
-            const bool on = (!e || atoi(e) != 0) && !splitMode;
-            // the shape (lin256_shape) and at least three rounds of its workgroups on the 64 slots of an XCD (the tile map deals row tiles to XCDs): at
-            // 1.75 rounds (time-branch linears with N = 512 at 42 segments) the 128x128 tile is 10 % faster
-            const i64 M = (i64)g.B * g.P1 * g.P0;
-            const i64 perXcd = (((M + 255) / 256 + 7) / 8) * ((g.N + 127) / 128);
-            if (on && lin256_shape(g) && g.cfg == 0 && perXcd >= 192)
-                g.cfg = 19;
-            // short-K ops of the 128x96 family (K <= 160: the level-1 1x1 rewrites, K = 96, and the time branch's last k3
-            // rewrite, K = 144) run on the 256x96 tile with 16-deep K-tiles (cfg 20, plain loop): no half-empty last K-tile
-            // (144 = 4.5 x 32) and a shorter pipeline fill - measured 88.8 -> 101.9, 84.6 -> 93.9, 90.4 -> 94.8 TFLOP/s at 42
-            // segments; longer K stays on the interleaved 32-deep loop (decoder.3.rewrite, K = 432: 121 vs 118.7). Same column
-            // decomposition and k order: identical bits. DMX_SHORTK=0 switches it off (A/B).
-            const char *sk = getenv("DMX_SHORTK");
-            // (the operand-split path keeps the tiles it instantiates)
-            if ((!sk || atoi(sk) != 0) && !splitMode && g.cfg == 2 && shortk_shape(g) && M >= 65536)
-                g.cfg = 20;
-        }
-        // the DConv k3 op is a copy of k2 with another epilogue: both are in the direct table
-        // (the direct kernels carry no residual operand for the LINEAR / TRCONV epilogues)
-        const bool resOk = !((g.epi == EPI_LINEAR || g.epi == EPI_TRCONV) && g.res >= 0);
-        // the level-0 1x1 rewrites (48 -> 96 + GLU) of an exact-split context run on the 128 x 96 direct-fragment split tile
-        // (igemm_split.hip, round 6): 0.900 -> 0.815 / 0.435 -> 0.386 ms at 42 segments against the fp32 direct kernel, which
-        // sits on the fp32 matrix pipe's ridge; an fp32 context keeps the direct kernel (its tiled fp32 form is 20 % slower)
-        const bool rewrite0Split = opts.gemm != GEMM_F32 && g.pro == PRO_NONE && g.epi == EPI_GLU && g.S1 == 1 && g.seg0 == 48 && g.N == 96;
-        // likewise the frequency branch's last transposed conv (48 -> 4 x Cout, K = 96): N = 64 (4 sources; igemm_split.hip
-        // narrow tile, gemm_select.cpp: 0.947 -> 0.917 ms) and N = 96 (6 sources: 1.57 -> 1.22 ms). The time branch's (N = 32 / 48) stays on
-        // the direct kernel (N = 32 measured: 0.286 -> 0.293 ms)
-        const bool lastTrSplit = opts.gemm != GEMM_F32 && g.pro == PRO_NONE && g.epi == EPI_TRCONV && g.S1 == 1 && g.seg0 == 96 &&
-                                 (g.N == 64 || g.N == 96);
-        if (resOk && !rewrite0Split && !lastTrSplit && (direct_available(g.N, g.S1, g.seg0, g.pro, g.epi) ||
-                      (g.epi == EPI_STATS_ONLY && direct_available(g.N, g.S1, g.seg0, g.pro, EPI_GN_GLU_SCALE_RES))))
-            g.cfg = kDirectCfg;
-        g.NB = (g.N + kTileCfgs[g.cfg].BN - 1) / kTileCfgs[g.cfg].BN;
+        const TileChoice t = choose_tile(g, paired, pin128Wide, opts.gemm, opts.sw); // all tile policy: gemm_select.cpp
+        g.cfg = t.cfg, g.NB = t.NB;
     }
     void push_gemm(const std::string &name, int stream, IGemm g)
     {
@@ -335,10 +164,9 @@ struct Builder
         const int G0 = P0 > 1 ? P0 : 1;
         const i64 rows = (i64)P1 * P0;
         // frequency branch, levels 0 / 1: the whole residual branch as ONE op with the (C, T) row of a bin resident on the CU
-        // (dconv_row.hip). A function of (C, hidden width, T) alone - never of the batch. DMX_DCONV_ROW=0: the op chain (A/B).
+        // (dconv_row.hip). A function of (C, hidden width, T) alone - never of the batch. PlanOpts::dconvRow off: the op chain (A/B).
         {
-            const char *e = getenv("DMX_DCONV_ROW");
-            if (P0 > 1 && (!e || atoi(e) != 0) && dconv_row_lds_bytes(C, C8, P1) > 0 && (i64)B * P1 * P0 * C < (1ll << 31) &&
+            if (P0 > 1 && opts.dconvRow && dconv_row_lds_bytes(C, C8, P1) > 0 && (i64)B * P1 * P0 * C < (1ll << 31) &&
                 pm.has(p + ".dconv.0.rowimg"))
             {
                 Op op;
@@ -391,7 +219,6 @@ struct Builder
             h.epi = EPI_STATS_ONLY;
             h.y = -1, h.ldy = 0;
             h.rowstat = rs;
-            finish(h, true); // tile choice of the full product: inherited by K3 below
             {
                 // statistics through the factorised weights (EPI_STATS_FACT): C/8 + 2 columns instead of 2C
                 IGemm f = h;
@@ -408,6 +235,7 @@ struct Builder
             k.epiStats = st2, k.epiW_w = W(w + "gn2.w"), k.epiB_w = W(w + "gn2.b");
             k.scale_w = W(w + "scale");
             k.res = y, k.y = y, k.ldy = C, k.yBatchStride = rows * C;
+            finish(k, true); // (the tile of the full product with row statistics, as when K2 computed them unfactorised: the sibling chain)
             k.rowstat = -1;
             push_gemm(nm + ".k3", stream, k);
         }
@@ -657,17 +485,11 @@ void build_plan(const PackedModel &pm, i64 seg, int B, Plan &pl, const PlanOpts 
         g.epi = epi, g.act = act;
         g.y = y, g.ldy = ldy, g.yBatchStride = (i64)rows * ldy;
         g.res = res, g.scale_w = scale, g.rowstat = rowstat;
-        b.finish(g, false);
         // GEMM_FP16X3: the fp16-term arithmetic exists on the linear-layer kernel only (128- / 64-row tiles of the 128-wide
         // family); an op must take ONE arithmetic at every batch size (batch = singles bitwise), so the quarter-height sibling
         // (a staged kernel, bf16 terms) is not offered to it
-        if (opts.gemm == GEMM_FP16X3 && g.N % 128 == 0 && g.K % 32 == 0)
-        {
-            if (g.cfg != 0 && g.cfg != 7)
-                g.cfg = 7;
-            g.NB = (g.N + kTileCfgs[g.cfg].BN - 1) / kTileCfgs[g.cfg].BN;
-            g.hterms = 1;
-        }
+        g.hterms = opts.gemm == GEMM_FP16X3 && N % 128 == 0 && K % 32 == 0 ? 1 : 0;
+        b.finish(g, false, g.hterms != 0);
         b.push_gemm(name, stream, g);
     };
     auto layernorm = [&](const std::string &name, int stream, i64 x, i64 y, int rows, const std::string &w,
@@ -706,10 +528,7 @@ void build_plan(const PackedModel &pm, i64 seg, int B, Plan &pl, const PlanOpts 
         g.epi = epi, g.act = 0;
         g.y = y, g.ldy = ldy, g.yBatchStride = (i64)rows * ldy;
         g.kv = kv, g.kvCol0 = kvCol0, g.kvT = rows, g.kvH = 8, g.kvHs = D / 8;
-        b.finish(g, false);
-        if (g.cfg != 0 && g.cfg != 7)
-            g.cfg = 7;
-        g.NB = (g.N + kTileCfgs[g.cfg].BN - 1) / kTileCfgs[g.cfg].BN;
+        b.finish(g, false, true);
         g.hterms = opts.gemm == GEMM_FP16X3 ? 1 : 0;
         b.push_gemm(name, stream, g);
     };

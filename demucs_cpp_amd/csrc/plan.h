@@ -135,13 +135,13 @@ struct IGemm
     i64 epiStats;             // A: [B*G0][4] for EPI_GN_GLU_SCALE_RES
     i64 epiW_w, epiB_w;       // W: [Np] GroupNorm affine in packed column order
     i64 rowstat;              // A: [M][NB][2] partial (sum, sumsq) per row and column block, or -1
-    int NB;                   // number of column blocks writing rowstat (= ceil(Np/BN)); set by engine cfg
+    int NB;                   // number of column blocks writing rowstat (= ceil(Np/BN)); the tile's (choose_tile)
     i64 table_w;              // W: [P0][C] (EPI_GLU freq-embedding add) or -1
     float tableScale;
     int Lout, Cout;           // EPI_TRCONV: output positions per (b,p1) row, channels
     int trS, trOff;           // EPI_TRCONV: n = (r, co), r < trS; output position j = trS*p0 + r - trOff
                               // (k8/s4 with the 2-sample crop: 4, 2; v3's uncropped k8/s4: 4, 0; k4/s2: 2, 0)
-    int cfg;                  // tile configuration index (engine)
+    int cfg;                  // tile configuration index (gemm_tiles.h; gemm_select.cpp choose_tile)
     GemmChoice choice;        // the kernel that runs the op in its context (exec.cpp dmx_get_plan)
     // EPI_KPL / EPI_VT: A (float offset) of three bf16 planes of B*kvT*(kvH*kvHs) elements each; rows are tokens (P1 = kvT,
     // P0 = 1), kvT a multiple of 64; -1 otherwise
@@ -361,56 +361,6 @@ struct PackedModel
     bool has(const std::string &name) const;
 };
 
-// tile configurations of the igemm kernel (engine.cpp instantiates exactly these)
-struct TileCfg
-{
-    int BM, BN;
-};
-static const TileCfg kTileCfgs[] = {
-    {128, 128}, // 0
-    {64, 64},   // 1
-    {128, 96},  // 2
-    {128, 48},  // 3
-    {256, 16},  // 4
-    {128, 32},  // 5
-    {128, 64},  // 6
-    {64, 128},  // 7  same column decomposition as 0 (2 waves x 4 fragments): bit-identical row statistics
-    {16, 256},  // 8  kDirectCfg: dgemm.hip direct kernels, one wave owns 16 rows x all columns (NB = 1)
-    // half-height siblings for launches that would leave CUs idle (few segments in flight). Same column
-    // decomposition as the tile they replace (waves x fragments along N), so the row statistics - and every
-    // other output bit - are identical; 64x64 (2 waves x 2 fragments along N) only replaces ops without row statistics.
-    {64, 64},   // 9   of 7 (ops without row statistics only)
-    {64, 96},   // 10  of 2
-    {64, 48},   // 11  of 3
-    {64, 32},   // 12  of 5
-    {64, 64},   // 13  of 6 (4 x 1 waves)
-    {128, 16},  // 14  of 4
-    // quarter-height siblings for one or two segments per call (M = 1344 / 2688 rows: even the half-height tiles
-    // leave most CUs with a single workgroup)
-    {32, 128},  // 15  of 7 (2 x 2 waves, 1 x 4 fragments: the column decomposition of 0 and 7, row statistics identical)
-    {32, 64},   // 16  of 9
-    {256, 128}, // 17  unused (no kernel, never chosen; the slot keeps the numbering)
-    {256, 128}, // 18  unused
-    {256, 128}, // 19  igemm_lin256.hip: four waves of 128x64 with their own pipelined loop, linear layers only
-                //     (same column decomposition as 0 / 7, bit-identical results)
-    {256, 96},  // 20  four waves of 64x96, 16-deep K-tiles, plain loop: the short-K ops of the 128x96 family (plan.cpp, DMX_SHORTK)
-};
-static const int kNumTileCfgs = 21;
-static const int kDirectCfg = 8;
-// cfg -> its half-height sibling (-1: none); stat = the op writes row statistics
-int half_cfg(int cfg, bool stat);
-// tile for an op at the ACTUAL number of rows M (all segments in flight): the largest tile of the chain
-// cfg -> half_cfg(cfg) -> ... that keeps the 256 CUs evenly busy
-int refine_cfg(int cfg, i64 M, int N, bool stat);
-// the shape conditions (everything but the row count) under which plan.cpp finish() moves an op to cfg 19 / cfg 20
-bool lin256_shape(const IGemm &g);
-bool shortk_shape(const IGemm &g);
-// shapes served by the direct kernels (must match the table in dgemm.hip)
-bool direct_available(int N, int S1, int seg0, int pro, int epi);
-// M1 = rows per batch element: the choice never depends on the batch size, so results are
-// bit-identical for any batching / sharding of segments
-int choose_cfg(i64 M1, int N, bool paired);
-
 // how the MFMA-bound convs / linears (and, where built, attention) form their fp32 products
 enum GemmMode
 {
@@ -419,16 +369,25 @@ enum GemmMode
     GEMM_FP16X3 = 2, // opt-in: as GEMM_BF16X3 (same plan), except that the linear layers run with fp16 terms under a per-row
                      // power-of-two scale where their weights allow (gemm_select.h): bounded, not exact
 };
+// the A/B switches of the kernel choice (gemm_select.h plan_opts_from_env reads them from the environment)
+struct GemmSwitches
+{
+    int splitLin = 1;   // DMX_SPLIT_LIN: which exact-split kernel families are offered (gemm_select.cpp select_gemm)
+    bool lin256 = true; // DMX_LIN256: cfg 19 for the large plain linear layers of an fp32 plan
+    bool shortK = true; // DMX_SHORTK: cfg 20 for the short-K ops of the 128x96 family of an fp32 plan
+};
 struct PlanOpts
 {
     int gemm = GEMM_F32;
     int kvPlanes = 0; // GEMM_BF16X3 only: K / V projections write the attention kernel's bf16 operand planes (EPI_KPL / EPI_VT)
+    bool dconvRow = true; // DMX_DCONV_ROW: the frequency branch's DConv residual branch as one OP_DCONV_ROW where the kernel exists
+    GemmSwitches sw;
 };
 
 struct Plan
 {
     int B = 1;
-    int gemm = GEMM_F32; // PlanOpts::gemm the plan was built for (tile rules differ: plan.cpp finish())
+    int gemm = GEMM_F32; // PlanOpts::gemm the plan was built for (tile rules differ: gemm_select.cpp choose_tile)
     Geo geo;
     int S = 4, D = 512;
     i64 arenaFloats = 0;

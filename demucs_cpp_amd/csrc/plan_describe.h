@@ -2,7 +2,7 @@
 // tests/cpu_interp.cpp reports for its own plan, so that the two plans can be compared word by word. Plain C++, no HIP.
 #pragma once
 #include "attention_select.h"
-#include "plan.h"
+#include "gemm_tiles.h"
 #include <algorithm>
 #include <cstdio>
 #include <string>

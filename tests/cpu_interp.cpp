@@ -1139,7 +1139,7 @@ extern "C"
             delete it;
             return nullptr;
         }
-        build_plan(it->pm, seg, B, it->pl);
+        build_plan(it->pm, seg, B, it->pl, plan_opts_from_env(GEMM_F32, false));
         it->A.assign((size_t)it->pl.arenaFloats, 0.f);
         std::copy(it->pl.constants.begin(), it->pl.constants.end(), it->A.begin());
         it->W = it->pm.blob.data();
@@ -1156,10 +1156,10 @@ extern "C"
             delete it;
             return nullptr;
         }
-        PlanOpts opts;
+        int gemm = GEMM_F32;
         if (const char *e = getenv("DMX_INTERP_GEMM")) // tools/plan_dump.py: the tile choices of the split modes (host only)
-            opts.gemm = atoi(e), opts.kvPlanes = opts.gemm != GEMM_F32;
-        build_plan(it->pm, seg, B, it->pl, opts);
+            gemm = atoi(e);
+        build_plan(it->pm, seg, B, it->pl, plan_opts_from_env(gemm, gemm != GEMM_F32));
         it->W = nullptr;
         return it;
     }
@@ -1258,7 +1258,10 @@ extern "C" int interp_plan_dump(void *h, char *buf, int cap)
 static void print_choice(std::string &all, const std::string &name, const IGemm &g, const GemmChoice &c)
 {
     char line[320];
-    snprintf(line, sizeof(line), "%s %d %d %d %d %d %d %s\n", name.c_str(), g.cfg, g.epi, g.hterms, c.family, c.arith, c.wnf, c.label ? c.label : "-");
+    IGemm chosen = g;
+    chosen.choice = c;
+    snprintf(line, sizeof(line), "%s %d %d %d %d %d %d %s %d\n", name.c_str(), g.cfg, g.epi, g.hterms, c.family, c.arith, c.wnf, c.label ? c.label : "-",
+             (int)gemm_kernel_exists(chosen));
     all += line;
 }
 static int copy_out(const std::string &all, char *buf, int cap)
@@ -1282,7 +1285,8 @@ static bool is_fp16_number(float x)
 }
 
 // The plan a context of GEMM mode `gemm` builds for the handle's model at segment length seg and batch B (gemm_select.h build_chosen_plan, as
-// exec.cpp dmx_get_plan calls it), one line per OP_IGEMM: name, tile cfg, epilogue, hterms, family, arithmetic, wnf, label.
+// exec.cpp dmx_get_plan calls it), one line per OP_IGEMM: name, tile cfg, epilogue, hterms, family, arithmetic, wnf, label, the chosen kernel exists
+// (gemm_select.h gemm_kernel_exists).
 // Model facts: both kinds of weight planes exist; BOTH inexact lists hold the blob elements that are not fp16 numbers (the fp16 list
 // of dmx_model_upload; every fp16 number is two-bf16-term exact, so it contains the bf16 list) plus all weights of the op named
 // `inexact` ("" = none).
@@ -1349,6 +1353,38 @@ extern "C" int interp_select_one(void *h, const char *name, int gemm, int linMod
             return copy_out(all, buf, cap);
         }
     return -2;
+}
+
+// The tile table (csrc/gemm_tiles.h), one line per tile cfg: cfg, BM, BN, waves along M, along N, row fragments, column fragments,
+// K sub-steps, kind (TileKind), fp32 label, split label or "-"
+extern "C" int interp_tiles(char *buf, int cap)
+{
+    std::string all;
+    char line[256];
+    for (int c = 0; c < kNumTileCfgs; ++c)
+    {
+        const TileCfg &t = kTileCfgs[c];
+        snprintf(line, sizeof(line), "%d %d %d %d %d %d %d %d %d %s %s\n", c, t.BM, t.BN, t.WM, t.WN, t.MF, t.NF, t.KS, t.kind, t.label, t.splitLabel ? t.splitLabel : "-");
+        all += line;
+    }
+    return copy_out(all, buf, cap);
+}
+
+// One list, two users: a hand-made op (N columns, S1 taps of seg0, prologue, epilogue, with or without a residual) of an fp32 plan.
+// Returns bit 0: choose_tile sends it to the direct kernels; bit 1: gemm_kernel_exists says the direct kernel for it is compiled
+extern "C" int interp_direct_probe(int N, int S1, int seg0, int pro, int epi, int res)
+{
+    IGemm g;
+    std::memset((void *)&g, 0, sizeof(g));
+    g.B = 1, g.P1 = 64, g.P0 = 1, g.L1 = 64, g.L0 = 1, g.Cin = seg0;
+    g.S1 = S1, g.stride1 = 1, g.dil1 = 1, g.pad1 = S1 / 2, g.seg0 = seg0, g.stride0 = 1;
+    g.K = S1 * seg0, g.Kp = rup(g.K, 16), g.N = N, g.Np = rup(N, 16), g.xBatchStride = (i64)g.L1 * g.L0 * g.Cin;
+    g.pro = pro, g.epi = epi, g.G0 = 1, g.NB = 1;
+    g.res = res ? 64 : -1, g.scale_w = g.rowstat = g.table_w = g.kv = -1;
+    const bool routed = choose_tile(g, epi == EPI_GLU || epi == EPI_GN_GLU_SCALE_RES, false, GEMM_F32, GemmSwitches()).cfg == kDirectCfg;
+    g.cfg = kDirectCfg;
+    g.choice = GemmChoice{GF_DIRECT, 0, 0, kTileCfgs[kDirectCfg].label};
+    return (routed ? 1 : 0) | (gemm_kernel_exists(g) ? 2 : 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

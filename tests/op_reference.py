@@ -488,7 +488,7 @@ def check_launch(pair, i, j, op, reads, values, snap, K_eff=None):
 
 def run_variants(pair, j, op, reads, values, snap, bits_plan, variants, launched, K_eff=None):
     """GEMM j on every tile cfg of its shape (dmx_debug_op_cfgs) under lin_mode 0 / 1 / 3: each distinct (cfg, family, wnf) meets the
-    op's bound; results of one arithmetic are bit-identical whatever the tile or family (plan.h kTileCfgs: siblings keep the column
+    op's bound; results of one arithmetic are bit-identical whatever the tile or family (gemm_tiles.h DMX_TILES: siblings keep the column
     decomposition; gemm_select.h: all families of one arithmetic give the same bits) - row-statistics partials included, among
     tiles of one column block width. The direct kernels (cfg 8, chosen by shape alone, with a k order of their own: dgemm.hip) are
     outside that claim: where the plan's kernel is one, the tile variants are compared with each other. K_eff: as check_op takes it

@@ -26,7 +26,7 @@ LABELS = {"dgemm_direct", "igemm_lin256x128", "igemm_splith_128x128", "igemm_spl
 @pytest.fixture(scope="module")
 def interp():
     srcs = [os.path.join(ROOT, "tests", "cpu_interp.cpp")] + [os.path.join(ROOT, "demucs_cpp_amd", "csrc", f)
-                                                              for f in ("plan.cpp", "plan.h", "model_pack.cpp", "gemm_select.cpp", "gemm_select.h")]
+                                                              for f in ("plan.cpp", "plan.h", "model_pack.cpp", "gemm_select.cpp", "gemm_select.h", "gemm_tiles.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", ROOT, "interp"], stdout=subprocess.DEVNULL)
     L = ctypes.CDLL(SO)
@@ -35,14 +35,17 @@ def interp():
     L.interp_free.argtypes = [ctypes.c_void_p]
     L.interp_select_dump.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
     L.interp_select_one.argtypes = [ctypes.c_void_p, ctypes.c_char_p] + [ctypes.c_int] * 8 + [ctypes.c_char_p, ctypes.c_int]
+    L.interp_tiles.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    L.interp_direct_probe.argtypes = [ctypes.c_int] * 6
     return L
 
 
 def parse(text):
     ops = []
     for ln in text.splitlines():
-        name, cfg, epi, ht, fam, arith, wnf, label = ln.split()
-        ops.append(dict(name=name, cfg=int(cfg), epi=int(epi), hterms=int(ht), family=int(fam), arith=int(arith), wnf=int(wnf), label=label))
+        name, cfg, epi, ht, fam, arith, wnf, label, exists = ln.split()
+        ops.append(dict(name=name, cfg=int(cfg), epi=int(epi), hterms=int(ht), family=int(fam), arith=int(arith), wnf=int(wnf), label=label,
+                        exists=int(exists)))
     return ops
 
 
@@ -74,6 +77,7 @@ def test_every_op_gets_one_choice_with_one_arithmetic(ns, interp, tmp_models):
                     for o in ops:
                         where = (seg, b, gemm, lin, o)
                         assert o["family"] != NONE and o["label"] in LABELS, where
+                        assert o["exists"], where  # the chosen kernel is compiled and its launcher takes the op (gemm_kernel_exists)
                         assert (o["arith"] != 0) == (o["family"] in SPLIT), where
                         assert (o["family"] == DIRECT) == (o["cfg"] == 8) or o["arith"], where
                         if gemm == F32:
@@ -128,13 +132,51 @@ def test_narrow_split_tiles_refuse_residuals_and_row_statistics(interp, tmp_mode
                 kw = dict(gemm=gemm, lin=lin, cfg=cfg, Np=np_)
                 assert one(interp, h, k1["name"], rowstat=-1, res=-1, **kw)["family"] == NARROW  # the base case is one the kernel takes
                 o = one(interp, h, k1["name"], rowstat=-1, res=64, **kw)
-                assert o["family"] == TILE and o["arith"] == 0 and not o["label"].startswith("igemm_split"), o
+                assert o["family"] == TILE and o["arith"] == 0 and not o["label"].startswith("igemm_split") and o["exists"], o
                 o = one(interp, h, k1["name"], rowstat=64, res=-1, **kw)
-                assert (o["family"] == NARROW) == (np_ == 32), o
+                assert (o["family"] == NARROW) == (np_ == 32) and o["exists"], o
             for cfg in (6, 13):
                 assert one(interp, h, tr["name"], gemm=gemm, lin=lin, cfg=cfg, rowstat=-1)["family"] == NARROW
                 o = one(interp, h, tr["name"], gemm=gemm, lin=lin, cfg=cfg, rowstat=64)
-                assert o["family"] == TILE and o["arith"] == 0, o
+                assert o["family"] == TILE and o["arith"] == 0 and o["exists"], o
             for cfg in (5, 12):  # no transposed-conv form at 32 columns
-                assert one(interp, h, tr["name"], gemm=gemm, lin=lin, cfg=cfg, N=32, Np=32, rowstat=-1)["family"] == TILE
+                o = one(interp, h, tr["name"], gemm=gemm, lin=lin, cfg=cfg, N=32, Np=32, rowstat=-1)
+                assert o["family"] == TILE and o["exists"], o
     interp.interp_free(h)
+
+
+def test_labels_are_the_tile_tables(interp):
+    """LABELS above is a hand-written pin: the labels the tile table (csrc/gemm_tiles.h) can produce - the fp32 and the exact-split
+    label of every tile that has a kernel - plus the labels of the kernels no tile cfg stands for."""
+    buf = ctypes.create_string_buffer(1 << 14)
+    assert interp.interp_tiles(buf, 1 << 14) > 0
+    rows = [ln.split() for ln in buf.value.decode().splitlines()]
+    assert [int(r[0]) for r in rows] == list(range(21))
+    table = {lab for r in rows if int(r[8]) != 0 for lab in r[9:11] if lab != "-"}
+    split_only = {"igemm_splith_128x128", "igemm_splith_64x128", "igemm_split_128x256", "igemm_split_128x192", "igemm_split_128x96d"}
+    assert not table & split_only
+    assert table | split_only == LABELS
+
+
+def test_direct_kernel_list_has_one_meaning(interp):
+    """One list, two users: over a brute-force sweep of shapes, the rule that sends an op of an fp32 plan to the direct kernels
+    (choose_tile) and the existence answer for the direct kernel (gemm_kernel_exists) agree - both read DMX_DIRECT_COMBOS and the
+    column-chunk rule of csrc/gemm_tiles.h. Column fragments 24 and 48 (N = 384, 768) reach the chunk rule."""
+    PRO_NONE, PRO_GN_GELU = 0, 2
+    EPI_GN_GLU_SCALE_RES = 3
+    routed = set()
+    for nf in list(range(1, 13)) + [24, 48]:
+        for s1 in (1, 3):
+            for seg0 in (8, 12, 16, 24, 32, 48, 96):
+                for pro in range(3):
+                    for epi in range(9):
+                        for res in (0, 1):
+                            for n in (16 * nf, 16 * nf - 4):  # a full and a partly filled last fragment
+                                r = interp.interp_direct_probe(n, s1, seg0, pro, epi, res)
+                                assert r in (0, 3), (n, s1, seg0, pro, epi, res, r)
+                                if r:
+                                    routed.add((nf, s1, seg0, pro, epi))
+                                    assert not (res and epi in (EPI_LINEAR, EPI_TRCONV))  # no residual operand on these epilogues
+    chunked = {(nf, 1, seg0, PRO_GN_GELU, EPI_GN_GLU_SCALE_RES) for nf in (24, 48) for seg0 in (24, 48)}
+    assert chunked <= routed and len(routed - chunked) == 18  # every row of the list and of the chunk rule, and nothing else
+    assert (1, 3, 48, PRO_NONE, EPI_LINEAR) in routed and (6, 1, 48, PRO_NONE, 2) in routed

@@ -157,7 +157,7 @@ def test_every_op_against_fp64_with_a_silent_segment(dmxb, L, tmp_models):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # every tile and every kernel family
-UNUSED_CFGS = {1, 17, 18}  # plan.h kTileCfgs: 1 is never chosen, 17 / 18 have no kernel (the slots keep the numbering)
+UNUSED_CFGS = {1, 17, 18}  # gemm_tiles.h DMX_TILES: 1 is never chosen, 17 / 18 have no kernel (the slots keep the numbering)
 FAMILIES = {1: "GF_DIRECT", 2: "GF_TILE", 3: "GF_LIN256", 4: "GF_SPLIT_STAGED", 5: "GF_SPLIT_STAGED_LIN", 6: "GF_SPLIT_LIN", 7: "GF_SPLIT_LINH",
             8: "GF_SPLIT_LINW", 9: "GF_SPLIT_WIDE_CONV", 10: "GF_SPLIT_NARROW"}
 # not reachable in f32 / bf16x3 contexts: the fp16-term linear kernel exists in fp16x3 contexts only (test_every_op_against_fp64

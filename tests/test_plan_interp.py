@@ -18,7 +18,7 @@ SO = os.path.join(ROOT, "tests", "_build", "libcpu_interp.so")
 
 @pytest.fixture(scope="module")
 def interp():
-    srcs = [os.path.join(ROOT, "tests", "cpu_interp.cpp")] + [os.path.join(ROOT, "demucs_cpp_amd", "csrc", f) for f in ("plan.cpp", "plan.h", "model_pack.cpp")]
+    srcs = [os.path.join(ROOT, "tests", "cpu_interp.cpp")] + [os.path.join(ROOT, "demucs_cpp_amd", "csrc", f) for f in ("plan.cpp", "plan.h", "model_pack.cpp", "gemm_select.cpp", "gemm_select.h", "gemm_tiles.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", ROOT, "interp"], stdout=subprocess.DEVNULL)
     L = ctypes.CDLL(SO)
@@ -144,6 +144,23 @@ TILES = {0: (128, 128), 1: (64, 64), 2: (128, 96), 3: (128, 48), 4: (256, 16), 5
 # the families with row statistics never cross (plan.h)
 FAMILY = {0: "2x4", 7: "2x4", 15: "2x4", 17: "2x4", 18: "2x4", 19: "2x4", 20: "1x6", 9: "2x2", 16: "2x2", 2: "1x6", 10: "1x6", 3: "1x3", 11: "1x3", 5: "1x2", 12: "1x2",
           6: "1x4", 13: "1x4", 4: "1x1", 14: "1x1", 8: "direct", 1: "2x2o"}
+
+
+def test_tile_table_equals_its_pins(interp):
+    """TILES and FAMILY above are hand-written pins of csrc/gemm_tiles.h: tile sizes, the column decomposition (waves x fragments
+    along N) and which slots have a kernel."""
+    buf = ctypes.create_string_buffer(1 << 14)
+    interp.interp_tiles.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    assert interp.interp_tiles(buf, 1 << 14) > 0
+    rows = [ln.split() for ln in buf.value.decode().splitlines()]
+    assert [int(r[0]) for r in rows] == sorted(TILES) == sorted(FAMILY)
+    NONE, TILE, DIRECT, LIN256 = range(4)  # gemm_tiles.h TileKind
+    for r in rows:
+        cfg, bm, bn, wm, wn, mf, nf, ks, kind = (int(v) for v in r[:9])
+        assert (bm, bn) == TILES[cfg] == (wm * mf * 16, wn * nf * 16), r
+        assert kind == {8: DIRECT, 19: LIN256, 1: NONE, 17: NONE, 18: NONE}.get(cfg, TILE), r
+        assert FAMILY[cfg] == ("direct" if kind == DIRECT else f"{wn}x{nf}" + ("o" if cfg == 1 else "")), r
+        assert ks == (0 if kind != TILE else 1 if cfg == 20 else 2), r  # 16-deep K-tiles on cfg 20 only
 
 
 @pytest.mark.parametrize("ns", [4, 6])

@@ -1,20 +1,20 @@
 #!/usr/bin/env python
-"""Ablation / tuning copies of csrc/igemm_split.hip and csrc/plan.cpp for the linear-layer kernel (never the product).
+"""Ablation / tuning copies of csrc/igemm_split.hip and csrc/gemm_select.cpp for the linear-layer kernel (never the product).
     linhalf : igemm_split_lin_kernel loads and splits the activations of every OTHER K-tile only (odd tiles reuse the planes of the
               tile before; results wrong): the loop with half the activation loads and half the split work per MFMA - what a
               128 x 256 tile would change, with everything else (weight staging, fragment reads, tile count) as it is
-    lin64   : plan.cpp keeps every linear layer on 64-row tiles (cfg 7) at any batch size
+    lin64   : choose_tile keeps every linear layer on 64-row tiles (cfg 7) at any batch size
     lin64x3 : lin64 + the 64-row kernel compiled for THREE workgroups per CU (168 registers)
 Writes build/variants/<file>_<name>.{hip,cpp}; build with
     make variant1src NAME=linhalf FILE=igemm_split SRC=build/variants/igemm_split_linhalf.hip
-    make variant2src NAME=lin64x3 FILE=igemm_split SRC=build/variants/igemm_split_x3.hip FILE2=plan SRC2=build/variants/plan_lin64.cpp"""
+    make variant2src NAME=lin64x3 FILE=igemm_split SRC=build/variants/igemm_split_x3.hip FILE2=gemm_select SRC2=build/variants/gemm_select_lin64.cpp"""
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 out = os.path.join(ROOT, "build", "variants")
 os.makedirs(out, exist_ok=True)
 src = open(os.path.join(ROOT, "demucs_cpp_amd", "csrc", "igemm_split.hip")).read()
-plan = open(os.path.join(ROOT, "demucs_cpp_amd", "csrc", "plan.cpp")).read()
+select = open(os.path.join(ROOT, "demucs_cpp_amd", "csrc", "gemm_select.cpp")).read()
 
 
 def sub(s, old, new):
@@ -45,9 +45,9 @@ lb = """template <int WMF, int WNF, int EPI, int ARITH = 0>
 __global__ __launch_bounds__(256, 2) void igemm_split_lin_kernel(const GemmArgs p)"""
 open(os.path.join(out, "igemm_split_x3.hip"), "w").write(sub(src, lb, lb.replace("__launch_bounds__(256, 2)", "__launch_bounds__(256, WMF == 1 ? 3 : 2)")))
 
-cfgline = "        g.cfg = refine_cfg(choose_cfg((i64)g.P1 * g.P0, g.N, paired), (i64)g.B * g.P1 * g.P0, g.N, g.rowstat >= 0);"
-open(os.path.join(out, "plan_lin64.cpp"), "w").write(sub(plan, cfgline, cfgline + """
-        if (opts.gemm != GEMM_F32 && g.cfg == 0 && g.pro == PRO_NONE && g.S1 == 1 && g.seg0 == g.K && g.K % 32 == 0 && g.N % 128 == 0 &&
-            (g.epi == EPI_LINEAR || g.epi == EPI_SCALE_RES || g.epi == EPI_KPL || g.epi == EPI_VT))
-            g.cfg = 7; // (experiment: the linear layers on 64-row tiles at any batch)"""))
-print("wrote igemm_split_linhalf.hip igemm_split_x3.hip plan_lin64.cpp")
+cfgline = "    int cfg = refine_cfg(choose_cfg(g.N, paired), M, g.N, g.rowstat >= 0);"
+open(os.path.join(out, "gemm_select_lin64.cpp"), "w").write(sub(select, cfgline, cfgline + """
+    if (gemm != GEMM_F32 && cfg == 0 && g.pro == PRO_NONE && g.S1 == 1 && g.seg0 == g.K && g.K % 32 == 0 && g.N % 128 == 0 &&
+        (g.epi == EPI_LINEAR || g.epi == EPI_SCALE_RES || g.epi == EPI_KPL || g.epi == EPI_VT))
+        cfg = 7; // (experiment: the linear layers on 64-row tiles at any batch)"""))
+print("wrote igemm_split_linhalf.hip igemm_split_x3.hip gemm_select_lin64.cpp")
