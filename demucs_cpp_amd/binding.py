@@ -51,6 +51,7 @@ EXPORTS = [
     "dmx_loud_encode_meters_device", "dmx_loud_encode_meters", "dmx_tracks_infer_meters", "dmx_tracks_infer_from_flac_meters",
     "dmx_limiter_tables", "dmx_limiter_slopes", "dmx_limiter_workspace_bytes", "dmx_limit_device", "dmx_limit_device_timed", "dmx_limit",
     "dmx_limiter_check", "dmx_loud_encode_limit_device", "dmx_loud_encode_limit", "dmx_tracks_infer_limit", "dmx_tracks_infer_from_flac_limit",
+    "dmx_bss_check", "dmx_bss_windows", "dmx_bss_eval_workspace_bytes", "dmx_bss_eval_device", "dmx_bss_eval_device_timed", "dmx_bss_eval",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -216,6 +217,14 @@ def lib():
         L.dmx_loud_encode_limit.argtypes = L.dmx_loud_encode_meters.argtypes + [vp, vp]
         L.dmx_tracks_infer_limit.argtypes = L.dmx_tracks_infer_meters.argtypes + [vp, vp]
         L.dmx_tracks_infer_from_flac_limit.argtypes = L.dmx_tracks_infer_from_flac_meters.argtypes + [vp, vp]
+        L.dmx_bss_check.argtypes = [vp]
+        L.dmx_bss_windows.argtypes = [i64, i64, i64]
+        L.dmx_bss_windows.restype = i64
+        L.dmx_bss_eval_workspace_bytes.argtypes = [ci, ci, i64, ci]
+        L.dmx_bss_eval_workspace_bytes.restype = i64
+        L.dmx_bss_eval_device.argtypes = [ci, vp, vp, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp]
+        L.dmx_bss_eval_device_timed.argtypes = L.dmx_bss_eval_device.argtypes + [vp]
+        L.dmx_bss_eval.argtypes = [ci, vp, vp, ci, ci, i64, vp, vp, vp, vp]
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -1143,6 +1152,50 @@ def limit(x: np.ndarray, rate: int, max_peak: float, gain: float = 1.0, true_pea
     _chk(lib().dmx_limit(device, x.ctypes.data, n, int(bool(interleaved)), int(rate), float(gain), float(max_peak), int(bool(true_peak)),
                          ctypes.byref(spec), M.ctypes.data, G.ctypes.data, ctypes.byref(res)))
     return M[:n], G[:n], res
+
+
+BSS_OK, BSS_SINGULAR = 0, 1  # DMX_BSS_*
+
+
+class BssSpec(ctypes.Structure):
+    """dmx_bss_spec: the window and the hop in samples, the filter length in taps; the defaults are museval's"""
+    _fields_ = [("window", ctypes.c_int64), ("hop", ctypes.c_int64), ("filters_len", ctypes.c_int)]
+
+    def __init__(self, window=44100, hop=44100, filters_len=512):
+        super().__init__(int(window), int(hop), int(filters_len))
+
+
+def bss_check(spec: Optional[BssSpec]):
+    """validates a BssSpec (dmx_bss_check; no GPU); raises DmxError naming the field"""
+    _chk(lib().dmx_bss_check(None if spec is None else ctypes.byref(spec)))
+
+
+def bss_windows(n: int, window: int = 44100, hop: int = 44100) -> int:
+    return lib().dmx_bss_windows(int(n), int(window), int(hop))
+
+
+def bss_eval_workspace_bytes(n_sources: int, channels: int, n: int, filters_len: int = 512) -> int:
+    return lib().dmx_bss_eval_workspace_bytes(int(n_sources), int(channels), int(n), int(filters_len))
+
+
+def bss_eval(refs: np.ndarray, ests: np.ndarray, window: int = 44100, hop: int = 44100, filters_len: int = 512, device: int = 0,
+             filters: bool = False) -> dict:
+    """BSS Eval v4 (dmx_bss_eval): refs and ests (J, C, n) float32 -> {"sdr", "isr", "sir", "sar"}: (J, nwin) float64 in dB,
+    "status": BSS_OK | BSS_SINGULAR and, with filters=True, "X": (J, J * C * filters_len, C) float64, the all-source filters."""
+    refs, ests = np.ascontiguousarray(refs, np.float32), np.ascontiguousarray(ests, np.float32)
+    assert refs.ndim == 3 and refs.shape == ests.shape, "refs, ests: expected two (J, C, n) arrays"
+    J, C, n = refs.shape
+    spec = BssSpec(window, hop, filters_len)
+    bss_check(spec)
+    m = np.zeros((4, J, max(bss_windows(n, window, hop), 1)), np.float64)
+    X = np.zeros((J, J * C * int(filters_len), C), np.float64) if filters else None
+    status = ctypes.c_int(-1)
+    _chk(lib().dmx_bss_eval(device, refs.ctypes.data, ests.ctypes.data, J, C, n, ctypes.byref(spec), m.ctypes.data, ctypes.byref(status),
+                            None if X is None else X.ctypes.data))
+    out = {"sdr": m[0], "isr": m[1], "sir": m[2], "sar": m[3], "status": status.value}
+    if filters:
+        out["X"] = X
+    return out
 
 
 def flac_bound(bits: int, n: int) -> int:

@@ -1026,3 +1026,113 @@ extern "C" int dmx_flac_decode_profile(int device, const void *d_file, int64_t b
         DMXCHK(ev.elapsed(k, k + 1, &ms[k]));
     return DMX_OK;
 }
+
+// --------------------------------------------------------------------------- BSS Eval v4 (bss.hip)
+static int bss_check(const char *fn, const dmx_bss_spec *spec)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: null spec pointer", fn);
+    if (spec->window < 1)
+        return fail(DMX_ERR_ARG, "%s: bss spec: window %lld is below 1", fn, (long long)spec->window);
+    if (spec->hop < 1)
+        return fail(DMX_ERR_ARG, "%s: bss spec: hop %lld is below 1", fn, (long long)spec->hop);
+    if (spec->filters_len < 1 || spec->filters_len > kBssMaxFilter)
+        return fail(DMX_ERR_ARG, "%s: bss spec: filters_len %d is not in [1, %d]", fn, spec->filters_len, kBssMaxFilter);
+    return DMX_OK;
+}
+extern "C" int dmx_bss_check(const dmx_bss_spec *spec) { return bss_check("dmx_bss_check", spec); }
+extern "C" int64_t dmx_bss_windows(int64_t n, int64_t window, int64_t hop) { return bss_windows(n, window, hop); }
+extern "C" int64_t dmx_bss_eval_workspace_bytes(int n_sources, int channels, int64_t n, int filters_len)
+{
+    return bss_workspace_bytes(n_sources, channels, n, filters_len);
+}
+
+static int bss_shape(const char *fn, int J, int C, int64_t n, const dmx_bss_spec *spec)
+{
+    DMXCHK(bss_check(fn, spec));
+    if (!bss_shape_ok(J, C, n, spec->filters_len))
+        return fail(DMX_ERR_ARG, "%s: n_sources %d, channels %d, n %lld, filters_len %d (1 .. %d sources, 1 | 2 channels, 1 <= n < 2^31, "
+                    "n_sources channels filters_len <= %d)", fn, J, C, (long long)n, spec->filters_len, kBssMaxSources, kBssMaxOrder);
+    return DMX_OK;
+}
+
+// marks: null, or seven events around the six stages
+static int bss_device(const char *fn, int device, const float *d_refs, const float *d_ests, int J, int C, int64_t n, int64_t plane_stride,
+                      const dmx_bss_spec *spec, double *d_metrics, int *d_status, double *d_filters, void *d_work, void *stream,
+                      hipEvent_t *marks)
+{
+    DMXCHK(bss_shape(fn, J, C, n, spec));
+    if (plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (n <= plane_stride)", fn, (long long)n, (long long)plane_stride);
+    if (!d_refs || !d_ests || !d_metrics || !d_status || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn,
+                    !d_refs ? "d_refs" : !d_ests ? "d_ests" : !d_metrics ? "d_metrics" : !d_status ? "d_status" : "d_work");
+    if ((((uintptr_t)d_refs | (uintptr_t)d_ests | (uintptr_t)d_status) & 3) != 0 || (((uintptr_t)d_metrics | (uintptr_t)d_filters) & 7) != 0 ||
+        ((uintptr_t)d_work & 255) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_refs, d_ests and d_status must be 4-byte aligned, d_metrics and d_filters 8-byte, d_work 256-byte", fn);
+    HIPCHK(hipSetDevice(device));
+    const BssJob job{d_refs, d_ests, J, C, spec->filters_len, n, plane_stride, spec->window, spec->hop, d_metrics, d_status, d_filters,
+                     (unsigned char *)d_work};
+    launch_bss(job, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_bss_eval_device(int device, const float *d_refs, const float *d_ests, int n_sources, int channels, int64_t n,
+                                   int64_t plane_stride, const dmx_bss_spec *spec, double *d_metrics, int *d_status, double *d_filters,
+                                   void *d_work, void *stream)
+{
+    return bss_device("dmx_bss_eval_device", device, d_refs, d_ests, n_sources, channels, n, plane_stride, spec, d_metrics, d_status, d_filters,
+                      d_work, stream, nullptr);
+}
+
+extern "C" int dmx_bss_eval_device_timed(int device, const float *d_refs, const float *d_ests, int n_sources, int channels, int64_t n,
+                                         int64_t plane_stride, const dmx_bss_spec *spec, double *d_metrics, int *d_status, double *d_filters,
+                                         void *d_work, void *stream, float *ms)
+{
+    const char *fn = "dmx_bss_eval_device_timed";
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    HIPCHK(hipSetDevice(device));
+    Events<7> ev(fn);
+    DMXCHK(ev.create());
+    DMXCHK(bss_device(fn, device, d_refs, d_ests, n_sources, channels, n, plane_stride, spec, d_metrics, d_status, d_filters, d_work, stream, ev.ev));
+    DMXCHK(ev.wait(6));
+    for (int k = 0; k < 6; ++k)
+        DMXCHK(ev.elapsed(k, k + 1, &ms[k]));
+    return DMX_OK;
+}
+
+extern "C" int dmx_bss_eval(int device, const float *refs, const float *ests, int n_sources, int channels, int64_t n, const dmx_bss_spec *spec,
+                            double *metrics, int *status, double *filters)
+{
+    const char *fn = "dmx_bss_eval";
+    DMXCHK(bss_shape(fn, n_sources, channels, n, spec));
+    if (!refs || !ests || !metrics || !status)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !refs ? "refs" : !ests ? "ests" : !metrics ? "metrics" : "status");
+    HIPCHK(hipSetDevice(device));
+    const int M = n_sources * channels;
+    const size_t inBytes = sizeof(float) * (size_t)M * (size_t)n;
+    const size_t outBytes = sizeof(double) * 4 * (size_t)n_sources * (size_t)bss_windows(n, spec->window, spec->hop);
+    const size_t filtBytes = sizeof(double) * (size_t)n_sources * (size_t)M * (size_t)spec->filters_len * (size_t)channels;
+    DevScratch d;
+    float *dIn = (float *)d.get(2 * inBytes);
+    unsigned char *dOut = (unsigned char *)d.get(outBytes + 256); // the metrics, then the status
+    double *dFilt = filters ? (double *)d.get(filtBytes) : nullptr;
+    void *dWork = d.get((size_t)bss_workspace_bytes(n_sources, channels, n, spec->filters_len));
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    int *dStatus = (int *)(dOut + ((outBytes + 255) & ~(size_t)255));
+    if (hipMemcpy(dIn, refs, inBytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dIn + (size_t)M * (size_t)n, ests, inBytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(bss_device(fn, device, dIn, dIn + (size_t)M * (size_t)n, n_sources, channels, n, n, spec, (double *)dOut, dStatus, dFilt, dWork, nullptr,
+                      nullptr));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(metrics, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(status, dStatus, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+        (filters && hipMemcpy(filters, dFilt, filtBytes, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
+}

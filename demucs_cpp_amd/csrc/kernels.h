@@ -5,6 +5,7 @@
 #include "loudness_plan.h"
 #include "meters_plan.h"
 #include "limiter_plan.h"
+#include "bss_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -478,6 +479,22 @@ struct LimitTable
     LimitPiece p[kMax];
 };
 void launch_limit_encode(const LimitPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// ---- BSS Eval v4 (bss.hip; specification: DESIGN.md section 2.18, restated in tests/bss_spec.py) ----
+// (the windows, the limits and the workspace: bss_plan.h)
+// refs and ests: J C planar fp32 planes of n samples, plane p = source * C + channel at p * stride. metrics: double [4][J][nwin]
+// (SDR, ISR, SIR, SAR), status: one int (DMX_BSS_*), filters: NULL or double [J][J C L][C], all on the device. marks: NULL, or
+// seven events around the six stages (gram, fill, cholesky, solve, project, windows)
+struct BssJob
+{
+    const float *refs, *ests;
+    int J, C, L;
+    i64 n, stride, window, hop;
+    double *metrics;
+    int *status;
+    double *filters;
+    unsigned char *work;
+};
+void launch_bss(const BssJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
 // ---- the track path's converter (resample.hip) ----
 // outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
 // output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the

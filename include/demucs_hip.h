@@ -589,6 +589,48 @@ extern "C"
                                          const dmx_loudness_spec *loud, dmx_loudness_result *report, dmx_meters_result *meters,
                                          const dmx_limiter_spec *lim, dmx_limit_result *limit);
 
+    /* ---- BSS Eval v4: SDR, ISR, SIR and SAR (csrc/bss.hip; DESIGN.md section 2.18, restated in tests/bss_spec.py; the
+     * counterpart of museval.eval_mus_track in the reference's scripts/evaluate-demixed-output.py). References and estimates
+     * are J sources (1 .. 8) of C channels (1 | 2) and n samples, fp32, taken to binary64 on load. Over the whole track the
+     * stage estimates distortion filters of filters_len taps (1 .. 512; J C filters_len <= 6144): X_i, the least-squares
+     * projection of estimate i onto the delayed references of all sources, and Y_i, onto those of source i alone, by the normal
+     * equations G X = D with a Cholesky factorisation - no pivoting, no regularisation, no fallback: a pivot that is not finite
+     * and positive gives DMX_BSS_SINGULAR and NaN everywhere. With p_all and p_own the two projections: e_spat = p_own - r_i,
+     * e_interf = p_all - p_own, e_artif = e_i - p_all, and per window [w hop, w hop + window), over channels and samples,
+     * SDR = sum r_i^2 / sum (e_i - r_i)^2, ISR = sum r_i^2 / sum e_spat^2, SIR = sum p_own^2 / sum e_interf^2, SAR = sum p_all^2
+     * / sum e_artif^2 in dB (+inf for a zero denominator). n < window: one window [0, n). A source whose reference is all zero
+     * is DROPPED: left out of every system, NaN in every window, its filters zero. A window in which a kept source's reference
+     * or estimate is all zero is NaN for every source. All arithmetic is binary64 in a fixed order: equal inputs, equal bits.
+     * Out of scope: framewise filters, the permutation search, the bss_eval_sources variant. */
+#define DMX_BSS_OK 0
+#define DMX_BSS_SINGULAR 1
+    typedef struct dmx_bss_spec
+    {
+        int64_t window, hop; /* samples, >= 1; museval's default: 44100 and 44100 */
+        int filters_len;     /* 1 .. 512; museval's default: 512 */
+    } dmx_bss_spec;
+    /* Pure host function; DMX_ERR_ARG with a message that names the field. */
+    int dmx_bss_check(const dmx_bss_spec *spec);
+    /* the windows of n samples; -1 for n, window or hop below 1. Pure host function. */
+    int64_t dmx_bss_windows(int64_t n, int64_t window, int64_t hop);
+    /* the bytes of d_work; -1 for arguments outside the ranges above or n >= 2^31. Pure host function. */
+    int64_t dmx_bss_eval_workspace_bytes(int n_sources, int channels, int64_t n, int filters_len);
+    /* d_refs and d_ests: planar planes, plane source * channels + channel at plane_stride (>= n) floats. d_metrics: double
+     * [4][n_sources][dmx_bss_windows] in the order SDR, ISR, SIR, SAR; d_status: one int, DMX_BSS_*; d_filters: NULL, or double
+     * [n_sources][n_sources channels filters_len][channels], X_i[(j, c, tau)][c'']; d_work: dmx_bss_eval_workspace_bytes, 256-
+     * byte aligned. Asynchronous on `stream`. */
+    int dmx_bss_eval_device(int device, const float *d_refs, const float *d_ests, int n_sources, int channels, int64_t n,
+                            int64_t plane_stride, const dmx_bss_spec *spec, double *d_metrics, int *d_status, double *d_filters,
+                            void *d_work, void *stream);
+    /* measurement (tools/bss_bench.py): the call above, synchronised, with the times of its six stages between HIP events in
+     * ms[0..6): gram, fill, cholesky, solve, project, windows */
+    int dmx_bss_eval_device_timed(int device, const float *d_refs, const float *d_ests, int n_sources, int channels, int64_t n,
+                                  int64_t plane_stride, const dmx_bss_spec *spec, double *d_metrics, int *d_status, double *d_filters,
+                                  void *d_work, void *stream, float *ms);
+    /* the same on host buffers: refs and ests [n_sources][channels][n]; filters may be NULL */
+    int dmx_bss_eval(int device, const float *refs, const float *ests, int n_sources, int channels, int64_t n, const dmx_bss_spec *spec,
+                     double *metrics, int *status, double *filters);
+
     /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
      * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
      * PCM as the stages above write it (16-bit pairs or packed 24 bit) -> a complete .flac file: "fLaC", one STREAMINFO block

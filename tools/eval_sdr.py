@@ -14,7 +14,9 @@ that from plain WAV stems:
     eval_sdr.py <reference dir> <estimate dir>
         <reference dir> : {drums,bass,other,vocals}.wav of one MUSDB18-HQ track (44.1 kHz stereo)
         <estimate dir>  : target_{i}_{name}.wav as written by the demucs*.cpp.main drivers
-prints one line per target in the format of SDR_scores.md. Reference values for 'Zeno - Signs', shift offset
+prints one line per target in the format of SDR_scores.md. With --bss [--device N] the full BSS Eval v4 decomposition runs
+on the GPU (demucs_cpp_amd.binding.bss_eval, csrc/bss.hip: 512-tap distortion filters over the whole track) and every line
+carries SDR, SIR, ISR and SAR, the nanmedian over the windows, in the table's column order. Reference values for 'Zeno - Signs', shift offset
 1337 (.github/SDR_scores.md:16-20): vocals 8.370, drums 10.002, bass 4.021, other 7.469 (4-source model).
 """
 from __future__ import annotations
@@ -95,6 +97,22 @@ def track_sdr(refs: Dict[str, np.ndarray], ests: Dict[str, np.ndarray]) -> Dict[
     return res
 
 
+def track_bss(refs: Dict[str, np.ndarray], ests: Dict[str, np.ndarray], device: int = 0) -> Dict[str, Dict[str, float]]:
+    """{target: {"SDR", "SIR", "ISR", "SAR"}}: the nanmedian over the 1 s windows of BSS Eval v4 on the GPU (museval's defaults)"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from demucs_cpp_amd import binding
+
+    names = [k for k in refs if k in ests]
+    n = min(min(len(refs[k]), len(ests[k])) for k in names)
+    planes = lambda d: np.stack([np.asarray(d[k][:n], np.float32).T for k in names])  # noqa: E731  (J, C, n)
+    out = binding.bss_eval(planes(refs), planes(ests), device=device)
+    if out["status"] != binding.BSS_OK:
+        print("bss_eval: the normal equations are singular (DMX_BSS_SINGULAR): every value is NaN", file=sys.stderr)
+    with np.errstate(all="ignore"):
+        return {k: {m: float(np.nanmedian(out[m.lower()][j])) if not np.isnan(out[m.lower()][j]).all() else float("nan")
+                    for m in ("SDR", "SIR", "ISR", "SAR")} for j, k in enumerate(names)}
+
+
 def load_dirs(ref_dir: str, est_dir: str):
     refs, ests = {}, {}
     for i, name in enumerate(TARGETS):
@@ -115,10 +133,21 @@ def main(argv):
     """eval_sdr.py <reference dir> <estimate dir>
     eval_sdr.py --track <reference dir> --estimates <estimate dir> [--reference-table htdemucs_4s|htdemucs_6s|htdemucs_ft|hdemucs_mmi]
                 [--tolerance 0.1]      prints the reference's own C++ score (.github/SDR_scores.md) and the verdict beside each
-                                       target; the exit code is the number of targets outside the tolerance"""
+                                       target; the exit code is the number of targets outside the tolerance
+    --bss [--device N] with either form: SDR, SIR, ISR and SAR per target from the GPU (the verdict stays the SDR's)"""
     ref_dir = est_dir = table = None
     tol = 0.1
-    args = argv[1:]
+    args = list(argv[1:])
+    bss, device = "--bss" in args, 0
+    if bss:
+        args.remove("--bss")
+    if "--device" in args:
+        k = args.index("--device")
+        device = int(args[k + 1]) if bss and k + 1 < len(args) and args[k + 1].isdigit() else -1
+        del args[k:k + 2]
+    if device < 0:
+        print(main.__doc__)
+        return 2
     if len(args) == 2 and not args[0].startswith("--"):
         ref_dir, est_dir = args
     else:
@@ -145,8 +174,12 @@ def main(argv):
         return 1
     want = REFERENCE_TABLES.get(table, {})
     bad = 0
+    full = track_bss(refs, ests, device) if bss else {}
     for name, v in track_sdr(refs, ests).items():
         line = f"{name:15s} ==> SDR: {v:7.3f}"
+        if bss:
+            v = full[name]["SDR"]
+            line = f"{name:15s} ==> " + "  ".join(f"{m}: {full[name][m]:7.3f}" for m in ("SDR", "SIR", "ISR", "SAR"))
         if name in want:
             ok = abs(v - want[name]) <= tol
             bad += 0 if ok else 1

@@ -26,7 +26,7 @@ convert() { # $1 checkpoint or container, $2 family -> prints the container path
   esac
 }
 score() { # $1 family, $2 stems dir, $3 reference table key
-  python "$R/tools/eval_sdr.py" --track "$DMX_MUSDB_TRACK" --estimates "$2" --reference-table "$3" --tolerance 0.1 | tee "$OUT/sdr_$1.txt"
+  python "$R/tools/eval_sdr.py" --track "$DMX_MUSDB_TRACK" --estimates "$2" --reference-table "$3" --tolerance 0.1 --bss | tee "$OUT/sdr_$1.txt"
   bad=$((bad + ${PIPESTATUS[0]}))
 }
 export DMX_SHIFT_OFFSET=${DMX_SHIFT:-1337}
