@@ -3,6 +3,7 @@
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
 //                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]
+//                         [--wiener N [--wiener-residual]]
 //                         [--limit] [--limit-attack MS] [--limit-release MS]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
@@ -56,6 +57,9 @@
 //   --flac-level N           with --flac: 0 (default) FIXED predictors alone, 1 adds an LPC predictor of order 8, 2 orders 8
 //                            and 12 (smaller files, the same samples); without --flac it changes nothing
 // With any of them the defaults are demucs's: rescale, 16 bit. Without any of them the files are float32 as before.
+//   --wiener N               refine the float32 stems with N (1 .. 8) EM iterations of the multichannel Wiener filter against the
+//                            track's mixture (dmx_wiener; demucs's wiener_iters); --wiener-residual adds the residual source.
+//                            Not together with PCM / FLAC / remix / loudness options or a resampled or FLAC-fed track for now.
 // A track at another rate (DMX_RESAMPLE=1) takes them at its own rate: the library converts inside the track path
 // (dmx_tracks_infer_rates, dmx_tracks_infer_from_flac_rates) and the outputs are the stems at the file's rate.
 // <model> may also be a bag of models (dmx_tracks_infer_bag through the demucscpp::demucs_bag overloads; every option
@@ -84,6 +88,7 @@ using namespace demucscpp;
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
               << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]"
+              << " [--wiener N [--wiener-residual]]"
               << " [--limit] [--limit-attack MS] [--limit-release MS] (--clip-mode limit: --limit without loudnorm)"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
@@ -136,10 +141,18 @@ int main(int argc, const char **argv)
     bool limit = false, clip_limit = false, limit_times = false;
     float limit_attack = DMX_LIMIT_ATTACK_MS, limit_release = DMX_LIMIT_RELEASE_MS;
     LimitReport limit_report; // filled as well with --limit
+    wiener_options wiener; // --wiener N [--wiener-residual]
+    bool with_wiener = false, wiener_residual = false;
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
         const std::string opt = argv[a];
+        if (opt == "--wiener-residual") // no value; it needs --wiener, checked behind the loop
+        {
+            wiener_residual = true;
+            --a;
+            continue;
+        }
         if (opt == "--int16" || opt == "--int24" || opt == "--float32") // no value: step back so that a += 2 moves by one
         {
             out_opts.encoding = opt == "--int16" ? DMX_PCM_S16 : opt == "--int24" ? DMX_PCM_S24 : DMX_PCM_F32;
@@ -175,6 +188,18 @@ int main(int argc, const char **argv)
         if (a + 1 >= argc)
             usage(argv[0]);
         const std::string val = argv[a + 1];
+        if (opt == "--wiener")
+        {
+            char *end = nullptr;
+            const long v = std::strtol(val.c_str(), &end, 10);
+            if (end == val.c_str() || *end || v < 1 || v > 8)
+            {
+                std::cerr << "--wiener " << val << ": expected the EM iterations, 1 .. 8" << std::endl;
+                usage(argv[0]);
+            }
+            wiener.iterations = (int)v, with_wiener = true;
+            continue;
+        }
         if (opt == "--loudnorm" || opt == "--loudnorm-each" || opt == "--max-peak")
         {
             char *end = nullptr;
@@ -311,6 +336,17 @@ int main(int argc, const char **argv)
     if (!remix_text.empty() && !two_stems.empty())
     {
         std::cerr << "--remix and --two-stems exclude each other" << std::endl;
+        usage(argv[0]);
+    }
+    if (wiener_residual && !with_wiener)
+    {
+        std::cerr << "--wiener-residual needs --wiener" << std::endl;
+        usage(argv[0]);
+    }
+    wiener.residual = wiener_residual;
+    if (with_wiener && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
+    {
+        std::cerr << "--wiener refines the float32 stems: not together with PCM, FLAC, remix or loudness options for now" << std::endl;
         usage(argv[0]);
     }
     if (limit_times && !limit)
@@ -508,8 +544,13 @@ int main(int argc, const char **argv)
             exit(1);
         any_rate = any_rate || native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE;
     }
+    if (with_wiener && (flac_in || any_rate))
+    {
+        std::cerr << "--wiener: not on a FLAC-fed or resampled track for now" << std::endl;
+        usage(argv[0]);
+    }
     std::cout << std::fixed << std::setprecision(3);
-    ProgressCallback cb = [](float progress, const std::string &msg) {
+    ProgressCallback cb =[](float progress, const std::string &msg) {
         std::cout << "(" << std::setw(3) << std::setfill(' ') << progress * 100.0f << "%) " << msg << std::endl;
     };
     std::vector<StemTensor> outs;
@@ -607,6 +648,8 @@ int main(int argc, const char **argv)
         else
             outs = with_opts ? demucs_inference_batch(model, tracks, cb, opts) : demucs_inference_batch(model, tracks, cb);
     }
+    if (with_wiener) // the stems against their track's mixture (dmx_wiener; the tracks are at 44.1 kHz here)
+        demucs_wiener(tracks, outs, wiener);
     static const char *names[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
     for (int f = 0; f < n_files; ++f)
     {

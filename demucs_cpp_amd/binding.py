@@ -52,6 +52,7 @@ EXPORTS = [
     "dmx_limiter_tables", "dmx_limiter_slopes", "dmx_limiter_workspace_bytes", "dmx_limit_device", "dmx_limit_device_timed", "dmx_limit",
     "dmx_limiter_check", "dmx_loud_encode_limit_device", "dmx_loud_encode_limit", "dmx_tracks_infer_limit", "dmx_tracks_infer_from_flac_limit",
     "dmx_bss_check", "dmx_bss_windows", "dmx_bss_eval_workspace_bytes", "dmx_bss_eval_device", "dmx_bss_eval_device_timed", "dmx_bss_eval",
+    "dmx_wiener_check", "dmx_wiener_workspace_bytes", "dmx_wiener_device", "dmx_wiener_device_timed", "dmx_wiener",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -225,6 +226,12 @@ def lib():
         L.dmx_bss_eval_device.argtypes = [ci, vp, vp, ci, ci, i64, i64, vp, vp, vp, vp, vp, vp]
         L.dmx_bss_eval_device_timed.argtypes = L.dmx_bss_eval_device.argtypes + [vp]
         L.dmx_bss_eval.argtypes = [ci, vp, vp, ci, ci, i64, vp, vp, vp, vp]
+        L.dmx_wiener_check.argtypes = [vp, ci, ci, i64]
+        L.dmx_wiener_workspace_bytes.argtypes = [vp, ci, ci, i64]
+        L.dmx_wiener_workspace_bytes.restype = i64
+        L.dmx_wiener_device.argtypes = [ci, vp, vp, ci, ci, i64, i64, vp, vp, vp, i64, vp]
+        L.dmx_wiener_device_timed.argtypes = L.dmx_wiener_device.argtypes + [vp]
+        L.dmx_wiener.argtypes = [ci, vp, vp, ci, ci, i64, vp, vp]
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -1195,6 +1202,35 @@ def bss_eval(refs: np.ndarray, ests: np.ndarray, window: int = 44100, hop: int =
     out = {"sdr": m[0], "isr": m[1], "sir": m[2], "sar": m[3], "status": status.value}
     if filters:
         out["X"] = X
+    return out
+
+
+class WienerSpec(ctypes.Structure):
+    """dmx_wiener_spec: EM iterations (1 .. 8), the residual source (0 | 1), the frames of a block"""
+    _fields_ = [("iterations", ctypes.c_int), ("residual", ctypes.c_int), ("win_len", ctypes.c_int)]
+
+    def __init__(self, iterations=1, residual=False, win_len=300):
+        super().__init__(int(iterations), int(residual), int(win_len))
+
+
+def wiener_check(spec: Optional[WienerSpec], n_sources: int, channels: int, n: int):
+    """validates a WienerSpec and a shape (dmx_wiener_check; no GPU); raises DmxError naming the field"""
+    _chk(lib().dmx_wiener_check(None if spec is None else ctypes.byref(spec), int(n_sources), int(channels), int(n)))
+
+
+def wiener_workspace_bytes(spec: WienerSpec, n_sources: int, channels: int, n: int) -> int:
+    return lib().dmx_wiener_workspace_bytes(ctypes.byref(spec), int(n_sources), int(channels), int(n))
+
+
+def wiener(mix: np.ndarray, ests: np.ndarray, iterations: int = 1, residual: bool = False, win_len: int = 300, device: int = 0) -> np.ndarray:
+    """the multichannel Wiener post-filter (dmx_wiener): mix (C, n) and ests (J, C, n) float32 -> the refined stems (J, C, n) float32"""
+    mix, ests = np.ascontiguousarray(mix, np.float32), np.ascontiguousarray(ests, np.float32)
+    assert mix.ndim == 2 and ests.ndim == 3 and ests.shape[1:] == mix.shape, "expected mix (C, n) and ests (J, C, n)"
+    J, C, n = ests.shape
+    spec = WienerSpec(iterations, residual, win_len)
+    wiener_check(spec, J, C, n)
+    out = np.empty_like(ests)
+    _chk(lib().dmx_wiener(device, mix.ctypes.data, ests.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
     return out
 
 

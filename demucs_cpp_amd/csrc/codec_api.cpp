@@ -1136,3 +1136,108 @@ extern "C" int dmx_bss_eval(int device, const float *refs, const float *ests, in
         return fail(DMX_ERR_HIP, "%s: download failed", fn);
     return DMX_OK;
 }
+
+// --------------------------------------------------------------------------- Wiener post-filter (wiener.hip)
+static int wiener_check(const char *fn, const dmx_wiener_spec *spec, int J, int C, int64_t n)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: null spec pointer", fn);
+    if (spec->iterations < 1 || spec->iterations > kWienerMaxIter)
+        return fail(DMX_ERR_ARG, "%s: wiener spec: iterations %d is not in [1, %d]", fn, spec->iterations, kWienerMaxIter);
+    if (spec->residual != 0 && spec->residual != 1)
+        return fail(DMX_ERR_ARG, "%s: wiener spec: residual %d is not 0 or 1", fn, spec->residual);
+    if (spec->win_len < 1)
+        return fail(DMX_ERR_ARG, "%s: wiener spec: win_len %d is below 1", fn, spec->win_len);
+    if (J < 1 || J > kWienerMaxSources)
+        return fail(DMX_ERR_ARG, "%s: n_sources %d is not in [1, %d]", fn, J, kWienerMaxSources);
+    if (C != 1 && C != 2)
+        return fail(DMX_ERR_ARG, "%s: channels %d is not 1 or 2", fn, C);
+    if (!wiener_shape_ok(J, C, n))
+        return fail(DMX_ERR_ARG, "%s: n %lld is not in (%d, 2^31)", fn, (long long)n, kWienerPad);
+    return DMX_OK;
+}
+extern "C" int dmx_wiener_check(const dmx_wiener_spec *spec, int n_sources, int channels, int64_t n)
+{
+    return wiener_check("dmx_wiener_check", spec, n_sources, channels, n);
+}
+extern "C" int64_t dmx_wiener_workspace_bytes(const dmx_wiener_spec *spec, int n_sources, int channels, int64_t n)
+{
+    if (wiener_check("dmx_wiener_workspace_bytes", spec, n_sources, channels, n) != DMX_OK)
+        return -1;
+    return wiener_workspace_bytes(n_sources, channels, n, spec->residual);
+}
+
+// marks: null, or iterations + 3 events around the stages
+static int wiener_device(const char *fn, int device, const float *d_mix, const float *d_ests, int J, int C, int64_t n, int64_t plane_stride,
+                         const dmx_wiener_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream, hipEvent_t *marks)
+{
+    DMXCHK(wiener_check(fn, spec, J, C, n));
+    if (plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (n <= plane_stride)", fn, (long long)n, (long long)plane_stride);
+    if (!d_mix || !d_ests || !d_out || !d_work)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !d_mix ? "d_mix" : !d_ests ? "d_ests" : !d_out ? "d_out" : "d_work");
+    if ((((uintptr_t)d_mix | (uintptr_t)d_ests | (uintptr_t)d_out) & 3) != 0 || ((uintptr_t)d_work & 255) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_mix, d_ests and d_out must be 4-byte aligned, d_work 256-byte", fn);
+    const int64_t need = wiener_workspace_bytes(J, C, n, spec->residual);
+    if (work_bytes < need)
+        return fail(DMX_ERR_ARG, "%s: work_bytes %lld is below dmx_wiener_workspace_bytes = %lld", fn, (long long)work_bytes, (long long)need);
+    HIPCHK(hipSetDevice(device));
+    const WienerJob job{d_mix, d_ests, d_out, J, C, spec->iterations, spec->residual, spec->win_len, n, plane_stride, (unsigned char *)d_work};
+    launch_wiener(job, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_wiener_device(int device, const float *d_mix, const float *d_ests, int n_sources, int channels, int64_t n,
+                                 int64_t plane_stride, const dmx_wiener_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream)
+{
+    return wiener_device("dmx_wiener_device", device, d_mix, d_ests, n_sources, channels, n, plane_stride, spec, d_out, d_work, work_bytes,
+                         stream, nullptr);
+}
+
+extern "C" int dmx_wiener_device_timed(int device, const float *d_mix, const float *d_ests, int n_sources, int channels, int64_t n,
+                                       int64_t plane_stride, const dmx_wiener_spec *spec, float *d_out, void *d_work, int64_t work_bytes,
+                                       void *stream, float *ms)
+{
+    const char *fn = "dmx_wiener_device_timed";
+    if (!ms)
+        return fail(DMX_ERR_ARG, "%s: null ms pointer", fn);
+    DMXCHK(wiener_check(fn, spec, n_sources, channels, n));
+    HIPCHK(hipSetDevice(device));
+    Events<kWienerMaxIter + 3> ev(fn);
+    DMXCHK(ev.create());
+    DMXCHK(wiener_device(fn, device, d_mix, d_ests, n_sources, channels, n, plane_stride, spec, d_out, d_work, work_bytes, stream, ev.ev));
+    const int stages = spec->iterations + 2;
+    DMXCHK(ev.wait(stages));
+    for (int k = 0; k < stages; ++k)
+        DMXCHK(ev.elapsed(k, k + 1, &ms[k]));
+    return DMX_OK;
+}
+
+extern "C" int dmx_wiener(int device, const float *mix, const float *ests, int n_sources, int channels, int64_t n, const dmx_wiener_spec *spec,
+                          float *out)
+{
+    const char *fn = "dmx_wiener";
+    DMXCHK(wiener_check(fn, spec, n_sources, channels, n));
+    if (!mix || !ests || !out)
+        return fail(DMX_ERR_ARG, "%s: null %s pointer", fn, !mix ? "mix" : !ests ? "ests" : "out");
+    HIPCHK(hipSetDevice(device));
+    const size_t plane = sizeof(float) * (size_t)n, M = (size_t)n_sources * (size_t)channels;
+    const int64_t workBytes = wiener_workspace_bytes(n_sources, channels, n, spec->residual);
+    DevScratch d;
+    float *dIn = (float *)d.get(((size_t)channels + M) * plane);
+    float *dOut = (float *)d.get(M * plane);
+    void *dWork = d.get((size_t)workBytes);
+    if (!d.ok)
+        return fail(DMX_ERR_HIP, "%s: hipMalloc failed", fn);
+    float *dEsts = dIn + (size_t)channels * (size_t)n;
+    if (hipMemcpy(dIn, mix, (size_t)channels * plane, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dEsts, ests, M * plane, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: upload failed", fn);
+    DMXCHK(wiener_device(fn, device, dIn, dEsts, n_sources, channels, n, n, spec, dOut, dWork, workBytes, nullptr, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: the kernels failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (hipMemcpy(out, dOut, M * plane, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(DMX_ERR_HIP, "%s: download failed", fn);
+    return DMX_OK;
+}

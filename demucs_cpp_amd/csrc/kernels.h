@@ -6,6 +6,7 @@
 #include "meters_plan.h"
 #include "limiter_plan.h"
 #include "bss_plan.h"
+#include "wiener_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -495,6 +496,19 @@ struct BssJob
     unsigned char *work;
 };
 void launch_bss(const BssJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
+// ---- the multichannel Wiener post-filter (wiener.hip; specification: DESIGN.md section 2.19, restated in tests/wiener_spec.py) ----
+// (the frames, the limits and the workspace: wiener_plan.h)
+// mix: C planar fp32 planes of n samples, plane c at c * stride; ests and out: J C planes, plane j * C + c at (j * C + c) * stride,
+// all on the device. marks: NULL, or iterations + 3 events around the stages (forward STFT, each EM launch, inverse)
+struct WienerJob
+{
+    const float *mix, *ests;
+    float *out;
+    int J, C, iterations, residual, win_len;
+    i64 n, stride;
+    unsigned char *work;
+};
+void launch_wiener(const WienerJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
 // ---- the track path's converter (resample.hip) ----
 // outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
 // output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the

@@ -334,6 +334,46 @@ inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model,
     return detail::batch_call("demucs_inference_batch", model, model.is_4sources ? 4 : 6, tracks, cb, &opts);
 }
 
+// The multichannel Wiener post-filter (dmx_wiener; demucs's wiener_iters / wiener_residual) on the
+// stems a batch call returned: every track's stems are refined against that track's mixture at 44.1 kHz, in place.
+struct wiener_options
+{
+    int iterations = 1;    // EM iterations, 1 .. 8
+    bool residual = false; // an extra source mixture - sum takes part and is dropped
+    int win_len = 300;     // frames of a block
+    int device = 0;
+};
+inline void demucs_wiener(const std::vector<StereoMatrix> &tracks, std::vector<StemTensor> &stems, const wiener_options &w)
+{
+    const dmx_wiener_spec spec{w.iterations, w.residual ? 1 : 0, w.win_len};
+    for (size_t t = 0; t < tracks.size() && t < stems.size(); ++t)
+    {
+        StemTensor &st = stems[t];
+        const int64_t n = st.n;
+        std::vector<float> mix((size_t)(2 * n)), planes((size_t)st.S * (size_t)(2 * n)); // planar, as the library takes them
+        for (int c = 0; c < 2; ++c)
+            for (int64_t i = 0; i < n; ++i)
+            {
+                mix[(size_t)(c * n + i)] = tracks[t](c, i);
+                for (int s = 0; s < st.S; ++s)
+                    planes[(size_t)((s * 2 + c) * n + i)] = st(s, c, i);
+            }
+        if (dmx_wiener(w.device, mix.data(), planes.data(), st.S, 2, n, &spec, planes.data()) != DMX_OK)
+            detail::die("demucs_wiener");
+        for (int s = 0; s < st.S; ++s)
+            for (int c = 0; c < 2; ++c)
+                for (int64_t i = 0; i < n; ++i)
+                    st(s, c, i) = planes[(size_t)((s * 2 + c) * n + i)];
+    }
+}
+inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model, const std::vector<StereoMatrix> &tracks, ProgressCallback cb,
+                                                      const inference_options &opts, const wiener_options &w)
+{
+    std::vector<StemTensor> out = demucs_inference_batch(model, tracks, cb, opts);
+    demucs_wiener(tracks, out, w);
+    return out;
+}
+
 // Stems as WAV-ready PCM, encoded on the GPU (dmx_tracks_infer_pcm): demucs's --two-stems, --clip-mode and --int24 /
 // --float32. The defaults are demucs's: 16 bit, rescale, all stems. two_stems: -1, or the index of the stem to isolate
 // (stem_index("vocals")): output 0 is that stem, output 1 the sum of the others.

@@ -631,6 +631,40 @@ extern "C"
     int dmx_bss_eval(int device, const float *refs, const float *ests, int n_sources, int channels, int64_t n, const dmx_bss_spec *spec,
                      double *metrics, int *status, double *filters);
 
+    /* ---- Multichannel Wiener post-filter with EM re-estimation (csrc/wiener.hip; DESIGN.md section 2.19, restated in
+     * tests/wiener_spec.py; what Open-Unmix calls niter, Spleeter --mwf and demucs wiener_iters). The mixture x[c][n] and the
+     * estimates e[j][c][n], J = 1 .. 8 sources of C = 1 | 2 channels and 2048 < n < 2^31 samples, go through an STFT (nfft 4096,
+     * hop 1024, periodic Hann, centred with reflect padding, fp32, complex64). The initial y_j is |E_j| with the mixture's phase
+     * (phase 1 where X = 0); with `residual` an extra source X - sum_j y_j takes part and is not returned. The frames are cut
+     * into blocks of win_len; per block s = max(1, max |X| / 10), x = X / s, y = y / s rounded to complex64. One iteration, in
+     * binary64: v_j = mean_c |y_j|^2, R_j(f) = sum_t y_j y_j^H / (1e-10 + sum_t v_j), Cxx = sum_j v_j R_j + 1e-5 I,
+     * y_j = v_j R_j Cxx^-1 x, rounded to complex64. After the last, y s goes through the inverse STFT (window, overlap-add in
+     * frame order, division by the window-square sum) to out[j][c][n]. A fixed order everywhere: equal inputs, equal bits.
+     * Out of scope: the ratio-mask initialisation, other STFT sizes, more than 2 channels, the multi-GPU engine. */
+    typedef struct dmx_wiener_spec
+    {
+        int iterations; /* 1 .. 8 */
+        int residual;   /* 0 | 1 */
+        int win_len;    /* frames of a block, >= 1; norbert's default: 300 */
+    } dmx_wiener_spec;
+    /* Pure host function; DMX_ERR_ARG with a message that names the field or argument. */
+    int dmx_wiener_check(const dmx_wiener_spec *spec, int n_sources, int channels, int64_t n);
+    /* the bytes of d_work: (1 + n_sources + residual) channels (1 + n / 1024) rows of 2064 complex64 and three small tables;
+     * -1 (and a message) where dmx_wiener_check fails. Pure host function. */
+    int64_t dmx_wiener_workspace_bytes(const dmx_wiener_spec *spec, int n_sources, int channels, int64_t n);
+    /* d_mix: planes c at c * plane_stride (>= n) floats; d_ests and d_out: planes source * channels + channel at plane_stride;
+     * d_work: work_bytes >= dmx_wiener_workspace_bytes, 256-byte aligned. Asynchronous on `stream`. */
+    int dmx_wiener_device(int device, const float *d_mix, const float *d_ests, int n_sources, int channels, int64_t n,
+                          int64_t plane_stride, const dmx_wiener_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream);
+    /* measurement (tools/wiener_bench.py): the call above, synchronised, with the times of its iterations + 2 stages between
+     * HIP events in ms[0 .. iterations + 2): forward STFT, each EM launch, inverse */
+    int dmx_wiener_device_timed(int device, const float *d_mix, const float *d_ests, int n_sources, int channels, int64_t n,
+                                int64_t plane_stride, const dmx_wiener_spec *spec, float *d_out, void *d_work, int64_t work_bytes,
+                                void *stream, float *ms);
+    /* the same on host buffers: mix [channels][n], ests and out [n_sources][channels][n] */
+    int dmx_wiener(int device, const float *mix, const float *ests, int n_sources, int channels, int64_t n, const dmx_wiener_spec *spec,
+                   float *out);
+
     /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
      * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
      * PCM as the stages above write it (16-bit pairs or packed 24 bit) -> a complete .flac file: "fLaC", one STREAMINFO block

@@ -125,6 +125,17 @@ def load_dirs(ref_dir: str, est_dir: str):
     return refs, ests
 
 
+def wiener_filter(refs, ests, iterations, device=0):
+    """the estimates {name: (n, 2)} after `iterations` of the Wiener post-filter against the mixture = the sum of the references"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from demucs_cpp_amd import binding as dmx
+    names = [k for k in refs if k in ests]
+    n = min(min(refs[k].shape[0], ests[k].shape[0]) for k in names)
+    mix = sum(np.asarray(refs[k][:n], np.float64) for k in names).T.astype(np.float32)
+    out = dmx.wiener(mix, np.stack([np.asarray(ests[k][:n], np.float32).T for k in names]), iterations, device=device)
+    return {k: out[j].T.astype(ests[k].dtype) for j, k in enumerate(names)}
+
+
 REFERENCE_TABLES = {"htdemucs_4s": SDR_SCORES_MD_CPP_4S, "htdemucs_6s": SDR_SCORES_MD_CPP_6S, "htdemucs_ft": SDR_SCORES_MD_CPP_FT,
                     "hdemucs_mmi": SDR_SCORES_MD_CPP_V3}
 
@@ -134,17 +145,26 @@ def main(argv):
     eval_sdr.py --track <reference dir> --estimates <estimate dir> [--reference-table htdemucs_4s|htdemucs_6s|htdemucs_ft|hdemucs_mmi]
                 [--tolerance 0.1]      prints the reference's own C++ score (.github/SDR_scores.md) and the verdict beside each
                                        target; the exit code is the number of targets outside the tolerance
-    --bss [--device N] with either form: SDR, SIR, ISR and SAR per target from the GPU (the verdict stays the SDR's)"""
+    --bss [--device N] with either form: SDR, SIR, ISR and SAR per target from the GPU (the verdict stays the SDR's)
+    --wiener N with either form: the estimates go through N EM iterations of the multichannel Wiener post-filter on the GPU
+                (binding.wiener) against the sum of the references before they are scored"""
     ref_dir = est_dir = table = None
     tol = 0.1
     args = list(argv[1:])
     bss, device = "--bss" in args, 0
     if bss:
         args.remove("--bss")
+    wiener_iters = 0
+    if "--wiener" in args:
+        k = args.index("--wiener")
+        wiener_iters = int(args[k + 1]) if k + 1 < len(args) and args[k + 1].isdigit() else -1
+        del args[k:k + 2]
     if "--device" in args:
         k = args.index("--device")
-        device = int(args[k + 1]) if bss and k + 1 < len(args) and args[k + 1].isdigit() else -1
+        device = int(args[k + 1]) if (bss or wiener_iters) and k + 1 < len(args) and args[k + 1].isdigit() else -1
         del args[k:k + 2]
+    if wiener_iters < 0:
+        device = -1
     if device < 0:
         print(main.__doc__)
         return 2
@@ -172,6 +192,8 @@ def main(argv):
     if not refs:
         print("no matching stems found", file=sys.stderr)
         return 1
+    if wiener_iters:
+        ests = wiener_filter(refs, ests, wiener_iters, device)
     want = REFERENCE_TABLES.get(table, {})
     bad = 0
     full = track_bss(refs, ests, device) if bss else {}
