@@ -3,7 +3,7 @@
 //                         [--other-method add|minus|none] [--remix NAME=TERMS,...]
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
 //                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]
-//                         [--wiener N [--wiener-residual]]
+//                         [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]
 //                         [--limit] [--limit-attack MS] [--limit-release MS]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
@@ -60,6 +60,9 @@
 //   --wiener N               refine the float32 stems with N (1 .. 8) EM iterations of the multichannel Wiener filter against the
 //                            track's mixture (dmx_wiener; demucs's wiener_iters); --wiener-residual adds the residual source.
 //                            Not together with PCM / FLAC / remix / loudness options or a resampled or FLAC-fed track for now.
+//   --mel NAME               beside each float32 stem, its log-mel features as target_{i}_{name}.mel.npy: float32
+//                            [chunks][n_mels][frames] of the stem's mono fold at the preset's rate (dmx_logmel_from_stems; NAME:
+//                            whisper, whisper128 or librosa). Not together with PCM / FLAC / remix / loudness options for now.
 // A track at another rate (DMX_RESAMPLE=1) takes them at its own rate: the library converts inside the track path
 // (dmx_tracks_infer_rates, dmx_tracks_infer_from_flac_rates) and the outputs are the stems at the file's rate.
 // <model> may also be a bag of models (dmx_tracks_infer_bag through the demucscpp::demucs_bag overloads; every option
@@ -88,7 +91,7 @@ using namespace demucscpp;
               << " [--other-method add|minus|none] [--remix NAME=[+|-][GAIN*]SOURCE...,...]"
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
               << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]"
-              << " [--wiener N [--wiener-residual]]"
+              << " [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]"
               << " [--limit] [--limit-attack MS] [--limit-release MS] (--clip-mode limit: --limit without loudnorm)"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
@@ -143,6 +146,8 @@ int main(int argc, const char **argv)
     LimitReport limit_report; // filled as well with --limit
     wiener_options wiener; // --wiener N [--wiener-residual]
     bool with_wiener = false, wiener_residual = false;
+    dmx_logmel_spec mel{}; // --mel NAME
+    bool with_mel = false;
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -188,6 +193,16 @@ int main(int argc, const char **argv)
         if (a + 1 >= argc)
             usage(argv[0]);
         const std::string val = argv[a + 1];
+        if (opt == "--mel")
+        {
+            if (dmx_logmel_preset(val.c_str(), &mel) != DMX_OK)
+            {
+                std::cerr << "--mel " << val << ": expected whisper, whisper128 or librosa" << std::endl;
+                usage(argv[0]);
+            }
+            with_mel = true;
+            continue;
+        }
         if (opt == "--wiener")
         {
             char *end = nullptr;
@@ -347,6 +362,11 @@ int main(int argc, const char **argv)
     if (with_wiener && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
     {
         std::cerr << "--wiener refines the float32 stems: not together with PCM, FLAC, remix or loudness options for now" << std::endl;
+        usage(argv[0]);
+    }
+    if (with_mel && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
+    {
+        std::cerr << "--mel goes with the float32 stems: not together with PCM, FLAC, remix or loudness options for now" << std::endl;
         usage(argv[0]);
     }
     if (limit_times && !limit)
@@ -544,6 +564,11 @@ int main(int argc, const char **argv)
             exit(1);
         any_rate = any_rate || native_rate[(size_t)i] != SUPPORTED_SAMPLE_RATE;
     }
+    if (with_mel && (flac_in || any_rate))
+    {
+        std::cerr << "--mel: not on a FLAC-fed or resampled track for now" << std::endl;
+        usage(argv[0]);
+    }
     if (with_wiener && (flac_in || any_rate))
     {
         std::cerr << "--wiener: not on a FLAC-fed or resampled track for now" << std::endl;
@@ -736,8 +761,22 @@ int main(int argc, const char **argv)
         }
         const StemTensor &out = outs[(size_t)f];
         std::vector<float> wave((size_t)(2 * audio.cols()));
+        MelTensor feat;
+        if (with_mel) // every stem of the track in one call (dmx_logmel_from_stems; the stems are at 44.1 kHz here)
+            feat = demucs_logmel(out, mel, SUPPORTED_SAMPLE_RATE);
         for (int target = 0; target < nb_sources; ++target)
         {
+            if (with_mel)
+            {
+                auto p_mel = p / ("target_" + std::to_string(target) + "_" + names[target] + ".mel.npy");
+                std::cout << "Writing mel file " << p_mel << std::endl;
+                const int64_t shape[3] = {feat.chunks, feat.n_mels, feat.frames};
+                if (dmx_npy_write_f32(p_mel.string().c_str(), feat.data.data() + (size_t)target * (size_t)(shape[0] * shape[1] * shape[2]), 3, shape) != DMX_OK)
+                {
+                    std::cerr << "Error writing " << p_mel << std::endl;
+                    exit(1);
+                }
+            }
             auto p_target = p / ("target_" + std::to_string(target) + "_" + names[target] + ".wav");
             std::cout << "Writing wav file " << p_target << std::endl;
             for (int64_t i = 0; i < audio.cols(); ++i)

@@ -53,6 +53,8 @@ EXPORTS = [
     "dmx_limiter_check", "dmx_loud_encode_limit_device", "dmx_loud_encode_limit", "dmx_tracks_infer_limit", "dmx_tracks_infer_from_flac_limit",
     "dmx_bss_check", "dmx_bss_windows", "dmx_bss_eval_workspace_bytes", "dmx_bss_eval_device", "dmx_bss_eval_device_timed", "dmx_bss_eval",
     "dmx_wiener_check", "dmx_wiener_workspace_bytes", "dmx_wiener_device", "dmx_wiener_device_timed", "dmx_wiener",
+    "dmx_logmel_check", "dmx_logmel_preset", "dmx_logmel_frames", "dmx_logmel_filters", "dmx_logmel_geometry", "dmx_logmel_workspace_bytes",
+    "dmx_logmel_device", "dmx_logmel_device_timed", "dmx_logmel", "dmx_logmel_from_stems", "dmx_npy_write_f32",
 ]
 
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_P2P = 0, 1, 2
@@ -232,6 +234,18 @@ def lib():
         L.dmx_wiener_device.argtypes = [ci, vp, vp, ci, ci, i64, i64, vp, vp, vp, i64, vp]
         L.dmx_wiener_device_timed.argtypes = L.dmx_wiener_device.argtypes + [vp]
         L.dmx_wiener.argtypes = [ci, vp, vp, ci, ci, i64, vp, vp]
+        L.dmx_logmel_check.argtypes = [vp, i64]
+        L.dmx_logmel_preset.argtypes = [ctypes.c_char_p, vp]
+        L.dmx_logmel_frames.argtypes = [vp, i64, vp, vp]
+        L.dmx_logmel_filters.argtypes = [vp, vp]
+        L.dmx_logmel_geometry.argtypes = [vp, vp, vp, vp]
+        L.dmx_logmel_workspace_bytes.argtypes = [vp, ci, i64]
+        L.dmx_logmel_workspace_bytes.restype = i64
+        L.dmx_logmel_device.argtypes = [ci, vp, ci, i64, i64, vp, vp, vp, i64, vp]
+        L.dmx_logmel_device_timed.argtypes = L.dmx_logmel_device.argtypes + [vp]
+        L.dmx_logmel.argtypes = [ci, vp, ci, i64, vp, vp]
+        L.dmx_logmel_from_stems.argtypes = [ci, vp, ci, ci, i64, ci, vp, vp]
+        L.dmx_npy_write_f32.argtypes = [ctypes.c_char_p, vp, ci, vp]
         L.dmx_tracks_infer_flac.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, ci, vp, vp, vp, ci, vp, vp]
         L.dmx_track_geometry.argtypes = [vp, i64, ci, ctypes.POINTER(i64), ctypes.POINTER(ci), ctypes.POINTER(i64)]
         L.dmx_track_stats_device.argtypes = [vp, fp, i64, fp]
@@ -1232,6 +1246,91 @@ def wiener(mix: np.ndarray, ests: np.ndarray, iterations: int = 1, residual: boo
     out = np.empty_like(ests)
     _chk(lib().dmx_wiener(device, mix.ctypes.data, ests.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
     return out
+
+
+MEL_SLANEY, MEL_HTK = 0, 1
+MEL_NORM_SLANEY, MEL_NORM_NONE = 0, 1
+LOG_NONE, LOG_DB, LOG_WHISPER = 0, 1, 2
+
+
+class LogmelSpec(ctypes.Structure):
+    """dmx_logmel_spec: the log-mel front end; logmel_preset fills Whisper's and librosa's defaults"""
+    _fields_ = [("sr", ctypes.c_int), ("n_fft", ctypes.c_int), ("hop", ctypes.c_int), ("n_mels", ctypes.c_int),
+                ("fmin", ctypes.c_double), ("fmax", ctypes.c_double), ("mel_scale", ctypes.c_int), ("mel_norm", ctypes.c_int),
+                ("log_mode", ctypes.c_int), ("chunk_frames", ctypes.c_int), ("amin", ctypes.c_double), ("top_db", ctypes.c_double)]
+
+    def __init__(self, sr=16000, n_fft=400, hop=160, n_mels=80, fmin=0.0, fmax=None, mel_scale=MEL_SLANEY, mel_norm=MEL_NORM_SLANEY,
+                 log_mode=LOG_WHISPER, chunk_frames=0, amin=1e-10, top_db=0.0):
+        super().__init__(int(sr), int(n_fft), int(hop), int(n_mels), float(fmin), float(sr / 2 if fmax is None else fmax), int(mel_scale),
+                         int(mel_norm), int(log_mode), int(chunk_frames), float(amin), float(top_db))
+
+
+def logmel_preset(name: str) -> LogmelSpec:
+    """"whisper" | "whisper128" | "librosa" (dmx_logmel_preset; no GPU)"""
+    spec = LogmelSpec()
+    _chk(lib().dmx_logmel_preset(name.encode(), ctypes.byref(spec)))
+    return spec
+
+
+def logmel_check(spec: LogmelSpec, n: int = -1):
+    """validates a LogmelSpec and, with n >= 0, a plane length (dmx_logmel_check; no GPU); raises DmxError naming the field"""
+    _chk(lib().dmx_logmel_check(ctypes.byref(spec), int(n)))
+
+
+def logmel_frames(spec: LogmelSpec, n: int):
+    """(chunks, frames of one chunk) of a plane of n samples (dmx_logmel_frames; no GPU)"""
+    chunks, frames = ctypes.c_int64(), ctypes.c_int64()
+    _chk(lib().dmx_logmel_frames(ctypes.byref(spec), int(n), ctypes.byref(chunks), ctypes.byref(frames)))
+    return chunks.value, frames.value
+
+
+def logmel_filters(spec: LogmelSpec) -> np.ndarray:
+    """the mel filterbank W (n_mels, n_fft / 2 + 1) float64 (dmx_logmel_filters; no GPU)"""
+    logmel_check(spec)
+    W = np.empty((spec.n_mels, spec.n_fft // 2 + 1), np.float64)
+    _chk(lib().dmx_logmel_filters(ctypes.byref(spec), W.ctypes.data))
+    return W
+
+
+def logmel_geometry(spec: LogmelSpec):
+    """(frames of a workgroup's tile, rows of a table slab, bytes of LDS) the kernel uses (dmx_logmel_geometry; no GPU)"""
+    ft, k, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _chk(lib().dmx_logmel_geometry(ctypes.byref(spec), ctypes.byref(ft), ctypes.byref(k), ctypes.byref(lds)))
+    return ft.value, k.value, lds.value
+
+
+def logmel_workspace_bytes(spec: LogmelSpec, planes: int, n: int) -> int:
+    return lib().dmx_logmel_workspace_bytes(ctypes.byref(spec), int(planes), int(n))
+
+
+def logmel(planes: np.ndarray, spec: LogmelSpec, device: int = 0) -> np.ndarray:
+    """log-mel features (dmx_logmel): planes (P, n) float32 at spec.sr -> (P, chunks, n_mels, frames) float32"""
+    planes = np.ascontiguousarray(planes, np.float32)
+    assert planes.ndim == 2, "expected planes (P, n)"
+    P, n = planes.shape
+    chunks, frames = logmel_frames(spec, n)
+    out = np.empty((P, chunks, spec.n_mels, frames), np.float32)
+    _chk(lib().dmx_logmel(device, planes.ctypes.data, P, n, ctypes.byref(spec), out.ctypes.data))
+    return out
+
+
+def logmel_from_stems(stems: np.ndarray, rate_in: int, spec: LogmelSpec, device: int = 0) -> np.ndarray:
+    """stems (S, C, n) float32 at rate_in -> the features of their mono folds at spec.sr, (S, chunks, n_mels, frames) float32
+    (dmx_logmel_from_stems: fold, dmx_resample_device and the stage on the device)"""
+    stems = np.ascontiguousarray(stems, np.float32)
+    assert stems.ndim == 3, "expected stems (S, C, n)"
+    S, C, n = stems.shape
+    chunks, frames = logmel_frames(spec, resample_length(n, rate_in, spec.sr))
+    out = np.empty((S, chunks, spec.n_mels, frames), np.float32)
+    _chk(lib().dmx_logmel_from_stems(device, stems.ctypes.data, S, C, n, int(rate_in), ctypes.byref(spec), out.ctypes.data))
+    return out
+
+
+def npy_write(path: str, data: np.ndarray):
+    """float32 `data` as a .npy file by the writer the CLI's --mel uses (dmx_npy_write_f32; no GPU)"""
+    data = np.ascontiguousarray(data, np.float32)
+    shape = (ctypes.c_int64 * data.ndim)(*data.shape)
+    _chk(lib().dmx_npy_write_f32(os.fsencode(path), data.ctypes.data, data.ndim, shape))
 
 
 def flac_bound(bits: int, n: int) -> int:

@@ -7,6 +7,7 @@
 #include "limiter_plan.h"
 #include "bss_plan.h"
 #include "wiener_plan.h"
+#include "logmel_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -509,6 +510,24 @@ struct WienerJob
     unsigned char *work;
 };
 void launch_wiener(const WienerJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
+// ---- log-mel features (logmel.hip; specification: DESIGN.md section 2.20, restated in tests/logmel_spec.py) ----
+// (chunks, frames, the tile and the workspace: logmel_plan.h)
+// x: `planes` fp32 planes of n samples, plane p at p * stride; out: [planes][chunks][n_mels][frames] floats; work: the
+// workspace, whose first hostBytes the launch copies from hostTables (logmel_host_tables; it must outlive the copy).
+// marks: NULL, or 4 events around the stages (tables, power-mel, finish)
+struct LogmelJob
+{
+    const float *x;
+    float *out;
+    int planes;
+    i64 n, stride;
+    LogmelSpec spec;
+    unsigned char *work;
+    const unsigned char *hostTables;
+};
+void launch_logmel(const LogmelJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
+// stems [sources][C][n] -> mono planes [sources][n]: 0.5 (L + R) in fp32 (C == 2), a copy (C == 1)
+void launch_logmel_fold(const float *in, float *out, int sources, int C, i64 n, hipStream_t s);
 // ---- the track path's converter (resample.hip) ----
 // outputs [k0, k1) of the conversion of `planes` planar planes (plane p = stem*2 + channel at src + p*n, n samples each):
 // output k of plane p goes to dst + stem*dstStem + channel*dstChan + k*dstStep (planar [S][2][n_out]: 2 n_out, n_out, 1; the

@@ -374,6 +374,31 @@ inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model,
     return out;
 }
 
+// Log-mel features of the stems a batch call returned (dmx_logmel_from_stems): each stem is folded to
+// mono, converted rate -> spec.sr and sent through Whisper's / librosa's front end on the device. spec: from dmx_logmel_preset.
+struct MelTensor
+{
+    std::vector<float> data; // [sources][chunks][n_mels][frames]
+    int64_t sources = 0, chunks = 0, n_mels = 0, frames = 0;
+};
+inline MelTensor demucs_logmel(const StemTensor &st, const dmx_logmel_spec &spec, int rate = 44100, int device = 0)
+{
+    const int64_t n = st.n;
+    std::vector<float> planes((size_t)st.S * (size_t)(2 * n)); // planar, as the library takes them
+    for (int s = 0; s < st.S; ++s)
+        for (int c = 0; c < 2; ++c)
+            for (int64_t i = 0; i < n; ++i)
+                planes[(size_t)((s * 2 + c) * n + i)] = st(s, c, i);
+    MelTensor m;
+    m.sources = st.S, m.n_mels = spec.n_mels;
+    if (dmx_logmel_frames(&spec, dmx_resample_length(n, rate, spec.sr), &m.chunks, &m.frames) != DMX_OK)
+        detail::die("demucs_logmel");
+    m.data.resize((size_t)(m.sources * m.chunks * m.n_mels * m.frames));
+    if (dmx_logmel_from_stems(device, planes.data(), st.S, 2, n, rate, &spec, m.data.data()) != DMX_OK)
+        detail::die("demucs_logmel");
+    return m;
+}
+
 // Stems as WAV-ready PCM, encoded on the GPU (dmx_tracks_infer_pcm): demucs's --two-stems, --clip-mode and --int24 /
 // --float32. The defaults are demucs's: 16 bit, rescale, all stems. two_stems: -1, or the index of the stem to isolate
 // (stem_index("vocals")): output 0 is that stem, output 1 the sum of the others.

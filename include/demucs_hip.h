@@ -665,6 +665,79 @@ extern "C"
     int dmx_wiener(int device, const float *mix, const float *ests, int n_sources, int channels, int64_t n, const dmx_wiener_spec *spec,
                    float *out);
 
+    /* ---- Log-mel features of the stems (csrc/logmel.hip; DESIGN.md section 2.20, restated in tests/logmel_spec.py; the front
+     * end of Whisper / WhisperX and of librosa.feature.melspectrogram + power_to_db). P planes of N fp32 samples at `sr`:
+     * centred frames (reflect padding of n_fft / 2, periodic Hann window), S[f] = |sum_n w[n] x[n] e^{-2 pi i f n / n_fft}|^2 for
+     * f = 0 .. n_fft / 2 in binary64, M[m] = sum_f W[m][f] S[f] with the triangular filterbank of librosa.filters.mel, then
+     *   DMX_LOG_NONE     M
+     *   DMX_LOG_DB       10 log10(max(amin, M)), raised to at least max - top_db when top_db > 0
+     *   DMX_LOG_WHISPER  L = log10(max(1e-10, M)), (max(L, max L - 8) + 4) / 4
+     * with `max` over one (plane, chunk), rounded once to fp32: out [P][chunks][n_mels][frames].
+     * chunk_frames = 0: one chunk, the whole plane, 1 + N / hop frames (N > n_fft / 2). chunk_frames = F > 0 (Whisper's
+     * 30-second windows): ceil(N / (F hop)) chunks of F hop samples, the last extended with zeros, each framed by itself with
+     * the last of its F + 1 frames dropped (F hop > n_fft / 2). A fixed order everywhere: equal inputs, equal bits.
+     * Out of scope: MFCC, Kaldi fbank, n_fft above 2048, the multi-GPU engine, fusion into the track slot's output chain. */
+    enum
+    {
+        DMX_MEL_SLANEY = 0,
+        DMX_MEL_HTK = 1,
+        DMX_MEL_NORM_SLANEY = 0,
+        DMX_MEL_NORM_NONE = 1,
+        DMX_LOG_NONE = 0,
+        DMX_LOG_DB = 1,
+        DMX_LOG_WHISPER = 2
+    };
+    typedef struct dmx_logmel_spec
+    {
+        int sr;           /* the rate of the planes, Hz */
+        int n_fft;        /* a multiple of 16 in [64, 2048] */
+        int hop;          /* 1 .. n_fft */
+        int n_mels;       /* 1 .. 128 */
+        double fmin, fmax; /* 0 <= fmin < fmax <= sr / 2 */
+        int mel_scale;    /* DMX_MEL_SLANEY | DMX_MEL_HTK */
+        int mel_norm;     /* DMX_MEL_NORM_SLANEY | DMX_MEL_NORM_NONE */
+        int log_mode;     /* DMX_LOG_NONE | DMX_LOG_DB | DMX_LOG_WHISPER */
+        int chunk_frames; /* 0: the whole plane; F > 0: chunks of F frames */
+        double amin;      /* DMX_LOG_DB: > 0 */
+        double top_db;    /* DMX_LOG_DB: <= 0 switches the clamp off */
+    } dmx_logmel_spec;
+    /* Pure host function (replaces nothing: it names a bad field or length before any GPU work). n < 0: the spec alone. */
+    int dmx_logmel_check(const dmx_logmel_spec *spec, int64_t n);
+    /* "whisper" (16000 / 400 / 160 / 80 mels, Slaney scale and norm, 0 .. 8000 Hz, chunks of 3000 frames: whisper.audio's
+     * log_mel_spectrogram behind pad_or_trim), "whisper128" (large-v3), "librosa" (22050 / 2048 / 512 / 128, DMX_LOG_DB, amin
+     * 1e-10, top_db 80: melspectrogram + power_to_db(ref=1)). Pure host function. */
+    int dmx_logmel_preset(const char *name, dmx_logmel_spec *spec);
+    /* the chunks and the frames of one chunk of n samples (replaces the shape arithmetic of librosa.stft) */
+    int dmx_logmel_frames(const dmx_logmel_spec *spec, int64_t n, int64_t *chunks, int64_t *frames);
+    /* W [n_mels][n_fft / 2 + 1] in binary64 (replaces librosa.filters.mel). Pure host function. */
+    int dmx_logmel_filters(const dmx_logmel_spec *spec, double *W);
+    /* the kernel's tile: frames of a workgroup, rows of a table slab, bytes of LDS (csrc/logmel_plan.h). Pure host function. */
+    int dmx_logmel_geometry(const dmx_logmel_spec *spec, int *tile_frames, int *slab_depth, int64_t *lds_bytes);
+    /* the bytes of d_work for `planes` planes of n samples (the binary64 tables and the tile maxima); -1 and a message where
+     * dmx_logmel_check fails. Pure host function. */
+    int64_t dmx_logmel_workspace_bytes(const dmx_logmel_spec *spec, int planes, int64_t n);
+    /* replaces an STFT + the mel matmul + the log on fp32 planes that had to leave the device. d_planes: plane p at
+     * p * plane_stride (>= n) floats; d_out: [planes][chunks][n_mels][frames] floats; d_work: work_bytes >=
+     * dmx_logmel_workspace_bytes, 256-byte aligned. Asynchronous on `stream`. */
+    int dmx_logmel_device(int device, const float *d_planes, int planes, int64_t n, int64_t plane_stride, const dmx_logmel_spec *spec,
+                          float *d_out, void *d_work, int64_t work_bytes, void *stream);
+    /* measurement (tools/logmel_bench.py): the call above, synchronised, with the times of its three stages between HIP events
+     * in ms[0 .. 3): the tables, the power-mel launch, the finish launch (0 where the mode has none) */
+    int dmx_logmel_device_timed(int device, const float *d_planes, int planes, int64_t n, int64_t plane_stride,
+                                const dmx_logmel_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream, float *ms);
+    /* the same on host buffers: planes [planes][n], out [planes][chunks][n_mels][frames] (replaces librosa.feature.melspectrogram
+     * / whisper.audio.log_mel_spectrogram on the CPU) */
+    int dmx_logmel(int device, const float *planes, int n_planes, int64_t n, const dmx_logmel_spec *spec, float *out);
+    /* stems as a call returned them, [n_sources][channels][n] fp32 at rate_in, to features in one call (replaces the fold, the
+     * resampler and the front end of a downstream model's loader): each stem is folded to mono as 0.5 (L + R) in fp32,
+     * converted rate_in -> spec->sr by dmx_resample_device (the bits of a dmx_resample call) and sent through the stage on the
+     * device. out: [n_sources][chunks][n_mels][frames] for dmx_resample_length(n, rate_in, spec->sr) samples. */
+    int dmx_logmel_from_stems(int device, const float *stems, int n_sources, int channels, int64_t n, int rate_in,
+                              const dmx_logmel_spec *spec, float *out);
+    /* `data` as a NumPy .npy file, format 1.0, little-endian float32, C order, shape[0 .. ndim) (1 <= ndim <= 8): what np.save
+     * writes (replaces a Python step between the CLI and np.load). Pure host function. */
+    int dmx_npy_write_f32(const char *path, const float *data, int ndim, const int64_t *shape);
+
     /* ---- stems as FLAC (csrc/flac.hip; demucs's --flac; no reference counterpart: the reference holds no encoder).
      * Specification (restated in tests/flac_spec.py with an independent decoder): interleaved stereo
      * PCM as the stages above write it (16-bit pairs or packed 24 bit) -> a complete .flac file: "fLaC", one STREAMINFO block
