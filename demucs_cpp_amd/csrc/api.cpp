@@ -4,7 +4,8 @@
 //   load_demucs_model  -> dmx_model_load        (src/model_load.cpp:50)
 //   model_inference    -> dmx_segment_infer*    (src/model_inference.cpp:48; exec.cpp)
 //   demucs_inference   -> dmx_track_infer       (src/model_apply.cpp:60-288; tracks_exec.cpp)
-// The codecs' own entry points are in codec_api.cpp, dmx_debug_* in debug_api.cpp.
+// The codecs' own entry points are in codec_api.cpp, the loudness stages' in loud_api.cpp, the analysis stages' in analysis_api.cpp,
+// dmx_debug_* in debug_api.cpp.
 // No CPU fallback exists: without a usable HIP device every compute entry point fails.
 #include "api_internal.h"
 

@@ -1,6 +1,7 @@
 // api_internal.h — host-side state shared by the units of the single-context C ABI (api.cpp: models and contexts; exec.cpp:
-// the plan executor; tracks_exec.cpp: the track path; codec_api.cpp: the codecs; debug_api.cpp) and engine.cpp
-// (multi-device / multi-model scheduler). Nothing here crosses the C ABI.
+// the plan executor; tracks_exec.cpp: the track path; codec_api.cpp: the codecs; loud_api.cpp: loudness, meters and limiter;
+// analysis_api.cpp: BSS Eval, Wiener, log-mel; debug_api.cpp) and engine.cpp (multi-device / multi-model scheduler). Nothing
+// here crosses the C ABI.
 #pragma once
 #include "../../include/demucs_hip.h"
 #include "kernels.h"
@@ -192,11 +193,11 @@ dmx::GemmModelFacts dmx_model_facts(const dmx_model *m);       // what the kerne
 dmx::Plan *dmx_get_plan(dmx_ctx *c, int batch);               // the context's plan for `batch`, built and chosen on first use
 int dmx_launch_op(const dmx_ctx *c, const dmx::Op &op, hipStream_t s, dmx::i64 zeroOff); // one op of a plan on stream s
 namespace dmx { extern std::mutex g_graphMutex; }             // every HIP graph API call of the process holds it
-// ---- tracks_exec.cpp, used by codec_api.cpp
+// ---- tracks_exec.cpp, used by codec_api.cpp and loud_api.cpp
 int dmx_pcm_check_spec(const char *fn, const dmx_output_spec *spec, int S); // S < 0: the model is not known yet
 int dmx_pcm_frame_bytes(int encoding);                                      // bytes of one stereo frame
 int dmx_remix_check_spec(const char *fn, int S, const dmx_remix_spec *spec, dmx::PcmGains *G, bool noModel);
-// ---- codec_api.cpp, used by tracks_exec.cpp (the loudness stage)
+// ---- loud_api.cpp, used by tracks_exec.cpp (the loudness stage)
 int dmx_loud_check_spec(const char *fn, const dmx_loudness_spec *spec, int rate, int track); // track < 0: no track to name
 // the same validator for the entry points that take the limiter: DMX_LOUD_LIMIT, DMX_LOUD_UNITY and the times
 int dmx_limit_check_spec(const char *fn, const dmx_loudness_spec *spec, const dmx_limiter_spec *lim, int rate, int track);
@@ -230,3 +231,8 @@ int dmx_ensure_buf(DevBuf &b, dmx::i64 floats);
 int dmx_track_overlap_add_planes(dmx_ctx *c, const float *d_seg_out, int n_segments, int64_t n, int shift_offset,
                                  const float *d_stats, float *d_out, int layout, int planeBase, int nPlanes);
 hipEvent_t dmx_batch_event(dmx_ctx *c, size_t i);
+
+#include "stage_call.h"
+// ---- codec_api.cpp, used by loud_api.cpp: the wait and the downloads that end a host call with encoded outputs
+int pcm_download(const HostTrip &t, void *out, float *peaks, const unsigned char *dOut, const float *dPeaks, int nOut, dmx::i64 bytes,
+                 dmx::i64 devStride);

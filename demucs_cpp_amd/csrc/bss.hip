@@ -463,18 +463,14 @@ void launch_bss(const BssJob &job, hipStream_t s, hipEvent_t *marks)
     double *X = (double *)(w + l.X), *Y = (double *)(w + l.Y), *proj = (double *)(w + l.proj);
     int *flags = (int *)(w + l.flags);
     const int64_t nwin = bss_windows(job.n, job.window, job.hop), corr = (int64_t)2 * l.M * 16 * l.Lp;
-    int mark = 0;
-    auto stamp = [&] {
-        if (marks)
-            (void)hipEventRecord(marks[mark++], s);
-    };
-    stamp();
+    Marks mark{marks, s};
+    mark();
     bss_gram_kernel<<<dim3((unsigned)l.chunks, 2 * l.M), 256, 0, s>>>(job.refs, job.ests, l.M, job.n, job.stride, l.Lp, part);
     bss_gram_sum_kernel<<<(unsigned)((corr + 255) / 256), 256, 0, s>>>(part, l.chunks, corr, rho, job.status);
-    stamp();
+    mark();
     bss_fill_kernel<<<dim3((l.nG + 255) / 256, l.nG), 256, 0, s>>>(rho, job.C, job.L, l.Lp, l.nG, G, Gown);
     bss_rhs_kernel<<<(l.nG * kBssCols + 255) / 256, 256, 0, s>>>(rho, job.C, job.L, l.Lp, l.nG, X, Y);
-    stamp();
+    mark();
     BssBatch bt{};
     bt.m[0] = BssMat{G, X, l.nG, l.nG};
     for (int j = 0; j < job.J; ++j)
@@ -490,7 +486,7 @@ void launch_bss(const BssJob &job, hipStream_t s, hipEvent_t *marks)
             bss_syrk_kernel<<<dim3(tiles, tiles, batch), 256, 0, s>>>(bt, k0);
         }
     }
-    stamp();
+    mark();
     for (int k = 0; k < panels; ++k)
     {
         const int k0 = k * kBssPanel, below = l.nG - k0 - kBssPanel;
@@ -505,15 +501,15 @@ void launch_bss(const BssJob &job, hipStream_t s, hipEvent_t *marks)
         if (k0 > 0)
             bss_subst_update_kernel<<<dim3(k0 / 64, batch), 256, 0, s>>>(bt, k0, 1);
     }
-    stamp();
+    mark();
     bss_project_kernel<<<dim3((unsigned)((job.n + kBssProjTile - 1) / kBssProjTile), 2), 256, 0, s>>>(job.refs, l.M, job.n, job.stride, job.L,
                                                                                                       X, Y, proj);
-    stamp();
+    mark();
     bss_window_kernel<<<dim3((unsigned)nwin, job.J), 256, 0, s>>>(job.refs, job.ests, job.C, job.n, job.stride, job.window, job.hop, l.Lp, rho,
                                                                  proj, job.metrics, flags);
     bss_finish_kernel<<<(unsigned)((nwin + 255) / 256), 256, 0, s>>>(job.J, nwin, flags, job.status, job.metrics);
     if (job.filters)
         bss_filters_kernel<<<(unsigned)(((int64_t)job.J * l.nG * job.C + 255) / 256), 256, 0, s>>>(X, job.J, job.C, l.nG, job.filters);
-    stamp();
+    mark();
 }
 } // namespace dmx

@@ -1044,14 +1044,11 @@ i64 flac_workspace_bytes(int bits, i64 n)
 void launch_flac_encode(const unsigned char *pcm, i64 pcmStride, int bits, i64 n, int rate, int nOut, unsigned char *out, i64 outStride,
                         long long *sizes, unsigned char *work, hipStream_t s, int level, hipEvent_t *marks)
 {
-    auto mark = [&](int k) { // tools/flac_bench.py: four events around the three launches
-        if (marks)
-            (void)hipEventRecord(marks[k], s);
-    };
+    Marks mark{marks, s}; // tools/flac_bench.py: four events around the three launches
     const FlacLayout lay = flac_layout(bits, n);
     const int nib = rate == 44100 ? 9 : rate == 48000 ? 10 : 0;
     const dim3 grid((unsigned)lay.nFrames, (unsigned)nOut);
-    mark(0);
+    mark();
 #define DMX_FLAC_FRAME(B, LV) hipLaunchKernelGGL((flac_frame_kernel<B, LV>), grid, dim3(256), 0, s, pcm, pcmStride, n, work, lay, nib)
     if (bits == 16)
     {
@@ -1072,11 +1069,11 @@ void launch_flac_encode(const unsigned char *pcm, i64 pcmStride, int bits, i64 n
             DMX_FLAC_FRAME(24, 2);
     }
 #undef DMX_FLAC_FRAME
-    mark(1);
+    mark();
     hipLaunchKernelGGL(flac_scan_kernel, dim3(nOut), dim3(256), 0, s, work, lay, out, outStride, sizes, n, bits, rate);
-    mark(2);
+    mark();
     hipLaunchKernelGGL(flac_compact_kernel, grid, dim3(256), 0, s, work, lay, flac_slot_bytes(bits), out, outStride);
-    mark(3);
+    mark();
 }
 #else
 // ------------------------------------------------------------------------------------------------ host: the same phases

@@ -825,25 +825,22 @@ __global__ __launch_bounds__(256) void flac_in_finish_kernel(FiInfo I, const int
 int launch_flac_decode(const unsigned char *file, long long bytes, const dmx_flac_info *info, int encoding, void *out, long long *status,
                        void *work, hipStream_t s, hipEvent_t *marks)
 {
-    auto mark = [&](int k) { // tools/flac_in_bench.py: six events around the five launches
-        if (marks)
-            (void)hipEventRecord(marks[k], s);
-    };
+    Marks mark{marks, s}; // tools/flac_in_bench.py: six events around the five launches
     FiInfo I;
     if (!fi_layout(*info, bytes, I))
         return -1;
     int *w = (int *)work;
-    mark(0);
+    mark();
     hipLaunchKernelGGL(flac_in_candidates_kernel, dim3(I.nChunks), dim3(FI_CHUNK_LANES), 0, s, file, I, w);
-    mark(1);
+    mark();
     hipLaunchKernelGGL(flac_in_scan_kernel, dim3(I.nChunks), dim3(FI_CHUNK_LANES), 0, s, file, I, w);
-    mark(2);
+    mark();
     hipLaunchKernelGGL(flac_in_chain_kernel, dim3(1), dim3(FI_CHUNK_LANES), 0, s, I, w, status);
-    mark(3);
+    mark();
     if (const char *e = getenv("DMX_FLAC_IN_LANES")) // measurement switch (tools/flac_in_bench.py): 1 .. 64
         I.decLanes = atoi(e) >= 1 && atoi(e) <= FI_DEC_LANES ? atoi(e) : I.decLanes;
     hipLaunchKernelGGL(flac_in_decode_kernel, dim3((I.cap + I.decLanes - 1) / I.decLanes), dim3(FI_DEC_LANES), 0, s, file, I, w);
-    mark(4);
+    mark();
     const unsigned gx = (unsigned)(((long long)I.total + 1023) / 1024);
     if (encoding == DMX_PCM_F32)
         hipLaunchKernelGGL(flac_in_finish_kernel<DMX_PCM_F32>, dim3(gx), dim3(256), 0, s, I, (const int *)w, (unsigned *)out);
@@ -851,7 +848,7 @@ int launch_flac_decode(const unsigned char *file, long long bytes, const dmx_fla
         hipLaunchKernelGGL(flac_in_finish_kernel<DMX_PCM_S16>, dim3(gx), dim3(256), 0, s, I, (const int *)w, (unsigned *)out);
     else
         hipLaunchKernelGGL(flac_in_finish_kernel<DMX_PCM_S24>, dim3(gx), dim3(256), 0, s, I, (const int *)w, (unsigned *)out);
-    mark(5);
+    mark();
     return 0;
 }
 #else

@@ -415,6 +415,19 @@ struct RemixTable
 };
 void launch_remix_peak(const RemixPiece *pieces, int P, const PcmGains &G, hipStream_t s);
 void launch_remix_encode(const RemixPiece *pieces, int P, const PcmGains &G, int encoding, int clip, hipStream_t s);
+// the `marks` argument of the launch_* functions below (the events of a timed call): each call records the next event on s;
+// nothing where marks is null
+struct Marks
+{
+    hipEvent_t *marks;
+    hipStream_t s;
+    int next = 0;
+    void operator()()
+    {
+        if (marks)
+            (void)hipEventRecord(marks[next++], s);
+    }
+};
 // ---- the loudness stage (loudness.hip; specification: DESIGN.md section 2.14, restated in tests/loudness_spec.py) ----
 struct LoudPiece : RemixPiece
 {

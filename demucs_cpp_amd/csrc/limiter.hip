@@ -510,22 +510,19 @@ void launch_limit(const LimJob &job, const TpFilter &f, bool truePeak, hipStream
     const unsigned tiles = (unsigned)lim_tiles(n), envs = job.link ? 1u : (unsigned)job.G.nOut;
     const int F = truePeak ? f.F : 1;
     (void)hipMemsetAsync(job.res, 0, sizeof(dmx_limit_result) * (size_t)job.G.nOut, s);
-    if (marks)
-        (void)hipEventRecord(marks[0], s);
+    Marks mark{marks, s};
+    mark();
     if (F == 4)
         hipLaunchKernelGGL(lim_detect_kernel<4>, dim3(tiles, envs), dim3(256), 0, s, job, f);
     else if (F == 2)
         hipLaunchKernelGGL(lim_detect_kernel<2>, dim3(tiles, envs), dim3(256), 0, s, job, f);
     else
         hipLaunchKernelGGL(lim_detect_kernel<1>, dim3(tiles, envs), dim3(256), 0, s, job, f);
-    if (marks)
-        (void)hipEventRecord(marks[1], s);
+    mark();
     hipLaunchKernelGGL(lim_carry_kernel, dim3(envs), dim3(64), 0, s, job);
-    if (marks)
-        (void)hipEventRecord(marks[2], s);
+    mark();
     hipLaunchKernelGGL(lim_envelope_kernel, dim3(tiles, envs), dim3(256), 0, s, job);
-    if (marks)
-        (void)hipEventRecord(marks[3], s);
+    mark();
     if (truePeak)
     {
         const dim3 grid(tiles, (unsigned)job.G.nOut);
@@ -536,8 +533,7 @@ void launch_limit(const LimJob &job, const TpFilter &f, bool truePeak, hipStream
         else
             hipLaunchKernelGGL(lim_tp_kernel<1>, grid, dim3(256), 0, s, job, f);
     }
-    if (marks)
-        (void)hipEventRecord(marks[4], s);
+    mark();
 }
 #else
 // ------------------------------------------------------------------------------------------------ host: the driver

@@ -253,16 +253,12 @@ void launch_logmel(const LogmelJob &job, hipStream_t s, hipEvent_t *marks)
     a.n_fft = sp.n_fft, a.hop = sp.hop, a.n_mels = sp.n_mels, a.log_mode = sp.log_mode, a.chunks = (int)l.fr.chunks;
     a.ft = l.tile.ft, a.K = l.tile.K, a.skew = l.tile.skew, a.nft = l.tile.nft, a.span = l.tile.span;
     a.amin = sp.amin, a.top_db = sp.top_db;
-    int mark = 0;
-    auto stamp = [&] {
-        if (marks)
-            (void)hipEventRecord(marks[mark++], s);
-    };
-    stamp();
+    Marks mark{marks, s};
+    mark();
     (void)hipMemcpyAsync(job.work, job.hostTables, (size_t)l.hostBytes, hipMemcpyHostToDevice, s);
     const i64 elems = (i64)a.nft * a.n_fft * 32;
     hipLaunchKernelGGL(logmel_tables_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, a);
-    stamp();
+    mark();
     const size_t smem = (size_t)(l.tile.ldsBytes - kLogmelLdsStatic);
     const dim3 grid((unsigned)l.tiles, (unsigned)l.fr.chunks, (unsigned)job.planes);
     auto go = [&](auto kern) {
@@ -275,11 +271,11 @@ void launch_logmel(const LogmelJob &job, hipStream_t s, hipEvent_t *marks)
         go(logmel_power_mel_kernel<2>);
     else
         go(logmel_power_mel_kernel<1>);
-    stamp();
+    mark();
     if (logmel_needs_max(sp))
         hipLaunchKernelGGL(logmel_finish_kernel, dim3((unsigned)(((i64)a.n_mels * a.frames + 1023) / 1024), (unsigned)l.fr.chunks, (unsigned)job.planes),
                            dim3(256), 0, s, a);
-    stamp();
+    mark();
 }
 
 } // namespace dmx

@@ -1,6 +1,6 @@
 // loud_chain.h — the workspace of one whole track's output chain: the loudness measurements, the gains, the true peaks, the
 // reports and the limiter, computed on the host. No HIP here: the one rule serves the stage alone
-// (codec_api.cpp: the reports are the caller's buffers) and a track slot (tracks_exec.cpp: the reports live in the workspace),
+// (loud_api.cpp: the reports are the caller's buffers) and a track slot (tracks_exec.cpp: the reports live in the workspace),
 // and tests/loud_chain_harness.cpp prints it.
 #pragma once
 #include "loudness_plan.h"

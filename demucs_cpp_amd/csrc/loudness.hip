@@ -618,22 +618,19 @@ __global__ __launch_bounds__(64) void loud_gain_tp_kernel(const unsigned char *w
 void launch_loud_measure(const RemixPiece &pc, const PcmGains &G, const LoudPlan &lp, unsigned char *work, int slot0, double *eOut,
                          void *resOut, hipStream_t s, hipEvent_t *marks)
 {
-    auto mark = [&](int k) {
-        if (marks)
-            (void)hipEventRecord(marks[k], s);
-    };
+    Marks mark{marks, s};
     const i64 slotBytes = loud_workspace_bytes(lp.n);
     const dim3 tiles((unsigned)lp.nTiles, (unsigned)G.nOut);
-    mark(0);
+    mark();
     hipLaunchKernelGGL(loud_tile_kernel<false>, tiles, dim3(128), 0, s, pc, G, lp, work, slotBytes, slot0);
-    mark(1);
+    mark();
     hipLaunchKernelGGL(loud_scan_kernel, dim3(2, (unsigned)G.nOut), dim3(64), 0, s, lp, work, slotBytes, slot0);
-    mark(2);
+    mark();
     hipLaunchKernelGGL(loud_tile_kernel<true>, tiles, dim3(128), 0, s, pc, G, lp, work, slotBytes, slot0);
-    mark(3);
+    mark();
     hipLaunchKernelGGL(loud_final_kernel, dim3((unsigned)G.nOut), dim3(256), 0, s, lp, work, slotBytes, slot0, eOut,
                        (dmx_loudness_result *)resOut);
-    mark(4);
+    mark();
 }
 
 void launch_loud_gain(const unsigned char *work, i64 slotBytes, int nOut, unsigned *peaks, int mode, int targetC, float maxPeak,

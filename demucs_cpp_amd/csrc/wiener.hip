@@ -401,19 +401,15 @@ void launch_wiener(const WienerJob &job, hipStream_t s, hipEvent_t *marks)
     a.spec = (float2 *)(job.work + l.spec);
     a.n = job.n, a.stride = job.stride, a.T = l.T, a.plane = l.plane, a.chunks = l.chunks;
     a.J = job.J, a.S = job.J + (job.residual ? 1 : 0), a.residual = job.residual, a.win_len = job.win_len;
-    int mark = 0;
-    auto stamp = [&] {
-        if (marks)
-            (void)hipEventRecord(marks[mark++], s);
-    };
-    stamp();
+    Marks mark{marks, s};
+    mark();
     hipLaunchKernelGGL(wiener_tables_kernel, dim3(16), dim3(256), 0, s, a.tw, a.win);
     const dim3 gs((unsigned)l.T, 1 + job.J), ge((unsigned)(l.blocks * kWienerTiles)), gi((unsigned)l.chunks, job.J);
     if (job.C == 2)
         hipLaunchKernelGGL(wiener_stft_kernel<2>, gs, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(wiener_stft_kernel<1>, gs, dim3(256), 0, s, a);
-    stamp();
+    mark();
     for (int it = 0; it < job.iterations; ++it)
     {
         a.first = it == 0, a.last = it == job.iterations - 1;
@@ -425,13 +421,13 @@ void launch_wiener(const WienerJob &job, hipStream_t s, hipEvent_t *marks)
             hipLaunchKernelGGL((wiener_em_kernel<1, true>), ge, dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL((wiener_em_kernel<1, false>), ge, dim3(256), 0, s, a);
-        stamp();
+        mark();
     }
     if (job.C == 2)
         hipLaunchKernelGGL(wiener_istft_kernel<2>, gi, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(wiener_istft_kernel<1>, gi, dim3(256), 0, s, a);
-    stamp();
+    mark();
 }
 
 } // namespace dmx
