@@ -4,6 +4,7 @@
 //                         [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level N] [--bag-weights w00,w01,...]
 //                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]
 //                         [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]
+//                         [--dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems NAMES]]
 //                         [--limit] [--limit-attack MS] [--limit-release MS]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
@@ -60,6 +61,10 @@
 //   --wiener N               refine the float32 stems with N (1 .. 8) EM iterations of the multichannel Wiener filter against the
 //                            track's mixture (dmx_wiener; demucs's wiener_iters); --wiener-residual adds the residual source.
 //                            Not together with PCM / FLAC / remix / loudness options or a resampled or FLAC-fed track for now.
+//   --dereverb               take the room out of the float32 stems by Weighted Prediction Error (dmx_dereverb; nara_wpe's
+//                            method): --dereverb-taps K (1 .. 16, default 10), --dereverb-delay D (1 .. 8, default 3),
+//                            --dereverb-iters I (1 .. 8, default 3), --dereverb-stems vocals,... (default: all). Behind --wiener
+//                            where both are given. Not together with PCM / FLAC / remix / loudness options for now.
 //   --mel NAME               beside each float32 stem, its log-mel features as target_{i}_{name}.mel.npy: float32
 //                            [chunks][n_mels][frames] of the stem's mono fold at the preset's rate (dmx_logmel_from_stems; NAME:
 //                            whisper, whisper128 or librosa). Not together with PCM / FLAC / remix / loudness options for now.
@@ -92,6 +97,7 @@ using namespace demucscpp;
               << " [--clip-mode rescale|clamp|none] [--int16|--int24|--float32] [--flac] [--flac-level 0|1|2] [--bag-weights w00,w01,...]"
               << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]"
               << " [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]"
+              << " [--dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems vocals,...]]"
               << " [--limit] [--limit-attack MS] [--limit-release MS] (--clip-mode limit: --limit without loudnorm)"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
@@ -146,6 +152,9 @@ int main(int argc, const char **argv)
     LimitReport limit_report; // filled as well with --limit
     wiener_options wiener; // --wiener N [--wiener-residual]
     bool with_wiener = false, wiener_residual = false;
+    dereverb_options dereverb; // --dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems a,b]
+    bool with_dereverb = false, dereverb_opts = false;
+    std::string dereverb_stems;
     dmx_logmel_spec mel{}; // --mel NAME
     bool with_mel = false;
     int a = 1;
@@ -155,6 +164,12 @@ int main(int argc, const char **argv)
         if (opt == "--wiener-residual") // no value; it needs --wiener, checked behind the loop
         {
             wiener_residual = true;
+            --a;
+            continue;
+        }
+        if (opt == "--dereverb") // no value; its own options below need it, checked behind the loop
+        {
+            with_dereverb = true;
             --a;
             continue;
         }
@@ -201,6 +216,24 @@ int main(int argc, const char **argv)
                 usage(argv[0]);
             }
             with_mel = true;
+            continue;
+        }
+        if (opt == "--dereverb-taps" || opt == "--dereverb-delay" || opt == "--dereverb-iters")
+        {
+            char *end = nullptr;
+            const long v = std::strtol(val.c_str(), &end, 10), top = opt == "--dereverb-taps" ? 16 : 8;
+            if (end == val.c_str() || *end || v < 1 || v > top)
+            {
+                std::cerr << opt << " " << val << ": expected 1 .. " << top << std::endl;
+                usage(argv[0]);
+            }
+            (opt == "--dereverb-taps" ? dereverb.taps : opt == "--dereverb-delay" ? dereverb.delay : dereverb.iterations) = (int)v;
+            dereverb_opts = true;
+            continue;
+        }
+        if (opt == "--dereverb-stems")
+        {
+            dereverb_stems = val, dereverb_opts = true;
             continue;
         }
         if (opt == "--wiener")
@@ -362,6 +395,16 @@ int main(int argc, const char **argv)
     if (with_wiener && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
     {
         std::cerr << "--wiener refines the float32 stems: not together with PCM, FLAC, remix or loudness options for now" << std::endl;
+        usage(argv[0]);
+    }
+    if (dereverb_opts && !with_dereverb)
+    {
+        std::cerr << "--dereverb-taps, --dereverb-delay, --dereverb-iters and --dereverb-stems need --dereverb" << std::endl;
+        usage(argv[0]);
+    }
+    if (with_dereverb && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
+    {
+        std::cerr << "--dereverb treats the float32 stems: not together with PCM, FLAC, remix or loudness options for now" << std::endl;
         usage(argv[0]);
     }
     if (with_mel && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
@@ -569,6 +612,11 @@ int main(int argc, const char **argv)
         std::cerr << "--mel: not on a FLAC-fed or resampled track for now" << std::endl;
         usage(argv[0]);
     }
+    if (with_dereverb && (flac_in || any_rate))
+    {
+        std::cerr << "--dereverb: not on a FLAC-fed or resampled track for now" << std::endl;
+        usage(argv[0]);
+    }
     if (with_wiener && (flac_in || any_rate))
     {
         std::cerr << "--wiener: not on a FLAC-fed or resampled track for now" << std::endl;
@@ -676,6 +724,26 @@ int main(int argc, const char **argv)
     if (with_wiener) // the stems against their track's mixture (dmx_wiener; the tracks are at 44.1 kHz here)
         demucs_wiener(tracks, outs, wiener);
     static const char *names[6] = {"drums", "bass", "other", "vocals", "guitar", "piano"};
+    if (with_dereverb) // behind the Wiener filter where both are given (dmx_dereverb)
+    {
+        const int S = outs.empty() ? 0 : outs[0].S;
+        for (size_t at = 0; at < dereverb_stems.size();)
+        {
+            const size_t end = std::min(dereverb_stems.find(',', at), dereverb_stems.size());
+            const std::string name = dereverb_stems.substr(at, end - at);
+            int s = 0;
+            while (s < S && name != names[s])
+                ++s;
+            if (s == S)
+            {
+                std::cerr << "--dereverb-stems " << dereverb_stems << ": " << name << " is not a source of this model" << std::endl;
+                return 1;
+            }
+            dereverb.stems.push_back(s);
+            at = end + 1;
+        }
+        demucs_dereverb(outs, dereverb);
+    }
     for (int f = 0; f < n_files; ++f)
     {
         const StereoMatrix &audio = tracks[(size_t)f];

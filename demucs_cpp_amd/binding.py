@@ -53,6 +53,7 @@ EXPORTS = [
     "dmx_limiter_check", "dmx_loud_encode_limit_device", "dmx_loud_encode_limit", "dmx_tracks_infer_limit", "dmx_tracks_infer_from_flac_limit",
     "dmx_bss_check", "dmx_bss_windows", "dmx_bss_eval_workspace_bytes", "dmx_bss_eval_device", "dmx_bss_eval_device_timed", "dmx_bss_eval",
     "dmx_wiener_check", "dmx_wiener_workspace_bytes", "dmx_wiener_device", "dmx_wiener_device_timed", "dmx_wiener",
+    "dmx_dereverb_check", "dmx_dereverb_workspace_bytes", "dmx_dereverb_device", "dmx_dereverb_device_timed", "dmx_dereverb",
     "dmx_logmel_check", "dmx_logmel_preset", "dmx_logmel_frames", "dmx_logmel_filters", "dmx_logmel_geometry", "dmx_logmel_workspace_bytes",
     "dmx_logmel_device", "dmx_logmel_device_timed", "dmx_logmel", "dmx_logmel_from_stems", "dmx_npy_write_f32",
 ]
@@ -234,6 +235,12 @@ def lib():
         L.dmx_wiener_device.argtypes = [ci, vp, vp, ci, ci, i64, i64, vp, vp, vp, i64, vp]
         L.dmx_wiener_device_timed.argtypes = L.dmx_wiener_device.argtypes + [vp]
         L.dmx_wiener.argtypes = [ci, vp, vp, ci, ci, i64, vp, vp]
+        L.dmx_dereverb_check.argtypes = [vp, ci, ci, i64]
+        L.dmx_dereverb_workspace_bytes.argtypes = [vp, ci, ci, i64]
+        L.dmx_dereverb_workspace_bytes.restype = i64
+        L.dmx_dereverb_device.argtypes = [ci, vp, ci, ci, i64, i64, vp, vp, vp, i64, vp]
+        L.dmx_dereverb_device_timed.argtypes = L.dmx_dereverb_device.argtypes + [vp]
+        L.dmx_dereverb.argtypes = [ci, vp, ci, ci, i64, vp, vp]
         L.dmx_logmel_check.argtypes = [vp, i64]
         L.dmx_logmel_preset.argtypes = [ctypes.c_char_p, vp]
         L.dmx_logmel_frames.argtypes = [vp, i64, vp, vp]
@@ -1245,6 +1252,37 @@ def wiener(mix: np.ndarray, ests: np.ndarray, iterations: int = 1, residual: boo
     wiener_check(spec, J, C, n)
     out = np.empty_like(ests)
     _chk(lib().dmx_wiener(device, mix.ctypes.data, ests.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
+    return out
+
+
+class DereverbSpec(ctypes.Structure):
+    """dmx_dereverb_spec: prediction taps (1 .. 16), delay (1 .. 8), iterations (1 .. 8), the floor of lam and the diagonal
+    loading, both relative"""
+    _fields_ = [("taps", ctypes.c_int), ("delay", ctypes.c_int), ("iterations", ctypes.c_int), ("eps", ctypes.c_double),
+                ("reg", ctypes.c_double)]
+
+    def __init__(self, taps=10, delay=3, iterations=3, eps=1e-10, reg=1e-10):
+        super().__init__(int(taps), int(delay), int(iterations), float(eps), float(reg))
+
+
+def dereverb_check(spec: Optional[DereverbSpec], n_sources: int, channels: int, n: int):
+    """validates a DereverbSpec and a shape (dmx_dereverb_check; no GPU); raises DmxError naming the field"""
+    _chk(lib().dmx_dereverb_check(None if spec is None else ctypes.byref(spec), int(n_sources), int(channels), int(n)))
+
+
+def dereverb_workspace_bytes(spec: DereverbSpec, n_sources: int, channels: int, n: int) -> int:
+    return lib().dmx_dereverb_workspace_bytes(ctypes.byref(spec), int(n_sources), int(channels), int(n))
+
+
+def dereverb(stems: np.ndarray, spec: Optional[DereverbSpec] = None, device: int = 0) -> np.ndarray:
+    """WPE de-reverberation (dmx_dereverb): stems (J, C, n) float32 -> (J, C, n) float32, every stem on its own"""
+    stems = np.ascontiguousarray(stems, np.float32)
+    assert stems.ndim == 3, "expected stems (J, C, n)"
+    J, C, n = stems.shape
+    spec = spec or DereverbSpec()
+    dereverb_check(spec, J, C, n)
+    out = np.empty_like(stems)
+    _chk(lib().dmx_dereverb(device, stems.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
     return out
 
 

@@ -1,5 +1,5 @@
 // analysis_api.cpp — what is computed on finished stems, as entry points of their own: BSS Eval v4 (bss.hip), the Wiener
-// post-filter (wiener.hip), the log-mel features (logmel.hip) and the .npy writer of their results.
+// post-filter (wiener.hip), the WPE de-reverberation (dereverb.hip), the log-mel features (logmel.hip) and the .npy writer of their results.
 #include "api_internal.h"
 
 #include <algorithm>
@@ -206,6 +206,103 @@ extern "C" int dmx_wiener(int device, const float *mix, const float *ests, int n
     DMXCHK(wiener_device(fn, device, dIn, dEsts, n_sources, channels, n, n, spec, dOut, dWork, workBytes, nullptr, nullptr));
     DMXCHK(t.wait());
     return t.down(out, dOut, M * plane);
+}
+
+// --------------------------------------------------------------------------- WPE de-reverberation (dereverb.hip)
+static int dereverb_check(const char *fn, const dmx_dereverb_spec *spec, int J, int C, int64_t n)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: null spec pointer", fn);
+    if (spec->taps < 1 || spec->taps > kDrvMaxTaps)
+        return fail(DMX_ERR_ARG, "%s: dereverb spec: taps %d is not in [1, %d]", fn, spec->taps, kDrvMaxTaps);
+    if (spec->delay < 1 || spec->delay > kDrvMaxDelay)
+        return fail(DMX_ERR_ARG, "%s: dereverb spec: delay %d is not in [1, %d]", fn, spec->delay, kDrvMaxDelay);
+    if (spec->iterations < 1 || spec->iterations > kDrvMaxIter)
+        return fail(DMX_ERR_ARG, "%s: dereverb spec: iterations %d is not in [1, %d]", fn, spec->iterations, kDrvMaxIter);
+    if (!(spec->eps > 0.0 && spec->eps < 1.0))
+        return fail(DMX_ERR_ARG, "%s: dereverb spec: eps %g is not in (0, 1)", fn, spec->eps);
+    if (!(spec->reg >= 0.0 && spec->reg < 1.0))
+        return fail(DMX_ERR_ARG, "%s: dereverb spec: reg %g is not in [0, 1)", fn, spec->reg);
+    if (J < 1 || J > kDrvMaxSources)
+        return fail(DMX_ERR_ARG, "%s: n_sources %d is not in [1, %d]", fn, J, kDrvMaxSources);
+    if (C != 1 && C != 2)
+        return fail(DMX_ERR_ARG, "%s: channels %d is not 1 or 2", fn, C);
+    if (!dereverb_shape_ok(J, C, n))
+        return fail(DMX_ERR_ARG, "%s: n %lld is not in (%d, 2^31)", fn, (long long)n, kWienerPad);
+    return DMX_OK;
+}
+extern "C" int dmx_dereverb_check(const dmx_dereverb_spec *spec, int n_sources, int channels, int64_t n)
+{
+    return dereverb_check("dmx_dereverb_check", spec, n_sources, channels, n);
+}
+extern "C" int64_t dmx_dereverb_workspace_bytes(const dmx_dereverb_spec *spec, int n_sources, int channels, int64_t n)
+{
+    if (dereverb_check("dmx_dereverb_workspace_bytes", spec, n_sources, channels, n) != DMX_OK)
+        return -1;
+    return dereverb_workspace_bytes(n_sources, channels, n, spec->taps);
+}
+
+// marks: null, or iterations + 3 events around the stages
+static int dereverb_device(const char *fn, int device, const float *d_stems, int J, int C, int64_t n, int64_t plane_stride,
+                           const dmx_dereverb_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream, hipEvent_t *marks)
+{
+    DMXCHK(dereverb_check(fn, spec, J, C, n));
+    if (plane_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld (n <= plane_stride)", fn, (long long)n, (long long)plane_stride);
+    DMXCHK(first_null(fn, {{"d_stems", d_stems}, {"d_out", d_out}, {"d_work", d_work}}));
+    if ((((uintptr_t)d_stems | (uintptr_t)d_out) & 3) != 0 || ((uintptr_t)d_work & 255) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_stems and d_out must be 4-byte aligned, d_work 256-byte", fn);
+    const int64_t need = dereverb_workspace_bytes(J, C, n, spec->taps);
+    if (work_bytes < need)
+        return fail(DMX_ERR_ARG, "%s: work_bytes %lld is below dmx_dereverb_workspace_bytes = %lld", fn, (long long)work_bytes, (long long)need);
+    HIPCHK(hipSetDevice(device));
+    const DereverbJob job{d_stems, d_out, J, C, DrvSpec{spec->taps, spec->delay, spec->iterations, spec->eps, spec->reg}, n, plane_stride,
+                          (unsigned char *)d_work};
+    launch_dereverb(job, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_dereverb_device(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                   const dmx_dereverb_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream)
+{
+    return dereverb_device("dmx_dereverb_device", device, d_stems, n_sources, channels, n, plane_stride, spec, d_out, d_work, work_bytes, stream,
+                           nullptr);
+}
+
+extern "C" int dmx_dereverb_device_timed(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                         const dmx_dereverb_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream, float *ms)
+{
+    const char *fn = "dmx_dereverb_device_timed";
+    float gaps[kDrvMaxIter + 2];
+    int stages = 0; // iterations + 2, once dereverb_device has checked the spec: the last event recorded, not the array's last
+    DMXCHK(timed_call<kDrvMaxIter + 3>(fn, device, ms, gaps, [&](hipEvent_t *marks) {
+        DMXCHK(dereverb_device(fn, device, d_stems, n_sources, channels, n, plane_stride, spec, d_out, d_work, work_bytes, stream, marks));
+        stages = spec->iterations + 2;
+        return DMX_OK;
+    }, &stages));
+    std::copy(gaps, gaps + stages, ms);
+    return DMX_OK;
+}
+
+extern "C" int dmx_dereverb(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_dereverb_spec *spec, float *out)
+{
+    const char *fn = "dmx_dereverb";
+    DMXCHK(dereverb_check(fn, spec, n_sources, channels, n));
+    DMXCHK(first_null(fn, {{"stems", stems}, {"out", out}}));
+    HIPCHK(hipSetDevice(device));
+    const size_t bytes = sizeof(float) * (size_t)n * (size_t)n_sources * (size_t)channels;
+    const int64_t workBytes = dereverb_workspace_bytes(n_sources, channels, n, spec->taps);
+    HostTrip t(fn);
+    float *dIn, *dOut;
+    void *dWork;
+    DMXCHK(t.alloc(&dIn, bytes));
+    DMXCHK(t.alloc(&dOut, bytes));
+    DMXCHK(t.alloc(&dWork, (size_t)workBytes));
+    DMXCHK(t.up(dIn, stems, bytes));
+    DMXCHK(dereverb_device(fn, device, dIn, n_sources, channels, n, n, spec, dOut, dWork, workBytes, nullptr, nullptr));
+    DMXCHK(t.wait());
+    return t.down(out, dOut, bytes);
 }
 
 // --------------------------------------------------------------------------- log-mel features (logmel.hip)

@@ -7,6 +7,7 @@
 #include "limiter_plan.h"
 #include "bss_plan.h"
 #include "wiener_plan.h"
+#include "dereverb_plan.h"
 #include "logmel_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -523,6 +524,20 @@ struct WienerJob
     unsigned char *work;
 };
 void launch_wiener(const WienerJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
+// ---- WPE de-reverberation (dereverb.hip; specification: DESIGN.md section 2.21, restated in tests/dereverb_spec.py) ----
+// (the limits, the tiles and the workspace: dereverb_plan.h)
+// x and out: J C planar fp32 planes of n samples, plane j * C + c at (j * C + c) * stride, on the device.
+// marks: NULL, or iterations + 3 events around the stages (forward STFT with the floor, each iteration, inverse)
+struct DereverbJob
+{
+    const float *x;
+    float *out;
+    int J, C;
+    DrvSpec spec;
+    i64 n, stride;
+    unsigned char *work;
+};
+void launch_dereverb(const DereverbJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
 // ---- log-mel features (logmel.hip; specification: DESIGN.md section 2.20, restated in tests/logmel_spec.py) ----
 // (chunks, frames, the tile and the workspace: logmel_plan.h)
 // x: `planes` fp32 planes of n samples, plane p at p * stride; out: [planes][chunks][n_mels][frames] floats; work: the

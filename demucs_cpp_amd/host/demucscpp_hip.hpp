@@ -374,6 +374,39 @@ inline std::vector<StemTensor> demucs_inference_batch(const demucs_model &model,
     return out;
 }
 
+// WPE de-reverberation (dmx_dereverb) of the stems a batch call returned, in place: every chosen stem
+// on its own, its two channels the array. `stems`: the indices to treat; empty: all.
+struct dereverb_options
+{
+    int taps = 10, delay = 3, iterations = 3;
+    double eps = 1e-10, reg = 1e-10;
+    std::vector<int> stems;
+    int device = 0;
+};
+inline void demucs_dereverb(std::vector<StemTensor> &stems, const dereverb_options &o)
+{
+    const dmx_dereverb_spec spec{o.taps, o.delay, o.iterations, o.eps, o.reg};
+    for (StemTensor &st : stems)
+    {
+        std::vector<int> pick = o.stems;
+        if (pick.empty())
+            for (int s = 0; s < st.S; ++s)
+                pick.push_back(s);
+        const int64_t n = st.n;
+        std::vector<float> planes(pick.size() * (size_t)(2 * n)); // planar, as the library takes them
+        for (size_t p = 0; p < pick.size(); ++p)
+            for (int c = 0; c < 2; ++c)
+                for (int64_t i = 0; i < n; ++i)
+                    planes[(p * 2 + (size_t)c) * (size_t)n + (size_t)i] = st(pick[p], c, i);
+        if (dmx_dereverb(o.device, planes.data(), (int)pick.size(), 2, n, &spec, planes.data()) != DMX_OK)
+            detail::die("demucs_dereverb");
+        for (size_t p = 0; p < pick.size(); ++p)
+            for (int c = 0; c < 2; ++c)
+                for (int64_t i = 0; i < n; ++i)
+                    st(pick[p], c, i) = planes[(p * 2 + (size_t)c) * (size_t)n + (size_t)i];
+    }
+}
+
 // Log-mel features of the stems a batch call returned (dmx_logmel_from_stems): each stem is folded to
 // mono, converted rate -> spec.sr and sent through Whisper's / librosa's front end on the device. spec: from dmx_logmel_preset.
 struct MelTensor

@@ -665,6 +665,39 @@ extern "C"
     int dmx_wiener(int device, const float *mix, const float *ests, int n_sources, int channels, int64_t n, const dmx_wiener_spec *spec,
                    float *out);
 
+    /* ---- De-reverberation of the stems by Weighted Prediction Error (csrc/dereverb.hip; DESIGN.md section 2.21, restated in
+     * tests/dereverb_spec.py; what nara_wpe computes). Stems x[j][c][n], J = 1 .. 8 of C = 1 | 2 channels and 2048 < n < 2^31
+     * samples; every stem is treated on its own, its channels are the array. The STFT is the Wiener stage's (fp32, complex64
+     * Y[c][t][f]); floor = eps max |Y|^2 per stem, a stem that is all zero is returned as zeros. With M = C taps and the
+     * stacked past Yt(t), row (k, c) = Y_c(t - delay - k) (zero before the first frame), Z = Y and per iteration in binary64:
+     * lam(t, f) = max(mean_c |Z_c|^2, floor), R(f) = sum_t Yt Yt^H / lam, P(f) = sum_t Yt Y^H / lam,
+     * R += reg (trace R / M) I, G = R^-1 P, Z(t) = Y(t) - G^H Yt(t). After the last, Z is rounded to complex64 and goes through
+     * the Wiener stage's inverse to out[j][c][n]. A fixed order everywhere: equal inputs, equal bits.
+     * Out of scope: other STFT sizes, more than 2 channels, psd_context, the online form, the multi-GPU engine. */
+    typedef struct dmx_dereverb_spec
+    {
+        int taps;       /* K, 1 .. 16; nara_wpe's default: 10 */
+        int delay;      /* D, 1 .. 8; default 3 */
+        int iterations; /* 1 .. 8; default 3 */
+        double eps;     /* the floor of lam relative to the stem's largest |Y|^2, in (0, 1); default 1e-10 */
+        double reg;     /* the diagonal loading relative to trace R / M, in [0, 1); default 1e-10 */
+    } dmx_dereverb_spec;
+    /* Pure host function; DMX_ERR_ARG with a message that names the field or argument. */
+    int dmx_dereverb_check(const dmx_dereverb_spec *spec, int n_sources, int channels, int64_t n);
+    /* the bytes of d_work (csrc/dereverb_plan.h: Y, Z and lam over the track, the correlation's partial tiles, G);
+     * -1 (and a message) where dmx_dereverb_check fails. Pure host function. */
+    int64_t dmx_dereverb_workspace_bytes(const dmx_dereverb_spec *spec, int n_sources, int channels, int64_t n);
+    /* d_stems and d_out: planes source * channels + channel at plane_stride (>= n) floats; d_work: work_bytes >=
+     * dmx_dereverb_workspace_bytes, 256-byte aligned. Asynchronous on `stream`. */
+    int dmx_dereverb_device(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                            const dmx_dereverb_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream);
+    /* measurement (tools/dereverb_bench.py): the call above, synchronised, with the times of its iterations + 2 stages between
+     * HIP events in ms[0 .. iterations + 2): forward STFT with the floor, each iteration (correlation, solve, filter), inverse */
+    int dmx_dereverb_device_timed(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                  const dmx_dereverb_spec *spec, float *d_out, void *d_work, int64_t work_bytes, void *stream, float *ms);
+    /* the same on host buffers: stems and out [n_sources][channels][n] */
+    int dmx_dereverb(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_dereverb_spec *spec, float *out);
+
     /* ---- Log-mel features of the stems (csrc/logmel.hip; DESIGN.md section 2.20, restated in tests/logmel_spec.py; the front
      * end of Whisper / WhisperX and of librosa.feature.melspectrogram + power_to_db). P planes of N fp32 samples at `sr`:
      * centred frames (reflect padding of n_fft / 2, periodic Hann window), S[f] = |sum_n w[n] x[n] e^{-2 pi i f n / n_fft}|^2 for
