@@ -5,6 +5,7 @@
 //                         [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]
 //                         [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]
 //                         [--dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems NAMES]]
+//                         [--tempo R] [--pitch SEMITONES] [--stretch-stems NAMES]
 //                         [--limit] [--limit-attack MS] [--limit-release MS]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
@@ -65,6 +66,12 @@
 //                            method): --dereverb-taps K (1 .. 16, default 10), --dereverb-delay D (1 .. 8, default 3),
 //                            --dereverb-iters I (1 .. 8, default 3), --dereverb-stems vocals,... (default: all). Behind --wiener
 //                            where both are given. Not together with PCM / FLAC / remix / loudness options for now.
+//   --tempo R, --pitch SEMITONES   change the tempo (R = 0.25 .. 4, above 1 faster) and the key (-12 .. 12, fractions allowed) of
+//                            the float32 stems by the phase vocoder (dmx_stretch; what librosa's time_stretch and pitch_shift
+//                            compute): the tempo as the nearest fraction with a denominator up to 4096, the key as a rate
+//                            conversion by the nearest fraction to 2^(SEMITONES / 12) with a denominator up to 512
+//                            (dmx_stretch_ratio). --stretch-stems vocals,... (default: all; the others are written as they
+//                            are). Behind --wiener and --dereverb. Not together with --mel, PCM / FLAC / remix / loudness options.
 //   --mel NAME               beside each float32 stem, its log-mel features as target_{i}_{name}.mel.npy: float32
 //                            [chunks][n_mels][frames] of the stem's mono fold at the preset's rate (dmx_logmel_from_stems; NAME:
 //                            whisper, whisper128 or librosa). Not together with PCM / FLAC / remix / loudness options for now.
@@ -98,6 +105,7 @@ using namespace demucscpp;
               << " [--loudnorm LUFS | --loudnorm-each LUFS | --loudness] [--max-peak DB] [--true-peak] [--meters]"
               << " [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]"
               << " [--dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems vocals,...]]"
+              << " [--tempo 0.25..4] [--pitch SEMITONES] [--stretch-stems vocals,...]"
               << " [--limit] [--limit-attack MS] [--limit-release MS] (--clip-mode limit: --limit without loudnorm)"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
@@ -157,6 +165,10 @@ int main(int argc, const char **argv)
     std::string dereverb_stems;
     dmx_logmel_spec mel{}; // --mel NAME
     bool with_mel = false;
+    stretch_options stretch; // --tempo R, --pitch SEMITONES [--stretch-stems a,b]
+    double tempo = 1.0, semitones = 0.0;
+    bool with_stretch = false;
+    std::string stretch_stems;
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -234,6 +246,24 @@ int main(int argc, const char **argv)
         if (opt == "--dereverb-stems")
         {
             dereverb_stems = val, dereverb_opts = true;
+            continue;
+        }
+        if (opt == "--tempo" || opt == "--pitch")
+        {
+            char *end = nullptr;
+            const double v = std::strtod(val.c_str(), &end), lo = opt == "--tempo" ? 0.25 : -12.0, hi = opt == "--tempo" ? 4.0 : 12.0;
+            if (end == val.c_str() || *end || !(v >= lo && v <= hi))
+            {
+                std::cerr << opt << " " << val << ": expected " << lo << " .. " << hi << std::endl;
+                usage(argv[0]);
+            }
+            (opt == "--tempo" ? tempo : semitones) = v;
+            with_stretch = true;
+            continue;
+        }
+        if (opt == "--stretch-stems")
+        {
+            stretch_stems = val;
             continue;
         }
         if (opt == "--wiener")
@@ -405,6 +435,16 @@ int main(int argc, const char **argv)
     if (with_dereverb && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
     {
         std::cerr << "--dereverb treats the float32 stems: not together with PCM, FLAC, remix or loudness options for now" << std::endl;
+        usage(argv[0]);
+    }
+    if (!stretch_stems.empty() && !with_stretch)
+    {
+        std::cerr << "--stretch-stems needs --tempo or --pitch" << std::endl;
+        usage(argv[0]);
+    }
+    if (with_stretch && (with_mel || with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
+    {
+        std::cerr << "--tempo and --pitch treat the float32 stems: not together with --mel, PCM, FLAC, remix or loudness options for now" << std::endl;
         usage(argv[0]);
     }
     if (with_mel && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
@@ -617,6 +657,11 @@ int main(int argc, const char **argv)
         std::cerr << "--dereverb: not on a FLAC-fed or resampled track for now" << std::endl;
         usage(argv[0]);
     }
+    if (with_stretch && (flac_in || any_rate))
+    {
+        std::cerr << "--tempo, --pitch: not on a FLAC-fed or resampled track for now" << std::endl;
+        usage(argv[0]);
+    }
     if (with_wiener && (flac_in || any_rate))
     {
         std::cerr << "--wiener: not on a FLAC-fed or resampled track for now" << std::endl;
@@ -744,6 +789,37 @@ int main(int argc, const char **argv)
         }
         demucs_dereverb(outs, dereverb);
     }
+    std::vector<StemTensor> stretched; // behind both (dmx_stretch): per track the chosen stems, at their new length
+    std::vector<int> stretch_slot(6, -1); // where a stem lies in them; -1: written as it is
+    if (with_stretch)
+    {
+        const int S = outs.empty() ? 0 : outs[0].S;
+        for (size_t at = 0; at < stretch_stems.size();)
+        {
+            const size_t end = std::min(stretch_stems.find(',', at), stretch_stems.size());
+            const std::string name = stretch_stems.substr(at, end - at);
+            int s = 0;
+            while (s < S && name != names[s])
+                ++s;
+            if (s == S)
+            {
+                std::cerr << "--stretch-stems " << stretch_stems << ": " << name << " is not a source of this model" << std::endl;
+                return 1;
+            }
+            stretch.stems.push_back(s);
+            at = end + 1;
+        }
+        for (int s = 0; s < S; ++s)
+            if (stretch.stems.empty())
+                stretch_slot[(size_t)s] = s;
+            else if (std::find(stretch.stems.begin(), stretch.stems.end(), s) != stretch.stems.end())
+                stretch_slot[(size_t)s] = (int)(std::find(stretch.stems.begin(), stretch.stems.end(), s) - stretch.stems.begin());
+        stretch.set(tempo, semitones);
+        std::cout << "Stretching by " << stretch.num << "/" << stretch.den << ", converting " << stretch.pitch_num << " -> " << stretch.pitch_den
+                  << std::endl;
+        for (const StemTensor &st : outs)
+            stretched.push_back(demucs_stretch(st, stretch));
+    }
     for (int f = 0; f < n_files; ++f)
     {
         const StereoMatrix &audio = tracks[(size_t)f];
@@ -847,12 +923,16 @@ int main(int argc, const char **argv)
             }
             auto p_target = p / ("target_" + std::to_string(target) + "_" + names[target] + ".wav");
             std::cout << "Writing wav file " << p_target << std::endl;
-            for (int64_t i = 0; i < audio.cols(); ++i)
+            const int slot = stretch_slot[(size_t)target];
+            const StemTensor &from = slot < 0 ? out : stretched[(size_t)f];
+            const int64_t cols = slot < 0 ? (int64_t)audio.cols() : from.n;
+            wave.resize((size_t)(2 * cols));
+            for (int64_t i = 0; i < cols; ++i)
             {
-                wave[(size_t)(2 * i)] = out(target, 0, i);
-                wave[(size_t)(2 * i + 1)] = out(target, 1, i);
+                wave[(size_t)(2 * i)] = from(slot < 0 ? target : slot, 0, i);
+                wave[(size_t)(2 * i + 1)] = from(slot < 0 ? target : slot, 1, i);
             }
-            if (!wavio::write_audio_file(wave.data(), audio.cols(), p_target.string())) // (every track is at 44.1 kHz here)
+            if (!wavio::write_audio_file(wave.data(), cols, p_target.string())) // (every track is at 44.1 kHz here)
             {
                 std::cerr << "Error writing " << p_target << std::endl;
                 exit(1);

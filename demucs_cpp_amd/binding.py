@@ -54,6 +54,8 @@ EXPORTS = [
     "dmx_bss_check", "dmx_bss_windows", "dmx_bss_eval_workspace_bytes", "dmx_bss_eval_device", "dmx_bss_eval_device_timed", "dmx_bss_eval",
     "dmx_wiener_check", "dmx_wiener_workspace_bytes", "dmx_wiener_device", "dmx_wiener_device_timed", "dmx_wiener",
     "dmx_dereverb_check", "dmx_dereverb_workspace_bytes", "dmx_dereverb_device", "dmx_dereverb_device_timed", "dmx_dereverb",
+    "dmx_stretch_check", "dmx_stretch_length", "dmx_stretch_workspace_bytes", "dmx_stretch_device", "dmx_stretch_device_timed", "dmx_stretch",
+    "dmx_stretch_ratio",
     "dmx_logmel_check", "dmx_logmel_preset", "dmx_logmel_frames", "dmx_logmel_filters", "dmx_logmel_geometry", "dmx_logmel_workspace_bytes",
     "dmx_logmel_device", "dmx_logmel_device_timed", "dmx_logmel", "dmx_logmel_from_stems", "dmx_npy_write_f32",
 ]
@@ -241,6 +243,15 @@ def lib():
         L.dmx_dereverb_device.argtypes = [ci, vp, ci, ci, i64, i64, vp, vp, vp, i64, vp]
         L.dmx_dereverb_device_timed.argtypes = L.dmx_dereverb_device.argtypes + [vp]
         L.dmx_dereverb.argtypes = [ci, vp, ci, ci, i64, vp, vp]
+        L.dmx_stretch_check.argtypes = [vp, ci, ci, i64]
+        L.dmx_stretch_length.argtypes = [vp, i64]
+        L.dmx_stretch_length.restype = i64
+        L.dmx_stretch_workspace_bytes.argtypes = [vp, ci, ci, i64]
+        L.dmx_stretch_workspace_bytes.restype = i64
+        L.dmx_stretch_device.argtypes = [ci, vp, ci, ci, i64, i64, vp, vp, i64, vp, i64, vp]
+        L.dmx_stretch_device_timed.argtypes = L.dmx_stretch_device.argtypes + [vp]
+        L.dmx_stretch.argtypes = [ci, vp, ci, ci, i64, vp, vp]
+        L.dmx_stretch_ratio.argtypes = [ctypes.c_double, ci, vp, vp]
         L.dmx_logmel_check.argtypes = [vp, i64]
         L.dmx_logmel_preset.argtypes = [ctypes.c_char_p, vp]
         L.dmx_logmel_frames.argtypes = [vp, i64, vp, vp]
@@ -1283,6 +1294,47 @@ def dereverb(stems: np.ndarray, spec: Optional[DereverbSpec] = None, device: int
     dereverb_check(spec, J, C, n)
     out = np.empty_like(stems)
     _chk(lib().dmx_dereverb(device, stems.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
+    return out
+
+
+class StretchSpec(ctypes.Structure):
+    """dmx_stretch_spec: the stretch rate num / den (above 1: faster, shorter; 1/4 .. 4) and the converter pitch_num -> pitch_den
+    behind it (equal: none), every term in [1, 2^20]"""
+    _fields_ = [("num", ctypes.c_int), ("den", ctypes.c_int), ("pitch_num", ctypes.c_int), ("pitch_den", ctypes.c_int)]
+
+    def __init__(self, num=1, den=1, pitch_num=1, pitch_den=1):
+        super().__init__(int(num), int(den), int(pitch_num), int(pitch_den))
+
+
+def stretch_ratio(value: float, max_den: int):
+    """the fraction (num, den) nearest to value with den <= max_den, of two equally near the smaller den (dmx_stretch_ratio)"""
+    num, den = ctypes.c_int(0), ctypes.c_int(0)
+    _chk(lib().dmx_stretch_ratio(float(value), int(max_den), ctypes.byref(num), ctypes.byref(den)))
+    return num.value, den.value
+
+
+def stretch_check(spec: Optional[StretchSpec], n_sources: int, channels: int, n: int):
+    """validates a StretchSpec and a shape (dmx_stretch_check; no GPU); raises DmxError naming the field"""
+    _chk(lib().dmx_stretch_check(None if spec is None else ctypes.byref(spec), int(n_sources), int(channels), int(n)))
+
+
+def stretch_length(spec: StretchSpec, n: int) -> int:
+    """the samples of a plane that dmx_stretch returns for n samples; -1 on a bad spec"""
+    return lib().dmx_stretch_length(ctypes.byref(spec), int(n))
+
+
+def stretch_workspace_bytes(spec: StretchSpec, n_sources: int, channels: int, n: int) -> int:
+    return lib().dmx_stretch_workspace_bytes(ctypes.byref(spec), int(n_sources), int(channels), int(n))
+
+
+def stretch(stems: np.ndarray, spec: StretchSpec, device: int = 0) -> np.ndarray:
+    """phase-vocoder time stretch and pitch shift (dmx_stretch): stems (J, C, n) float32 -> (J, C, stretch_length) float32"""
+    stems = np.ascontiguousarray(stems, np.float32)
+    assert stems.ndim == 3, "expected stems (J, C, n)"
+    J, C, n = stems.shape
+    stretch_check(spec, J, C, n)
+    out = np.empty((J, C, stretch_length(spec, n)), np.float32)
+    _chk(lib().dmx_stretch(device, stems.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
     return out
 
 

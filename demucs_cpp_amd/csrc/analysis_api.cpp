@@ -1,8 +1,10 @@
 // analysis_api.cpp — what is computed on finished stems, as entry points of their own: BSS Eval v4 (bss.hip), the Wiener
-// post-filter (wiener.hip), the WPE de-reverberation (dereverb.hip), the log-mel features (logmel.hip) and the .npy writer of their results.
+// post-filter (wiener.hip), the WPE de-reverberation (dereverb.hip), the time stretch and pitch shift (stretch.hip), the log-mel
+// features (logmel.hip) and the .npy writer of their results.
 #include "api_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 
 using namespace dmx;
@@ -303,6 +305,163 @@ extern "C" int dmx_dereverb(int device, const float *stems, int n_sources, int c
     DMXCHK(dereverb_device(fn, device, dIn, n_sources, channels, n, n, spec, dOut, dWork, workBytes, nullptr, nullptr));
     DMXCHK(t.wait());
     return t.down(out, dOut, bytes);
+}
+
+// --------------------------------------------------------------------------- time stretch and pitch shift (stretch.hip)
+static StretchSpec stretch_spec(const dmx_stretch_spec *s) { return StretchSpec{s->num, s->den, s->pitch_num, s->pitch_den}; }
+static int stretch_check(const char *fn, const dmx_stretch_spec *spec, int J, int C, int64_t n)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: null spec pointer", fn);
+    const std::pair<const char *, int> terms[] = {{"num", spec->num}, {"den", spec->den}, {"pitch_num", spec->pitch_num}, {"pitch_den", spec->pitch_den}};
+    for (const auto &t : terms)
+        if (t.second < 1 || t.second > kStretchMaxTerm)
+            return fail(DMX_ERR_ARG, "%s: stretch spec: %s %d is not in [1, %d]", fn, t.first, t.second, kStretchMaxTerm);
+    const StretchSpec s = stretch_spec(spec);
+    if (!stretch_spec_ok(s))
+        return fail(DMX_ERR_ARG, "%s: stretch spec: the rate num / den = %d / %d is not in [1/%d, %d]", fn, s.num, s.den, kStretchMaxRate, kStretchMaxRate);
+    if (J < 1 || J > kStretchMaxSources)
+        return fail(DMX_ERR_ARG, "%s: n_sources %d is not in [1, %d]", fn, J, kStretchMaxSources);
+    if (C != 1 && C != 2)
+        return fail(DMX_ERR_ARG, "%s: channels %d is not 1 or 2", fn, C);
+    if (!wiener_shape_ok(1, C, n))
+        return fail(DMX_ERR_ARG, "%s: n %lld is not in (%d, 2^31)", fn, (long long)n, kWienerPad);
+    if (!stretch_shape_ok(J, C, n, s))
+        return fail(DMX_ERR_ARG, "%s: the stretched length ceil(n den / num) = %lld is not in (%d, 2^31)", fn, (long long)stretch_mid_length(n, s),
+                    kWienerPad);
+    if (stretch_converts(s) && resample_check(s.pnum, s.pden, J * C) != DMX_OK)
+    {
+        const std::string why = dmx_err_string(); // the converter's own refusal, passed on
+        return fail(DMX_ERR_ARG, "%s: stretch spec: pitch_num / pitch_den = %d / %d: %s", fn, s.pnum, s.pden, why.c_str());
+    }
+    return DMX_OK;
+}
+extern "C" int dmx_stretch_check(const dmx_stretch_spec *spec, int n_sources, int channels, int64_t n)
+{
+    return stretch_check("dmx_stretch_check", spec, n_sources, channels, n);
+}
+extern "C" int64_t dmx_stretch_length(const dmx_stretch_spec *spec, int64_t n)
+{
+    if (!spec || !stretch_spec_ok(stretch_spec(spec)) || n < 0 || n >= ((int64_t)1 << 31))
+        return -1;
+    const int64_t mid = stretch_mid_length(n, stretch_spec(spec));
+    return spec->pitch_num == spec->pitch_den ? mid : dmx_resample_length(mid, spec->pitch_num, spec->pitch_den);
+}
+extern "C" int64_t dmx_stretch_workspace_bytes(const dmx_stretch_spec *spec, int n_sources, int channels, int64_t n)
+{
+    if (stretch_check("dmx_stretch_workspace_bytes", spec, n_sources, channels, n) != DMX_OK)
+        return -1;
+    return stretch_workspace_bytes(n_sources, channels, n, stretch_spec(spec));
+}
+
+// The fraction nearest to `value` among those with a denominator of at most max_den; of two equally near, the smaller
+// denominator. Exact: value = M / 2^k with M below 2^53, so |value - n / d| = |M d - n 2^k| / (d 2^k), and two of them are
+// compared by cross-multiplying in 128-bit integers (M d < 2^73; a numerator |M d - n 2^k| <= 2^(k - 1) times d <= 2^20).
+extern "C" int dmx_stretch_ratio(double value, int max_den, int *num, int *den)
+{
+    const char *fn = "dmx_stretch_ratio";
+    DMXCHK(first_null(fn, {{"num", num}, {"den", den}}));
+    if (!(value >= 1.0 / 1024 && value <= 1024.0))
+        return fail(DMX_ERR_ARG, "%s: value %g is not in [1/1024, 1024]", fn, value);
+    if (max_den < 1 || max_den > kStretchMaxTerm)
+        return fail(DMX_ERR_ARG, "%s: max_den %d is not in [1, %d]", fn, max_den, kStretchMaxTerm);
+    typedef unsigned __int128 u128;
+    int e = 0;
+    const u128 M = (u128)std::ldexp(std::frexp(value, &e), 53); // value = M 2^(e - 53), an integer below 2^53
+    const int k = 53 - e;                                      // 42 .. 62
+    u128 bestErr = 0;
+    int64_t bestN = 0, bestD = 0;
+    for (int64_t d = 1; d <= max_den; ++d)
+    {
+        const u128 Md = M * (u128)d;
+        u128 n = (Md + ((u128)1 << (k - 1))) >> k; // the integer nearest to value d, at least 1
+        if (n == 0)
+            n = 1;
+        const u128 err = Md > (n << k) ? Md - (n << k) : (n << k) - Md;
+        if (bestD == 0 || err * (u128)bestD < bestErr * (u128)d) // err / d < bestErr / bestD: strictly nearer only
+            bestErr = err, bestN = (int64_t)n, bestD = d;
+    }
+    *num = (int)bestN, *den = (int)bestD;
+    return DMX_OK;
+}
+
+// marks: null, or 5 events around the stages. *stages, where given: the index of the last event recorded
+static int stretch_device(const char *fn, int device, const float *d_stems, int J, int C, int64_t n, int64_t plane_stride,
+                          const dmx_stretch_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream,
+                          hipEvent_t *marks, int *stages = nullptr)
+{
+    DMXCHK(stretch_check(fn, spec, J, C, n));
+    const int64_t nOut = dmx_stretch_length(spec, n);
+    if (plane_stride < n || out_stride < nOut)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld, dmx_stretch_length = %lld, out_stride = %lld (n <= plane_stride, "
+                    "the length <= out_stride)", fn, (long long)n, (long long)plane_stride, (long long)nOut, (long long)out_stride);
+    DMXCHK(first_null(fn, {{"d_stems", d_stems}, {"d_out", d_out}, {"d_work", d_work}}));
+    if ((((uintptr_t)d_stems | (uintptr_t)d_out) & 3) != 0 || ((uintptr_t)d_work & 255) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_stems and d_out must be 4-byte aligned, d_work 256-byte", fn);
+    const StretchSpec s = stretch_spec(spec);
+    const int64_t need = stretch_workspace_bytes(J, C, n, s);
+    if (work_bytes < need)
+        return fail(DMX_ERR_ARG, "%s: work_bytes %lld is below dmx_stretch_workspace_bytes = %lld", fn, (long long)work_bytes, (long long)need);
+    HIPCHK(hipSetDevice(device));
+    if (stretch_converts(s)) // the filter's upload blocks: ahead of the launches
+        DMXCHK(resample_prepare(device, s.pnum, s.pden));
+    const StretchJob job{d_stems, d_out, J, C, s, n, plane_stride, out_stride, (unsigned char *)d_work};
+    launch_stretch(job, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    if (stages)
+        *stages = 3;
+    if (!stretch_converts(s))
+        return DMX_OK;
+    const StretchLayout l = stretch_layout(J, C, n, s);
+    DMXCHK(dmx_resample_device(device, (const float *)((unsigned char *)d_work + l.tmp), l.n2, J * C, l.mid, 1, s.pnum, s.pden, d_out, out_stride,
+                               1, stream));
+    if (marks)
+        HIPCHK(hipEventRecord(marks[4], (hipStream_t)stream));
+    if (stages)
+        *stages = 4;
+    return DMX_OK;
+}
+
+extern "C" int dmx_stretch_device(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                  const dmx_stretch_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream)
+{
+    return stretch_device("dmx_stretch_device", device, d_stems, n_sources, channels, n, plane_stride, spec, d_out, out_stride, d_work, work_bytes,
+                          stream, nullptr);
+}
+
+extern "C" int dmx_stretch_device_timed(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                        const dmx_stretch_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes,
+                                        void *stream, float *ms)
+{
+    const char *fn = "dmx_stretch_device_timed";
+    float gaps[4] = {0.f, 0.f, 0.f, 0.f}; // the converter's entry stays 0 where there is none
+    int stages = 0;
+    DMXCHK(timed_call<5>(fn, device, ms, gaps, [&](hipEvent_t *marks) {
+        return stretch_device(fn, device, d_stems, n_sources, channels, n, plane_stride, spec, d_out, out_stride, d_work, work_bytes, stream, marks,
+                              &stages);
+    }, &stages));
+    std::copy(gaps, gaps + 4, ms);
+    return DMX_OK;
+}
+
+extern "C" int dmx_stretch(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_stretch_spec *spec, float *out)
+{
+    const char *fn = "dmx_stretch";
+    DMXCHK(stretch_check(fn, spec, n_sources, channels, n));
+    DMXCHK(first_null(fn, {{"stems", stems}, {"out", out}}));
+    HIPCHK(hipSetDevice(device));
+    const size_t planes = (size_t)n_sources * (size_t)channels;
+    const int64_t nOut = dmx_stretch_length(spec, n), workBytes = stretch_workspace_bytes(n_sources, channels, n, stretch_spec(spec));
+    HostTrip t(fn);
+    float *dIn, *dOut;
+    void *dWork;
+    DMXCHK(t.alloc(&dIn, sizeof(float) * planes * (size_t)n));
+    DMXCHK(t.alloc(&dOut, sizeof(float) * planes * (size_t)nOut));
+    DMXCHK(t.alloc(&dWork, (size_t)workBytes));
+    DMXCHK(t.up(dIn, stems, sizeof(float) * planes * (size_t)n));
+    DMXCHK(stretch_device(fn, device, dIn, n_sources, channels, n, n, spec, dOut, nOut, dWork, workBytes, nullptr, nullptr));
+    DMXCHK(t.wait());
+    return t.down(out, dOut, sizeof(float) * planes * (size_t)nOut);
 }
 
 // --------------------------------------------------------------------------- log-mel features (logmel.hip)

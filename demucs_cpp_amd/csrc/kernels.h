@@ -8,6 +8,7 @@
 #include "bss_plan.h"
 #include "wiener_plan.h"
 #include "dereverb_plan.h"
+#include "stretch_plan.h"
 #include "logmel_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -538,6 +539,21 @@ struct DereverbJob
     unsigned char *work;
 };
 void launch_dereverb(const DereverbJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
+// ---- phase-vocoder time stretch (stretch.hip; specification: DESIGN.md section 2.22, restated in tests/stretch_spec.py) ----
+// (the limits, the lengths and the workspace: stretch_plan.h)
+// x: J C planar fp32 planes of n samples at `stride`. The stretched planes of stretch_mid_length(n, spec) samples go to `out` at
+// outStride or, where the spec has a converter, to the workspace's tmp at the layout's mid: the caller runs the converter.
+// marks: NULL, or 4 events around the stages (forward STFT, products + carry, fused inverse)
+struct StretchJob
+{
+    const float *x;
+    float *out;
+    int J, C;
+    StretchSpec spec;
+    i64 n, stride, outStride;
+    unsigned char *work;
+};
+void launch_stretch(const StretchJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
 // ---- log-mel features (logmel.hip; specification: DESIGN.md section 2.20, restated in tests/logmel_spec.py) ----
 // (chunks, frames, the tile and the workspace: logmel_plan.h)
 // x: `planes` fp32 planes of n samples, plane p at p * stride; out: [planes][chunks][n_mels][frames] floats; work: the

@@ -9,7 +9,8 @@
 //   wiener_istft_kernel   one workgroup per (source, chunk of frames): inverse transform of both channels of `ispec` + src C
 //                         planes at once, the windowed frames go to a ring of four hops in LDS, each finished hop is divided by
 //                         its window-square sum and written; the frames never reach HBM. Chunks start 3 frames early, so every
-//                         hop is summed in frame order whatever the cut.
+//                         hop is summed in frame order whatever the cut. Its text is wiener_istft_body, whose frame loop takes
+//                         the spectrum from a source: PlainSpectrum here, the phase vocoder's in stretch.hip.
 #pragma once
 #include "kernels.h"
 #include "fft4096.h"
@@ -97,8 +98,25 @@ __global__ __launch_bounds__(256) void wiener_stft_kernel(const WienerArgs p)
 }
 
 // ------------------------------------------------------------------------------------------------ inverse STFT + overlap-add
+// The spectrum source of the inverse's frame loop: seek(f) once per frame, in ascending order, then bin(m, k, a, b) once per
+// bin the thread owns (k = tid + 256 m for m = 0 .. 7; thread 0 also the Nyquist bin 2048 as m = 8, last): the two channels'
+// values. m is a constant of the unrolled loop, so a source may keep a state per owned bin in registers. The plain source
+// reads the rows of `ispec`.
 template <int C>
-__global__ __launch_bounds__(256) void wiener_istft_kernel(const WienerArgs p)
+struct PlainSpectrum
+{
+    const float2 *y0, *r0;
+    i64 plane;
+    __device__ PlainSpectrum(const WienerArgs &p, int src) : y0(p.ispec + (i64)src * C * p.plane), r0(nullptr), plane(p.plane) {}
+    __device__ __forceinline__ void seek(i64 f) { r0 = y0 + f * kWienerRow; }
+    __device__ __forceinline__ void bin(int, int k, float2 &a, float2 &b) const
+    {
+        a = r0[k], b = C == 2 ? r0[plane + k] : make_float2(0.f, 0.f);
+    }
+};
+
+template <int C, class Source>
+__device__ __forceinline__ void wiener_istft_body(const WienerArgs &p, Source &spectrum)
 {
     __shared__ float2 buf[FFT_N];
     __shared__ float2 ring[FFT_N]; // the four hops that still collect frames; position (1024 f + i) & 4095, each owned by the
@@ -117,19 +135,19 @@ __global__ __launch_bounds__(256) void wiener_istft_kernel(const WienerArgs p)
     }
     const i64 t0 = ch * kWienerChunk, t1 = min(p.T, t0 + kWienerChunk);
     const i64 fBeg = max((i64)0, t0 - 3), fEnd = ch == p.chunks - 1 ? p.T + 3 : t1;
-    const float2 *y0 = p.ispec + (i64)src * C * p.plane;
     __syncthreads();
     for (i64 f = fBeg; f < fEnd; ++f)
     {
         if (f < p.T)
         {
             // Z[k] = Y0[k] + i Y1[k] with the Hermitian extension; the imaginary parts of DC and Nyquist are ignored
-            const float2 *r0 = y0 + f * kWienerRow;
+            spectrum.seek(f);
 #pragma unroll
             for (int m = 0; m < 8; ++m)
             {
                 const int k = tid + 256 * m;
-                float2 a = r0[k], b = C == 2 ? r0[p.plane + k] : make_float2(0.f, 0.f);
+                float2 a, b;
+                spectrum.bin(m, k, a, b);
                 if (k == 0)
                     a.y = 0.f, b.y = 0.f;
                 buf[FSW(k)] = make_float2(a.x - b.y, a.y + b.x);
@@ -137,7 +155,11 @@ __global__ __launch_bounds__(256) void wiener_istft_kernel(const WienerArgs p)
                     buf[FSW(FFT_N - k)] = make_float2(a.x + b.y, b.x - a.y);
             }
             if (tid == 0)
-                buf[FSW(2048)] = make_float2(r0[2048].x, C == 2 ? r0[p.plane + 2048].x : 0.f);
+            {
+                float2 a, b;
+                spectrum.bin(8, 2048, a, b);
+                buf[FSW(2048)] = make_float2(a.x, b.x);
+            }
             __syncthreads();
             fft4096<+1>(buf, twS, tid); // ends with a barrier
 #pragma unroll
@@ -172,6 +194,13 @@ __global__ __launch_bounds__(256) void wiener_istft_kernel(const WienerArgs p)
         }
         __syncthreads(); // the image is rewritten by the next frame's spectrum
     }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void wiener_istft_kernel(const WienerArgs p)
+{
+    PlainSpectrum<C> spectrum(p, blockIdx.y);
+    wiener_istft_body<C>(p, spectrum);
 }
 
 } // namespace dmx

@@ -407,6 +407,53 @@ inline void demucs_dereverb(std::vector<StemTensor> &stems, const dereverb_optio
     }
 }
 
+// Phase-vocoder time stretch and pitch shift (dmx_stretch) of the stems of one track: the chosen
+// stems (`stems`: their indices; empty: all), in that order, as a tensor of dmx_stretch_length samples. set() fills the spec
+// from a tempo factor (0.25 .. 4) and a pitch change in semitones (-12 .. 12) through dmx_stretch_ratio.
+struct stretch_options
+{
+    int num = 1, den = 1, pitch_num = 1, pitch_den = 1;
+    std::vector<int> stems;
+    int device = 0;
+    void set(double tempo, double semitones)
+    {
+        int tn = 1, td = 1;
+        if (dmx_stretch_ratio(std::pow(2.0, semitones / 12.0), 512, &pitch_num, &pitch_den) != DMX_OK ||
+            dmx_stretch_ratio(tempo, 4096, &tn, &td) != DMX_OK)
+            detail::die("stretch_options::set");
+        // the rate tempo * pitch_den / pitch_num as a fraction of terms the library takes: the nearest one where the product's are too large
+        const int64_t n = (int64_t)tn * pitch_den, d = (int64_t)td * pitch_num;
+        if (n <= (1 << 20) && d <= (1 << 20))
+            num = (int)n, den = (int)d;
+        else if (dmx_stretch_ratio((double)n / (double)d, 1 << 20, &num, &den) != DMX_OK)
+            detail::die("stretch_options::set");
+    }
+};
+inline StemTensor demucs_stretch(const StemTensor &st, const stretch_options &o)
+{
+    const dmx_stretch_spec spec{o.num, o.den, o.pitch_num, o.pitch_den};
+    std::vector<int> pick = o.stems;
+    if (pick.empty())
+        for (int s = 0; s < st.S; ++s)
+            pick.push_back(s);
+    const int64_t n = st.n, m = dmx_stretch_length(&spec, n);
+    if (m < 0 || dmx_stretch_check(&spec, (int)pick.size(), 2, n) != DMX_OK)
+        detail::die("demucs_stretch");
+    std::vector<float> in(pick.size() * (size_t)(2 * n)), res(pick.size() * (size_t)(2 * m)); // planar, as the library takes them
+    for (size_t p = 0; p < pick.size(); ++p)
+        for (int c = 0; c < 2; ++c)
+            for (int64_t i = 0; i < n; ++i)
+                in[(p * 2 + (size_t)c) * (size_t)n + (size_t)i] = st(pick[p], c, i);
+    if (dmx_stretch(o.device, in.data(), (int)pick.size(), 2, n, &spec, res.data()) != DMX_OK)
+        detail::die("demucs_stretch");
+    StemTensor out((int)pick.size(), m);
+    for (size_t p = 0; p < pick.size(); ++p)
+        for (int c = 0; c < 2; ++c)
+            for (int64_t i = 0; i < m; ++i)
+                out((int)p, c, i) = res[(p * 2 + (size_t)c) * (size_t)m + (size_t)i];
+    return out;
+}
+
 // Log-mel features of the stems a batch call returned (dmx_logmel_from_stems): each stem is folded to
 // mono, converted rate -> spec.sr and sent through Whisper's / librosa's front end on the device. spec: from dmx_logmel_preset.
 struct MelTensor

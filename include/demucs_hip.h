@@ -698,6 +698,47 @@ extern "C"
     /* the same on host buffers: stems and out [n_sources][channels][n] */
     int dmx_dereverb(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_dereverb_spec *spec, float *out);
 
+    /* ---- Time stretch and pitch shift of the stems by the phase vocoder (csrc/stretch.hip; DESIGN.md section 2.22, restated in
+     * tests/stretch_spec.py; what librosa.phase_vocoder, effects.time_stretch and effects.pitch_shift compute). Stems x[j][c][n],
+     * J = 1 .. 8 of C = 1 | 2 channels and 2048 < n < 2^31 samples; every plane is treated on its own. The STFT is the Wiener
+     * stage's (fp32, complex64 D[a][k], T = 1 + n / 1024 frames; frames from T on read as zero). The rate is num / den (above 1:
+     * faster and shorter); the output has n' = ceil(n den / num) samples, 2048 < n' < 2^31, and T' = 1 + n' / 1024 frames. For
+     * output frame t: a = (t num) div den, alpha = ((t num) mod den) / den. In binary64, with unit(z) = z / |z| (1 where z = 0):
+     * ph[0] = unit(D[0]), ph[t + 1] = ph[t] unit(D[a + 1]) conj(unit(D[a])),
+     * Y[t] = ((1 - alpha) |D[a]| + alpha |D[a + 1]|) ph[t], rounded to complex64; Y goes through the Wiener stage's inverse to n'
+     * samples. Where pitch_num != pitch_den the converter of dmx_resample_device from rate pitch_num to rate pitch_den follows and
+     * leaves dmx_resample_length(n', pitch_num, pitch_den) samples: s semitones up at the tempo r are pitch_num / pitch_den ~
+     * 2^(s / 12) with num / den = r pitch_den / pitch_num. A fixed order everywhere: equal inputs, equal bits.
+     * Out of scope: phase locking and transient handling, other STFT sizes, more than 2 channels, the multi-track entry points. */
+    typedef struct dmx_stretch_spec
+    {
+        int num, den;             /* the rate, each in [1, 2^20], 1/4 <= num / den <= 4 */
+        int pitch_num, pitch_den; /* the converter behind the inverse, each in [1, 2^20]; equal: none */
+    } dmx_stretch_spec;
+    /* Pure host function; DMX_ERR_ARG with a message that names the field or argument (the converter's refusal of a ratio is
+     * passed on behind pitch_num / pitch_den). */
+    int dmx_stretch_check(const dmx_stretch_spec *spec, int n_sources, int channels, int64_t n);
+    /* the samples of an output plane for n samples in; -1 on a bad spec or n outside [0, 2^31). Pure host function. */
+    int64_t dmx_stretch_length(const dmx_stretch_spec *spec, int64_t n);
+    /* the bytes of d_work (csrc/stretch_plan.h: D over the track, a complex128 row per plane and chunk of 12 output frames, with
+     * a converter the stretched planes); -1 (and a message) where dmx_stretch_check fails. Pure host function. */
+    int64_t dmx_stretch_workspace_bytes(const dmx_stretch_spec *spec, int n_sources, int channels, int64_t n);
+    /* d_stems: planes source * channels + channel at plane_stride (>= n) floats; d_out: the same planes at out_stride
+     * (>= dmx_stretch_length) floats, not overlapping d_stems; d_work: work_bytes >= dmx_stretch_workspace_bytes, 256-byte
+     * aligned. Asynchronous on `stream` (the first call of a process with a new pitch ratio uploads its filter first). */
+    int dmx_stretch_device(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                           const dmx_stretch_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream);
+    /* measurement (tools/stretch_bench.py): the call above, synchronised, with the times of its stages between HIP events in
+     * ms[0 .. 4): forward STFT, phasor products + carry, fused vocoder and inverse, converter (0 where there is none) */
+    int dmx_stretch_device_timed(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                 const dmx_stretch_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes,
+                                 void *stream, float *ms);
+    /* the same on host buffers: stems [n_sources][channels][n], out [n_sources][channels][dmx_stretch_length] */
+    int dmx_stretch(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_stretch_spec *spec, float *out);
+    /* the fraction num / den nearest to `value` (in [1/1024, 1024]) with den <= max_den (1 .. 2^20); of two equally near, the
+     * smaller denominator. Exact in integers. Pure host function. */
+    int dmx_stretch_ratio(double value, int max_den, int *num, int *den);
+
     /* ---- Log-mel features of the stems (csrc/logmel.hip; DESIGN.md section 2.20, restated in tests/logmel_spec.py; the front
      * end of Whisper / WhisperX and of librosa.feature.melspectrogram + power_to_db). P planes of N fp32 samples at `sr`:
      * centred frames (reflect padding of n_fft / 2, periodic Hann window), S[f] = |sum_n w[n] x[n] e^{-2 pi i f n / n_fft}|^2 for
