@@ -14,16 +14,16 @@ NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
 QUIET := 2> >(grep -v "packed-fp32-ops' is not a recognized feature" >&2)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(NOPK)
 LIB := demucs_cpp_amd/lib/libdemucs_hip.so
-OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o loudness.o meters.o limiter.o bss.o wiener.o dereverb.o stretch.o logmel.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o loud_api.o analysis_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
+OBJS := $(addprefix build/,igemm.o igemm_split.o igemm_lin256.o dgemm.o dconv_row.o fft.o misc.o tracks.o attention.o attention_split.o resample.o pcm.o loudness.o meters.o limiter.o bss.o wiener.o dereverb.o stretch.o hpss.o logmel.o flac.o flac_in.o v3.o api.o exec.o tracks_exec.o codec_api.o loud_api.o analysis_api.o debug_api.o engine.o plan.o model_pack.o tracks_plan.o gemm_select.o)
 
 all: $(LIB) cli oracle interp op_step plan_harness chain_harness rates_harness att_harness flac_in_host flac_host loudness_host meters_host limiter_host harness micro
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/bss_plan.h $(CSRC)/wiener_plan.h $(CSRC)/dereverb_plan.h $(CSRC)/stretch_plan.h $(CSRC)/wiener_stft.h $(CSRC)/logmel_plan.h $(CSRC)/fft4096.h $(CSRC)/loud_chain.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_tiles.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/pcm_gather.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/bss_plan.h $(CSRC)/wiener_plan.h $(CSRC)/dereverb_plan.h $(CSRC)/stretch_plan.h $(CSRC)/hpss_plan.h $(CSRC)/wiener_stft.h $(CSRC)/logmel_plan.h $(CSRC)/fft4096.h $(CSRC)/loud_chain.h $(CSRC)/tp_phases.h $(CSRC)/plan.h $(CSRC)/gemm_tiles.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/igemm_common.h $(CSRC)/attention_common.h $(CSRC)/attention_select.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@ $(QUIET)
 # the limiter's products are separate roundings: contraction off for the whole file
 build/limiter.o: HIPFLAGS += -ffp-contract=off
-build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/bss_plan.h $(CSRC)/wiener_plan.h $(CSRC)/dereverb_plan.h $(CSRC)/stretch_plan.h $(CSRC)/logmel_plan.h $(CSRC)/loud_chain.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_tiles.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/stage_call.h $(CSRC)/tracks_plan.h include/demucs_hip.h
+build/%.o: $(CSRC)/%.cpp $(CSRC)/kernels.h $(CSRC)/loudness_plan.h $(CSRC)/meters_plan.h $(CSRC)/limiter_plan.h $(CSRC)/bss_plan.h $(CSRC)/wiener_plan.h $(CSRC)/dereverb_plan.h $(CSRC)/stretch_plan.h $(CSRC)/hpss_plan.h $(CSRC)/logmel_plan.h $(CSRC)/loud_chain.h $(CSRC)/plan.h $(CSRC)/plan_describe.h $(CSRC)/attention_select.h $(CSRC)/gemm_tiles.h $(CSRC)/gemm_select.h $(CSRC)/api_internal.h $(CSRC)/stage_call.h $(CSRC)/tracks_plan.h include/demucs_hip.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@ $(QUIET)
 
@@ -171,7 +171,7 @@ clean:
 # experiment builds: make variant NAME=timing FLAGS="-DDMX_TIMING -DDMX_PIN_LOADS=1"
 variant:
 	@mkdir -p build/$(NAME)
-	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc tracks attention attention_split resample pcm loudness meters limiter bss wiener dereverb stretch logmel flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) $$([ $$f = limiter ] && echo -ffp-contract=off) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
+	for f in igemm igemm_split igemm_lin256 dgemm dconv_row fft misc tracks attention attention_split resample pcm loudness meters limiter bss wiener dereverb stretch hpss logmel flac flac_in v3; do $(HIPCC) $(HIPFLAGS) $(FLAGS) $$([ $$f = limiter ] && echo -ffp-contract=off) -c $(CSRC)/$$f.hip -o build/$(NAME)/$$f.o & done; \
 	for f in api exec tracks_exec codec_api loud_api analysis_api debug_api engine plan model_pack tracks_plan gemm_select; do $(HIPCC) $(HIPFLAGS) $(FLAGS) -x hip -c $(CSRC)/$$f.cpp -o build/$(NAME)/$$f.o & done; wait
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o demucs_cpp_amd/lib/libdemucs_hip_$(NAME).so build/$(NAME)/*.o
 # one file rebuilt with other flags, the rest of the product's objects unchanged:

@@ -6,6 +6,7 @@
 //                         [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]
 //                         [--dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems NAMES]]
 //                         [--tempo R] [--pitch SEMITONES] [--stretch-stems NAMES]
+//                         [--hpss [--hpss-kernel H,P] [--hpss-margin H,P] [--hpss-power N] [--hpss-residual] [--hpss-stems NAMES]]
 //                         [--limit] [--limit-attack MS] [--limit-release MS]
 //                         <model> <out dir> <wav or flac file>...
 // An input whose content begins with "fLaC" (or an ID3v2 tag and "fLaC") is a FLAC file. When every input is a FLAC file
@@ -72,6 +73,13 @@
 //                            conversion by the nearest fraction to 2^(SEMITONES / 12) with a denominator up to 512
 //                            (dmx_stretch_ratio). --stretch-stems vocals,... (default: all; the others are written as they
 //                            are). Behind --wiener and --dereverb. Not together with --mel, PCM / FLAC / remix / loudness options.
+//   --hpss                   beside each float32 stem, its harmonic and its percussive part by median filtering (dmx_hpss; what
+//                            librosa.effects.hpss computes) as target_{i}_{name}.harmonic.wav and .percussive.wav:
+//                            --hpss-kernel H,P (the windows along time and frequency, odd, 3 .. 31, default 31,31),
+//                            --hpss-margin H,P (1 .. 100, default 1,1), --hpss-power N (1 .. 8, default 2), --hpss-residual
+//                            (what the two masks leave, as .residual.wav), --hpss-stems drums,... (default: all). Behind
+//                            --wiener and --dereverb. Not together with --tempo, --pitch, --mel, PCM / FLAC / remix / loudness
+//                            options or a FLAC-fed or resampled track: each is refused by name.
 //   --mel NAME               beside each float32 stem, its log-mel features as target_{i}_{name}.mel.npy: float32
 //                            [chunks][n_mels][frames] of the stem's mono fold at the preset's rate (dmx_logmel_from_stems; NAME:
 //                            whisper, whisper128 or librosa). Not together with PCM / FLAC / remix / loudness options for now.
@@ -106,6 +114,7 @@ using namespace demucscpp;
               << " [--wiener N [--wiener-residual]] [--mel whisper|whisper128|librosa]"
               << " [--dereverb [--dereverb-taps K] [--dereverb-delay D] [--dereverb-iters I] [--dereverb-stems vocals,...]]"
               << " [--tempo 0.25..4] [--pitch SEMITONES] [--stretch-stems vocals,...]"
+              << " [--hpss [--hpss-kernel H,P] [--hpss-margin H,P] [--hpss-power N] [--hpss-residual] [--hpss-stems drums,...]]"
               << " [--limit] [--limit-attack MS] [--limit-release MS] (--clip-mode limit: --limit without loudnorm)"
               << " <model file | ft model dir | file1,file2,...> <out dir> <wav file>..." << std::endl;
     exit(1);
@@ -169,6 +178,9 @@ int main(int argc, const char **argv)
     double tempo = 1.0, semitones = 0.0;
     bool with_stretch = false;
     std::string stretch_stems;
+    hpss_options hpss; // --hpss [--hpss-kernel H,P] [--hpss-margin H,P] [--hpss-power N] [--hpss-residual] [--hpss-stems a,b]
+    bool with_hpss = false, hpss_opts = false;
+    std::string hpss_stems;
     int a = 1;
     for (; a < argc && std::string(argv[a]).rfind("--", 0) == 0; a += 2)
     {
@@ -182,6 +194,13 @@ int main(int argc, const char **argv)
         if (opt == "--dereverb") // no value; its own options below need it, checked behind the loop
         {
             with_dereverb = true;
+            --a;
+            continue;
+        }
+        if (opt == "--hpss" || opt == "--hpss-residual") // no value; --hpss-residual needs --hpss, checked behind the loop
+        {
+            (opt == "--hpss" ? with_hpss : hpss.residual) = true;
+            hpss_opts |= opt != "--hpss";
             --a;
             continue;
         }
@@ -264,6 +283,39 @@ int main(int argc, const char **argv)
         if (opt == "--stretch-stems")
         {
             stretch_stems = val;
+            continue;
+        }
+        if (opt == "--hpss-kernel" || opt == "--hpss-margin") // two values, H,P
+        {
+            const bool windows = opt == "--hpss-kernel";
+            char *mid = nullptr, *end = nullptr;
+            const double h = std::strtod(val.c_str(), &mid), q = *mid == ',' ? std::strtod(mid + 1, &end) : 0.0;
+            auto good = [&](double v) { return windows ? v >= 3 && v <= 31 && v == std::floor(v) && std::fmod(v, 2.0) == 1.0 : v >= 1.0 && v <= 100.0; };
+            if (mid == val.c_str() || *mid != ',' || end == mid + 1 || *end || !good(h) || !good(q))
+            {
+                std::cerr << opt << " " << val << ": expected H,P, each " << (windows ? "odd and 3 .. 31" : "1 .. 100") << std::endl;
+                usage(argv[0]);
+            }
+            if (windows)
+                hpss.kernel_h = (int)h, hpss.kernel_p = (int)q;
+            else
+                hpss.margin_h = h, hpss.margin_p = q;
+            hpss_opts = true;
+            continue;
+        }
+        if (opt == "--hpss-power")
+        {
+            if (!parse_int(val, 1, 8, hpss.power))
+            {
+                std::cerr << "--hpss-power " << val << ": expected 1 .. 8" << std::endl;
+                usage(argv[0]);
+            }
+            hpss_opts = true;
+            continue;
+        }
+        if (opt == "--hpss-stems")
+        {
+            hpss_stems = val, hpss_opts = true;
             continue;
         }
         if (opt == "--wiener")
@@ -446,6 +498,25 @@ int main(int argc, const char **argv)
     {
         std::cerr << "--tempo and --pitch treat the float32 stems: not together with --mel, PCM, FLAC, remix or loudness options for now" << std::endl;
         usage(argv[0]);
+    }
+    if (hpss_opts && !with_hpss)
+    {
+        std::cerr << "--hpss-kernel, --hpss-margin, --hpss-power, --hpss-residual and --hpss-stems need --hpss" << std::endl;
+        usage(argv[0]);
+    }
+    if (with_hpss) // what is not wired up behind or beside it is refused by name
+    {
+        const std::pair<bool, const char *> others[] = {
+            {with_stretch, "--tempo / --pitch"}, {with_mel, "--mel"}, {flac, "--flac"},
+            {loud_mode >= 0, "--loudnorm / --loudnorm-each / --loudness"}, {limit, "--limit"}, {!remix_text.empty(), "--remix"},
+            {!two_stems.empty(), "--two-stems"}, {other_method >= 0, "--other-method"},
+            {with_out_opts, "the PCM output options (--int16, --int24, --float32, --clip-mode, --max-peak)"}};
+        for (const auto &o : others)
+            if (o.first)
+            {
+                std::cerr << "--hpss splits the float32 stems: not together with " << o.second << " for now" << std::endl;
+                usage(argv[0]);
+            }
     }
     if (with_mel && (with_out_opts || flac || limit || loud_mode >= 0 || !remix_text.empty() || !two_stems.empty() || other_method >= 0))
     {
@@ -662,6 +733,11 @@ int main(int argc, const char **argv)
         std::cerr << "--tempo, --pitch: not on a FLAC-fed or resampled track for now" << std::endl;
         usage(argv[0]);
     }
+    if (with_hpss && (flac_in || any_rate))
+    {
+        std::cerr << "--hpss: not on a FLAC-fed or resampled track (DMX_RESAMPLE) for now" << std::endl;
+        usage(argv[0]);
+    }
     if (with_wiener && (flac_in || any_rate))
     {
         std::cerr << "--wiener: not on a FLAC-fed or resampled track for now" << std::endl;
@@ -820,6 +896,35 @@ int main(int argc, const char **argv)
         for (const StemTensor &st : outs)
             stretched.push_back(demucs_stretch(st, stretch));
     }
+    std::vector<StemTensor> split;    // behind --wiener and --dereverb (dmx_hpss): per track the chosen stems' kinds
+    std::vector<int> hpss_slot(6, -1); // where a stem lies in them; -1: not split
+    const int hpss_kinds = hpss.residual ? 3 : 2;
+    if (with_hpss)
+    {
+        const int S = outs.empty() ? 0 : outs[0].S;
+        for (size_t at = 0; at < hpss_stems.size();)
+        {
+            const size_t end = std::min(hpss_stems.find(',', at), hpss_stems.size());
+            const std::string name = hpss_stems.substr(at, end - at);
+            int s = 0;
+            while (s < S && name != names[s])
+                ++s;
+            if (s == S)
+            {
+                std::cerr << "--hpss-stems " << hpss_stems << ": " << name << " is not a source of this model" << std::endl;
+                return 1;
+            }
+            hpss.stems.push_back(s);
+            at = end + 1;
+        }
+        for (int s = 0; s < S; ++s)
+            if (hpss.stems.empty())
+                hpss_slot[(size_t)s] = s;
+            else if (std::find(hpss.stems.begin(), hpss.stems.end(), s) != hpss.stems.end())
+                hpss_slot[(size_t)s] = (int)(std::find(hpss.stems.begin(), hpss.stems.end(), s) - hpss.stems.begin());
+        for (const StemTensor &st : outs)
+            split.push_back(demucs_hpss(st, hpss));
+    }
     for (int f = 0; f < n_files; ++f)
     {
         const StereoMatrix &audio = tracks[(size_t)f];
@@ -936,6 +1041,23 @@ int main(int argc, const char **argv)
             {
                 std::cerr << "Error writing " << p_target << std::endl;
                 exit(1);
+            }
+            static const char *kinds[3] = {"harmonic", "percussive", "residual"};
+            for (int kind = 0; hpss_slot[(size_t)target] >= 0 && kind < hpss_kinds; ++kind)
+            {
+                auto p_kind = p / ("target_" + std::to_string(target) + "_" + names[target] + "." + kinds[kind] + ".wav");
+                std::cout << "Writing wav file " << p_kind << std::endl;
+                const int layer = hpss_slot[(size_t)target] * hpss_kinds + kind;
+                for (int64_t i = 0; i < (int64_t)audio.cols(); ++i)
+                {
+                    wave[(size_t)(2 * i)] = split[(size_t)f](layer, 0, i);
+                    wave[(size_t)(2 * i + 1)] = split[(size_t)f](layer, 1, i);
+                }
+                if (!wavio::write_audio_file(wave.data(), audio.cols(), p_kind.string()))
+                {
+                    std::cerr << "Error writing " << p_kind << std::endl;
+                    exit(1);
+                }
             }
         }
     }

@@ -56,6 +56,8 @@ EXPORTS = [
     "dmx_dereverb_check", "dmx_dereverb_workspace_bytes", "dmx_dereverb_device", "dmx_dereverb_device_timed", "dmx_dereverb",
     "dmx_stretch_check", "dmx_stretch_length", "dmx_stretch_workspace_bytes", "dmx_stretch_device", "dmx_stretch_device_timed", "dmx_stretch",
     "dmx_stretch_ratio",
+    "dmx_hpss_check", "dmx_hpss_workspace_bytes", "dmx_hpss_geometry", "dmx_hpss_device", "dmx_hpss_device_timed", "dmx_hpss",
+    "dmx_hpss_filter_device",
     "dmx_logmel_check", "dmx_logmel_preset", "dmx_logmel_frames", "dmx_logmel_filters", "dmx_logmel_geometry", "dmx_logmel_workspace_bytes",
     "dmx_logmel_device", "dmx_logmel_device_timed", "dmx_logmel", "dmx_logmel_from_stems", "dmx_npy_write_f32",
 ]
@@ -252,6 +254,14 @@ def lib():
         L.dmx_stretch_device_timed.argtypes = L.dmx_stretch_device.argtypes + [vp]
         L.dmx_stretch.argtypes = [ci, vp, ci, ci, i64, vp, vp]
         L.dmx_stretch_ratio.argtypes = [ctypes.c_double, ci, vp, vp]
+        L.dmx_hpss_check.argtypes = [vp, ci, ci, i64]
+        L.dmx_hpss_workspace_bytes.argtypes = [vp, ci, ci, i64]
+        L.dmx_hpss_workspace_bytes.restype = i64
+        L.dmx_hpss_geometry.argtypes = [vp, vp]
+        L.dmx_hpss_device.argtypes = [ci, vp, ci, ci, i64, i64, vp, vp, i64, vp, i64, vp]
+        L.dmx_hpss_device_timed.argtypes = L.dmx_hpss_device.argtypes + [vp]
+        L.dmx_hpss.argtypes = [ci, vp, ci, ci, i64, vp, vp]
+        L.dmx_hpss_filter_device.argtypes = [ci, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp]
         L.dmx_logmel_check.argtypes = [vp, i64]
         L.dmx_logmel_preset.argtypes = [ctypes.c_char_p, vp]
         L.dmx_logmel_frames.argtypes = [vp, i64, vp, vp]
@@ -1336,6 +1346,58 @@ def stretch(stems: np.ndarray, spec: StretchSpec, device: int = 0) -> np.ndarray
     out = np.empty((J, C, stretch_length(spec, n)), np.float32)
     _chk(lib().dmx_stretch(device, stems.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
     return out
+
+
+HPSS_MASKS, HPSS_MEDIANS = 0, 1
+
+
+class HpssSpec(ctypes.Structure):
+    """dmx_hpss_spec: the median windows along time and frequency (odd, 3 .. 31), the power of the soft masks (1 .. 8), the
+    margins (1 .. 100) and whether a residual is a third output; the defaults are librosa's"""
+    _fields_ = [("kernel_h", ctypes.c_int), ("kernel_p", ctypes.c_int), ("power", ctypes.c_int), ("residual", ctypes.c_int),
+                ("margin_h", ctypes.c_double), ("margin_p", ctypes.c_double)]
+
+    def __init__(self, kernel_h=31, kernel_p=31, power=2, margin_h=1.0, margin_p=1.0, residual=0):
+        super().__init__(int(kernel_h), int(kernel_p), int(power), int(residual), float(margin_h), float(margin_p))
+
+
+def hpss_check(spec: Optional[HpssSpec], n_sources: int, channels: int, n: int):
+    """validates an HpssSpec and a shape (dmx_hpss_check; no GPU); raises DmxError naming the field"""
+    _chk(lib().dmx_hpss_check(None if spec is None else ctypes.byref(spec), int(n_sources), int(channels), int(n)))
+
+
+def hpss_workspace_bytes(spec: HpssSpec, n_sources: int, channels: int, n: int) -> int:
+    return lib().dmx_hpss_workspace_bytes(ctypes.byref(spec), int(n_sources), int(channels), int(n))
+
+
+def hpss_geometry():
+    """(tile_frames, tile_bins) of the filter kernel (dmx_hpss_geometry; no GPU)"""
+    tf, tb = ctypes.c_int(0), ctypes.c_int(0)
+    _chk(lib().dmx_hpss_geometry(ctypes.byref(tf), ctypes.byref(tb)))
+    return tf.value, tb.value
+
+
+def hpss(stems: np.ndarray, spec: Optional[HpssSpec] = None, device: int = 0) -> np.ndarray:
+    """harmonic/percussive split (dmx_hpss): stems (J, C, n) float32 -> (J, K, C, n) float32, K = 2 + residual: harmonic,
+    percussive, residual"""
+    spec = spec or HpssSpec()
+    stems = np.ascontiguousarray(stems, np.float32)
+    assert stems.ndim == 3, "expected stems (J, C, n)"
+    J, C, n = stems.shape
+    hpss_check(spec, J, C, n)
+    out = np.empty((J, 2 + spec.residual, C, n), np.float32)
+    _chk(lib().dmx_hpss(device, stems.ctypes.data, J, C, n, ctypes.byref(spec), out.ctypes.data))
+    return out
+
+
+def hpss_filter(d_spec: int, planes: int, frames: int, bins: int, row: int, spec: Optional[HpssSpec], what: int, d_a: int, d_b: int,
+                stream=None, device: int = 0):
+    """the filter kernel alone (dmx_hpss_filter_device) on device addresses (e.g. torch.Tensor.data_ptr()): d_spec complex64
+    [planes][frames][row] whose columns [0, bins) are the plane -> d_a, d_b float32 [planes][frames][row]: M_h and M_p
+    (HPSS_MASKS) or H and P (HPSS_MEDIANS); columns from `bins` on are not written. Asynchronous on `stream`."""
+    spec = spec or HpssSpec()
+    _chk(lib().dmx_hpss_filter_device(device, d_spec, int(planes), int(frames), int(bins), int(row), ctypes.byref(spec), int(what), d_a, d_b,
+                                      stream))
 
 
 MEL_SLANEY, MEL_HTK = 0, 1

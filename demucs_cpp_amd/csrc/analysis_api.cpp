@@ -1,6 +1,6 @@
 // analysis_api.cpp — what is computed on finished stems, as entry points of their own: BSS Eval v4 (bss.hip), the Wiener
-// post-filter (wiener.hip), the WPE de-reverberation (dereverb.hip), the time stretch and pitch shift (stretch.hip), the log-mel
-// features (logmel.hip) and the .npy writer of their results.
+// post-filter (wiener.hip), the WPE de-reverberation (dereverb.hip), the time stretch and pitch shift (stretch.hip), the
+// harmonic/percussive split (hpss.hip), the log-mel features (logmel.hip) and the .npy writer of their results.
 #include "api_internal.h"
 
 #include <algorithm>
@@ -462,6 +462,134 @@ extern "C" int dmx_stretch(int device, const float *stems, int n_sources, int ch
     DMXCHK(stretch_device(fn, device, dIn, n_sources, channels, n, n, spec, dOut, nOut, dWork, workBytes, nullptr, nullptr));
     DMXCHK(t.wait());
     return t.down(out, dOut, sizeof(float) * planes * (size_t)nOut);
+}
+
+// --------------------------------------------------------------------------- harmonic/percussive split (hpss.hip)
+static HpssSpec hpss_spec(const dmx_hpss_spec *s) { return HpssSpec{s->kernel_h, s->kernel_p, s->power, s->residual, s->margin_h, s->margin_p}; }
+static int hpss_spec_check(const char *fn, const dmx_hpss_spec *spec)
+{
+    if (!spec)
+        return fail(DMX_ERR_ARG, "%s: null spec pointer", fn);
+    const std::pair<const char *, int> windows[] = {{"kernel_h", spec->kernel_h}, {"kernel_p", spec->kernel_p}};
+    for (const auto &w : windows)
+        if (!hpss_kernel_ok(w.second))
+            return fail(DMX_ERR_ARG, "%s: hpss spec: %s %d is not odd and in [3, %d]", fn, w.first, w.second, kHpssMaxKernel);
+    if (spec->power < 1 || spec->power > kHpssMaxPower)
+        return fail(DMX_ERR_ARG, "%s: hpss spec: power %d is not in [1, %d]", fn, spec->power, kHpssMaxPower);
+    const std::pair<const char *, double> margins[] = {{"margin_h", spec->margin_h}, {"margin_p", spec->margin_p}};
+    for (const auto &m : margins)
+        if (!hpss_margin_ok(m.second))
+            return fail(DMX_ERR_ARG, "%s: hpss spec: %s %g is not in [1, %g]", fn, m.first, m.second, kHpssMaxMargin);
+    if (spec->residual != 0 && spec->residual != 1)
+        return fail(DMX_ERR_ARG, "%s: hpss spec: residual %d is not 0 or 1", fn, spec->residual);
+    return DMX_OK;
+}
+static int hpss_check(const char *fn, const dmx_hpss_spec *spec, int J, int C, int64_t n)
+{
+    DMXCHK(hpss_spec_check(fn, spec));
+    if (J < 1 || J > kHpssMaxSources)
+        return fail(DMX_ERR_ARG, "%s: n_sources %d is not in [1, %d]", fn, J, kHpssMaxSources);
+    if (C != 1 && C != 2)
+        return fail(DMX_ERR_ARG, "%s: channels %d is not 1 or 2", fn, C);
+    if (!hpss_shape_ok(J, C, n))
+        return fail(DMX_ERR_ARG, "%s: n %lld is not in (%d, 2^31)", fn, (long long)n, kWienerPad);
+    return DMX_OK;
+}
+extern "C" int dmx_hpss_check(const dmx_hpss_spec *spec, int n_sources, int channels, int64_t n)
+{
+    return hpss_check("dmx_hpss_check", spec, n_sources, channels, n);
+}
+extern "C" int64_t dmx_hpss_workspace_bytes(const dmx_hpss_spec *spec, int n_sources, int channels, int64_t n)
+{
+    if (hpss_check("dmx_hpss_workspace_bytes", spec, n_sources, channels, n) != DMX_OK)
+        return -1;
+    return hpss_workspace_bytes(n_sources, channels, n);
+}
+extern "C" int dmx_hpss_geometry(int *tile_frames, int *tile_bins)
+{
+    DMXCHK(first_null("dmx_hpss_geometry", {{"tile_frames", tile_frames}, {"tile_bins", tile_bins}}));
+    *tile_frames = kHpssTileFrames, *tile_bins = kHpssTileBins;
+    return DMX_OK;
+}
+
+extern "C" int dmx_hpss_filter_device(int device, const void *d_spec, int planes, int frames, int bins, int row, const dmx_hpss_spec *spec,
+                                      int what, float *d_a, float *d_b, void *stream)
+{
+    const char *fn = "dmx_hpss_filter_device";
+    DMXCHK(hpss_spec_check(fn, spec));
+    if (!hpss_filter_shape_ok(planes, frames, bins, row))
+        return fail(DMX_ERR_ARG, "%s: planes = %d, frames = %d, bins = %d, row = %d (1 <= planes <= %d, 1 <= frames <= %d, 1 <= bins <= row <= %d)",
+                    fn, planes, frames, bins, row, kHpssMaxPlanes, kHpssMaxFrames, kHpssMaxRow);
+    if (what != DMX_HPSS_MASKS && what != DMX_HPSS_MEDIANS)
+        return fail(DMX_ERR_ARG, "%s: what %d is not DMX_HPSS_MASKS or DMX_HPSS_MEDIANS", fn, what);
+    DMXCHK(first_null(fn, {{"d_spec", d_spec}, {"d_a", d_a}, {"d_b", d_b}}));
+    if (((uintptr_t)d_spec & 7) != 0 || (((uintptr_t)d_a | (uintptr_t)d_b) & 3) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_spec must be 8-byte aligned, d_a and d_b 4-byte", fn);
+    HIPCHK(hipSetDevice(device));
+    launch_hpss_filter((const float2 *)d_spec, planes, frames, bins, row, hpss_spec(spec), what, d_a, d_b, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+// marks: null, or 4 events around the stages
+static int hpss_device(const char *fn, int device, const float *d_stems, int J, int C, int64_t n, int64_t plane_stride, const dmx_hpss_spec *spec,
+                       float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream, hipEvent_t *marks)
+{
+    DMXCHK(hpss_check(fn, spec, J, C, n));
+    if (plane_stride < n || out_stride < n)
+        return fail(DMX_ERR_ARG, "%s: n = %lld, plane_stride = %lld, out_stride = %lld (n <= plane_stride, n <= out_stride)", fn, (long long)n,
+                    (long long)plane_stride, (long long)out_stride);
+    DMXCHK(first_null(fn, {{"d_stems", d_stems}, {"d_out", d_out}, {"d_work", d_work}}));
+    if ((((uintptr_t)d_stems | (uintptr_t)d_out) & 3) != 0 || ((uintptr_t)d_work & 255) != 0)
+        return fail(DMX_ERR_ARG, "%s: d_stems and d_out must be 4-byte aligned, d_work 256-byte", fn);
+    const int64_t need = hpss_workspace_bytes(J, C, n);
+    if (work_bytes < need)
+        return fail(DMX_ERR_ARG, "%s: work_bytes %lld is below dmx_hpss_workspace_bytes = %lld", fn, (long long)work_bytes, (long long)need);
+    HIPCHK(hipSetDevice(device));
+    const HpssJob job{d_stems, d_out, J, C, hpss_spec(spec), n, plane_stride, out_stride, (unsigned char *)d_work};
+    launch_hpss(job, (hipStream_t)stream, marks);
+    HIPCHK(hipGetLastError());
+    return DMX_OK;
+}
+
+extern "C" int dmx_hpss_device(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                               const dmx_hpss_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream)
+{
+    return hpss_device("dmx_hpss_device", device, d_stems, n_sources, channels, n, plane_stride, spec, d_out, out_stride, d_work, work_bytes, stream,
+                       nullptr);
+}
+
+extern "C" int dmx_hpss_device_timed(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                                     const dmx_hpss_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream,
+                                     float *ms)
+{
+    const char *fn = "dmx_hpss_device_timed";
+    float gaps[3];
+    DMXCHK(timed_call<4>(fn, device, ms, gaps, [&](hipEvent_t *marks) {
+        return hpss_device(fn, device, d_stems, n_sources, channels, n, plane_stride, spec, d_out, out_stride, d_work, work_bytes, stream, marks);
+    }));
+    std::copy(gaps, gaps + 3, ms);
+    return DMX_OK;
+}
+
+extern "C" int dmx_hpss(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_hpss_spec *spec, float *out)
+{
+    const char *fn = "dmx_hpss";
+    DMXCHK(hpss_check(fn, spec, n_sources, channels, n));
+    DMXCHK(first_null(fn, {{"stems", stems}, {"out", out}}));
+    HIPCHK(hipSetDevice(device));
+    const size_t planes = (size_t)n_sources * (size_t)channels, kinds = (size_t)(2 + spec->residual);
+    const int64_t workBytes = hpss_workspace_bytes(n_sources, channels, n);
+    HostTrip t(fn);
+    float *dIn, *dOut;
+    void *dWork;
+    DMXCHK(t.alloc(&dIn, sizeof(float) * planes * (size_t)n));
+    DMXCHK(t.alloc(&dOut, sizeof(float) * planes * kinds * (size_t)n));
+    DMXCHK(t.alloc(&dWork, (size_t)workBytes));
+    DMXCHK(t.up(dIn, stems, sizeof(float) * planes * (size_t)n));
+    DMXCHK(hpss_device(fn, device, dIn, n_sources, channels, n, n, spec, dOut, n, dWork, workBytes, nullptr, nullptr));
+    DMXCHK(t.wait());
+    return t.down(out, dOut, sizeof(float) * planes * kinds * (size_t)n);
 }
 
 // --------------------------------------------------------------------------- log-mel features (logmel.hip)

@@ -9,6 +9,7 @@
 #include "wiener_plan.h"
 #include "dereverb_plan.h"
 #include "stretch_plan.h"
+#include "hpss_plan.h"
 #include "logmel_plan.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -554,6 +555,24 @@ struct StretchJob
     unsigned char *work;
 };
 void launch_stretch(const StretchJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
+// ---- harmonic/percussive split (hpss.hip; specification: DESIGN.md section 2.23, restated in tests/hpss_spec.py) ----
+// (the limits, the tile and the workspace: hpss_plan.h)
+// the filter kernel alone: D complex64 [planes][frames][row] -> A, B fp32 [planes][frames][row], columns [0, bins); what:
+// kHpssMasks (M_h, M_p) or kHpssMedians (H, P)
+void launch_hpss_filter(const float2 *D, int planes, int frames, int bins, int row, const HpssSpec &spec, int what, float *A, float *B,
+                        hipStream_t s);
+// x: J C planar fp32 planes of n samples at `stride`; out: the planes ((j K) + kind) C + c at outStride, K = 2 + residual.
+// marks: NULL, or 4 events around the stages (forward STFT, filter, the inverses)
+struct HpssJob
+{
+    const float *x;
+    float *out;
+    int J, C;
+    HpssSpec spec;
+    i64 n, stride, outStride;
+    unsigned char *work;
+};
+void launch_hpss(const HpssJob &job, hipStream_t s, hipEvent_t *marks = nullptr);
 // ---- log-mel features (logmel.hip; specification: DESIGN.md section 2.20, restated in tests/logmel_spec.py) ----
 // (chunks, frames, the tile and the workspace: logmel_plan.h)
 // x: `planes` fp32 planes of n samples, plane p at p * stride; out: [planes][chunks][n_mels][frames] floats; work: the

@@ -10,7 +10,8 @@
 //                         planes at once, the windowed frames go to a ring of four hops in LDS, each finished hop is divided by
 //                         its window-square sum and written; the frames never reach HBM. Chunks start 3 frames early, so every
 //                         hop is summed in frame order whatever the cut. Its text is wiener_istft_body, whose frame loop takes
-//                         the spectrum from a source: PlainSpectrum here, the phase vocoder's in stretch.hip.
+//                         the spectrum from a source: PlainSpectrum here, the phase vocoder's in stretch.hip, the masked
+//                         spectrum of hpss.hip, which also writes several kinds of output per source.
 #pragma once
 #include "kernels.h"
 #include "fft4096.h"
@@ -101,7 +102,8 @@ __global__ __launch_bounds__(256) void wiener_stft_kernel(const WienerArgs p)
 // The spectrum source of the inverse's frame loop: seek(f) once per frame, in ascending order, then bin(m, k, a, b) once per
 // bin the thread owns (k = tid + 256 m for m = 0 .. 7; thread 0 also the Nyquist bin 2048 as m = 8, last): the two channels'
 // values. m is a constant of the unrolled loop, so a source may keep a state per owned bin in registers. The plain source
-// reads the rows of `ispec`.
+// reads the rows of `ispec`. Where a stage leaves `kinds` outputs per source, the call for kind `kind` writes the planes
+// (src kinds + kind) C + channel; the defaults are the one output per source of the other stages.
 template <int C>
 struct PlainSpectrum
 {
@@ -116,13 +118,13 @@ struct PlainSpectrum
 };
 
 template <int C, class Source>
-__device__ __forceinline__ void wiener_istft_body(const WienerArgs &p, Source &spectrum)
+__device__ __forceinline__ void wiener_istft_body(const WienerArgs &p, Source &spectrum, int kinds = 1, int kind = 0)
 {
     __shared__ float2 buf[FFT_N];
     __shared__ float2 ring[FFT_N]; // the four hops that still collect frames; position (1024 f + i) & 4095, each owned by the
                                    // thread i & 255 in every frame: no barrier between the add and the emit
     __shared__ float2 twS[2048];
-    const int tid = threadIdx.x, src = blockIdx.y;
+    const int tid = threadIdx.x, src = blockIdx.y * kinds + kind; // the first output plane is src C
     const i64 ch = blockIdx.x;
     for (int k = tid; k < 2048; k += 256)
         twS[k] = p.tw[k];

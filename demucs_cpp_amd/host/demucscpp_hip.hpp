@@ -454,6 +454,43 @@ inline StemTensor demucs_stretch(const StemTensor &st, const stretch_options &o)
     return out;
 }
 
+// Median-filter harmonic/percussive split (dmx_hpss) of the stems of one track: for the chosen stems
+// (`stems`: their indices; empty: all), in that order, a tensor of K = 2 + residual layers each, layer p K + kind with kind 0
+// harmonic, 1 percussive, 2 residual.
+struct hpss_options
+{
+    int kernel_h = 31, kernel_p = 31, power = 2;
+    double margin_h = 1.0, margin_p = 1.0;
+    bool residual = false;
+    std::vector<int> stems;
+    int device = 0;
+};
+inline StemTensor demucs_hpss(const StemTensor &st, const hpss_options &o)
+{
+    const dmx_hpss_spec spec{o.kernel_h, o.kernel_p, o.power, o.residual ? 1 : 0, o.margin_h, o.margin_p};
+    std::vector<int> pick = o.stems;
+    if (pick.empty())
+        for (int s = 0; s < st.S; ++s)
+            pick.push_back(s);
+    const int64_t n = st.n;
+    const size_t K = o.residual ? 3 : 2;
+    if (dmx_hpss_check(&spec, (int)pick.size(), 2, n) != DMX_OK)
+        detail::die("demucs_hpss");
+    std::vector<float> in(pick.size() * (size_t)(2 * n)), res(pick.size() * K * (size_t)(2 * n)); // planar, as the library takes them
+    for (size_t p = 0; p < pick.size(); ++p)
+        for (int c = 0; c < 2; ++c)
+            for (int64_t i = 0; i < n; ++i)
+                in[(p * 2 + (size_t)c) * (size_t)n + (size_t)i] = st(pick[p], c, i);
+    if (dmx_hpss(o.device, in.data(), (int)pick.size(), 2, n, &spec, res.data()) != DMX_OK)
+        detail::die("demucs_hpss");
+    StemTensor out((int)(pick.size() * K), n);
+    for (size_t p = 0; p < pick.size() * K; ++p)
+        for (int c = 0; c < 2; ++c)
+            for (int64_t i = 0; i < n; ++i)
+                out((int)p, c, i) = res[(p * 2 + (size_t)c) * (size_t)n + (size_t)i];
+    return out;
+}
+
 // Log-mel features of the stems a batch call returned (dmx_logmel_from_stems): each stem is folded to
 // mono, converted rate -> spec.sr and sent through Whisper's / librosa's front end on the device. spec: from dmx_logmel_preset.
 struct MelTensor

@@ -739,6 +739,60 @@ extern "C"
      * smaller denominator. Exact in integers. Pure host function. */
     int dmx_stretch_ratio(double value, int max_den, int *num, int *den);
 
+    /* ---- Harmonic/percussive split of the stems by median filtering (csrc/hpss.hip; DESIGN.md section 2.23, restated in
+     * tests/hpss_spec.py; Fitzgerald 2010 with Driedger's margins, what librosa.decompose.hpss and effects.hpss compute). Stems
+     * x[j][c][n], J = 1 .. 8 of C = 1 | 2 channels and 2048 < n < 2^31 samples; every plane is treated on its own. The STFT is
+     * the Wiener stage's (fp32, complex64 D[t][k], T = 1 + n / 1024 frames, 2049 bins). S = fp32(sqrt(re^2 + im^2)) with the
+     * squares, the sum and the root in binary64; H[t][k] is the median of S[t - h .. t + h][k] (kernel_h = 2 h + 1) and P[t][k]
+     * the median of S[t][k - p .. k + p] (kernel_p = 2 p + 1), an index outside the plane folded by half-sample symmetric
+     * reflection (d c b a | a b c d | d c b a; SciPy's `reflect`, NumPy's `symmetric`), as often as it takes. In binary64
+     * without contraction softmask(x, r) is a / (a + b) with z = max(x, r), a = (x / z)^power, b = (r / z)^power by repeated
+     * multiplication, and where z < FLT_MIN 0.5 if both margins are 1, else 0. M_h = softmask(H, margin_h P) and
+     * M_p = softmask(P, margin_p H), each rounded once to fp32. The outputs are the Wiener stage's inverse of M_h D (harmonic),
+     * of M_p D (percussive) and, with `residual`, of ((1 - M_h) - M_p) D, the products in fp32. A fixed order everywhere: equal
+     * inputs, equal bits. The masks over frames of digital silence are decided by the forward transform's rounding residue and
+     * multiply values at that level.
+     * Out of scope: hard masks (an infinite power), windows above 31, other STFT sizes, more than 2 channels, the multi-track
+     * entry points, an HPSS-aware tempo change. */
+    typedef struct dmx_hpss_spec
+    {
+        int kernel_h, kernel_p;    /* the windows along time and along frequency: odd, 3 .. 31 (librosa: 31) */
+        int power;                 /* 1 .. 8 (librosa: 2) */
+        int residual;              /* 0 | 1: a third output, what the two masks leave */
+        double margin_h, margin_p; /* 1 .. 100 (librosa: 1) */
+    } dmx_hpss_spec;
+    enum
+    {
+        DMX_HPSS_MASKS = 0,  /* dmx_hpss_filter_device writes M_h and M_p */
+        DMX_HPSS_MEDIANS = 1 /* ... H and P */
+    };
+    /* Pure host function; DMX_ERR_ARG with a message that names the field or argument. */
+    int dmx_hpss_check(const dmx_hpss_spec *spec, int n_sources, int channels, int64_t n);
+    /* the bytes of d_work (csrc/hpss_plan.h: D over the track and two fp32 mask planes per plane); -1 (and a message) where
+     * dmx_hpss_check fails. Pure host function. */
+    int64_t dmx_hpss_workspace_bytes(const dmx_hpss_spec *spec, int n_sources, int channels, int64_t n);
+    /* the tile of the filter kernel, for tests and callers that size their spectra. Pure host function. */
+    int dmx_hpss_geometry(int *tile_frames, int *tile_bins);
+    /* d_stems: planes source * channels + channel at plane_stride (>= n) floats; d_out: the planes
+     * ((source * K) + kind) * channels + channel at out_stride (>= n) floats, K = 2 + residual, kind 0 harmonic, 1 percussive,
+     * 2 residual, not overlapping d_stems; d_work: work_bytes >= dmx_hpss_workspace_bytes, 256-byte aligned. Asynchronous on
+     * `stream`. */
+    int dmx_hpss_device(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                        const dmx_hpss_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream);
+    /* measurement (tools/hpss_bench.py): the call above, synchronised, with the times of its stages between HIP events in
+     * ms[0 .. 3): forward STFT, the filter kernel, the inverses */
+    int dmx_hpss_device_timed(int device, const float *d_stems, int n_sources, int channels, int64_t n, int64_t plane_stride,
+                              const dmx_hpss_spec *spec, float *d_out, int64_t out_stride, void *d_work, int64_t work_bytes, void *stream,
+                              float *ms);
+    /* the same on host buffers: stems [n_sources][channels][n], out [n_sources][K][channels][n] */
+    int dmx_hpss(int device, const float *stems, int n_sources, int channels, int64_t n, const dmx_hpss_spec *spec, float *out);
+    /* The filter kernel alone, on spectra of the caller: d_spec complex64 [planes][frames][row], 8-byte aligned, of which the
+     * columns [0, bins) are the plane (1 <= bins <= row <= 2^20, 1 <= frames <= 2^24, 1 <= planes <= 65535); d_a and d_b fp32
+     * [planes][frames][row]: with DMX_HPSS_MASKS M_h and M_p, with DMX_HPSS_MEDIANS H and P. Columns from `bins` on are not
+     * written. `residual` of the spec is not used. Asynchronous on `stream`. */
+    int dmx_hpss_filter_device(int device, const void *d_spec, int planes, int frames, int bins, int row, const dmx_hpss_spec *spec,
+                               int what, float *d_a, float *d_b, void *stream);
+
     /* ---- Log-mel features of the stems (csrc/logmel.hip; DESIGN.md section 2.20, restated in tests/logmel_spec.py; the front
      * end of Whisper / WhisperX and of librosa.feature.melspectrogram + power_to_db). P planes of N fp32 samples at `sr`:
      * centred frames (reflect padding of n_fft / 2, periodic Hann window), S[f] = |sum_n w[n] x[n] e^{-2 pi i f n / n_fft}|^2 for
